@@ -7,12 +7,17 @@ pass of the serving hot path over the batch: prior map -> input transform -> MLP
 output transform -> Gaussian log-likelihood / T + ln prior  (== 4096 x util.Log_prob.__call__
 of the reference).  Inputs are resident in HBM before the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 For N > 1 launch with torch.distributed.run (one rank per GPU); walkers shard across ranks
 with no data-path collective (weak scaling: 4096 walkers per GPU).  Rank 0 prints ONE JSON line.
 
-Besides the contract's fields the line carries: ``roofline`` (dominant kernel, HIP-event timing, p10/p50/p90 of
+A plain run sets up, warms up, times the K steps and prints the headline line (``metric``, ``value``, ``unit``,
+``higher_is_better``, ``dtype``, ``ms_per_step``, the configuration); nothing else runs.  ``--dump-outputs DIR`` writes
+what the last timed step computed (the 4096 log-probabilities per rank, float32) as ``DIR/log_prob.npy``
+(``DIR/log_prob_rank<r>.npy`` for N > 1); the inputs are seeded, so two builds compare output for output.
+
+With ``--full`` the line also carries: ``roofline`` (dominant kernel, HIP-event timing, p10/p50/p90 of
 single launches, PMC traffic from profiles/), ``cpu_baseline`` (N = 1), ``mcmc`` (ensemble iterations/s of the
 bare sampler loop), ``strong_scaling`` (N > 1: the same 4096 walkers split over the ranks), ``training``
 (optimiser steps of ChtoModelv2(26,457), batch 500 per GPU, gradient all-reduce for N > 1, with its own roofline
@@ -1077,7 +1082,13 @@ def main():
                     "rate_vs_walkers, hmc, chto_v2, dense_1000): one JSON object with just those, no headline")
     ap.add_argument("--launch-check", action="store_true", help="ranks only rendezvous (linna_amd.dist.init), sum their ranks over "
                     "the process group and rank 0 prints that: what the CPU test of the self-launcher runs (no GPU needed)")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline: roofline, strong scaling (N > 1), "
+                    "training, ensemble samplers and drivers, the secondary workloads, the CPU baseline, summary")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write the log-probabilities of the last timed step "
+                    "as DIR/log_prob.npy (float32; DIR/log_prob_rank<r>.npy per rank for N > 1)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world == 1 and args.gpus > 1:
@@ -1188,13 +1199,15 @@ def main():
         elapsed = float(tmax.item())
 
     _stage("headline timed")
+    if args.dump_outputs:                   # before anything else runs: what the last timed step left in `out`
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        name = "log_prob.npy" if world == 1 else "log_prob_rank%d.npy" % rank
+        np.save(os.path.join(args.dump_outputs, name), out.cpu().numpy().astype(np.float32))
     # sanity: the timed path produced finite numbers
     assert torch.isfinite(out).all(), "non-finite log-probabilities in the timed path"
 
     def headline_line():
-        ms_kernel, flop_launch, ms_q = time_dominant_kernel(lp, z, out, max(500, args.steps))
-        achieved = flop_launch / (ms_kernel * 1e-3) / 1e12
-        return {
+        line = {
             "metric": "emulator log-likelihood evals/sec",
             "value": world * NWALKERS * args.steps / elapsed,
             "unit": "evals/s",
@@ -1207,17 +1220,28 @@ def main():
                        "nwalkers_per_gpu": NWALKERS, "flop_per_eval": 2 * MACS_PER_EVAL + 3 * NOUT,
                        "launch": "hipGraph replay" if graph is not None else "direct launches",
                        "parallelism": "walkers sharded, %d rank(s), no data-path collective" % world},
-            "roofline": {"bound": "mfma", "achieved": achieved, "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": achieved / FP32_MFMA_PEAK_TFLOPS, "traffic": pmc_traffic(),
-                         "traffic_source": "profiles/%s (rocprofv3 --pmc passes of this kernel, not measured in this run)" % TRAFFIC_FILE,
-                         "kernel": "net_stream_kernel<6, 0, false, 0, 16> (whole network per launch: 16 walkers/workgroup, activations in LDS, fragment-order weight stream loaded straight into the MFMA operand registers, v_mfma_f32_16x16x4_f32)",
-                         "avg_launch_ms": ms_kernel, "launch_ms_p10_p50_p90": ms_q, "flop_per_launch": flop_launch},
-            "step_tflops": world * NWALKERS * args.steps * (2 * MACS_PER_EVAL) / elapsed / 1e12,
         }
+        if args.full:                       # runs of its own: HIP events around the dominant kernel
+            ms_kernel, flop_launch, ms_q = time_dominant_kernel(lp, z, out, max(500, args.steps))
+            achieved = flop_launch / (ms_kernel * 1e-3) / 1e12
+            line["roofline"] = {"bound": "mfma", "achieved": achieved, "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                "frac": achieved / FP32_MFMA_PEAK_TFLOPS, "traffic": pmc_traffic(),
+                                "traffic_source": "profiles/%s (rocprofv3 --pmc passes of this kernel, not measured in this run)" % TRAFFIC_FILE,
+                                "kernel": "net_stream_kernel<6, 0, false, 0, 16> (whole network per launch: 16 walkers/workgroup, activations in LDS, fragment-order weight stream loaded straight into the MFMA operand registers, v_mfma_f32_16x16x4_f32)",
+                                "avg_launch_ms": ms_kernel, "launch_ms_p10_p50_p90": ms_q, "flop_per_launch": flop_launch}
+        line["step_tflops"] = world * NWALKERS * args.steps * (2 * MACS_PER_EVAL) / elapsed / 1e12
+        return line
+
+    res = headline_line() if rank == 0 else None
+    if not args.full:                       # a plain run: the headline line and nothing else
+        if rank == 0:
+            print(json.dumps(res), flush=True)
+        if world > 1:
+            _shutdown(rank)
+        return
 
     # N > 1: from here on the sections call collectives; the headline line is put together first and a watchdog holds it
     dog = None
-    res = headline_line() if rank == 0 else None
     if world > 1:
         global _DOG
         dog = _DOG = _Watchdog(float(os.environ.get("LINNA_BENCH_WATCHDOG_S", "420")), rank)
@@ -1379,15 +1403,20 @@ def main():
         else:
             dog.emit(res)                            # (cancels the watchdog's own print; the shutdown below is still covered)
     if world > 1:
-        from linna_amd import dist as ldist
         _at("shutdown")
-        if rank == 0:
-            # the line is out: a stuck teardown must not hold the launcher -- but it is a hang, and the exit code says so
-            threading_guard = __import__("threading").Timer(float(os.environ.get("LINNA_BENCH_TEARDOWN_S", "120")),
-                                                            lambda: os._exit(_Watchdog.EXIT_HANG))
-            threading_guard.daemon = True
-            threading_guard.start()
-        ldist.shutdown()
+        _shutdown(rank)
+
+
+def _shutdown(rank):
+    """N > 1, after rank 0's line: every rank leaves the process group."""
+    from linna_amd import dist as ldist
+    if rank == 0:
+        # the line is out: a stuck teardown must not hold the launcher -- but it is a hang, and the exit code says so
+        threading_guard = __import__("threading").Timer(float(os.environ.get("LINNA_BENCH_TEARDOWN_S", "120")),
+                                                        lambda: os._exit(_Watchdog.EXIT_HANG))
+        threading_guard.daemon = True
+        threading_guard.start()
+    ldist.shutdown()
 
 
 _DOG = None

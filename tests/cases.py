@@ -73,3 +73,16 @@ def training_problem(name):
     Y[1, 2, nout - 1] = 1e-30
     return dict(kind=kind, nin=nin, nout=nout, kw=kw, full=full, weights=synth.weights(kind, nin, nout, seed, **kw),
                 data=data, cov=cov, sigma=sigma, X_mean=X_mean, X_std=X_std, y_mean=y_mean, y_std=y_std, X=X, Y=Y)
+
+
+def transform_objects():
+    """The five data-vector transforms whose pickles the reference's own unpickler must read (tests/test_host_api.py;
+    what it read and computed is stored by make_golden.py as transform_pickles.npz)."""
+    import torch
+    from linna_amd import util
+    t = lambda a: torch.as_tensor(np.asarray(a, np.float32))
+    return {"X_transform": util.X_transform_class(t(np.arange(4.0)), t(np.full(4, 2.0)), "cpu", [0, 2]),
+            "y_transform": util.Y_transform_class(t(np.zeros(3)), t(np.ones(3)), "cpu"),
+            "y_invtransform": util.Y_invtransform_class(t(np.zeros(3)), t(np.ones(3)), t(np.ones(3)), "cpu"),
+            "y_transform_data": util.Y_transform_data(np.array([1.0, 2.0, 3.0]), "cpu"),
+            "y_invtransform_data": util.Y_invtransform_data(np.array([1.0, 2.0, 3.0]), "cpu")}

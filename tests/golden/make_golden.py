@@ -821,9 +821,38 @@ def gen_cond(out):
     out[c["name"]] = rec
 
 
+# ------------------------------------------------------------------ this package's transform pickles, read by the reference
+def gen_transform_pickles(out):
+    """The pickles of tests/cases.transform_objects() written by THIS package, loaded by the reference's CPU_Unpickler: the
+    class each became, its attributes (tensors as arrays, everything else as repr) and what it computes on fixed inputs."""
+    tests_dir = os.path.dirname(HERE)
+    for p in (tests_dir, os.path.dirname(tests_dir)):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    import cases
+    g = torch.Generator().manual_seed(611)
+    x, y = torch.rand(5, 4, generator=g) + 0.5, torch.rand(5, 3, generator=g)
+    rec = dict(x=x.numpy(), y=y.numpy())
+    with tempfile.TemporaryDirectory() as tmp:
+        for k, o in cases.transform_objects().items():
+            path = os.path.join(tmp, k + ".pkl")
+            o.pickle(path)
+            with open(path, "rb") as f:
+                r = rutil.CPU_Unpickler(f).load()
+            rec[k + "/class"] = np.array("%s.%s" % (type(r).__module__, type(r).__name__))
+            rec[k + "/attrs"] = np.array(sorted(r.__dict__))
+            for a, v in r.__dict__.items():
+                if torch.is_tensor(v):
+                    rec[k + "/tensor/" + a] = v.numpy()
+                else:
+                    rec[k + "/repr/" + a] = np.array(repr(v))
+            rec[k + "/out"] = r(x if k == "X_transform" else y).numpy()
+    out["transform_pickles"] = rec
+
+
 GENERATORS = [("cond", gen_cond), ("host_designs", gen_host_designs), ("importance", gen_importance), ("fixture", gen_fixture), ("serving", gen_serving), ("training", gen_training), ("train_nn", gen_train_nn), ("train_nn_ypos", gen_train_nn_ypos), ("train_nn_usebest", gen_train_nn_usebest),
               ("loader_order", gen_loader_order), ("early_stopping", gen_early_stopping), ("hmc", gen_hmc), ("hmc_move", gen_hmc_move), ("callbacks", gen_callbacks),
-              ("init_parity", gen_init_parity), ("train33", gen_train33)]
+              ("init_parity", gen_init_parity), ("train33", gen_train33), ("transform_pickles", gen_transform_pickles)]
 
 
 def main():

@@ -405,8 +405,8 @@ def _bench2(extra_env, *argv):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         e.pop(k, None)
     e.update(extra_env)
-    return subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "30", "--no-secondary",
-                           "--no-cpu-baseline"] + list(argv), capture_output=True, text=True, env=e, timeout=600)
+    return subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "30", "--full",
+                           "--no-secondary", "--no-cpu-baseline"] + list(argv), capture_output=True, text=True, env=e, timeout=600)
 
 
 def test_two_rank_bench_line_and_its_watchdog():

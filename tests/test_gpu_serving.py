@@ -694,3 +694,34 @@ def test_dense_factor_skips_its_zero_triangle(nout):
             np.testing.assert_array_equal(got[2], got[0], err_msg="engine %d" % rows)
     finally:
         lib.linna_dense_tri(mode0)
+
+
+def test_plain_bench_run_times_the_steps_and_dumps_what_they_computed(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: ONE JSON line with the headline's fields and nothing
+    measured besides it (roofline, training, samplers, CPU baseline: --full), K timed steps behind `ms_per_step`, and
+    DIR/log_prob.npy = the 4096 log-probabilities of the last timed step -- those of the same seeded problem evaluated here."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3",
+                        "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"] == "emulator log-likelihood evals/sec" and d["unit"] == "evals/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["steps"] == 7 and d["warmup"] == 3 and d["n_gpus"] == 1
+    assert abs(d["value"] - 4096 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    assert not {"roofline", "training", "mcmc", "cpu_baseline", "summary"} & set(d)
+    assert os.listdir(str(tmp_path / "out")) == ["log_prob.npy"]
+    got = np.load(str(tmp_path / "out" / "log_prob.npy"))
+    assert got.dtype == np.float32 and got.shape == (4096,) and np.all(np.isfinite(got))
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    import bench
+    lp, _, _ = bench.build_problem(torch.device("cuda", 0))
+    z = torch.as_tensor(np.random.RandomState(100).standard_normal((bench.NWALKERS, bench.NIN)).astype(np.float32), device="cuda")
+    out = torch.empty(bench.NWALKERS, dtype=torch.float32, device="cuda")
+    lp.evaluate(z, out=out)
+    np.testing.assert_allclose(got, out.cpu().numpy(), rtol=1e-6, atol=0)

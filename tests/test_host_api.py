@@ -364,16 +364,26 @@ def _npy(tmp_path, v):
 
 def test_transform_pickles_name_the_references_classes(tmp_path):
     """``X_transform.pkl`` & co. written here name ``linna.util.<Class>`` (identical attribute sets), so a run directory
-    continues under the reference without this package; this package's own reader maps the name back.  Where the
-    reference tree is present (the build container), its own unpickler loads the files as ITS classes and they transform
-    like ours."""
+    continues under the reference without this package; this package's own reader maps the name back.  The reference's
+    side is stored (tests/golden/make_golden.py: transform_pickles.npz): its own unpickler loaded these files as ITS
+    classes, with the attributes recorded there, and they transformed fixed inputs to the recorded outputs -- which the
+    objects here reproduce bit for bit."""
     from linna_amd import util
-    t = lambda a: torch.as_tensor(np.asarray(a, np.float32))
-    objs = {"X_transform": util.X_transform_class(t(np.arange(4.0)), t(np.full(4, 2.0)), "cpu", [0, 2]),
-            "y_transform": util.Y_transform_class(t(np.zeros(3)), t(np.ones(3)), "cpu"),
-            "y_invtransform": util.Y_invtransform_class(t(np.zeros(3)), t(np.ones(3)), t(np.ones(3)), "cpu"),
-            "y_transform_data": util.Y_transform_data(np.array([1.0, 2.0, 3.0]), "cpu"),
-            "y_invtransform_data": util.Y_invtransform_data(np.array([1.0, 2.0, 3.0]), "cpu")}
+    g = cases.golden("transform_pickles")
+    objs = cases.transform_objects()
+    x, y = torch.from_numpy(g["x"]), torch.from_numpy(g["y"])
+
+    class _Recorded(object):
+        pass
+
+    class _StateReader(util.CPU_Unpickler):
+        """The stream as the reference's unpickler sees it: the class it names, the attributes it sets."""
+        def find_class(self, module, name):
+            if module == "linna.util":
+                self.named = module + "." + name
+                return _Recorded
+            return util.CPU_Unpickler.find_class(self, module, name)
+
     for k, o in objs.items():
         path = os.path.join(str(tmp_path), k + ".pkl")
         o.pickle(path)
@@ -382,28 +392,19 @@ def test_transform_pickles_name_the_references_classes(tmp_path):
         with open(path, "rb") as f:
             back = util.CPU_Unpickler(f).load()
         assert type(back) is type(o)
-    if not os.path.isdir("/root/reference/linna"):
-        pytest.skip("reference tree not present: the reference-side half of this check runs in the build container")
-    # in a process of its own: the reference import installs stand-ins for its absent third-party modules
-    x, y = torch.rand(5, 4) + 0.5, torch.rand(5, 3)
-    torch.save({"x": x, "y": y, "want": {k: o(x if k == "X_transform" else y) for k, o in objs.items()}},
-               os.path.join(str(tmp_path), "io.pt"))
-    code = (
-        "import sys, os, torch\n"
-        "sys.path.insert(0, %r)\n"
-        "import _ref_import\n"
-        "_, rutil, _, _ = _ref_import.import_reference()\n"
-        "d = %r\n"
-        "io = torch.load(os.path.join(d, 'io.pt'))\n"
-        "for k, want in io['want'].items():\n"
-        "    with open(os.path.join(d, k + '.pkl'), 'rb') as f:\n"
-        "        r = rutil.CPU_Unpickler(f).load()\n"
-        "    assert type(r).__module__ == 'linna.util', type(r)\n"
-        "    assert torch.equal(r(io['x'] if k == 'X_transform' else io['y']), want), k\n"
-        "print('REFERENCE_READS_OK')\n") % (cases.GOLDEN, str(tmp_path))
-    import subprocess
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert "REFERENCE_READS_OK" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
+        with open(path, "rb") as f:
+            rd = _StateReader(f)
+            state = rd.load().__dict__
+        assert rd.named == str(g[k + "/class"]), k
+        assert sorted(state) == list(g[k + "/attrs"]), k
+        for a, v in state.items():
+            if torch.is_tensor(v):
+                want = g[k + "/tensor/" + a]
+                assert v.dtype == torch.from_numpy(want).dtype and v.device.type == "cpu", (k, a)
+                np.testing.assert_array_equal(v.numpy(), want, err_msg="%s.%s" % (k, a))
+            else:
+                assert repr(v) == str(g[k + "/repr/" + a]), (k, a)
+        np.testing.assert_array_equal(o(x if k == "X_transform" else y).numpy(), g[k + "/out"], err_msg=k)
 
 
 def test_checkpoint_written_in_reference_layout(tmp_path):

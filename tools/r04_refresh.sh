@@ -3,7 +3,7 @@
 # counters.  usage: tools/r04_refresh.sh [hmc_v2] [chto_v2]
 set -e
 root=$(pwd); out=$root/gpurun_out/prof_r04; mkdir -p $out
-python bench.py > $out/bench.json 2> $out/bench.err || { tail -5 $out/bench.err; exit 1; }
+python bench.py --full > $out/bench.json 2> $out/bench.err || { tail -5 $out/bench.err; exit 1; }
 export TMPDIR=/tmp
 PMC="SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F32"
 for w in "$@"; do
