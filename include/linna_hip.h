@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define LINNA_ABI_VERSION 11   /* 11: every descriptor struct a caller fills (linna_gemm_t, linna_layer_t, linna_logprob_desc_t, linna_loss_desc_t) starts with `uint32_t struct_size` = its sizeof in the caller's header, checked by the entries that take it -- a binding built against another layout is refused instead of read at wrong offsets; linna_slice_init / linna_slice_half_step(maxsteps): zeus' stepping-out budget; the shrinking test is zeus' `Z0 < lnP`; 10: + linna_slice_fusion, linna_slice_half_step(expect_rows); 9: + linna_stretch_run, linna_chain_append_t, linna_acorr_*, linna_chain_meanstd, linna_val_metrics, linna_loss_desc_t::ylog; 8: + the exception barrier (LINNA_ERR_INTERNAL, linna_debug_raise) and linna_logprob_desc_t GREW by one pointer (Sfac, appended: a binding compiled against the v7 struct must be rebuilt -- linna_logprob_create copies the struct at the new size); 4: + linna_comm_* (RCCL); 5: + linna_net_prepare, linna_net_forward_loss; 6: + linna_net_adamw_step, linna_net_train_step, linna_net_train_step_update; 7: + linna_engine_rows, linna_slice_half_step, linna_program_describe, linna_net_train_launches, linna_logprob_grad_leapfrog, linna_hmc_start */
+#define LINNA_ABI_VERSION 12   /* 12: + linna_logprob_set_precision, linna_logprob_precision (the opt-in bf16 serving engine; linna_logprob_desc_t unchanged); 11: every descriptor struct a caller fills (linna_gemm_t, linna_layer_t, linna_logprob_desc_t, linna_loss_desc_t) starts with `uint32_t struct_size` = its sizeof in the caller's header, checked by the entries that take it -- a binding built against another layout is refused instead of read at wrong offsets; linna_slice_init / linna_slice_half_step(maxsteps): zeus' stepping-out budget; the shrinking test is zeus' `Z0 < lnP`; 10: + linna_slice_fusion, linna_slice_half_step(expect_rows); 9: + linna_stretch_run, linna_chain_append_t, linna_acorr_*, linna_chain_meanstd, linna_val_metrics, linna_loss_desc_t::ylog; 8: + the exception barrier (LINNA_ERR_INTERNAL, linna_debug_raise) and linna_logprob_desc_t GREW by one pointer (Sfac, appended: a binding compiled against the v7 struct must be rebuilt -- linna_logprob_create copies the struct at the new size); 4: + linna_comm_* (RCCL); 5: + linna_net_prepare, linna_net_forward_loss; 6: + linna_net_adamw_step, linna_net_train_step, linna_net_train_step_update; 7: + linna_engine_rows, linna_slice_half_step, linna_program_describe, linna_net_train_launches, linna_logprob_grad_leapfrog, linna_hmc_start */
 
 typedef struct linna_ctx linna_ctx_t;
 typedef struct linna_net linna_net_t;
@@ -275,6 +275,22 @@ int linna_logprob_destroy(linna_logprob_t* lp);
  * afterwards -- the reference has no counterpart because `model.load_state_dict`
  * (predictor_gpu.py:439-445) rebinds the tensors the forward pass reads. */
 int linna_weights_changed(linna_ctx_t* ctx);
+/* Emulator precision of a log-probability object.  LINNA_PRECISION_FP32 (default): exact fp32 arithmetic, the parity path.
+ * LINNA_PRECISION_BF16 (opt-in, serving only): the whole-network kernel streams the weights as bf16 (rounded to nearest-even,
+ * a residual block's 0.1 folded in first) and rounds the activations to bf16 where the matrix cores read them; the
+ * network input enters as bf16(x) + bf16(x - bf16(x)), and every epilogue, the output map, the log-likelihood and the prior
+ * map stay fp32.  Served in bf16: linna_logprob_eval, linna_logprob_eval_if, linna_stretch_half_step, linna_stretch_run;
+ * linna_logprob_eval_slice_points and linna_slice_half_step return LINNA_ERR_UNSUPPORTED (callers fall back to
+ * linna_slice_points + linna_logprob_eval_if), as do linna_logprob_grad and linna_logprob_grad_leapfrog -- a bf16 object
+ * never computes silently in fp32.  Setting bf16 allocates the bf16 weight streams (call it outside graph capture); they are
+ * laid out on first use and follow the weights like the fp32 copy (linna_adamw_step, linna_graph_launch,
+ * linna_weights_changed).  LINNA_ERR_UNSUPPORTED when the object cannot be served in bf16: a dense inverse covariance, a
+ * network outside the whole-network kernel (wider than 1024, more than 256 inputs) or one whose first op is not a linear
+ * layer.  LINNA_ERR_INVALID for a NULL handle or an unknown code (no GPU needed). */
+#define LINNA_PRECISION_FP32 0
+#define LINNA_PRECISION_BF16 1
+int linna_logprob_set_precision(linna_logprob_t* lp, int precision);
+int linna_logprob_precision(const linna_logprob_t* lp, int* out);
 /* Rows per workgroup of the whole-network kernel: 0 (default) = chosen per launch from the batch size -- the fewest
  * of 4 / 8 / 16 that still fit the batch into one workgroup per CU; 4, 8 or 16 = that engine for every launch of the
  * process (tests and measurements; results differ between engines in the last bits: another summation order over k).

@@ -11,7 +11,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LINNA_LIB_PATH") or os.path.join(_HERE, "liblinna_hip.so")   # (LINNA_LIB_PATH: a diagnostic build, tools/ns_stamps.py)
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 c_float_p = C.c_void_p   # device pointers travel as void*
 c_int_p = C.c_void_p
@@ -124,6 +124,8 @@ _SIGNATURES = {
     "linna_logprob_create": (_I, [_V, _V, C.POINTER(LogprobDesc), _PV]),
     "linna_logprob_destroy": (_I, [_V]),
     "linna_weights_changed": (_I, [_V]),
+    "linna_logprob_set_precision": (_I, [_V, _I]),
+    "linna_logprob_precision": (_I, [_V, _V]),
     "linna_engine_rows": (_I, [_I]),
     "linna_dense_tri": (_I, [_I]),
     "linna_slice_fusion": (_I, [_I]),
@@ -201,7 +203,9 @@ def load():
     return lib
 
 
-ERR_UNSUPPORTED = -3     # LINNA_ERR_UNSUPPORTED (include/linna_hip.h)
+ERR_INVALID = -1         # LINNA_ERR_INVALID (include/linna_hip.h)
+ERR_UNSUPPORTED = -3     # LINNA_ERR_UNSUPPORTED
+PRECISION = {"fp32": 0, "bf16": 1}   # LINNA_PRECISION_FP32 / LINNA_PRECISION_BF16 (linna_logprob_set_precision)
 ERR_INTERNAL = -4        # LINNA_ERR_INTERNAL: a C++ exception caught at the C boundary
 
 

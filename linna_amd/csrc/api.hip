@@ -919,6 +919,9 @@ struct linna_logprob {
     bool dense_fused = false;                // the streams end in the dense inverse covariance (output map folded in)
     int dense_tri = 2;                       // NsDense::tri, fixed when the object is created (the stream's size depends on it)
     NsDense dense() const { return NsDense{d.Sfac ? d.Sfac : d.S, d.lds, d.outmap.cscale, d.outmap.cshift, d.Sfac ? 1 : 0, dense_tri}; }
+    int precision = LINNA_PRECISION_FP32;    // linna_logprob_set_precision
+    StreamCopy packed_bf;                    // the bf16 weight streams (allocated when bf16 is first set, laid out lazily)
+    bool bf16() const { return precision == LINNA_PRECISION_BF16; }
 };
 
 struct LpLayout { size_t x0, fwd, d, part, dh, bwd, dx, total; int slots; };
@@ -951,7 +954,7 @@ static int stream_copy_refresh(StreamCopy& sc, const linna_net* n, int rows, voi
     const unsigned long long epoch = g_weights_epoch.load();
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(S(stream), &cap);
-    const std::vector<linna_layer_t>& LL = prog == 0 ? n->Lfull : n->L;     // (the forward programs carry the input skip)
+    const std::vector<linna_layer_t>& LL = prog == 0 || prog == NS_PROG_BF16_CODE ? n->Lfull : n->L;     // (the forward programs carry the input skip)
     if (cap != hipStreamCaptureStatusNone) {
         // a captured launch carries its own re-layout, so that every replay sees the weights of that
         // moment; the copy is not valid for direct launches until they redo it
@@ -967,6 +970,7 @@ static int stream_copy_refresh(StreamCopy& sc, const linna_net* n, int rows, voi
 // The copy the engine for `B` rows reads, re-laid if the weights moved since it was made; *rows: that engine.
 static int lp_refresh_stream(linna_logprob* lp, int B, void* stream, const float** packed, int* rows) {
     *rows = net_stream_rows(B);
+    if (lp->bf16()) return stream_copy_refresh(lp->packed_bf, lp->net, *rows, stream, packed, NS_PROG_BF16_CODE, nullptr, 1);
     const NsDense dn = lp->dense();
     return stream_copy_refresh(lp->packed, lp->net, *rows, stream, packed, 0, lp->dense_fused ? &dn : nullptr, 1);   // serve: SIDE segments on the 16-row engine
 }
@@ -976,6 +980,19 @@ static int lp_forward(linna_logprob* lp, const float* Z, int ldz, int B, float* 
     const linna_logprob_desc_t& d = lp->d;
     const int ldx = ld4(d.nin), ldd = ld4(d.nout);
     const linna_net* n = lp->net;
+    if (lp->bf16()) {
+        // bf16 runs the whole-network kernel or nothing: never silently fp32
+        if (keep_activations || !fused_enabled() || !lp->packed_bf.ready() || !d.w || (d.outmap.cexp && (!d.outmap.cpost || !d.outmap.cshift2))) {
+            set_error("logprob: this bf16 log-probability cannot run the whole-network kernel here (LINNA_DISABLE_FUSED, or no diagonal likelihood)");
+            return LINNA_ERR_UNSUPPORTED;
+        }
+        const float* packed = nullptr; int rows = 16;
+        TRY(lp_refresh_stream(lp, B, stream, &packed, &rows));
+        return launch_net_stream(n->Lfull.data(), (int)n->Lfull.size(), n->in_size, packed, Z, ldz, B, d.nin, d.is_flat, d.a1, d.a2,
+                                 d.log10_flag, d.xmean, d.xstd, d.outmap.cscale, d.outmap.cshift, d.w, d.temperature, lnP, nullptr, 0,
+                                 TH, ldt, nullptr, nullptr, gate, rows, nullptr, S(stream), d.outmap.cexp ? d.outmap.cpost : nullptr,
+                                 d.outmap.cexp ? d.outmap.cshift2 : nullptr, 1);
+    }
     if (!keep_activations && fused_enabled() && lp->packed.ready() && (!d.outmap.cexp || (d.outmap.cpost && d.outmap.cshift2 && !lp->dense_fused))) {
         // whole-network kernel (net_stream.hip): prior map -> every layer -> output transform -> diagonal
         // log-likelihood in ONE launch, weights streamed from the fragment-order copy
@@ -1047,11 +1064,39 @@ int linna_logprob_create(linna_ctx_t* ctx, linna_net_t* net, const linna_logprob
     return LINNA_OK;
 } LINNA_CATCH_INT
 int linna_logprob_destroy(linna_logprob_t* lp) try {
-    if (lp) { lp->packed.release(); lp->packed_g2.release(); }
+    if (lp) { lp->packed.release(); lp->packed_g2.release(); lp->packed_bf.release(); }
     delete lp;
     return LINNA_OK;
 } LINNA_CATCH_INT
 int linna_weights_changed(linna_ctx_t*) try { g_weights_epoch.fetch_add(1); return LINNA_OK; } LINNA_CATCH_INT
+// The opt-in bf16 serving engine.  Checks first (no GPU needed), then the bf16 streams are allocated here -- outside any
+// graph capture -- and laid out by the first launch that reads them, like the fp32 copy (weight epoch).
+int linna_logprob_set_precision(linna_logprob_t* lp, int precision) try {
+    if (!lp) { set_error("logprob_set_precision: null handle"); return LINNA_ERR_INVALID; }
+    if (precision != LINNA_PRECISION_FP32 && precision != LINNA_PRECISION_BF16) {
+        set_error("logprob_set_precision: unknown precision %d (LINNA_PRECISION_FP32 0, LINNA_PRECISION_BF16 1)", precision);
+        return LINNA_ERR_INVALID;
+    }
+    if (precision == LINNA_PRECISION_FP32) { lp->precision = precision; return LINNA_OK; }
+    const linna_net* n = lp->net;
+    if (!lp->d.w) { set_error("logprob_set_precision: bf16 needs a diagonal likelihood (a dense covariance is served in fp32 only)"); return LINNA_ERR_UNSUPPORTED; }
+    const char* why = nullptr;
+    if (!net_stream_bf16_eligible(n->Lfull.data(), (int)n->Lfull.size(), n->in_size, &why)) {
+        set_error("logprob_set_precision: no bf16 engine for this network: %s", why ? why : "not eligible");
+        return LINNA_ERR_UNSUPPORTED;
+    }
+    if (!lp->packed_bf.ready() && lp->packed_bf.alloc(net_stream_bf16_packed_floats(n->Lfull.data(), (int)n->Lfull.size(), n->in_size)) != LINNA_OK) {
+        set_error("logprob_set_precision: hipMalloc(bf16 weight stream) failed");
+        return LINNA_ERR_HIP;
+    }
+    lp->precision = precision;
+    return LINNA_OK;
+} LINNA_CATCH_INT
+int linna_logprob_precision(const linna_logprob_t* lp, int* out) try {
+    if (!lp || !out) { set_error("logprob_precision: null argument"); return LINNA_ERR_INVALID; }
+    *out = lp->precision;
+    return LINNA_OK;
+} LINNA_CATCH_INT
 int linna_program_describe(const linna_layer_t* layers, int nlayers, int in_size, int rows, int dense_nout, char* buf, size_t n) try {
     if (!layers || nlayers < 1 || !buf || !n) { set_error("program_describe: bad arguments"); return LINNA_ERR_INVALID; }
     CHECK_STRUCT(layers, linna_layer_t, "program_describe");
@@ -1114,6 +1159,10 @@ static int lp_eval_slice_points(linna_logprob_t* lp, const float* coords, int ld
     }
     const linna_logprob_desc_t& d = lp->d;
     if (ndim != d.nin) { set_error("logprob_eval_slice_points: ndim %d, log-probability has %d parameters", ndim, d.nin); return LINNA_ERR_INVALID; }
+    if (lp->bf16()) {
+        set_error("logprob_eval_slice_points: no bf16 slice move");
+        return LINNA_ERR_UNSUPPORTED;          // the caller falls back to linna_slice_points + a bf16 linna_logprob_eval_if
+    }
     if (!fused_enabled() || !lp->packed.ready() || (d.outmap.cexp && (!d.w || !d.outmap.cpost || !d.outmap.cshift2)) ||
         (!d.w && !lp->dense_fused) || d.nin > 64) {
         set_error("logprob_eval_slice_points: this log-probability does not run the whole-network kernel");
@@ -1161,6 +1210,7 @@ int linna_slice_half_step(linna_logprob_t* lp, float* coords, int ldc, int ndim,
     for (int r = 0; r < nshr_rounds; ++r) if (nt_sched[r] < 1) { set_error("slice_half_step: nt_sched[%d] = %d", r, nt_sched[r]); return LINNA_ERR_INVALID; }
     const linna_logprob_desc_t& d = lp->d;
     if (ndim != d.nin) { set_error("slice_half_step: ndim %d, log-probability has %d parameters", ndim, d.nin); return LINNA_ERR_INVALID; }
+    if (lp->bf16()) { set_error("slice_half_step: no bf16 slice move"); return LINNA_ERR_UNSUPPORTED; }
     if (!fused_enabled() || !lp->packed.ready() || (d.outmap.cexp && (!d.w || !d.outmap.cpost || !d.outmap.cshift2)) ||
         (!d.w && !lp->dense_fused) || d.nin > 64) {
         set_error("slice_half_step: this log-probability does not run the whole-network kernel");
@@ -1222,8 +1272,8 @@ int linna_stretch_half_step(linna_logprob_t* lp, float* coords, int ldc, int ndi
     }
     const linna_logprob_desc_t& d = lp->d;
     if (ndim != d.nin) { set_error("stretch_half_step: ndim %d, log-probability has %d parameters", ndim, d.nin); return LINNA_ERR_INVALID; }
-    if (!fused_enabled() || !lp->packed.ready() || (d.outmap.cexp && (!d.w || !d.outmap.cpost || !d.outmap.cshift2)) ||
-        (!d.w && !lp->dense_fused) || d.nin > 64) {
+    if (!fused_enabled() || !(lp->bf16() ? lp->packed_bf.ready() : lp->packed.ready()) ||
+        (d.outmap.cexp && (!d.w || !d.outmap.cpost || !d.outmap.cshift2)) || (!d.w && !lp->dense_fused) || d.nin > 64) {
         set_error("stretch_half_step: this log-probability does not run the whole-network kernel");
         return LINNA_ERR_UNSUPPORTED;          // the caller falls back to propose / eval / accept
     }
@@ -1237,7 +1287,7 @@ int linna_stretch_half_step(linna_logprob_t* lp, float* coords, int ldc, int ndi
                              d.a2, d.log10_flag, d.xmean, d.xstd, df ? nullptr : d.outmap.cscale, df ? nullptr : d.outmap.cshift,
                              df ? nullptr : d.w, d.temperature, nullptr, nullptr, 0, nullptr, 0, &mv, nullptr, nullptr, rows,
                              df ? &dn : nullptr, S(stream), d.outmap.cexp ? d.outmap.cpost : nullptr,
-                             d.outmap.cexp ? d.outmap.cshift2 : nullptr);
+                             d.outmap.cexp ? d.outmap.cshift2 : nullptr, lp->bf16() ? 1 : 0);
 } LINNA_CATCH_INT
 
 
@@ -1250,8 +1300,8 @@ int linna_stretch_run(linna_logprob_t* lp, float* coords, int ldc, int ndim, flo
     }
     const linna_logprob_desc_t& d = lp->d;
     if (ndim != d.nin) { set_error("stretch_run: ndim %d, log-probability has %d parameters", ndim, d.nin); return LINNA_ERR_INVALID; }
-    if (!fused_enabled() || !lp->packed.ready() || (d.outmap.cexp && (!d.w || !d.outmap.cpost || !d.outmap.cshift2)) ||
-        (!d.w && !lp->dense_fused) || d.nin > 64) {
+    if (!fused_enabled() || !(lp->bf16() ? lp->packed_bf.ready() : lp->packed.ready()) ||
+        (d.outmap.cexp && (!d.w || !d.outmap.cpost || !d.outmap.cshift2)) || (!d.w && !lp->dense_fused) || d.nin > 64) {
         set_error("stretch_run: this log-probability does not run the whole-network kernel");
         return LINNA_ERR_UNSUPPORTED;          // the caller loops over linna_stretch_half_step / the three-launch form
     }
@@ -1270,7 +1320,7 @@ int linna_stretch_run(linna_logprob_t* lp, float* coords, int ldc, int ndim, flo
                                   d.a2, d.log10_flag, d.xmean, d.xstd, df ? nullptr : d.outmap.cscale, df ? nullptr : d.outmap.cshift,
                                   df ? nullptr : d.w, d.temperature, nullptr, nullptr, 0, nullptr, 0, &mv, nullptr, nullptr, rows,
                                   df ? &dn : nullptr, S(stream), d.outmap.cexp ? d.outmap.cpost : nullptr,
-                                  d.outmap.cexp ? d.outmap.cshift2 : nullptr));
+                                  d.outmap.cexp ? d.outmap.cshift2 : nullptr, lp->bf16() ? 1 : 0));
         }
     }
     return LINNA_OK;
@@ -1322,6 +1372,10 @@ int linna_chain_meanstd(linna_ctx_t*, const float* CT, int ndim, int nwp, int nw
 static int logprob_grad_impl(linna_logprob_t* lp, const float* Z, int ldz, int B, void* ws, float* lnP, float* G, int ldg,
                              const NsGrad* leap, void* stream) {
     if (!lp || !Z || !ws || !lnP || !G || B < 1) { set_error("logprob_grad: bad arguments"); return LINNA_ERR_INVALID; }
+    if (lp->bf16()) {
+        set_error("logprob_grad: this log-probability is set to bf16, which serves lnP only (no bf16 gradient); set it back to fp32");
+        return LINNA_ERR_UNSUPPORTED;
+    }
     const linna_logprob_desc_t& d = lp->d;
     if (d.outmap.cexp) { set_error("logprob_grad: ypositive (exp) output map has no gradient path"); return LINNA_ERR_UNSUPPORTED; }
     if (!d.gscale || (!d.w && !d.Ssym)) { set_error("logprob_grad: descriptor lacks gscale / Ssym"); return LINNA_ERR_INVALID; }

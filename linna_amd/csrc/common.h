@@ -494,7 +494,12 @@ int launch_net_stream(const linna_layer_t* layers, int nl, int in_size, const fl
                       int nin, const int* is_flat, const float* a1, const float* a2, const int* lg, const float* xmean,
                       const float* xstd, const float* cscale, const float* cshift, const float* w, float T, float* lnP,
                       float* D, int ldd, float* TH, int ldt, const NsMove* mv, const NsGrad* gr, const int* gate, int rows,
-                      const NsDense* dn, hipStream_t s, const float* cpost = nullptr, const float* cshift2 = nullptr);
+                      const NsDense* dn, hipStream_t s, const float* cpost = nullptr, const float* cshift2 = nullptr, int bf = 0);
+// the opt-in bf16 serving engine (linna_logprob_set_precision): its program (pack / launch with prog NS_PROG_BF16_CODE and
+// bf = 1) exists for the networks below; *why: the reason when it does not
+constexpr int NS_PROG_BF16_CODE = 5;
+bool net_stream_bf16_eligible(const linna_layer_t* layers, int nl, int in_size, const char** why);
+size_t net_stream_bf16_packed_floats(const linna_layer_t* layers, int nl, int in_size);
 
 // autocorr.hip: convergence statistics of a walker chain (running lagged products, emcee's estimator, checkmeanstd's moments)
 int launch_chain_append_t(const float* block, int ldb, int nsteps, int nw, int ndim, int wstride, float* CT, int nwp,

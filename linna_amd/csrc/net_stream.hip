@@ -61,6 +61,9 @@
 
 namespace linna {
 
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));   // B (and A) operand of v_mfma_f32_16x16x32_bf16
+typedef short s16x4 __attribute__((ext_vector_type(4)));     // ... of v_mfma_f32_4x4x4_16b_bf16 (the builtin takes the bits)
+
 constexpr int NS_ROWS = 16;                // rows per workgroup of the large-batch engine (and the LDS layout bound)
 constexpr int NS_NW = 8;                 // waves per workgroup
 constexpr int NS_NT = 4;                 // 16-column tiles per wave and step
@@ -174,6 +177,7 @@ struct NsPackArgs {
     int run_seg[NS_MAXRUN], run_pass[NS_MAXRUN], run_first[NS_MAXRUN + 1];
     int nseg, nrun, G, bias_total;
     int small;                                     // layout of the 4x4x1 engines: lane = column, load t = k chunk
+    int bf;                                        // bf16 stream (NsProgram::bf): 32 k per step, eight bf16 per 16-byte vector
     float* out;                                    // weights, then biases
 };
 // stream[w][g][t][lane][e], run r = (segment, pass), s = g - first[r], li = lane & 15, kq = lane >> 4:
@@ -181,9 +185,41 @@ struct NsPackArgs {
 //   SPLIT  n = 64 (w % ncg) + 16 t + li,     k = 16 ((w / ncg) steps + s) + 4 kq + e
 // value = [Wa | alpha Wb](n, k), zero outside.  Small-batch engines (p.small): the same 64 columns x 16 k per
 // (w, g) with lane = column and load t = k chunk:  n = ... + lane,  k = ... + 4 t + e.
+// bf16 stream (p.bf): a step is 32 k, each 16-byte vector eight bf16 -- 16 k in the formulas above becomes 32 and
+// 4 kq (4 t) becomes 8 kq (8 t), e < 8.  The fp32 value (alpha Wb with alpha folded, rscale applied) is rounded to
+// nearest-even by a plain cast (v_cvt_pk_bf16_f32: a NaN stays a NaN).
+__device__ __forceinline__ float ns_pack_value(const NsPackSeg& S, int n, int k) {
+    float v = 0.f;
+    if (k < S.Kapad) {
+        if (k < S.Ka) v = !S.Wa ? (k == n ? 1.f : 0.f) : S.transA ? S.Wa[(size_t)k * S.lda + n] : S.Wa[(size_t)n * S.lda + k];
+    } else if (k - S.Kapad < S.Kb) {
+        v = S.alpha * (S.transB ? S.Wb[(size_t)(k - S.Kapad) * S.ldb + n] : S.Wb[(size_t)n * S.ldb + (k - S.Kapad)]);
+    }
+    return S.rscale ? v * S.rscale[n] : v;
+}
+__device__ __forceinline__ void ns_pack_bf16(const NsPackArgs& p, size_t idx) {
+    const int lane = (int)(idx & 63);
+    size_t q = idx >> 6;
+    const int t = (int)(q % NS_NT); q /= NS_NT;
+    const int g = (int)(q % p.G);
+    const int w = (int)(q / p.G);
+    int r = 0;
+    while (r + 1 < p.nrun && g >= p.run_first[r + 1]) ++r;
+    const NsPackSeg& S = p.seg[p.run_seg[r]];
+    const int s = g - p.run_first[r];
+    const int nl = p.small ? lane : 16 * t + (lane & 15), kl = p.small ? 8 * t : 8 * (lane >> 4);
+    int n, k0;
+    if (S.type == NS_WIDE) { n = 512 * p.run_pass[r] + 64 * w + nl; k0 = 32 * s + kl + (p.run_pass[r] ? S.koff2 : 0); }
+    else { n = 64 * (w % S.ncg) + nl; k0 = 32 * ((w / S.ncg) * S.steps + s) + kl; }
+    bf16x8 v;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = (__bf16)(n < S.N ? ns_pack_value(S, n, k0 + e) : 0.f);
+    reinterpret_cast<bf16x8*>(p.out)[idx] = v;
+}
 __global__ void ns_pack_kernel(NsPackArgs p) {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t nw4 = (size_t)NS_NW * p.G * NS_NT * 64;
+    if (idx < nw4 && p.bf) { ns_pack_bf16(p, idx); return; }
     if (idx < nw4) {
         const int lane = (int)(idx & 63);
         size_t q = idx >> 6;
@@ -286,7 +322,17 @@ __device__ __forceinline__ float ns_prior_theta(float z, int flat, float a1, flo
 // output, every residual block's hidden h) are written to global memory from the epilogues with inline-asm
 // stores: the compiler does not see them, so its counted vmcnt waits for the weight stream stay counted
 // (stores only ever make the hardware counter read higher, i.e. the waits conservative).
-template <int R, int MOVE, bool GRAD, int STORE, int ROWS>
+// BF: the opt-in bf16 serving engine (linna_logprob_set_precision; MOVE 0 / 1, no GRAD, no STORE).  The stream holds bf16
+// weights (ns_pack_kernel, p.bf) and one step covers 32 k x 64 columns -- the same 4 KiB per wave and step, so the ring,
+// its four 1-KiB loads and the counted waits keep their shape and a segment takes half the steps.  Activations stay fp32
+// in LDS and are rounded to bf16 (nearest-even) where the A operand is read: two ds_read_b128 per step (8 k per lane).
+// 16 rows: v_mfma_f32_16x16x32_bf16, one per column tile and step (lane group kq owns k 8 kq .. 8 kq + 7 of the step in
+// A and B alike); 8 / 4 rows: v_mfma_f32_4x4x4_16b_bf16 with the CBSZ / ABID broadcast of the fp32 4x4x1 form, block b of
+// the A read holding row set b & 3 and k chunk b >> 2 (8 k), two instructions (halves of the chunk) per (row set, chunk).
+// The network input goes in as x_hi = bf16(x) at column c and x_lo = x - x_hi at column nin + c, and the first layer is
+// packed [W | W] (ns_build_one): the input is not quantised to 8 bits.  Epilogues, the finish and the prior map are the
+// fp32 kernel's.  SIDE segments are off in bf16 (K4 = false; the program builder plans none).
+template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF = false>
 __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_kernel(NsArgs a) {
     constexpr int NT = NS_NT, NW = NS_NW;
     constexpr int RG = 32;                         // threads per walker row in prologue / reduce / finish
@@ -294,7 +340,9 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_kernel(NsArgs a) {
     constexpr int RS = SM ? ROWS / 4 : 1;
     constexpr int NQ = SM ? RS : NT;               // result quads per lane: (row set) or (column tile)
     constexpr int NACC = SM ? 4 * RS : NT;
-    constexpr bool K4 = !SM && (STORE == 0 || (GRAD && STORE == 2));   // 16-row engine, serving and the one-launch gradient: programs may hold SIDE segments
+    static_assert(!BF || (!GRAD && STORE == 0 && MOVE != 2), "bf16: serving and the fused stretch move only");
+    constexpr int AK = BF ? 2 : 1;                 // 16-byte A fragments per lane and step
+    constexpr bool K4 = !SM && !BF && (STORE == 0 || (GRAD && STORE == 2));   // 16-row engine, serving and the one-launch gradient: programs may hold SIDE segments
     // (the one-launch gradient with SIDE segments in its forward half was measured SLOWER: 156.4 against 154.2 us at ChtoModelv2(33,33))
     // TRB: a whole training step's network work in ONE launch (linna_net_train_step): gather + transform + forward with the
     // activations kept + chi^2-ratio loss (STORE == 3) as the forward half, the loss finish as the TURNAROUND (loss rows,
@@ -573,7 +621,14 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_kernel(NsArgs a) {
             if (prow && row0 + pr < a.B && c < a.t_ldxb)
                 asm volatile("global_store_dword %0, %1, off" :: "v"(a.t_xb + (size_t)(row0 + pr) * a.t_ldxb + c), "v"(x) : "memory");
         }
-        if (c < kpad0 && prow) act[pr * LD + c] = x;
+        if constexpr (BF) {                         // x_hi at c, x_lo at nin + c, zeros from 2 nin (ns_build_one: [W | W])
+            if (prow) {
+                if (in) { const float hi = (float)(__bf16)x; act[pr * LD + c] = hi; act[pr * LD + nin + c] = x - hi; }
+                else if (c >= 2 * nin && c < kpad0) act[pr * LD + c] = 0.f;
+            }
+        } else {
+            if (c < kpad0 && prow) act[pr * LD + c] = x;
+        }
     }
 #ifdef NS_STAMPS_FINE
     NS_STAMP();                                    // first 64 input columns transformed and in LDS
@@ -624,7 +679,14 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_kernel(NsArgs a) {
             if (prow && row0 + pr < a.B && c < a.t_ldxb)
                 asm volatile("global_store_dword %0, %1, off" :: "v"(a.t_xb + (size_t)(row0 + pr) * a.t_ldxb + c), "v"(x) : "memory");
         }
-        if (prow) act[pr * LD + c] = x;
+        if constexpr (BF) {
+            if (prow) {
+                if (c < nin) { const float hi = (float)(__bf16)x; act[pr * LD + c] = hi; act[pr * LD + nin + c] = x - hi; }
+                else if (c >= 2 * nin) act[pr * LD + c] = 0.f;
+            }
+        } else {
+            if (prow) act[pr * LD + c] = x;
+        }
     }
     __builtin_amdgcn_sched_barrier(0);
 #ifdef NS_STAMPS_FINE
@@ -648,7 +710,11 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_kernel(NsArgs a) {
     float* const lx0 = lden + 16;                  // [ROWS][64]: the input rows, for a later input-skip segment
     if (a.x0_keep && prow) {
 #pragma unroll
-        for (int i = 0; i < ZPRE; ++i) lx0[pr * 64 + pc0 + i * RG] = (pc0 + i * RG < kpad0) ? act[pr * LD + pc0 + i * RG] : 0.f;
+        for (int i = 0; i < ZPRE; ++i) {
+            const int c = pc0 + i * RG;
+            if constexpr (BF) lx0[pr * 64 + c] = c < nin ? act[pr * LD + c] + act[pr * LD + nin + c] : 0.f;   // x_hi + x_lo = x exactly
+            else lx0[pr * 64 + c] = (c < kpad0) ? act[pr * LD + c] : 0.f;
+        }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                  // raw: __syncthreads() would drain the weight stream
@@ -658,7 +724,7 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_kernel(NsArgs a) {
     // ---- 4. the step loop
     const uint32_t act_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)act;
     f32x4 acc[NACC];
-    f32x4 Aq[2];
+    f32x4 Aq[2][AK];
     // 4x4x1 engine: block b = lane >> 2 of the A read holds row set b & 3 (rows wrap below ROWS: never selected), k chunk b >> 2
     const int sm_arow = (4 * ((lane >> 2) & 3) + (lane & 3)) % ROWS, sm_achunk = lane >> 4;
     int si = 0, pass = 0, P = 0, kleft;
@@ -670,9 +736,10 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_kernel(NsArgs a) {
     int s_gbit = -1, s_mbit = -1;                       // LB: bit column of the signs this segment writes / is gated by
     auto gstore = [&](float* p, float v) { asm volatile("global_store_dword %0, %1, off" :: "v"(p), "v"(v) : "memory"); };
     uint32_t ap;
-    auto a_read = [&](f32x4& dst) {
-        asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(ap) : "memory");
-        ap += 64;
+    auto a_read = [&](f32x4* dst) {
+        asm volatile("ds_read_b128 %0, %1" : "=v"(dst[0]) : "v"(ap) : "memory");
+        if constexpr (BF) asm volatile("ds_read_b128 %0, %1 offset:16" : "=v"(dst[1]) : "v"(ap) : "memory");
+        ap += 64 * AK;
     };
     // (kernel-argument arrays are indexed through readfirstlane: one instantiation -- STORE == 1 on the 16-row engine --
     // could not prove the segment index uniform and copied the whole 2 KB argument block to scratch)
@@ -686,7 +753,7 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_kernel(NsArgs a) {
         if constexpr (LB) { const int j = __builtin_amdgcn_readfirstlane(si); s_gbit = ka->gbit[j]; s_mbit = ka->mbit[j]; }
     };
     auto begin_run = [&]() {                       // accumulators and A pointer of run (si, pass)
-        const int arow = SM ? sm_arow : li, ak = SM ? 4 * sm_achunk : 4 * kq;
+        const int arow = SM ? sm_arow : li, ak = AK * (SM ? 4 * sm_achunk : 4 * kq);
 #pragma unroll
         for (int t = 0; t < NACC; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
         if (s_type == NS_WIDE) {
@@ -726,10 +793,45 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_kernel(NsArgs a) {
         // steps are in flight instead of R).  Not in the merged training launch: its register allocation does not survive
         // the longer slot lifetimes (2.3 KB of scratch per lane, +40 % on the step).
         constexpr int RU = LATE_REFILL ? (U + R - 1) % R : U;
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(Aq[U & 1]) :: "memory");
+        if constexpr (BF) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(Aq[U & 1][0]), "+v"(Aq[U & 1][AK - 1]) :: "memory");
+        else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(Aq[U & 1][0]) :: "memory");
         a_read(Aq[(U + 1) & 1]);                   // next step's A (speculative at a run end)
-        const f32x4 av = Aq[U & 1];
-        if constexpr (SM) {
+        const f32x4 av = Aq[U & 1][0];
+        if constexpr (BF) {
+            // A rounded to bf16 where it is read: k 8 j + e of the lane's 8 (j = 0, 1: the two fragments)
+            bf16x8 ab;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { ab[e] = (__bf16)Aq[U & 1][0][e]; ab[4 + e] = (__bf16)Aq[U & 1][AK - 1][e]; }
+            if constexpr (SM) {
+                // acc[4 r + c] += A(row set r, k chunk c, half h) x B(chunk c = load c, half h); ABID = block 4 c + r
+                const s16x4 alo = __builtin_bit_cast(s16x4, __builtin_shufflevector(ab, ab, 0, 1, 2, 3));
+                const s16x4 ahi = __builtin_bit_cast(s16x4, __builtin_shufflevector(ab, ab, 4, 5, 6, 7));
+#define NS_B4(r, c, h, A4) acc[4 * (r) + (c)] = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(A4, \
+                __builtin_bit_cast(s16x4, __builtin_shufflevector(__builtin_bit_cast(bf16x8, Bq[U][c]), __builtin_bit_cast(bf16x8, Bq[U][c]), \
+                                                                  4 * (h), 4 * (h) + 1, 4 * (h) + 2, 4 * (h) + 3)), acc[4 * (r) + (c)], 4, 4 * (c) + (r), 0);
+#define NS_B4R(r, h, A4) NS_B4(r, 0, h, A4) NS_B4(r, 1, h, A4) NS_B4(r, 2, h, A4) NS_B4(r, 3, h, A4)
+                NS_B4R(0, 0, alo)
+                if constexpr (RS > 1) { NS_B4R(1, 0, alo) }
+                NS_B4R(0, 1, ahi)
+                if constexpr (RS > 1) { NS_B4R(1, 1, ahi) }
+#undef NS_B4R
+#undef NS_B4
+                if constexpr (refill) {
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) Bq[RU][t] = wload(t);
+                }
+            } else {
+#pragma unroll
+                for (int h = 0; h < NT; h += 2) {
+                    acc[h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab, __builtin_bit_cast(bf16x8, Bq[U][h]), acc[h], 0, 0, 0);
+                    acc[h + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab, __builtin_bit_cast(bf16x8, Bq[U][h + 1]), acc[h + 1], 0, 0, 0);
+                    if constexpr (refill) {
+                        Bq[RU][h] = wload(h);
+                        Bq[RU][h + 1] = wload(h + 1);
+                    }
+                }
+            }
+        } else if constexpr (SM) {
             // acc[4 r + c] += A(rows of set r, k chunk c, element e) x B(k chunk c = load c, element e); ABID = block 4 c + r
 #define NS_M4(r, c, e) acc[4 * (r) + (c)] = __builtin_amdgcn_mfma_f32_4x4x1f32(av[e], Bq[U][c][e], acc[4 * (r) + (c)], 4, 4 * (c) + (r), 0);
 #define NS_M4R(r, e) NS_M4(r, 0, e) NS_M4(r, 1, e) NS_M4(r, 2, e) NS_M4(r, 3, e)
@@ -1322,7 +1424,8 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_kernel(NsArgs a) {
     // The last speculative A read.  Both fragments are operands of the wait: the compiler does not know that the
     // inline-asm ds_read lands later, and a fragment nobody reads again would otherwise be dead at once -- its
     // registers could be handed to an accumulator of the final step, which the returning LDS data then overwrites.
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(Aq[0]), "+v"(Aq[1]) :: "memory");
+    if constexpr (BF) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(Aq[0][0]), "+v"(Aq[0][AK - 1]), "+v"(Aq[1][0]), "+v"(Aq[1][AK - 1]) :: "memory");
+    else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(Aq[0][0]), "+v"(Aq[1][0]) :: "memory");
     NS_STAMP();
 
     if constexpr (((STORE == 1 || STORE == 2) && !GRAD) || TRB) { NS_STAMPS_FLUSH(); return; }   // every output is in global memory already
@@ -1477,6 +1580,7 @@ struct NsProgram {
     int dense = 0, u_col = 0, u_same = 0;                   // dense inverse covariance appended as the last segment
     int x0_keep = 0;                                        // an input-skip segment copies the network input later
     size_t side_f4 = 0;                                     // 16-byte vectors of all SIDE blocks
+    bool bf = false;                                        // bf16 stream: 32 k per step, first layer [W | W] over [x_hi ; x_lo]
     size_t lds_for(int rows, bool grad) const {
         size_t b = (size_t)(2 * rows * LD + ((bias_total + 3) & ~3)) * sizeof(float) + 128 + (x0_keep ? 4096 : 0);   // + [16] set rows, [16] den (STORE == 3), kept input rows
 #ifdef NS_STAMPS
@@ -1522,7 +1626,8 @@ int net_stream_dense_tri(int mode) {
 // Translate the op list into segments; ok = false when something does not fit this kernel.
 enum { NS_PROG_FWD = 0, NS_PROG_FWD_NOGRAD = 1, NS_PROG_DX = 2, NS_PROG_DX_INPUT = 3, NS_PROG_FWD_DENSE = 4, NS_PROG_FWD_DXI = 5,
        NS_PROG_TRAIN = 6 };   // TRAIN: forward + loss segment (FWD_DENSE with the loss's inverse covariance) followed by the dX chain down to op 1
-static NsProgram ns_build_one(const linna_layer_t* layers, int nl, int in_size, int mode, const NsDense* dn = nullptr, bool k4 = false);
+static NsProgram ns_build_one(const linna_layer_t* layers, int nl, int in_size, int mode, const NsDense* dn = nullptr, bool k4 = false,
+                              bool bf = false);
 static NsProgram ns_build(const linna_layer_t* layers, int nl, int in_size, bool k4 = false) {
     NsProgram p = ns_build_one(layers, nl, in_size, NS_PROG_FWD, nullptr, k4);
     if (!p.ok) p = ns_build_one(layers, nl, in_size, NS_PROG_FWD_NOGRAD, nullptr, k4);      // the backward half may be what did not fit
@@ -1538,8 +1643,12 @@ static NsProgram ns_build(const linna_layer_t* layers, int nl, int in_size, bool
 // Gaussian log-likelihood (util.py:953-955) with a dense covariance then needs no GEMM launch of its own.
 // k4: SPLIT segments of <= 32 columns become SIDE segments where they fit (see NsPackArgs): the kernel's K4 path, i.e. the
 // serving instantiations of the 16-row engine only.
-static NsProgram ns_build_one(const linna_layer_t* layers, int nl, int in_size, int mode, const NsDense* dn, bool k4) {
+// bf: the bf16 serving program (NS_PROG_FWD_NOGRAD only, no dense segment, no SIDE segments): a step is 32 k, and the
+// first layer (a plain linear map) is [W | W] over K' = 2 nin -- its input rows are x_hi = bf16(x) and x_lo = x - x_hi.
+static NsProgram ns_build_one(const linna_layer_t* layers, int nl, int in_size, int mode, const NsDense* dn, bool k4, bool bf) {
     NsProgram p;
+    if (bf && (mode != NS_PROG_FWD_NOGRAD || dn || k4)) return p;
+    const int KS = bf ? 32 : 16;                            // k per step
     const bool allow_grad = mode == NS_PROG_FWD, dx_prog = mode == NS_PROG_DX || mode == NS_PROG_DX_INPUT;
     const bool train = mode == NS_PROG_TRAIN;
     if ((mode == NS_PROG_FWD_DENSE || train) && (!dn || !dn->S)) return p;
@@ -1614,6 +1723,11 @@ static NsProgram ns_build_one(const linna_layer_t* layers, int nl, int in_size, 
     }
     if (dx_prog) in_size = layers[nl - 1].N;                   // the rows of this program are d loss / d output
     if (lins.empty() || lins.back().relu || (int)lins.size() > NS_MAXSEG) return p;
+    if (bf) {                                               // [x_hi ; x_lo]: the first layer twice, no padding between the halves
+        Lin& f = lins[0];
+        if (f.Wb || f.same_buf || f.transA || !f.Wa || f.Ka != in_size || f.x0_col) return p;
+        f.Kapad = in_size; f.Wb = f.Wa; f.ldb = f.lda; f.Kb = f.Ka; f.alpha = 1.f;
+    }
     if (mode == NS_PROG_FWD_DENSE || train) {
         Lin& last = lins.back();
         if (last.Wb || last.same_buf || last.dst_col) return p;               // the last op must be a plain linear layer
@@ -1664,7 +1778,7 @@ static NsProgram ns_build_one(const linna_layer_t* layers, int nl, int in_size, 
     std::vector<int> in_ext(lins.size());
     for (size_t i = 0; i < lins.size(); ++i) {
         const Lin& L = lins[i];
-        const int ksteps = (L.Kapad + ceil16(L.Kb)) / 16;
+        const int ksteps = bf ? (L.Kapad + L.Kb + 31) / 32 : (L.Kapad + ceil16(L.Kb)) / 16;
         NsSeg s; NsPackSeg q;
         std::memset(&s, 0, sizeof(s));
         s.relu = L.relu; s.dst_col = L.dst_col; s.bias_off = bias_off;
@@ -1694,14 +1808,14 @@ static NsProgram ns_build_one(const linna_layer_t* layers, int nl, int in_size, 
             in_ext[i] = NS_NW * s.kslice;
             q.bias_pad = 64; q.ncg = 1;
         } else if (split) {
-            s.type = NS_SPLIT; s.steps = split_steps; s.passes = 1; s.kslice = 16 * s.steps;
+            s.type = NS_SPLIT; s.steps = split_steps; s.passes = 1; s.kslice = KS * s.steps;
             s.ncg_log2 = ncg == 1 ? 0 : ncg == 2 ? 1 : 2;
             s.zext = 64 * ncg;
             in_ext[i] = (NS_NW / ncg) * s.kslice;
             q.bias_pad = 64 * ncg; q.ncg = ncg;
         } else {
             s.type = NS_WIDE; s.steps = ksteps; s.passes = passes;
-            in_ext[i] = 16 * ksteps;
+            in_ext[i] = KS * ksteps;
             q.bias_pad = 512 * passes; q.ncg = 1;
         }
         q.Wa = L.Wa; q.lda = L.lda; q.Ka = L.Ka; q.Kapad = L.Kapad; q.Wb = L.Wb; q.ldb = L.ldb; q.Kb = L.Kb; q.alpha = L.alpha;
@@ -1779,7 +1893,8 @@ static NsProgram ns_build_one(const linna_layer_t* layers, int nl, int in_size, 
         }
     }
     for (const NsSeg& s : p.seg) if (s.type != NS_WIDE) maxext = std::max(maxext, s.dst_col + s.zext);
-    if (p.kpad0 > (dx_prog ? 1024 : 256)) return p;
+    if (p.kpad0 > (dx_prog ? 1024 : bf ? 512 : 256)) return p;
+    p.bf = bf;
     p.nout = lins[nfwd - 1].N;
     p.G = Gf; p.Gstride = G; p.nseg_f = nfwd; p.grad_ok = want_grad;
     for (size_t i = 0; i < lins.size(); ++i) { p.seg_op.push_back(lins[i].op); p.seg_hidden.push_back(lins[i].same_buf ? 1 : 0); }
@@ -1811,6 +1926,20 @@ static NsProgram ns_build_one(const linna_layer_t* layers, int nl, int in_size, 
 
 static const NsProgram& ns_build_prog(const linna_layer_t* layers, int nl, int in_size, int prog, const NsDense* dn = nullptr, bool k4 = false);
 bool net_stream_eligible(const linna_layer_t* layers, int nl, int in_size) { return ns_build_prog(layers, nl, in_size, 0, nullptr).ok; }
+bool net_stream_bf16_eligible(const linna_layer_t* layers, int nl, int in_size, const char** why) {
+    const char* r = nullptr;
+    int width = 0;
+    for (int i = 0; i < nl; ++i) width = std::max(width, std::max(layers[i].N, layers[i].op == LINNA_OP_RESBLOCK ? layers[i].C : 0));
+    if (in_size > 256) r = "more than 256 network inputs: outside the whole-network kernel";
+    else if (width > 1024) r = "a layer wider than 1024: outside the whole-network kernel";
+    else if (nl < 1 || layers[0].op != LINNA_OP_LINEAR) r = "the first op is not a linear layer (the bf16 input split needs one)";
+    else if (!ns_build_prog(layers, nl, in_size, NS_PROG_BF16_CODE, nullptr).ok) r = "the network does not fit the bf16 program of the whole-network kernel";
+    if (why) *why = r;
+    return r == nullptr;
+}
+size_t net_stream_bf16_packed_floats(const linna_layer_t* layers, int nl, int in_size) {
+    return ns_build_prog(layers, nl, in_size, NS_PROG_BF16_CODE, nullptr).packed_floats;
+}
 size_t net_stream_packed_floats(const linna_layer_t* layers, int nl, int in_size) {
     return ns_build_prog(layers, nl, in_size, 0, nullptr).packed_floats;
 }
@@ -1872,6 +2001,7 @@ static NsProgram ns_build_prog_uncached(const linna_layer_t* layers, int nl, int
         NsProgram p = dn ? ns_build_one(layers, nl, in_size, NS_PROG_FWD_DENSE, dn, true) : ns_build(layers, nl, in_size, true);
         if (p.ok) return p;
     }
+    if (prog == NS_PROG_BF16_CODE) return dn ? NsProgram() : ns_build_one(layers, nl, in_size, NS_PROG_FWD_NOGRAD, nullptr, false, true);
     if (prog == 0 && dn) return ns_build_one(layers, nl, in_size, NS_PROG_FWD_DENSE, dn);
     if (prog == 3) return ns_build_one(layers, nl, in_size, NS_PROG_FWD_DXI);
     if (prog == 4) return ns_build_one(layers, nl, in_size, NS_PROG_TRAIN, dn);
@@ -1959,6 +2089,7 @@ int launch_net_stream_pack(const linna_layer_t* layers, int nl, int in_size, flo
     ::memset(static_cast<void*>(&a), 0, sizeof(a));
     a.nseg = (int)p.seg.size(); a.G = p.Gstride; a.bias_total = p.bias_total; a.out = packed;
     a.small = rows < 16;
+    a.bf = p.bf ? 1 : 0;
     int nrun = 0, first = 0;
     for (int i = 0; i < a.nseg; ++i) {
         a.seg[i] = p.pack[i];
@@ -1980,19 +2111,19 @@ int launch_net_stream_pack(const linna_layer_t* layers, int nl, int in_size, flo
     return check_hip(hipGetLastError(), "net_stream pack launch");
 }
 
-template <int MOVE, bool GRAD, int STORE, int ROWS>
+template <int MOVE, bool GRAD, int STORE, int ROWS, bool BF = false>
 static int ns_launch_rows(const NsArgs& a, int B, size_t lds_bytes, hipStream_t s, int extra = 0) {
     static bool attr_set = false;
     if (!attr_set) {
-        const int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(&net_stream_kernel<NS_R, MOVE, GRAD, STORE, ROWS>),
+        const int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(&net_stream_kernel<NS_R, MOVE, GRAD, STORE, ROWS, BF>),
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, NS_LDS_BYTES), "hipFuncSetAttribute");
         if (rc != LINNA_OK) return rc;
         attr_set = true;
     }
-    hipLaunchKernelGGL((net_stream_kernel<NS_R, MOVE, GRAD, STORE, ROWS>), dim3((B + ROWS - 1) / ROWS + extra), dim3(64 * NS_NW), lds_bytes, s, a);
+    hipLaunchKernelGGL((net_stream_kernel<NS_R, MOVE, GRAD, STORE, ROWS, BF>), dim3((B + ROWS - 1) / ROWS + extra), dim3(64 * NS_NW), lds_bytes, s, a);
     return check_hip(hipGetLastError(), "net_stream launch");
 }
-template <int MOVE, bool GRAD, int STORE = 0>
+template <int MOVE, bool GRAD, int STORE = 0, bool BF = false>
 static int ns_launch_kernel(const NsArgs& a0, int B, const NsProgram& p, int rows, hipStream_t s, int extra = 0, size_t lds_extra = 0) {
     const size_t lds = p.lds_for(rows, GRAD) + lds_extra;
 #ifdef NS_STAMPS
@@ -2003,8 +2134,11 @@ static int ns_launch_kernel(const NsArgs& a0, int B, const NsProgram& p, int row
 #else
     const NsArgs& a = a0;
 #endif
-    if (rows == 4) return ns_launch_rows<MOVE, GRAD, STORE, 4>(a, B, lds, s, extra);
-    if constexpr (STORE == 3 && GRAD) {
+    if (rows == 4) return ns_launch_rows<MOVE, GRAD, STORE, 4, BF>(a, B, lds, s, extra);
+    if constexpr (BF) {
+        if (rows == 8) return ns_launch_rows<MOVE, GRAD, STORE, 8, BF>(a, B, lds, s, extra);
+        if (rows == 16) return ns_launch_rows<MOVE, GRAD, STORE, 16, BF>(a, B, lds, s, extra);
+    } else if constexpr (STORE == 3 && GRAD) {
         // the one-launch training step exists for the 4-row engine only (batches up to 1024 rows; the caller checks): on the
         // 8-row engine it was measured SLOWER than its two halves (batch 1500 at (26,457): 218.5 against 210.9 us per step)
     } else {
@@ -2226,8 +2360,8 @@ int launch_net_stream(const linna_layer_t* layers, int nl, int in_size, const fl
                       int nin, const int* is_flat, const float* a1, const float* a2, const int* lg, const float* xmean,
                       const float* xstd, const float* cscale, const float* cshift, const float* w, float T, float* lnP,
                       float* D, int ldd, float* TH, int ldt, const NsMove* mv, const NsGrad* gr, const int* gate, int rows,
-                      const NsDense* dn, hipStream_t s, const float* cpost, const float* cshift2) {
-    const NsProgram& p = ns_build_prog(layers, nl, in_size, 0, dn, net_stream_k4(rows, 1));
+                      const NsDense* dn, hipStream_t s, const float* cpost, const float* cshift2, int bf) {
+    const NsProgram& p = bf ? ns_build_prog(layers, nl, in_size, NS_PROG_BF16_CODE, dn) : ns_build_prog(layers, nl, in_size, 0, dn, net_stream_k4(rows, 1));
     if ((cpost != nullptr) != (cshift2 != nullptr) || (cpost && (dn || gr))) {
         set_error("net_stream: the exp output map needs cpost and cshift2, and has no dense / gradient program"); return LINNA_ERR_INVALID;
     }
@@ -2258,9 +2392,15 @@ int launch_net_stream(const linna_layer_t* layers, int nl, int in_size, const fl
         a.sl_Z0 = mv->sl_Z0; a.sl_L = mv->sl_L; a.sl_R = mv->sl_R; a.sl_Zt = mv->sl_Zt; a.sl_m = mv->sl_m; a.sl_nt = mv->sl_nt;
         a.sl_seed = mv->sl_seed; a.sl_step = mv->sl_step; a.sl_stream = mv->sl_stream; a.sl_flags = mv->sl_flags;
         if (mv->sb) a.sb = *mv->sb;
-        if (mv->slice) return ns_launch_kernel<2, false>(a, B, p, rows, s);
+        if (mv->slice) {
+            if (bf) { set_error("net_stream: the slice move has no bf16 instantiation"); return LINNA_ERR_UNSUPPORTED; }
+            return ns_launch_kernel<2, false>(a, B, p, rows, s);
+        }
+        if (bf) return ns_launch_kernel<1, false, 0, true>(a, B, p, rows, s);
         return ns_launch_kernel<1, false>(a, B, p, rows, s);
     }
+    if (bf && gr) { set_error("net_stream: no bf16 gradient"); return LINNA_ERR_UNSUPPORTED; }
+    if (bf) return ns_launch_kernel<0, false, 0, true>(a, B, p, rows, s);
     if (gr) {
         a.gscale = gr->gscale; a.Gout = gr->G; a.ldg = gr->ldg;
         a.hm_p = gr->hm_p; a.hm_ldp = gr->hm_ldp; a.hm_q = gr->hm_q; a.hm_mass = gr->hm_mass; a.hm_ek = gr->hm_ek; a.hm_ed = gr->hm_ed;

@@ -21,8 +21,8 @@ from ._lib import stage
 
 
 def ml_sampler(outdir, theory, priors, data, cov, init, pool, nwalkers, gpunode, omegab2cut=None, nepoch=4500,
-               method="zeus", nbest=None, chisqcut=None, loglikelihoodfunc=None):
-    """main.py:22-75: the hyper-parameter schedule of To et al. 2022."""
+               method="zeus", nbest=None, chisqcut=None, loglikelihoodfunc=None, emulator_precision="fp32"):
+    """main.py:22-75: the hyper-parameter schedule of To et al. 2022.  ``emulator_precision``: see ``ml_sampler_core``."""
     ntrainArr = [10000, 10000, 10000, 10000]
     nvalArr = [500, 500, 500, 500]
     if method == "emcee":
@@ -39,14 +39,16 @@ def ml_sampler(outdir, theory, priors, data, cov, init, pool, nwalkers, gpunode,
     return ml_sampler_core(ntrainArr, nvalArr, nkeepArr, ntimesArr, ntautolArr, meanshiftArr, stdshiftArr, outdir, theory,
                            priors, data, cov, init, pool, nwalkers, "cuda", None, False, temperatureArr, omegab2cut, False, 1,
                            gpunode, lnn.ChtoModelv2, params, method, nbest=nbest, chisqcut=chisqcut,
-                           loglikelihoodfunc=loglikelihoodfunc)
+                           loglikelihoodfunc=loglikelihoodfunc, emulator_precision=emulator_precision)
 
 
 def ml_sampler_core(ntrainArr, nvalArr, nkeepArr, ntimesArr, ntautolArr, meanshiftArr, stdshiftArr, outdir, theory, priors,
                     data, cov, init, pool, nwalkers, device, dolog10index, ypositive, temperatureArr, omegab2cut=None,
                     docuda=False, tsize=1, gpunode=None, nnmodel_in=None, params=None, method="emcee", nbest=None,
-                    chisqcut=None, loglikelihoodfunc=None, nsigma=3, externalloglike=None):
+                    chisqcut=None, loglikelihoodfunc=None, nsigma=3, externalloglike=None, emulator_precision="fp32"):
     """main.py:77-335.  Returns ``(chain[nsamp, ndim] in theta space, log_prob)``.
+    ``emulator_precision`` ("fp32" or the opt-in "bf16"): the arithmetic of the emulator while SAMPLING (``util.Log_prob``);
+    training and every other evaluation stay fp32.
     ``gpunode`` / ``docuda`` / ``device`` (main.py:193-245: which Slurm node runs ``train_gpu.py`` under srun) keep their
     places in the signature; the emulator always trains in this process on the local GPU."""
     if method == "emcee":
@@ -137,7 +139,7 @@ def ml_sampler_core(ntrainArr, nvalArr, nkeepArr, ntimesArr, ntautolArr, meanshi
             continue
         log_prob = Log_prob(data.astype(np.float32), inv_cov.astype(np.float32), model, y_invtransform_data, transform,
                             temperature, nograd=True, loglikelihoodfunc=loglikelihoodfunc or gaussianlogliklihood,
-                            externalloglike=externalloglike)
+                            externalloglike=externalloglike, precision=emulator_precision)
         if pool is not None:
             pool.noduplicate = True                                              # main.py:282-283
         with stage("run_mcmc"):

@@ -316,10 +316,18 @@ class Log_prob(object):
     ``__call__`` accepts one walker ``x[ndim]`` (reference semantics: returns a scalar) or a
     batch ``x[B, ndim]`` (returns ``[B]``, every row evaluated as the reference evaluates one
     walker -- the reference itself is only correct for B = 1).
+
+    ``precision="bf16"`` (opt-in; default ``"fp32"``) serves lnP from the whole-network kernel's bf16 engine: weights
+    and matrix-core operands rounded to bf16, everything else fp32 (include/linna_hip.h, linna_logprob_set_precision).
+    Serving only: ``evaluate_with_grad`` raises.  A network or likelihood the bf16 engine cannot serve (a dense
+    covariance, a layer wider than 1024, ...) raises ``ValueError`` naming the reason when the object is first used.
     """
 
     def __init__(self, data_new, invcov_new, model, y_invtransform_data, transform, temperature, loglikelihoodfunc=None,
-                 nograd=False, externalloglike=None):
+                 nograd=False, externalloglike=None, precision="fp32"):
+        if precision not in _lib.PRECISION:
+            raise ValueError("Log_prob: precision must be 'fp32' or 'bf16', not %r" % (precision,))
+        self.precision = precision
         self.data_new = data_new
         self.invcov_new = invcov_new
         self.model = model
@@ -395,6 +403,13 @@ class Log_prob(object):
         d.temperature = self.T
         h = C.c_void_p()
         _lib.call("linna_logprob_create", _lib.ctx(dev.index), net.net_handle(), C.byref(d), C.byref(h))
+        rc = _lib.load().linna_logprob_set_precision(h, _lib.PRECISION[self.precision])
+        if rc != 0:
+            msg = _lib.load().linna_last_error().decode()
+            _lib.load().linna_logprob_destroy(h)
+            if rc == _lib.ERR_UNSUPPORTED:
+                raise ValueError("Log_prob(precision=%r): %s" % (self.precision, msg))
+            _lib.check(rc)
         self._plan = dict(handle=h, keep=k, desc=d, dev=dev, nin=nin, nout=nout, net_sig=net._net_sig)
         self._ws = {}
 
@@ -456,6 +471,8 @@ class Log_prob(object):
     def evaluate_with_grad(self, z, out=None, grad=None):
         """``(lnP[B], d lnP/d z [B, nin])`` -- what ``torch.autograd.grad(lnP, x)`` yields in
         HMCSampler.py:32, batched per walker."""
+        if self.precision != "fp32":
+            raise ValueError("Log_prob.evaluate_with_grad: no gradient in %s (serving only); use precision='fp32'" % self.precision)
         p = self._ensure()
         self._check_rows(z, p)
         B = z.shape[0]

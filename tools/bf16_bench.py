@@ -1,0 +1,115 @@
+#!/usr/bin/env python
+"""fp32 against the opt-in bf16 serving engine (linna_logprob_set_precision), device events, resident inputs, after warm-up:
+  headline  the 4x4 512 MLP (bench.py's problem) at 4096 walkers, one linna_logprob_eval
+  v2_64     one 64-row ChtoModelv2(33,33) evaluation
+  stretch   one 2048-proposal stretch half step (linna_stretch_half_step, the 4096-walker ensemble, MLP)
+  emcee128  emcee iterations per second at 128 walkers on ChtoModelv2(33,33) (linna_stretch_run blocks)
+Prints ONE JSON line.  FLOP/s count 2 x multiply-adds of the network per walker, against the bf16 dense peak (2.5 PF spec);
+bytes = the weight stream each workgroup reads per launch (padded fragment layout) x workgroups.
+usage: python tools/bf16_bench.py [--reps N]"""
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import bench  # noqa: E402
+from linna_amd import _lib, nn, predictor_gpu, sampler, util  # noqa: E402
+from oracle import emulator  # noqa: E402
+
+BF16_PEAK = 2.5e15
+REPS = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 200
+
+
+def timed(fn, reps):
+    for _ in range(10):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / reps          # us per call
+
+
+def with_precision(lp, precision):
+    return util.Log_prob(lp.data_new, lp.invcov_new, lp.model, lp.y_invtransform_data, lp.transform, lp.T, lp.loglikelihoodfunc,
+                         nograd=True, precision=precision)
+
+
+def v2_problem(dev):
+    """ChtoModelv2(33,33), bench.py's transforms and likelihood (diagonal)."""
+    lp0, _, c = bench.build_problem(dev)
+    torch.manual_seed(4321)
+    model = nn.ChtoModelv2(33, 33, None)
+    t = lambda a: torch.as_tensor(np.asarray(a, np.float32))
+    pred = predictor_gpu.Predictor(33, 33, model=model, device=dev,
+                                   X_transform=util.X_transform_class(t(c["X_mean"]), t(c["X_std"]), "cpu", None),
+                                   y_transform=util.Y_transform_class(t(c["y_mean"]), t(c["y_std"]), "cpu"))
+    return util.Log_prob(lp0.data_new, lp0.invcov_new, pred, lp0.y_invtransform_data, lp0.transform, 1.0,
+                         util.gaussianlogliklihood, nograd=True)
+
+
+def stream_bytes(kind, bf, **kw):
+    """Weight bytes one workgroup streams per launch: every matrix product, K padded to the step (16 fp32 / 32 bf16, the
+    first layer twice as wide in bf16: [W | W] over [x_hi ; x_lo]), N to 64 columns."""
+    ks, bpe = (32, 2) if bf else (16, 4)
+    tot = 0
+    for i, op in enumerate(emulator.topology(kind, 33, 33, **kw)):
+        if op[0] == "linear":
+            _, _, K, N, _ = op
+            K = 2 * K if (bf and i == 0) else K
+            tot += -(-K // ks) * ks * -(-N // 64) * 64
+        elif op[0] == "resblock":
+            _, _, K, C, N = op
+            tot += -(-K // ks) * ks * 64 + -(-(K + C) // ks) * ks * -(-N // 64) * 64
+    return tot * bpe
+
+
+def main():
+    dev = torch.device("cuda", 0)
+    res = {"tool": "bf16_bench", "reps": REPS, "bf16_peak_flops": BF16_PEAK}
+    lp_mlp, _, _ = bench.build_problem(dev)
+    lp_v2 = v2_problem(dev)
+    macs = {"MLP": emulator.macs_per_eval("MLP", 33, 33, width=512, depth=4), "ChtoModelv2": emulator.macs_per_eval("ChtoModelv2", 33, 33)}
+    for prec in ("fp32", "bf16"):
+        bf = prec == "bf16"
+        m = with_precision(lp_mlp, prec)
+        v = with_precision(lp_v2, prec)
+        for tag, lp, kind, B in (("headline", m, "MLP", 4096), ("v2_64", v, "ChtoModelv2", 64)):
+            z = torch.randn(B, 33, device=dev) * 0.5
+            out = torch.empty(B, device=dev)
+            us = timed(lambda: lp.evaluate(z, out=out), REPS)
+            kw = dict(width=512, depth=4) if kind == "MLP" else {}
+            rows = 16 if B >= 2048 else 4
+            wg = -(-B // rows)
+            res["%s_%s_us" % (tag, prec)] = round(us, 2)
+            res["%s_%s_tflops" % (tag, prec)] = round(2.0 * macs[kind] * B / (us * 1e-6) / 1e12, 2)
+            res["%s_%s_pct_bf16_peak" % (tag, prec)] = round(100.0 * 2.0 * macs[kind] * B / (us * 1e-6) / BF16_PEAK, 3)
+            res["%s_%s_stream_bytes_per_wg" % (tag, prec)] = stream_bytes(kind, bf, **kw)
+            res["%s_%s_stream_bytes_per_launch" % (tag, prec)] = stream_bytes(kind, bf, **kw) * wg
+        # 2048-proposal stretch half step: the fused half steps of a 4096-walker ensemble (one step = two half steps)
+        ens = sampler.EnsembleSampler(4096, 33, m, seed=1)
+        ens.set_state(0.3 * np.random.RandomState(0).standard_normal((4096, 33)).astype(np.float32))
+        us = timed(ens.step, REPS // 4)
+        assert ens.fused is True, "stretch half step did not run fused"
+        res["stretch_half_step_%s_us" % prec] = round(us / 2, 2)
+        # emcee at 128 walkers, ChtoModelv2(33,33): iterations per second of blocks of linna_stretch_run
+        e128 = sampler.EnsembleSampler(128, 33, v, seed=2)
+        e128.set_state(0.3 * np.random.RandomState(1).standard_normal((128, 33)).astype(np.float32))
+        e128.run(50, store=False)
+        torch.cuda.synchronize()
+        us = timed(lambda: e128.run(100, store=False), 3)
+        res["emcee128_%s_it_per_s" % prec] = round(100.0 / (us * 1e-6), 1)
+    res["headline_speedup"] = round(res["headline_fp32_us"] / res["headline_bf16_us"], 3)
+    res["v2_64_speedup"] = round(res["v2_64_fp32_us"] / res["v2_64_bf16_us"], 3)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
