@@ -74,8 +74,6 @@ struct linna_ctx {
     int device;
     hipStream_t aux = nullptr;               // second stream: parameter-gradient GEMMs run beside the dX chain
     std::vector<hipEvent_t> events;          // fork/join markers (no timing)
-    int overlap = -1;                        // -1 unknown, 0 off (env LINNA_BWD_STREAMS=0), 1 on
-    int group = -1;                          // -1 unknown, 0 off (env LINNA_BWD_GROUP=0), 1 on
     unsigned* counters = nullptr;            // zeroed, self-resetting arrival counters (fused loss)
     int loss_fused = -1;                     // -1 unknown, 0 off (env LINNA_LOSS_FUSED=0), 1 on
     void* comm = nullptr;                    // RCCL communicator state (comm.hip), set by linna_comm_init
@@ -112,15 +110,15 @@ struct linna_net {
     int stream_fwd = -1;
     StreamCopy packed_loss;                  // ... for forward + chi^2-ratio loss in one launch (linna_net_forward_loss)
     NsDense loss_dn{nullptr, 0, nullptr, nullptr};   // the inverse covariance that stream ends in
-    int stream_loss = -1;                    // -1 unknown, 0 no (not eligible / LINNA_LOSS_STREAM=0), 1 yes
+    int stream_loss = -1;                    // -1 unknown, 0 no (not eligible), 1 yes
     StreamCopy packed_dx[2];                 // ... for the one-launch dX chain of the backward ([1]: down to the network input)
     StreamCopy packed_tb;                    // ... for forward + loss + dX chain in ONE launch (linna_net_train_step on the small-batch engines)
-    int stream_tb = -1;                      // -1 unknown, 0 no (not eligible / LINNA_TRAIN_MERGED=0), 1 yes
+    int stream_tb = -1;                      // -1 unknown, 0 no (not eligible / LINNA_BWD_STREAM=0), 1 yes
     int as_merged = -1;                      // which streams as_args describes: 1 = packed_tb, 0 = packed_loss + packed_dx[0]
     AsArgs as_args;                          // linna_net_adamw_step's descriptor table, valid for (as_params, as_n, as_k)
     const float* as_params = nullptr; size_t as_n = 0; int as_k = -1; int as_state = -1;   // as_state: -1 unknown, 0 unsupported, 1 ready
     int upd_state = -1; int upd_B = 0;       // linna_net_train_step_update: -1 unknown, 0 unsupported, 1 every parameter gradient of the step is in the grouped launch
-    int stream_bwd[2] = {-1, -1};            // -1 unknown, 0 no (network out of reach / LINNA_BWD_STREAM=0), 1 yes                     // -1 unknown, 0 no (network out of reach / LINNA_FWD_STREAM=0), 1 yes
+    int stream_bwd[2] = {-1, -1};            // -1 unknown, 0 no (network out of reach / LINNA_BWD_STREAM=0), 1 yes
     std::vector<linna_layer_t> L;   // without the trailing INSKIP
     std::vector<linna_layer_t> Lfull;   // with it: what the serving programs of the whole-network kernel are built from
     int in_size, out_size;
@@ -129,27 +127,48 @@ struct linna_net {
     int max_w, max_c;
 };
 
-static int stream_copy_refresh(StreamCopy& sc, const linna_net* n, int rows, void* stream, const float** out, int prog = 0,
-                               const NsDense* dn = nullptr, int serve = 0);
+static int stream_copy_refresh(StreamCopy& sc, const linna_net* n, int rows, void* stream, const float** out, NsKind kind,
+                               const NsDense* dn = nullptr);
 
-struct FwdLayout {
-    std::vector<size_t> t_off, y_off;   // float offsets, per op (y_off of the last op unused)
-    size_t total;
-};
-
-static FwdLayout fwd_layout(const linna_net* n, int B) {
-    FwdLayout f;
-    size_t off = 0;
+// forward workspace: per op, the hidden h of a residual block, then the op's output (the last op's is the caller's)
+static size_t fwd_floats(const linna_net* n, int B) {
+    size_t f = 0;
+    for (size_t i = 0; i < n->L.size(); ++i) {
+        if (n->L[i].op == LINNA_OP_RESBLOCK) f += (size_t)B * ld4(n->L[i].C);
+        if (i + 1 < n->L.size()) f += (size_t)B * ld4(n->L[i].N);
+    }
+    return f;
+}
+// Per op, where a training step's activations and their gradients live (NsOpBufs): the forward workspace `fwd_ws` in
+// fwd_floats' order (the last op's output is `out`), and the backward workspace `bwd_ws` walked from the last op down --
+// d/d(op input) for every op but the first (whose is `dX`, or none), d/dh behind it for a residual block.  No backward
+// workspace: those entries stay unset.
+static std::vector<NsOpBufs> net_bufs(const linna_net* n, int B, const float* X, int ldx, void* fwd_ws, float* out, int ldo,
+                                      void* bwd_ws = nullptr, float* dX = nullptr, int lddx = 0) {
     const int nl = (int)n->L.size();
-    f.t_off.assign(nl, 0);
-    f.y_off.assign(nl, 0);
+    float* w = static_cast<float*>(fwd_ws);
+    size_t off = 0;
+    std::vector<NsOpBufs> ops(nl, NsOpBufs{});
     for (int i = 0; i < nl; ++i) {
         const linna_layer_t& l = n->L[i];
-        if (l.op == LINNA_OP_RESBLOCK) { f.t_off[i] = off; off += (size_t)B * ld4(l.C); }
-        if (i + 1 < nl) { f.y_off[i] = off; off += (size_t)B * ld4(l.N); }
+        NsOpBufs& o = ops[i];
+        const bool last = i == nl - 1;
+        if (l.op == LINNA_OP_RESBLOCK) { o.t = w + off; off += (size_t)B * ld4(l.C); }
+        o.ldt = ld4(l.C);
+        if (last) { o.y = out; o.ldy = ldo; }
+        else { o.y = w + off; o.ldy = ld4(l.N); off += (size_t)B * ld4(l.N); }
+        o.x = i == 0 ? X : ops[i - 1].y; o.ldx = i == 0 ? ldx : ops[i - 1].ldy;
+        // the input went through a ReLU iff the producing op is a resblock or a linear with relu
+        o.gate = i > 0 && (n->L[i - 1].op == LINNA_OP_RESBLOCK || n->L[i - 1].relu) ? o.x : nullptr;
     }
-    f.total = off;
-    return f;
+    float* cur = static_cast<float*>(bwd_ws);
+    for (int i = nl - 1; i >= 0 && cur; --i) {
+        const linna_layer_t& l = n->L[i];
+        ops[i].dprev = i == 0 ? dX : cur; ops[i].ldp = i == 0 ? lddx : ld4(l.K);
+        if (i > 0) cur += (size_t)B * ld4(l.K);
+        if (l.op == LINNA_OP_RESBLOCK) { ops[i].dt = cur; ops[i].lddt = ld4(l.C); cur += (size_t)B * ld4(l.C); }
+    }
+    return ops;
 }
 
 extern "C" {
@@ -345,22 +364,23 @@ static void net_ensure_fwd(linna_net* n, bool may_alloc) {
     const int nl = (int)n->L.size();
     if (n->stream_fwd < 0) {
         const char* e = getenv("LINNA_FWD_STREAM");
-        n->stream_fwd = !n->has_inskip && !(e && e[0] == '0') && net_stream_eligible(n->L.data(), nl, n->in_size) ? 1 : 0;
+        n->stream_fwd = !n->has_inskip && !(e && e[0] == '0') && net_stream_plan(NS_STORE, n->L.data(), nl, n->in_size).ok ? 1 : 0;
     }
     if (n->stream_fwd == 1 && !n->packed.ready() && may_alloc) {
-        if (n->packed.alloc(net_stream_packed_floats(n->L.data(), nl, n->in_size)) != LINNA_OK) n->stream_fwd = 0;
+        if (n->packed.alloc(net_stream_plan(NS_STORE, n->L.data(), nl, n->in_size).packed_floats) != LINNA_OK) n->stream_fwd = 0;
     }
 }
 static void net_ensure_dx(linna_net* n, int wi, bool may_alloc) {
     const int nl = (int)n->L.size();
+    const NsKind kind = wi ? NS_DX_INPUT : NS_DX;
     if (n->stream_bwd[wi] < 0) {
         const char* e = getenv("LINNA_BWD_STREAM");
         n->stream_bwd[wi] = !n->has_inskip && (nl >= 2 || wi) && !(e && e[0] == '0') &&
-                            net_stream_dx_eligible(n->L.data(), nl, n->in_size, wi) ? 1 : 0;
+                            net_stream_plan(kind, n->L.data(), nl, n->in_size).ok ? 1 : 0;
     }
     StreamCopy& sc = n->packed_dx[wi];
     if (n->stream_bwd[wi] == 1 && !sc.ready() && may_alloc) {
-        if (sc.alloc(net_stream_dx_packed_floats(n->L.data(), nl, n->in_size, wi)) != LINNA_OK) n->stream_bwd[wi] = 0;
+        if (sc.alloc(net_stream_plan(kind, n->L.data(), nl, n->in_size).packed_floats) != LINNA_OK) n->stream_bwd[wi] = 0;
     }
 }
 int linna_net_prepare(linna_net_t* n, int backward, int input_grad) try {
@@ -379,7 +399,7 @@ int linna_net_prepare(linna_net_t* n, int backward, int input_grad) try {
     return LINNA_OK;
 } LINNA_CATCH_INT
 
-size_t linna_net_fwd_ws_bytes(const linna_net_t* n, int B) try { return (fwd_layout(n, B).total + 16) * sizeof(float); } LINNA_CATCH_SIZE
+size_t linna_net_fwd_ws_bytes(const linna_net_t* n, int B) try { return (fwd_floats(n, B) + 16) * sizeof(float); } LINNA_CATCH_SIZE
 // backward scratch: one buffer per op for the gradient wrt that op's input (no reuse: the
 // parameter-gradient GEMMs of an op may still be reading it on the auxiliary stream while the dX
 // chain moves on) + one dT buffer per residual block
@@ -396,10 +416,10 @@ size_t linna_net_bwd_ws_bytes(const linna_net_t* n, int B) try { return (bwd_flo
 int linna_net_forward(linna_net_t* n, const float* X, int ldx, int B, void* ws, float* OUT, int ldo,
                       const linna_colmap_t* om, void* stream) try {
     if (!n || !X || !OUT || B < 1) { set_error("net_forward: bad arguments"); return LINNA_ERR_INVALID; }
-    const FwdLayout f = fwd_layout(n, B);
     float* w = static_cast<float*>(ws);
     const int nl = (int)n->L.size();
     if (nl > 1 && !w) { set_error("net_forward: workspace required"); return LINNA_ERR_INVALID; }
+    const std::vector<NsOpBufs> ops = net_bufs(n, B, X, ldx, w, OUT, ldo);
     if ((!om || !om->cexp) && !n->has_inskip) {
         // ONE launch (net_stream.hip, STORE): at batch 500 the ten layer GEMMs are 10-30 us of latency each.  The
         // fragment-order weight copy is re-laid whenever the weights moved (every optimiser step: ~10 us).
@@ -409,24 +429,17 @@ int linna_net_forward(linna_net_t* n, const float* X, int ldx, int B, void* ws, 
         if (n->stream_fwd == 1 && n->packed.ready()) {
             const int rows = net_stream_rows(B);
             const float* packed = nullptr;
-            TRY(stream_copy_refresh(n->packed, n, rows, stream, &packed));
-            std::vector<float*> y(nl), t(nl);
-            std::vector<int> ldy(nl), ldt(nl);
-            for (int i = 0; i < nl; ++i) {
-                const bool last = i == nl - 1;
-                y[i] = last ? OUT : w + f.y_off[i]; ldy[i] = last ? ldo : ld4(n->L[i].N);
-                t[i] = n->L[i].op == LINNA_OP_RESBLOCK ? w + f.t_off[i] : nullptr; ldt[i] = ld4(n->L[i].C);
-            }
-            return launch_net_stream_store(n->L.data(), nl, n->in_size, packed, X, ldx, B, y.data(), ldy.data(), t.data(),
-                                           ldt.data(), om ? om->cscale : nullptr, om ? om->cshift : nullptr, rows, S(stream));
+            TRY(stream_copy_refresh(n->packed, n, rows, stream, &packed, NS_STORE));
+            return launch_net_stream_store(n->L.data(), nl, n->in_size, packed, X, ldx, B, ops.data(), om ? om->cscale : nullptr,
+                                           om ? om->cshift : nullptr, rows, S(stream));
         }
     }
     const float* hin = X; int ldh = ldx;
     for (int i = 0; i < nl; ++i) {
         const linna_layer_t& l = n->L[i];
         const bool last = (i == nl - 1);
-        float* Y = last ? OUT : w + f.y_off[i];
-        const int ldy = last ? ldo : ld4(l.N);
+        float* Y = ops[i].y;
+        const int ldy = ops[i].ldy;
         if (l.op == LINNA_OP_LINEAR) {
             GemmArgs a = gemm_zero();
             a.M = B; a.N = l.N; a.C = Y; a.ldc = ldy; a.relu = l.relu;
@@ -447,8 +460,7 @@ int linna_net_forward(linna_net_t* n, const float* X, int ldx, int B, void* ws, 
             }
             TRY(gemm_launch(a, S(stream)));
         } else {
-            float* T = w + f.t_off[i];
-            TRY(linna_resblock_fwd(nullptr, hin, ldh, l.W1, l.b1, l.W2, l.b2, l.Ws, T, ld4(l.C), Y, ldy, B, l.K, l.C, l.N, stream));
+            TRY(linna_resblock_fwd(nullptr, hin, ldh, l.W1, l.b1, l.W2, l.b2, l.Ws, ops[i].t, ops[i].ldt, Y, ldy, B, l.K, l.C, l.N, stream));
         }
         hin = Y; ldh = ldy;
     }
@@ -457,19 +469,18 @@ int linna_net_forward(linna_net_t* n, const float* X, int ldx, int B, void* ws, 
 
 static void net_ensure_loss(linna_net* n, const NsDense& dn) {
     const int nl = (int)n->L.size();
-    const char* e = getenv("LINNA_LOSS_STREAM");
-    const bool ok = !n->has_inskip && !(e && e[0] == '0') && net_stream_dense_eligible(n->L.data(), nl, n->in_size, dn);
+    const NsPlan loss = net_stream_plan(NS_TRAIN_FWD, n->L.data(), nl, n->in_size, &dn);
+    const bool ok = !n->has_inskip && loss.ok;
     n->packed_loss.release();
     n->stream_loss = 0; n->loss_dn = dn;
-    if (ok && n->packed_loss.alloc(net_stream_dense_packed_floats(n->L.data(), nl, n->in_size, dn)) == LINNA_OK) n->stream_loss = 1;
+    if (ok && n->packed_loss.alloc(loss.packed_floats) == LINNA_OK) n->stream_loss = 1;
     // the same loss behind the one-launch training step (forward + loss + dX chain in one weight stream)
-    const char* m = getenv("LINNA_TRAIN_MERGED");
     const char* b = getenv("LINNA_BWD_STREAM");
-    const bool okm = ok && n->stream_loss == 1 && !(m && m[0] == '0') && !(b && b[0] == '0') && nl >= 2 &&
-                     net_stream_tb_eligible(n->L.data(), nl, n->in_size, dn);
+    const NsPlan merged = ok && n->stream_loss == 1 && !(b && b[0] == '0') && nl >= 2 ? net_stream_plan(NS_TRAIN_STEP, n->L.data(), nl, n->in_size, &dn)
+                                                                                   : NsPlan{false, 0, false, nullptr};
     n->packed_tb.release();
     n->stream_tb = 0; n->as_merged = -1; n->as_state = -1;
-    if (okm && n->packed_tb.alloc(net_stream_tb_packed_floats(n->L.data(), nl, n->in_size, dn)) == LINNA_OK) n->stream_tb = 1;
+    if (merged.ok && n->packed_tb.alloc(merged.packed_floats) == LINNA_OK) n->stream_tb = 1;
 }
 // The one-launch training step serves this batch size (the 4-row engine only) -- decided the same way by every entry
 // that touches the training streams of a step (train_step, train_step_update, adamw_step)
@@ -527,36 +538,15 @@ static int net_train_merged_impl(linna_net_t* n, const linna_loss_desc_t* d, con
         set_error("net_train_step: bad arguments"); return LINNA_ERR_INVALID;
     }
     if (d->nout != n->out_size) { set_error("net_train_step: loss for %d outputs, network has %d", d->nout, n->out_size); return LINNA_ERR_INVALID; }
-    const int nl = (int)n->L.size();
-    const FwdLayout f = fwd_layout(n, B);
-    float* w = static_cast<float*>(fwd_ws);
-    float* bw = static_cast<float*>(bwd_ws);
     const int rows = net_stream_rows(B);
     const float* packed = nullptr;
-    TRY(stream_copy_refresh(n->packed_tb, n, rows, stream, &packed, 4, &n->loss_dn));
-    std::vector<float*> y(nl), t(nl), dprev(nl, nullptr), dt(nl, nullptr);
-    std::vector<const float*> hinp(nl, nullptr);
-    std::vector<int> ldy_(nl), ldt(nl), ldpv(nl, 0), ldhv(nl, 0), lddt(nl, 0);
-    for (int i = 0; i < nl; ++i) {
-        const bool last = i == nl - 1;
-        y[i] = last ? PRED : w + f.y_off[i]; ldy_[i] = last ? ldp : ld4(n->L[i].N);
-        t[i] = n->L[i].op == LINNA_OP_RESBLOCK ? w + f.t_off[i] : nullptr; ldt[i] = ld4(n->L[i].C);
-    }
-    float* cur = bw;
-    for (int i = nl - 1; i >= 1; --i) {                            // net_backward_impl's workspace walk (no input gradient)
-        const linna_layer_t& l = n->L[i];
-        dprev[i] = cur; ldpv[i] = ld4(l.K);
-        cur += (size_t)B * ld4(l.K);
-        const bool hin_relu = n->L[i - 1].op == LINNA_OP_RESBLOCK || n->L[i - 1].relu;
-        hinp[i] = hin_relu ? w + f.y_off[i - 1] : nullptr; ldhv[i] = ld4(n->L[i - 1].N);
-        if (l.op == LINNA_OP_RESBLOCK) { dt[i] = cur; lddt[i] = ld4(l.C); cur += (size_t)B * ld4(l.C); }
-    }
+    TRY(stream_copy_refresh(n->packed_tb, n, rows, stream, &packed, NS_TRAIN_STEP, &n->loss_dn));
+    const std::vector<NsOpBufs> ops = net_bufs(n, B, XB, ldxb, fwd_ws, PRED, ldp, bwd_ws);   // (no input gradient)
     const NsTrainLoss L{YN, ldyn, den, inv_batch, loss_rows, dPRED, lddp};
     const bool prep = hyper && step_dev;
     const NsPost post{nullptr, 0, 0.f, nullptr, prep ? step_dev : nullptr, prep ? hyper : nullptr, b1, b2};
-    return launch_net_stream_train_bwd(n->L.data(), nl, n->in_size, packed, X, ldx, ROWS, B, lg, xmean, xstd, XB, ldxb, y.data(),
-                                       ldy_.data(), t.data(), ldt.data(), L, n->loss_dn, dprev.data(), ldpv.data(), hinp.data(),
-                                       ldhv.data(), dt.data(), lddt.data(), rows, S(stream), prep ? &post : nullptr);
+    return launch_net_stream_train_bwd(n->L.data(), (int)n->L.size(), n->in_size, packed, X, ldx, ROWS, B, lg, xmean, xstd, XB, ldxb,
+                                       ops.data(), L, n->loss_dn, rows, S(stream), prep ? &post : nullptr);
 }
 // (the loss descriptor's stream state, as net_forward_loss_impl establishes it)
 static int net_train_ensure_loss(linna_net_t* n, const linna_loss_desc_t* d, void* stream) {
@@ -614,22 +604,14 @@ static int net_forward_loss_impl(linna_net_t* n, const linna_loss_desc_t* d, con
         net_ensure_loss(n, dn);
     }
     if (n->stream_loss != 1) { set_error("net_forward_loss: this network / loss does not run the whole-network kernel"); return LINNA_ERR_UNSUPPORTED; }
-    const FwdLayout f = fwd_layout(n, B);
-    float* w = static_cast<float*>(ws);
-    if (nl > 1 && !w) { set_error("net_forward_loss: workspace required"); return LINNA_ERR_INVALID; }
+    if (nl > 1 && !ws) { set_error("net_forward_loss: workspace required"); return LINNA_ERR_INVALID; }
     const int rows = net_stream_rows(B);
     const float* packed = nullptr;
-    TRY(stream_copy_refresh(n->packed_loss, n, rows, stream, &packed, 0, &n->loss_dn));
-    std::vector<float*> y(nl), t(nl);
-    std::vector<int> ldy_(nl), ldt(nl);
-    for (int i = 0; i < nl; ++i) {
-        const bool last = i == nl - 1;
-        y[i] = last ? PRED : w + f.y_off[i]; ldy_[i] = last ? ldp : ld4(n->L[i].N);
-        t[i] = n->L[i].op == LINNA_OP_RESBLOCK ? w + f.t_off[i] : nullptr; ldt[i] = ld4(n->L[i].C);
-    }
+    TRY(stream_copy_refresh(n->packed_loss, n, rows, stream, &packed, NS_TRAIN_FWD, &n->loss_dn));
+    const std::vector<NsOpBufs> ops = net_bufs(n, B, XB, ldxb, ws, PRED, ldp);
     const NsTrainLoss L{YN, ldyn, den, inv_batch, loss_rows, dPRED, lddp};
-    TRY(launch_net_stream_train(n->L.data(), nl, n->in_size, packed, X, ldx, ROWS, B, lg, xmean, xstd, XB, ldxb, y.data(),
-                                ldy_.data(), t.data(), ldt.data(), L, n->loss_dn, rows, S(stream)));
+    TRY(launch_net_stream_train(n->L.data(), nl, n->in_size, packed, X, ldx, ROWS, B, lg, xmean, xstd, XB, ldxb, ops.data(), L,
+                                n->loss_dn, rows, S(stream)));
     if (defer_post) return LINNA_OK;                 // linna_net_train_step: they ride in the backward's dX launch
     // the batch mean -- and, when the caller hands in its AdamW state, the step counter and bias corrections of the
     // update that will follow this step's backward (linna_adamw_step(prepared = 1)): two single-thread jobs, one launch
@@ -667,40 +649,26 @@ static int net_backward_impl(linna_net_t* n, const float* X, int ldx, int B, voi
                              int lddo, float* dX, int lddx, int pg, void* stream, const NsPost* post, const NetUpdate* upd,
                              bool dx_done, const GemmPost* gpost) {
     if (!n || !X || !dOUT || !bwd_ws || B < 1) { set_error("net_backward: bad arguments"); return LINNA_ERR_INVALID; }
-    const FwdLayout f = fwd_layout(n, B);
-    const float* w = static_cast<const float*>(fwd_ws);
-    float* bw = static_cast<float*>(bwd_ws);
+    const std::vector<NsOpBufs> ops = net_bufs(n, B, X, ldx, fwd_ws, nullptr, 0, bwd_ws, dX, lddx);
     const int nl = (int)n->L.size();
     hipStream_t st = S(stream);
 
-    // ---- auxiliary stream for the parameter gradients (off the dX critical path)
+    // ---- with a context: an auxiliary stream for the parameter gradients (off the dX critical path), and the dW GEMMs
+    // (1-128 tiles each, 251 together for ChtoModelv2(33,33)) collected and launched as ONE grid after the dX chain --
+    // 13 launches of ~18 us each on the auxiliary stream were the critical path of the step.  What does not fit that grid
+    // goes to the auxiliary stream as it becomes possible.
     linna_ctx* ctx = n->ctx;
-    bool overlap = false;
-    if (pg && ctx) {
-        if (ctx->overlap < 0) {
-            const char* e = getenv("LINNA_BWD_STREAMS");
-            ctx->overlap = (e && e[0] == '0') ? 0 : 1;
-        }
-        if (ctx->overlap == 1) {
-            if (!ctx->aux) TRY(check_hip(hipStreamCreateWithFlags(&ctx->aux, hipStreamNonBlocking), "hipStreamCreate"));
-            while ((int)ctx->events.size() < 2 * nl + 4) {
-                hipEvent_t e;
-                TRY(check_hip(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate"));
-                ctx->events.push_back(e);
-            }
-            overlap = true;
+    const bool overlap = pg && ctx;
+    if (overlap) {
+        if (!ctx->aux) TRY(check_hip(hipStreamCreateWithFlags(&ctx->aux, hipStreamNonBlocking), "hipStreamCreate"));
+        while ((int)ctx->events.size() < 2 * nl + 4) {
+            hipEvent_t e;
+            TRY(check_hip(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate"));
+            ctx->events.push_back(e);
         }
     }
     int next_event = 0;
     void* aux = overlap ? (void*)ctx->aux : stream;
-    // Parameter gradients: the bias column sums go to the auxiliary stream as they become possible; the dW GEMMs
-    // (1-128 tiles each, 251 together for ChtoModelv2(33,33)) are collected and launched as ONE grid after the
-    // dX chain -- 13 launches of ~18 us each on the auxiliary stream were the critical path of the step.
-    if (pg && ctx && ctx->group < 0) {
-        const char* e = getenv("LINNA_BWD_GROUP");
-        ctx->group = (e && e[0] == '0') ? 0 : 1;
-    }
-    const bool grouping = pg && ctx && ctx->group == 1;
     GemmGroupArgs grp;                  // the grouped parameter-gradient launch: descriptors by value, filled as we go
     grp.nprob = 0;
     GemmGroupArgsS grpu;                // ... and its form with the optimiser in the epilogue
@@ -737,7 +705,7 @@ static int net_backward_impl(linna_net_t* n, const float* X, int ldx, int B, voi
         set_pair(a, 0, dY, lddy, LAY_MN, Xin, ldxin, LAY_MN, B);
         a.M = N; a.N = K; a.C = dW; a.ldc = lddw; a.alpha0 = scale;
         if (upd) {
-            if (!(grouping && grpu.nprob < GEMM_UPD_MAX && gemm_group_ok(a))) { set_error("net_backward: update outside the grouped launch"); return LINNA_ERR_INVALID; }
+            if (!(overlap && grpu.nprob < GEMM_UPD_MAX && gemm_group_ok(a))) { set_error("net_backward: update outside the grouped launch"); return LINNA_ERR_INVALID; }
             const AsRange* rw = as_range_of(dW + pdiff, 0);
             const AsRange* rb = db ? as_range_of(db + pdiff, 1) : nullptr;
             if (!rw || (db && !rb)) { set_error("net_backward: update of a tensor outside the flat parameter buffer"); return LINNA_ERR_INVALID; }
@@ -748,7 +716,7 @@ static int net_backward_impl(linna_net_t* n, const float* X, int ldx, int B, voi
             grp_blocks += gemm_group_blocks(a);
             return LINNA_OK;
         }
-        if (grouping && grp.nprob < GEMM_GROUP_MAX && gemm_group_ok(a)) {
+        if (overlap && grp.nprob < GEMM_GROUP_MAX && gemm_group_ok(a)) {
             // one tile grid for every dW of the step; the bias gradient (column sums of dY) rides in the same tiles
             grp.p[grp.nprob++] = GemmGroupProb{dY, Xin, dW, db, lddy, ldxin, lddw, B, N, K, scale, grp_blocks};
             grp_blocks += gemm_group_blocks(a);
@@ -776,24 +744,8 @@ static int net_backward_impl(linna_net_t* n, const float* X, int ldx, int B, voi
         if (n->stream_bwd[wi] == 1 && sc.ready()) {
             const int rows = net_stream_rows(B);
             const float* packed = nullptr;
-            TRY(stream_copy_refresh(sc, n, rows, stream, &packed, 1 + wi));
-            std::vector<float*> dprev(nl, nullptr), dt(nl, nullptr);
-            std::vector<const float*> hinp(nl, nullptr), tp(nl, nullptr);
-            std::vector<int> ldpv(nl, 0), ldhv(nl, 0), lddt(nl, 0), ldtv(nl, 0);
-            float* cur = bw;
-            for (int i = nl - 1; i >= (wi ? 0 : 1); --i) {                 // the same workspace walk as the loop below
-                const linna_layer_t& l = n->L[i];
-                dprev[i] = (i == 0) ? dX : cur; ldpv[i] = (i == 0) ? lddx : ld4(l.K);
-                if (i > 0) cur += (size_t)B * ld4(l.K);
-                const bool hin_relu = (i > 0) && (n->L[i - 1].op == LINNA_OP_RESBLOCK || n->L[i - 1].relu);
-                hinp[i] = hin_relu ? w + f.y_off[i - 1] : nullptr; ldhv[i] = (i == 0) ? ldx : ld4(n->L[i - 1].N);
-                if (l.op == LINNA_OP_RESBLOCK) {
-                    dt[i] = cur; lddt[i] = ld4(l.C); cur += (size_t)B * ld4(l.C);
-                    tp[i] = w + f.t_off[i]; ldtv[i] = ld4(l.C);
-                }
-            }
-            TRY(launch_net_stream_dx(n->L.data(), nl, n->in_size, packed, dOUT, lddo, B, dprev.data(), ldpv.data(), hinp.data(),
-                                     ldhv.data(), dt.data(), lddt.data(), tp.data(), ldtv.data(), wi, rows, st, post));
+            TRY(stream_copy_refresh(sc, n, rows, stream, &packed, wi ? NS_DX_INPUT : NS_DX));
+            TRY(launch_net_stream_dx(n->L.data(), nl, n->in_size, packed, dOUT, lddo, B, ops.data(), wi, rows, st, post));
             fused_dx = true;
         }
     }
@@ -803,18 +755,14 @@ static int net_backward_impl(linna_net_t* n, const float* X, int ldx, int B, voi
         else if (post->step) TRY(launch_adamw_prepare(post->hyper, post->step, post->b1, post->b2, st));
     }
     const float* dcur = dOUT; int ldd = lddo;
-    float* cursor = bw;
     for (int i = nl - 1; i >= 0; --i) {
         const linna_layer_t& l = n->L[i];
-        const float* hin = (i == 0) ? X : w + f.y_off[i - 1];
-        const int ldh = (i == 0) ? ldx : ld4(n->L[i - 1].N);
+        const float* hin = ops[i].x;
+        const int ldh = ops[i].ldx;
         const bool need_dx = (i > 0) || (dX != nullptr);
-        float* dprev = (i == 0) ? dX : cursor;
-        const int ldp = (i == 0) ? lddx : ld4(l.K);
-        if (i > 0) cursor += (size_t)B * ld4(l.K);
-        // hin went through a ReLU iff the producing op is a resblock or a linear with relu
-        const bool hin_relu = (i > 0) && (n->L[i - 1].op == LINNA_OP_RESBLOCK || n->L[i - 1].relu);
-        const float* mask = hin_relu ? hin : nullptr;
+        float* dprev = ops[i].dprev;
+        const int ldp = ops[i].ldp;
+        const float* mask = ops[i].gate;
         if (l.op == LINNA_OP_LINEAR) {
             if (pg) {                // dW, db need only dcur (already produced on st) and hin
                 TRY(param_grads(dcur, ldd, hin, ldh, l.gW, ld4(l.K), l.gb, l.K, l.N, 1.f));
@@ -834,10 +782,9 @@ static int net_backward_impl(linna_net_t* n, const float* X, int ldx, int B, voi
                 TRY(gemm_launch(a, st));
             }
         } else {
-            const float* T = w + f.t_off[i];
-            const int ldt = ld4(l.C);
-            float* dT = cursor;
-            cursor += (size_t)B * ldt;
+            const float* T = ops[i].t;
+            const int ldt = ops[i].ldt;
+            float* dT = ops[i].dt;
             if (!fused_dx) {   // dT = 0.1 * (dcur W2) * (T > 0)
                 GemmArgs a = gemm_zero();
                 set_pair(a, 0, dcur, ldd, LAY_K, l.W2, ld4(l.C), LAY_MN, l.N);
@@ -922,6 +869,7 @@ struct linna_logprob {
     int precision = LINNA_PRECISION_FP32;    // linna_logprob_set_precision
     StreamCopy packed_bf;                    // the bf16 weight streams (allocated when bf16 is first set, laid out lazily)
     bool bf16() const { return precision == LINNA_PRECISION_BF16; }
+    NsKind kind() const { return bf16() ? NS_SERVE_BF16 : dense_fused ? NS_SERVE_DENSE : NS_SERVE; }   // the serving program
 };
 
 struct LpLayout { size_t x0, fwd, d, part, dh, bwd, dx, total; int slots; };
@@ -948,20 +896,20 @@ static bool fused_enabled() {
     static const bool on = !(getenv("LINNA_DISABLE_FUSED") && getenv("LINNA_DISABLE_FUSED")[0] == '1');
     return on;
 }
-static int stream_copy_refresh(StreamCopy& sc, const linna_net* n, int rows, void* stream, const float** out, int prog,
-                               const NsDense* dn, int serve) {
+static int stream_copy_refresh(StreamCopy& sc, const linna_net* n, int rows, void* stream, const float** out, NsKind kind,
+                               const NsDense* dn) {
     const int k = rows < 16 ? 1 : 0;
     const unsigned long long epoch = g_weights_epoch.load();
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(S(stream), &cap);
-    const std::vector<linna_layer_t>& LL = prog == 0 || prog == NS_PROG_BF16_CODE ? n->Lfull : n->L;     // (the forward programs carry the input skip)
+    const std::vector<linna_layer_t>& LL = ns_kind_full_layers(kind) ? n->Lfull : n->L;
     if (cap != hipStreamCaptureStatusNone) {
         // a captured launch carries its own re-layout, so that every replay sees the weights of that
         // moment; the copy is not valid for direct launches until they redo it
-        TRY(launch_net_stream_pack(LL.data(), (int)LL.size(), n->in_size, sc.buf[k], rows, prog, dn, S(stream), serve));
+        TRY(launch_net_stream_pack(kind, LL.data(), (int)LL.size(), n->in_size, sc.buf[k], rows, dn, S(stream)));
         sc.epoch[k] = 0;
     } else if (sc.epoch[k] != epoch) {
-        TRY(launch_net_stream_pack(LL.data(), (int)LL.size(), n->in_size, sc.buf[k], rows, prog, dn, S(stream), serve));
+        TRY(launch_net_stream_pack(kind, LL.data(), (int)LL.size(), n->in_size, sc.buf[k], rows, dn, S(stream)));
         sc.epoch[k] = epoch;
     }
     *out = sc.buf[k];
@@ -970,16 +918,28 @@ static int stream_copy_refresh(StreamCopy& sc, const linna_net* n, int rows, voi
 // The copy the engine for `B` rows reads, re-laid if the weights moved since it was made; *rows: that engine.
 static int lp_refresh_stream(linna_logprob* lp, int B, void* stream, const float** packed, int* rows) {
     *rows = net_stream_rows(B);
-    if (lp->bf16()) return stream_copy_refresh(lp->packed_bf, lp->net, *rows, stream, packed, NS_PROG_BF16_CODE, nullptr, 1);
     const NsDense dn = lp->dense();
-    return stream_copy_refresh(lp->packed, lp->net, *rows, stream, packed, 0, lp->dense_fused ? &dn : nullptr, 1);   // serve: SIDE segments on the 16-row engine
+    return stream_copy_refresh(lp->bf16() ? lp->packed_bf : lp->packed, lp->net, *rows, stream, packed, lp->kind(),
+                               lp->kind() == NS_SERVE_DENSE ? &dn : nullptr);
+}
+// One launch of the serving program on the copy for `rows`: the descriptor's prior map, input transform, output map and
+// likelihood (the dense program carries the output map and the covariance in its stream); the rest is what the entries vary.
+static int lp_launch(const linna_logprob* lp, const float* packed, int rows, const float* Z, int ldz, int B, float* lnP, float* D,
+                     int ldd, float* TH, int ldt, const NsMove* mv, const NsGrad* gr, const int* gate, void* stream) {
+    const linna_logprob_desc_t& d = lp->d;
+    const linna_net* n = lp->net;
+    const NsDense dn = lp->dense();
+    const bool df = lp->kind() == NS_SERVE_DENSE;
+    return launch_net_stream(lp->kind(), n->Lfull.data(), (int)n->Lfull.size(), n->in_size, packed, Z, ldz, B, d.nin, d.is_flat, d.a1,
+                             d.a2, d.log10_flag, d.xmean, d.xstd, df ? nullptr : d.outmap.cscale, df ? nullptr : d.outmap.cshift,
+                             df ? nullptr : d.w, d.temperature, lnP, D, ldd, TH, ldt, mv, gr, gate, rows, df ? &dn : nullptr, S(stream),
+                             d.outmap.cexp ? d.outmap.cpost : nullptr, d.outmap.cexp ? d.outmap.cshift2 : nullptr);
 }
 
 static int lp_forward(linna_logprob* lp, const float* Z, int ldz, int B, float* w, const LpLayout& L, float* lnP,
                       float* TH, int ldt, void* stream, bool keep_activations, const int* gate = nullptr) {
     const linna_logprob_desc_t& d = lp->d;
     const int ldx = ld4(d.nin), ldd = ld4(d.nout);
-    const linna_net* n = lp->net;
     if (lp->bf16()) {
         // bf16 runs the whole-network kernel or nothing: never silently fp32
         if (keep_activations || !fused_enabled() || !lp->packed_bf.ready() || !d.w || (d.outmap.cexp && (!d.outmap.cpost || !d.outmap.cshift2))) {
@@ -988,28 +948,17 @@ static int lp_forward(linna_logprob* lp, const float* Z, int ldz, int B, float* 
         }
         const float* packed = nullptr; int rows = 16;
         TRY(lp_refresh_stream(lp, B, stream, &packed, &rows));
-        return launch_net_stream(n->Lfull.data(), (int)n->Lfull.size(), n->in_size, packed, Z, ldz, B, d.nin, d.is_flat, d.a1, d.a2,
-                                 d.log10_flag, d.xmean, d.xstd, d.outmap.cscale, d.outmap.cshift, d.w, d.temperature, lnP, nullptr, 0,
-                                 TH, ldt, nullptr, nullptr, gate, rows, nullptr, S(stream), d.outmap.cexp ? d.outmap.cpost : nullptr,
-                                 d.outmap.cexp ? d.outmap.cshift2 : nullptr, 1);
+        return lp_launch(lp, packed, rows, Z, ldz, B, lnP, nullptr, 0, TH, ldt, nullptr, nullptr, gate, stream);
     }
     if (!keep_activations && fused_enabled() && lp->packed.ready() && (!d.outmap.cexp || (d.outmap.cpost && d.outmap.cshift2 && !lp->dense_fused))) {
         // whole-network kernel (net_stream.hip): prior map -> every layer -> output transform -> diagonal
         // log-likelihood in ONE launch, weights streamed from the fragment-order copy
         const float* packed = nullptr; int rows = 16;
         TRY(lp_refresh_stream(lp, B, stream, &packed, &rows));
-        if (lp->dense_fused) {
-            // dense covariance: the output map is folded into the stream's last layer and the inverse covariance is its
-            // last segment -- lnP comes out of the same launch
-            const NsDense dn = lp->dense();
-            return launch_net_stream(n->Lfull.data(), (int)n->Lfull.size(), n->in_size, packed, Z, ldz, B, d.nin, d.is_flat, d.a1, d.a2,
-                                     d.log10_flag, d.xmean, d.xstd, nullptr, nullptr, nullptr, d.temperature, lnP, nullptr, 0,
-                                     TH, ldt, nullptr, nullptr, gate, rows, &dn, S(stream));
-        }
-        TRY(launch_net_stream(n->Lfull.data(), (int)n->Lfull.size(), n->in_size, packed, Z, ldz, B, d.nin, d.is_flat, d.a1, d.a2,
-                              d.log10_flag, d.xmean, d.xstd, d.outmap.cscale, d.outmap.cshift, d.w, d.temperature,
-                              d.w ? lnP : nullptr, d.w ? nullptr : w + L.d, ldd, TH, ldt, nullptr, nullptr, gate, rows, nullptr,
-                              S(stream), d.outmap.cexp ? d.outmap.cpost : nullptr, d.outmap.cexp ? d.outmap.cshift2 : nullptr));
+        // dense covariance: the output map is folded into the stream's last layer and the inverse covariance is its last
+        // segment -- lnP comes out of the same launch
+        if (lp->dense_fused) return lp_launch(lp, packed, rows, Z, ldz, B, lnP, nullptr, 0, TH, ldt, nullptr, nullptr, gate, stream);
+        TRY(lp_launch(lp, packed, rows, Z, ldz, B, d.w ? lnP : nullptr, d.w ? nullptr : w + L.d, ldd, TH, ldt, nullptr, nullptr, gate, stream));
         if (d.w) return LINNA_OK;
         return loglike_dense_impl(w + L.d, ldd, B, d.nout, d.Sfac ? d.Sfac : d.S, d.lds, d.Sfac != nullptr, Z, ldz, d.nin, d.temperature,
                                          w + L.part, lnP, stream);
@@ -1038,17 +987,19 @@ int linna_logprob_create(linna_ctx_t* ctx, linna_net_t* net, const linna_logprob
     const NsDense dn = lp->dense();
     const bool want_dense = !desc->w && desc->S && !desc->outmap.cexp &&
                             !(getenv("LINNA_DENSE_FUSED") && getenv("LINNA_DENSE_FUSED")[0] == '0');
-    if (want_dense && net_stream_dense_eligible(net->Lfull.data(), (int)net->Lfull.size(), net->in_size, dn)) {
+    const NsPlan dense = want_dense ? net_stream_plan(NS_SERVE_DENSE, net->Lfull.data(), (int)net->Lfull.size(), net->in_size, &dn)
+                                    : NsPlan{false, 0, false, nullptr};
+    const NsPlan serve = net_stream_plan(NS_SERVE, net->Lfull.data(), (int)net->Lfull.size(), net->in_size);
+    if (dense.ok) {
         lp->dense_fused = true;
-        if (lp->packed.alloc(net_stream_dense_packed_floats(net->Lfull.data(), (int)net->Lfull.size(), net->in_size, dn)) != LINNA_OK) {
+        if (lp->packed.alloc(dense.packed_floats) != LINNA_OK) {
             set_error("logprob_create: hipMalloc(weight stream) failed");
             delete lp; return LINNA_ERR_HIP;
         }
-    } else if (net_stream_eligible(net->Lfull.data(), (int)net->Lfull.size(), net->in_size)) {
-        const size_t nf = net_stream_packed_floats(net->Lfull.data(), (int)net->Lfull.size(), net->in_size);
-        lp->grad_fused = net_stream_has_grad(net->Lfull.data(), (int)net->Lfull.size(), net->in_size) && !desc->outmap.cexp &&
+    } else if (serve.ok) {
+        lp->grad_fused = serve.grad_ok && !desc->outmap.cexp &&
                          !(getenv("LINNA_DISABLE_FUSED_GRAD") && getenv("LINNA_DISABLE_FUSED_GRAD")[0] == '1');
-        if (lp->packed.alloc(nf) != LINNA_OK) {
+        if (lp->packed.alloc(serve.packed_floats) != LINNA_OK) {
             set_error("logprob_create: hipMalloc(weight stream) failed");
             delete lp; return LINNA_ERR_HIP;
         }
@@ -1056,9 +1007,9 @@ int linna_logprob_create(linna_ctx_t* ctx, linna_net_t* net, const linna_logprob
     // lnP + gradient in one launch for the networks the MLP-only fused gradient does not cover (residual blocks, SPLIT
     // segments): forward program + dX chain in one weight stream, gates from the activations the same launch stored
     if (!lp->grad_fused && desc->w && desc->gscale && !desc->outmap.cexp && !net->has_inskip &&
-        !(getenv("LINNA_DISABLE_FUSED_GRAD") && getenv("LINNA_DISABLE_FUSED_GRAD")[0] == '1') &&
-        net_stream_dxi_eligible(net->L.data(), (int)net->L.size(), net->in_size)) {
-        if (lp->packed_g2.alloc(net_stream_dxi_packed_floats(net->L.data(), (int)net->L.size(), net->in_size)) == LINNA_OK) lp->grad2 = true;
+        !(getenv("LINNA_DISABLE_FUSED_GRAD") && getenv("LINNA_DISABLE_FUSED_GRAD")[0] == '1')) {
+        const NsPlan g2 = net_stream_plan(NS_GRAD_INPUT, net->L.data(), (int)net->L.size(), net->in_size);
+        if (g2.ok && lp->packed_g2.alloc(g2.packed_floats) == LINNA_OK) lp->grad2 = true;
     }
     *out = lp;
     return LINNA_OK;
@@ -1080,12 +1031,12 @@ int linna_logprob_set_precision(linna_logprob_t* lp, int precision) try {
     if (precision == LINNA_PRECISION_FP32) { lp->precision = precision; return LINNA_OK; }
     const linna_net* n = lp->net;
     if (!lp->d.w) { set_error("logprob_set_precision: bf16 needs a diagonal likelihood (a dense covariance is served in fp32 only)"); return LINNA_ERR_UNSUPPORTED; }
-    const char* why = nullptr;
-    if (!net_stream_bf16_eligible(n->Lfull.data(), (int)n->Lfull.size(), n->in_size, &why)) {
-        set_error("logprob_set_precision: no bf16 engine for this network: %s", why ? why : "not eligible");
+    const NsPlan bf = net_stream_plan(NS_SERVE_BF16, n->Lfull.data(), (int)n->Lfull.size(), n->in_size);
+    if (!bf.ok) {
+        set_error("logprob_set_precision: no bf16 engine for this network: %s", bf.why ? bf.why : "not eligible");
         return LINNA_ERR_UNSUPPORTED;
     }
-    if (!lp->packed_bf.ready() && lp->packed_bf.alloc(net_stream_bf16_packed_floats(n->Lfull.data(), (int)n->Lfull.size(), n->in_size)) != LINNA_OK) {
+    if (!lp->packed_bf.ready() && lp->packed_bf.alloc(bf.packed_floats) != LINNA_OK) {
         set_error("logprob_set_precision: hipMalloc(bf16 weight stream) failed");
         return LINNA_ERR_HIP;
     }
@@ -1103,10 +1054,11 @@ int linna_program_describe(const linna_layer_t* layers, int nlayers, int in_size
     for (int i = 1; i < nlayers; ++i) CHECK_STRUCT(layers + i, linna_layer_t, "program_describe");
     // (pointers are only compared, never read: a placeholder stands for the dense inverse covariance)
     static float dummy;
-    if (dense_nout == -1) return net_stream_describe(layers, nlayers, in_size, 3, nullptr, rows, 1, buf, n);   // the one-launch gradient's program
+    if (dense_nout == -1) return net_stream_describe(NS_GRAD_INPUT, layers, nlayers, in_size, nullptr, rows, buf, n);   // the one-launch gradient's program
     const int dn_cols = dense_nout < -1 ? -dense_nout : dense_nout;         // < -1: the factored form (chi^2 = |d L|^2) of -dense_nout columns
     NsDense dn{&dummy, (dn_cols + 3) & ~3, nullptr, nullptr, dense_nout < -1 ? 1 : 0, net_stream_dense_tri(-1)};
-    return net_stream_describe(layers, nlayers, in_size, 0, dn_cols > 0 ? &dn : nullptr, rows, 1, buf, n);
+    if (dn_cols > 0) return net_stream_describe(NS_SERVE_DENSE, layers, nlayers, in_size, &dn, rows, buf, n);
+    return net_stream_describe(NS_SERVE, layers, nlayers, in_size, nullptr, rows, buf, n);
 } LINNA_CATCH_INT
 int linna_dense_tri(int mode) try {
     if (mode < -1 || mode > 2) { set_error("linna_dense_tri: %d (-1 query, 0, 1 or 2)", mode); return LINNA_ERR_INVALID; }
@@ -1170,20 +1122,13 @@ static int lp_eval_slice_points(linna_logprob_t* lp, const float* coords, int ld
     }
     const float* packed = nullptr; int rows = 16;
     TRY(lp_refresh_stream(lp, b_engine > 0 ? b_engine : nrep * ns, stream, &packed, &rows));
-    const linna_net* n = lp->net;
     NsMove mv{const_cast<float*>(coords), ldc, nullptr, S_idx, w, 0, list, ns, 0ull, count, mul, 0, 0.f, nullptr, 1};
     mv.sb = sb;
     if (sd) {
         mv.sl_Z0 = sd->Z0; mv.sl_L = sd->L; mv.sl_R = sd->R; mv.sl_Zt = sd->Ze; mv.sl_m = sd->m; mv.sl_nt = sd->nt;
         mv.sl_seed = sd->seed; mv.sl_step = sd->step_dev; mv.sl_stream = sd->stream_id; mv.sl_flags = sd->flags;
     }
-    const NsDense dn = lp->dense();
-    const bool df = lp->dense_fused;
-    return launch_net_stream(n->Lfull.data(), (int)n->Lfull.size(), n->in_size, packed, DIR, ldd, nrep * ns, d.nin, d.is_flat, d.a1,
-                             d.a2, d.log10_flag, d.xmean, d.xstd, df ? nullptr : d.outmap.cscale, df ? nullptr : d.outmap.cshift,
-                             df ? nullptr : d.w, d.temperature, lnP, nullptr, 0, nullptr, 0, &mv, nullptr, gate, rows,
-                             df ? &dn : nullptr, S(stream), d.outmap.cexp ? d.outmap.cpost : nullptr,
-                             d.outmap.cexp ? d.outmap.cshift2 : nullptr);
+    return lp_launch(lp, packed, rows, DIR, ldd, nrep * ns, lnP, nullptr, 0, nullptr, 0, &mv, nullptr, gate, stream);
 }
 int linna_logprob_eval_slice_points(linna_logprob_t* lp, const float* coords, int ldc, int ndim, const int* S_idx, int ns,
                                     const float* DIR, int ldd, const float* w, int nrep, float* lnP, const int* gate,
@@ -1279,15 +1224,8 @@ int linna_stretch_half_step(linna_logprob_t* lp, float* coords, int ldc, int ndi
     }
     const float* packed = nullptr; int rows = 16;
     TRY(lp_refresh_stream(lp, ns, stream, &packed, &rows));
-    const linna_net* n = lp->net;
     NsMove mv{coords, ldc, logp, S_idx, ccoords, ldcc, C_idx, nc, seed, step_dev, step_offset, stream_id, a, naccept, 0};
-    const NsDense dn = lp->dense();
-    const bool df = lp->dense_fused;
-    return launch_net_stream(n->Lfull.data(), (int)n->Lfull.size(), n->in_size, packed, nullptr, 0, ns, d.nin, d.is_flat, d.a1,
-                             d.a2, d.log10_flag, d.xmean, d.xstd, df ? nullptr : d.outmap.cscale, df ? nullptr : d.outmap.cshift,
-                             df ? nullptr : d.w, d.temperature, nullptr, nullptr, 0, nullptr, 0, &mv, nullptr, nullptr, rows,
-                             df ? &dn : nullptr, S(stream), d.outmap.cexp ? d.outmap.cpost : nullptr,
-                             d.outmap.cexp ? d.outmap.cshift2 : nullptr, lp->bf16() ? 1 : 0);
+    return lp_launch(lp, packed, rows, nullptr, 0, ns, nullptr, nullptr, 0, nullptr, 0, &mv, nullptr, nullptr, stream);
 } LINNA_CATCH_INT
 
 
@@ -1308,19 +1246,12 @@ int linna_stretch_run(linna_logprob_t* lp, float* coords, int ldc, int ndim, flo
     const int ns = nw / 2;
     const float* packed = nullptr; int rows = 16;
     TRY(lp_refresh_stream(lp, ns, stream, &packed, &rows));
-    const linna_net* n = lp->net;
-    const NsDense dn = lp->dense();
-    const bool df = lp->dense_fused;
     for (int i = 0; i < nsteps; ++i) {
         const int* sp = splits + (size_t)i * split_stride;
         for (int h = 0; h < 2; ++h) {
             NsMove mv{coords, ldc, logp, sp + h * ns, coords, ldc, sp + (1 - h) * ns, ns, seed, step_dev, step_offset + i, h, a, naccept, 0};
             if (chain) { mv.chain = chain + (size_t)i * nw * ndim; mv.lps = logps + (size_t)i * nw; }
-            TRY(launch_net_stream(n->Lfull.data(), (int)n->Lfull.size(), n->in_size, packed, nullptr, 0, ns, d.nin, d.is_flat, d.a1,
-                                  d.a2, d.log10_flag, d.xmean, d.xstd, df ? nullptr : d.outmap.cscale, df ? nullptr : d.outmap.cshift,
-                                  df ? nullptr : d.w, d.temperature, nullptr, nullptr, 0, nullptr, 0, &mv, nullptr, nullptr, rows,
-                                  df ? &dn : nullptr, S(stream), d.outmap.cexp ? d.outmap.cpost : nullptr,
-                                  d.outmap.cexp ? d.outmap.cshift2 : nullptr, lp->bf16() ? 1 : 0));
+            TRY(lp_launch(lp, packed, rows, nullptr, 0, ns, nullptr, nullptr, 0, nullptr, 0, &mv, nullptr, nullptr, stream));
         }
     }
     return LINNA_OK;
@@ -1379,41 +1310,27 @@ static int logprob_grad_impl(linna_logprob_t* lp, const float* Z, int ldz, int B
     const linna_logprob_desc_t& d = lp->d;
     if (d.outmap.cexp) { set_error("logprob_grad: ypositive (exp) output map has no gradient path"); return LINNA_ERR_UNSUPPORTED; }
     if (!d.gscale || (!d.w && !d.Ssym)) { set_error("logprob_grad: descriptor lacks gscale / Ssym"); return LINNA_ERR_INVALID; }
+    NsGrad gr{d.gscale, G, ldg, nullptr, 0, nullptr, nullptr, 0.f, 0.f};
+    if (leap) { gr.hm_p = leap->hm_p; gr.hm_ldp = leap->hm_ldp; gr.hm_q = leap->hm_q; gr.hm_mass = leap->hm_mass; gr.hm_ek = leap->hm_ek; gr.hm_ed = leap->hm_ed; }
     if (fused_enabled() && lp->packed.ready() && lp->grad_fused && d.w) {
         // lnP and d lnP / d z in ONE launch: forward segments, turnaround, backward segments over W^T (net_stream.hip)
         const float* packed = nullptr; int rows = 16;
         TRY(lp_refresh_stream(lp, B, stream, &packed, &rows));
-        const linna_net* n = lp->net;
-        NsGrad gr{d.gscale, G, ldg, nullptr, 0, nullptr, nullptr, 0.f, 0.f};
-        if (leap) { gr.hm_p = leap->hm_p; gr.hm_ldp = leap->hm_ldp; gr.hm_q = leap->hm_q; gr.hm_mass = leap->hm_mass; gr.hm_ek = leap->hm_ek; gr.hm_ed = leap->hm_ed; }
-        return launch_net_stream(n->Lfull.data(), (int)n->Lfull.size(), n->in_size, packed, Z, ldz, B, d.nin, d.is_flat, d.a1, d.a2,
-                                 d.log10_flag, d.xmean, d.xstd, d.outmap.cscale, d.outmap.cshift, d.w, d.temperature, lnP,
-                                 nullptr, 0, nullptr, 0, nullptr, &gr, nullptr, rows, nullptr, S(stream));
+        return lp_launch(lp, packed, rows, Z, ldz, B, lnP, nullptr, 0, nullptr, 0, nullptr, &gr, nullptr, stream);
     }
     const LpLayout L = lp_layout(lp, B, 1);
     float* w = static_cast<float*>(ws);
     const int ldx = ld4(d.nin), ldd = ld4(d.nout);
     if (fused_enabled() && lp->grad2 && lp->packed_g2.ready() && d.w) {
-        // ONE launch for any network: forward segments (activations kept in the workspace), turnaround, dX chain down to
-        // the input, prior map's derivative (net_stream.hip, GRAD + STORE == 2) -- six launches otherwise
-        linna_net* n = lp->net;
-        const int nl = (int)n->L.size();
+        // ONE launch for any network: forward segments (the signs the gates need kept as bits in LDS), turnaround, dX chain
+        // down to the input, prior map's derivative (net_stream.hip, GRAD + STORE == 2) -- six launches otherwise
+        const linna_net* n = lp->net;
         const int rows = net_stream_rows(B);
         const float* packed = nullptr;
-        TRY(stream_copy_refresh(lp->packed_g2, n, rows, stream, &packed, 3));
-        const FwdLayout f = fwd_layout(n, B);
-        float* base = w + L.fwd;
-        std::vector<float*> y(nl, nullptr), t(nl, nullptr);
-        std::vector<int> ldy(nl, 0), ldt(nl, 0);
-        for (int i = 0; i < nl; ++i) {
-            if (i < nl - 1) { y[i] = base + f.y_off[i]; ldy[i] = ld4(n->L[i].N); }
-            if (n->L[i].op == LINNA_OP_RESBLOCK) { t[i] = base + f.t_off[i]; ldt[i] = ld4(n->L[i].C); }
-        }
-        NsGrad gr{d.gscale, G, ldg, nullptr, 0, nullptr, nullptr, 0.f, 0.f};
-        if (leap) { gr.hm_p = leap->hm_p; gr.hm_ldp = leap->hm_ldp; gr.hm_q = leap->hm_q; gr.hm_mass = leap->hm_mass; gr.hm_ek = leap->hm_ek; gr.hm_ed = leap->hm_ed; }
-        return launch_net_stream_grad2(n->L.data(), nl, n->in_size, packed, Z, ldz, B, d.nin, d.is_flat, d.a1, d.a2, d.log10_flag,
-                                       d.xmean, d.xstd, d.outmap.cscale, d.outmap.cshift, d.w, d.temperature, lnP, gr, y.data(),
-                                       ldy.data(), t.data(), ldt.data(), rows, S(stream));
+        TRY(stream_copy_refresh(lp->packed_g2, n, rows, stream, &packed, NS_GRAD_INPUT));
+        return launch_net_stream_grad2(n->L.data(), (int)n->L.size(), n->in_size, packed, Z, ldz, B, d.nin, d.is_flat, d.a1, d.a2,
+                                       d.log10_flag, d.xmean, d.xstd, d.outmap.cscale, d.outmap.cshift, d.w, d.temperature, lnP, gr,
+                                       rows, S(stream));
     }
     TRY(lp_forward(lp, Z, ldz, B, w, L, lnP, nullptr, 0, stream, true));
     if (d.w) {
@@ -1543,9 +1460,8 @@ int linna_adamw_step(linna_ctx_t*, float* p, const float* g, float* m, float* v,
 // two streams, or `params[n]` is not exactly its tensors back to back: the caller then uses linna_adamw_step.
 // The placement tables of the flat parameter buffer `p[n]` in the two training streams (net_stream_adamw_args), cached.
 static int net_ensure_as_args(linna_net_t* net, int B, const float* p, size_t n) {
-    static const bool off = getenv("LINNA_ADAMW_STREAMS") && getenv("LINNA_ADAMW_STREAMS")[0] == '0';
     const int merged = net_tb_usable(net, B) ? 1 : 0;
-    if (off || net->stream_loss != 1 || (!merged && (net->stream_bwd[0] != 1 || !net->packed_loss.ready() || !net->packed_dx[0].ready()))) {
+    if (net->stream_loss != 1 || (!merged && (net->stream_bwd[0] != 1 || !net->packed_loss.ready() || !net->packed_dx[0].ready()))) {
         set_error("the network does not train through the whole-network streams"); return LINNA_ERR_UNSUPPORTED;
     }
     const int rows = net_stream_rows(B), k = rows < 16 ? 1 : 0;
@@ -1569,10 +1485,10 @@ int linna_net_adamw_step(linna_net_t* net, int B, float* p, const float* g, floa
     const float* dummy = nullptr;
     const bool merged = net->as_merged == 1;
     if (merged) {
-        TRY(stream_copy_refresh(net->packed_tb, net, rows, stream, &dummy, 4, &net->loss_dn));
+        TRY(stream_copy_refresh(net->packed_tb, net, rows, stream, &dummy, NS_TRAIN_STEP, &net->loss_dn));
     } else {
-        TRY(stream_copy_refresh(net->packed_loss, net, rows, stream, &dummy, 0, &net->loss_dn));
-        TRY(stream_copy_refresh(net->packed_dx[0], net, rows, stream, &dummy, 1, nullptr));
+        TRY(stream_copy_refresh(net->packed_loss, net, rows, stream, &dummy, NS_TRAIN_FWD, &net->loss_dn));
+        TRY(stream_copy_refresh(net->packed_dx[0], net, rows, stream, &dummy, NS_DX));
     }
     if (!prepared) TRY(launch_adamw_prepare(hyper, step_dev, b1, b2, S(stream)));
     TRY(launch_adamw_streams(net->as_args, p, g, m, v, hyper, b1, b2, eps, S(stream)));
@@ -1600,16 +1516,13 @@ int linna_net_train_step_update(linna_net_t* net, const linna_loss_desc_t* d, co
     if (!net || !params || !m || !v || !hyper || !step_dev || !bwd_ws || B < 1) { set_error("net_train_step_update: bad arguments"); return LINNA_ERR_INVALID; }
     if (!d) { set_error("net_train_step_update: null loss descriptor"); return LINNA_ERR_INVALID; }
     CHECK_STRUCT(d, linna_loss_desc_t, "net_train_step_update");
-    static const bool off = getenv("LINNA_ADAMW_IN_GEMM") && getenv("LINNA_ADAMW_IN_GEMM")[0] == '0';
-    if (off || net->has_inskip) { set_error("net_train_step_update: switched off / input-skip network"); return LINNA_ERR_UNSUPPORTED; }
+    if (net->has_inskip) { set_error("net_train_step_update: input-skip network"); return LINNA_ERR_UNSUPPORTED; }
     TRY(net_train_ensure_loss(net, d, stream));
     TRY(net_ensure_as_args(net, B, params, n));
     if (net->upd_state < 0 || net->upd_B != B) {
         // every parameter gradient of the step must be a problem of the grouped launch, and the gradient pointers of the layer
         // table must mirror the parameter buffer (same distance for every tensor)
-        linna_ctx* ctx = net->ctx;
-        if (ctx && ctx->group < 0) { const char* e = getenv("LINNA_BWD_GROUP"); ctx->group = (e && e[0] == '0') ? 0 : 1; }
-        bool ok = ctx && ctx->group == 1;
+        bool ok = net->ctx != nullptr;         // (the grouped launch needs a context)
         int nprob = 0;
         long long diff = 0; bool have = false;
         auto same = [&](const float* w, const float* g) { if (!w) return; if (!g) { ok = false; return; } if (!have) { diff = w - g; have = true; } else if (w - g != diff) ok = false; };

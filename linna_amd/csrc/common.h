@@ -387,32 +387,42 @@ struct NsDense { const float* S; int lds; const float* cscale; const float* cshi
                  int tri = 2; };         // how the factor's zero upper triangle is skipped (net_stream_dense_tri): 0 not, 1 short second pass, 2 balanced blocks
 // process-wide default of NsDense::tri for log-probability objects created afterwards (LINNA_DENSE_TRI); returns the previous value
 int net_stream_dense_tri(int mode);
-// net_stream.hip (program-driven whole-network kernel: residual blocks, widths up to 1024)
-bool net_stream_eligible(const linna_layer_t* layers, int nl, int in_size);
-size_t net_stream_packed_floats(const linna_layer_t* layers, int nl, int in_size);
+// net_stream.hip (program-driven whole-network kernel: residual blocks, widths up to 1024).  The programs it runs, one
+// weight stream each:
+enum NsKind {
+    NS_SERVE,          // log-probability: prior map, network, output map, diagonal likelihood (+ the fused MLP gradient)
+    NS_SERVE_DENSE,    // ... with the output map folded into the last layer and the dense inverse covariance (NsDense) behind it
+    NS_SERVE_BF16,     // the opt-in bf16 serving engine (linna_logprob_set_precision): diagonal likelihood, no gradient
+    NS_STORE,          // training / validation forward: every op's output stored for the backward
+    NS_TRAIN_FWD,      // training forward + chi^2-ratio loss (NsDense: the loss's inverse covariance)
+    NS_DX,             // the dX chain of a training step: ops nl-1..1
+    NS_DX_INPUT,       // ... down to op 0
+    NS_GRAD_INPUT,     // forward + dX chain down to the input: lnP and its gradient in one launch, any network it covers
+    NS_TRAIN_STEP,     // forward + loss + dX chain down to op 1: the merged training step (4-row engine)
+};
+// the serving programs are built from the layer list with the trailing input skip, the training ones from the list without
+inline bool ns_kind_full_layers(NsKind k) { return k == NS_SERVE || k == NS_SERVE_DENSE || k == NS_SERVE_BF16; }
+// Planning query (no GPU): ok: the network has this program (NS_GRAD_INPUT: and its sign-bit gates fit the LDS;
+// NS_TRAIN_STEP: with the dX chain); packed_floats: the size of a copy of its weight stream, for every engine; grad_ok: the
+// serving program holds the fused MLP gradient; why: NS_SERVE_BF16's reason when it is refused.
+struct NsPlan { bool ok; size_t packed_floats; bool grad_ok; const char* why; };
+NsPlan net_stream_plan(NsKind kind, const linna_layer_t* layers, int nl, int in_size, const NsDense* dn = nullptr);
 // rows per workgroup for a batch of B rows: 16 (v_mfma_f32_16x16x4_f32), or 8 / 4 (v_mfma_f32_4x4x1_16b_f32) when 16-row
 // workgroups would leave CUs idle.  The 16-row engine and the small ones read different orders of the weight stream.
 int net_stream_rows(int B);
 int net_stream_force_rows(int rows);   // 0 automatic, 4 / 8 / 16 forced; returns the previous setting, -1 for an invalid value
-int launch_net_stream_pack(const linna_layer_t* layers, int nl, int in_size, float* packed, int rows, int prog,
-                           const NsDense* dn, hipStream_t s, int serve = 0);      // prog 0 + dn: the forward program with the dense segment
-bool net_stream_dense_eligible(const linna_layer_t* layers, int nl, int in_size, const NsDense& dn);
-int net_stream_describe(const linna_layer_t* layers, int nl, int in_size, int prog, const NsDense* dn, int rows, int serve, char* buf,
-                        size_t n);
-size_t net_stream_dense_packed_floats(const linna_layer_t* layers, int nl, int in_size, const NsDense& dn);
-// the dX chain of a training step as a program of the same kernel (prog 1: ops nl-1..1, prog 2: down to op 0)
-bool net_stream_dx_eligible(const linna_layer_t* layers, int nl, int in_size, int with_input);
-size_t net_stream_dx_packed_floats(const linna_layer_t* layers, int nl, int in_size, int with_input);
+int launch_net_stream_pack(NsKind kind, const linna_layer_t* layers, int nl, int in_size, float* packed, int rows, const NsDense* dn,
+                           hipStream_t s);
+int net_stream_describe(NsKind kind, const linna_layer_t* layers, int nl, int in_size, const NsDense* dn, int rows, char* buf, size_t n);
+// Where a training step's activations and their gradients live, per op (api.hip: net_bufs): y its output, t the hidden h
+// of a residual block, x its input and `gate` = x where x went through a ReLU (else null; leading dimension ldx); dprev
+// d/d(op input), dt d/dh of a residual block.
+struct NsOpBufs { float* y; int ldy; float* t; int ldt; const float* x; int ldx; const float* gate; float* dprev; int ldp; float* dt; int lddt; };
 // A small job that rides in the dX-chain launch as one extra workgroup (linna_net_train_step): the batch mean of the loss
 // rows (out = scale * sum rows[n], sum_scale_prepare_kernel's order) and AdamW's step counter / bias corrections
 struct NsPost { const float* rows; int n; float scale; float* out; int* step; float* hyper; float b1, b2; };
-struct NsTrainLoss;
-bool net_stream_tb_eligible(const linna_layer_t* layers, int nl, int in_size, const NsDense& dn);
-size_t net_stream_tb_packed_floats(const linna_layer_t* layers, int nl, int in_size, const NsDense& dn);
 int launch_net_stream_dx(const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* dOUT, int lddo,
-                         int B, float* const* dprev, const int* ldp, const float* const* hin, const int* ldh,
-                         float* const* dt, const int* lddt, const float* const* t, const int* ldt, int with_input, int rows,
-                         hipStream_t s, const NsPost* post = nullptr);
+                         int B, const NsOpBufs* ops, int with_input, int rows, hipStream_t s, const NsPost* post = nullptr);
 // sampler moves fused around the evaluation.  slice == 0: stretch half step, rows of the batch are the walkers
 // S[0..B).  slice == 1: rows are the slice sampler's trial points coords[S[k]] + cc[row] * DIR[k], k = row % nc
 // (DIR is passed as the launch's Z / ldz; cc = w[nrep * ns], nc = ns; nothing is written back).
@@ -430,22 +440,19 @@ struct NsMove {
 };
 // training / validation forward: every op's output stored for the backward (STORE instantiation)
 int launch_net_stream_store(const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* X, int ldx,
-                            int B, float* const* y, const int* ldy, float* const* t, const int* ldt, const float* cscale,
-                            const float* cshift, int rows, hipStream_t s);
+                            int B, const NsOpBufs* ops, const float* cscale, const float* cshift, int rows, hipStream_t s);
 // training forward + chi^2-ratio loss in one launch (STORE == 3)
 struct NsTrainLoss { const float* YN; int ldyn;      // normalised targets of the whole set, NaN where masked
                      const float* den; float inv_batch; float* loss_rows; float* dP; int lddp; };
 int launch_loss_targets(const float* Y, int ldy, int n, const linna_loss_desc_t& d, float* YN, int ldyn, hipStream_t s);
 int launch_net_stream_train(const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* X, int ldx,
                             const int* ROWS, int B, const int* lg, const float* xmean, const float* xstd, float* XB, int ldxb,
-                            float* const* y, const int* ldy, float* const* t, const int* ldt, const NsTrainLoss& L,
-                            const NsDense& dn, int rows, hipStream_t s);
-// the same followed by the dX chain down to op 1 in the SAME launch (GRAD + STORE == 3; prog 4)
+                            const NsOpBufs* ops, const NsTrainLoss& L, const NsDense& dn, int rows, hipStream_t s);
+// the same followed by the dX chain down to op 1 in the SAME launch (GRAD + STORE == 3; NS_TRAIN_STEP)
 int launch_net_stream_train_bwd(const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* X, int ldx,
                                 const int* ROWS, int B, const int* lg, const float* xmean, const float* xstd, float* XB, int ldxb,
-                                float* const* y, const int* ldy, float* const* t, const int* ldt, const NsTrainLoss& L,
-                                const NsDense& dn, float* const* dprev, const int* ldp, const float* const* hin, const int* ldh,
-                                float* const* dt, const int* lddt, int rows, hipStream_t s, const NsPost* post);
+                                const NsOpBufs* ops, const NsTrainLoss& L, const NsDense& dn, int rows, hipStream_t s,
+                                const NsPost* post);
 // gradient fused behind the evaluation (plain ReLU MLPs, diagonal covariance): G = d lnP / d z
 // hm_*: a leapfrog kick and drift riding in the gradient's finish (HMCSampler.py:35-49): P += ek G; Q += ed P / mass, Q the
 // launch's own input rows (hm_p == nullptr: none)
@@ -481,25 +488,17 @@ int net_stream_adamw_args(const linna_layer_t* layers, int nl, int in_size, int 
                           float* s_fwd, const NsDense* dn, float* s_dx, AsArgs* out, int merged = 0);
 int launch_adamw_streams(const AsArgs& a, float* p, const float* g, float* m, float* v, const float* hyper, float b1, float b2,
                          float eps, hipStream_t s);
-bool net_stream_has_grad(const linna_layer_t* layers, int nl, int in_size);
-// forward + dX chain down to the input in one stream (any network both programs cover; diagonal covariance)
-bool net_stream_dxi_eligible(const linna_layer_t* layers, int nl, int in_size);
-size_t net_stream_dxi_packed_floats(const linna_layer_t* layers, int nl, int in_size);
+// forward + dX chain down to the input in one launch (NS_GRAD_INPUT; diagonal covariance)
 int launch_net_stream_grad2(const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* Z, int ldz, int B,
                             int nin, const int* is_flat, const float* a1, const float* a2, const int* lg, const float* xmean,
                             const float* xstd, const float* cscale, const float* cshift, const float* w, float T, float* lnP,
-                            const NsGrad& gr, float* const* y, const int* ldy, float* const* t, const int* ldt, int rows,
-                            hipStream_t s);
-int launch_net_stream(const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* Z, int ldz, int B,
+                            const NsGrad& gr, int rows, hipStream_t s);
+// a serving launch (kind NS_SERVE, NS_SERVE_DENSE with dn, or NS_SERVE_BF16)
+int launch_net_stream(NsKind kind, const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* Z, int ldz, int B,
                       int nin, const int* is_flat, const float* a1, const float* a2, const int* lg, const float* xmean,
                       const float* xstd, const float* cscale, const float* cshift, const float* w, float T, float* lnP,
                       float* D, int ldd, float* TH, int ldt, const NsMove* mv, const NsGrad* gr, const int* gate, int rows,
-                      const NsDense* dn, hipStream_t s, const float* cpost = nullptr, const float* cshift2 = nullptr, int bf = 0);
-// the opt-in bf16 serving engine (linna_logprob_set_precision): its program (pack / launch with prog NS_PROG_BF16_CODE and
-// bf = 1) exists for the networks below; *why: the reason when it does not
-constexpr int NS_PROG_BF16_CODE = 5;
-bool net_stream_bf16_eligible(const linna_layer_t* layers, int nl, int in_size, const char** why);
-size_t net_stream_bf16_packed_floats(const linna_layer_t* layers, int nl, int in_size);
+                      const NsDense* dn, hipStream_t s, const float* cpost = nullptr, const float* cshift2 = nullptr);
 
 // autocorr.hip: convergence statistics of a walker chain (running lagged products, emcee's estimator, checkmeanstd's moments)
 int launch_chain_append_t(const float* block, int ldb, int nsteps, int nw, int ndim, int wstride, float* CT, int nwp,

@@ -1623,16 +1623,10 @@ int net_stream_dense_tri(int mode) {
     return prev;
 }
 
-// Translate the op list into segments; ok = false when something does not fit this kernel.
+// Translate the op list into segments; ok = false when something does not fit this kernel.  The builder's modes (the
+// programs of NsKind are built from these in ns_build_kind):
 enum { NS_PROG_FWD = 0, NS_PROG_FWD_NOGRAD = 1, NS_PROG_DX = 2, NS_PROG_DX_INPUT = 3, NS_PROG_FWD_DENSE = 4, NS_PROG_FWD_DXI = 5,
        NS_PROG_TRAIN = 6 };   // TRAIN: forward + loss segment (FWD_DENSE with the loss's inverse covariance) followed by the dX chain down to op 1
-static NsProgram ns_build_one(const linna_layer_t* layers, int nl, int in_size, int mode, const NsDense* dn = nullptr, bool k4 = false,
-                              bool bf = false);
-static NsProgram ns_build(const linna_layer_t* layers, int nl, int in_size, bool k4 = false) {
-    NsProgram p = ns_build_one(layers, nl, in_size, NS_PROG_FWD, nullptr, k4);
-    if (!p.ok) p = ns_build_one(layers, nl, in_size, NS_PROG_FWD_NOGRAD, nullptr, k4);      // the backward half may be what did not fit
-    return p;
-}
 // mode NS_PROG_DX: the dX chain of a training step as a program of its own (linna_net_backward's order): the rows are
 // d loss / d output, the segments run over the transposed weights from the last op down to op 1 (NS_PROG_DX_INPUT: op 0).
 // A residual block y = relu(0.1 (W2 h + b2) + Ws x), h = relu(W1 x + b1) comes back as  dh = 0.1 (dy W2) [h > 0],
@@ -1642,10 +1636,11 @@ static NsProgram ns_build(const linna_layer_t* layers, int nl, int in_size, bool
 // layer's weights and bias, and the dense inverse covariance appended as one more bias-free segment U = d S -- the
 // Gaussian log-likelihood (util.py:953-955) with a dense covariance then needs no GEMM launch of its own.
 // k4: SPLIT segments of <= 32 columns become SIDE segments where they fit (see NsPackArgs): the kernel's K4 path, i.e. the
-// serving instantiations of the 16-row engine only.
+// 16-row engine of the programs ns_side names.
 // bf: the bf16 serving program (NS_PROG_FWD_NOGRAD only, no dense segment, no SIDE segments): a step is 32 k, and the
 // first layer (a plain linear map) is [W | W] over K' = 2 nin -- its input rows are x_hi = bf16(x) and x_lo = x - x_hi.
-static NsProgram ns_build_one(const linna_layer_t* layers, int nl, int in_size, int mode, const NsDense* dn, bool k4, bool bf) {
+static NsProgram ns_build_one(const linna_layer_t* layers, int nl, int in_size, int mode, const NsDense* dn = nullptr,
+                              bool k4 = false, bool bf = false) {
     NsProgram p;
     if (bf && (mode != NS_PROG_FWD_NOGRAD || dn || k4)) return p;
     const int KS = bf ? 32 : 16;                            // k per step
@@ -1924,26 +1919,6 @@ static NsProgram ns_build_one(const linna_layer_t* layers, int nl, int in_size, 
     return p;
 }
 
-static const NsProgram& ns_build_prog(const linna_layer_t* layers, int nl, int in_size, int prog, const NsDense* dn = nullptr, bool k4 = false);
-bool net_stream_eligible(const linna_layer_t* layers, int nl, int in_size) { return ns_build_prog(layers, nl, in_size, 0, nullptr).ok; }
-bool net_stream_bf16_eligible(const linna_layer_t* layers, int nl, int in_size, const char** why) {
-    const char* r = nullptr;
-    int width = 0;
-    for (int i = 0; i < nl; ++i) width = std::max(width, std::max(layers[i].N, layers[i].op == LINNA_OP_RESBLOCK ? layers[i].C : 0));
-    if (in_size > 256) r = "more than 256 network inputs: outside the whole-network kernel";
-    else if (width > 1024) r = "a layer wider than 1024: outside the whole-network kernel";
-    else if (nl < 1 || layers[0].op != LINNA_OP_LINEAR) r = "the first op is not a linear layer (the bf16 input split needs one)";
-    else if (!ns_build_prog(layers, nl, in_size, NS_PROG_BF16_CODE, nullptr).ok) r = "the network does not fit the bf16 program of the whole-network kernel";
-    if (why) *why = r;
-    return r == nullptr;
-}
-size_t net_stream_bf16_packed_floats(const linna_layer_t* layers, int nl, int in_size) {
-    return ns_build_prog(layers, nl, in_size, NS_PROG_BF16_CODE, nullptr).packed_floats;
-}
-size_t net_stream_packed_floats(const linna_layer_t* layers, int nl, int in_size) {
-    return ns_build_prog(layers, nl, in_size, 0, nullptr).packed_floats;
-}
-
 // Engine for a batch of B rows: the fewest rows per workgroup that still fit the batch into one workgroup per CU
 // (linna_engine_rows forces one for tests and measurements; LINNA_NS_ROWS in the environment sets the initial value,
 // read ONCE -- the launch path reads an atomic, not the environment).
@@ -1977,47 +1952,47 @@ int net_stream_rows(int B) {
     return B <= 4 * ncu ? 4 : B <= 8 * ncu ? 8 : 16;
 }
 
-// SIDE segments: serving launches (linna_logprob_*, the fused sampler moves) on the 16-row engine; LINNA_NS_K4=0 turns them off
-bool net_stream_k4(int rows, int serve) {
-    static const bool on = !(getenv("LINNA_NS_K4") && getenv("LINNA_NS_K4")[0] == '0');
-    return on && serve && rows == 16;
+// SIDE segments (the kernel's K4 path) run on the 16-row engine of the serving programs and the one-launch gradient.  In the
+// gradient's forward half they were measured slower in round 3 (with the activations stored for the gates); with the gates
+// as sign bits in LDS and the per-segment tables read through the kernel-argument segment (without that the instantiation
+// spilled 2.5 KB per lane): 151.4 -> 148.7 us at ChtoModelv2(33,33), 4096 chains (NOTES R4).  Not in bf16.
+static bool ns_side(NsKind kind, int rows) {
+    return rows == 16 && (kind == NS_SERVE || kind == NS_SERVE_DENSE || kind == NS_GRAD_INPUT);
 }
 
-// SIDE segments in the forward half of the one-launch gradient (16-row engine).  Round 3 measured them slower there (with the
-// activations stored for the gates); with the gates as sign bits in LDS and the per-segment tables read through the
-// kernel-argument segment (without that the instantiation spilled 2.5 KB per lane): 151.4 -> 148.7 us at ChtoModelv2(33,33),
-// 4096 chains (NOTES R4).  LINNA_G2_SIDE=0 turns them off.
-bool net_stream_g2_side() {
-    static const bool on = !(getenv("LINNA_G2_SIDE") && getenv("LINNA_G2_SIDE")[0] == '0');
-    return on;
-}
-
-static NsProgram ns_build_prog_uncached(const linna_layer_t* layers, int nl, int in_size, int prog, const NsDense* dn, bool k4) {
-    if (k4 && prog == 3) {
-        NsProgram p = ns_build_one(layers, nl, in_size, NS_PROG_FWD_DXI, nullptr, true);
-        if (p.ok && p.dxi_ok) return p;
+static NsProgram ns_build_kind(NsKind kind, const linna_layer_t* layers, int nl, int in_size, const NsDense* dn, bool side) {
+    NsProgram p;
+    switch (kind) {
+    case NS_SERVE: case NS_STORE:
+        p = ns_build_one(layers, nl, in_size, NS_PROG_FWD, nullptr, side);
+        if (!p.ok) p = ns_build_one(layers, nl, in_size, NS_PROG_FWD_NOGRAD, nullptr, side);   // the backward half may be what did not fit
+        break;
+    case NS_SERVE_DENSE: case NS_TRAIN_FWD: p = ns_build_one(layers, nl, in_size, NS_PROG_FWD_DENSE, dn, side); break;
+    case NS_SERVE_BF16: p = ns_build_one(layers, nl, in_size, NS_PROG_FWD_NOGRAD, dn, false, true); break;
+    case NS_DX: p = ns_build_one(layers, nl, in_size, NS_PROG_DX); break;
+    case NS_DX_INPUT: p = ns_build_one(layers, nl, in_size, NS_PROG_DX_INPUT); break;
+    case NS_GRAD_INPUT: p = ns_build_one(layers, nl, in_size, NS_PROG_FWD_DXI, nullptr, side); break;
+    case NS_TRAIN_STEP: p = ns_build_one(layers, nl, in_size, NS_PROG_TRAIN, dn); break;
     }
-    if (k4 && prog == 0) {                     // the serving programs of the 16-row engine; the plain program where this one does not fit
-        NsProgram p = dn ? ns_build_one(layers, nl, in_size, NS_PROG_FWD_DENSE, dn, true) : ns_build(layers, nl, in_size, true);
-        if (p.ok) return p;
-    }
-    if (prog == NS_PROG_BF16_CODE) return dn ? NsProgram() : ns_build_one(layers, nl, in_size, NS_PROG_FWD_NOGRAD, nullptr, false, true);
-    if (prog == 0 && dn) return ns_build_one(layers, nl, in_size, NS_PROG_FWD_DENSE, dn);
-    if (prog == 3) return ns_build_one(layers, nl, in_size, NS_PROG_FWD_DXI);
-    if (prog == 4) return ns_build_one(layers, nl, in_size, NS_PROG_TRAIN, dn);
-    return prog == 0 ? ns_build(layers, nl, in_size) : ns_build_one(layers, nl, in_size, prog == 2 ? NS_PROG_DX_INPUT : NS_PROG_DX);
+    // the SIDE program where it fits, the plain one otherwise
+    if (side && !(p.ok && (kind != NS_GRAD_INPUT || p.dxi_ok))) return ns_build_kind(kind, layers, nl, in_size, dn, false);
+    return p;
 }
 // Kernel-configuration cache: a program is a pure function of the op list (shapes AND parameter pointers:
-// the pack descriptors carry them), the program kind and the dense descriptor, so it is built once and looked up by
-// those bytes on every later launch -- no segment planning, no vector allocation on the launch path.  Entries live for
-// the life of the library (a handful per network; the table is cleared if it ever reaches 256 entries).
-static const NsProgram& ns_build_prog(const linna_layer_t* layers, int nl, int in_size, int prog, const NsDense* dn, bool k4) {
+// the pack descriptors carry them), the program kind, the engine (SIDE segments or not) and the dense descriptor, so it
+// is built once and looked up by those bytes on every later launch -- no segment planning, no vector allocation on the
+// launch path.  Entries live for the life of the library (a handful per network; the table is cleared if it ever reaches
+// 256 entries).  A lookup hands out shared ownership: a clear by a later lookup never frees a program a caller still
+// holds.  rows: the engine that runs it (0: any; no SIDE segments).
+typedef std::shared_ptr<const NsProgram> NsProgramRef;
+static NsProgramRef ns_program(NsKind kind, const linna_layer_t* layers, int nl, int in_size, const NsDense* dn, int rows) {
     static std::mutex mu;
-    static std::unordered_map<std::string, std::unique_ptr<NsProgram>> cache;
+    static std::unordered_map<std::string, NsProgramRef> cache;
+    const bool side = ns_side(kind, rows);
     std::string key;
     key.reserve((size_t)nl * sizeof(linna_layer_t) + 64);
     key.append(reinterpret_cast<const char*>(layers), (size_t)nl * sizeof(linna_layer_t));
-    const int hdr[4] = {nl, in_size, prog, k4 ? 1 : 0};
+    const int hdr[4] = {nl, in_size, (int)kind, side ? 1 : 0};
     key.append(reinterpret_cast<const char*>(hdr), sizeof(hdr));
     if (dn) {                                               // field by field: the struct has padding bytes
         const void* const ptrs[3] = {dn->S, dn->cscale, dn->cshift};
@@ -2028,16 +2003,82 @@ static const NsProgram& ns_build_prog(const linna_layer_t* layers, int nl, int i
     }
     std::lock_guard<std::mutex> lock(mu);
     auto it = cache.find(key);
-    if (it != cache.end()) return *it->second;
+    if (it != cache.end()) return it->second;
     if (cache.size() >= 256) cache.clear();
-    auto ins = cache.emplace(std::move(key), std::unique_ptr<NsProgram>(new NsProgram(ns_build_prog_uncached(layers, nl, in_size, prog, dn, k4))));
-    return *ins.first->second;
+    NsProgramRef p = std::make_shared<const NsProgram>(ns_build_kind(kind, layers, nl, in_size, dn, side));
+    cache.emplace(std::move(key), p);
+    return p;
 }
-static int ns_g2_cols(const NsProgram& p, const linna_layer_t* layers, int nl);
+
+// columns of what segment i of a one-launch forward + backward program (NS_GRAD_INPUT, NS_TRAIN_STEP) writes: the hidden h
+// of a residual block, a forward op's output, or (the backward half) d/d(op input)
+static int ns_seg_cols(const NsProgram& p, const linna_layer_t* layers, int i) {
+    const linna_layer_t& l = layers[p.seg_op[i]];
+    return p.seg_hidden[i] ? l.C : i < p.nseg_f ? l.N : l.K;
+}
+// The gates of a one-launch backward half (NS_GRAD_INPUT, NS_TRAIN_STEP): what the backward gates on is the SIGN of a
+// forward activation, and the workgroup that needs it is the one that computed it -- one bit per (row, column) in LDS
+// behind the program's own LDS (NsArgs::nbw, bits_off).  gbit[i]: the first bit column of forward segment i's signs (-1:
+// no gate asks for them; every tensor rounded up to 64 columns); mbit[i]: the columns backward segment i gates on (-1:
+// none).  ok = false when a gate has no producer.
+struct NsGates {
+    int gbit[NS_MAXSEG], mbit[NS_MAXSEG];
+    int ncols = 0;
+    bool ok = true;
+    size_t lds0 = 0, lds = 0;                               // the program's LDS (8-byte aligned), and with the bits
+};
+static NsGates ns_gates(const NsProgram& p, const linna_layer_t* layers, int nl, int rows) {
+    NsGates g;
+    for (int i = 0; i < NS_MAXSEG; ++i) g.gbit[i] = g.mbit[i] = -1;
+    for (int i = 0; i < p.nseg_f; ++i) {                    // forward: keep the signs a gate will ask for
+        const int op = p.seg_op[i];
+        if (op >= nl || (!p.seg_hidden[i] && op == nl - 1)) continue;   // the loss segment and the network output gate nothing
+        g.gbit[i] = g.ncols;
+        g.ncols += (ns_seg_cols(p, layers, i) + 63) & ~63;
+    }
+    for (int i = p.nseg_f; i < (int)p.seg.size(); ++i) {
+        // d/dh of a residual block: gated by its h; d/d(input of op): by the producing op's output, if it went through a ReLU
+        const int op = p.seg_op[i];
+        const bool hidden = p.seg_hidden[i] != 0;
+        if (!hidden && !(op > 0 && (layers[op - 1].op == LINNA_OP_RESBLOCK || layers[op - 1].relu))) continue;
+        const int src = hidden ? op : op - 1;
+        for (int j = 0; j < p.nseg_f; ++j)
+            if (p.seg_op[j] == src && (p.seg_hidden[j] != 0) == hidden) g.mbit[i] = g.gbit[j];
+        if (g.mbit[i] < 0) g.ok = false;
+    }
+    g.lds0 = (p.lds_for(rows, true) + 7) & ~(size_t)7;
+    g.lds = g.lds0 + (size_t)rows * (g.ncols / 32) * sizeof(unsigned);
+    return g;
+}
+
+// why the bf16 program does not exist for this network (null: it does)
+static const char* ns_bf16_refusal(const NsProgram& p, const linna_layer_t* layers, int nl, int in_size) {
+    int width = 0;
+    for (int i = 0; i < nl; ++i) width = std::max(width, std::max(layers[i].N, layers[i].op == LINNA_OP_RESBLOCK ? layers[i].C : 0));
+    if (in_size > 256) return "more than 256 network inputs: outside the whole-network kernel";
+    if (width > 1024) return "a layer wider than 1024: outside the whole-network kernel";
+    if (nl < 1 || layers[0].op != LINNA_OP_LINEAR) return "the first op is not a linear layer (the bf16 input split needs one)";
+    if (!p.ok) return "the network does not fit the bf16 program of the whole-network kernel";
+    return nullptr;
+}
+NsPlan net_stream_plan(NsKind kind, const linna_layer_t* layers, int nl, int in_size, const NsDense* dn) {
+    const NsProgramRef pref = ns_program(kind, layers, nl, in_size, dn, 0);
+    const NsProgram& p = *pref;
+    NsPlan r{p.ok, p.packed_floats, p.grad_ok, nullptr};
+    if (kind == NS_TRAIN_STEP) r.ok = p.ok && p.train_ok;
+    if (kind == NS_GRAD_INPUT) {
+        r.ok = p.ok && p.dxi_ok && ns_gates(p, layers, nl, NS_ROWS).lds <= (size_t)NS_LDS_BYTES;
+        // one copy serves every engine: the 16-row one reads the SIDE program
+        r.packed_floats = std::max(r.packed_floats, ns_program(kind, layers, nl, in_size, dn, 16)->packed_floats);
+    }
+    if (kind == NS_SERVE_BF16) { r.why = ns_bf16_refusal(p, layers, nl, in_size); r.ok = r.why == nullptr; }
+    return r;
+}
+
 // Text form of a program (tests, diagnostics): one line per segment, "type steps passes ncg kc dst_col zext".
-int net_stream_describe(const linna_layer_t* layers, int nl, int in_size, int prog, const NsDense* dn, int rows, int serve, char* buf,
-                        size_t n) {
-    const NsProgram& p = ns_build_prog(layers, nl, in_size, prog, dn, (prog == 0 && net_stream_k4(rows, serve)) || (prog == 3 && rows == 16 && net_stream_g2_side()));
+int net_stream_describe(NsKind kind, const linna_layer_t* layers, int nl, int in_size, const NsDense* dn, int rows, char* buf, size_t n) {
+    const NsProgramRef pref = ns_program(kind, layers, nl, in_size, dn, rows);
+    const NsProgram& p = *pref;
     std::string out = p.ok ? "ok" : "not eligible";
     char line[160];
     snprintf(line, sizeof line, " G %d Gstride %d nseg_f %d LD %d kpad0 %d packed_floats %zu grad %d\n", p.G, p.Gstride, p.nseg_f, p.LD,
@@ -2050,40 +2091,20 @@ int net_stream_describe(const linna_layer_t* layers, int nl, int in_size, int pr
                  g.zext, p.pack[i].N);
         out += line;
     }
-    if (p.ok && prog == 3) {                        // the one-launch gradient: its LDS with the sign-bit matrix, on the 16-row engine
-        const int cols = ns_g2_cols(p, layers, nl);
-        const size_t need = ((p.lds_for(NS_ROWS, true) + 7) & ~(size_t)7) + (size_t)NS_ROWS * (cols / 32) * sizeof(unsigned);
-        snprintf(line, sizeof line, "lds %zu of %d bytes with %d sign-bit columns: %s\n", need, NS_LDS_BYTES, cols,
-                 need <= (size_t)NS_LDS_BYTES && p.dxi_ok ? "one launch" : "layered");
+    if (p.ok && kind == NS_GRAD_INPUT) {            // the one-launch gradient: its LDS with the sign-bit matrix, on the 16-row engine
+        const NsGates g = ns_gates(p, layers, nl, NS_ROWS);
+        snprintf(line, sizeof line, "lds %zu of %d bytes with %d sign-bit columns: %s\n", g.lds, NS_LDS_BYTES, g.ncols,
+                 g.lds <= (size_t)NS_LDS_BYTES && p.dxi_ok ? "one launch" : "layered");
         out += line;
     }
     if (buf && n) { snprintf(buf, n, "%s", out.c_str()); }
     return p.ok ? (int)p.seg.size() : 0;
 }
-bool net_stream_dense_eligible(const linna_layer_t* layers, int nl, int in_size, const NsDense& dn) {
-    return ns_build_prog(layers, nl, in_size, 0, &dn).ok;
-}
-size_t net_stream_dense_packed_floats(const linna_layer_t* layers, int nl, int in_size, const NsDense& dn) {
-    return ns_build_prog(layers, nl, in_size, 0, &dn).packed_floats;
-}
-bool net_stream_tb_eligible(const linna_layer_t* layers, int nl, int in_size, const NsDense& dn) {
-    const NsProgram& p = ns_build_prog(layers, nl, in_size, 4, &dn);
-    return p.ok && p.train_ok;
-}
-size_t net_stream_tb_packed_floats(const linna_layer_t* layers, int nl, int in_size, const NsDense& dn) {
-    return ns_build_prog(layers, nl, in_size, 4, &dn).packed_floats;
-}
-bool net_stream_dx_eligible(const linna_layer_t* layers, int nl, int in_size, int with_input) {
-    return nl >= (with_input ? 1 : 2) && ns_build_prog(layers, nl, in_size, with_input ? 2 : 1).ok;
-}
-size_t net_stream_dx_packed_floats(const linna_layer_t* layers, int nl, int in_size, int with_input) {
-    return ns_build_prog(layers, nl, in_size, with_input ? 2 : 1).packed_floats;
-}
 
-// prog: 0 the forward program (+ the fused gradient's backward half), 1 / 2 the dX chain without / with op 0
-int launch_net_stream_pack(const linna_layer_t* layers, int nl, int in_size, float* packed, int rows, int prog,
-                           const NsDense* dn, hipStream_t s, int serve) {
-    const NsProgram& p = ns_build_prog(layers, nl, in_size, prog, dn, (prog == 0 && net_stream_k4(rows, serve)) || (prog == 3 && rows == 16 && net_stream_g2_side()));
+int launch_net_stream_pack(NsKind kind, const linna_layer_t* layers, int nl, int in_size, float* packed, int rows, const NsDense* dn,
+                           hipStream_t s) {
+    const NsProgramRef pref = ns_program(kind, layers, nl, in_size, dn, rows);
+    const NsProgram& p = *pref;
     if (!p.ok) { set_error("net_stream: network not eligible"); return LINNA_ERR_UNSUPPORTED; }
     NsPackArgs a;
     ::memset(static_cast<void*>(&a), 0, sizeof(a));
@@ -2241,14 +2262,16 @@ __global__ __launch_bounds__(AS_BLOCK) void adamw_streams_kernel(AsArgs a, float
 }
 
 // Descriptor table of adamw_streams_kernel for the flat buffer `params[nflat]` the layers' parameters live in, the
-// forward(+loss) stream `s_fwd` (program 0 with `dn`) and the dX-chain stream `s_dx` (program 1).  LINNA_ERR_UNSUPPORTED
+// forward + loss stream `s_fwd` (NS_TRAIN_FWD with `dn`) and the dX-chain stream `s_dx` (NS_DX).  LINNA_ERR_UNSUPPORTED
 // when the buffer is not exactly the layers' tensors back to back, or a stream folds something into the weights that
 // an element-wise scatter cannot reproduce (output maps, a second bias).
 int net_stream_adamw_args(const linna_layer_t* layers, int nl, int in_size, int rows, const float* params, size_t nflat,
                           float* s_fwd, const NsDense* dn, float* s_dx, AsArgs* out, int merged) {
-    // merged: ONE stream holds the forward + loss segments [0, nseg_f) and the dX chain [nseg_f, nseg) (NS_PROG_TRAIN)
-    const NsProgram& pf = merged ? ns_build_prog(layers, nl, in_size, 4, dn) : ns_build_prog(layers, nl, in_size, 0, dn);
-    const NsProgram& pd = merged ? pf : ns_build_prog(layers, nl, in_size, 1);
+    // merged: ONE stream holds the forward + loss segments [0, nseg_f) and the dX chain [nseg_f, nseg) (NS_TRAIN_STEP)
+    const NsProgramRef pf_ref = ns_program(merged ? NS_TRAIN_STEP : NS_TRAIN_FWD, layers, nl, in_size, dn, rows);
+    const NsProgramRef pd_ref = merged ? pf_ref : ns_program(NS_DX, layers, nl, in_size, nullptr, rows);
+    const NsProgram& pf = *pf_ref;
+    const NsProgram& pd = *pd_ref;
     if (merged) s_dx = s_fwd;
     if (!pf.ok || !pd.ok || !s_fwd || !s_dx || (merged && !pf.train_ok)) { set_error("adamw_streams: no forward / dX-chain program"); return LINNA_ERR_UNSUPPORTED; }
     const size_t f_lo = 0, f_hi = merged ? (size_t)pf.nseg_f : pf.pack.size();
@@ -2335,33 +2358,57 @@ int launch_adamw_streams(const AsArgs& a, float* p, const float* g, float* m, fl
     return check_hip(hipGetLastError(), "adamw_streams launch");
 }
 
-bool net_stream_has_grad(const linna_layer_t* layers, int nl, int in_size) { return ns_build_prog(layers, nl, in_size, 0).grad_ok; }
-// bit columns of the one-launch gradient's sign matrix: every tensor a gate asks for, each rounded up to 64 columns
-static int ns_g2_cols(const NsProgram& p, const linna_layer_t* layers, int nl) {
-    int n = 0;
-    for (int i = 0; i < p.nseg_f; ++i) {
+// The launch header every program shares: rows Z[B][ldz] of nin columns, the weight stream and the program's steps and
+// segment table.  full: the whole program (forward and backward halves), else its forward segments only.
+static NsArgs ns_args(const NsProgram& p, const float* packed, const float* Z, int ldz, int B, int nin, bool full) {
+    NsArgs a;
+    ::memset(static_cast<void*>(&a), 0, sizeof(a));
+    a.Z = Z; a.ldz = ldz; a.B = B; a.nin = nin;
+    a.packed = packed;
+    a.Gstride = p.Gstride; a.nseg_f = p.nseg_f;
+    a.G = full ? p.Gstride : p.G;
+    a.nseg = full ? (int)p.seg.size() : p.nseg_f;
+    a.LD = p.LD; a.kpad0 = p.kpad0; a.nout = p.nout; a.bias_total = p.bias_total;
+    a.T = 1.f;
+    for (int i = 0; i < (int)p.seg.size(); ++i) a.seg[i] = p.seg[i];
+    return a;
+}
+// The store table of segments [lo, hi) from the caller's per-op buffers: forward segments (dx = false) write op i's output
+// y or the hidden h t of its residual block; dX-chain segments write d/d(op input) dprev gated by that input (`gate`), or
+// d/dh dt gated by h.  The loss segment stores nothing.
+static void ns_store_table(NsArgs& a, const NsProgram& p, const linna_layer_t* layers, int nl, const NsOpBufs* ops, int lo, int hi,
+                           bool dx) {
+    for (int i = lo; i < hi; ++i) {
         const int op = p.seg_op[i];
-        if (p.seg_hidden[i]) n += (layers[op].C + 63) & ~63;
-        else if (op < nl - 1) n += (layers[op].N + 63) & ~63;
+        if (op >= nl) continue;
+        const NsOpBufs& b = ops[op];
+        a.gn[i] = p.seg_hidden[i] ? layers[op].C : dx ? layers[op].K : layers[op].N;   // (a dX-chain program's segments are all nseg_f)
+        if (!dx) { a.gout[i] = p.seg_hidden[i] ? b.t : b.y; a.gld[i] = p.seg_hidden[i] ? b.ldt : b.ldy; }
+        else if (p.seg_hidden[i]) { a.gout[i] = b.dt; a.gld[i] = b.lddt; a.gmask[i] = b.t; a.gmld[i] = b.ldt; }
+        else { a.gout[i] = b.dprev; a.gld[i] = b.ldp; a.gmask[i] = b.gate; a.gmld[i] = b.ldx; }
     }
-    return n;
 }
-bool net_stream_dxi_eligible(const linna_layer_t* layers, int nl, int in_size) {
-    const NsProgram& p = ns_build_prog(layers, nl, in_size, 3);
-    if (!p.ok || !p.dxi_ok) return false;
-    return ((p.lds_for(NS_ROWS, true) + 7) & ~(size_t)7) + (size_t)NS_ROWS * (ns_g2_cols(p, layers, nl) / 32) * sizeof(unsigned) <= (size_t)NS_LDS_BYTES;
-}
-size_t net_stream_dxi_packed_floats(const linna_layer_t* layers, int nl, int in_size) {
-    const size_t a = ns_build_prog(layers, nl, in_size, 3).packed_floats;
-    return net_stream_g2_side() ? std::max(a, ns_build_prog(layers, nl, in_size, 3, nullptr, true).packed_floats) : a;
+// the sign-bit gates (ns_gates) into the launch; false when they do not fit the LDS or a gate has no producer (*lds_extra:
+// the launch's LDS beyond the program's own)
+static bool ns_set_gates(NsArgs& a, const NsGates& g, const NsProgram& p, int rows, size_t* lds_extra) {
+    for (int i = 0; i < NS_MAXSEG; ++i) { a.gbit[i] = g.gbit[i]; a.mbit[i] = g.mbit[i]; }
+    a.nbw = g.ncols / 32;
+    a.bits_off = (int)(g.lds0 / sizeof(float));
+    *lds_extra = g.lds - p.lds_for(rows, true);
+    return g.ok && g.lds <= (size_t)NS_LDS_BYTES;
 }
 
-int launch_net_stream(const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* Z, int ldz, int B,
+int launch_net_stream(NsKind kind, const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* Z, int ldz, int B,
                       int nin, const int* is_flat, const float* a1, const float* a2, const int* lg, const float* xmean,
                       const float* xstd, const float* cscale, const float* cshift, const float* w, float T, float* lnP,
                       float* D, int ldd, float* TH, int ldt, const NsMove* mv, const NsGrad* gr, const int* gate, int rows,
-                      const NsDense* dn, hipStream_t s, const float* cpost, const float* cshift2, int bf) {
-    const NsProgram& p = bf ? ns_build_prog(layers, nl, in_size, NS_PROG_BF16_CODE, dn) : ns_build_prog(layers, nl, in_size, 0, dn, net_stream_k4(rows, 1));
+                      const NsDense* dn, hipStream_t s, const float* cpost, const float* cshift2) {
+    const bool bf = kind == NS_SERVE_BF16;
+    if ((kind == NS_SERVE_DENSE) != (dn != nullptr) || !(kind == NS_SERVE || kind == NS_SERVE_DENSE || bf)) {
+        set_error("net_stream: not a serving program"); return LINNA_ERR_INVALID;
+    }
+    const NsProgramRef pref = ns_program(kind, layers, nl, in_size, dn, rows);
+    const NsProgram& p = *pref;
     if ((cpost != nullptr) != (cshift2 != nullptr) || (cpost && (dn || gr))) {
         set_error("net_stream: the exp output map needs cpost and cshift2, and has no dense / gradient program"); return LINNA_ERR_INVALID;
     }
@@ -2369,21 +2416,13 @@ int launch_net_stream(const linna_layer_t* layers, int nl, int in_size, const fl
     if (dn && (w || gr || cscale || cshift)) { set_error("net_stream: the dense program carries its own output map and has no fused gradient"); return LINNA_ERR_INVALID; }
     if (mv && (nin > 64 || (!w && !dn))) { set_error("net_stream: fused sampler moves need <= 64 parameters and a log-likelihood in the launch"); return LINNA_ERR_UNSUPPORTED; }
     if (gr && (!p.grad_ok || !w || !lnP || !gr->gscale || !gr->G || mv)) { set_error("net_stream: no fused gradient for this network / likelihood"); return LINNA_ERR_UNSUPPORTED; }
-    NsArgs a;
-    ::memset(static_cast<void*>(&a), 0, sizeof(a));
-    a.Z = Z; a.ldz = ldz; a.B = B; a.nin = nin;
+    NsArgs a = ns_args(p, packed, Z, ldz, B, nin, gr != nullptr);    // forward only: stop after the forward segments
     a.is_flat = is_flat; a.a1 = a1; a.a2 = a2; a.lg = lg; a.xmean = xmean; a.xstd = xstd;
-    a.packed = packed;
-    a.Gstride = p.Gstride; a.nseg_f = p.nseg_f;
-    a.G = gr ? p.Gstride : p.G;                        // forward only: stop after the forward segments
-    a.nseg = gr ? (int)p.seg.size() : p.nseg_f;
-    a.LD = p.LD; a.kpad0 = p.kpad0; a.nout = p.nout; a.bias_total = p.bias_total;
     a.cscale = cscale; a.cshift = cshift; a.w = w; a.T = T;
     a.cpost = cpost; a.cshift2 = cshift2;
     a.dense = p.dense ? (dn && dn->factored ? 2 : 1) : 0; a.u_col = p.u_col; a.u_same = p.u_same; a.x0_keep = p.x0_keep;
     a.lnP = lnP; a.D = D; a.ldd = ldd; a.TH = TH; a.ldt = ldt;
-    for (int i = 0; i < (int)p.seg.size(); ++i) a.seg[i] = p.seg[i];
-    a.stamps = nullptr; a.gate = gate;
+    a.gate = gate;
     if (mv) {
         a.mv_coords = mv->coords; a.mv_ldc = mv->ldc; a.mv_logp = mv->logp; a.mv_S = mv->S;
         a.mv_cc = mv->cc; a.mv_ldcc = mv->ldcc; a.mv_C = mv->C; a.mv_nc = mv->nc;
@@ -2409,215 +2448,116 @@ int launch_net_stream(const linna_layer_t* layers, int nl, int in_size, const fl
     return ns_launch_kernel<0, false>(a, B, p, rows, s);
 }
 
-// Training / validation forward: X[B][ldx] (transformed inputs) -> every op's output in global memory.
-// `y[i]`, `ldy[i]`: destination of op i's output; `t[i]`, `ldt[i]`: of the hidden h of residual block i.
+// Training / validation forward: X[B][ldx] (transformed inputs) -> every op's output (`ops[i].y`, the hidden h of a
+// residual block `ops[i].t`) in global memory.
 int launch_net_stream_store(const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* X, int ldx,
-                            int B, float* const* y, const int* ldy, float* const* t, const int* ldt, const float* cscale,
-                            const float* cshift, int rows, hipStream_t s) {
-    const NsProgram& p = ns_build_prog(layers, nl, in_size, 0);
+                            int B, const NsOpBufs* ops, const float* cscale, const float* cshift, int rows, hipStream_t s) {
+    const NsProgramRef pref = ns_program(NS_STORE, layers, nl, in_size, nullptr, rows);
+    const NsProgram& p = *pref;
     if (!p.ok) { set_error("net_stream: network not eligible"); return LINNA_ERR_UNSUPPORTED; }
-    NsArgs a;
-    ::memset(static_cast<void*>(&a), 0, sizeof(a));
-    a.Z = X; a.ldz = ldx; a.B = B; a.nin = in_size;
+    NsArgs a = ns_args(p, packed, X, ldx, B, in_size, false);
     // the prologue's transform constants are loaded (and ignored): any readable arrays of >= in_size entries
     a.is_flat = reinterpret_cast<const int*>(X); a.a1 = X; a.a2 = X; a.lg = nullptr; a.xmean = X; a.xstd = X;
-    a.packed = packed;
-    a.Gstride = p.Gstride; a.nseg_f = p.nseg_f; a.G = p.G; a.nseg = p.nseg_f;
-    a.LD = p.LD; a.kpad0 = p.kpad0; a.nout = p.nout; a.bias_total = p.bias_total;
-    a.T = 1.f;
     a.cscale = cscale; a.cshift = cshift;                   // column affine of the last output (Y transforms), or null
-    for (int i = 0; i < (int)p.seg.size(); ++i) a.seg[i] = p.seg[i];
-    for (int i = 0; i < p.nseg_f; ++i) {
-        const int op = p.seg_op[i];
-        if (p.seg_hidden[i]) { a.gout[i] = t[op]; a.gld[i] = ldt[op]; a.gn[i] = layers[op].C; }
-        else { a.gout[i] = y[op]; a.gld[i] = ldy[op]; a.gn[i] = layers[op].N; }
-    }
+    ns_store_table(a, p, layers, nl, ops, 0, p.nseg_f, false);
     return ns_launch_kernel<0, false, 1>(a, B, p, rows, s);
 }
 
 
-// lnP and d lnP / d z in ONE launch for any network the forward and dX-chain programs cover (GRAD + STORE == 2): forward
-// segments store the activations the gates need (`y[i]` / `t[i]`: output of op i / hidden h of residual block i, in the
-// caller's workspace), the turnaround forms d lnP / d out, the dX chain runs down to the network input gating on those
-// activations, the finish applies the prior map's derivative.  Diagonal covariance.
+// lnP and d lnP / d z in ONE launch for any network the forward and dX-chain programs cover (GRAD + STORE == 2): the
+// forward segments keep the signs of the activations the gates need (ns_gates; round 2 kept the activations themselves in
+// the caller's workspace: 40 MB written and read back per 4096-chain launch of ChtoModelv2(33,33), in bursts at the run
+// ends of 256 workgroups in step, each read an exposed L2 round trip behind a drained weight ring), the turnaround forms
+// d lnP / d out, the dX chain runs down to the network input gating on those signs, the finish applies the prior map's
+// derivative.  Diagonal covariance.
 int launch_net_stream_grad2(const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* Z, int ldz, int B,
                             int nin, const int* is_flat, const float* a1, const float* a2, const int* lg, const float* xmean,
                             const float* xstd, const float* cscale, const float* cshift, const float* w, float T, float* lnP,
-                            const NsGrad& gr, float* const* y, const int* ldy, float* const* t, const int* ldt, int rows,
-                            hipStream_t s) {
-    const NsProgram& p = ns_build_prog(layers, nl, in_size, 3, nullptr, rows == 16 && net_stream_g2_side());
+                            const NsGrad& gr, int rows, hipStream_t s) {
+    const NsProgramRef pref = ns_program(NS_GRAD_INPUT, layers, nl, in_size, nullptr, rows);
+    const NsProgram& p = *pref;
     if (!p.ok || !p.dxi_ok) { set_error("net_stream: no forward + dX program for this network"); return LINNA_ERR_UNSUPPORTED; }
     if (!w || !lnP || !gr.gscale || !gr.G) { set_error("net_stream: the one-launch gradient needs a diagonal covariance"); return LINNA_ERR_INVALID; }
-    NsArgs a;
-    ::memset(static_cast<void*>(&a), 0, sizeof(a));
-    a.Z = Z; a.ldz = ldz; a.B = B; a.nin = nin;
+    NsArgs a = ns_args(p, packed, Z, ldz, B, nin, true);
     a.is_flat = is_flat; a.a1 = a1; a.a2 = a2; a.lg = lg; a.xmean = xmean; a.xstd = xstd;
-    a.packed = packed;
-    a.Gstride = p.Gstride; a.nseg_f = p.nseg_f; a.G = p.Gstride; a.nseg = (int)p.seg.size();
-    a.LD = p.LD; a.kpad0 = p.kpad0; a.nout = p.nout; a.bias_total = p.bias_total;
     a.cscale = cscale; a.cshift = cshift; a.w = w; a.T = T; a.lnP = lnP;
     a.gscale = gr.gscale; a.Gout = gr.G; a.ldg = gr.ldg;
     a.hm_p = gr.hm_p; a.hm_ldp = gr.hm_ldp; a.hm_q = gr.hm_q; a.hm_mass = gr.hm_mass; a.hm_ek = gr.hm_ek; a.hm_ed = gr.hm_ed;
-    for (int i = 0; i < (int)p.seg.size(); ++i) a.seg[i] = p.seg[i];
-    // What the backward gates on is the SIGN of a forward activation, and the workgroup that needs it is the one that
-    // computed it: one bit per (row, column) in LDS (NsArgs::nbw).  Round 2 kept the activations themselves in the caller's
-    // workspace (y / t: 40 MB written and read back per 4096-chain launch of ChtoModelv2(33,33), in bursts at the run ends of
-    // 256 workgroups in step, each read an exposed L2 round trip behind a drained weight ring); gout / gmask are flags now.
-    (void)y; (void)ldy; (void)t; (void)ldt;
-    std::vector<int> base_y(nl, -1), base_t(nl, -1);
-    int ncolbits = 0;
-    for (int i = 0; i < NS_MAXSEG; ++i) a.gbit[i] = a.mbit[i] = -1;
-    for (int i = 0; i < p.nseg_f; ++i) {                      // forward: keep the signs a gate will ask for
-        const int op = p.seg_op[i];
-        if (p.seg_hidden[i]) { base_t[op] = ncolbits; a.gn[i] = layers[op].C; }
-        else if (op < nl - 1) { base_y[op] = ncolbits; a.gn[i] = layers[op].N; }
-        else continue;
-        a.gbit[i] = ncolbits;
-        ncolbits += (a.gn[i] + 63) & ~63;
+    const NsGates g = ns_gates(p, layers, nl, rows);
+    for (int i = 0; i < (int)p.seg.size(); ++i) if (i >= p.nseg_f || g.gbit[i] >= 0) a.gn[i] = ns_seg_cols(p, layers, i);
+    size_t lds_extra = 0;
+    if (!ns_set_gates(a, g, p, rows, &lds_extra)) {
+        set_error(g.ok ? "net_stream: the one-launch gradient's sign bits do not fit the LDS" : "net_stream: a gate of the one-launch gradient has no producer");
+        return LINNA_ERR_UNSUPPORTED;
     }
-    for (int i = p.nseg_f; i < (int)p.seg.size(); ++i) {
-        const int op = p.seg_op[i];
-        if (p.seg_hidden[i]) {                                // d/dh of residual block op: gated by its h
-            a.mbit[i] = base_t[op]; a.gn[i] = layers[op].C;
-            if (a.mbit[i] < 0) { set_error("net_stream: a gate of the one-launch gradient has no producer"); return LINNA_ERR_UNSUPPORTED; }
-        } else {                                              // d/d(input of op): gated by the producing op's output, if it went through a ReLU
-            const bool relu_in = op > 0 && (layers[op - 1].op == LINNA_OP_RESBLOCK || layers[op - 1].relu);
-            a.mbit[i] = relu_in ? base_y[op - 1] : -1; a.gn[i] = layers[op].K;
-            if (relu_in && a.mbit[i] < 0) { set_error("net_stream: a gate of the one-launch gradient has no producer"); return LINNA_ERR_UNSUPPORTED; }
-        }
-    }
-    a.nbw = ncolbits / 32;
-    const size_t lds0 = (p.lds_for(rows, true) + 7) & ~(size_t)7;
-    a.bits_off = (int)(lds0 / sizeof(float));
-    const size_t lds_bits = (size_t)rows * a.nbw * sizeof(unsigned);
-    if (lds0 + lds_bits > (size_t)NS_LDS_BYTES) { set_error("net_stream: the one-launch gradient's sign bits do not fit the LDS"); return LINNA_ERR_UNSUPPORTED; }
-    return ns_launch_kernel<0, true, 2>(a, B, p, rows, s, 0, lds0 + lds_bits - p.lds_for(rows, true));
+    return ns_launch_kernel<0, true, 2>(a, B, p, rows, s, 0, lds_extra);
 }
 
-// Training forward + loss in one launch (STORE == 3): X[n][ldx] the resident set, ROWS the batch (null: rows 0..B-1);
-// `dn` = {Cinv, ldc, null, null}: the inverse covariance in the network's normalised output space as the last segment.
-int launch_net_stream_train(const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* X, int ldx,
-                            const int* ROWS, int B, const int* lg, const float* xmean, const float* xstd, float* XB, int ldxb,
-                            float* const* y, const int* ldy, float* const* t, const int* ldt, const NsTrainLoss& L,
-                            const NsDense& dn, int rows, hipStream_t s) {
-    const NsProgram& p = ns_build_prog(layers, nl, in_size, 0, &dn);
-    if (!p.ok || !p.dense) { set_error("net_stream: network + loss not eligible"); return LINNA_ERR_UNSUPPORTED; }
-    NsArgs a;
-    ::memset(static_cast<void*>(&a), 0, sizeof(a));
-    a.Z = X; a.ldz = ldx; a.B = B; a.nin = in_size;
+// the forward + loss half of a training launch (STORE == 3): the batch rows ROWS (null: 0..B-1) of X gathered and
+// X-transformed into XB, every activation stored, the loss rows and d loss / d pred written
+static NsArgs ns_train_args(const NsProgram& p, bool full, const linna_layer_t* layers, int nl, int in_size, const float* packed,
+                            const float* X, int ldx, const int* ROWS, int B, const int* lg, const float* xmean, const float* xstd,
+                            float* XB, int ldxb, const NsOpBufs* ops, const NsTrainLoss& L) {
+    NsArgs a = ns_args(p, packed, X, ldx, B, in_size, full);
     a.is_flat = reinterpret_cast<const int*>(xmean); a.a1 = xmean; a.a2 = xmean;     // loaded and ignored
     a.lg = lg; a.xmean = xmean; a.xstd = xstd;
-    a.packed = packed;
-    a.Gstride = p.Gstride; a.nseg_f = p.nseg_f; a.G = p.G; a.nseg = p.nseg_f;
-    a.LD = p.LD; a.kpad0 = p.kpad0; a.nout = p.nout; a.bias_total = p.bias_total;
-    a.T = 1.f;
     a.dense = p.dense; a.u_col = p.u_col; a.u_same = p.u_same;
-    for (int i = 0; i < (int)p.seg.size(); ++i) a.seg[i] = p.seg[i];
-    for (int i = 0; i < p.nseg_f; ++i) {
-        const int op = p.seg_op[i];
-        if (op >= nl) continue;                                   // the loss segment stores nothing
-        if (p.seg_hidden[i]) { a.gout[i] = t[op]; a.gld[i] = ldt[op]; a.gn[i] = layers[op].C; }
-        else { a.gout[i] = y[op]; a.gld[i] = ldy[op]; a.gn[i] = layers[op].N; }
-    }
+    ns_store_table(a, p, layers, nl, ops, 0, p.nseg_f, false);
     a.t_rows = ROWS; a.t_xb = XB; a.t_ldxb = ldxb;
     a.t_Y = L.YN; a.t_ldy = L.ldyn;
     a.t_den = L.den; a.t_inv_batch = L.inv_batch; a.t_loss_rows = L.loss_rows; a.t_dP = L.dP; a.t_lddp = L.lddp;
+    return a;
+}
+
+// Training forward + loss in one launch (STORE == 3); `dn` = {Cinv, ldc, null, null}: the inverse covariance in the
+// network's normalised output space as the last segment.
+int launch_net_stream_train(const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* X, int ldx,
+                            const int* ROWS, int B, const int* lg, const float* xmean, const float* xstd, float* XB, int ldxb,
+                            const NsOpBufs* ops, const NsTrainLoss& L, const NsDense& dn, int rows, hipStream_t s) {
+    const NsProgramRef pref = ns_program(NS_TRAIN_FWD, layers, nl, in_size, &dn, rows);
+    const NsProgram& p = *pref;
+    if (!p.ok || !p.dense) { set_error("net_stream: network + loss not eligible"); return LINNA_ERR_UNSUPPORTED; }
+    const NsArgs a = ns_train_args(p, false, layers, nl, in_size, packed, X, ldx, ROWS, B, lg, xmean, xstd, XB, ldxb, ops, L);
     return ns_launch_kernel<0, false, 3>(a, B, p, rows, s);
 }
 
 // A training step's network work in ONE launch (TRB: GRAD + STORE == 3): launch_net_stream_train's forward + loss, its
-// finish as the turnaround, then launch_net_stream_dx's chain down to op 1 -- same arguments as the two of them.  `post`:
-// only the AdamW step constants ride here (the loss rows are not complete before every workgroup's turnaround: the batch
-// mean rides in the parameter-gradient launch instead).
+// finish as the turnaround, then launch_net_stream_dx's chain down to op 1 -- same arguments as the two of them; the gates
+// of the backward half are sign bits in LDS (ns_gates: the activations go to memory all the same, the parameter
+// gradients read them, but no gate is read back from there).  `post`: only the AdamW step constants ride here (the loss
+// rows are not complete before every workgroup's turnaround: the batch mean rides in the parameter-gradient launch instead).
 int launch_net_stream_train_bwd(const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* X, int ldx,
                                 const int* ROWS, int B, const int* lg, const float* xmean, const float* xstd, float* XB, int ldxb,
-                                float* const* y, const int* ldy, float* const* t, const int* ldt, const NsTrainLoss& L,
-                                const NsDense& dn, float* const* dprev, const int* ldp, const float* const* hin, const int* ldh,
-                                float* const* dt, const int* lddt, int rows, hipStream_t s, const NsPost* post) {
-    const NsProgram& p = ns_build_prog(layers, nl, in_size, 4, &dn);
+                                const NsOpBufs* ops, const NsTrainLoss& L, const NsDense& dn, int rows, hipStream_t s,
+                                const NsPost* post) {
+    const NsProgramRef pref = ns_program(NS_TRAIN_STEP, layers, nl, in_size, &dn, rows);
+    const NsProgram& p = *pref;
     if (!p.ok || !p.train_ok || !p.dense) { set_error("net_stream: network + loss have no one-launch training program"); return LINNA_ERR_UNSUPPORTED; }
     if (rows != 4) { set_error("net_stream: the one-launch training step runs on the 4-row engine"); return LINNA_ERR_UNSUPPORTED; }
-    NsArgs a;
-    ::memset(static_cast<void*>(&a), 0, sizeof(a));
-    a.Z = X; a.ldz = ldx; a.B = B; a.nin = in_size;
-    a.is_flat = reinterpret_cast<const int*>(xmean); a.a1 = xmean; a.a2 = xmean;     // loaded and ignored
-    a.lg = lg; a.xmean = xmean; a.xstd = xstd;
-    a.packed = packed;
-    a.Gstride = p.Gstride; a.nseg_f = p.nseg_f; a.G = p.Gstride; a.nseg = (int)p.seg.size();
-    a.LD = p.LD; a.kpad0 = p.kpad0; a.nout = p.nout; a.bias_total = p.bias_total;
-    a.T = 1.f;
-    a.dense = p.dense; a.u_col = p.u_col; a.u_same = p.u_same;
-    for (int i = 0; i < (int)p.seg.size(); ++i) a.seg[i] = p.seg[i];
-    for (int i = 0; i < (int)p.seg.size(); ++i) {
-        const int op = p.seg_op[i];
-        if (i < p.nseg_f) {
-            if (op >= nl) continue;                               // the loss segment stores nothing
-            if (p.seg_hidden[i]) { a.gout[i] = t[op]; a.gld[i] = ldt[op]; a.gn[i] = layers[op].C; }
-            else { a.gout[i] = y[op]; a.gld[i] = ldy[op]; a.gn[i] = layers[op].N; }
-        } else if (p.seg_hidden[i]) {                             // d/dh of residual block op, gated by its stored h
-            a.gout[i] = dt[op]; a.gld[i] = lddt[op]; a.gn[i] = layers[op].C; a.gmask[i] = t[op]; a.gmld[i] = ldt[op];
-        } else {                                                  // d/d(input of op), gated by the producing op's output
-            a.gout[i] = dprev[op]; a.gld[i] = ldp[op]; a.gn[i] = layers[op].K; a.gmask[i] = hin[op]; a.gmld[i] = ldh[op];
-        }
+    NsArgs a = ns_train_args(p, true, layers, nl, in_size, packed, X, ldx, ROWS, B, lg, xmean, xstd, XB, ldxb, ops, L);
+    ns_store_table(a, p, layers, nl, ops, p.nseg_f, (int)p.seg.size(), true);
+    const NsGates g = ns_gates(p, layers, nl, rows);
+    size_t lds_extra = 0;
+    if (!ns_set_gates(a, g, p, rows, &lds_extra)) {
+        set_error(g.ok ? "net_stream: the training step's sign bits do not fit the LDS" : "net_stream: a gate of the one-launch training step has no producer");
+        return LINNA_ERR_UNSUPPORTED;
     }
-    // the gates of the backward half: sign bits in LDS (see launch_net_stream_grad2) -- the activations go to memory all the
-    // same (the parameter gradients read them), but no gate is read back from there
-    std::vector<int> base_y(nl, -1), base_t(nl, -1);
-    int ncolbits = 0;
-    for (int i = 0; i < NS_MAXSEG; ++i) a.gbit[i] = a.mbit[i] = -1;
-    for (int i = 0; i < p.nseg_f; ++i) {
-        const int op = p.seg_op[i];
-        if (op >= nl) continue;
-        if (p.seg_hidden[i]) base_t[op] = ncolbits; else if (op < nl - 1) base_y[op] = ncolbits; else continue;
-        a.gbit[i] = ncolbits;
-        ncolbits += (a.gn[i] + 63) & ~63;
-    }
-    for (int i = p.nseg_f; i < (int)p.seg.size(); ++i) {
-        const int op = p.seg_op[i];
-        if (!a.gmask[i]) continue;
-        a.mbit[i] = p.seg_hidden[i] ? base_t[op] : (op > 0 ? base_y[op - 1] : -1);
-        if (a.mbit[i] < 0) { set_error("net_stream: a gate of the one-launch training step has no producer"); return LINNA_ERR_UNSUPPORTED; }
-    }
-    a.nbw = ncolbits / 32;
-    const size_t lds0 = (p.lds_for(rows, true) + 7) & ~(size_t)7;
-    a.bits_off = (int)(lds0 / sizeof(float));
-    const size_t lds_bits = (size_t)rows * a.nbw * sizeof(unsigned);
-    if (lds0 + lds_bits > (size_t)NS_LDS_BYTES) { set_error("net_stream: the training step's sign bits do not fit the LDS"); return LINNA_ERR_UNSUPPORTED; }
-    a.t_rows = ROWS; a.t_xb = XB; a.t_ldxb = ldxb;
-    a.t_Y = L.YN; a.t_ldy = L.ldyn;
-    a.t_den = L.den; a.t_inv_batch = L.inv_batch; a.t_loss_rows = L.loss_rows; a.t_dP = L.dP; a.t_lddp = L.lddp;
     int extra = 0;
     if (post && post->step) { a.p_step = post->step; a.p_hyper = post->hyper; a.p_b1 = post->b1; a.p_b2 = post->b2; extra = 1; }
-    return ns_launch_kernel<0, true, 3>(a, B, p, rows, s, extra, lds0 + lds_bits - p.lds_for(rows, true));
+    return ns_launch_kernel<0, true, 3>(a, B, p, rows, s, extra, lds_extra);
 }
-}  // namespace linna
 
-namespace linna {
 // The dX chain of a training step in one launch (what linna_net_backward otherwise runs as one GEMM per op):
-// dOUT[B][lddo] -> for every op i >= first (1, or 0 with_input) the gradient with respect to its input, gated by the
-// stored forward activation hin[i] (null: no gate), into dprev[i]; for residual blocks also d/dh into dt[i], gated by
-// the stored h (t[i]).
+// dOUT[B][lddo] -> for every op i >= first (1, or 0 with_input) the gradient with respect to its input, gated by that input
+// where it went through a ReLU, into ops[i].dprev; for residual blocks also d/dh into ops[i].dt, gated by the stored h.
 int launch_net_stream_dx(const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* dOUT, int lddo,
-                         int B, float* const* dprev, const int* ldp, const float* const* hin, const int* ldh,
-                         float* const* dt, const int* lddt, const float* const* t, const int* ldt, int with_input, int rows,
-                         hipStream_t s, const NsPost* post) {
-    const NsProgram& p = ns_build_prog(layers, nl, in_size, with_input ? 2 : 1);
+                         int B, const NsOpBufs* ops, int with_input, int rows, hipStream_t s, const NsPost* post) {
+    const NsProgramRef pref = ns_program(with_input ? NS_DX_INPUT : NS_DX, layers, nl, in_size, nullptr, rows);
+    const NsProgram& p = *pref;
     if (!p.ok) { set_error("net_stream: no dX-chain program for this network"); return LINNA_ERR_UNSUPPORTED; }
-    NsArgs a;
-    ::memset(static_cast<void*>(&a), 0, sizeof(a));
-    const int nout = layers[nl - 1].N;
-    a.Z = dOUT; a.ldz = lddo; a.B = B; a.nin = nout;
+    NsArgs a = ns_args(p, packed, dOUT, lddo, B, layers[nl - 1].N, false);
     a.is_flat = reinterpret_cast<const int*>(dOUT); a.a1 = dOUT; a.a2 = dOUT; a.lg = nullptr; a.xmean = dOUT; a.xstd = dOUT;
-    a.packed = packed;
-    a.Gstride = p.Gstride; a.nseg_f = p.nseg_f; a.G = p.G; a.nseg = p.nseg_f;
-    a.LD = p.LD; a.kpad0 = p.kpad0; a.nout = p.nout; a.bias_total = p.bias_total;
-    a.T = 1.f;
-    for (int i = 0; i < (int)p.seg.size(); ++i) a.seg[i] = p.seg[i];
-    for (int i = 0; i < p.nseg_f; ++i) {
-        const int op = p.seg_op[i];
-        if (p.seg_hidden[i]) { a.gout[i] = dt[op]; a.gld[i] = lddt[op]; a.gn[i] = layers[op].C; a.gmask[i] = t[op]; a.gmld[i] = ldt[op]; }
-        else { a.gout[i] = dprev[op]; a.gld[i] = ldp[op]; a.gn[i] = layers[op].K; a.gmask[i] = hin[op]; a.gmld[i] = ldh[op]; }
-    }
+    ns_store_table(a, p, layers, nl, ops, 0, p.nseg_f, true);
     if (post && post->n > 0) {                    // the rider (see NsArgs::p_rows): one more workgroup
         a.p_rows = post->rows; a.p_n = post->n; a.p_scale = post->scale; a.p_out = post->out;
         a.p_step = post->step; a.p_hyper = post->hyper; a.p_b1 = post->b1; a.p_b2 = post->b2;
