@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define LINNA_ABI_VERSION 12   /* 12: + linna_logprob_set_precision, linna_logprob_precision (the opt-in bf16 serving engine; linna_logprob_desc_t unchanged); 11: every descriptor struct a caller fills (linna_gemm_t, linna_layer_t, linna_logprob_desc_t, linna_loss_desc_t) starts with `uint32_t struct_size` = its sizeof in the caller's header, checked by the entries that take it -- a binding built against another layout is refused instead of read at wrong offsets; linna_slice_init / linna_slice_half_step(maxsteps): zeus' stepping-out budget; the shrinking test is zeus' `Z0 < lnP`; 10: + linna_slice_fusion, linna_slice_half_step(expect_rows); 9: + linna_stretch_run, linna_chain_append_t, linna_acorr_*, linna_chain_meanstd, linna_val_metrics, linna_loss_desc_t::ylog; 8: + the exception barrier (LINNA_ERR_INTERNAL, linna_debug_raise) and linna_logprob_desc_t GREW by one pointer (Sfac, appended: a binding compiled against the v7 struct must be rebuilt -- linna_logprob_create copies the struct at the new size); 4: + linna_comm_* (RCCL); 5: + linna_net_prepare, linna_net_forward_loss; 6: + linna_net_adamw_step, linna_net_train_step, linna_net_train_step_update; 7: + linna_engine_rows, linna_slice_half_step, linna_program_describe, linna_net_train_launches, linna_logprob_grad_leapfrog, linna_hmc_start */
+#define LINNA_ABI_VERSION 12   /* 12: + linna_logprob_set_precision, linna_logprob_precision (the opt-in bf16 serving engine; linna_logprob_desc_t unchanged), + linna_net_set_train_precision, linna_net_train_precision (the opt-in bf16 training step; entries added, no struct changed); 11: every descriptor struct a caller fills (linna_gemm_t, linna_layer_t, linna_logprob_desc_t, linna_loss_desc_t) starts with `uint32_t struct_size` = its sizeof in the caller's header, checked by the entries that take it -- a binding built against another layout is refused instead of read at wrong offsets; linna_slice_init / linna_slice_half_step(maxsteps): zeus' stepping-out budget; the shrinking test is zeus' `Z0 < lnP`; 10: + linna_slice_fusion, linna_slice_half_step(expect_rows); 9: + linna_stretch_run, linna_chain_append_t, linna_acorr_*, linna_chain_meanstd, linna_val_metrics, linna_loss_desc_t::ylog; 8: + the exception barrier (LINNA_ERR_INTERNAL, linna_debug_raise) and linna_logprob_desc_t GREW by one pointer (Sfac, appended: a binding compiled against the v7 struct must be rebuilt -- linna_logprob_create copies the struct at the new size); 4: + linna_comm_* (RCCL); 5: + linna_net_prepare, linna_net_forward_loss; 6: + linna_net_adamw_step, linna_net_train_step, linna_net_train_step_update; 7: + linna_engine_rows, linna_slice_half_step, linna_program_describe, linna_net_train_launches, linna_logprob_grad_leapfrog, linna_hmc_start */
 
 typedef struct linna_ctx linna_ctx_t;
 typedef struct linna_net linna_net_t;
@@ -208,6 +208,19 @@ int linna_net_backward(linna_net_t* net, const float* X, int ldx, int B, void* f
  * B <= 1024) and the grouped parameter-gradient launch with the optimiser in its epilogue; 3 = forward + loss and dX chain
  * as two launches; 0 = the network or its loss trains layer by layer. */
 int linna_net_train_launches(const linna_net_t* net, int B);
+/* Training-step precision of a network handle (codes as linna_logprob_set_precision).  LINNA_PRECISION_FP32 (default): every
+ * result as before.  LINNA_PRECISION_BF16 (opt-in): linna_net_train_step_update, linna_net_train_step and linna_net_adamw_step
+ * run the merged training step on a bf16 weight stream -- the weights rounded to nearest-even after the fp32 folding (0.1 W2),
+ * the activations and d loss / d activation rounded where the matrix cores read them, the first layer as [W | W] over
+ * bf16(x) and x - bf16(x); the loss's inverse covariance, the stored activations, the parameter gradients, AdamW and the
+ * parameters stay fp32, and the optimiser writes the next step's bf16 stream itself.  linna_net_forward, linna_net_backward
+ * and linna_net_forward_loss stay fp32.  On a bf16 handle those three entries return LINNA_ERR_UNSUPPORTED, with "bf16" in
+ * the message, where the bf16 step does not apply (a batch past the 4-row engine, B > 4 x CUs) -- never the fp32 step.
+ * LINNA_ERR_INVALID for a NULL handle or an unknown code (no GPU needed); LINNA_ERR_UNSUPPORTED with the reason for a network
+ * without a bf16 step (input skip, wider than 1024, more than 256 inputs, a first op that is not a linear layer, one layer).
+ * Setting bf16 allocates the bf16 stream: call it outside graph capture, before linna_net_prepare. */
+int linna_net_set_train_precision(linna_net_t* net, int precision);
+int linna_net_train_precision(const linna_net_t* net, int* out);
 int linna_net_stream_state(const linna_net_t* net, int* fwd, int* dx, int* dx_input);
 
 /* ------------------------------------------------------------------ prior map + input transform

@@ -19,7 +19,7 @@ def _stale(target, deps):
 
 def build(force=False, verbose=True):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(HERE, "..", "include", "linna_hip.h")]
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "net_stream_body.inc"), os.path.join(HERE, "..", "include", "linna_hip.h")]
     objs = []
     for src in SOURCES:
         s = os.path.join(CSRC, src)

@@ -130,6 +130,8 @@ _SIGNATURES = {
     "linna_dense_tri": (_I, [_I]),
     "linna_slice_fusion": (_I, [_I]),
     "linna_net_train_launches": (_I, [_V, _I]),
+    "linna_net_set_train_precision": (_I, [_V, _I]),
+    "linna_net_train_precision": (_I, [_V, _V]),
     "linna_program_describe": (_I, [_V, _I, _I, _I, _I, _V, C.c_size_t]),
     "linna_logprob_ws_bytes": (_SZ, [_V, _I, _I]),
     "linna_logprob_eval": (_I, [_V, _V, _I, _I, _V, _V, _V, _I, _V]),
@@ -205,7 +207,7 @@ def load():
 
 ERR_INVALID = -1         # LINNA_ERR_INVALID (include/linna_hip.h)
 ERR_UNSUPPORTED = -3     # LINNA_ERR_UNSUPPORTED
-PRECISION = {"fp32": 0, "bf16": 1}   # LINNA_PRECISION_FP32 / LINNA_PRECISION_BF16 (linna_logprob_set_precision)
+PRECISION = {"fp32": 0, "bf16": 1}   # LINNA_PRECISION_FP32 / LINNA_PRECISION_BF16 (linna_logprob_set_precision, linna_net_set_train_precision)
 ERR_INTERNAL = -4        # LINNA_ERR_INTERNAL: a C++ exception caught at the C boundary
 
 

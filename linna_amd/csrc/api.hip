@@ -114,7 +114,9 @@ struct linna_net {
     StreamCopy packed_dx[2];                 // ... for the one-launch dX chain of the backward ([1]: down to the network input)
     StreamCopy packed_tb;                    // ... for forward + loss + dX chain in ONE launch (linna_net_train_step on the small-batch engines)
     int stream_tb = -1;                      // -1 unknown, 0 no (not eligible / LINNA_BWD_STREAM=0), 1 yes
-    int as_merged = -1;                      // which streams as_args describes: 1 = packed_tb, 0 = packed_loss + packed_dx[0]
+    int as_merged = -1;                      // which streams as_args describes: 1 = packed_tb, 0 = packed_loss + packed_dx[0], 2 = packed_tbf
+    int train_prec = LINNA_PRECISION_FP32;   // linna_net_set_train_precision: the form of the training step's network launch
+    StreamCopy packed_tbf;                   // LINNA_PRECISION_BF16: the bf16 training stream (NS_TRAIN_STEP_BF16; [1] only, the 4-row engine)
     AsArgs as_args;                          // linna_net_adamw_step's descriptor table, valid for (as_params, as_n, as_k)
     const float* as_params = nullptr; size_t as_n = 0; int as_k = -1; int as_state = -1;   // as_state: -1 unknown, 0 unsupported, 1 ready
     int upd_state = -1; int upd_B = 0;       // linna_net_train_step_update: -1 unknown, 0 unsupported, 1 every parameter gradient of the step is in the grouped launch
@@ -352,7 +354,7 @@ int linna_net_create(linna_ctx_t* ctx, const linna_layer_t* layers, int nlayers,
 int linna_net_destroy(linna_net_t* net) try {
     if (net) {
         net->packed.release(); net->packed_dx[0].release(); net->packed_dx[1].release(); net->packed_loss.release();
-        net->packed_tb.release();
+        net->packed_tb.release(); net->packed_tbf.release();
     }
     delete net;
     return LINNA_OK;
@@ -479,6 +481,7 @@ static void net_ensure_loss(linna_net* n, const NsDense& dn) {
     const NsPlan merged = ok && n->stream_loss == 1 && !(b && b[0] == '0') && nl >= 2 ? net_stream_plan(NS_TRAIN_STEP, n->L.data(), nl, n->in_size, &dn)
                                                                                    : NsPlan{false, 0, false, nullptr};
     n->packed_tb.release();
+    n->packed_tbf.epoch[0] = n->packed_tbf.epoch[1] = 0;     // (the bf16 stream holds the loss's inverse covariance too)
     n->stream_tb = 0; n->as_merged = -1; n->as_state = -1;
     if (merged.ok && n->packed_tb.alloc(merged.packed_floats) == LINNA_OK) n->stream_tb = 1;
 }
@@ -486,6 +489,17 @@ static void net_ensure_loss(linna_net* n, const NsDense& dn) {
 // that touches the training streams of a step (train_step, train_step_update, adamw_step)
 static bool net_tb_usable(const linna_net* n, int B) {
     return n->stream_tb == 1 && n->packed_tb.ready() && net_stream_rows(B) == 4;     // (batches of up to 1024 rows)
+}
+// A bf16 net (linna_net_set_train_precision): the training entries run the bf16 step or return LINNA_ERR_UNSUPPORTED with the
+// reason -- never the fp32 one
+static bool net_bf16(const linna_net* n) { return n->train_prec == LINNA_PRECISION_BF16; }
+static int net_tbf_check(const linna_net* n, int B, const char* who) {
+    if (!n->packed_tbf.ready()) { set_error("%s: bf16 training stream not allocated", who); return LINNA_ERR_UNSUPPORTED; }
+    if (net_stream_rows(B) != 4) {
+        set_error("%s: the bf16 training step runs on the 4-row engine only; a batch of %d rows needs the %d-row engine", who, B, net_stream_rows(B));
+        return LINNA_ERR_UNSUPPORTED;
+    }
+    return LINNA_OK;
 }
 int linna_loss_targets(linna_ctx_t*, const linna_loss_desc_t* d, const float* Y, int ldy, int nrows, float* YN, int ldyn, void* stream) try {
     if (!d || !Y || !YN || nrows < 1) { set_error("loss_targets: bad arguments"); return LINNA_ERR_INVALID; }
@@ -506,7 +520,7 @@ int linna_net_prepare_loss(linna_net_t* n, const linna_loss_desc_t* d) try {
 // d loss / d pred.  Replaces linna_gather_xform + linna_net_forward + linna_chi2_ratio_loss_fwd_bwd (seven launches for
 // nout > 64) when the network + loss fit the whole-network kernel; LINNA_ERR_UNSUPPORTED otherwise (the caller then
 // runs that sequence).  The batch mean is a second, tiny launch (fixed summation order).
-struct NetUpdate { float* params; float* m; float* v; size_t n; float* hyper; float b1, b2, eps; };
+struct NetUpdate { float* params; float* m; float* v; size_t n; float* hyper; float b1, b2, eps; bool bf; };   // bf: the bf16 training stream's writer
 static int net_backward_impl(linna_net_t* n, const float* X, int ldx, int B, void* fwd_ws, void* bwd_ws, const float* dOUT,
                              int lddo, float* dX, int lddx, int pg, void* stream, const NsPost* post, const NetUpdate* upd = nullptr,
                              bool dx_done = false, const GemmPost* gpost = nullptr);
@@ -534,19 +548,20 @@ static int net_train_merged_impl(linna_net_t* n, const linna_loss_desc_t* d, con
                                  const int* lg, const float* xmean, const float* xstd, float* XB, int ldxb, void* fwd_ws, float* PRED,
                                  int ldp, const float* YN, int ldyn, const float* den, float inv_batch, float* loss_rows,
                                  float* dPRED, int lddp, void* bwd_ws, float* hyper, int* step_dev, float b1, float b2, void* stream) {
+    const bool bf = net_bf16(n);
     if (!n || !d || !X || !xmean || !xstd || !XB || !PRED || !YN || !den || !loss_rows || !dPRED || !fwd_ws || !bwd_ws || B < 1) {
         set_error("net_train_step: bad arguments"); return LINNA_ERR_INVALID;
     }
     if (d->nout != n->out_size) { set_error("net_train_step: loss for %d outputs, network has %d", d->nout, n->out_size); return LINNA_ERR_INVALID; }
     const int rows = net_stream_rows(B);
     const float* packed = nullptr;
-    TRY(stream_copy_refresh(n->packed_tb, n, rows, stream, &packed, NS_TRAIN_STEP, &n->loss_dn));
+    TRY(stream_copy_refresh(bf ? n->packed_tbf : n->packed_tb, n, rows, stream, &packed, bf ? NS_TRAIN_STEP_BF16 : NS_TRAIN_STEP, &n->loss_dn));
     const std::vector<NsOpBufs> ops = net_bufs(n, B, XB, ldxb, fwd_ws, PRED, ldp, bwd_ws);   // (no input gradient)
     const NsTrainLoss L{YN, ldyn, den, inv_batch, loss_rows, dPRED, lddp};
     const bool prep = hyper && step_dev;
     const NsPost post{nullptr, 0, 0.f, nullptr, prep ? step_dev : nullptr, prep ? hyper : nullptr, b1, b2};
     return launch_net_stream_train_bwd(n->L.data(), (int)n->L.size(), n->in_size, packed, X, ldx, ROWS, B, lg, xmean, xstd, XB, ldxb,
-                                       ops.data(), L, n->loss_dn, rows, S(stream), prep ? &post : nullptr);
+                                       ops.data(), L, n->loss_dn, rows, S(stream), prep ? &post : nullptr, bf);
 }
 // (the loss descriptor's stream state, as net_forward_loss_impl establishes it)
 static int net_train_ensure_loss(linna_net_t* n, const linna_loss_desc_t* d, void* stream) {
@@ -571,7 +586,8 @@ int linna_net_train_step(linna_net_t* n, const linna_loss_desc_t* d, const float
     if (!d) { set_error("net_train_step: null loss descriptor"); return LINNA_ERR_INVALID; }
     CHECK_STRUCT(d, linna_loss_desc_t, "net_train_step");
     TRY(net_train_ensure_loss(n, d, stream));
-    if (net_tb_usable(n, B)) {
+    if (net_bf16(n)) TRY(net_tbf_check(n, B, "net_train_step"));
+    if (net_bf16(n) || net_tb_usable(n, B)) {
         // two launches: forward + loss + dX chain, then every parameter gradient (the batch mean of the loss riding in it)
         TRY(net_train_merged_impl(n, d, X, ldx, ROWS, B, lg, xmean, xstd, XB, ldxb, fwd_ws, PRED, ldp, YN, ldyn, den, inv_batch,
                                   loss_rows, dPRED, lddp, bwd_ws, hyper, step_dev, b1, b2, stream));
@@ -623,9 +639,35 @@ static int net_forward_loss_impl(linna_net_t* n, const linna_loss_desc_t* d, con
 
 int linna_net_train_launches(const linna_net_t* n, int B) try {
     if (!n || B < 1) { set_error("net_train_launches: bad arguments"); return LINNA_ERR_INVALID; }
+    if (net_bf16(n)) return n->loss_dn.S && n->packed_tbf.ready() && net_stream_rows(B) == 4 ? 2 : 0;
     if (n->stream_loss != 1) return 0;
     if (net_tb_usable(n, B)) return 2;
     return n->stream_bwd[0] == 1 ? 3 : 0;
+} LINNA_CATCH_INT
+// The bf16 training step (linna_hip.h).  Checks first (no GPU), then the bf16 stream is allocated; its size depends on the
+// network and the loss's width only, so a placeholder inverse covariance plans it before the loss is known.
+int linna_net_set_train_precision(linna_net_t* n, int precision) try {
+    if (!n) { set_error("net_set_train_precision: null handle"); return LINNA_ERR_INVALID; }
+    if (precision != LINNA_PRECISION_FP32 && precision != LINNA_PRECISION_BF16) {
+        set_error("net_set_train_precision: unknown precision %d (LINNA_PRECISION_FP32 0, LINNA_PRECISION_BF16 1)", precision);
+        return LINNA_ERR_INVALID;
+    }
+    if (precision == LINNA_PRECISION_FP32) { n->train_prec = precision; n->as_state = -1; return LINNA_OK; }
+    if (n->has_inskip) { set_error("net_set_train_precision: no bf16 training step for an input-skip network (it has no merged training step)"); return LINNA_ERR_UNSUPPORTED; }
+    const NsDense dn = n->loss_dn.S ? n->loss_dn : NsDense{n->L.back().W, (int)ld4(n->out_size), nullptr, nullptr};
+    const NsPlan plan = net_stream_plan(NS_TRAIN_STEP_BF16, n->L.data(), (int)n->L.size(), n->in_size, &dn);
+    if (!plan.ok) { set_error("net_set_train_precision: no bf16 training step for this network: %s", plan.why ? plan.why : "not eligible"); return LINNA_ERR_UNSUPPORTED; }
+    if (!n->packed_tbf.ready() || n->packed_tbf.floats != plan.packed_floats) {
+        n->packed_tbf.release();
+        if (n->packed_tbf.alloc(plan.packed_floats) != LINNA_OK) { set_error("net_set_train_precision: hipMalloc(bf16 training stream) failed"); return LINNA_ERR_HIP; }
+    }
+    n->train_prec = precision; n->as_state = -1;
+    return LINNA_OK;
+} LINNA_CATCH_INT
+int linna_net_train_precision(const linna_net_t* n, int* out) try {
+    if (!n || !out) { set_error("net_train_precision: null argument"); return LINNA_ERR_INVALID; }
+    *out = n->train_prec;
+    return LINNA_OK;
 } LINNA_CATCH_INT
 int linna_net_stream_state(const linna_net_t* n, int* fwd, int* dx, int* dx_input) try {
     if (!n) { set_error("net_stream_state: null network"); return LINNA_ERR_INVALID; }
@@ -808,7 +850,7 @@ static int net_backward_impl(linna_net_t* n, const float* X, int ldx, int B, voi
         dcur = dprev; ldd = ldp;
     }
     if (grp.nprob) { TRY(gemm_launch_group(grp, grp_blocks, st, gpost)); gpost = nullptr; }     // every dY is on `st` by now: one grid over all the dW tiles
-    if (grpu.nprob) { TRY(gemm_launch_group_update(grpu, gu, grp_blocks, st, gpost)); gpost = nullptr; }
+    if (grpu.nprob) { TRY(gemm_launch_group_update(grpu, gu, grp_blocks, st, gpost, upd && upd->bf)); gpost = nullptr; }
     if (gpost && gpost->n > 0) TRY(launch_sum_scale(gpost->rows, gpost->n, gpost->scale, gpost->out, st));   // (no grouped launch to ride in)
     if (overlap && aux_used) {       // join: the caller's stream continues only after every gradient is written
         hipEvent_t e = ctx->events[next_event++];
@@ -1460,15 +1502,20 @@ int linna_adamw_step(linna_ctx_t*, float* p, const float* g, float* m, float* v,
 // two streams, or `params[n]` is not exactly its tensors back to back: the caller then uses linna_adamw_step.
 // The placement tables of the flat parameter buffer `p[n]` in the two training streams (net_stream_adamw_args), cached.
 static int net_ensure_as_args(linna_net_t* net, int B, const float* p, size_t n) {
-    const int merged = net_tb_usable(net, B) ? 1 : 0;
-    if (net->stream_loss != 1 || (!merged && (net->stream_bwd[0] != 1 || !net->packed_loss.ready() || !net->packed_dx[0].ready()))) {
+    const bool bf = net_bf16(net);
+    if (bf) {
+        TRY(net_tbf_check(net, B, "net_adamw_step"));
+        if (!net->loss_dn.S) { set_error("net_adamw_step: bf16 training stream: no loss seen yet (linna_net_prepare_loss)"); return LINNA_ERR_UNSUPPORTED; }
+    }
+    const int merged = bf ? 2 : net_tb_usable(net, B) ? 1 : 0;
+    if (!bf && (net->stream_loss != 1 || (!merged && (net->stream_bwd[0] != 1 || !net->packed_loss.ready() || !net->packed_dx[0].ready())))) {
         set_error("the network does not train through the whole-network streams"); return LINNA_ERR_UNSUPPORTED;
     }
     const int rows = net_stream_rows(B), k = rows < 16 ? 1 : 0;
     if (net->as_state < 0 || net->as_params != p || net->as_n != n || net->as_k != k || net->as_merged != merged) {
         net->as_params = p; net->as_n = n; net->as_k = k; net->as_merged = merged;
-        net->as_state = (merged ? net_stream_adamw_args(net->L.data(), (int)net->L.size(), net->in_size, rows, p, n, net->packed_tb.buf[k],
-                                                        &net->loss_dn, nullptr, &net->as_args, 1)
+        net->as_state = (merged ? net_stream_adamw_args(net->L.data(), (int)net->L.size(), net->in_size, rows, p, n,
+                                                        (bf ? net->packed_tbf : net->packed_tb).buf[k], &net->loss_dn, nullptr, &net->as_args, merged)
                                 : net_stream_adamw_args(net->L.data(), (int)net->L.size(), net->in_size, rows, p, n, net->packed_loss.buf[k],
                                                         &net->loss_dn, net->packed_dx[0].buf[k], &net->as_args)) == LINNA_OK ? 1 : 0;
         net->upd_state = -1;
@@ -1483,20 +1530,21 @@ int linna_net_adamw_step(linna_net_t* net, int B, float* p, const float* g, floa
     const int rows = net_stream_rows(B), k = rows < 16 ? 1 : 0;
     // both streams must hold the CURRENT weights and their constant parts before they are patched in place
     const float* dummy = nullptr;
-    const bool merged = net->as_merged == 1;
+    const bool merged = net->as_merged >= 1, bf = net->as_merged == 2;
     if (merged) {
-        TRY(stream_copy_refresh(net->packed_tb, net, rows, stream, &dummy, NS_TRAIN_STEP, &net->loss_dn));
+        TRY(stream_copy_refresh(bf ? net->packed_tbf : net->packed_tb, net, rows, stream, &dummy, bf ? NS_TRAIN_STEP_BF16 : NS_TRAIN_STEP, &net->loss_dn));
     } else {
         TRY(stream_copy_refresh(net->packed_loss, net, rows, stream, &dummy, NS_TRAIN_FWD, &net->loss_dn));
         TRY(stream_copy_refresh(net->packed_dx[0], net, rows, stream, &dummy, NS_DX));
     }
     if (!prepared) TRY(launch_adamw_prepare(hyper, step_dev, b1, b2, S(stream)));
-    TRY(launch_adamw_streams(net->as_args, p, g, m, v, hyper, b1, b2, eps, S(stream)));
+    TRY(launch_adamw_streams(net->as_args, p, g, m, v, hyper, b1, b2, eps, S(stream), bf));
     const unsigned long long epoch = g_weights_epoch.fetch_add(1) + 1;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(S(stream), &cap);
     if (cap == hipStreamCaptureStatusNone) {
-        if (merged) net->packed_tb.epoch[k] = epoch;
+        if (bf) net->packed_tbf.epoch[k] = epoch;
+        else if (merged) net->packed_tb.epoch[k] = epoch;
         else { net->packed_loss.epoch[k] = epoch; net->packed_dx[0].epoch[k] = epoch; }
     }
     return LINNA_OK;
@@ -1518,6 +1566,7 @@ int linna_net_train_step_update(linna_net_t* net, const linna_loss_desc_t* d, co
     CHECK_STRUCT(d, linna_loss_desc_t, "net_train_step_update");
     if (net->has_inskip) { set_error("net_train_step_update: input-skip network"); return LINNA_ERR_UNSUPPORTED; }
     TRY(net_train_ensure_loss(net, d, stream));
+    if (net_bf16(net)) TRY(net_tbf_check(net, B, "net_train_step_update"));
     TRY(net_ensure_as_args(net, B, params, n));
     if (net->upd_state < 0 || net->upd_B != B) {
         // every parameter gradient of the step must be a problem of the grouped launch, and the gradient pointers of the layer
@@ -1542,9 +1591,12 @@ int linna_net_train_step_update(linna_net_t* net, const linna_loss_desc_t* d, co
         net->upd_state = (ok && nprob <= GEMM_UPD_MAX) ? 1 : 0;
         net->upd_B = B;
     }
-    if (net->upd_state != 1) { set_error("net_train_step_update: a parameter gradient of this network falls outside the grouped launch"); return LINNA_ERR_UNSUPPORTED; }
-    const NetUpdate upd{params, m, v, n, hyper, b1, b2, eps};
-    const bool merged = net->as_merged == 1;
+    if (net->upd_state != 1) {
+        set_error("net_train_step_update: a parameter gradient of this network falls outside the grouped launch%s", net_bf16(net) ? " (bf16 step)" : "");
+        return LINNA_ERR_UNSUPPORTED;
+    }
+    const bool merged = net->as_merged >= 1, bf = net->as_merged == 2;
+    const NetUpdate upd{params, m, v, n, hyper, b1, b2, eps, bf};
     if (merged) {
         // TWO launches: forward + loss + dX chain (AdamW's step constants riding in it), then every parameter gradient with the
         // optimiser in the tiles' epilogue (the batch mean of the loss riding in it)
@@ -1563,7 +1615,8 @@ int linna_net_train_step_update(linna_net_t* net, const linna_loss_desc_t* d, co
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(S(stream), &cap);
     if (cap == hipStreamCaptureStatusNone) {
-        if (merged) net->packed_tb.epoch[k] = epoch;
+        if (bf) net->packed_tbf.epoch[k] = epoch;
+        else if (merged) net->packed_tb.epoch[k] = epoch;
         else { net->packed_loss.epoch[k] = epoch; net->packed_dx[0].epoch[k] = epoch; }
     }
     return LINNA_OK;

@@ -399,12 +399,13 @@ enum NsKind {
     NS_DX_INPUT,       // ... down to op 0
     NS_GRAD_INPUT,     // forward + dX chain down to the input: lnP and its gradient in one launch, any network it covers
     NS_TRAIN_STEP,     // forward + loss + dX chain down to op 1: the merged training step (4-row engine)
+    NS_TRAIN_STEP_BF16,   // ... in bf16 (linna_net_set_train_precision): bf16 runs, the loss segment an fp32 run, first layer [W | W]
 };
 // the serving programs are built from the layer list with the trailing input skip, the training ones from the list without
 inline bool ns_kind_full_layers(NsKind k) { return k == NS_SERVE || k == NS_SERVE_DENSE || k == NS_SERVE_BF16; }
 // Planning query (no GPU): ok: the network has this program (NS_GRAD_INPUT: and its sign-bit gates fit the LDS;
 // NS_TRAIN_STEP: with the dX chain); packed_floats: the size of a copy of its weight stream, for every engine; grad_ok: the
-// serving program holds the fused MLP gradient; why: NS_SERVE_BF16's reason when it is refused.
+// serving program holds the fused MLP gradient; why: NS_SERVE_BF16's / NS_TRAIN_STEP_BF16's reason when it is refused.
 struct NsPlan { bool ok; size_t packed_floats; bool grad_ok; const char* why; };
 NsPlan net_stream_plan(NsKind kind, const linna_layer_t* layers, int nl, int in_size, const NsDense* dn = nullptr);
 // rows per workgroup for a batch of B rows: 16 (v_mfma_f32_16x16x4_f32), or 8 / 4 (v_mfma_f32_4x4x1_16b_f32) when 16-row
@@ -452,7 +453,7 @@ int launch_net_stream_train(const linna_layer_t* layers, int nl, int in_size, co
 int launch_net_stream_train_bwd(const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* X, int ldx,
                                 const int* ROWS, int B, const int* lg, const float* xmean, const float* xstd, float* XB, int ldxb,
                                 const NsOpBufs* ops, const NsTrainLoss& L, const NsDense& dn, int rows, hipStream_t s,
-                                const NsPost* post);
+                                const NsPost* post, bool bf = false);     // bf: NS_TRAIN_STEP_BF16 (net_stream_train_bf16_kernel)
 // gradient fused behind the evaluation (plain ReLU MLPs, diagonal covariance): G = d lnP / d z
 // hm_*: a leapfrog kick and drift riding in the gradient's finish (HMCSampler.py:35-49): P += ek G; Q += ed P / mass, Q the
 // launch's own input rows (hm_p == nullptr: none)
@@ -475,6 +476,16 @@ __device__ __forceinline__ size_t as_slot(const AsPlace& q, int small, int nn, i
     const int t = small ? kr >> 2 : nl >> 4, lane = small ? nl : (nl & 15) + 16 * (kr >> 2);
     return ((((size_t)w * q.G + g) * 4 + t) * 64 + lane) * 4 + (kr & 3);
 }
+// the same for a bf16 stream of the small-batch engines (NS_TRAIN_STEP_BF16): the bf16 element index of (nn, kk) -- a step is 32 k,
+// each 16-byte vector eight bf16 (lane = column, load t = k chunk of 8)
+__device__ __forceinline__ size_t as_slot_bf16(const AsPlace& q, int nn, int kk) {
+    const int nl = nn & 63, ks = kk >> 5, kr = kk & 31;
+    int w, g;
+    if (q.type == 0) { w = (nn & 511) >> 6; g = ((nn >> 9) ? q.first1 : q.first0) + ks; }
+    else { const int kp = ks / q.steps; w = kp * q.ncg + (nn >> 6); g = q.first0 + (ks - kp * q.steps); }
+    return ((((size_t)w * q.G + g) * 4 + (kr >> 3)) * 64 + nl) * 8 + (kr & 7);
+}
+typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
 // torch.optim.AdamW's single-tensor update of one element (pointwise.hip adamw_kernel's arithmetic, operation for operation)
 __device__ __forceinline__ void adamw_one(float& pi, float gi, float& mi, float& vi, float lr, float wd, float bc1, float sbc2,
                                           float beta1, float beta2, float eps) {
@@ -484,10 +495,12 @@ __device__ __forceinline__ void adamw_one(float& pi, float gi, float& mi, float&
     const float denom = sqrtf(vi) / sbc2 + eps;
     pi = pi - (lr / bc1) * (mi / denom);
 }
+// merged = 2: the bf16 training stream (NS_TRAIN_STEP_BF16): the places say where the bf16 elements go (as_slot_bf16, ncols = the
+// matrix's columns K), and the first layer's [W | W] is two places of one matrix (pl[0] and pl[1]: it has no dX-chain place)
 int net_stream_adamw_args(const linna_layer_t* layers, int nl, int in_size, int rows, const float* params, size_t nflat,
                           float* s_fwd, const NsDense* dn, float* s_dx, AsArgs* out, int merged = 0);
 int launch_adamw_streams(const AsArgs& a, float* p, const float* g, float* m, float* v, const float* hyper, float b1, float b2,
-                         float eps, hipStream_t s);
+                         float eps, hipStream_t s, bool bf = false);
 // forward + dX chain down to the input in one launch (NS_GRAD_INPUT; diagonal covariance)
 int launch_net_stream_grad2(const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* Z, int ldz, int B,
                             int nin, const int* is_flat, const float* a1, const float* a2, const int* lg, const float* xmean,
@@ -528,7 +541,9 @@ struct GemmUpdate { long long pdiff, mdiff, vdiff;           // parameter / mome
                     AsPlace pl[GEMM_UPD_MAX][2]; AsBias bias[GEMM_UPD_MAX]; };
 struct GemmUpd1 { long long pdiff, mdiff, vdiff; const float* hyper; float beta1, beta2, eps; int small; AsPlace pl[2]; AsBias bias; };
 struct GemmPost { const float* rows; int n; float scale; float* out; };   // batch mean of the loss rows riding as one extra workgroup
-int gemm_launch_group_update(const GemmGroupArgsS& g, const GemmUpdate& u, int nblocks, hipStream_t stream, const GemmPost* post = nullptr);
+// bf: the places are those of a bf16 training stream (net_stream_adamw_args, merged = 2)
+int gemm_launch_group_update(const GemmGroupArgsS& g, const GemmUpdate& u, int nblocks, hipStream_t stream, const GemmPost* post = nullptr,
+                             bool bf = false);
 bool gemm_group_ok(const GemmArgs& a);
 int gemm_group_blocks(const GemmArgs& a);
 int gemm_launch_group(const GemmGroupArgs& g, int nblocks, hipStream_t stream, const GemmPost* post = nullptr);

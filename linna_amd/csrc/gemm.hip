@@ -154,7 +154,9 @@ __device__ unsigned long long g_gemm_rt[2 * 1024];       // s_memrealtime (100 M
 // workgroup alone on its CU spends 1.65 k cycles per K tile in fragments + MFMAs for 1.0 k of matrix pipe).  With CH2 the k
 // steps alternate between two accumulators -- dependent MFMAs sit two issues apart -- which are added once after the K
 // loop (one fixed order: even k steps + odd k steps; every update form of a training step shares this kernel).
-template <int WM, int WN, int TM, int TN, int ALAY, int BLAY, int NS, int KS, bool UPD = false, bool CH2 = false>
+// BFW (with UPD): the update epilogue writes a bf16 training stream (as_slot_bf16: each value the nearest-even rounding of
+// the fp32 one it would write, sub-dword stores from plain C++)
+template <int WM, int WN, int TM, int TN, int ALAY, int BLAY, int NS, int KS, bool UPD = false, bool CH2 = false, bool BFW = false>
 __device__ __forceinline__ void gemm_body(const GemmArgs& a, const int block_all, const KSplit ks, float* const db = nullptr,
                                           const GemmUpd1* const up = nullptr) {
     static_assert(!CH2 || (TM == 1 && TN == 1), "two accumulator chains: one tile per wave");
@@ -496,6 +498,20 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& a, const int block_all
             for (int j = 0; j < 2; ++j) {
                 const AsPlace& q = up->pl[j];
                 if (!q.out || !cok || r0 >= a.M) continue;
+                if constexpr (BFW) {
+                    __bf16* const ob = reinterpret_cast<__bf16*>(q.out);
+                    if (q.trans) {          // four consecutive k of one vector (koff and r0 are multiples of 4)
+                        *reinterpret_cast<bf16x4_t*>(ob + as_slot_bf16(q, col, q.koff + r0)) =
+                            bf16x4_t{(__bf16)(q.scale * pv[4 * eg]), (__bf16)(q.scale * pv[4 * eg + 1]), (__bf16)(q.scale * pv[4 * eg + 2]),
+                                     (__bf16)(q.scale * pv[4 * eg + 3])};
+                    } else {                // rows r0 .. r0 + 3: neighbouring lanes of the stream, 8 bf16 apart
+                        const size_t s0 = as_slot_bf16(q, r0, q.koff + col);
+#pragma unroll
+                        for (int e4 = 0; e4 < 4; ++e4)
+                            if (r0 + e4 < a.M) ob[s0 + 8 * e4] = (__bf16)(q.scale * pv[4 * eg + e4]);
+                    }
+                    continue;
+                }
                 if (q.trans) {
                     *reinterpret_cast<f32x4*>(q.out + as_slot(q, up->small, col, q.koff + r0)) =
                         f32x4{q.scale * pv[4 * eg], q.scale * pv[4 * eg + 1], q.scale * pv[4 * eg + 2], q.scale * pv[4 * eg + 3]};
@@ -616,7 +632,7 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void gemm_group_kernel(const Gem
     gemm_body<WM, WN, TM, TN, ALAY, BLAY, NS, KS, false, true>(a, (int)blockIdx.x - q.first, KSplit{1, nullptr, nullptr}, q.db);
 }
 
-template <int WM, int WN, int TM, int TN, int ALAY, int BLAY, int NS, int KS>
+template <int WM, int WN, int TM, int TN, int ALAY, int BLAY, int NS, int KS, bool BFW = false>
 __global__ __launch_bounds__(WM * WN * KS * 64) void gemm_group_update_kernel(const GemmGroupArgsS g, const GemmUpdate u, const GemmPost post) {
     if (post.n > 0 && blockIdx.x == gridDim.x - 1) { gemm_post_mean<WM * WN * KS * 64>(post); return; }
     int p = 0;
@@ -632,7 +648,7 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void gemm_group_update_kernel(co
     GemmUpd1 up;
     up.pdiff = u.pdiff; up.mdiff = u.mdiff; up.vdiff = u.vdiff; up.hyper = u.hyper; up.beta1 = u.beta1; up.beta2 = u.beta2;
     up.eps = u.eps; up.small = u.small; up.pl[0] = u.pl[p][0]; up.pl[1] = u.pl[p][1]; up.bias = u.bias[p];
-    gemm_body<WM, WN, TM, TN, ALAY, BLAY, NS, KS, true, true>(a, (int)blockIdx.x - q.first, KSplit{1, nullptr, nullptr}, q.db, &up);
+    gemm_body<WM, WN, TM, TN, ALAY, BLAY, NS, KS, true, true, BFW>(a, (int)blockIdx.x - q.first, KSplit{1, nullptr, nullptr}, q.db, &up);
 }
 
 // ---------------------------------------------------------------------------- launcher
@@ -745,10 +761,11 @@ int gemm_launch_group(const GemmGroupArgs& g, int nblocks, hipStream_t stream, c
     return check_hip(hipGetLastError(), "gemm group launch");
 }
 
-int gemm_launch_group_update(const GemmGroupArgsS& g, const GemmUpdate& u, int nblocks, hipStream_t stream, const GemmPost* post) {
+int gemm_launch_group_update(const GemmGroupArgsS& g, const GemmUpdate& u, int nblocks, hipStream_t stream, const GemmPost* post, bool bf) {
     constexpr size_t lds = (size_t)4 * (64 + 64) * BK * sizeof(float);
     const GemmPost q = post ? *post : GemmPost{nullptr, 0, 0.f, nullptr};
-    hipLaunchKernelGGL((gemm_group_update_kernel<2, 2, 1, 1, LAY_MN, LAY_MN, 4, 1>), dim3(nblocks + (q.n > 0 ? 1 : 0)), dim3(256), lds, stream, g, u, q);
+    if (bf) hipLaunchKernelGGL((gemm_group_update_kernel<2, 2, 1, 1, LAY_MN, LAY_MN, 4, 1, true>), dim3(nblocks + (q.n > 0 ? 1 : 0)), dim3(256), lds, stream, g, u, q);
+    else hipLaunchKernelGGL((gemm_group_update_kernel<2, 2, 1, 1, LAY_MN, LAY_MN, 4, 1>), dim3(nblocks + (q.n > 0 ? 1 : 0)), dim3(256), lds, stream, g, u, q);
     return check_hip(hipGetLastError(), "gemm group update launch");
 }
 

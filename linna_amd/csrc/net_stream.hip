@@ -179,6 +179,7 @@ struct NsPackArgs {
     int small;                                     // layout of the 4x4x1 engines: lane = column, load t = k chunk
     int bf;                                        // bf16 stream (NsProgram::bf): 32 k per step, eight bf16 per 16-byte vector
     float* out;                                    // weights, then biases
+    int f32seg;                                    // bf: this segment's runs are fp32 all the same (NsProgram::f32seg; -1: none)
 };
 // stream[w][g][t][lane][e], run r = (segment, pass), s = g - first[r], li = lane & 15, kq = lane >> 4:
 //   WIDE   n = 16 (32 pass + 4 w + t) + li,  k = 16 s + 4 kq + e
@@ -216,10 +217,17 @@ __device__ __forceinline__ void ns_pack_bf16(const NsPackArgs& p, size_t idx) {
     for (int e = 0; e < 8; ++e) v[e] = (__bf16)(n < S.N ? ns_pack_value(S, n, k0 + e) : 0.f);
     reinterpret_cast<bf16x8*>(p.out)[idx] = v;
 }
+// the segment whose run holds vector idx of the stream
+__device__ __forceinline__ int ns_pack_seg_of(const NsPackArgs& p, size_t idx) {
+    const int g = (int)((idx >> 6) / NS_NT % p.G);
+    int r = 0;
+    while (r + 1 < p.nrun && g >= p.run_first[r + 1]) ++r;
+    return p.run_seg[r];
+}
 __global__ void ns_pack_kernel(NsPackArgs p) {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t nw4 = (size_t)NS_NW * p.G * NS_NT * 64;
-    if (idx < nw4 && p.bf) { ns_pack_bf16(p, idx); return; }
+    if (idx < nw4 && p.bf && ns_pack_seg_of(p, idx) != p.f32seg) { ns_pack_bf16(p, idx); return; }
     if (idx < nw4) {
         const int lane = (int)(idx & 63);
         size_t q = idx >> 6;
@@ -332,1242 +340,23 @@ __device__ __forceinline__ float ns_prior_theta(float z, int flat, float a1, flo
 // The network input goes in as x_hi = bf16(x) at column c and x_lo = x - x_hi at column nin + c, and the first layer is
 // packed [W | W] (ns_build_one): the input is not quantised to 8 bits.  Epilogues, the finish and the prior map are the
 // fp32 kernel's.  SIDE segments are off in bf16 (K4 = false; the program builder plans none).
+// BF + TRB: the opt-in bf16 training step (net_stream_train_bf16_kernel, 4-row engine).  The forward segments and the dX
+// chain consume bf16 steps as above; the loss segment (the dense inverse covariance behind the last layer) stays an fp32
+// run inside the same stream -- both formats move 4 KiB per wave and step, so only the consumer differs.  It is chosen
+// once per run (begin_run: f32run); inside `step` the choice selects between two MFMA sequences and touches no memory.
+// The kernel body is net_stream_body.inc, the text of both kernels below: the whole-network kernel, and the opt-in bf16
+// training step (linna_net_set_train_precision) -- the merged training launch (GRAD + STORE == 3, 4-row engine) on a bf16
+// stream whose loss segment stays fp32, a kernel of its own rather than a net_stream_kernel specialisation.  (One text
+// included twice instead of a device function both call: inlined into a wrapper, the same body compiles to other
+// instructions for every existing instantiation.)
 template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF = false>
 __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_kernel(NsArgs a) {
-    constexpr int NT = NS_NT, NW = NS_NW;
-    constexpr int RG = 32;                         // threads per walker row in prologue / reduce / finish
-    constexpr bool SM = ROWS < 16;                 // 4x4x1 engine: ROWS / 4 row sets, lane = column
-    constexpr int RS = SM ? ROWS / 4 : 1;
-    constexpr int NQ = SM ? RS : NT;               // result quads per lane: (row set) or (column tile)
-    constexpr int NACC = SM ? 4 * RS : NT;
-    static_assert(!BF || (!GRAD && STORE == 0 && MOVE != 2), "bf16: serving and the fused stretch move only");
-    constexpr int AK = BF ? 2 : 1;                 // 16-byte A fragments per lane and step
-    constexpr bool K4 = !SM && !BF && (STORE == 0 || (GRAD && STORE == 2));   // 16-row engine, serving and the one-launch gradient: programs may hold SIDE segments
-    // (the one-launch gradient with SIDE segments in its forward half was measured SLOWER: 156.4 against 154.2 us at ChtoModelv2(33,33))
-    // TRB: a whole training step's network work in ONE launch (linna_net_train_step): gather + transform + forward with the
-    // activations kept + chi^2-ratio loss (STORE == 3) as the forward half, the loss finish as the TURNAROUND (loss rows,
-    // d loss / d pred to memory AND into LDS as the input of the first backward segment), then the dX chain (STORE == 2's
-    // epilogues: gates from the activations this very launch stored, read through the L2) -- one prologue and one launch
-    // boundary less than forward + loss and dX chain as two launches, the weight ring never drained in between.
-    constexpr bool TRB = GRAD && STORE == 3;
-    constexpr bool DXE = STORE == 2 || TRB;        // epilogues of dX segments: gate by the stored activation, store
-    constexpr bool G2 = GRAD && STORE == 2;        // lnP + gradient in one launch: nothing of the forward half goes to global memory
-    // the gates are sign bits in LDS (NsArgs::nbw).  The merged training launch can gate the same way (LB = G2 || TRB: its
-    // launcher fills gbit / mbit), measured SLOWER on its 4-row engine (155.4 against 152.4 us per step at (26,457): the
-    // gate loads are not what its run ends wait for, the ballots and bit writes of every forward epilogue are extra) -- off.
-    constexpr bool LB = G2;
-    constexpr bool LATE_REFILL = true;             // see `step`
-    static_assert(ROWS == 16 || ROWS == 8 || ROWS == 4, "rows per workgroup");
-    static_assert(R % 2 == 0, "the A double buffer alternates with the ring slot parity");
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int LD = a.LD, ABUF = ROWS * LD;
-    // The per-segment tables are indexed at run time.  Through `a` (a by-value argument) such an index makes the compiler
-    // keep a private copy of the whole 2.3 KB block whenever it cannot split it -- scratch traffic at every run end, and which
-    // instantiation is hit changes with unrelated edits (STORE == 1 on the 16-row engine in round 2, the merged training
-    // launch with the refill one slot back in round 3).  Through the kernel-argument segment itself they are scalar loads.
-    // (Only in the instantiations where that copy has appeared -- the training ones: the serving ones and the one-launch
-    // gradient lose 0.3-0.7 % to the explicit pointer; tests/test_abi.py watches every kernel's scratch size.)
-    constexpr bool KA = STORE == 3 || STORE == 1 || GRAD;    // (R4: every GRAD instantiation -- G2 since it holds SIDE code, the MLP gradient since the short-second-pass selects)
-    const NsArgs* const ka = KA ? reinterpret_cast<const NsArgs*>((const void*)__builtin_amdgcn_kernarg_segment_ptr()) : &a;
-    float* const act = smem;                       // [2][ROWS][LD]
-    float* const lbias = smem + 2 * ABUF;          // packed biases of every segment
-    unsigned* const lbits = reinterpret_cast<unsigned*>(smem + a.bits_off);   // G2: sign bits [ROWS][nbw]
-    const int nbw = a.nbw;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int li = lane & 15, kq = lane >> 4;
-    const int row0 = blockIdx.x * ROWS;
-    if (a.gate && a.gate[0] == 0) return;
-    // MOVE == 2 with a row list (the later rounds of linna_slice_half_step): only the trial points of the walkers still
-    // active are evaluated -- row r of the launch is trial point mv_C[r] (= j ns + k), mv_step[0] * mv_step_off rows in
-    // all, counted on the device; the workgroups behind them leave at once
-    int mv_rows = a.B;
-    if constexpr (MOVE == 2) {
-        if (a.mv_C) {
-            mv_rows = a.mv_step[0] * a.mv_step_off;
-            if (row0 >= mv_rows) return;
-        }
-    }
-    if constexpr ((STORE == 2 && !GRAD) || TRB) {
-        if ((a.p_n > 0 || a.p_step) && blockIdx.x == gridDim.x - 1) {
-            // sum_scale_prepare_kernel's arithmetic in its order: 1024 strided partial sums (two per thread here),
-            // sixteen wave sums, added in wave order
-            float* const part = smem;
-            float acc0 = 0.f, acc1 = 0.f;
-            for (int i = tid; i < a.p_n; i += 1024) acc0 += a.p_rows[i];
-            for (int i = tid + 512; i < a.p_n; i += 1024) acc1 += a.p_rows[i];
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) { acc0 += __shfl_xor(acc0, o, 64); acc1 += __shfl_xor(acc1, o, 64); }
-            if (lane == 0) { part[wave] = acc0; part[8 + wave] = acc1; }
-            __syncthreads();
-            if (tid == 0 && a.p_out) {
-                float t = 0.f;
-                for (int w = 0; w < 16; ++w) t += part[w];
-                a.p_out[0] = t * a.p_scale;
-            }
-            if (tid == 64 && a.p_step) {
-                const int t = ++a.p_step[0];
-                a.p_hyper[2] = (float)(1.0 - pow((double)a.p_b1, (double)t));
-                a.p_hyper[3] = (float)sqrt(1.0 - pow((double)a.p_b2, (double)t));
-            }
-            return;
-        }
-    }
-#ifdef NS_STAMPS
-    unsigned long long* const lstamp = reinterpret_cast<unsigned long long*>(lbias + ((a.bias_total + 3) & ~3) + 32 + (a.x0_keep ? 1024 : 0)) + wave * 32;   // (not for GRAD: its masks live there)
-    int nstamp = 0;
-#define NS_STAMP() do { const unsigned long long t_ = __builtin_readcyclecounter(); \
-        if (lane == 0 && nstamp < 32) lstamp[nstamp] = t_; ++nstamp; } while (0)
-#define NS_STAMPS_FLUSH() do { if (lane < 32) a.stamps[((size_t)blockIdx.x * NW + wave) * 32 + lane] = lane < nstamp ? lstamp[lane] : 0ull; } while (0)
-#else
-#define NS_STAMP() do {} while (0)
-#define NS_STAMPS_FLUSH() do {} while (0)
-#endif
-    NS_STAMP();
-
-    // ---- 1. every small load of the kernel, up front, straight-line (no branch on a loaded value)
-    const int prt = tid / RG, pc0 = tid % RG;
-    const bool prow = prt < ROWS;                   // (ROWS < 16: the thread rows past ROWS only keep the barriers company)
-    const int pr = SM ? min(prt, ROWS - 1) : prt;
-    int grow = min(row0 + pr, a.B - 1);
-    if constexpr (MOVE == 2) {
-        if (a.mv_C) grow = a.mv_C[min(row0 + pr, mv_rows - 1)];     // the trial point this row evaluates
-    }
-    int zsrc = grow;                                // STORE == 3: the row of the resident set this batch row is
-    float zden = 1.f;
-    if constexpr (STORE == 3) {
-        zsrc = a.t_rows ? a.t_rows[grow] : grow;
-        zden = a.t_den[zsrc];
-    }
-    const int kpad0 = a.kpad0, nin = a.nin, nout = a.nout, nseg = a.nseg;
-    const int nlast = (TRB ? a.nseg_f : nseg) - 2;  // STORE == 3: the network's last layer (the loss segment follows it)
-    constexpr int ZPRE = 2;
-    float zr[ZPRE], za1[ZPRE], za2[ZPRE], zxm[ZPRE], zxs[ZPRE]; int zfl[ZPRE], zlg[ZPRE];
-    const int* const lgp = a.lg ? a.lg : a.is_flat;
-    int mv_wk = 0; float mv_factor = 0.f, mv_lnp_old = 0.f, mv_logu = 0.f;
-    if constexpr (MOVE == 1) {
-        mv_wk = a.mv_S[grow];
-        const U4 rb = walker_bits(a.mv_seed, (uint32_t)mv_wk, (uint32_t)(a.mv_step[0] + a.mv_step_off), (uint32_t)a.mv_stream, 0u);
-        const float t = (a.mv_a - 1.f) * u01(rb.x) + 1.f;
-        const float zf = t * t / a.mv_a;
-        const int j = (int)(((uint64_t)rb.y * (uint64_t)a.mv_nc) >> 32);
-        const int wc = a.mv_C[j];
-        mv_factor = ((float)nin - 1.f) * logf(zf);
-        mv_logu = logf(u01(rb.z));
-        mv_lnp_old = a.mv_logp[mv_wk];
-#pragma unroll
-        for (int i = 0; i < ZPRE; ++i) {
-            const int c = min(pc0 + i * RG, nin - 1);
-            const float cr = a.mv_cc[(size_t)wc * a.mv_ldcc + c], sx = a.mv_coords[(size_t)mv_wk * a.mv_ldc + c];
-            zr[i] = cr - (cr - sx) * zf;
-        }
-    }
-    if constexpr (MOVE == 2) {
-        // trial points of the ensemble slice sampler, never written to memory: row j*ns + k is
-        // coords[S[k]] + w[j*ns + k] * DIR[k]   (what linna_slice_points materialises)
-        const int k = grow % a.mv_nc;                                   // mv_nc: ns (walkers per half ensemble)
-        const int wk = a.mv_S[k];
-        float wgt;
-        if (a.sb.logp) {
-            // slice_begin_kernel's arithmetic, per row: two distinct complementary walkers, the direction between them, a uniform
-            // height under the density, a unit bracket placed uniformly around 0; this row's end of it, jt steps out
-            const SliceBegin& b = a.sb;
-            const int jt = grow / a.mv_nc;
-            const U4 rb = walker_bits(b.seed, (uint32_t)wk, (uint32_t)b.step[0], (uint32_t)b.half, 0u);
-            const int ia = (int)(((uint64_t)rb.x * (uint64_t)b.nc) >> 32);
-            int ib = (int)(((uint64_t)rb.y * (uint64_t)(b.nc - 1)) >> 32);
-            ib += (ib >= ia);
-            const int wa = b.C[ia], wb = b.C[ib];
-            const float mu = b.mu[0];
-            const float l = -u01(rb.w);
-            wgt = jt < b.m ? l - (float)jt : l + 1.f + (float)(jt - b.m);
-            const bool first = jt == 0 && prow && row0 + pr < a.B;      // the rows that write the walker's state for the later launches
-#pragma unroll
-            for (int i = 0; i < ZPRE; ++i) {
-                const int c = min(pc0 + i * RG, nin - 1);
-                const float dir = mu * (b.cc[(size_t)wa * b.ldcc + c] - b.cc[(size_t)wb * b.ldcc + c]);
-                zr[i] = a.mv_coords[(size_t)wk * a.mv_ldc + c] + wgt * dir;
-                if (first && pc0 + i * RG < nin) b.DIR[(size_t)k * b.ldd + c] = dir;
-            }
-            if (first && pc0 == 0) {
-                b.Z0[k] = b.logp[wk] + logf(u01(rb.z));
-                b.L[k] = l; b.R[k] = l + 1.f;
-                int J, K;
-                slice_budget(b.seed, (uint32_t)wk, (uint32_t)b.step[0], (uint32_t)b.half, b.maxsteps, J, K);
-                b.flags[3 * k] = J; b.flags[3 * k + 1] = K; b.flags[3 * k + 2] = 1;
-            }
-            if (blockIdx.x == 0 && tid == 0) {
-                for (int i = 0; i < b.nslots; ++i) {       // [4 + nslots + i]: the same counts summed over the calls so far (usage statistics)
-                    b.counters[4 + b.nslots + i] += b.counters[4 + i];
-                    b.counters[4 + i] = 0;
-                }
-                b.counters[4 + 2 * b.nslots] += 1;         // calls
-                if (b.zero_totals) { b.counters[0] = 0; b.counters[1] = 0; }
-            }
-        } else {
-        if (a.sl_Zt) {
-            // lanes 0 .. 2 m - 1 of the row's 32 hold "lnP at bracket end j exceeds Z0"; the count of leading ones per side is
-            // the number of steps out.  Lane i < nt holds the uniform of trial i; the row walks the trials up to its own.
-            const int ns_ = a.mv_nc, m = a.sl_m, jt = grow / ns_;
-            const float z0 = a.sl_Z0[k];
-            const float zend = a.sl_Zt[(size_t)min(pc0, 2 * m - 1) * ns_ + k];
-            const unsigned long long bal = __ballot(pc0 < 2 * m && zend > z0);
-            const unsigned bits = (unsigned)(bal >> (lane & 32));
-            const unsigned lm = bits & ((1u << m) - 1u), rm = (bits >> m) & ((1u << m) - 1u);
-            // (never more steps than the budget of that side has left: slice_side_steps in common.h)
-            const int nl = min(__builtin_ctz(~lm), a.sl_flags[3 * k]), nr = min(__builtin_ctz(~rm), a.sl_flags[3 * k + 1]);
-            float l = a.sl_L[k], r = a.sl_R[k];
-            for (int j = 0; j < m; ++j) {                               // (one unit at a time: the rounding of slice_expand_multi_kernel)
-                if (j < nl) l -= 1.f;
-                if (j < nr) r += 1.f;
-            }
-            const U4 tb = walker_bits(a.sl_seed, (uint32_t)wk, (uint32_t)a.sl_step[0], (uint32_t)a.sl_stream, (uint32_t)(pc0 + 1));
-            const int myu = __float_as_int(u01(tb.x));
-            wgt = 0.f;
-            for (int jj = 0; jj < a.sl_nt; ++jj) {
-                const int ulo = __builtin_amdgcn_readlane(myu, jj), uhi = __builtin_amdgcn_readlane(myu, 32 + jj);
-                const float u = __int_as_float((lane & 32) ? uhi : ulo);
-                const float w = l + u * (r - l);
-                if (jj == jt) wgt = w;
-                if (jj < jt) { if (w < 0.f) l = w; else r = w; }
-            }
-        } else {
-            wgt = a.mv_cc[grow];                                        // mv_cc: w[nrep * ns]
-        }
-#pragma unroll
-        for (int i = 0; i < ZPRE; ++i) {
-            const int c = min(pc0 + i * RG, nin - 1);
-            zr[i] = a.mv_coords[(size_t)wk * a.mv_ldc + c] + wgt * a.Z[(size_t)k * a.ldz + c];   // Z: DIR[ns][ldz]
-        }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < ZPRE; ++i) {
-        const int c = min(pc0 + i * RG, nin - 1);
-        if constexpr (MOVE == 0) zr[i] = a.Z[(size_t)(STORE == 3 ? zsrc : grow) * a.ldz + c];
-        zfl[i] = a.is_flat[c]; za1[i] = a.a1[c]; za2[i] = a.a2[c];
-        zlg[i] = lgp[c]; zxm[i] = a.xmean[c]; zxs[i] = a.xstd[c];
-    }
-    const int nb4 = (a.bias_total + 3) >> 2;       // packed biases, 16 bytes per thread and round
-    const f32x4* const bsrc = reinterpret_cast<const f32x4*>(a.packed + (size_t)NW * a.Gstride * NT * 256);
-    constexpr int BMAX = 3;                        // 3 x 512 x 4 floats >= every eligible network's biases
-    f32x4 breg[BMAX];
-#pragma unroll
-    for (int i = 0; i < BMAX; ++i) {
-        const int j = tid + i * 64 * NW;
-        breg[i] = bsrc[min(j, nb4 - 1)];
-    }
-    constexpr int FIN = 2;
-    const float* const csp = a.cscale ? a.cscale : a.xmean;   // always a readable pointer
-    const float* const ctp = a.cshift ? a.cshift : a.xmean;
-    const float* const wtp = a.w ? a.w : a.xmean;
-    float fcs[FIN], fct[FIN], fw[FIN], fgs[FIN];
-#pragma unroll
-    for (int i = 0; i < FIN; ++i) {
-        const int cc = min(pc0 + i * RG, nout - 1);
-        if constexpr (GRAD && !TRB) fgs[i] = a.gscale[cc]; else fgs[i] = 0.f;
-        const int c1 = a.cscale ? cc : 0, c2 = a.cshift ? cc : 0, c3 = a.w ? cc : 0;
-        const float cs = csp[c1], ct = ctp[c2], ww = wtp[c3];
-        fcs[i] = a.cscale ? cs : 1.f; fct[i] = a.cshift ? ct : 0.f; fw[i] = a.w ? ww : 0.f;
-    }
-
-    // ---- 2. weight stream: wave-uniform base + 32-bit per-lane offset + immediate
-    const char* const wbase = reinterpret_cast<const char*>(a.packed) + (size_t)wave * a.Gstride * NS_STEP_B;
-    const unsigned wlast = (unsigned)(a.G - 1) * NS_STEP_B;
-    unsigned woff = 0;
-    const unsigned voff = 16u * (unsigned)lane;
-    f32x4 Bq[R][NT];
-    auto wload = [&](int t) { return *reinterpret_cast<const f32x4*>(wbase + (size_t)(voff + woff) + t * 1024); };
-    auto wadvance = [&]() { woff = min(woff + NS_STEP_B, wlast); };   // past the end: reload the last step (never used)
-    constexpr int PRE = NS_PRE < R ? NS_PRE : R;
-    auto prefetch = [&](auto Uc) {
-        constexpr int U = decltype(Uc)::value;
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            Bq[U][t] = wload(t);
-            __builtin_amdgcn_sched_barrier(0);     // keep the issue order: the loop's counted vmcnt depends on it
-        }
-        wadvance();
-    };
-#define NS_PF(U, LO, HI) if constexpr (U >= LO && U < HI) prefetch(std::integral_constant<int, U>{});
-#define NS_PF_ALL(LO, HI) NS_PF(0, LO, HI) NS_PF(1, LO, HI) NS_PF(2, LO, HI) NS_PF(3, LO, HI) NS_PF(4, LO, HI) NS_PF(5, LO, HI) \
-    NS_PF(6, LO, HI) NS_PF(7, LO, HI)
-    NS_PF_ALL(0, PRE)
-#ifdef NS_STAMPS_FINE
-    NS_STAMP();                                    // every small load and the first weight slots requested
-#endif
-
-    // ---- 3. network input x = X_transform(Transform(z)) into buffer 0, zero padded to kpad0; biases to LDS
-    float zz = 0.f;
-    float theta[ZPRE];
-#pragma unroll
-    for (int i = 0; i < ZPRE; ++i) {
-        const int c = pc0 + i * RG;
-        const bool in = c < nin;
-        const float z = in ? zr[i] : 0.f;
-        zz += z * z;
-        float th = ns_prior_theta(z, zfl[i], za1[i], za2[i]);
-        float lt = log10f(th);
-        asm volatile("" : "+v"(lt));
-        theta[i] = th;
-        const float t = (a.lg && zlg[i]) ? lt : th;
-        float x = in ? (t - zxm[i]) / zxs[i] : 0.f;
-        if constexpr ((STORE == 1 || STORE == 2) && !GRAD) x = z;   // rows arrive transformed
-        if constexpr (STORE == 3) {                 // X_transform of a gathered row (util.py:483-497), as linna_gather_xform
-            float lz = log10f(z);
-            asm volatile("" : "+v"(lz));
-            const float tz = (a.lg && zlg[i]) ? lz : z;
-            x = in ? (tz - zxm[i]) / zxs[i] : 0.f;
-            if (prow && row0 + pr < a.B && c < a.t_ldxb)
-                asm volatile("global_store_dword %0, %1, off" :: "v"(a.t_xb + (size_t)(row0 + pr) * a.t_ldxb + c), "v"(x) : "memory");
-        }
-        if constexpr (BF) {                         // x_hi at c, x_lo at nin + c, zeros from 2 nin (ns_build_one: [W | W])
-            if (prow) {
-                if (in) { const float hi = (float)(__bf16)x; act[pr * LD + c] = hi; act[pr * LD + nin + c] = x - hi; }
-                else if (c >= 2 * nin && c < kpad0) act[pr * LD + c] = 0.f;
-            }
-        } else {
-            if (c < kpad0 && prow) act[pr * LD + c] = x;
-        }
-    }
-#ifdef NS_STAMPS_FINE
-    NS_STAMP();                                    // first 64 input columns transformed and in LDS
-#endif
-    // inputs wider than ZPRE*RG = 64 columns (none of the reference's models; <= 256 supported) and the zero
-    // pad of a SPLIT first segment: plain loop, loads waited in place
-    if constexpr ((STORE == 1 || STORE == 2) && !GRAD) {
-        // rows arrive transformed (the dX chain's input is d loss / d pred, 457 or 1000 columns wide): every thread of the
-        // workgroup copies, four independent loads in flight each -- the per-row loop below waits for every load in place
-        const int wcols = kpad0 - ZPRE * RG;
-        if (wcols > 0) {
-            constexpr int CP = 4;
-            for (int base = 0; base < ROWS * wcols; base += CP * 64 * NW) {
-                float v[CP];
-#pragma unroll
-                for (int u = 0; u < CP; ++u) {
-                    const int idx = min(base + u * 64 * NW + tid, ROWS * wcols - 1);
-                    const int r = idx / wcols, c = ZPRE * RG + idx % wcols;
-                    v[u] = a.Z[(size_t)min(row0 + r, a.B - 1) * a.ldz + min(c, nin - 1)];
-                }
-#pragma unroll
-                for (int u = 0; u < CP; ++u) {
-                    const int idx = base + u * 64 * NW + tid;
-                    if (idx < ROWS * wcols) {
-                        const int r = idx / wcols, c = ZPRE * RG + idx % wcols;
-                        act[r * LD + c] = c < nin ? v[u] : 0.f;
-                    }
-                }
-            }
-        }
-    } else
-#pragma unroll 1
-    for (int c = pc0 + ZPRE * RG; c < kpad0; c += RG) {
-        float x = 0.f;
-        if (c < nin) {
-            const float z = a.Z[(size_t)grow * a.ldz + c];
-            zz += z * z;
-            const float th = ns_prior_theta(z, a.is_flat[c], a.a1[c], a.a2[c]);
-            const float t = (a.lg && a.lg[c]) ? log10f(th) : th;
-            x = (t - a.xmean[c]) / a.xstd[c];
-            if constexpr ((STORE == 1 || STORE == 2) && !GRAD) x = z;
-            if constexpr (STORE == 3) {
-                const float zz3 = a.Z[(size_t)zsrc * a.ldz + c];
-                x = (((a.lg && a.lg[c]) ? log10f(zz3) : zz3) - a.xmean[c]) / a.xstd[c];
-            }
-        }
-        if constexpr (STORE == 3) {
-            if (prow && row0 + pr < a.B && c < a.t_ldxb)
-                asm volatile("global_store_dword %0, %1, off" :: "v"(a.t_xb + (size_t)(row0 + pr) * a.t_ldxb + c), "v"(x) : "memory");
-        }
-        if constexpr (BF) {
-            if (prow) {
-                if (c < nin) { const float hi = (float)(__bf16)x; act[pr * LD + c] = hi; act[pr * LD + nin + c] = x - hi; }
-                else if (c >= 2 * nin) act[pr * LD + c] = 0.f;
-            }
-        } else {
-            if (prow) act[pr * LD + c] = x;
-        }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#ifdef NS_STAMPS_FINE
-    NS_STAMP();                                    // the rest of the input in LDS
-#endif
-    NS_PF_ALL(PRE, (LATE_REFILL ? R - 1 : R))
-#undef NS_PF_ALL
-#undef NS_PF
-#pragma unroll
-    for (int o = RG / 2; o >= 1; o >>= 1) zz += __shfl_xor(zz, o, 64);
-#pragma unroll
-    for (int i = 0; i < BMAX; ++i) {
-        const int j = tid + i * 64 * NW;
-        if (j < nb4) reinterpret_cast<f32x4*>(lbias)[j] = breg[i];
-    }
-    int* const lsrc = reinterpret_cast<int*>(lbias + ((a.bias_total + 3) & ~3));      // STORE == 3: [ROWS] set rows, [ROWS] den
-    float* const lden = reinterpret_cast<float*>(lsrc + 16);
-    if constexpr (STORE == 3) {
-        if (prow && pc0 == 0) { lsrc[pr] = zsrc; lden[pr] = zden; }
-    }
-    float* const lx0 = lden + 16;                  // [ROWS][64]: the input rows, for a later input-skip segment
-    if (a.x0_keep && prow) {
-#pragma unroll
-        for (int i = 0; i < ZPRE; ++i) {
-            const int c = pc0 + i * RG;
-            if constexpr (BF) lx0[pr * 64 + c] = c < nin ? act[pr * LD + c] + act[pr * LD + nin + c] : 0.f;   // x_hi + x_lo = x exactly
-            else lx0[pr * 64 + c] = (c < kpad0) ? act[pr * LD + c] : 0.f;
-        }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();                  // raw: __syncthreads() would drain the weight stream
-    asm volatile("" ::: "memory");
-    NS_STAMP();
-
-    // ---- 4. the step loop
-    const uint32_t act_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)act;
-    f32x4 acc[NACC];
-    f32x4 Aq[2][AK];
-    // 4x4x1 engine: block b = lane >> 2 of the A read holds row set b & 3 (rows wrap below ROWS: never selected), k chunk b >> 2
-    const int sm_arow = (4 * ((lane >> 2) & 3) + (lane & 3)) % ROWS, sm_achunk = lane >> 4;
-    int si = 0, pass = 0, P = 0, kleft;
-    int s_type, s_steps, s_passes, s_bias, s_dst, s_relu, s_kslice, s_zext, s_ncgl, s_mstore = 0, s_mapply = 0, s_x0col = 0, s_x0n = 0, s_kcl = 0;
-    unsigned* const lmask = reinterpret_cast<unsigned*>(lbias + ((a.bias_total + 3) & ~3));   // GRAD: [slot][512 lanes]
-    float lnp_grad = 0.f;                          // GRAD: lnP, stored at the very end (no store next to the weight loads)
-    float* s_gout = nullptr; int s_gld = 0, s_gn = 0;   // STORE: global destination of the current segment's output
-    const float* s_gmask = nullptr; int s_gmld = 0;     // STORE == 2: forward activation gating it
-    int s_gbit = -1, s_mbit = -1;                       // LB: bit column of the signs this segment writes / is gated by
-    auto gstore = [&](float* p, float v) { asm volatile("global_store_dword %0, %1, off" :: "v"(p), "v"(v) : "memory"); };
-    uint32_t ap;
-    auto a_read = [&](f32x4* dst) {
-        asm volatile("ds_read_b128 %0, %1" : "=v"(dst[0]) : "v"(ap) : "memory");
-        if constexpr (BF) asm volatile("ds_read_b128 %0, %1 offset:16" : "=v"(dst[1]) : "v"(ap) : "memory");
-        ap += 64 * AK;
-    };
-    // (kernel-argument arrays are indexed through readfirstlane: one instantiation -- STORE == 1 on the 16-row engine --
-    // could not prove the segment index uniform and copied the whole 2 KB argument block to scratch)
-    auto load_seg = [&]() {
-        const NsSeg S = ka->seg[__builtin_amdgcn_readfirstlane(si)];
-        s_type = S.type; kleft = s_steps = S.steps; s_passes = S.passes; s_bias = S.bias_off;
-        s_dst = S.dst_col; s_relu = S.relu; s_kslice = S.kslice; s_zext = S.zext; s_ncgl = S.ncg_log2; s_x0col = S.x0_col; s_x0n = S.x0_n;
-        if constexpr (GRAD) { s_mstore = S.mask_store; s_mapply = S.mask_apply; }
-        if constexpr (STORE) { const int j = __builtin_amdgcn_readfirstlane(si); s_gout = ka->gout[j]; s_gld = ka->gld[j]; s_gn = ka->gn[j]; }
-        if constexpr (DXE) { const int j = __builtin_amdgcn_readfirstlane(si); s_gmask = ka->gmask[j]; s_gmld = ka->gmld[j]; }
-        if constexpr (LB) { const int j = __builtin_amdgcn_readfirstlane(si); s_gbit = ka->gbit[j]; s_mbit = ka->mbit[j]; }
-    };
-    auto begin_run = [&]() {                       // accumulators and A pointer of run (si, pass)
-        const int arow = SM ? sm_arow : li, ak = AK * (SM ? 4 * sm_achunk : 4 * kq);
-#pragma unroll
-        for (int t = 0; t < NACC; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (s_type == NS_WIDE) {
-            // the wave's 64-column block of this run: 8 pass + wave -- or, balanced triangular factor (zext < 0), w then 15 - w
-            const int blk = s_zext < 0 ? (pass ? 15 - wave : wave) : 8 * pass + wave;
-            if constexpr (SM) {
-                const float b = lbias[s_bias + 64 * blk + lane];
-#pragma unroll
-                for (int r = 0; r < RS; ++r) acc[4 * r] = f32x4{b, b, b, b};
-            } else {
-#pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    const float b = lbias[s_bias + 16 * (4 * blk + t) + li];
-                    acc[t] = f32x4{b, b, b, b};
-                }
-            }
-            if (s_zext < 0) kleft = s_steps - 4 * blk;             // its rows start at 64 blk
-            ap = act_lds + 4u * (uint32_t)(P * ABUF + arow * LD + ak + (s_zext < 0 ? 64 * blk : (pass ? s_kslice : 0)));   // (kslice: 0 but for a short second pass)
-        } else {
-            ap = act_lds + 4u * (uint32_t)(P * ABUF + arow * LD + ak + (wave >> s_ncgl) * s_kslice);
-        }
-    };
-    auto lds_barrier = [&]() {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-    };
-    load_seg();
-    begin_run();
-    a_read(Aq[0]);
-
-    auto step = [&](auto Uc, auto Refill) {
-        constexpr int U = decltype(Uc)::value;
-        constexpr bool refill = decltype(Refill)::value;
-        // the refill of this step goes to the slot the PREVIOUS step consumed: a load whose target the MFMAs just issued
-        // still read waits for them at issue (measured: the same loads one slot back, 1.2-1.4 % off every launch; R - 1
-        // steps are in flight instead of R).  Not in the merged training launch: its register allocation does not survive
-        // the longer slot lifetimes (2.3 KB of scratch per lane, +40 % on the step).
-        constexpr int RU = LATE_REFILL ? (U + R - 1) % R : U;
-        if constexpr (BF) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(Aq[U & 1][0]), "+v"(Aq[U & 1][AK - 1]) :: "memory");
-        else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(Aq[U & 1][0]) :: "memory");
-        a_read(Aq[(U + 1) & 1]);                   // next step's A (speculative at a run end)
-        const f32x4 av = Aq[U & 1][0];
-        if constexpr (BF) {
-            // A rounded to bf16 where it is read: k 8 j + e of the lane's 8 (j = 0, 1: the two fragments)
-            bf16x8 ab;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { ab[e] = (__bf16)Aq[U & 1][0][e]; ab[4 + e] = (__bf16)Aq[U & 1][AK - 1][e]; }
-            if constexpr (SM) {
-                // acc[4 r + c] += A(row set r, k chunk c, half h) x B(chunk c = load c, half h); ABID = block 4 c + r
-                const s16x4 alo = __builtin_bit_cast(s16x4, __builtin_shufflevector(ab, ab, 0, 1, 2, 3));
-                const s16x4 ahi = __builtin_bit_cast(s16x4, __builtin_shufflevector(ab, ab, 4, 5, 6, 7));
-#define NS_B4(r, c, h, A4) acc[4 * (r) + (c)] = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(A4, \
-                __builtin_bit_cast(s16x4, __builtin_shufflevector(__builtin_bit_cast(bf16x8, Bq[U][c]), __builtin_bit_cast(bf16x8, Bq[U][c]), \
-                                                                  4 * (h), 4 * (h) + 1, 4 * (h) + 2, 4 * (h) + 3)), acc[4 * (r) + (c)], 4, 4 * (c) + (r), 0);
-#define NS_B4R(r, h, A4) NS_B4(r, 0, h, A4) NS_B4(r, 1, h, A4) NS_B4(r, 2, h, A4) NS_B4(r, 3, h, A4)
-                NS_B4R(0, 0, alo)
-                if constexpr (RS > 1) { NS_B4R(1, 0, alo) }
-                NS_B4R(0, 1, ahi)
-                if constexpr (RS > 1) { NS_B4R(1, 1, ahi) }
-#undef NS_B4R
-#undef NS_B4
-                if constexpr (refill) {
-#pragma unroll
-                    for (int t = 0; t < NT; ++t) Bq[RU][t] = wload(t);
-                }
-            } else {
-#pragma unroll
-                for (int h = 0; h < NT; h += 2) {
-                    acc[h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab, __builtin_bit_cast(bf16x8, Bq[U][h]), acc[h], 0, 0, 0);
-                    acc[h + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab, __builtin_bit_cast(bf16x8, Bq[U][h + 1]), acc[h + 1], 0, 0, 0);
-                    if constexpr (refill) {
-                        Bq[RU][h] = wload(h);
-                        Bq[RU][h + 1] = wload(h + 1);
-                    }
-                }
-            }
-        } else if constexpr (SM) {
-            // acc[4 r + c] += A(rows of set r, k chunk c, element e) x B(k chunk c = load c, element e); ABID = block 4 c + r
-#define NS_M4(r, c, e) acc[4 * (r) + (c)] = __builtin_amdgcn_mfma_f32_4x4x1f32(av[e], Bq[U][c][e], acc[4 * (r) + (c)], 4, 4 * (c) + (r), 0);
-#define NS_M4R(r, e) NS_M4(r, 0, e) NS_M4(r, 1, e) NS_M4(r, 2, e) NS_M4(r, 3, e)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                NS_M4R(0, e)
-                if constexpr (RS > 1) { NS_M4R(1, e) }
-            }
-#undef NS_M4R
-#undef NS_M4
-            if constexpr (refill) {
-#pragma unroll
-                for (int t = 0; t < NT; ++t) Bq[RU][t] = wload(t);
-            }
-        } else {
-#pragma unroll
-            for (int h = 0; h < NT; h += 2) {
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    acc[h] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], Bq[U][h][s], acc[h], 0, 0, 0);
-                    acc[h + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s], Bq[U][h + 1][s], acc[h + 1], 0, 0, 0);
-                }
-                if constexpr (refill) {
-                    Bq[RU][h] = wload(h);
-                    Bq[RU][h + 1] = wload(h + 1);
-                }
-            }
-        }
-        if constexpr (refill) wadvance();
-        if (--kleft == 0) {
-            // ---- end of run (si, pass).  The next segment's descriptor is requested first: the scalar
-            // load's latency then hides under the epilogue stores and the barrier.
-            const int nxi = __builtin_amdgcn_readfirstlane(min(si + 1, nseg - 1));
-            const NsSeg NX = ka->seg[nxi];
-            float* nx_gout = nullptr; int nx_gld = 0, nx_gn = 0;
-            const float* nx_gmask = nullptr; int nx_gmld = 0;
-            if constexpr (STORE) { nx_gout = ka->gout[nxi]; nx_gld = ka->gld[nxi]; nx_gn = ka->gn[nxi]; }
-            if constexpr (DXE) { nx_gmask = ka->gmask[nxi]; nx_gmld = ka->gmld[nxi]; }
-            int nx_gbit = -1, nx_mbit = -1;
-            if constexpr (LB) { nx_gbit = ka->gbit[nxi]; nx_mbit = ka->mbit[nxi]; }
-            const int cur_steps = s_steps;
-            auto take_seg = [&](const NsSeg& X) {
-                s_type = X.type; s_steps = X.steps; s_passes = X.passes; s_bias = X.bias_off;
-                s_dst = X.dst_col; s_relu = X.relu; s_kslice = X.kslice; s_zext = X.zext; s_ncgl = X.ncg_log2; s_x0col = X.x0_col; s_x0n = X.x0_n;
-                if constexpr (K4) s_kcl = X.kcl;
-                if constexpr (GRAD) { s_mstore = X.mask_store; s_mapply = X.mask_apply; }
-                kleft = X.steps;
-            };
-            auto take_next = [&]() {
-                take_seg(NX);
-                if constexpr (STORE) { s_gout = nx_gout; s_gld = nx_gld; s_gn = nx_gn; }
-                if constexpr (DXE) { s_gmask = nx_gmask; s_gmld = nx_gmld; }
-                if constexpr (LB) { s_gbit = nx_gbit; s_mbit = nx_mbit; }
-            };
-            // SIDE segment next (and this run is its predecessor's last): its weights are requested NOW, by loads the compiler
-            // does not see, so that they fly under this segment's epilogue and barrier
-            f32x4 sdw[2][NT];
-            bool side_next = false;
-            if constexpr (K4) {
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-                    for (int t = 0; t < NT; ++t) sdw[s2][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-                if (NX.type == NS_SIDE && si + 1 < nseg && (s_type != NS_WIDE || pass + 1 == s_passes)) {
-                    side_next = true;
-                    const char* const sb = reinterpret_cast<const char*>(a.packed + NX.side_off) + (size_t)wave * NX.steps * NS_STEP_B + voff;
-#pragma unroll
-                    for (int t = 0; t < NT; ++t)
-                        asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(sdw[0][t]) : "v"(sb + t * 1024) : "memory");
-                    if (NX.steps > 1) {
-#pragma unroll
-                        for (int t = 0; t < NT; ++t)
-                            asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(sdw[1][t]) : "v"(sb + NS_STEP_B + t * 1024) : "memory");
-                    }
-                }
-            }
-            bool seg_done = true;
-#ifdef NS_STAMPS_FINE
-            const bool fine = si >= NS_STAMPS_FINE && si < NS_STAMPS_FINE + 4;
-            if (fine) NS_STAMP();                  // run end reached (last MFMA issued)
-#endif
-            // result quads: fin[q][e] is (row, column) = SM ? (4 q + e, lane) : (4 kq + e, 16 q + li) of the wave's 64 columns
-            if constexpr (SM) {
-#pragma unroll
-                for (int q = 0; q < NQ; ++q) acc[q] = (acc[4 * q] + acc[4 * q + 1]) + (acc[4 * q + 2] + acc[4 * q + 3]);
-            }
-#define fin acc
-#define q_row(q, e) (SM ? 4 * (q) + (e) : 4 * kq + (e))
-#define q_col(q) (SM ? lane : 16 * (q) + li)
-            if (s_type == NS_WIDE) {
-                float* const nxt = act + (P ^ 1) * ABUF + s_dst + (s_zext < 0 ? 64 * (pass ? 15 - wave : wave) : 512 * pass + 64 * wave);
-                // STORE == 3, last network layer: the targets and the per-column constants of delta, fetched by inline-asm
-                // loads the compiler does not count (a visible load in this loop body would turn its counted vmcnt waits
-                // for the weight ring into vmcnt(0) in EVERY step); one explicit wait for all of them
-                float ty[NQ][4];                        // STORE == 3: normalised targets; STORE == 2: gates
-                if constexpr (STORE == 3) {
-                    if (si == nlast) {
-#pragma unroll
-                        for (int t = 0; t < NQ; ++t) {
-                            const int dc = min(512 * pass + 64 * wave + q_col(t), nout - 1);
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                const float* py = a.t_Y + (size_t)lsrc[q_row(t, e)] * a.t_ldy + dc;
-                                asm volatile("global_load_dword %0, %1, off" : "=v"(ty[t][e]) : "v"(py) : "memory");
-                            }
-                        }
-#pragma unroll
-                        for (int t = 0; t < NQ; ++t)
-                            asm volatile("s_waitcnt vmcnt(0)" : "+v"(ty[t][0]), "+v"(ty[t][1]), "+v"(ty[t][2]), "+v"(ty[t][3]) :: "memory");
-                    }
-                }
-                unsigned long long gw[SM ? NQ : 1][4];      // G2: the 64 sign bits of this wave's columns, per result row
-                if constexpr (LB) {
-                    if (s_mbit >= 0) {
-                        const int cw = 512 * pass + 64 * wave, w0 = (s_mbit + cw) >> 5;
-                        const bool mine = cw < ((s_gn + 63) & ~63);             // (past the tensor: padding columns, their gradients are zero)
-#pragma unroll
-                        for (int t = 0; t < (SM ? NQ : 1); ++t)
-#pragma unroll
-                            for (int e = 0; e < 4; ++e)
-                                gw[t][e] = mine ? *reinterpret_cast<const unsigned long long*>(lbits + (SM ? 4 * t + e : 4 * kq + e) * nbw + w0) : 0ull;
-                    }
-                }
-                if constexpr (DXE && !LB) {
-                    // the gates (stored forward activations), by loads the compiler does not count -- a visible load in this
-                    // loop body makes every step's wait for the weight ring a vmcnt(0) -- with one explicit wait
-                    if (s_gmask) {
-#pragma unroll
-                        for (int t = 0; t < NQ; ++t) {
-                            const int mc = min(512 * pass + 64 * wave + q_col(t), s_gn - 1);
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                const float* pg = s_gmask + (size_t)min(row0 + q_row(t, e), a.B - 1) * s_gmld + mc;
-                                if constexpr (GRAD)     // written earlier in this very launch: served by the L2, not this CU's L1
-                                    asm volatile("global_load_dword %0, %1, off sc1" : "=v"(ty[t][e]) : "v"(pg) : "memory");
-                                else
-                                    asm volatile("global_load_dword %0, %1, off" : "=v"(ty[t][e]) : "v"(pg) : "memory");
-                            }
-                        }
-#pragma unroll
-                        for (int t = 0; t < NQ; ++t)
-                            asm volatile("s_waitcnt vmcnt(0)" : "+v"(ty[t][0]), "+v"(ty[t][1]), "+v"(ty[t][2]), "+v"(ty[t][3]) :: "memory");
-                    }
-                }
-                unsigned mbits = 0xFFFFu;
-                if constexpr (GRAD) {
-                    if (s_mapply) mbits = lmask[(s_mapply - 1 + pass) * (64 * NW) + threadIdx.x];   // sign bits of this very (row, col)
-                    if (s_mstore) {
-                        unsigned m = 0;
-#pragma unroll
-                        for (int t = 0; t < NQ; ++t)
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) m |= (fin[t][e] > 0.f ? 1u : 0u) << (4 * t + e);
-                        lmask[(s_mstore - 1 + pass) * (64 * NW) + threadIdx.x] = m;
-                    }
-                }
-#pragma unroll
-                for (int t = 0; t < NQ; ++t)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {  // 16x16x4 C/D layout: col = lane&15, row = 4*(lane>>4) + e; 4x4x1: col = lane, row = 4 t + e
-                        float v = fin[t][e];
-                        if constexpr (GRAD) v = ((mbits >> (4 * t + e)) & 1u) ? v : 0.f;
-                        v = s_relu ? fmaxf(v, 0.f) : v;
-                        if constexpr (LB) {
-                            if (s_mbit >= 0 && !((gw[SM ? t : 0][e] >> (SM ? lane : 16 * t + li)) & 1ull)) v = 0.f;
-                        } else if constexpr (DXE) {
-                            if (s_gmask && !(ty[t][e] > 0.f)) v = 0.f;
-                        }
-                        float v_lds = v;
-                        if constexpr (STORE == 3) {
-                            if (si == nlast) {                 // the network's last layer: delta replaces pred in LDS
-                                const int dc = 512 * pass + 64 * wave + q_col(t);
-                                const float yn = ty[t][e];
-                                v_lds = dc < nout ? (isnan(yn) ? -0.f : (yn - v) + 0.f) : 0.f;   // -0: "masked", read back by the finish
-                            }
-                        }
-                        nxt[q_row(t, e) * LD + q_col(t)] = v_lds;
-                        if constexpr (LB) {
-                            if (s_gbit >= 0) {                 // the sign of this activation, for the gate of its gradient
-                                const unsigned long long bb = __ballot(v > 0.f);
-                                const int cw = 512 * pass + 64 * wave;          // (a wave whose 64 columns lie past the tensor's
-                                const bool mine = cw < ((s_gn + 63) & ~63);     //  bit range writes nothing: the next row's bits, or the
-                                const int c0 = s_gbit + cw;                     //  neighbouring workgroup's LDS, sit there)
-                                if constexpr (SM) {            // lane = column: 64 columns of row 4 t + e
-                                    if (lane == 0 && mine) *reinterpret_cast<unsigned long long*>(lbits + (4 * t + e) * nbw + (c0 >> 5)) = bb;
-                                } else {                       // 16 columns of tile t for each of the rows 4 kq + e
-                                    if (li == 0 && mine) reinterpret_cast<unsigned short*>(lbits + (4 * kq + e) * nbw)[(c0 + 16 * t) >> 4] = (unsigned short)(bb >> (16 * kq));
-                                }
-                            }
-                        }
-                        if constexpr (STORE && !G2) {
-                            const int grow_ = row0 + q_row(t, e), gcol = 512 * pass + 64 * wave + q_col(t);
-                            if (s_gout && grow_ < a.B && gcol < s_gn) {
-                                float vs = v;                      // the network's last output carries the column affine
-                                if constexpr (STORE == 1)
-                                    if (si == nseg - 1) vs = vs * (a.cscale ? a.cscale[gcol] : 1.f) + (a.cshift ? a.cshift[gcol] : 0.f);
-                                gstore(s_gout + (size_t)grow_ * s_gld + gcol, vs);
-                            }
-                        }
-                    }
-#ifdef NS_STAMPS_FINE
-                if (fine) NS_STAMP();              // epilogue done (LDS writes and stores issued)
-#endif
-                if (++pass == s_passes) {
-                    lds_barrier();
-                    NS_STAMP();
-                    P ^= 1; pass = 0; ++si;
-                    take_next();
-                } else {
-                    kleft = s_zext > 0 ? s_zext : cur_steps;    // (a short second pass: NsSeg::zext)
-                    seg_done = false;
-                }
-            } else {
-                // [8 waves][ROWS][64 cols]; the column is swizzled per row so that the reduce below reads without bank
-                // conflicts: col ^= 16*(row>>2) (16 rows), col ^= 32*(row&1) (4x4x1 engines)
-                float* const part = act + (P ^ 1) * ABUF;
-                constexpr int PW = ROWS * 64;
-#pragma unroll
-                for (int t = 0; t < NQ; ++t)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int rr = q_row(t, e);
-                        part[wave * PW + rr * 64 + (q_col(t) ^ (SM ? 32 * (rr & 1) : 16 * kq))] = fin[t][e];
-                    }
-#ifdef NS_STAMPS_FINE
-                if (fine) NS_STAMP();              // partials written (issued)
-#endif
-                lds_barrier();
-#ifdef NS_STAMPS_FINE
-                if (fine) NS_STAMP();              // first barrier passed
-#endif
-                // thread (row sr, lane sc0 of RGS): columns sc0, sc0+RGS, ...; wave of (K part kp, group cg) = kp*ncg + cg.
-                // 16 rows: the prologue's 32 threads per row; 8 / 4 rows: ALL 512 threads, 64 / 128 per row (with 32 per row
-                // three quarters of a 4-row workgroup watched the other quarter reduce)
-                constexpr int RGS = SM ? 64 * NW / ROWS : RG;
-                const int sr = SM ? tid / RGS : pr, sc0 = SM ? tid % RGS : pc0;
-                const bool srow = SM ? true : prow;
-                float* const cur = act + P * ABUF + sr * LD + s_dst;
-                const int ncol = 64 << s_ncgl, nkp = NW >> s_ncgl;
-                const int sw = SM ? 32 * (sr & 1) : 16 * (sr >> 2);
-                constexpr int NGJ = 256 / RGS;          // (SPLIT outputs are <= 256 columns: 8 / 4 / 2 per thread)
-                float sg[NGJ];
-                if constexpr (DXE && !LB) {
-                    if (s_gmask) {
-#pragma unroll
-                        for (int j = 0; j < NGJ; ++j) {
-                            const float* pg = s_gmask + (size_t)min(row0 + sr, a.B - 1) * s_gmld + min(sc0 + RGS * j, s_gn - 1);
-                            if constexpr (GRAD)
-                                asm volatile("global_load_dword %0, %1, off sc1" : "=v"(sg[j]) : "v"(pg) : "memory");
-                            else
-                                asm volatile("global_load_dword %0, %1, off" : "=v"(sg[j]) : "v"(pg) : "memory");
-                        }
-#pragma unroll
-                        for (int j = 0; j < NGJ; ++j) asm volatile("s_waitcnt vmcnt(0)" : "+v"(sg[j]) :: "memory");
-                    }
-                }
-                int gj = 0;
-                if constexpr ((!LB && !DXE && !STORE) || (LB && !SM)) {
-                    // serving (and the one-launch gradient on the 16-row engine): FOUR adjacent columns per thread and trip, as 16-byte LDS accesses (the swizzle moves whole groups of
-                    // 16 / 32 columns, the biases start at multiples of 64): a quarter of the LDS instructions of the column-per-
-                    // trip loop below, and all K parts of a trip in flight -- 256 output columns were 8 trips of ~130 cycles
-                    // each behind the barrier.  The sums in the order of the loop below.
-                    auto reduce4 = [&](auto NKc) {
-                        constexpr int NK = decltype(NKc)::value;
-                        for (int c = 4 * sc0; c < (srow ? s_zext : 0); c += 4 * RGS) {
-                            f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-                            if (c < ncol) {
-                                const float* src = part + (c >> 6) * PW + sr * 64 + ((c & 63) ^ sw);
-                                constexpr int CH = LB && NK > 4 ? 4 : NK;        // K parts in flight (the gradient launch has no 32 registers to spare)
-                                const f32x4 b = *reinterpret_cast<const f32x4*>(lbias + s_bias + c);
-#pragma unroll
-                                for (int k0 = 0; k0 < NK; k0 += CH) {
-                                    f32x4 x[CH];
-#pragma unroll
-                                    for (int kp = 0; kp < CH; ++kp) x[kp] = *reinterpret_cast<const f32x4*>(src + ((k0 + kp) << s_ncgl) * PW);
-#pragma unroll
-                                    for (int kp = 0; kp < CH; ++kp) v += x[kp];
-                                }
-                                v += b;
-                                if (s_relu) v = f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
-                            }
-                            if constexpr (LB) {
-                                // the gate: four sign bits of the tensor this gradient belongs to (bit columns s_mbit + c ..; c & 31 <= 28)
-                                const bool mine = c < ((s_gn + 63) & ~63);
-                                if (s_mbit >= 0) {
-                                    const unsigned nib = mine ? (lbits[sr * nbw + ((s_mbit + c) >> 5)] >> (c & 31)) & 0xFu : 0u;
-#pragma unroll
-                                    for (int e = 0; e < 4; ++e) v[e] = ((nib >> e) & 1u) ? v[e] : 0.f;
-                                }
-                                *reinterpret_cast<f32x4*>(cur + c) = v;
-                                if (s_gbit >= 0) {
-                                    // the signs of these activations: the eight threads of a 32-column word OR their nibbles together
-                                    unsigned w32 = ((v[0] > 0.f ? 1u : 0u) | (v[1] > 0.f ? 2u : 0u) | (v[2] > 0.f ? 4u : 0u) | (v[3] > 0.f ? 8u : 0u)) << (c & 31);
-                                    w32 |= __shfl_xor(w32, 1, 64); w32 |= __shfl_xor(w32, 2, 64); w32 |= __shfl_xor(w32, 4, 64);
-                                    if ((sc0 & 7) == 0 && mine) lbits[sr * nbw + ((s_gbit + c) >> 5)] = w32;
-                                }
-                            } else {
-                                *reinterpret_cast<f32x4*>(cur + c) = v;
-                            }
-                        }
-                    };
-                    if (nkp == NW) reduce4(std::integral_constant<int, NW>{});
-                    else if (nkp == NW / 2) reduce4(std::integral_constant<int, NW / 2>{});
-                    else reduce4(std::integral_constant<int, 2>{});
-                } else
-                for (int c = sc0; c < (srow ? s_zext : 0); c += RGS, ++gj) {
-                    float v = 0.f;
-                    if (c < ncol) {
-                        const float* src = part + (c >> 6) * PW + sr * 64 + ((c & 63) ^ sw);
-                        // the partials of this column's K parts, all reads in flight (8, 4 or 2 of them: the same sums in the
-                        // same order as one loop over kp < nkp)
-                        if (nkp == NW) {
-                            float x[NW];
-#pragma unroll
-                            for (int kp = 0; kp < NW; ++kp) x[kp] = src[(kp << s_ncgl) * PW];
-#pragma unroll
-                            for (int kp = 0; kp < NW; ++kp) v += x[kp];
-                        } else if (nkp == NW / 2) {
-                            float x[NW / 2];
-#pragma unroll
-                            for (int kp = 0; kp < NW / 2; ++kp) x[kp] = src[(kp << s_ncgl) * PW];
-#pragma unroll
-                            for (int kp = 0; kp < NW / 2; ++kp) v += x[kp];
-                        } else {
-                            const float x0 = src[0], x1 = src[(1 << s_ncgl) * PW];
-                            v += x0; v += x1;
-                        }
-                        v += lbias[s_bias + c];
-                        if (s_relu) v = fmaxf(v, 0.f);
-                        if constexpr (LB) {
-                            if (s_mbit >= 0 && !(c < ((s_gn + 63) & ~63) && ((lbits[sr * nbw + ((s_mbit + c) >> 5)] >> (c & 31)) & 1u))) v = 0.f;
-                        } else if constexpr (DXE) {
-                            float gv = 1.f;             // (dynamic register-array index: a select chain)
-#pragma unroll
-                            for (int j = 0; j < NGJ; ++j) gv = gj == j ? sg[j] : gv;
-                            if (s_gmask && !(gv > 0.f)) v = 0.f;
-                        }
-                        if constexpr (STORE && !G2) {
-                            if (s_gout && row0 + sr < a.B && c < s_gn) {
-                                float vs = v;
-                                if constexpr (STORE == 1)
-                                    if (si == nseg - 1) vs = vs * (a.cscale ? a.cscale[c] : 1.f) + (a.cshift ? a.cshift[c] : 0.f);
-                                gstore(s_gout + (size_t)(row0 + sr) * s_gld + c, vs);
-                            }
-                        }
-                    }
-                    cur[c] = v;
-                    if constexpr (LB) {
-                        if (s_gbit >= 0) {                  // (every lane of a wave runs the same trips of this loop)
-                            const unsigned long long bb = __ballot(v > 0.f);
-                            const bool mine = c < ((s_gn + 63) & ~63);
-                            if constexpr (SM) { if (lane == 0 && mine) *reinterpret_cast<unsigned long long*>(lbits + sr * nbw + ((s_gbit + c) >> 5)) = bb; }
-                            else { if ((lane & 31) == 0 && mine) lbits[sr * nbw + ((s_gbit + c) >> 5)] = (unsigned)(bb >> (lane & 32)); }
-                        }
-                    }
-                }
-                if constexpr (STORE == 3) {
-                    if (si == nlast) {
-                        // the network's last layer (nout <= 256): thread (row sr, lane sc0) turns its own columns
-                        // sc0 + RGS j of pred into delta, in place (asm loads: see the WIDE epilogue)
-                        constexpr int NJ = NGJ;
-                        const int ysrc = lsrc[sr];
-                        float sy[NJ];
-#pragma unroll
-                        for (int j = 0; j < NJ; ++j) {
-                            const int c = min(sc0 + RGS * j, nout - 1);
-                            asm volatile("global_load_dword %0, %1, off" : "=v"(sy[j]) : "v"(a.t_Y + (size_t)ysrc * a.t_ldy + c) : "memory");
-                        }
-#pragma unroll
-                        for (int j = 0; j < NJ; ++j) asm volatile("s_waitcnt vmcnt(0)" : "+v"(sy[j]) :: "memory");
-#pragma unroll
-                        for (int j = 0; j < NJ; ++j) {
-                            const int c = sc0 + RGS * j;
-                            if (c < nout && srow) cur[c] = isnan(sy[j]) ? -0.f : (sy[j] - cur[c]) + 0.f;
-                        }
-                    }
-                }
-#ifdef NS_STAMPS_FINE
-                if (fine) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); NS_STAMP(); }   // reduce done
-#endif
-                lds_barrier();
-                NS_STAMP();
-                ++si;
-                take_next();
-            }
-            if constexpr (GRAD) {
-                if (seg_done && si == a.nseg_f) {   // (seg_done: not again after a pass of the first backward segment)
-                    if constexpr (DXE && !LB)       // the forward activations every wave stored are in memory before any gate load
-                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    if constexpr (TRB) {
-                        // ---- turnaround of a training step = the loss finish: delta and U = delta Cinv sit in LDS (U at column
-                        // u_col of buffer P, or at column 0 with delta in the other buffer).  loss_b = delta . U / den
-                        // (util.py:1086-1088); d loss / d pred = -2 U inv_batch / den, zero where delta was masked, goes to
-                        // memory (the last layer's parameter gradient reads it) AND over delta / U in LDS: the input rows of the
-                        // first backward segment (their padding columns hold the zeros the forward left there).
-                        {
-                            const float* const F = act + P * ABUF + pr * LD;
-                            const bool rok = prow && row0 + pr < a.B;
-                            const float* const Dv = a.u_same ? F : act + (P ^ 1) * ABUF + pr * LD;
-                            const float* const Uv = a.u_same ? F + a.u_col : F;
-                            float chi = 0.f;
-                            for (int c = pc0; c < nout; c += RG) chi += Dv[c] * Uv[c];
-#pragma unroll
-                            for (int o = RG / 2; o >= 1; o >>= 1) chi += __shfl_xor(chi, o, 64);
-                            if (rok && pc0 == 0) gstore(a.t_loss_rows + row0 + pr, chi / lden[pr]);
-                        }
-                        lds_barrier();                  // every row's chi is taken before delta is overwritten (u_same)
-                        {
-                            constexpr int TPR = 64 * NW / ROWS;
-                            const int fr = tid / TPR, fc = tid % TPR;
-                            float* const Fr = act + P * ABUF + fr * LD;
-                            const float* const Dr = a.u_same ? Fr : act + (P ^ 1) * ABUF + fr * LD;
-                            const float* const Ur = a.u_same ? Fr + a.u_col : Fr;
-                            const float dr = lden[fr];
-                            const bool rowok = row0 + fr < a.B;
-                            for (int c = fc; c < a.t_lddp; c += TPR) {
-                                float g = 0.f;
-                                if (c < nout && rowok) {
-                                    const bool masked = __float_as_uint(Dr[c]) == 0x80000000u;
-                                    g = masked ? 0.f : (-2.f * Ur[c]) * a.t_inv_batch / dr;
-                                }
-                                if (rowok) gstore(a.t_dP + (size_t)(row0 + fr) * a.t_lddp + c, g);
-                                if (c < nout) Fr[c] = g;
-                            }
-                        }
-                        lds_barrier();
-                    } else {
-                    // ---- turnaround: the output rows (bias added) sit in buffer P.  lnP as in the finish, and
-                    // d lnP / d out = -(d w) gscale / T written over them: the input of the first backward segment
-                    float* const F = act + P * ABUF + pr * LD;
-                    float chi = 0.f;
-#pragma unroll
-                    for (int i = 0; i < FIN; ++i) {
-                        const int c = pc0 + i * RG;
-                        if (c < nout && prow) {
-                            const float d = F[c] * fcs[i] + fct[i];
-                            chi += (d * fw[i]) * d;
-                            F[c] = -(d * fw[i]) * fgs[i] / a.T;
-                        }
-                    }
-#pragma unroll
-                    for (int o = RG / 2; o >= 1; o >>= 1) chi += __shfl_xor(chi, o, 64);
-                    lnp_grad = (-0.5f * chi) / a.T + (-0.5f * zz);
-                    lds_barrier();
-                    }
-                }
-            }
-#undef fin
-#undef q_row
-#undef q_col
-            if (seg_done && si < nseg && s_x0col > 0) {
-                // input skip: the kept input rows go behind this segment's regular input (one GEMM over [h ; x0])
-                if (prow) {
-                    float* const dstp = act + P * ABUF + pr * LD + s_x0col;
-#pragma unroll
-                    for (int i = 0; i < ZPRE; ++i)
-                        if (pc0 + i * RG < s_x0n) dstp[pc0 + i * RG] = lx0[pr * 64 + pc0 + i * RG];
-                }
-                lds_barrier();
-            }
-            if constexpr (K4) {
-                if (side_next && seg_done) {
-                    // ---- SIDE run: the segment now in s_* (taken above), whole, right here.  Wave w owns the k range
-                    // [w kslice, (w + 1) kslice) (ncg = 1); a step covers kc chunks of 16 k: tile t of the weights is
-                    // (column tile t % (4 / kc), chunk t / (4 / kc)).
-#pragma unroll
-                    for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    const bool kc4 = s_kcl == 2, kc1 = s_kcl == 0;
-                    const uint32_t abase = act_lds + 4u * (uint32_t)(P * ABUF + li * LD + 4 * kq + wave * s_kslice);
-#pragma unroll
-                    for (int s2 = 0; s2 < 2; ++s2) {
-                        if (s2 < s_steps) {
-                            const uint32_t as = abase + (uint32_t)s2 * (64u << s_kcl);
-                            f32x4 af0, af1, af2 = f32x4{0.f, 0.f, 0.f, 0.f}, af3 = f32x4{0.f, 0.f, 0.f, 0.f};
-                            asm volatile("ds_read_b128 %0, %1" : "=v"(af0) : "v"(as) : "memory");
-                            af1 = f32x4{0.f, 0.f, 0.f, 0.f};
-                            if (!kc1) asm volatile("ds_read_b128 %0, %1 offset:64" : "=v"(af1) : "v"(as) : "memory");
-                            if (kc4) {
-                                asm volatile("ds_read_b128 %0, %1 offset:128" : "=v"(af2) : "v"(as) : "memory");
-                                asm volatile("ds_read_b128 %0, %1 offset:192" : "=v"(af3) : "v"(as) : "memory");
-                            }
-                            if (s2 == 0)
-                                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)"
-                                             : "+v"(af0), "+v"(af1), "+v"(af2), "+v"(af3), "+v"(sdw[0][0]), "+v"(sdw[0][1]), "+v"(sdw[0][2]),
-                                               "+v"(sdw[0][3]), "+v"(sdw[1][0]), "+v"(sdw[1][1]), "+v"(sdw[1][2]), "+v"(sdw[1][3]) :: "memory");
-                            else
-                                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(af0), "+v"(af1), "+v"(af2), "+v"(af3) :: "memory");
-                            // tile t multiplies chunk t (kc = 4), t >> 1 (kc = 2) or the one chunk (kc = 1)
-                            const f32x4 f1 = kc4 ? af1 : af0, f2 = kc4 ? af2 : kc1 ? af0 : af1, f3 = kc4 ? af3 : kc1 ? af0 : af1;
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(af0[e], sdw[s2][0][e], acc[0], 0, 0, 0);
-                                acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(f1[e], sdw[s2][1][e], acc[1], 0, 0, 0);
-                            }
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(f2[e], sdw[s2][2][e], acc[2], 0, 0, 0);
-                                acc[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(f3[e], sdw[s2][3][e], acc[3], 0, 0, 0);
-                            }
-                        }
-                    }
-                    int treal = NT;
-                    if (kc4) { acc[0] = (acc[0] + acc[1]) + (acc[2] + acc[3]); treal = 1; }
-                    else if (!kc1) { acc[0] = acc[0] + acc[2]; acc[1] = acc[1] + acc[3]; treal = 2; }
-                    float* const part = act + (P ^ 1) * ABUF;       // [8 waves][16 rows][64]: the SPLIT layout and swizzle
-                    constexpr int PW = ROWS * 64;
-#pragma unroll
-                    for (int t = 0; t < NT; ++t)
-                        if (t < treal) {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) part[wave * PW + (4 * kq + e) * 64 + ((16 * t + li) ^ (16 * kq))] = acc[t][e];
-                        }
-#ifdef NS_STAMPS_FINE
-                    if (fine) NS_STAMP();          // SIDE: MFMAs issued, partials written
-#endif
-                    lds_barrier();
-#ifdef NS_STAMPS_FINE
-                    if (fine) NS_STAMP();          // SIDE: first barrier passed
-#endif
-                    {                                  // four adjacent columns per thread, 16-byte accesses: the SPLIT reduce's form
-                        float* const cur = act + P * ABUF + pr * LD + s_dst;
-                        const int ncol = 16 * treal, sw = 16 * (pr >> 2);
-                        for (int c = 4 * pc0; c < s_zext; c += 4 * RG) {
-                            f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-                            if (c < ncol) {
-                                const float* src = part + pr * 64 + (c ^ sw);
-                                constexpr int CH = LB ? 4 : NW;
-                                const f32x4 b = *reinterpret_cast<const f32x4*>(lbias + s_bias + c);
-#pragma unroll
-                                for (int k0 = 0; k0 < NW; k0 += CH) {
-                                    f32x4 x[CH];
-#pragma unroll
-                                    for (int kp = 0; kp < CH; ++kp) x[kp] = *reinterpret_cast<const f32x4*>(src + (k0 + kp) * PW);
-#pragma unroll
-                                    for (int kp = 0; kp < CH; ++kp) v += x[kp];
-                                }
-                                v += b;
-                                if (s_relu) v = f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
-                            }
-                            if constexpr (LB) {         // a backward SIDE segment (d/dh) is gated by the sign bits of h; a forward one records them
-                                const bool mine = c < ((s_gn + 63) & ~63);
-                                if (s_mbit >= 0) {
-                                    const unsigned nib = mine ? (lbits[pr * nbw + ((s_mbit + c) >> 5)] >> (c & 31)) & 0xFu : 0u;
-#pragma unroll
-                                    for (int e = 0; e < 4; ++e) v[e] = ((nib >> e) & 1u) ? v[e] : 0.f;
-                                }
-                                *reinterpret_cast<f32x4*>(cur + c) = v;
-                                if (s_gbit >= 0) {
-                                    unsigned w32 = ((v[0] > 0.f ? 1u : 0u) | (v[1] > 0.f ? 2u : 0u) | (v[2] > 0.f ? 4u : 0u) | (v[3] > 0.f ? 8u : 0u)) << (c & 31);
-                                    w32 |= __shfl_xor(w32, 1, 64); w32 |= __shfl_xor(w32, 2, 64); w32 |= __shfl_xor(w32, 4, 64);
-                                    if ((pc0 & 7) == 0 && mine) lbits[pr * nbw + ((s_gbit + c) >> 5)] = w32;
-                                }
-                            } else {
-                                *reinterpret_cast<f32x4*>(cur + c) = v;
-                            }
-                        }
-                    }
-#ifdef NS_STAMPS_FINE
-                    if (fine) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); NS_STAMP(); }   // SIDE: reduce done
-#endif
-                    lds_barrier();
-                    NS_STAMP();
-                    ++si;
-                    const int n2i = __builtin_amdgcn_readfirstlane(min(si, nseg - 1));
-                    const NsSeg N2 = ka->seg[n2i];
-                    take_seg(N2);
-                    if constexpr (LB) { s_gbit = ka->gbit[n2i]; s_mbit = ka->mbit[n2i]; s_gn = ka->gn[n2i]; }
-                }
-            }
-            if (si < nseg) {
-                begin_run();
-                a_read(Aq[(U + 1) & 1]);           // replaces the speculative fragment
-            }
-#ifdef NS_STAMPS_FINE
-            if (fine) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); NS_STAMP(); }   // next run ready to issue
-#endif
-        }
-    };
-    using T_ = std::true_type; using F_ = std::false_type;
-#define NS_STEP(U, RF) if constexpr (U < R) step(std::integral_constant<int, U>{}, RF{});
-    const int ngroups = a.G / R, rem = a.G - ngroups * R;
-#pragma unroll 1
-    for (int it = 0; it < ngroups; ++it) {
-        NS_STEP(0, T_) NS_STEP(1, T_) NS_STEP(2, T_) NS_STEP(3, T_) NS_STEP(4, T_) NS_STEP(5, T_) NS_STEP(6, T_) NS_STEP(7, T_)
-    }
-#define NS_TAIL(U) if constexpr (U < R - 1) { if (rem > U) step(std::integral_constant<int, U>{}, F_{}); }
-    NS_TAIL(0) NS_TAIL(1) NS_TAIL(2) NS_TAIL(3) NS_TAIL(4) NS_TAIL(5) NS_TAIL(6)
-#undef NS_STEP
-#undef NS_TAIL
-    // The last speculative A read.  Both fragments are operands of the wait: the compiler does not know that the
-    // inline-asm ds_read lands later, and a fragment nobody reads again would otherwise be dead at once -- its
-    // registers could be handed to an accumulator of the final step, which the returning LDS data then overwrites.
-    if constexpr (BF) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(Aq[0][0]), "+v"(Aq[0][AK - 1]), "+v"(Aq[1][0]), "+v"(Aq[1][AK - 1]) :: "memory");
-    else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(Aq[0][0]), "+v"(Aq[1][0]) :: "memory");
-    NS_STAMP();
-
-    if constexpr (((STORE == 1 || STORE == 2) && !GRAD) || TRB) { NS_STAMPS_FLUSH(); return; }   // every output is in global memory already
-    if constexpr (STORE == 3) {
-        // ---- 5 (loss).  delta and U = delta Cinv sit in LDS (as d and U of the dense serving program): chi2 = delta . U,
-        // loss_b = chi2 / den (util.py:1086-1088), d loss / d pred = -2 U inv_batch / den, zero where delta was masked
-        const float* const F = act + P * ABUF + pr * LD;
-        const bool rok = prow && row0 + pr < a.B;
-        const float* const Dv = a.u_same ? F : act + (P ^ 1) * ABUF + pr * LD;
-        const float* const Uv = a.u_same ? F + a.u_col : F;
-        float chi = 0.f;
-        for (int c = pc0; c < nout; c += RG) chi += Dv[c] * Uv[c];
-#pragma unroll
-        for (int o = RG / 2; o >= 1; o >>= 1) chi += __shfl_xor(chi, o, 64);
-        if (rok && pc0 == 0) a.t_loss_rows[row0 + pr] = chi / lden[pr];
-        {
-            // d loss / d pred by ALL threads of the workgroup, 512 / ROWS per row (the row's 32 threads alone walked a
-            // 457-wide row in 15 rounds while three quarters of the workgroup waited: 8 k cycles at the kernel's tail)
-            constexpr int TPR = 64 * NW / ROWS;
-            const int fr = tid / TPR, fc = tid % TPR;
-            if (row0 + fr < a.B) {
-                const float* const Fr = act + P * ABUF + fr * LD;
-                const float* const Dr = a.u_same ? Fr : act + (P ^ 1) * ABUF + fr * LD;
-                const float* const Ur = a.u_same ? Fr + a.u_col : Fr;
-                const float dr = lden[fr];
-                for (int c = fc; c < a.t_lddp; c += TPR) {
-                    float g = 0.f;
-                    if (c < nout) {
-                        const bool masked = __float_as_uint(Dr[c]) == 0x80000000u;
-                        g = masked ? 0.f : (-2.f * Ur[c]) * a.t_inv_batch / dr;
-                    }
-                    a.t_dP[(size_t)(row0 + fr) * a.t_lddp + c] = g;
-                }
-            }
-        }
-        NS_STAMP();
-        NS_STAMPS_FLUSH();
-        return;
-    }
-    // ---- 5 (GRAD). d lnP / d x sits in buffer P: the derivative of the input transform and of the prior map
-    // (util.py:339-347, 483-497), minus z for the Gaussian prior term; lnP from the turnaround
-    if constexpr (GRAD) {
-        const float* const F = act + P * ABUF + pr * LD;
-        const bool rok = prow && row0 + pr < a.B;
-        if (rok) {
-#pragma unroll
-            for (int j = 0; j < ZPRE; ++j) {
-                const int c = pc0 + j * RG;
-                if (c < nin) {
-                    float g = F[c] / zxs[j];
-                    if (a.lg && zlg[j]) g = g / (theta[j] * 2.30258509299404568f);
-                    const float z = zr[j];
-                    const float dth = zfl[j] ? za2[j] * (expf(-0.5f * z * z) * 0.398942280401432678f) : za2[j];
-                    const float gz = g * dth - z;
-                    a.Gout[(size_t)(row0 + pr) * a.ldg + c] = gz;
-                    if (a.hm_p) {
-                        // the leapfrog's kick with this gradient and the drift to the next position (hmc_kick_drift_kernel's
-                        // arithmetic: the launch between two gradient evaluations it replaces was 4.5 us of nothing)
-                        float* const pp = a.hm_p + (size_t)(row0 + pr) * a.hm_ldp + c;
-                        float pm = *pp;
-                        if (a.hm_ek != 0.f) { pm += a.hm_ek * gz; *pp = pm; }
-                        if (a.hm_ed != 0.f) a.hm_q[(size_t)(row0 + pr) * a.ldz + c] = z + a.hm_ed * (pm / a.hm_mass[c]);
-                    }
-                }
-            }
-            if (pc0 == 0) a.lnP[row0 + pr] = isnan(lnp_grad) ? -INFINITY : lnp_grad;
-        }
-        if constexpr (STORE == 2) { NS_STAMP(); NS_STAMPS_FLUSH(); }     // (diagnostic build; the MLP-only GRAD keeps its masks where the stamps would sit)
-        return;
-    }
-    // ---- 5. output rows are in buffer P (bias added, no ReLU): output transform, d, log-likelihood
-    {
-        const float* const F = act + P * ABUF + pr * LD;
-        const bool rok = prow && row0 + pr < a.B;
-        float chi = 0.f;
-        auto column = [&](int c, float cs, float ct, float ww) {
-            float d = F[c] * cs + ct;
-            if (a.cpost) d = expf(d) * a.cpost[c] + a.cshift2[c];
-            if (a.D && rok) a.D[(size_t)(row0 + pr) * a.ldd + c] = d;
-            chi += (d * ww) * d;
-        };
-        if (a.dense) {
-            // the last segment multiplied d (output map folded into the last layer) by the dense inverse covariance
-            const float* const Dv = a.u_same ? F : act + (P ^ 1) * ABUF + pr * LD;
-            const float* const U = a.u_same ? F + a.u_col : F;
-            const bool fac = a.dense == 2;      // the segment multiplied by L (S = L L^T): chi2 = |d L|^2, a sum of squares
-            for (int c = pc0; c < nout; c += RG) {
-                const float d = Dv[c];
-                if (a.D && rok) a.D[(size_t)(row0 + pr) * a.ldd + c] = d;
-                const float u = U[c];
-                chi += (fac ? u : d) * u;
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < FIN; ++i)
-                if (pc0 + i * RG < nout) column(pc0 + i * RG, fcs[i], fct[i], fw[i]);
-            for (int c = pc0 + FIN * RG; c < nout; c += RG)        // wide outputs: constants straight from memory
-                column(c, a.cscale ? a.cscale[c] : 1.f, a.cshift ? a.cshift[c] : 0.f, a.w ? a.w[c] : 0.f);
-        }
-#pragma unroll
-        for (int o = RG / 2; o >= 1; o >>= 1) chi += __shfl_xor(chi, o, 64);
-        float lnp_new = (-0.5f * chi) / a.T + (-0.5f * zz);
-        lnp_new = isnan(lnp_new) ? -INFINITY : lnp_new;
-        if constexpr (MOVE == 2) {
-            if (a.lnP && pc0 == 0 && prow && row0 + pr < mv_rows) a.lnP[a.mv_C ? grow : row0 + pr] = lnp_new;
-        } else {
-            if (a.lnP && (a.w || a.dense) && pc0 == 0 && rok) a.lnP[row0 + pr] = lnp_new;
-        }
-        if constexpr (MOVE == 1) {
-            // Metropolis test of the stretch move (linna_stretch_accept); every lane of the row agrees
-            const bool mv_acc = rok && mv_factor + lnp_new - mv_lnp_old > mv_logu;
-            if (mv_acc) {
-#pragma unroll
-                for (int j = 0; j < ZPRE; ++j)
-                    if (pc0 + j * RG < nin) a.mv_coords[(size_t)mv_wk * a.mv_ldc + pc0 + j * RG] = zr[j];
-                if (pc0 == 0) {
-                    a.mv_logp[mv_wk] = lnp_new;
-                    if (a.mv_naccept) a.mv_naccept[mv_wk] += 1;
-                }
-            }
-            if (a.mv_chain && rok) {
-                // the walker's position after this iteration goes straight into the chain block (a walker moves in ONE of the
-                // two half steps of an iteration: the two launches together fill the row)
-#pragma unroll
-                for (int j = 0; j < ZPRE; ++j)
-                    if (pc0 + j * RG < nin)
-                        a.mv_chain[(size_t)mv_wk * nin + pc0 + j * RG] = mv_acc ? zr[j] : a.mv_coords[(size_t)mv_wk * a.mv_ldc + pc0 + j * RG];
-                if (pc0 == 0) a.mv_lps[mv_wk] = mv_acc ? lnp_new : mv_lnp_old;
-            }
-        }
-        if (a.TH && rok) {
-#pragma unroll
-            for (int j = 0; j < ZPRE; ++j)
-                if (pc0 + j * RG < nin) a.TH[(size_t)(row0 + pr) * a.ldt + pc0 + j * RG] = theta[j];
-            for (int c = pc0 + ZPRE * RG; c < nin; c += RG)     // wide inputs: theta recomputed rather than kept
-                a.TH[(size_t)(row0 + pr) * a.ldt + c] = ns_prior_theta(a.Z[(size_t)grow * a.ldz + c], a.is_flat[c], a.a1[c], a.a2[c]);
-        }
-    }
-    NS_STAMP();
-    NS_STAMPS_FLUSH();
-#undef NS_STAMP
-#undef NS_STAMPS_FLUSH
+#include "net_stream_body.inc"
+}
+template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF>
+__global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_train_bf16_kernel(NsArgs a) {
+    static_assert(BF && GRAD && STORE == 3 && ROWS == 4 && MOVE == 0, "the bf16 training step only");
+#include "net_stream_body.inc"
 }
 
 // ---------------------------------------------------------------------------- host side: the program
@@ -1581,6 +370,7 @@ struct NsProgram {
     int x0_keep = 0;                                        // an input-skip segment copies the network input later
     size_t side_f4 = 0;                                     // 16-byte vectors of all SIDE blocks
     bool bf = false;                                        // bf16 stream: 32 k per step, first layer [W | W] over [x_hi ; x_lo]
+    int f32seg = -1;                                        // ... but for this segment, an fp32 run (the training step's loss)
     size_t lds_for(int rows, bool grad) const {
         size_t b = (size_t)(2 * rows * LD + ((bias_total + 3) & ~3)) * sizeof(float) + 128 + (x0_keep ? 4096 : 0);   // + [16] set rows, [16] den (STORE == 3), kept input rows
 #ifdef NS_STAMPS
@@ -1642,8 +432,7 @@ enum { NS_PROG_FWD = 0, NS_PROG_FWD_NOGRAD = 1, NS_PROG_DX = 2, NS_PROG_DX_INPUT
 static NsProgram ns_build_one(const linna_layer_t* layers, int nl, int in_size, int mode, const NsDense* dn = nullptr,
                               bool k4 = false, bool bf = false) {
     NsProgram p;
-    if (bf && (mode != NS_PROG_FWD_NOGRAD || dn || k4)) return p;
-    const int KS = bf ? 32 : 16;                            // k per step
+    if (bf && ((mode != NS_PROG_FWD_NOGRAD && mode != NS_PROG_TRAIN) || (mode == NS_PROG_FWD_NOGRAD && dn) || k4)) return p;
     const bool allow_grad = mode == NS_PROG_FWD, dx_prog = mode == NS_PROG_DX || mode == NS_PROG_DX_INPUT;
     const bool train = mode == NS_PROG_TRAIN;
     if ((mode == NS_PROG_FWD_DENSE || train) && (!dn || !dn->S)) return p;
@@ -1739,6 +528,10 @@ static NsProgram ns_build_one(const linna_layer_t* layers, int nl, int in_size, 
         p.dense = 1; p.u_col = Q.dst_col; p.u_same = behind ? 1 : 0;
     }
     const int nfwd = (int)lins.size();
+    // k per step of segment i: 32 in a bf16 stream, but for the training step's loss segment (the dense inverse covariance
+    // behind the last layer), an fp32 run inside it
+    const int f32seg = bf && train ? nfwd - 1 : -1;
+    auto seg_ks = [&](int i) { return bf && i != f32seg ? 32 : 16; };
     if (fwd_dxi) {
         if (in_size > 64 || lins.back().N > 64) return p;      // (prologue / turnaround constants are held for <= 64 columns)
         push_dx(0);
@@ -1773,7 +566,8 @@ static NsProgram ns_build_one(const linna_layer_t* layers, int nl, int in_size, 
     std::vector<int> in_ext(lins.size());
     for (size_t i = 0; i < lins.size(); ++i) {
         const Lin& L = lins[i];
-        const int ksteps = bf ? (L.Kapad + L.Kb + 31) / 32 : (L.Kapad + ceil16(L.Kb)) / 16;
+        const int KS = seg_ks((int)i);
+        const int ksteps = KS == 32 ? (L.Kapad + L.Kb + 31) / 32 : (L.Kapad + ceil16(L.Kb)) / 16;
         NsSeg s; NsPackSeg q;
         std::memset(&s, 0, sizeof(s));
         s.relu = L.relu; s.dst_col = L.dst_col; s.bias_off = bias_off;
@@ -1889,7 +683,7 @@ static NsProgram ns_build_one(const linna_layer_t* layers, int nl, int in_size, 
     }
     for (const NsSeg& s : p.seg) if (s.type != NS_WIDE) maxext = std::max(maxext, s.dst_col + s.zext);
     if (p.kpad0 > (dx_prog ? 1024 : bf ? 512 : 256)) return p;
-    p.bf = bf;
+    p.bf = bf; p.f32seg = f32seg;
     p.nout = lins[nfwd - 1].N;
     p.G = Gf; p.Gstride = G; p.nseg_f = nfwd; p.grad_ok = want_grad;
     for (size_t i = 0; i < lins.size(); ++i) { p.seg_op.push_back(lins[i].op); p.seg_hidden.push_back(lins[i].same_buf ? 1 : 0); }
@@ -1973,6 +767,7 @@ static NsProgram ns_build_kind(NsKind kind, const linna_layer_t* layers, int nl,
     case NS_DX_INPUT: p = ns_build_one(layers, nl, in_size, NS_PROG_DX_INPUT); break;
     case NS_GRAD_INPUT: p = ns_build_one(layers, nl, in_size, NS_PROG_FWD_DXI, nullptr, side); break;
     case NS_TRAIN_STEP: p = ns_build_one(layers, nl, in_size, NS_PROG_TRAIN, dn); break;
+    case NS_TRAIN_STEP_BF16: p = ns_build_one(layers, nl, in_size, NS_PROG_TRAIN, dn, false, true); break;
     }
     // the SIDE program where it fits, the plain one otherwise
     if (side && !(p.ok && (kind != NS_GRAD_INPUT || p.dxi_ok))) return ns_build_kind(kind, layers, nl, in_size, dn, false);
@@ -2066,6 +861,11 @@ NsPlan net_stream_plan(NsKind kind, const linna_layer_t* layers, int nl, int in_
     const NsProgram& p = *pref;
     NsPlan r{p.ok, p.packed_floats, p.grad_ok, nullptr};
     if (kind == NS_TRAIN_STEP) r.ok = p.ok && p.train_ok;
+    if (kind == NS_TRAIN_STEP_BF16) {
+        r.why = ns_bf16_refusal(p, layers, nl, in_size);
+        if (!r.why && !p.train_ok) r.why = "the network has no merged training step (one layer only)";
+        r.ok = r.why == nullptr;
+    }
     if (kind == NS_GRAD_INPUT) {
         r.ok = p.ok && p.dxi_ok && ns_gates(p, layers, nl, NS_ROWS).lds <= (size_t)NS_LDS_BYTES;
         // one copy serves every engine: the 16-row one reads the SIDE program
@@ -2110,7 +910,7 @@ int launch_net_stream_pack(NsKind kind, const linna_layer_t* layers, int nl, int
     ::memset(static_cast<void*>(&a), 0, sizeof(a));
     a.nseg = (int)p.seg.size(); a.G = p.Gstride; a.bias_total = p.bias_total; a.out = packed;
     a.small = rows < 16;
-    a.bf = p.bf ? 1 : 0;
+    a.bf = p.bf ? 1 : 0; a.f32seg = p.f32seg;
     int nrun = 0, first = 0;
     for (int i = 0; i < a.nseg; ++i) {
         a.seg[i] = p.pack[i];
@@ -2196,6 +996,9 @@ __device__ __forceinline__ void as_update(f32x4& P4, const f32x4& G4, f32x4& M4,
 
 // One work item = a 4 x 4 block of a weight matrix (rows n0..n0+3, columns k0..k0+3; 16-byte loads and stores throughout:
 // the forward stream takes the block's rows as four vectors, the dX-chain stream its columns) or four bias elements.
+// BF: the places are in a bf16 training stream (as_slot_bf16): each value the nearest-even rounding of the fp32 one, the
+// columns past the matrix's K not written (the first layer's second half starts right behind them)
+template <bool BF = false>
 __global__ __launch_bounds__(AS_BLOCK) void adamw_streams_kernel(AsArgs a, float* __restrict__ p, const float* __restrict__ g,
                                                             float* __restrict__ m, float* __restrict__ v,
                                                             const float* __restrict__ hyper, float beta1, float beta2, float eps) {
@@ -2243,6 +1046,24 @@ __global__ __launch_bounds__(AS_BLOCK) void adamw_streams_kernel(AsArgs a, float
     for (int j = 0; j < 2; ++j) {
         const AsPlace& q = W.pl[j];
         if (!q.out) continue;
+        if constexpr (BF) {
+            __bf16* const ob = reinterpret_cast<__bf16*>(q.out);
+            if (!q.trans) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (n0 + r < W.N && k0 + e < q.ncols) ob[as_slot_bf16(q, n0 + r, q.koff + k0 + e)] = (__bf16)(q.scale * P4[r][e]);
+            } else {
+                // column k0 + e, rows n0..n0+3: four consecutive k of one vector (koff and n0 are multiples of 4)
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (k0 + e < q.ncols)
+                        *reinterpret_cast<bf16x4_t*>(ob + as_slot_bf16(q, k0 + e, q.koff + n0)) =
+                            bf16x4_t{(__bf16)(q.scale * P4[0][e]), (__bf16)(q.scale * P4[1][e]), (__bf16)(q.scale * P4[2][e]), (__bf16)(q.scale * P4[3][e])};
+            }
+            continue;
+        }
         if (!q.trans) {
             // row n0 + r, columns k0..k0+3: one vector of the stream (koff and k0 are multiples of 4; pad columns hold zeros)
 #pragma unroll
@@ -2268,7 +1089,9 @@ __global__ __launch_bounds__(AS_BLOCK) void adamw_streams_kernel(AsArgs a, float
 int net_stream_adamw_args(const linna_layer_t* layers, int nl, int in_size, int rows, const float* params, size_t nflat,
                           float* s_fwd, const NsDense* dn, float* s_dx, AsArgs* out, int merged) {
     // merged: ONE stream holds the forward + loss segments [0, nseg_f) and the dX chain [nseg_f, nseg) (NS_TRAIN_STEP)
-    const NsProgramRef pf_ref = ns_program(merged ? NS_TRAIN_STEP : NS_TRAIN_FWD, layers, nl, in_size, dn, rows);
+    const bool bf = merged == 2;
+    if (bf && rows != 4) { set_error("adamw_streams: the bf16 training stream is the 4-row engine's"); return LINNA_ERR_UNSUPPORTED; }
+    const NsProgramRef pf_ref = ns_program(bf ? NS_TRAIN_STEP_BF16 : merged ? NS_TRAIN_STEP : NS_TRAIN_FWD, layers, nl, in_size, dn, rows);
     const NsProgramRef pd_ref = merged ? pf_ref : ns_program(NS_DX, layers, nl, in_size, nullptr, rows);
     const NsProgram& pf = *pf_ref;
     const NsProgram& pd = *pd_ref;
@@ -2296,17 +1119,27 @@ int net_stream_adamw_args(const linna_layer_t* layers, int nl, int in_size, int 
         for (int i = 0; i < seg; ++i) first += ns_seg_steps(p.seg[i]);
         return first + pass * p.seg[seg].steps;
     };
-    auto place = [&](const NsProgram& p, float* base, const float* W, AsPlace* q, size_t lo, size_t hi) -> int {
+    // q2 (bf16 stream): where the second half of the first layer's [W | W] goes
+    auto place = [&](const NsProgram& p, float* base, const float* W, int K, AsPlace* q, size_t lo, size_t hi, AsPlace* q2) -> int {
         for (size_t i = lo; i < hi; ++i) {
             const NsPackSeg& S = p.pack[i];
             const bool isA = S.Wa == W, isB = S.Wb == W;
             if (!isA && !isB) continue;
             if (q->out) { set_error("adamw_streams: a weight matrix twice in one stream"); return LINNA_ERR_UNSUPPORTED; }
             if (S.rscale || S.rshift || S.b2) { set_error("adamw_streams: folded output map"); return LINNA_ERR_UNSUPPORTED; }
-            q->out = base; q->scale = isA ? 1.f : S.alpha; q->trans = isA ? S.transA : S.transB; q->koff = isA ? 0 : S.Kapad;
-            q->ncols = S.N; q->type = S.type; q->ncg = S.ncg; q->steps = S.steps; q->G = p.Gstride;
-            q->first0 = runs_first(p, (int)i, 0); q->first1 = p.seg[i].passes > 1 ? runs_first(p, (int)i, 1) : q->first0;
             if (p.seg[i].passes > 2) { set_error("adamw_streams: %d passes", p.seg[i].passes); return LINNA_ERR_UNSUPPORTED; }
+            auto fill = [&](AsPlace* d, bool a_part) {
+                d->out = base; d->scale = a_part ? 1.f : S.alpha; d->trans = a_part ? S.transA : S.transB; d->koff = a_part ? 0 : S.Kapad;
+                d->ncols = S.N; d->type = S.type; d->ncg = S.ncg; d->steps = S.steps; d->G = p.Gstride;
+                d->first0 = runs_first(p, (int)i, 0); d->first1 = p.seg[i].passes > 1 ? runs_first(p, (int)i, 1) : d->first0;
+                if (bf && !d->trans) d->ncols = K;         // (bf16: the bound on the columns of W a writer stores)
+            };
+            if (isA && isB) {                               // the bf16 first layer [W | W]
+                if (!bf || !q2 || q2->out) { set_error("adamw_streams: a weight matrix twice in one segment"); return LINNA_ERR_UNSUPPORTED; }
+                fill(q, true); fill(q2, false);
+            } else {
+                fill(q, isA);
+            }
         }
         return LINNA_OK;
     };
@@ -2339,8 +1172,8 @@ int net_stream_adamw_args(const linna_layer_t* layers, int nl, int in_size, int 
             R.idx = (short)nw;
             AsMat& W = out->w[nw++];
             W.N = t.N; W.ld = ld;
-            int rc = place(pf, s_fwd, t.ptr, &W.pl[0], f_lo, f_hi);
-            if (rc == LINNA_OK) rc = place(pd, s_dx, t.ptr, &W.pl[1], d_lo, d_hi);
+            int rc = place(pf, s_fwd, t.ptr, t.K, &W.pl[0], f_lo, f_hi, &W.pl[1]);
+            if (rc == LINNA_OK) rc = place(pd, s_dx, t.ptr, t.K, &W.pl[1], d_lo, d_hi, nullptr);
             if (rc != LINNA_OK) return rc;
             if (!W.pl[0].out) { set_error("adamw_streams: a weight matrix outside the forward stream"); return LINNA_ERR_UNSUPPORTED; }
         }
@@ -2353,8 +1186,9 @@ int net_stream_adamw_args(const linna_layer_t* layers, int nl, int in_size, int 
 }
 
 int launch_adamw_streams(const AsArgs& a, float* p, const float* g, float* m, float* v, const float* hyper, float b1, float b2,
-                         float eps, hipStream_t s) {
-    hipLaunchKernelGGL(adamw_streams_kernel, dim3(a.nblocks), dim3(AS_BLOCK), 0, s, a, p, g, m, v, hyper, b1, b2, eps);
+                         float eps, hipStream_t s, bool bf) {
+    if (bf) hipLaunchKernelGGL(adamw_streams_kernel<true>, dim3(a.nblocks), dim3(AS_BLOCK), 0, s, a, p, g, m, v, hyper, b1, b2, eps);
+    else hipLaunchKernelGGL(adamw_streams_kernel<false>, dim3(a.nblocks), dim3(AS_BLOCK), 0, s, a, p, g, m, v, hyper, b1, b2, eps);
     return check_hip(hipGetLastError(), "adamw_streams launch");
 }
 
@@ -2529,11 +1363,12 @@ int launch_net_stream_train(const linna_layer_t* layers, int nl, int in_size, co
 int launch_net_stream_train_bwd(const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* X, int ldx,
                                 const int* ROWS, int B, const int* lg, const float* xmean, const float* xstd, float* XB, int ldxb,
                                 const NsOpBufs* ops, const NsTrainLoss& L, const NsDense& dn, int rows, hipStream_t s,
-                                const NsPost* post) {
-    const NsProgramRef pref = ns_program(NS_TRAIN_STEP, layers, nl, in_size, &dn, rows);
+                                const NsPost* post, bool bf) {
+    const NsProgramRef pref = ns_program(bf ? NS_TRAIN_STEP_BF16 : NS_TRAIN_STEP, layers, nl, in_size, &dn, rows);
     const NsProgram& p = *pref;
     if (!p.ok || !p.train_ok || !p.dense) { set_error("net_stream: network + loss have no one-launch training program"); return LINNA_ERR_UNSUPPORTED; }
-    if (rows != 4) { set_error("net_stream: the one-launch training step runs on the 4-row engine"); return LINNA_ERR_UNSUPPORTED; }
+    if (rows != 4) { set_error(bf ? "net_stream: the bf16 training step runs on the 4-row engine (batches of up to 1024 rows)"
+                                  : "net_stream: the one-launch training step runs on the 4-row engine"); return LINNA_ERR_UNSUPPORTED; }
     NsArgs a = ns_train_args(p, true, layers, nl, in_size, packed, X, ldx, ROWS, B, lg, xmean, xstd, XB, ldxb, ops, L);
     ns_store_table(a, p, layers, nl, ops, p.nseg_f, (int)p.seg.size(), true);
     const NsGates g = ns_gates(p, layers, nl, rows);
@@ -2544,6 +1379,20 @@ int launch_net_stream_train_bwd(const linna_layer_t* layers, int nl, int in_size
     }
     int extra = 0;
     if (post && post->step) { a.p_step = post->step; a.p_hyper = post->hyper; a.p_b1 = post->b1; a.p_b2 = post->b2; extra = 1; }
+    if (bf) {
+        static bool attr_set = false;
+#ifdef NS_STAMPS
+        set_error("net_stream: the NS_STAMPS build has no bf16 training step"); return LINNA_ERR_UNSUPPORTED;
+#endif
+        if (!attr_set) {
+            const int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(&net_stream_train_bf16_kernel<NS_R, 0, true, 3, 4, true>),
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, NS_LDS_BYTES), "hipFuncSetAttribute");
+            if (rc != LINNA_OK) return rc;
+            attr_set = true;
+        }
+        hipLaunchKernelGGL((net_stream_train_bf16_kernel<NS_R, 0, true, 3, 4, true>), dim3((B + 3) / 4 + extra), dim3(64 * NS_NW), p.lds_for(rows, true) + lds_extra, s, a);
+        return check_hip(hipGetLastError(), "net_stream bf16 training launch");
+    }
     return ns_launch_kernel<0, true, 3>(a, B, p, rows, s, extra, lds_extra);
 }
 

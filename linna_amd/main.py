@@ -17,12 +17,14 @@ from .nn import *  # noqa: F401,F403
 from .util import (limit_threads_to_quota, Transform, invTransform, NN_samplerv1, generate_training_point, train_NN, retrieve_model, Log_prob,
                    gaussianlogliklihood, run_mcmc, read_chain_and_cut, LogPrior, logp_theory_data)
 from . import nn as lnn
+from . import _lib
 from ._lib import stage
 
 
 def ml_sampler(outdir, theory, priors, data, cov, init, pool, nwalkers, gpunode, omegab2cut=None, nepoch=4500,
-               method="zeus", nbest=None, chisqcut=None, loglikelihoodfunc=None, emulator_precision="fp32"):
-    """main.py:22-75: the hyper-parameter schedule of To et al. 2022.  ``emulator_precision``: see ``ml_sampler_core``."""
+               method="zeus", nbest=None, chisqcut=None, loglikelihoodfunc=None, emulator_precision="fp32", train_precision="fp32"):
+    """main.py:22-75: the hyper-parameter schedule of To et al. 2022.  ``emulator_precision``, ``train_precision``: see
+    ``ml_sampler_core``."""
     ntrainArr = [10000, 10000, 10000, 10000]
     nvalArr = [500, 500, 500, 500]
     if method == "emcee":
@@ -39,18 +41,22 @@ def ml_sampler(outdir, theory, priors, data, cov, init, pool, nwalkers, gpunode,
     return ml_sampler_core(ntrainArr, nvalArr, nkeepArr, ntimesArr, ntautolArr, meanshiftArr, stdshiftArr, outdir, theory,
                            priors, data, cov, init, pool, nwalkers, "cuda", None, False, temperatureArr, omegab2cut, False, 1,
                            gpunode, lnn.ChtoModelv2, params, method, nbest=nbest, chisqcut=chisqcut,
-                           loglikelihoodfunc=loglikelihoodfunc, emulator_precision=emulator_precision)
+                           loglikelihoodfunc=loglikelihoodfunc, emulator_precision=emulator_precision, train_precision=train_precision)
 
 
 def ml_sampler_core(ntrainArr, nvalArr, nkeepArr, ntimesArr, ntautolArr, meanshiftArr, stdshiftArr, outdir, theory, priors,
                     data, cov, init, pool, nwalkers, device, dolog10index, ypositive, temperatureArr, omegab2cut=None,
                     docuda=False, tsize=1, gpunode=None, nnmodel_in=None, params=None, method="emcee", nbest=None,
-                    chisqcut=None, loglikelihoodfunc=None, nsigma=3, externalloglike=None, emulator_precision="fp32"):
+                    chisqcut=None, loglikelihoodfunc=None, nsigma=3, externalloglike=None, emulator_precision="fp32",
+                    train_precision="fp32"):
     """main.py:77-335.  Returns ``(chain[nsamp, ndim] in theta space, log_prob)``.
     ``emulator_precision`` ("fp32" or the opt-in "bf16"): the arithmetic of the emulator while SAMPLING (``util.Log_prob``);
-    training and every other evaluation stay fp32.
+    every other evaluation stays fp32.  ``train_precision`` ("fp32" or the opt-in "bf16"): the training step's network
+    launch (``Predictor.train``); the parameters, the optimiser and validation stay fp32.
     ``gpunode`` / ``docuda`` / ``device`` (main.py:193-245: which Slurm node runs ``train_gpu.py`` under srun) keep their
     places in the signature; the emulator always trains in this process on the local GPU."""
+    if train_precision not in _lib.PRECISION:
+        raise ValueError("ml_sampler_core: train_precision must be 'fp32' or 'bf16', not %r" % (train_precision,))
     if method == "emcee":
         filename = "chemcee_256.h5"
     elif method == "zeus":
@@ -128,7 +134,8 @@ def ml_sampler_core(ntrainArr, nvalArr, nkeepArr, ntimesArr, ntautolArr, meanshi
         if (master or world > 1) and not ldist.agree(os.path.isfile(os.path.join(outdir_in, "finish.pkl"))):
             args[15] = nnmodel_in
             with stage("train_NN"):
-                train_NN(*args, device=device if str(device).startswith("cuda") else "cuda", rank=rank)   # every rank: data parallel
+                train_NN(*args, device=device if str(device).startswith("cuda") else "cuda", rank=rank,    # every rank: data parallel
+                         precision=train_precision)
             if master:
                 with open(os.path.join(outdir_in, "finish.pkl"), "wb") as f:     # train_gpu.py:36-38
                     pickle.dump([True], f)

@@ -286,7 +286,26 @@ class _Emulator(object):
         h = C.c_void_p()
         _lib.call("linna_net_create", _lib.ctx(self._flat.device.index), arr, len(self.ops), self.in_size, C.byref(h))
         self._net, self._net_sig = h, sig
+        if getattr(self, "_train_precision", "fp32") != "fp32":
+            self._apply_train_precision(h)      # a rebuilt handle keeps the training precision
         return h
+
+    def set_train_precision(self, precision):
+        """The precision of the training step's network launch on this model's handle (``"fp32"`` or the opt-in ``"bf16"``:
+        ``linna_net_set_train_precision``); ValueError with the reason when the network has no such step."""
+        if precision not in _lib.PRECISION:
+            raise ValueError("training precision must be 'fp32' or 'bf16', not %r" % (precision,))
+        self._train_precision = precision
+        self._apply_train_precision(self.net_handle(with_grads=True))
+
+    def _apply_train_precision(self, h):
+        prec = self._train_precision
+        rc = _lib.load().linna_net_set_train_precision(h, _lib.PRECISION[prec])
+        if rc == _lib.ERR_UNSUPPORTED:
+            self._train_precision = "fp32"
+            _lib.check(_lib.load().linna_net_set_train_precision(h, _lib.PRECISION["fp32"]))
+            raise ValueError("training precision %r: %s" % (prec, _lib.load().linna_last_error().decode()))
+        _lib.check(rc)
 
     def workspace(self, B, kind="fwd"):
         key = (kind, int(B))

@@ -198,8 +198,8 @@ class _AdamWState(object):
             if rc == 0:
                 self._streams = True
                 return
-            if rc != _lib.ERR_UNSUPPORTED or self._streams is True:
-                _lib.check(rc)
+            if rc != _lib.ERR_UNSUPPORTED or self._streams is True or getattr(self.model, "_train_precision", "fp32") != "fp32":
+                _lib.check(rc)          # (a bf16 training step has no flat-buffer fallback)
             self._streams = False
         _lib.call("linna_adamw_step", _lib.ctx(self.m.device.index), _lib.ptr(flat),
                   _lib.ptr(self.model.flat_grads()), _lib.ptr(self.m), _lib.ptr(self.v), n, _lib.ptr(self.hyper),
@@ -316,13 +316,19 @@ class Predictor(object):
 
     # ------------------------------------------------------------------ training
     def train(self, dataset, num_epochs, loss_fn, val_dataset=None, val_metric_fn=None, initfrombest=False, pool=None,
-              nocpu=False, rank=0, size=1, dist_group=None, checkpoint_every=1, progress=False, patience=500, profile=None):
+              nocpu=False, rank=0, size=1, dist_group=None, checkpoint_every=1, progress=False, patience=500, profile=None,
+              precision="fp32"):
         """predictor_gpu.py:201-449.  ``dist_group``, ``checkpoint_every``, ``progress``, ``patience`` (the
         reference hard-wires 500, :256) and ``profile`` (a dict that receives where the epochs' time went) are additions
-        with the reference's behaviour as default."""
+        with the reference's behaviour as default.  ``precision="bf16"`` (opt-in; default ``"fp32"``) runs every optimiser
+        step's network launch on bf16 weights and matrix-core operands (include/linna_hip.h, linna_net_set_train_precision);
+        the parameters, the optimiser, validation and checkpoints stay fp32.  A network or batch without a bf16 step raises
+        ValueError before anything runs."""
+        if precision not in _lib.PRECISION:
+            raise ValueError("Predictor.train: precision must be 'fp32' or 'bf16', not %r" % (precision,))
         from . import trainer          # the HIP training engine (kept separate from the API shell)
         return trainer.run(self, dataset, num_epochs, loss_fn, val_dataset, val_metric_fn, initfrombest, rank, size,
-                           dist_group, checkpoint_every, progress, patience, profile)
+                           dist_group, checkpoint_every, progress, patience, profile, precision=precision)
 
 
 def _t2n(t):

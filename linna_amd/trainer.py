@@ -24,8 +24,9 @@ from .predictor_gpu import EarlyStopping, _AdamWState, _lower_median
 
 
 class TrainEngine(object):
-    def __init__(self, pred, loader, loss_fn, val_loader, world_size=1, dist_group=None, use_graph=False):
+    def __init__(self, pred, loader, loss_fn, val_loader, world_size=1, dist_group=None, use_graph=False, precision="fp32"):
         self.pred, self.model = pred, pred.model
+        self.precision = precision
         dev = self.model.device
         if dev.type != "cuda":
             raise _lib.LinnaHipError("training runs on the GPU only (no CPU fallback)")
@@ -67,8 +68,16 @@ class TrainEngine(object):
         self._updated = False
         self.YN = None
         self.inv_batch = 1.0 / (B * self.world)          # the global batch is B per rank x ranks
+        # the training step's precision goes on the handle before it is prepared and before any capture; a network or batch
+        # without a bf16 step is refused here, before any step runs -- and a bf16 step never falls back to the fp32 forms
+        self.model.set_train_precision(precision)
         _lib.call("linna_net_prepare", self.model.net_handle(with_grads=True), 1, 0)   # no allocation on the launch path
         _lib.call("linna_net_prepare_loss", self.model.net_handle(with_grads=True), C.byref(self.desc))
+        if precision != "fp32":
+            if _lib.load().linna_net_train_launches(self.model.net_handle(with_grads=True), B) != 2:
+                raise ValueError("training precision %r: a batch of %d rows per rank is past the 4-row engine of the whole-network "
+                                 "kernel, the only one with a bf16 training step" % (precision, B))
+            self.one_launch = self.one_update = True     # ERR_UNSUPPORTED from a step raises: no fallback
 
     def _chi2_md(self, Y):
         n = Y.shape[0]
@@ -318,7 +327,7 @@ class _EpochProf(object):
 
 
 def run(pred, dataset, num_epochs, loss_fn, val_dataset, val_metric_fn, initfrombest, rank, size, dist_group,
-        checkpoint_every, progress, patience=500, profile=None):
+        checkpoint_every, progress, patience=500, profile=None, precision="fp32"):
     """The body of ``Predictor.train``; returns (train_losses[steps], val_metrics[epochs, 3]).
 
     One host wait per epoch.  Everything the controller reads -- the last training loss and the three validation metrics,
@@ -338,7 +347,7 @@ def run(pred, dataset, num_epochs, loss_fn, val_dataset, val_metric_fn, initfrom
         ldist.enter("Predictor.train (data parallel, size = %d)" % size, dist_group)   # every rank must be here: fail within minutes, not never
     model = pred.model
     with _lib.stage("train_NN.engine_setup"):
-        engine = TrainEngine(pred, dataset, loss_fn, val_dataset, world_size=size, dist_group=dist_group)
+        engine = TrainEngine(pred, dataset, loss_fn, val_dataset, world_size=size, dist_group=dist_group, precision=precision)
     if pred.optim == "automatic" or pred.optim is None:
         with _lib.stage("train_NN.lr_range_test"):
             lr = _read_lr(pred, engine, rank, size, dist_group)

@@ -681,8 +681,8 @@ def _load_samples(outdir_list, usebest=False):
 
 
 def train_nn(outdir, model, train_x, train_y, val_x, val_y, X_transform, y_transform, loss_fn, val_metric_fn, dev="cpu",
-             verbose=False, retrain=True, pool=None, nocpu=False, size=0, rank=0, params=None, dist_group=None):
-    """util.py:1272-1306: wrap the arrays and run ``Predictor.train``."""
+             verbose=False, retrain=True, pool=None, nocpu=False, size=0, rank=0, params=None, dist_group=None, precision="fp32"):
+    """util.py:1272-1306: wrap the arrays and run ``Predictor.train`` (``precision``: its training-step precision)."""
     if not retrain and os.path.isfile(os.path.join(outdir, "best.pth.tar")):
         return None
     model = predictor_gpu.Predictor(train_x.shape[-1], train_y.shape[-1], X_transform=X_transform, y_transform=y_transform,
@@ -693,16 +693,19 @@ def train_nn(outdir, model, train_x, train_y, val_x, val_y, X_transform, y_trans
                                            drop_last=False)
     model.train_history = model.train(loader, params["num_epochs"], loss_fn, val_loader, val_metric_fn, initfrombest=True,
                                       pool=None, nocpu=nocpu, rank=rank, size=size, dist_group=dist_group,
-                                      checkpoint_every=params.get("checkpoint_every", 1))
+                                      checkpoint_every=params.get("checkpoint_every", 1), precision=precision)
     return model
 
 
 def train_NN(nnsampler, cov, inv_cov, sigma, outdir_in, outdir_list, data, dolog10index=None, ypositive=False, retrain=True,
              norder=2, temperature=None, docuda=False, pool=None, tsize=1, nnmodel_in=None, params=None, usebest=False,
-             device=None, dist_group=None, rank=0):
+             device=None, dist_group=None, rank=0, precision="fp32"):
     """Prepare statistics, transforms and loss, then train (util.py:1315-1472).  Same positional
     signature as the reference (``model_args.pkl`` holds the first 18 arguments, main.py:197).
-    ``docuda`` is accepted for parity; training always runs on the GPU here."""
+    ``docuda`` is accepted for parity; training always runs on the GPU here.
+    ``precision`` ("fp32" or the opt-in "bf16"): the training step's network launch (``Predictor.train``)."""
+    if precision not in _lib.PRECISION:
+        raise ValueError("train_NN: precision must be 'fp32' or 'bf16', not %r" % (precision,))
     if device is None:
         device = "cuda"
     sigma = np.asarray(sigma)
@@ -770,7 +773,7 @@ def train_NN(nnsampler, cov, inv_cov, sigma, outdir_in, outdir_list, data, dolog
         nnsampler.model = nnmodel
     return train_nn(outdir_in, nnmodel, train_x, train_y, val_x, val_y, X_transform, y_transform, loss_fn, val_metric_fn,
                     dev=device, verbose=True, retrain=retrain, pool=pool, nocpu=True, size=tsize, rank=rank, params=params,
-                    dist_group=dist_group)
+                    dist_group=dist_group, precision=precision)
 
 
 # ------------------------------------------------------------------ training-point generation (util.py:736-897, 1167-1270)
