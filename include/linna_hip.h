@@ -292,9 +292,11 @@ int linna_weights_changed(linna_ctx_t* ctx);
  * LINNA_PRECISION_BF16 (opt-in, serving only): the whole-network kernel streams the weights as bf16 (rounded to nearest-even,
  * a residual block's 0.1 folded in first) and rounds the activations to bf16 where the matrix cores read them; the
  * network input enters as bf16(x) + bf16(x - bf16(x)), and every epilogue, the output map, the log-likelihood and the prior
- * map stay fp32.  Served in bf16: linna_logprob_eval, linna_logprob_eval_if, linna_stretch_half_step, linna_stretch_run;
- * linna_logprob_eval_slice_points and linna_slice_half_step return LINNA_ERR_UNSUPPORTED (callers fall back to
- * linna_slice_points + linna_logprob_eval_if), as do linna_logprob_grad and linna_logprob_grad_leapfrog -- a bf16 object
+ * map stay fp32.  Served in bf16: linna_logprob_eval, linna_logprob_eval_if, linna_stretch_half_step, linna_stretch_run,
+ * linna_logprob_eval_slice_points and linna_slice_half_step (the trial points are formed in fp32 in the launch's prologue,
+ * as on an fp32 object; where the two slice entries return LINNA_ERR_UNSUPPORTED for their other reasons -- more than 64
+ * parameters, LINNA_DISABLE_FUSED -- callers fall back to linna_slice_points + linna_logprob_eval_if, which is bf16 too).
+ * Not served: linna_logprob_grad and linna_logprob_grad_leapfrog return LINNA_ERR_UNSUPPORTED -- a bf16 object
  * never computes silently in fp32.  Setting bf16 allocates the bf16 weight streams (call it outside graph capture); they are
  * laid out on first use and follow the weights like the fp32 copy (linna_adamw_step, linna_graph_launch,
  * linna_weights_changed).  LINNA_ERR_UNSUPPORTED when the object cannot be served in bf16: a dense inverse covariance, a

@@ -1153,11 +1153,8 @@ static int lp_eval_slice_points(linna_logprob_t* lp, const float* coords, int ld
     }
     const linna_logprob_desc_t& d = lp->d;
     if (ndim != d.nin) { set_error("logprob_eval_slice_points: ndim %d, log-probability has %d parameters", ndim, d.nin); return LINNA_ERR_INVALID; }
-    if (lp->bf16()) {
-        set_error("logprob_eval_slice_points: no bf16 slice move");
-        return LINNA_ERR_UNSUPPORTED;          // the caller falls back to linna_slice_points + a bf16 linna_logprob_eval_if
-    }
-    if (!fused_enabled() || !lp->packed.ready() || (d.outmap.cexp && (!d.w || !d.outmap.cpost || !d.outmap.cshift2)) ||
+    // (a bf16 handle runs the bf16 stream or nothing: where this refuses, the caller's fallback evaluates in bf16 too)
+    if (!fused_enabled() || !(lp->bf16() ? lp->packed_bf.ready() : lp->packed.ready()) || (d.outmap.cexp && (!d.w || !d.outmap.cpost || !d.outmap.cshift2)) ||
         (!d.w && !lp->dense_fused) || d.nin > 64) {
         set_error("logprob_eval_slice_points: this log-probability does not run the whole-network kernel");
         return LINNA_ERR_UNSUPPORTED;          // the caller falls back to linna_slice_points + linna_logprob_eval_if
@@ -1197,8 +1194,7 @@ int linna_slice_half_step(linna_logprob_t* lp, float* coords, int ldc, int ndim,
     for (int r = 0; r < nshr_rounds; ++r) if (nt_sched[r] < 1) { set_error("slice_half_step: nt_sched[%d] = %d", r, nt_sched[r]); return LINNA_ERR_INVALID; }
     const linna_logprob_desc_t& d = lp->d;
     if (ndim != d.nin) { set_error("slice_half_step: ndim %d, log-probability has %d parameters", ndim, d.nin); return LINNA_ERR_INVALID; }
-    if (lp->bf16()) { set_error("slice_half_step: no bf16 slice move"); return LINNA_ERR_UNSUPPORTED; }
-    if (!fused_enabled() || !lp->packed.ready() || (d.outmap.cexp && (!d.w || !d.outmap.cpost || !d.outmap.cshift2)) ||
+    if (!fused_enabled() || !(lp->bf16() ? lp->packed_bf.ready() : lp->packed.ready()) || (d.outmap.cexp && (!d.w || !d.outmap.cpost || !d.outmap.cshift2)) ||
         (!d.w && !lp->dense_fused) || d.nin > 64) {
         set_error("slice_half_step: this log-probability does not run the whole-network kernel");
         return LINNA_ERR_UNSUPPORTED;          // the caller falls back to the round-by-round entries

@@ -330,7 +330,8 @@ __device__ __forceinline__ float ns_prior_theta(float z, int flat, float a1, flo
 // output, every residual block's hidden h) are written to global memory from the epilogues with inline-asm
 // stores: the compiler does not see them, so its counted vmcnt waits for the weight stream stay counted
 // (stores only ever make the hardware counter read higher, i.e. the waits conservative).
-// BF: the opt-in bf16 serving engine (linna_logprob_set_precision; MOVE 0 / 1, no GRAD, no STORE).  The stream holds bf16
+// BF: the opt-in bf16 serving engine (linna_logprob_set_precision; MOVE 0 / 1, no GRAD, no STORE; MOVE 2 is the same engine
+// in a kernel of its own, net_stream_slice_bf16_kernel).  The stream holds bf16
 // weights (ns_pack_kernel, p.bf) and one step covers 32 k x 64 columns -- the same 4 KiB per wave and step, so the ring,
 // its four 1-KiB loads and the counted waits keep their shape and a segment takes half the steps.  Activations stay fp32
 // in LDS and are rounded to bf16 (nearest-even) where the A operand is read: two ds_read_b128 per step (8 k per lane).
@@ -344,7 +345,8 @@ __device__ __forceinline__ float ns_prior_theta(float z, int flat, float a1, flo
 // chain consume bf16 steps as above; the loss segment (the dense inverse covariance behind the last layer) stays an fp32
 // run inside the same stream -- both formats move 4 KiB per wave and step, so only the consumer differs.  It is chosen
 // once per run (begin_run: f32run); inside `step` the choice selects between two MFMA sequences and touches no memory.
-// The kernel body is net_stream_body.inc, the text of both kernels below: the whole-network kernel, and the opt-in bf16
+// The kernel body is net_stream_body.inc, the text of the kernels below: the whole-network kernel, the opt-in bf16 slice
+// evaluation (MOVE == 2 on a bf16 stream, described at net_stream_slice_bf16_kernel), and the opt-in bf16
 // training step (linna_net_set_train_precision) -- the merged training launch (GRAD + STORE == 3, 4-row engine) on a bf16
 // stream whose loss segment stays fp32, a kernel of its own rather than a net_stream_kernel specialisation.  (One text
 // included twice instead of a device function both call: inlined into a wrapper, the same body compiles to other
@@ -357,6 +359,18 @@ template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF>
 __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_train_bf16_kernel(NsArgs a) {
     static_assert(BF && GRAD && STORE == 3 && ROWS == 4 && MOVE == 0, "the bf16 training step only");
 #include "net_stream_body.inc"
+}
+// BF + MOVE == 2: the ensemble slice move's evaluation on the bf16 serving engine (linna_slice_half_step,
+// linna_logprob_eval_slice_points on a bf16 handle; 16-, 8- and 4-row engines).  Everything the slice move adds happens in
+// fp32 before the network input reaches LDS (row list and device-side count, the fused set-up, the derived trial points)
+// and in the finish; the input split, the bf16 steps and the epilogues are the serving engine's.  A kernel of its own
+// for the same reason as the training step.
+template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF>
+__global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_slice_bf16_kernel(NsArgs a) {
+    static_assert(BF && !GRAD && STORE == 0 && MOVE == 2, "the bf16 slice evaluation only");
+#define NS_BODY_SLICE_BF16
+#include "net_stream_body.inc"
+#undef NS_BODY_SLICE_BF16
 }
 
 // ---------------------------------------------------------------------------- host side: the program
@@ -969,6 +983,30 @@ static int ns_launch_kernel(const NsArgs& a0, int B, const NsProgram& p, int row
     set_error("net_stream: %d rows per workgroup", rows);
     return LINNA_ERR_INVALID;
 }
+// the slice evaluation of a bf16 serving program: net_stream_slice_bf16_kernel, one instantiation per engine
+template <int ROWS>
+static int ns_launch_slice_bf16_rows(const NsArgs& a, int B, size_t lds_bytes, hipStream_t s) {
+    static bool attr_set = false;
+    if (!attr_set) {
+        const int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(&net_stream_slice_bf16_kernel<NS_R, 2, false, 0, ROWS, true>),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, NS_LDS_BYTES), "hipFuncSetAttribute");
+        if (rc != LINNA_OK) return rc;
+        attr_set = true;
+    }
+    hipLaunchKernelGGL((net_stream_slice_bf16_kernel<NS_R, 2, false, 0, ROWS, true>), dim3((B + ROWS - 1) / ROWS), dim3(64 * NS_NW), lds_bytes, s, a);
+    return check_hip(hipGetLastError(), "net_stream bf16 slice launch");
+}
+static int ns_launch_slice_bf16(const NsArgs& a, int B, const NsProgram& p, int rows, hipStream_t s) {
+#ifdef NS_STAMPS
+    set_error("net_stream: the NS_STAMPS build has no bf16 slice evaluation"); return LINNA_ERR_UNSUPPORTED;
+#endif
+    const size_t lds = p.lds_for(rows, false);
+    if (rows == 4) return ns_launch_slice_bf16_rows<4>(a, B, lds, s);
+    if (rows == 8) return ns_launch_slice_bf16_rows<8>(a, B, lds, s);
+    if (rows == 16) return ns_launch_slice_bf16_rows<16>(a, B, lds, s);
+    set_error("net_stream: %d rows per workgroup", rows);
+    return LINNA_ERR_INVALID;
+}
 
 // ------------------------------------------------------------------ AdamW that writes the weight streams itself
 // A training step ends with AdamW over the flat parameter buffer and begins with two re-layouts of the updated weights
@@ -1266,7 +1304,7 @@ int launch_net_stream(NsKind kind, const linna_layer_t* layers, int nl, int in_s
         a.sl_seed = mv->sl_seed; a.sl_step = mv->sl_step; a.sl_stream = mv->sl_stream; a.sl_flags = mv->sl_flags;
         if (mv->sb) a.sb = *mv->sb;
         if (mv->slice) {
-            if (bf) { set_error("net_stream: the slice move has no bf16 instantiation"); return LINNA_ERR_UNSUPPORTED; }
+            if (bf) return ns_launch_slice_bf16(a, B, p, rows, s);
             return ns_launch_kernel<2, false>(a, B, p, rows, s);
         }
         if (bf) return ns_launch_kernel<1, false, 0, true>(a, B, p, rows, s);

@@ -1,4 +1,5 @@
-// The body of the whole-network kernels (net_stream.hip: net_stream_kernel, net_stream_train_bf16_kernel), included
+// The body of the whole-network kernels (net_stream.hip: net_stream_kernel, net_stream_train_bf16_kernel,
+// net_stream_slice_bf16_kernel), included
 // inside each kernel's braces; its template parameters R, MOVE, GRAD, STORE, ROWS, BF and its argument NsArgs a are theirs.
     constexpr int NT = NS_NT, NW = NS_NW;
     constexpr int RG = 32;                         // threads per walker row in prologue / reduce / finish
@@ -6,8 +7,12 @@
     constexpr int RS = SM ? ROWS / 4 : 1;
     constexpr int NQ = SM ? RS : NT;               // result quads per lane: (row set) or (column tile)
     constexpr int NACC = SM ? 4 * RS : NT;
+#ifdef NS_BODY_SLICE_BF16                          // (defined around the include by net_stream_slice_bf16_kernel alone)
+    static_assert(BF && !GRAD && STORE == 0 && MOVE == 2, "bf16: the slice evaluation");
+#else
     static_assert(!BF || (!GRAD && STORE == 0 && MOVE != 2) || (GRAD && STORE == 3 && MOVE == 0 && ROWS == 4),
                   "bf16: serving, the fused stretch move and the merged training step (4-row engine)");
+#endif
     constexpr bool BFT = BF && GRAD && STORE == 3;   // the bf16 training step: one fp32 run (the loss segment) in the stream
     constexpr int AK = BF ? 2 : 1;                 // 16-byte A fragments per lane and step
     constexpr bool K4 = !SM && !BF && (STORE == 0 || (GRAD && STORE == 2));   // 16-row engine, serving and the one-launch gradient: programs may hold SIDE segments

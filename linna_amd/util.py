@@ -319,8 +319,10 @@ class Log_prob(object):
 
     ``precision="bf16"`` (opt-in; default ``"fp32"``) serves lnP from the whole-network kernel's bf16 engine: weights
     and matrix-core operands rounded to bf16, everything else fp32 (include/linna_hip.h, linna_logprob_set_precision).
-    Serving only: ``evaluate_with_grad`` raises.  A network or likelihood the bf16 engine cannot serve (a dense
-    covariance, a layer wider than 1024, ...) raises ``ValueError`` naming the reason when the object is first used.
+    Both ensemble samplers run their fused moves on it (the stretch move and zeus' slice move: ``EnsembleSampler``,
+    ``SliceEnsembleSampler``'s one-call half step).  Serving only: ``evaluate_with_grad`` raises.  A network or likelihood the
+    bf16 engine cannot serve (a dense covariance, a layer wider than 1024, ...) raises ``ValueError`` naming the reason
+    when the object is first used.
     """
 
     def __init__(self, data_new, invcov_new, model, y_invtransform_data, transform, temperature, loglikelihoodfunc=None,

@@ -4,9 +4,12 @@
   v2_64     one 64-row ChtoModelv2(33,33) evaluation
   stretch   one 2048-proposal stretch half step (linna_stretch_half_step, the 4096-walker ensemble, MLP)
   emcee128  emcee iterations per second at 128 walkers on ChtoModelv2(33,33) (linna_stretch_run blocks)
-Prints ONE JSON line.  FLOP/s count 2 x multiply-adds of the network per walker, against the bf16 dense peak (2.5 PF spec);
+  slice128 / slice4096   zeus iterations per second (SliceEnsembleSampler.run) on ChtoModelv2(33,33) at 128 walkers and
+            on the MLP at 4096: fp32 one-call, bf16 one-call, bf16 round loop, alternating, mu fixed (slice_rates)
+Prints ONE JSON line.  --only-slice / --no-slice: the slice objects alone / left out; --slice-trace: the bf16 one-call
+route at 128 walkers alone (the process to put under a kernel trace).  FLOP/s count 2 x multiply-adds of the network per walker, against the bf16 dense peak (2.5 PF spec);
 bytes = the weight stream each workgroup reads per launch (padded fragment layout) x workgroups.
-usage: python tools/bf16_bench.py [--reps N]"""
+usage: python tools/bf16_bench.py [--reps N] [--only-slice | --no-slice | --slice-trace]"""
 import json
 import os
 import sys
@@ -71,11 +74,65 @@ def stream_bytes(kind, bf, **kw):
     return tot * bpe
 
 
+def slice_rates(lp32, nw, iters, repeats, only=None):
+    """zeus iterations per second through SliceEnsembleSampler.run at `nw` walkers: fp32 one-call, bf16 one-call and bf16 round
+    loop (fast=False: what a bf16 Log_prob ran before the bf16 slice evaluation existed), alternating in one process,
+    `repeats` timed runs of `iters` iterations each.  mu is tuned once (fp32) and then FIXED (tune=False) and every route
+    starts from the tuned run's ensemble, so the three do the same work; the evaluations per walker and iteration are
+    printed beside each rate, and the spread over the repeats beside the median."""
+    import time
+    t = sampler.SliceEnsembleSampler(nw, 33, lp32, seed=1)
+    t.set_state(0.05 * np.random.RandomState(7).standard_normal((nw, 33)))
+    t.run(150, store=False)
+    torch.cuda.synchronize()
+    mu, x0 = float(t.mu), t.coords[:, :33].cpu().numpy().copy()
+    lpb = with_precision(lp32, "bf16")
+    routes = {"fp32_one_call": (lp32, True), "bf16_one_call": (lpb, True), "bf16_round_loop": (lpb, False)}
+    if only:
+        routes = {only: routes[only]}
+    ens, rates, evals = {}, {k: [] for k in routes}, {}
+    for k, (lp, fast) in routes.items():
+        e = sampler.SliceEnsembleSampler(nw, 33, lp, seed=3, tune=False, mu=mu, fast=fast)
+        e.set_state(x0)
+        e.run(80, store=False)                               # warm-up; the later rounds' engines settle (iteration 64)
+        torch.cuda.synchronize()
+        ens[k] = e
+    for _ in range(repeats):
+        for k, e in ens.items():
+            n0, i0 = e.neval, e.iteration
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            e.run(iters, store=False)
+            torch.cuda.synchronize()
+            rates[k].append(iters / (time.perf_counter() - t0))
+            evals[k] = (e.neval - n0) / max(1, e.iteration - i0) / nw
+    out = {"walkers": nw, "mu": round(mu, 4), "iterations_per_run": iters, "repeats": repeats}
+    for k, e in ens.items():
+        r = np.asarray(rates[k])
+        out[k] = {"it_per_s": round(float(np.median(r)), 1), "it_per_s_min": round(float(r.min()), 1), "it_per_s_max": round(float(r.max()), 1),
+                  "spread_pct": round(100.0 * float(r.max() - r.min()) / float(np.median(r)), 2),
+                  "evals_per_walker_per_iteration": round(evals[k], 2), "one_call": e._fast_ok is True, "overflows": e.noverflow}
+    if not only:
+        assert out["fp32_one_call"]["one_call"] and out["bf16_one_call"]["one_call"] and not out["bf16_round_loop"]["one_call"]
+        out["bf16_one_call_over_round_loop"] = round(out["bf16_one_call"]["it_per_s"] / out["bf16_round_loop"]["it_per_s"], 3)
+        out["bf16_over_fp32_one_call"] = round(out["bf16_one_call"]["it_per_s"] / out["fp32_one_call"]["it_per_s"], 3)
+    return out
+
+
 def main():
     dev = torch.device("cuda", 0)
     res = {"tool": "bf16_bench", "reps": REPS, "bf16_peak_flops": BF16_PEAK}
     lp_mlp, _, _ = bench.build_problem(dev)
     lp_v2 = v2_problem(dev)
+    if "--slice-trace" in sys.argv:                          # the bf16 one-call route at 128 walkers alone (for a kernel trace)
+        print(json.dumps({"tool": "bf16_bench", "slice128": slice_rates(lp_v2, 128, 600, 3, only="bf16_one_call")}))
+        return
+    if "--no-slice" not in sys.argv:
+        res["slice128"] = dict(slice_rates(lp_v2, 128, 600, 5), workload="ChtoModelv2(33,33)")
+        res["slice4096"] = dict(slice_rates(lp_mlp, 4096, 100, 5), workload="4x512 MLP")
+    if "--only-slice" in sys.argv:
+        print(json.dumps(res))
+        return
     macs = {"MLP": emulator.macs_per_eval("MLP", 33, 33, width=512, depth=4), "ChtoModelv2": emulator.macs_per_eval("ChtoModelv2", 33, 33)}
     for prec in ("fp32", "bf16"):
         bf = prec == "bf16"
