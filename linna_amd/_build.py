@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "liblinna_hip.so")
-SOURCES = ["gemm.hip", "pointwise.hip", "net_stream.hip", "autocorr.hip", "api.hip", "comm.hip"]
+SOURCES = ["gemm.hip", "pointwise.hip", "net_program.hip", "net_stream.hip", "autocorr.hip", "api.hip", "comm.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-fast-math", "-ffp-contract=off"]
 
 
@@ -19,7 +19,8 @@ def _stale(target, deps):
 
 def build(force=False, verbose=True):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "net_stream_body.inc"), os.path.join(HERE, "..", "include", "linna_hip.h")]
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "net_program.h"), os.path.join(CSRC, "net_stream_body.inc"),
+               os.path.join(HERE, "..", "include", "linna_hip.h")]
     objs = []
     for src in SOURCES:
         s = os.path.join(CSRC, src)
@@ -41,18 +42,22 @@ def build(force=False, verbose=True):
 def build_stamps(extra=("-DNS_STAMPS",), name="liblinna_hip_stamps.so", verbose=True, base=True, source="net_stream.hip"):
     """Diagnostic variant next to the product library: ONE source (net_stream.hip by default) compiled with extra
     definitions -- phase stamps (every launch of the whole-network kernel then needs LINNA_FUSED_STAMPS), experiment
-    switches -- the other objects shared.  Load it with LINNA_LIB_PATH."""
+    switches -- the other objects shared.  net_stream.hip takes its planner net_program.hip along: the two must agree on
+    the LDS a launch needs, which NS_STAMPS changes.  Load it with LINNA_LIB_PATH."""
     if base:
         build(verbose=verbose)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    o = os.path.join(CSRC, "%s_%s.o" % (os.path.splitext(source)[0], os.path.splitext(name)[0].replace("liblinna_hip_", "")))
-    src = os.path.join(CSRC, source)
-    if _stale(o, [src, os.path.join(CSRC, "common.h")]) or True:
-        cmd = [hipcc] + FLAGS + list(extra) + ["-c", src, "-o", o]
+    tag = os.path.splitext(name)[0].replace("liblinna_hip_", "")
+    sources = ["net_program.hip", source] if source == "net_stream.hip" else [source]
+    variant = []
+    for src in sources:
+        o = os.path.join(CSRC, "%s_%s.o" % (os.path.splitext(src)[0], tag))
+        variant.append(o)
+        cmd = [hipcc] + FLAGS + list(extra) + ["-c", os.path.join(CSRC, src), "-o", o]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)
-    objs = [os.path.join(CSRC, s.replace(".hip", ".o")) for s in SOURCES if s != source] + [o]
+    objs = [os.path.join(CSRC, s.replace(".hip", ".o")) for s in SOURCES if s not in sources] + variant
     lib = os.path.join(HERE, name)
     subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs + ["-ldl"])
     return lib

@@ -387,7 +387,7 @@ struct NsDense { const float* S; int lds; const float* cscale; const float* cshi
                  int tri = 2; };         // how the factor's zero upper triangle is skipped (net_stream_dense_tri): 0 not, 1 short second pass, 2 balanced blocks
 // process-wide default of NsDense::tri for log-probability objects created afterwards (LINNA_DENSE_TRI); returns the previous value
 int net_stream_dense_tri(int mode);
-// net_stream.hip (program-driven whole-network kernel: residual blocks, widths up to 1024).  The programs it runs, one
+// net_stream.hip (program-driven whole-network kernel: residual blocks, widths up to 1024) and its planner net_program.hip.  The programs it runs, one
 // weight stream each:
 enum NsKind {
     NS_SERVE,          // log-probability: prior map, network, output map, diagonal likelihood (+ the fused MLP gradient)

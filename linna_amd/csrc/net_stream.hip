@@ -47,51 +47,24 @@
 // (lane = column, see ns_pack_kernel), so a workgroup of 8 (4) rows needs 2x (4x) the weight bandwidth per flop:
 // 64 (128) B/clk/CU at full MFMA rate against the 64 B/clk a CU's vector L1 delivers -- the small engines are
 // L1-fill bound, which still halves the time of a launch that cannot fill the chip.
-#include "common.h"
+#include "net_program.h"
 #include <stdlib.h>
 #include <type_traits>
-#include <vector>
 #include <cstring>
 #include <algorithm>
-#include <atomic>
-#include <memory>
-#include <mutex>
-#include <string>
-#include <unordered_map>
 
 namespace linna {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));   // B (and A) operand of v_mfma_f32_16x16x32_bf16
 typedef short s16x4 __attribute__((ext_vector_type(4)));     // ... of v_mfma_f32_4x4x4_16b_bf16 (the builtin takes the bits)
 
-constexpr int NS_ROWS = 16;                // rows per workgroup of the large-batch engine (and the LDS layout bound)
-constexpr int NS_NW = 8;                 // waves per workgroup
-constexpr int NS_NT = 4;                 // 16-column tiles per wave and step
-constexpr int NS_MAXSEG = 20;
-constexpr int NS_MAXRUN = 40;
-constexpr unsigned NS_STEP_B = NS_NT * 1024;
-constexpr int NS_LDS_BYTES = 160 * 1024;
 #ifndef NS_R
 #define NS_R 6
 #endif
 #ifndef NS_PRE
 #define NS_PRE 2
 #endif
-enum { NS_WIDE = 0, NS_SPLIT = 1, NS_SIDE = 2 };
-
-struct NsSeg {            // kernel-side view of a segment
-    int type, steps, passes, bias_off;
-    int dst_col, relu, kslice, zext;   // SPLIT: kslice = k offset between K parts (16*steps), zext = columns written
-                                       // WIDE with a SHORT second pass (zext > 0): pass 1 runs zext steps from k offset kslice -- the
-                                       // lower-triangular factor of a dense inverse covariance has no rows k < 512 in columns >= 512
-    int ncg_log2;                      // SPLIT: log2 of the number of 64-column groups
-    int mask_store, mask_apply;        // GRAD: 1 + LDS slot of the ReLU sign bits this WIDE segment records / applies (0: none)
-    int x0_n;                          // ... that many columns of them (a multiple of 16)
-    int x0_col;                        // > 0: the network INPUT rows (kept aside in LDS) are copied to this column of the segment's
-                                       // input buffer before it runs (ChtoModelv2_linear's input skip, nn.py:160-163,195)
-    int kcl, side_off;                 // SIDE: log2 of the k chunks per wave and step; float offset of its weights from `packed`
-};
-
+// the launch's arguments: the program's segment table (net_program.h) behind everything the prologue and the finish read
 struct NsArgs {
     const float* Z; int ldz; int B; int nin;
     const int* is_flat; const float* a1; const float* a2; const int* lg;
@@ -152,18 +125,6 @@ struct NsArgs {
 };
 
 // ------------------------------------------------------------------ weight re-layout
-struct NsPackSeg {
-    const float* Wa; int lda, Ka, Kapad;          // first K part (Wa NULL: identity)
-    const float* Wb; int ldb, Kb; float alpha;    // second K part, scaled (residual blocks)
-    const float* b; float bscale;
-    const float* b2; float b2scale;                // second bias term (input skip: alpha * bl)
-    int N, type, steps, passes, bias_off, bias_pad, ncg;
-    int transA;                                   // Wa is read transposed: value(n, k) = Wa[k][n] (backward segments)
-    int transB;                                   // the same for Wb
-    const float* rscale; const float* rshift;     // per output column: weights and bias * rscale, bias + rshift (folded output map)
-    int kc, side_off;                             // SIDE segments: k chunks per wave and step (2 or 4), float offset of their block
-    int koff2;                                    // WIDE with a short second pass: k offset of pass 1 (NsSeg::kslice)
-};
 // SIDE segments (serving programs of the 16-row engine): a SPLIT segment of <= 32 output columns -- the hidden
 // h = relu(W1 x + b1) of a residual block, 1000 -> 16 and 500 -> 32 in ChtoModelv2 -- costs the step loop 8 + 4 steps of
 // which three quarters / half multiply zero weights (a wave's four 16-column tiles need 64 columns).  As a SIDE segment it
@@ -339,7 +300,7 @@ __device__ __forceinline__ float ns_prior_theta(float z, int flat, float a1, flo
 // A and B alike); 8 / 4 rows: v_mfma_f32_4x4x4_16b_bf16 with the CBSZ / ABID broadcast of the fp32 4x4x1 form, block b of
 // the A read holding row set b & 3 and k chunk b >> 2 (8 k), two instructions (halves of the chunk) per (row set, chunk).
 // The network input goes in as x_hi = bf16(x) at column c and x_lo = x - x_hi at column nin + c, and the first layer is
-// packed [W | W] (ns_build_one): the input is not quantised to 8 bits.  Epilogues, the finish and the prior map are the
+// packed [W | W] (net_program.hip, ns_lower): the input is not quantised to 8 bits.  Epilogues, the finish and the prior map are the
 // fp32 kernel's.  SIDE segments are off in bf16 (K4 = false; the program builder plans none).
 // BF + TRB: the opt-in bf16 training step (net_stream_train_bf16_kernel, 4-row engine).  The forward segments and the dX
 // chain consume bf16 steps as above; the loss segment (the dense inverse covariance behind the last layer) stays an fp32
@@ -373,381 +334,9 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_slice_bf16_kernel(Ns
 #undef NS_BODY_SLICE_BF16
 }
 
-// ---------------------------------------------------------------------------- host side: the program
-struct NsProgram {
-    std::vector<NsPackSeg> pack;
-    std::vector<NsSeg> seg;
-    int G = 0, LD = 0, kpad0 = 0, nout = 0, bias_total = 0;
-    int Gstride = 0, nseg_f = 0, mask_slots = 0;            // G: forward steps; Gstride: forward + backward steps
-    size_t lds_bytes = 0, lds_bytes_grad = 0, packed_floats = 0;   // LDS of the 16-row engine (lds_for: any engine)
-    int dense = 0, u_col = 0, u_same = 0;                   // dense inverse covariance appended as the last segment
-    int x0_keep = 0;                                        // an input-skip segment copies the network input later
-    size_t side_f4 = 0;                                     // 16-byte vectors of all SIDE blocks
-    bool bf = false;                                        // bf16 stream: 32 k per step, first layer [W | W] over [x_hi ; x_lo]
-    int f32seg = -1;                                        // ... but for this segment, an fp32 run (the training step's loss)
-    size_t lds_for(int rows, bool grad) const {
-        size_t b = (size_t)(2 * rows * LD + ((bias_total + 3) & ~3)) * sizeof(float) + 128 + (x0_keep ? 4096 : 0);   // + [16] set rows, [16] den (STORE == 3), kept input rows
-#ifdef NS_STAMPS
-        b += NS_NW * 32 * 8;
-#endif
-        return b + (grad ? (size_t)mask_slots * 64 * NS_NW * sizeof(unsigned) : 0);
-    }
-    bool ok = false, grad_ok = false;                       // grad_ok: backward segments appended (ReLU MLPs)
-    bool dxi_ok = false;                                    // the dX chain down to the input appended (NS_PROG_FWD_DXI)
-    bool train_ok = false;                                  // forward + loss + dX chain (NS_PROG_TRAIN)
-    std::vector<int> seg_op, seg_hidden;                    // forward segments: op index; 1 = the hidden h of a residual block
-                                                            // (dX-chain program: 1 = d/dh of a residual block, else d/d(input) of the op)
-};
-
-static int ceil16(int k) { return (k + 15) & ~15; }
-// steps of a segment in every wave's stream (a WIDE segment's second pass may be shorter: NsSeg::zext)
-// zext < 0: the BALANCED triangular assignment of a 16-block lower-triangular factor -- wave w multiplies column block w
-// (rows from 64 w) and then block 15 - w (rows from 64 (15 - w)): steps - 4 w and steps - 4 (15 - w) steps, 2 steps - 60 in
-// every wave
-static int ns_seg_steps(const NsSeg& s) {
-    if (s.type == NS_WIDE && s.zext < 0) return 2 * s.steps - 60;
-    return s.type == NS_WIDE && s.zext > 0 ? s.steps + (s.passes - 1) * s.zext : s.steps * s.passes;
-}
-static std::atomic<int> g_dense_tri{-1};
-static int ns_dense_tri_resolved() {
-    int m = g_dense_tri.load(std::memory_order_relaxed);
-    if (m < 0) {
-        const char* env = getenv("LINNA_DENSE_TRI");
-        int v = env ? atoi(env) : 2;
-        if (v < 0 || v > 2) v = 2;
-        int expect = -1;
-        g_dense_tri.compare_exchange_strong(expect, v);
-        m = g_dense_tri.load(std::memory_order_relaxed);
-    }
-    return m;
-}
-int net_stream_dense_tri(int mode) {
-    const int prev = ns_dense_tri_resolved();
-    if (mode >= 0 && mode <= 2) g_dense_tri.store(mode);
-    return prev;
-}
-
-// Translate the op list into segments; ok = false when something does not fit this kernel.  The builder's modes (the
-// programs of NsKind are built from these in ns_build_kind):
-enum { NS_PROG_FWD = 0, NS_PROG_FWD_NOGRAD = 1, NS_PROG_DX = 2, NS_PROG_DX_INPUT = 3, NS_PROG_FWD_DENSE = 4, NS_PROG_FWD_DXI = 5,
-       NS_PROG_TRAIN = 6 };   // TRAIN: forward + loss segment (FWD_DENSE with the loss's inverse covariance) followed by the dX chain down to op 1
-// mode NS_PROG_DX: the dX chain of a training step as a program of its own (linna_net_backward's order): the rows are
-// d loss / d output, the segments run over the transposed weights from the last op down to op 1 (NS_PROG_DX_INPUT: op 0).
-// A residual block y = relu(0.1 (W2 h + b2) + Ws x), h = relu(W1 x + b1) comes back as  dh = 0.1 (dy W2) [h > 0],
-// written behind dy, and ONE GEMM over [dy ; dh] with [Ws^T | W1^T]; the gate of every output (the stored forward
-// activation) is applied by the kernel's STORE == 2 epilogue.
-// mode NS_PROG_FWD_DENSE: the forward program with the output map (d = raw * cscale + cshift) folded into the last
-// layer's weights and bias, and the dense inverse covariance appended as one more bias-free segment U = d S -- the
-// Gaussian log-likelihood (util.py:953-955) with a dense covariance then needs no GEMM launch of its own.
-// k4: SPLIT segments of <= 32 columns become SIDE segments where they fit (see NsPackArgs): the kernel's K4 path, i.e. the
-// 16-row engine of the programs ns_side names.
-// bf: the bf16 serving program (NS_PROG_FWD_NOGRAD only, no dense segment, no SIDE segments): a step is 32 k, and the
-// first layer (a plain linear map) is [W | W] over K' = 2 nin -- its input rows are x_hi = bf16(x) and x_lo = x - x_hi.
-static NsProgram ns_build_one(const linna_layer_t* layers, int nl, int in_size, int mode, const NsDense* dn = nullptr,
-                              bool k4 = false, bool bf = false) {
-    NsProgram p;
-    if (bf && ((mode != NS_PROG_FWD_NOGRAD && mode != NS_PROG_TRAIN) || (mode == NS_PROG_FWD_NOGRAD && dn) || k4)) return p;
-    const bool allow_grad = mode == NS_PROG_FWD, dx_prog = mode == NS_PROG_DX || mode == NS_PROG_DX_INPUT;
-    const bool train = mode == NS_PROG_TRAIN;
-    if ((mode == NS_PROG_FWD_DENSE || train) && (!dn || !dn->S)) return p;
-    if (nl < 1 || in_size < 1 || in_size > 256) return p;
-    // 1. linear maps: [Wa | alpha Wb] over K = [Kapad ; Kb], N outputs, written to dst_col (same_buf: into the input's buffer)
-    struct Lin { const float* Wa; int lda, Ka, Kapad; const float* Wb; int ldb, Kb; float alpha; const float* b; float bscale;
-                 int N, relu, dst_col; bool same_buf; int transA = 0; int force_wide = 0; int mask_apply_of = -1; int op = -1;
-                 int transB = 0; const float* rscale = nullptr; const float* rshift = nullptr;
-                 const float* b2 = nullptr; float b2scale = 0.f; int x0_col = 0; };
-    std::vector<Lin> lins;
-    int width = in_size;
-    // NS_PROG_FWD_DXI: the forward program followed by the dX chain down to the network input in ONE stream -- lnP and
-    // d lnP / d z in one launch for ANY network (residual blocks, SPLIT segments): the forward segments store their
-    // activations, the backward segments gate on them (the kernel's GRAD + STORE == 2 instantiation)
-    const bool fwd_dxi = mode == NS_PROG_FWD_DXI;
-    for (int i = 0; i < nl && (dx_prog || fwd_dxi || train); ++i) {      // shape checks as in the forward program
-        const linna_layer_t& l = layers[i];
-        if (l.K != width || l.N < 1 || l.N > 1024 || l.K > 1024) return p;
-        if (l.op == LINNA_OP_LINEAR) { if (l.alpha != 1.f) return p; }
-        else if (l.op == LINNA_OP_RESBLOCK) { if (l.C < 1 || l.C > 64 || (!l.Ws && l.K != l.N)) return p; }
-        else return p;
-        width = l.N;
-    }
-    auto push_dx = [&](int first) {
-      for (int i = nl - 1; i >= first; --i) {
-        const linna_layer_t& l = layers[i];
-        const int npad = ceil16(l.N);
-        if (l.op == LINNA_OP_LINEAR) {
-            Lin B{l.W, (l.K + 3) & ~3, l.N, npad, nullptr, 0, 0, 0.f, nullptr, 0.f, l.K, 0, 0, false};
-            B.transA = 1; B.op = i;
-            lins.push_back(B);
-        } else {
-            Lin A{nullptr, 0, 0, 0, l.W2, (l.C + 3) & ~3, l.N, 0.1f, nullptr, 0.f, l.C, 0, npad, true};     // dh behind dy
-            A.transB = 1; A.op = i;
-            lins.push_back(A);
-            Lin B{l.Ws, (l.K + 3) & ~3, l.N, npad, l.W1, (l.K + 3) & ~3, l.C, 1.f, nullptr, 0.f, l.K, 0, 0, false};
-            B.transA = 1; B.transB = 1; B.op = i;
-            lins.push_back(B);
-        }
-      }
-    };
-    if (dx_prog) push_dx(mode == NS_PROG_DX_INPUT ? 0 : 1);
-    width = in_size;
-    for (int i = 0; i < nl && !dx_prog; ++i) {
-        const linna_layer_t& l = layers[i];
-        if (l.K != width && l.op != LINNA_OP_INSKIP) return p;
-        if (l.op == LINNA_OP_LINEAR) {
-            if (l.alpha != 1.f || l.N < 1 || l.N > 1024) return p;
-            lins.push_back(Lin{l.W, (l.K + 3) & ~3, l.K, ceil16(l.K), nullptr, 0, 0, 0.f, l.b, 1.f, l.N, l.relu, 0, false});
-            lins.back().op = i;
-        } else if (l.op == LINNA_OP_RESBLOCK) {
-            if (l.C < 1 || l.C > 64 || l.N < 1 || l.N > 1024 || (!l.Ws && l.K != l.N)) return p;
-            const int inpad = ceil16(l.K);
-            lins.push_back(Lin{l.W1, (l.K + 3) & ~3, l.K, inpad, nullptr, 0, 0, 0.f, l.b1, 1.f, l.C, 1, inpad, true});   // h behind x
-            lins.back().op = i;
-            lins.push_back(Lin{l.Ws, (l.K + 3) & ~3, l.K, inpad, l.W2, (l.C + 3) & ~3, l.C, 0.1f, l.b2, 0.1f, l.N, 1, 0, false});
-            lins.back().op = i;
-        } else if (l.op == LINNA_OP_INSKIP) {
-            // out = last(h) + alpha (x0 Wl^T + bl) (nn.py:195): the last layer becomes ONE GEMM over [h ; x0] with [W | alpha Wl]
-            // and bias b + alpha bl; x0 (the network input, kept in LDS) is copied behind h before the segment runs
-            if (i != nl - 1 || lins.empty() || l.K != in_size || l.N != width || in_size > 64 || mode == NS_PROG_FWD) return p;
-            Lin& last = lins.back();
-            if (last.Wb || last.same_buf || last.relu || !last.Wa) return p;
-            last.Wb = l.W; last.ldb = (l.K + 3) & ~3; last.Kb = l.K; last.alpha = l.alpha;
-            last.b2 = l.b; last.b2scale = l.alpha; last.x0_col = last.Kapad;
-            p.x0_keep = 1;
-            continue;
-        } else {
-            return p;
-        }
-        width = l.N;
-    }
-    if (dx_prog) in_size = layers[nl - 1].N;                   // the rows of this program are d loss / d output
-    if (lins.empty() || lins.back().relu || (int)lins.size() > NS_MAXSEG) return p;
-    if (bf) {                                               // [x_hi ; x_lo]: the first layer twice, no padding between the halves
-        Lin& f = lins[0];
-        if (f.Wb || f.same_buf || f.transA || !f.Wa || f.Ka != in_size || f.x0_col) return p;
-        f.Kapad = in_size; f.Wb = f.Wa; f.ldb = f.lda; f.Kb = f.Ka; f.alpha = 1.f;
-    }
-    if (mode == NS_PROG_FWD_DENSE || train) {
-        Lin& last = lins.back();
-        if (last.Wb || last.same_buf || last.dst_col) return p;               // the last op must be a plain linear layer
-        last.rscale = dn->cscale; last.rshift = dn->cshift;
-        const int no = last.N, npad = ceil16(no);
-        if ((int)lins.size() + 1 > NS_MAXSEG) return p;
-        const bool behind = no <= 256;                                          // SPLIT: U behind d in the same buffer
-        Lin Q{dn->S, dn->lds, no, npad, nullptr, 0, 0, 0.f, nullptr, 0.f, no, 0, behind ? npad : 0, behind};
-        Q.op = nl;
-        // factored: the matrix is L (S = L L^T, not symmetric) and the segment must produce d L: U_n = sum_k d_k L[k][n] -- the
-        // pack kernel reads it transposed (the row-dot GEMM of the layered path reads S[k][n] as it is)
-        if (dn->factored) Q.transA = 1;
-        lins.push_back(Q);
-        p.dense = 1; p.u_col = Q.dst_col; p.u_same = behind ? 1 : 0;
-    }
-    const int nfwd = (int)lins.size();
-    // k per step of segment i: 32 in a bf16 stream, but for the training step's loss segment (the dense inverse covariance
-    // behind the last layer), an fp32 run inside it
-    const int f32seg = bf && train ? nfwd - 1 : -1;
-    auto seg_ks = [&](int i) { return bf && i != f32seg ? 32 : 16; };
-    if (fwd_dxi) {
-        if (in_size > 64 || lins.back().N > 64) return p;      // (prologue / turnaround constants are held for <= 64 columns)
-        push_dx(0);
-        if ((int)lins.size() > NS_MAXSEG) return p;
-    }
-    if (train) {                                               // the turnaround works on the rows in LDS: any width
-        if (nl < 2) return p;
-        push_dx(1);
-        if ((int)lins.size() > NS_MAXSEG) return p;
-    }
-    // Backward (d lnP / d z) for plain ReLU MLPs whose hidden layers come out as WIDE segments: the backward
-    // GEMM of layer l is a forward-shaped segment over W_l^T (contraction N_l, K_l outputs); for l >= 1 it is
-    // forced WIDE so that its lane <-> (row, column) map equals that of the layer whose sign bits it applies.
-    bool want_grad = allow_grad && in_size <= 64 && lins.back().N <= 64 && 2 * nfwd <= NS_MAXSEG;
-    for (int i = 0; i < nfwd && want_grad; ++i) {
-        const Lin& L = lins[i];
-        if (L.Wb || L.same_buf || L.dst_col || !L.Wa) want_grad = false;
-        if (i < nfwd - 1 && (!L.relu || L.N <= 256)) want_grad = false;       // hidden layers must be WIDE (N > 256)
-    }
-    if (want_grad) {
-        for (int i = nfwd - 1; i >= 0; --i) {
-            const Lin F = lins[i];
-            Lin Bk{F.Wa, F.lda, F.N, ceil16(F.N), nullptr, 0, 0, 0.f, nullptr, 0.f, F.Ka, 0, 0, false};
-            Bk.transA = 1; Bk.force_wide = i >= 1; Bk.mask_apply_of = i - 1;
-            lins.push_back(Bk);
-        }
-    }
-
-    // 2. segment shapes.  SPLIT when it must write into its own input buffer (h of a residual block) or when
-    //    splitting K over the idle waves saves at least three steps; WIDE otherwise.
-    int bias_off = 0, G = 0, zero_off = -1, zero_pad = 0;
-    std::vector<int> in_ext(lins.size());
-    for (size_t i = 0; i < lins.size(); ++i) {
-        const Lin& L = lins[i];
-        const int KS = seg_ks((int)i);
-        const int ksteps = KS == 32 ? (L.Kapad + L.Kb + 31) / 32 : (L.Kapad + ceil16(L.Kb)) / 16;
-        NsSeg s; NsPackSeg q;
-        std::memset(&s, 0, sizeof(s));
-        s.relu = L.relu; s.dst_col = L.dst_col; s.bias_off = bias_off;
-        const int passes = (L.N + 511) / 512;
-        int ncg = L.N <= 64 ? 1 : L.N <= 128 ? 2 : L.N <= 256 ? 4 : 0;
-        const int split_steps = ncg ? (ksteps + NS_NW / ncg - 1) / (NS_NW / ncg) : 0;
-        const bool split = ncg && !L.force_wide && (L.same_buf || split_steps + 3 <= ksteps * passes);
-        if (L.same_buf && !ncg) return p;
-        const int kc = L.N <= 16 ? 4 : L.N <= 32 ? 2 : 1;
-        const int side_steps = (ksteps + NS_NW * kc - 1) / (NS_NW * kc);
-        // (never the first segment nor the last forward one: the kernel runs a SIDE segment between two runs of the step loop;
-        // kc = 1, <= 64 columns: the SPLIT mapping itself, run out of the stream -- 250 -> 64 is two steps per wave)
-        // ... and, in the one-launch gradient, d/dh of a residual block (0.1 dy W2 gated by h: 500 / 250 / 125 -> 16 / 32 / 64,
-        // the second K part alone, read transposed): one SIDE step each instead of 4 / 2 / 1 SPLIT steps and a SPLIT boundary
-        // (the LAST forward segment too where nothing follows it in the launch -- serving programs without a backward half:
-        // ChtoModelv2's 33 -> 33 last layer is one SIDE step instead of a three-step WIDE run)
-        const bool last_ok = (int)i == nfwd - 1 && !want_grad && !fwd_dxi && !train && !dx_prog;
-        const bool side_fwd = ((int)i < nfwd - 1 || last_ok) && !L.Wb && !L.transA && L.Wa;
-        const bool side_bwd = fwd_dxi && (int)i > nfwd && !L.Wa && L.Wb && L.transB && L.Kapad == 0 && !L.relu;
-        const bool side_pays = split || (side_fwd && !L.force_wide && side_steps < ksteps * passes);   // (a short WIDE run of <= 64 columns)
-        const bool side = k4 && side_pays && ncg == 1 && side_steps <= 2 && i > 0 && (side_fwd || side_bwd) && p.seg.back().type != NS_SIDE &&
-                          !L.rscale && !L.rshift && !L.b2 && !L.x0_col;
-        if (side) {
-            s.type = NS_SIDE; s.steps = side_steps; s.passes = 1; s.kslice = 16 * kc * s.steps;
-            s.ncg_log2 = 0; s.kcl = kc == 4 ? 2 : kc == 2 ? 1 : 0;
-            s.zext = 64;
-            in_ext[i] = NS_NW * s.kslice;
-            q.bias_pad = 64; q.ncg = 1;
-        } else if (split) {
-            s.type = NS_SPLIT; s.steps = split_steps; s.passes = 1; s.kslice = KS * s.steps;
-            s.ncg_log2 = ncg == 1 ? 0 : ncg == 2 ? 1 : 2;
-            s.zext = 64 * ncg;
-            in_ext[i] = (NS_NW / ncg) * s.kslice;
-            q.bias_pad = 64 * ncg; q.ncg = ncg;
-        } else {
-            s.type = NS_WIDE; s.steps = ksteps; s.passes = passes;
-            in_ext[i] = KS * ksteps;
-            q.bias_pad = 512 * passes; q.ncg = 1;
-        }
-        q.Wa = L.Wa; q.lda = L.lda; q.Ka = L.Ka; q.Kapad = L.Kapad; q.Wb = L.Wb; q.ldb = L.ldb; q.Kb = L.Kb; q.alpha = L.alpha;
-        q.b = L.b; q.bscale = L.bscale; q.N = L.N; q.type = s.type; q.steps = s.steps; q.passes = s.passes; q.bias_off = bias_off;
-        q.transA = L.transA; q.transB = L.transB; q.rscale = L.rscale; q.rshift = L.rshift; q.b2 = L.b2; q.b2scale = L.b2scale;
-        q.kc = side ? kc : 1; q.side_off = 0;
-        s.x0_col = L.x0_col; s.x0_n = L.x0_col ? ceil16(L.Kb) : 0;
-        if (L.transA && !dx_prog) {                                     // backward segments have no bias: ONE shared block of zeros
-            if (zero_off < 0) { zero_off = bias_off; zero_pad = 0; }
-            s.bias_off = q.bias_off = zero_off;
-            const int grow = std::max(0, q.bias_pad - zero_pad);
-            zero_pad += grow; q.bias_pad = grow;            // (the first backward segment's record carries the block; later ones extend it)
-        }
-        bias_off += q.bias_pad;
-        // the Cholesky factor of a dense inverse covariance (NsDense::factored) is lower triangular: in the second pass (columns
-        // >= 512) the rows k < 512 are zero -- that pass starts at k = 512 (bit-identical: the skipped products are zeros)
-        // tri = 2 and exactly 16 column blocks (960 < nout <= 1024): the balanced assignment instead (ns_seg_steps) -- the zero
-        // rows of EVERY 64-column block are skipped, not only those of the second pass, and every wave runs the same number
-        // of steps: 66 instead of 94 at nout = 1000
-        if (dn && dn->tri > 0 && s.type == NS_WIDE && dn->factored && L.Wa == dn->S && passes == 2 && ksteps > 32 && !train) {
-            if (dn->tri == 2 && (L.N + 63) / 64 == 16 && ksteps > 60) s.zext = -1;
-            else { s.kslice = 512; s.zext = ksteps - 32; }
-        }
-        q.koff2 = s.type == NS_WIDE ? (s.zext < 0 ? -1 : s.kslice) : 0;
-        if (!side) G += ns_seg_steps(s);           // (a SIDE segment is not part of the weight stream)
-        p.seg.push_back(s); p.pack.push_back(q);
-    }
-    if (want_grad) {
-        // sign-bit slots: one per pass of every hidden forward segment; the backward segment of layer i+1 applies them
-        int slot = 0;
-        for (int i = 0; i < nfwd - 1; ++i) {
-            if (p.seg[i].type != NS_WIDE) { want_grad = false; break; }
-            p.seg[i].mask_store = 1 + slot;
-            slot += p.seg[i].passes;
-        }
-        for (size_t j = nfwd; j < lins.size() && want_grad; ++j) {
-            const int of = lins[j].mask_apply_of;
-            if (of < 0) continue;
-            if (p.seg[j].type != NS_WIDE || p.seg[j].passes != p.seg[of].passes) { want_grad = false; break; }
-            p.seg[j].mask_apply = p.seg[of].mask_store;
-        }
-        if (want_grad) p.mask_slots = slot;
-        else {   // drop the backward half again
-            for (size_t j = lins.size(); j-- > (size_t)nfwd;) { G -= ns_seg_steps(p.seg[j]); bias_off -= p.pack[j].bias_pad; }
-            p.seg.resize(nfwd); p.pack.resize(nfwd); lins.resize(nfwd); in_ext.resize(nfwd);
-            for (int i = 0; i < nfwd; ++i) p.seg[i].mask_store = 0;
-        }
-    }
-    int Gf = 0;
-    for (int i = 0; i < nfwd; ++i) if (p.seg[i].type != NS_SIDE) Gf += ns_seg_steps(p.seg[i]);
-
-    // 3. every column a segment reads must have been WRITTEN (finite; zero where the weights are zero):
-    //    track the defined prefix [0, def) of the current buffer and widen the zero fill of the last
-    //    SPLIT writer (or of the prologue) where a consumer reads further.
-    p.kpad0 = in_ext[0];
-    int def = p.kpad0, writer = -1;                         // writer: segment whose write ends at `def` (-1 prologue, -2 fixed)
-    int maxext = 64;
-    for (size_t i = 0; i < p.seg.size(); ++i) {
-        NsSeg& s = p.seg[i];
-        if (in_ext[i] > def) {
-            if (writer == -1) p.kpad0 = def = in_ext[i];
-            else if (writer >= 0) { NsSeg& w = p.seg[writer]; w.zext = in_ext[i] - w.dst_col; def = in_ext[i]; }
-            else return p;
-        }
-        maxext = std::max(maxext, in_ext[i]);
-        if (s.type == NS_WIDE) {
-            if (s.dst_col != 0) return p;
-            def = 512 * s.passes; writer = -2;
-            maxext = std::max(maxext, def);
-        } else {
-            if (s.dst_col > def) return p;
-            if (s.dst_col == 0) def = s.zext;               // overwrites its input from column 0
-            else def = std::max(def, s.dst_col + s.zext);
-            writer = (int)i;
-        }
-    }
-    for (const NsSeg& s : p.seg) if (s.type != NS_WIDE) maxext = std::max(maxext, s.dst_col + s.zext);
-    if (p.kpad0 > (dx_prog ? 1024 : bf ? 512 : 256)) return p;
-    p.bf = bf; p.f32seg = f32seg;
-    p.nout = lins[nfwd - 1].N;
-    p.G = Gf; p.Gstride = G; p.nseg_f = nfwd; p.grad_ok = want_grad;
-    for (size_t i = 0; i < lins.size(); ++i) { p.seg_op.push_back(lins[i].op); p.seg_hidden.push_back(lins[i].same_buf ? 1 : 0); }
-    p.dxi_ok = fwd_dxi;
-    p.train_ok = train;
-    p.bias_total = bias_off;
-    p.LD = std::max(((maxext + 63) & ~63) + 4, 516);        // >= 516: SPLIT partials need [8][rows][64] floats in one buffer
-    if (bias_off > 3 * 64 * NS_NW * 4) return p;            // BMAX rounds of float4 per thread
-    p.lds_bytes = (size_t)(2 * NS_ROWS * p.LD + ((bias_off + 3) & ~3)) * sizeof(float) + 128 + (p.x0_keep ? 4096 : 0);
-#ifdef NS_STAMPS
-    p.lds_bytes += NS_NW * 32 * 8;
-#endif
-    if (p.lds_bytes > (size_t)NS_LDS_BYTES) return p;
-    p.lds_bytes_grad = p.lds_bytes + (size_t)p.mask_slots * 64 * NS_NW * sizeof(unsigned);
-    if (p.grad_ok && p.lds_bytes_grad > (size_t)NS_LDS_BYTES) return p;   // (never for the eligible shapes)
-    int nrun = 0;
-    for (const NsSeg& s : p.seg) nrun += s.passes;
-    if (nrun > NS_MAXRUN) return p;
-    p.packed_floats = (size_t)NS_NW * G * NS_NT * 256 + (size_t)((bias_off + 3) & ~3);
-    for (size_t i = 0; i < p.seg.size(); ++i)
-        if (p.seg[i].type == NS_SIDE) {            // blocks of their own behind the biases
-            p.seg[i].side_off = p.pack[i].side_off = (int)p.packed_floats;
-            p.packed_floats += (size_t)NS_NW * p.seg[i].steps * NS_NT * 256;
-            p.side_f4 += (size_t)NS_NW * p.seg[i].steps * NS_NT * 64;
-        }
-    p.ok = true;
-    return p;
-}
-
-// Engine for a batch of B rows: the fewest rows per workgroup that still fit the batch into one workgroup per CU
-// (linna_engine_rows forces one for tests and measurements; LINNA_NS_ROWS in the environment sets the initial value,
-// read ONCE -- the launch path reads an atomic, not the environment).
-static std::atomic<int> g_forced_rows{-1};
-static int ns_forced_rows_resolved() {             // -1 (never read) -> the environment's value, once
-    int forced = g_forced_rows.load(std::memory_order_relaxed);
-    if (forced < 0) {
-        const char* const env = getenv("LINNA_NS_ROWS");
-        const int v = env ? atoi(env) : 0;
-        forced = (v == 4 || v == 8 || v == 16) ? v : 0;
-        int expect = -1;
-        g_forced_rows.compare_exchange_strong(expect, forced);
-        forced = g_forced_rows.load(std::memory_order_relaxed);
-    }
-    return forced;
-}
-int net_stream_force_rows(int rows) {
-    if (rows != 0 && rows != 4 && rows != 8 && rows != 16) return -1;
-    (void)ns_forced_rows_resolved();               // the environment's value is what `prev = engine_rows(4); ...; engine_rows(prev)` must restore
-    return g_forced_rows.exchange(rows);
-}
+// ---------------------------------------------------------------------------- host side: the launches
+// Engine for a batch of B rows: the fewest rows per workgroup that still fit the batch into one workgroup per CU, unless
+// one is forced (ns_forced_rows_resolved, net_program.hip).
 int net_stream_rows(int B) {
     const int forced = ns_forced_rows_resolved();
     if (forced) return forced;
@@ -758,161 +347,6 @@ int net_stream_rows(int B) {
                   ? pr.multiProcessorCount : 256;
     }
     return B <= 4 * ncu ? 4 : B <= 8 * ncu ? 8 : 16;
-}
-
-// SIDE segments (the kernel's K4 path) run on the 16-row engine of the serving programs and the one-launch gradient.  In the
-// gradient's forward half they were measured slower in round 3 (with the activations stored for the gates); with the gates
-// as sign bits in LDS and the per-segment tables read through the kernel-argument segment (without that the instantiation
-// spilled 2.5 KB per lane): 151.4 -> 148.7 us at ChtoModelv2(33,33), 4096 chains (NOTES R4).  Not in bf16.
-static bool ns_side(NsKind kind, int rows) {
-    return rows == 16 && (kind == NS_SERVE || kind == NS_SERVE_DENSE || kind == NS_GRAD_INPUT);
-}
-
-static NsProgram ns_build_kind(NsKind kind, const linna_layer_t* layers, int nl, int in_size, const NsDense* dn, bool side) {
-    NsProgram p;
-    switch (kind) {
-    case NS_SERVE: case NS_STORE:
-        p = ns_build_one(layers, nl, in_size, NS_PROG_FWD, nullptr, side);
-        if (!p.ok) p = ns_build_one(layers, nl, in_size, NS_PROG_FWD_NOGRAD, nullptr, side);   // the backward half may be what did not fit
-        break;
-    case NS_SERVE_DENSE: case NS_TRAIN_FWD: p = ns_build_one(layers, nl, in_size, NS_PROG_FWD_DENSE, dn, side); break;
-    case NS_SERVE_BF16: p = ns_build_one(layers, nl, in_size, NS_PROG_FWD_NOGRAD, dn, false, true); break;
-    case NS_DX: p = ns_build_one(layers, nl, in_size, NS_PROG_DX); break;
-    case NS_DX_INPUT: p = ns_build_one(layers, nl, in_size, NS_PROG_DX_INPUT); break;
-    case NS_GRAD_INPUT: p = ns_build_one(layers, nl, in_size, NS_PROG_FWD_DXI, nullptr, side); break;
-    case NS_TRAIN_STEP: p = ns_build_one(layers, nl, in_size, NS_PROG_TRAIN, dn); break;
-    case NS_TRAIN_STEP_BF16: p = ns_build_one(layers, nl, in_size, NS_PROG_TRAIN, dn, false, true); break;
-    }
-    // the SIDE program where it fits, the plain one otherwise
-    if (side && !(p.ok && (kind != NS_GRAD_INPUT || p.dxi_ok))) return ns_build_kind(kind, layers, nl, in_size, dn, false);
-    return p;
-}
-// Kernel-configuration cache: a program is a pure function of the op list (shapes AND parameter pointers:
-// the pack descriptors carry them), the program kind, the engine (SIDE segments or not) and the dense descriptor, so it
-// is built once and looked up by those bytes on every later launch -- no segment planning, no vector allocation on the
-// launch path.  Entries live for the life of the library (a handful per network; the table is cleared if it ever reaches
-// 256 entries).  A lookup hands out shared ownership: a clear by a later lookup never frees a program a caller still
-// holds.  rows: the engine that runs it (0: any; no SIDE segments).
-typedef std::shared_ptr<const NsProgram> NsProgramRef;
-static NsProgramRef ns_program(NsKind kind, const linna_layer_t* layers, int nl, int in_size, const NsDense* dn, int rows) {
-    static std::mutex mu;
-    static std::unordered_map<std::string, NsProgramRef> cache;
-    const bool side = ns_side(kind, rows);
-    std::string key;
-    key.reserve((size_t)nl * sizeof(linna_layer_t) + 64);
-    key.append(reinterpret_cast<const char*>(layers), (size_t)nl * sizeof(linna_layer_t));
-    const int hdr[4] = {nl, in_size, (int)kind, side ? 1 : 0};
-    key.append(reinterpret_cast<const char*>(hdr), sizeof(hdr));
-    if (dn) {                                               // field by field: the struct has padding bytes
-        const void* const ptrs[3] = {dn->S, dn->cscale, dn->cshift};
-        key.append(reinterpret_cast<const char*>(ptrs), sizeof(ptrs));
-        key.append(reinterpret_cast<const char*>(&dn->lds), sizeof(int));
-        key.append(reinterpret_cast<const char*>(&dn->factored), sizeof(int));
-        key.append(reinterpret_cast<const char*>(&dn->tri), sizeof(int));
-    }
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = cache.find(key);
-    if (it != cache.end()) return it->second;
-    if (cache.size() >= 256) cache.clear();
-    NsProgramRef p = std::make_shared<const NsProgram>(ns_build_kind(kind, layers, nl, in_size, dn, side));
-    cache.emplace(std::move(key), p);
-    return p;
-}
-
-// columns of what segment i of a one-launch forward + backward program (NS_GRAD_INPUT, NS_TRAIN_STEP) writes: the hidden h
-// of a residual block, a forward op's output, or (the backward half) d/d(op input)
-static int ns_seg_cols(const NsProgram& p, const linna_layer_t* layers, int i) {
-    const linna_layer_t& l = layers[p.seg_op[i]];
-    return p.seg_hidden[i] ? l.C : i < p.nseg_f ? l.N : l.K;
-}
-// The gates of a one-launch backward half (NS_GRAD_INPUT, NS_TRAIN_STEP): what the backward gates on is the SIGN of a
-// forward activation, and the workgroup that needs it is the one that computed it -- one bit per (row, column) in LDS
-// behind the program's own LDS (NsArgs::nbw, bits_off).  gbit[i]: the first bit column of forward segment i's signs (-1:
-// no gate asks for them; every tensor rounded up to 64 columns); mbit[i]: the columns backward segment i gates on (-1:
-// none).  ok = false when a gate has no producer.
-struct NsGates {
-    int gbit[NS_MAXSEG], mbit[NS_MAXSEG];
-    int ncols = 0;
-    bool ok = true;
-    size_t lds0 = 0, lds = 0;                               // the program's LDS (8-byte aligned), and with the bits
-};
-static NsGates ns_gates(const NsProgram& p, const linna_layer_t* layers, int nl, int rows) {
-    NsGates g;
-    for (int i = 0; i < NS_MAXSEG; ++i) g.gbit[i] = g.mbit[i] = -1;
-    for (int i = 0; i < p.nseg_f; ++i) {                    // forward: keep the signs a gate will ask for
-        const int op = p.seg_op[i];
-        if (op >= nl || (!p.seg_hidden[i] && op == nl - 1)) continue;   // the loss segment and the network output gate nothing
-        g.gbit[i] = g.ncols;
-        g.ncols += (ns_seg_cols(p, layers, i) + 63) & ~63;
-    }
-    for (int i = p.nseg_f; i < (int)p.seg.size(); ++i) {
-        // d/dh of a residual block: gated by its h; d/d(input of op): by the producing op's output, if it went through a ReLU
-        const int op = p.seg_op[i];
-        const bool hidden = p.seg_hidden[i] != 0;
-        if (!hidden && !(op > 0 && (layers[op - 1].op == LINNA_OP_RESBLOCK || layers[op - 1].relu))) continue;
-        const int src = hidden ? op : op - 1;
-        for (int j = 0; j < p.nseg_f; ++j)
-            if (p.seg_op[j] == src && (p.seg_hidden[j] != 0) == hidden) g.mbit[i] = g.gbit[j];
-        if (g.mbit[i] < 0) g.ok = false;
-    }
-    g.lds0 = (p.lds_for(rows, true) + 7) & ~(size_t)7;
-    g.lds = g.lds0 + (size_t)rows * (g.ncols / 32) * sizeof(unsigned);
-    return g;
-}
-
-// why the bf16 program does not exist for this network (null: it does)
-static const char* ns_bf16_refusal(const NsProgram& p, const linna_layer_t* layers, int nl, int in_size) {
-    int width = 0;
-    for (int i = 0; i < nl; ++i) width = std::max(width, std::max(layers[i].N, layers[i].op == LINNA_OP_RESBLOCK ? layers[i].C : 0));
-    if (in_size > 256) return "more than 256 network inputs: outside the whole-network kernel";
-    if (width > 1024) return "a layer wider than 1024: outside the whole-network kernel";
-    if (nl < 1 || layers[0].op != LINNA_OP_LINEAR) return "the first op is not a linear layer (the bf16 input split needs one)";
-    if (!p.ok) return "the network does not fit the bf16 program of the whole-network kernel";
-    return nullptr;
-}
-NsPlan net_stream_plan(NsKind kind, const linna_layer_t* layers, int nl, int in_size, const NsDense* dn) {
-    const NsProgramRef pref = ns_program(kind, layers, nl, in_size, dn, 0);
-    const NsProgram& p = *pref;
-    NsPlan r{p.ok, p.packed_floats, p.grad_ok, nullptr};
-    if (kind == NS_TRAIN_STEP) r.ok = p.ok && p.train_ok;
-    if (kind == NS_TRAIN_STEP_BF16) {
-        r.why = ns_bf16_refusal(p, layers, nl, in_size);
-        if (!r.why && !p.train_ok) r.why = "the network has no merged training step (one layer only)";
-        r.ok = r.why == nullptr;
-    }
-    if (kind == NS_GRAD_INPUT) {
-        r.ok = p.ok && p.dxi_ok && ns_gates(p, layers, nl, NS_ROWS).lds <= (size_t)NS_LDS_BYTES;
-        // one copy serves every engine: the 16-row one reads the SIDE program
-        r.packed_floats = std::max(r.packed_floats, ns_program(kind, layers, nl, in_size, dn, 16)->packed_floats);
-    }
-    if (kind == NS_SERVE_BF16) { r.why = ns_bf16_refusal(p, layers, nl, in_size); r.ok = r.why == nullptr; }
-    return r;
-}
-
-// Text form of a program (tests, diagnostics): one line per segment, "type steps passes ncg kc dst_col zext".
-int net_stream_describe(NsKind kind, const linna_layer_t* layers, int nl, int in_size, const NsDense* dn, int rows, char* buf, size_t n) {
-    const NsProgramRef pref = ns_program(kind, layers, nl, in_size, dn, rows);
-    const NsProgram& p = *pref;
-    std::string out = p.ok ? "ok" : "not eligible";
-    char line[160];
-    snprintf(line, sizeof line, " G %d Gstride %d nseg_f %d LD %d kpad0 %d packed_floats %zu grad %d\n", p.G, p.Gstride, p.nseg_f, p.LD,
-             p.kpad0, p.packed_floats, (int)p.grad_ok);
-    out += line;
-    for (size_t i = 0; p.ok && i < p.seg.size(); ++i) {
-        const NsSeg& g = p.seg[i];
-        snprintf(line, sizeof line, "%s steps %d passes %d ncg %d kc %d dst %d zext %d N %d\n",
-                 g.type == NS_WIDE ? "WIDE" : g.type == NS_SPLIT ? "SPLIT" : "SIDE", g.steps, g.passes, 1 << g.ncg_log2, 1 << g.kcl, g.dst_col,
-                 g.zext, p.pack[i].N);
-        out += line;
-    }
-    if (p.ok && kind == NS_GRAD_INPUT) {            // the one-launch gradient: its LDS with the sign-bit matrix, on the 16-row engine
-        const NsGates g = ns_gates(p, layers, nl, NS_ROWS);
-        snprintf(line, sizeof line, "lds %zu of %d bytes with %d sign-bit columns: %s\n", g.lds, NS_LDS_BYTES, g.ncols,
-                 g.lds <= (size_t)NS_LDS_BYTES && p.dxi_ok ? "one launch" : "layered");
-        out += line;
-    }
-    if (buf && n) { snprintf(buf, n, "%s", out.c_str()); }
-    return p.ok ? (int)p.seg.size() : 0;
 }
 
 int launch_net_stream_pack(NsKind kind, const linna_layer_t* layers, int nl, int in_size, float* packed, int rows, const NsDense* dn,
@@ -946,17 +380,23 @@ int launch_net_stream_pack(NsKind kind, const linna_layer_t* layers, int nl, int
     return check_hip(hipGetLastError(), "net_stream pack launch");
 }
 
-template <int MOVE, bool GRAD, int STORE, int ROWS, bool BF = false>
-static int ns_launch_rows(const NsArgs& a, int B, size_t lds_bytes, hipStream_t s, int extra = 0) {
+// One launch of the whole-network kernel instantiation `Kernel`: 64 NS_NW threads per workgroup and `lds_bytes` of dynamic
+// LDS, which the instantiation is allowed up to the CU's whole LDS before its first launch.
+template <void (*Kernel)(NsArgs)>
+static int ns_launch(const NsArgs& a, int nblocks, size_t lds_bytes, hipStream_t s, const char* what) {
     static bool attr_set = false;
     if (!attr_set) {
-        const int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(&net_stream_kernel<NS_R, MOVE, GRAD, STORE, ROWS, BF>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, NS_LDS_BYTES), "hipFuncSetAttribute");
+        const int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, NS_LDS_BYTES),
+                                 "hipFuncSetAttribute");
         if (rc != LINNA_OK) return rc;
         attr_set = true;
     }
-    hipLaunchKernelGGL((net_stream_kernel<NS_R, MOVE, GRAD, STORE, ROWS, BF>), dim3((B + ROWS - 1) / ROWS + extra), dim3(64 * NS_NW), lds_bytes, s, a);
-    return check_hip(hipGetLastError(), "net_stream launch");
+    hipLaunchKernelGGL(Kernel, dim3(nblocks), dim3(64 * NS_NW), lds_bytes, s, a);
+    return check_hip(hipGetLastError(), what);
+}
+template <int MOVE, bool GRAD, int STORE, int ROWS, bool BF = false>
+static int ns_launch_rows(const NsArgs& a, int B, size_t lds_bytes, hipStream_t s, int extra = 0) {
+    return ns_launch<net_stream_kernel<NS_R, MOVE, GRAD, STORE, ROWS, BF>>(a, (B + ROWS - 1) / ROWS + extra, lds_bytes, s, "net_stream launch");
 }
 template <int MOVE, bool GRAD, int STORE = 0, bool BF = false>
 static int ns_launch_kernel(const NsArgs& a0, int B, const NsProgram& p, int rows, hipStream_t s, int extra = 0, size_t lds_extra = 0) {
@@ -986,15 +426,7 @@ static int ns_launch_kernel(const NsArgs& a0, int B, const NsProgram& p, int row
 // the slice evaluation of a bf16 serving program: net_stream_slice_bf16_kernel, one instantiation per engine
 template <int ROWS>
 static int ns_launch_slice_bf16_rows(const NsArgs& a, int B, size_t lds_bytes, hipStream_t s) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        const int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(&net_stream_slice_bf16_kernel<NS_R, 2, false, 0, ROWS, true>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, NS_LDS_BYTES), "hipFuncSetAttribute");
-        if (rc != LINNA_OK) return rc;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((net_stream_slice_bf16_kernel<NS_R, 2, false, 0, ROWS, true>), dim3((B + ROWS - 1) / ROWS), dim3(64 * NS_NW), lds_bytes, s, a);
-    return check_hip(hipGetLastError(), "net_stream bf16 slice launch");
+    return ns_launch<net_stream_slice_bf16_kernel<NS_R, 2, false, 0, ROWS, true>>(a, (B + ROWS - 1) / ROWS, lds_bytes, s, "net_stream bf16 slice launch");
 }
 static int ns_launch_slice_bf16(const NsArgs& a, int B, const NsProgram& p, int rows, hipStream_t s) {
 #ifdef NS_STAMPS
@@ -1016,7 +448,6 @@ static int ns_launch_slice_bf16(const NsArgs& a, int B, const NsProgram& p, int 
 // (one store), the dX-chain stream holds the transposed matrix (four 4-byte stores; neighbouring lanes fill
 // neighbouring vectors).  Biases go to the forward stream's bias block.  Constant parts of a stream (zero padding, the
 // loss's inverse covariance) are written by the ordinary re-layout once and never touched here.
-constexpr int AS_BLOCK = 64;               // one wave per block: ~1200 blocks for 1.3 M parameters, five per CU
 __device__ __forceinline__ void as_update(f32x4& P4, const f32x4& G4, f32x4& M4, f32x4& V4, float lr, float wd, float bc1,
                                           float sbc2, float beta1, float beta2, float eps) {
 #pragma unroll
@@ -1119,110 +550,6 @@ __global__ __launch_bounds__(AS_BLOCK) void adamw_streams_kernel(AsArgs a, float
         }
     }
 }
-
-// Descriptor table of adamw_streams_kernel for the flat buffer `params[nflat]` the layers' parameters live in, the
-// forward + loss stream `s_fwd` (NS_TRAIN_FWD with `dn`) and the dX-chain stream `s_dx` (NS_DX).  LINNA_ERR_UNSUPPORTED
-// when the buffer is not exactly the layers' tensors back to back, or a stream folds something into the weights that
-// an element-wise scatter cannot reproduce (output maps, a second bias).
-int net_stream_adamw_args(const linna_layer_t* layers, int nl, int in_size, int rows, const float* params, size_t nflat,
-                          float* s_fwd, const NsDense* dn, float* s_dx, AsArgs* out, int merged) {
-    // merged: ONE stream holds the forward + loss segments [0, nseg_f) and the dX chain [nseg_f, nseg) (NS_TRAIN_STEP)
-    const bool bf = merged == 2;
-    if (bf && rows != 4) { set_error("adamw_streams: the bf16 training stream is the 4-row engine's"); return LINNA_ERR_UNSUPPORTED; }
-    const NsProgramRef pf_ref = ns_program(bf ? NS_TRAIN_STEP_BF16 : merged ? NS_TRAIN_STEP : NS_TRAIN_FWD, layers, nl, in_size, dn, rows);
-    const NsProgramRef pd_ref = merged ? pf_ref : ns_program(NS_DX, layers, nl, in_size, nullptr, rows);
-    const NsProgram& pf = *pf_ref;
-    const NsProgram& pd = *pd_ref;
-    if (merged) s_dx = s_fwd;
-    if (!pf.ok || !pd.ok || !s_fwd || !s_dx || (merged && !pf.train_ok)) { set_error("adamw_streams: no forward / dX-chain program"); return LINNA_ERR_UNSUPPORTED; }
-    const size_t f_lo = 0, f_hi = merged ? (size_t)pf.nseg_f : pf.pack.size();
-    const size_t d_lo = merged ? (size_t)pf.nseg_f : 0, d_hi = pd.pack.size();
-    ::memset(static_cast<void*>(out), 0, sizeof(*out));
-    out->small = rows < 16;
-    struct T { const float* ptr; int N, K, bias; };
-    std::vector<T> ts;
-    for (int i = 0; i < nl; ++i) {
-        const linna_layer_t& l = layers[i];
-        if (l.op == LINNA_OP_LINEAR) { ts.push_back({l.W, l.N, l.K, 0}); ts.push_back({l.b, l.N, 0, 1}); }
-        else if (l.op == LINNA_OP_RESBLOCK) {
-            ts.push_back({l.W1, l.C, l.K, 0}); ts.push_back({l.b1, l.C, 0, 1});
-            ts.push_back({l.W2, l.N, l.C, 0}); ts.push_back({l.b2, l.N, 0, 1});
-            if (l.Ws) ts.push_back({l.Ws, l.N, l.K, 0});
-        } else { set_error("adamw_streams: op %d", l.op); return LINNA_ERR_UNSUPPORTED; }
-    }
-    std::sort(ts.begin(), ts.end(), [](const T& x, const T& y) { return x.ptr < y.ptr; });
-    if ((int)ts.size() > AS_MAXR) { set_error("adamw_streams: %d tensors", (int)ts.size()); return LINNA_ERR_UNSUPPORTED; }
-    auto runs_first = [](const NsProgram& p, int seg, int pass) {
-        int first = 0;
-        for (int i = 0; i < seg; ++i) first += ns_seg_steps(p.seg[i]);
-        return first + pass * p.seg[seg].steps;
-    };
-    // q2 (bf16 stream): where the second half of the first layer's [W | W] goes
-    auto place = [&](const NsProgram& p, float* base, const float* W, int K, AsPlace* q, size_t lo, size_t hi, AsPlace* q2) -> int {
-        for (size_t i = lo; i < hi; ++i) {
-            const NsPackSeg& S = p.pack[i];
-            const bool isA = S.Wa == W, isB = S.Wb == W;
-            if (!isA && !isB) continue;
-            if (q->out) { set_error("adamw_streams: a weight matrix twice in one stream"); return LINNA_ERR_UNSUPPORTED; }
-            if (S.rscale || S.rshift || S.b2) { set_error("adamw_streams: folded output map"); return LINNA_ERR_UNSUPPORTED; }
-            if (p.seg[i].passes > 2) { set_error("adamw_streams: %d passes", p.seg[i].passes); return LINNA_ERR_UNSUPPORTED; }
-            auto fill = [&](AsPlace* d, bool a_part) {
-                d->out = base; d->scale = a_part ? 1.f : S.alpha; d->trans = a_part ? S.transA : S.transB; d->koff = a_part ? 0 : S.Kapad;
-                d->ncols = S.N; d->type = S.type; d->ncg = S.ncg; d->steps = S.steps; d->G = p.Gstride;
-                d->first0 = runs_first(p, (int)i, 0); d->first1 = p.seg[i].passes > 1 ? runs_first(p, (int)i, 1) : d->first0;
-                if (bf && !d->trans) d->ncols = K;         // (bf16: the bound on the columns of W a writer stores)
-            };
-            if (isA && isB) {                               // the bf16 first layer [W | W]
-                if (!bf || !q2 || q2->out) { set_error("adamw_streams: a weight matrix twice in one segment"); return LINNA_ERR_UNSUPPORTED; }
-                fill(q, true); fill(q2, false);
-            } else {
-                fill(q, isA);
-            }
-        }
-        return LINNA_OK;
-    };
-    size_t off = 0;
-    unsigned blk = 0;
-    int nw = 0, nb = 0;
-    for (size_t i = 0; i < ts.size(); ++i) {
-        const T& t = ts[i];
-        if (!t.ptr || t.ptr != params + off) { set_error("adamw_streams: the parameters are not one contiguous buffer"); return LINNA_ERR_UNSUPPORTED; }
-        const int ld = t.bias ? 0 : (t.K + 3) & ~3;
-        const size_t nf = t.bias ? (size_t)((t.N + 3) & ~3) : (size_t)t.N * ld;
-        AsRange& R = out->r[i];
-        R.off4 = (unsigned)(off / 4); R.blk0 = blk; R.kind = (short)t.bias;
-        R.n4 = t.bias ? (unsigned)(nf / 4) : (unsigned)((t.N + 3) / 4) * (unsigned)(ld / 4);      // work items (see the kernel)
-        blk += (R.n4 + AS_BLOCK - 1) / AS_BLOCK;
-        if (t.bias) {
-            if (nb >= AS_MAXB) { set_error("adamw_streams: biases"); return LINNA_ERR_UNSUPPORTED; }
-            R.idx = (short)nb;
-            AsBias& B = out->b[nb++];
-            B.N = t.N;
-            for (size_t j = f_lo; j < f_hi; ++j) {
-                const NsPackSeg& S = pf.pack[j];
-                if (S.b != t.ptr) continue;
-                if (B.out || S.rscale || S.rshift || S.b2) { set_error("adamw_streams: bias folded or used twice"); return LINNA_ERR_UNSUPPORTED; }
-                B.out = s_fwd + (size_t)NS_NW * pf.Gstride * NS_NT * 256 + S.bias_off; B.scale = S.bscale;
-            }
-            for (size_t j = d_lo; j < d_hi; ++j) if (pd.pack[j].b == t.ptr) { set_error("adamw_streams: bias in the dX program"); return LINNA_ERR_UNSUPPORTED; }
-        } else {
-            if (nw >= AS_MAXW) { set_error("adamw_streams: weight matrices"); return LINNA_ERR_UNSUPPORTED; }
-            R.idx = (short)nw;
-            AsMat& W = out->w[nw++];
-            W.N = t.N; W.ld = ld;
-            int rc = place(pf, s_fwd, t.ptr, t.K, &W.pl[0], f_lo, f_hi, &W.pl[1]);
-            if (rc == LINNA_OK) rc = place(pd, s_dx, t.ptr, t.K, &W.pl[1], d_lo, d_hi, nullptr);
-            if (rc != LINNA_OK) return rc;
-            if (!W.pl[0].out) { set_error("adamw_streams: a weight matrix outside the forward stream"); return LINNA_ERR_UNSUPPORTED; }
-        }
-        off += nf;
-    }
-    if (off != nflat) { set_error("adamw_streams: %zu of %zu floats covered", off, nflat); return LINNA_ERR_UNSUPPORTED; }
-    // every pack segment's weights must have been found among the tensors (the loss's constant matrix excepted)
-    out->nr = (int)ts.size(); out->nblocks = blk;
-    return LINNA_OK;
-}
-
 int launch_adamw_streams(const AsArgs& a, float* p, const float* g, float* m, float* v, const float* hyper, float b1, float b2,
                          float eps, hipStream_t s, bool bf) {
     if (bf) hipLaunchKernelGGL(adamw_streams_kernel<true>, dim3(a.nblocks), dim3(AS_BLOCK), 0, s, a, p, g, m, v, hyper, b1, b2, eps);
@@ -1418,18 +745,11 @@ int launch_net_stream_train_bwd(const linna_layer_t* layers, int nl, int in_size
     int extra = 0;
     if (post && post->step) { a.p_step = post->step; a.p_hyper = post->hyper; a.p_b1 = post->b1; a.p_b2 = post->b2; extra = 1; }
     if (bf) {
-        static bool attr_set = false;
 #ifdef NS_STAMPS
         set_error("net_stream: the NS_STAMPS build has no bf16 training step"); return LINNA_ERR_UNSUPPORTED;
 #endif
-        if (!attr_set) {
-            const int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(&net_stream_train_bf16_kernel<NS_R, 0, true, 3, 4, true>),
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, NS_LDS_BYTES), "hipFuncSetAttribute");
-            if (rc != LINNA_OK) return rc;
-            attr_set = true;
-        }
-        hipLaunchKernelGGL((net_stream_train_bf16_kernel<NS_R, 0, true, 3, 4, true>), dim3((B + 3) / 4 + extra), dim3(64 * NS_NW), p.lds_for(rows, true) + lds_extra, s, a);
-        return check_hip(hipGetLastError(), "net_stream bf16 training launch");
+        return ns_launch<net_stream_train_bf16_kernel<NS_R, 0, true, 3, 4, true>>(a, (B + 3) / 4 + extra, p.lds_for(rows, true) + lds_extra, s,
+                                                                                  "net_stream bf16 training launch");
     }
     return ns_launch_kernel<0, true, 3>(a, B, p, rows, s, extra, lds_extra);
 }

@@ -294,7 +294,7 @@
             if (prow && row0 + pr < a.B && c < a.t_ldxb)
                 asm volatile("global_store_dword %0, %1, off" :: "v"(a.t_xb + (size_t)(row0 + pr) * a.t_ldxb + c), "v"(x) : "memory");
         }
-        if constexpr (BF) {                         // x_hi at c, x_lo at nin + c, zeros from 2 nin (ns_build_one: [W | W])
+        if constexpr (BF) {                         // x_hi at c, x_lo at nin + c, zeros from 2 nin (net_program.hip, ns_lower: [W | W])
             if (prow) {
                 if (in) { const float hi = (float)(__bf16)x; act[pr * LD + c] = hi; act[pr * LD + nin + c] = x - hi; }
                 else if (c >= 2 * nin && c < kpad0) act[pr * LD + c] = 0.f;

@@ -438,13 +438,13 @@ class ResBlock_batchnorm(object):
         self.op = _Op(_lib.OP_RESBLOCK, "block", in_size, out_size, C=channel)
 
 
-def describe_program(model, rows=16, dense_nout=0):
-    """The serving program the whole-network kernel would run for ``model`` on the engine of ``rows`` rows per workgroup, as
-    text (``linna_program_describe``: host-side planning, no GPU needed; parameter pointers are placeholders)."""
+def program_layers(model):
+    """``model.ops`` as the ``linna_layer_t`` array the host-side planner reads: shapes and flags of every op, parameter
+    pointers as placeholders (distinct, 16-byte aligned, never read)."""
     arr = _lib.sized_array(_lib.Layer, len(model.ops))
     nxt = [4096]
 
-    def fake(n):                                            # distinct, 16-byte aligned, never read
+    def fake(n):
         p = nxt[0]
         nxt[0] += 16 * ((int(n) + 3) // 4 + 1)
         return C.c_void_p(p)
@@ -457,6 +457,13 @@ def describe_program(model, rows=16, dense_nout=0):
                 L.Ws = fake(op.N * op.K)
         else:
             L.W, L.b = fake(op.N * op.K), fake(op.N)
+    return arr
+
+
+def describe_program(model, rows=16, dense_nout=0):
+    """The serving program the whole-network kernel would run for ``model`` on the engine of ``rows`` rows per workgroup, as
+    text (``linna_program_describe``: host-side planning, no GPU needed; parameter pointers are placeholders)."""
+    arr = program_layers(model)
     buf = C.create_string_buffer(8192)
     n = _lib.load().linna_program_describe(arr, len(model.ops), model.in_size, int(rows), int(dense_nout), buf, len(buf))
     if n < 0:

@@ -593,7 +593,7 @@ def test_dense_covariance_in_the_direct_form_as_a_side_segment(nout, how, monkey
     """chi^2 = d S d^T with S itself as the program's last segment (not its Cholesky factor): what a caller gets with
     LINNA_DENSE_FACTORED=0, and what a singular / indefinite inverse covariance gets by itself (the factorisation fails,
     util.py:953-955 has no such requirement).  For nout <= 64 that segment is a SIDE segment of the 16-row serving engine
-    (outside the weight stream, net_stream.hip `last_ok`): every engine against the float64 oracle and the layered path."""
+    (outside the weight stream, net_program.hip `NsShapeCtx::last_side`): every engine against the float64 oracle and the layered path."""
     from oracle import likelihood
     nin = 8
     prob = _custom_problem(nin, nout, 900 + nout, 64, 2, dense=True)
