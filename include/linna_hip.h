@@ -301,11 +301,29 @@ int linna_weights_changed(linna_ctx_t* ctx);
  * laid out on first use and follow the weights like the fp32 copy (linna_adamw_step, linna_graph_launch,
  * linna_weights_changed).  LINNA_ERR_UNSUPPORTED when the object cannot be served in bf16: a dense inverse covariance, a
  * network outside the whole-network kernel (wider than 1024, more than 256 inputs) or one whose first op is not a linear
- * layer.  LINNA_ERR_INVALID for a NULL handle or an unknown code (no GPU needed). */
+ * layer.  LINNA_ERR_INVALID for a NULL handle or an unknown code (no GPU needed).  The gradient entries have a bf16 form
+ * behind a second, separate opt-in: linna_logprob_set_grad_precision below. */
 #define LINNA_PRECISION_FP32 0
 #define LINNA_PRECISION_BF16 1
 int linna_logprob_set_precision(linna_logprob_t* lp, int precision);
 int linna_logprob_precision(const linna_logprob_t* lp, int* out);
+/* Gradient precision of a log-probability object (codes as above; default LINNA_PRECISION_FP32).  LINNA_PRECISION_BF16 is
+ * accepted only on a handle whose serving precision is already bf16 (LINNA_ERR_INVALID otherwise: a handle has ONE lnP
+ * surface), and makes linna_logprob_grad and linna_logprob_grad_leapfrog run lnP and d lnP / d z in one launch of the
+ * whole-network kernel on a bf16 weight stream of its own (forward segments, then the dX chain down to the input).  What is
+ * rounded where: the weights of both halves to bf16 (nearest-even) after the fp32 folding of a residual block's 0.1, so a
+ * weight has ONE bf16 value forward and transposed; the network input enters as bf16(x) + bf16(x - bf16(x)); the activations
+ * of the forward half and the deltas of the backward half are rounded where the matrix cores read them, accumulated in fp32.
+ * Kept in fp32: every epilogue (bias, ReLU, the gates -- the signs of the ROUNDED forward's activations), the turnaround
+ * (output map, diagonal likelihood, d lnP / d out), the prior map and its derivative, and the leapfrog's kick and drift.
+ * lnP of this launch and of linna_logprob_eval on the same handle round in the same places.  With bf16 set the gradient
+ * entries run that launch or return LINNA_ERR_UNSUPPORTED (LINNA_DISABLE_FUSED), never a layered or an fp32 form.
+ * LINNA_ERR_UNSUPPORTED, with the reason, where no such program exists: an exp (ypositive) output map, an input-skip network,
+ * more than 64 inputs or outputs, a network outside the bf16 engine, sign bits that do not fit the LDS.  The checks need no
+ * GPU; the stream copy is allocated here (call it outside graph capture), laid out on first use, and follows the weights like
+ * the others.  linna_logprob_set_precision(lp, LINNA_PRECISION_FP32) resets the gradient precision to fp32 as well. */
+int linna_logprob_set_grad_precision(linna_logprob_t* lp, int precision);
+int linna_logprob_grad_precision(const linna_logprob_t* lp, int* out);
 /* Rows per workgroup of the whole-network kernel: 0 (default) = chosen per launch from the batch size -- the fewest
  * of 4 / 8 / 16 that still fit the batch into one workgroup per CU; 4, 8 or 16 = that engine for every launch of the
  * process (tests and measurements; results differ between engines in the last bits: another summation order over k).
@@ -335,6 +353,10 @@ int linna_slice_fusion(int mask);
  * kernel's reach. */
 int linna_program_describe(const linna_layer_t* layers, int nlayers, int in_size, int rows, int dense_nout, char* buf,
                            size_t n);
+/* The same text for the program of the bf16 one-launch gradient (linna_logprob_set_grad_precision): forward segments over
+ * [x_hi ; x_lo], then the dX chain down to the input, 32 k per step, no SIDE segments; the last line reports the sign-bit
+ * columns.  Returns 0 segments where the network has no such program. */
+int linna_program_describe_grad_bf16(const linna_layer_t* layers, int nlayers, int in_size, int rows, char* buf, size_t n);
 size_t linna_logprob_ws_bytes(const linna_logprob_t* lp, int B, int with_grad);
 /* lnP[B]; THETA[B][ldt] optional (physical parameters, for chain_transformed). */
 int linna_logprob_eval(linna_logprob_t* lp, const float* Z, int ldz, int B, void* ws, float* lnP,

@@ -5,6 +5,11 @@ gradient comes from the HIP reverse pass instead of torch autograd); ``x0`` is o
 ``[ndim]`` as in the reference, or ``[B, ndim]`` for B independent chains advanced together.
 ``sample(num_samps, num_steps, step_size)`` returns the reference's list of dicts for a single
 chain.  ``momenta`` / ``uniforms`` may be supplied to replay a given random stream.
+
+``lnP`` may be a ``Log_prob(precision="bf16", grad_precision="bf16")``: every leapfrog step is then one launch of the bf16
+whole-network kernel, and the chain samples the bf16 lnP surface exactly (lnP at both ends of a trajectory comes from that
+same launch form); the rounded gradient only lowers the acceptance rate.  ``precision="bf16"`` alone has no gradient and
+is refused when the sampler is built.
 """
 import numpy as np
 import torch

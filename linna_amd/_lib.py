@@ -126,6 +126,8 @@ _SIGNATURES = {
     "linna_weights_changed": (_I, [_V]),
     "linna_logprob_set_precision": (_I, [_V, _I]),
     "linna_logprob_precision": (_I, [_V, _V]),
+    "linna_logprob_set_grad_precision": (_I, [_V, _I]),
+    "linna_logprob_grad_precision": (_I, [_V, _V]),
     "linna_engine_rows": (_I, [_I]),
     "linna_dense_tri": (_I, [_I]),
     "linna_slice_fusion": (_I, [_I]),
@@ -133,6 +135,7 @@ _SIGNATURES = {
     "linna_net_set_train_precision": (_I, [_V, _I]),
     "linna_net_train_precision": (_I, [_V, _V]),
     "linna_program_describe": (_I, [_V, _I, _I, _I, _I, _V, C.c_size_t]),
+    "linna_program_describe_grad_bf16": (_I, [_V, _I, _I, _I, _V, C.c_size_t]),
     "linna_logprob_ws_bytes": (_SZ, [_V, _I, _I]),
     "linna_logprob_eval": (_I, [_V, _V, _I, _I, _V, _V, _V, _I, _V]),
     "linna_logprob_grad": (_I, [_V, _V, _I, _I, _V, _V, _V, _I, _V]),

@@ -911,6 +911,8 @@ struct linna_logprob {
     int precision = LINNA_PRECISION_FP32;    // linna_logprob_set_precision
     StreamCopy packed_bf;                    // the bf16 weight streams (allocated when bf16 is first set, laid out lazily)
     bool bf16() const { return precision == LINNA_PRECISION_BF16; }
+    int grad_precision = LINNA_PRECISION_FP32;   // linna_logprob_set_grad_precision (bf16 only on a bf16 handle)
+    StreamCopy packed_gbf;                   // the bf16 forward + dX-chain streams (NS_GRAD_INPUT_BF16), allocated when it is first set
     NsKind kind() const { return bf16() ? NS_SERVE_BF16 : dense_fused ? NS_SERVE_DENSE : NS_SERVE; }   // the serving program
 };
 
@@ -1057,7 +1059,7 @@ int linna_logprob_create(linna_ctx_t* ctx, linna_net_t* net, const linna_logprob
     return LINNA_OK;
 } LINNA_CATCH_INT
 int linna_logprob_destroy(linna_logprob_t* lp) try {
-    if (lp) { lp->packed.release(); lp->packed_g2.release(); lp->packed_bf.release(); }
+    if (lp) { lp->packed.release(); lp->packed_g2.release(); lp->packed_bf.release(); lp->packed_gbf.release(); }
     delete lp;
     return LINNA_OK;
 } LINNA_CATCH_INT
@@ -1070,7 +1072,7 @@ int linna_logprob_set_precision(linna_logprob_t* lp, int precision) try {
         set_error("logprob_set_precision: unknown precision %d (LINNA_PRECISION_FP32 0, LINNA_PRECISION_BF16 1)", precision);
         return LINNA_ERR_INVALID;
     }
-    if (precision == LINNA_PRECISION_FP32) { lp->precision = precision; return LINNA_OK; }
+    if (precision == LINNA_PRECISION_FP32) { lp->precision = precision; lp->grad_precision = LINNA_PRECISION_FP32; return LINNA_OK; }
     const linna_net* n = lp->net;
     if (!lp->d.w) { set_error("logprob_set_precision: bf16 needs a diagonal likelihood (a dense covariance is served in fp32 only)"); return LINNA_ERR_UNSUPPORTED; }
     const NsPlan bf = net_stream_plan(NS_SERVE_BF16, n->Lfull.data(), (int)n->Lfull.size(), n->in_size);
@@ -1089,6 +1091,44 @@ int linna_logprob_precision(const linna_logprob_t* lp, int* out) try {
     if (!lp || !out) { set_error("logprob_precision: null argument"); return LINNA_ERR_INVALID; }
     *out = lp->precision;
     return LINNA_OK;
+} LINNA_CATCH_INT
+// The second opt-in of a bf16 handle: lnP and its gradient from the bf16 one-launch program.  Checks first (no GPU needed),
+// then the third stream copy is allocated here and laid out by the first launch that reads it (weight epoch).
+int linna_logprob_set_grad_precision(linna_logprob_t* lp, int precision) try {
+    if (!lp) { set_error("logprob_set_grad_precision: null handle"); return LINNA_ERR_INVALID; }
+    if (precision != LINNA_PRECISION_FP32 && precision != LINNA_PRECISION_BF16) {
+        set_error("logprob_set_grad_precision: unknown precision %d (LINNA_PRECISION_FP32 0, LINNA_PRECISION_BF16 1)", precision);
+        return LINNA_ERR_INVALID;
+    }
+    if (precision == LINNA_PRECISION_FP32) { lp->grad_precision = precision; return LINNA_OK; }
+    if (!lp->bf16()) {
+        set_error("logprob_set_grad_precision: a bf16 gradient needs a bf16 handle (linna_logprob_set_precision first): lnP has one surface per handle");
+        return LINNA_ERR_INVALID;
+    }
+    const linna_net* n = lp->net;
+    if (lp->d.outmap.cexp) { set_error("logprob_set_grad_precision: no bf16 gradient: the ypositive (exp) output map has no gradient path"); return LINNA_ERR_UNSUPPORTED; }
+    if (!lp->d.w || !lp->d.gscale) { set_error("logprob_set_grad_precision: no bf16 gradient: it needs a diagonal likelihood with gscale"); return LINNA_ERR_UNSUPPORTED; }
+    const NsPlan g = net_stream_plan(NS_GRAD_INPUT_BF16, n->Lfull.data(), (int)n->Lfull.size(), n->in_size);
+    if (!g.ok) {
+        set_error("logprob_set_grad_precision: no bf16 gradient for this network: %s", g.why ? g.why : "not eligible");
+        return LINNA_ERR_UNSUPPORTED;
+    }
+    if (!lp->packed_gbf.ready() && lp->packed_gbf.alloc(g.packed_floats) != LINNA_OK) {
+        set_error("logprob_set_grad_precision: hipMalloc(bf16 gradient weight stream) failed");
+        return LINNA_ERR_HIP;
+    }
+    lp->grad_precision = precision;
+    return LINNA_OK;
+} LINNA_CATCH_INT
+int linna_logprob_grad_precision(const linna_logprob_t* lp, int* out) try {
+    if (!lp || !out) { set_error("logprob_grad_precision: null argument"); return LINNA_ERR_INVALID; }
+    *out = lp->grad_precision;
+    return LINNA_OK;
+} LINNA_CATCH_INT
+int linna_program_describe_grad_bf16(const linna_layer_t* layers, int nlayers, int in_size, int rows, char* buf, size_t n) try {
+    if (!layers || nlayers < 1 || !buf || !n) { set_error("program_describe_grad_bf16: bad arguments"); return LINNA_ERR_INVALID; }
+    for (int i = 0; i < nlayers; ++i) CHECK_STRUCT(layers + i, linna_layer_t, "program_describe_grad_bf16");
+    return net_stream_describe(NS_GRAD_INPUT_BF16, layers, nlayers, in_size, nullptr, rows, buf, n);
 } LINNA_CATCH_INT
 int linna_program_describe(const linna_layer_t* layers, int nlayers, int in_size, int rows, int dense_nout, char* buf, size_t n) try {
     if (!layers || nlayers < 1 || !buf || !n) { set_error("program_describe: bad arguments"); return LINNA_ERR_INVALID; }
@@ -1341,11 +1381,27 @@ int linna_chain_meanstd(linna_ctx_t*, const float* CT, int ndim, int nwp, int nw
 static int logprob_grad_impl(linna_logprob_t* lp, const float* Z, int ldz, int B, void* ws, float* lnP, float* G, int ldg,
                              const NsGrad* leap, void* stream) {
     if (!lp || !Z || !ws || !lnP || !G || B < 1) { set_error("logprob_grad: bad arguments"); return LINNA_ERR_INVALID; }
-    if (lp->bf16()) {
+    if (lp->bf16() && lp->grad_precision != LINNA_PRECISION_BF16) {
         set_error("logprob_grad: this log-probability is set to bf16, which serves lnP only (no bf16 gradient); set it back to fp32");
         return LINNA_ERR_UNSUPPORTED;
     }
     const linna_logprob_desc_t& d = lp->d;
+    if (lp->bf16()) {
+        // the bf16 one-launch program or nothing: never a layered or fp32 form
+        if (!fused_enabled() || !lp->packed_gbf.ready() || !d.w || !d.gscale || d.outmap.cexp) {
+            set_error("logprob_grad: this bf16 log-probability cannot run its one-launch gradient here (LINNA_DISABLE_FUSED, or no bf16 gradient stream)");
+            return LINNA_ERR_UNSUPPORTED;
+        }
+        NsGrad gb{d.gscale, G, ldg, nullptr, 0, nullptr, nullptr, 0.f, 0.f};
+        if (leap) { gb.hm_p = leap->hm_p; gb.hm_ldp = leap->hm_ldp; gb.hm_q = leap->hm_q; gb.hm_mass = leap->hm_mass; gb.hm_ek = leap->hm_ek; gb.hm_ed = leap->hm_ed; }
+        const linna_net* n = lp->net;
+        const int rows = net_stream_rows(B);
+        const float* packed = nullptr;
+        TRY(stream_copy_refresh(lp->packed_gbf, n, rows, stream, &packed, NS_GRAD_INPUT_BF16));
+        return launch_net_stream_grad2(n->L.data(), (int)n->L.size(), n->in_size, packed, Z, ldz, B, d.nin, d.is_flat, d.a1, d.a2,
+                                       d.log10_flag, d.xmean, d.xstd, d.outmap.cscale, d.outmap.cshift, d.w, d.temperature, lnP, gb,
+                                       rows, S(stream), true);
+    }
     if (d.outmap.cexp) { set_error("logprob_grad: ypositive (exp) output map has no gradient path"); return LINNA_ERR_UNSUPPORTED; }
     if (!d.gscale || (!d.w && !d.Ssym)) { set_error("logprob_grad: descriptor lacks gscale / Ssym"); return LINNA_ERR_INVALID; }
     NsGrad gr{d.gscale, G, ldg, nullptr, 0, nullptr, nullptr, 0.f, 0.f};

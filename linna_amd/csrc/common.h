@@ -400,12 +400,13 @@ enum NsKind {
     NS_GRAD_INPUT,     // forward + dX chain down to the input: lnP and its gradient in one launch, any network it covers
     NS_TRAIN_STEP,     // forward + loss + dX chain down to op 1: the merged training step (4-row engine)
     NS_TRAIN_STEP_BF16,   // ... in bf16 (linna_net_set_train_precision): bf16 runs, the loss segment an fp32 run, first layer [W | W]
+    NS_GRAD_INPUT_BF16,   // NS_GRAD_INPUT in bf16 (linna_logprob_set_grad_precision): every run bf16, first layer [W | W], no SIDE segments
 };
 // the serving programs are built from the layer list with the trailing input skip, the training ones from the list without
 inline bool ns_kind_full_layers(NsKind k) { return k == NS_SERVE || k == NS_SERVE_DENSE || k == NS_SERVE_BF16; }
-// Planning query (no GPU): ok: the network has this program (NS_GRAD_INPUT: and its sign-bit gates fit the LDS;
-// NS_TRAIN_STEP: with the dX chain); packed_floats: the size of a copy of its weight stream, for every engine; grad_ok: the
-// serving program holds the fused MLP gradient; why: NS_SERVE_BF16's / NS_TRAIN_STEP_BF16's reason when it is refused.
+// Planning query (no GPU): ok: the network has this program (NS_GRAD_INPUT, NS_GRAD_INPUT_BF16: and its sign-bit gates fit
+// the LDS; NS_TRAIN_STEP: with the dX chain); packed_floats: the size of a copy of its weight stream, for every engine;
+// grad_ok: the serving program holds the fused MLP gradient; why: the reason when a bf16 kind is refused.
 struct NsPlan { bool ok; size_t packed_floats; bool grad_ok; const char* why; };
 NsPlan net_stream_plan(NsKind kind, const linna_layer_t* layers, int nl, int in_size, const NsDense* dn = nullptr);
 // rows per workgroup for a batch of B rows: 16 (v_mfma_f32_16x16x4_f32), or 8 / 4 (v_mfma_f32_4x4x1_16b_f32) when 16-row
@@ -501,11 +502,11 @@ int net_stream_adamw_args(const linna_layer_t* layers, int nl, int in_size, int 
                           float* s_fwd, const NsDense* dn, float* s_dx, AsArgs* out, int merged = 0);
 int launch_adamw_streams(const AsArgs& a, float* p, const float* g, float* m, float* v, const float* hyper, float b1, float b2,
                          float eps, hipStream_t s, bool bf = false);
-// forward + dX chain down to the input in one launch (NS_GRAD_INPUT; diagonal covariance)
+// forward + dX chain down to the input in one launch (NS_GRAD_INPUT, or bf: NS_GRAD_INPUT_BF16; diagonal covariance)
 int launch_net_stream_grad2(const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* Z, int ldz, int B,
                             int nin, const int* is_flat, const float* a1, const float* a2, const int* lg, const float* xmean,
                             const float* xstd, const float* cscale, const float* cshift, const float* w, float T, float* lnP,
-                            const NsGrad& gr, int rows, hipStream_t s);
+                            const NsGrad& gr, int rows, hipStream_t s, bool bf = false);
 // a serving launch (kind NS_SERVE, NS_SERVE_DENSE with dn, or NS_SERVE_BF16)
 int launch_net_stream(NsKind kind, const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* Z, int ldz, int B,
                       int nin, const int* is_flat, const float* a1, const float* a2, const int* lg, const float* xmean,

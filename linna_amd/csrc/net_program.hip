@@ -70,7 +70,7 @@ struct NsBuildOpts {
     // SPLIT segments of <= 32 columns become SIDE segments where they fit (see NsPackArgs): the kernel's K4 path, i.e. the
     // 16-row engine of the programs ns_side names
     bool side = false;
-    // the bf16 programs (serving without a dense segment, the merged training step; no SIDE segments): a step is 32 k, and the
+    // the bf16 programs (serving without a dense segment, the merged training step, the one-launch gradient; no SIDE segments): a step is 32 k, and the
     // first layer (a plain linear map) is [W | W] over K' = 2 nin -- its input rows are x_hi = bf16(x) and x_lo = x - x_hi
     bool bf = false;
 };
@@ -428,6 +428,7 @@ static NsProgram ns_build_kind(NsKind kind, const linna_layer_t* layers, int nl,
     case NS_DX: o.forward = false; break;
     case NS_DX_INPUT: o.forward = false; o.dx_first = 0; break;
     case NS_GRAD_INPUT: o.bwd = NS_BWD_INPUT; break;
+    case NS_GRAD_INPUT_BF16: o.bwd = NS_BWD_INPUT; o.bf = true; if (dn) return NsProgram(); break;
     case NS_TRAIN_STEP: case NS_TRAIN_STEP_BF16: o.dense = true; o.bwd = NS_BWD_TRAIN; o.bf = kind == NS_TRAIN_STEP_BF16; break;
     }
     NsProgram p = ns_build_one(layers, nl, in_size, o, dn);
@@ -518,6 +519,17 @@ NsPlan net_stream_plan(NsKind kind, const linna_layer_t* layers, int nl, int in_
         r.packed_floats = std::max(r.packed_floats, ns_program(kind, layers, nl, in_size, dn, 16)->packed_floats);
     }
     if (kind == NS_SERVE_BF16) { r.why = ns_bf16_refusal(p, layers, nl, in_size); r.ok = r.why == nullptr; }
+    if (kind == NS_GRAD_INPUT_BF16) {
+        // the reasons of its own first: ns_lower refuses them all as "does not fit"
+        bool inskip = false;
+        for (int i = 0; i < nl; ++i) inskip = inskip || layers[i].op == LINNA_OP_INSKIP;
+        if (inskip) r.why = "an input-skip network has no one-launch gradient";
+        else if (in_size > 64 || (nl >= 1 && layers[nl - 1].N > 64)) r.why = "more than 64 network inputs or outputs: outside the one-launch gradient";
+        else r.why = ns_bf16_refusal(p, layers, nl, in_size);
+        if (!r.why && !p.dxi_ok) r.why = "the network has no forward + dX program";
+        if (!r.why && ns_gates(p, layers, nl, NS_ROWS).lds > (size_t)NS_LDS_BYTES) r.why = "the sign bits of the one-launch gradient do not fit the LDS";
+        r.ok = r.why == nullptr;
+    }
     return r;
 }
 
@@ -537,7 +549,7 @@ int net_stream_describe(NsKind kind, const linna_layer_t* layers, int nl, int in
                  g.zext, p.pack[i].N);
         out += line;
     }
-    if (p.ok && kind == NS_GRAD_INPUT) {            // the one-launch gradient: its LDS with the sign-bit matrix, on the 16-row engine
+    if (p.ok && (kind == NS_GRAD_INPUT || kind == NS_GRAD_INPUT_BF16)) {            // the one-launch gradient: its LDS with the sign-bit matrix, on the 16-row engine
         const NsGates g = ns_gates(p, layers, nl, NS_ROWS);
         snprintf(line, sizeof line, "lds %zu of %d bytes with %d sign-bit columns: %s\n", g.lds, NS_LDS_BYTES, g.ncols,
                  g.lds <= (size_t)NS_LDS_BYTES && p.dxi_ok ? "one launch" : "layered");

@@ -292,7 +292,7 @@ __device__ __forceinline__ float ns_prior_theta(float z, int flat, float a1, flo
 // stores: the compiler does not see them, so its counted vmcnt waits for the weight stream stay counted
 // (stores only ever make the hardware counter read higher, i.e. the waits conservative).
 // BF: the opt-in bf16 serving engine (linna_logprob_set_precision; MOVE 0 / 1, no GRAD, no STORE; MOVE 2 is the same engine
-// in a kernel of its own, net_stream_slice_bf16_kernel).  The stream holds bf16
+// in a kernel of its own, net_stream_slice_bf16_kernel; so is GRAD + STORE == 2, net_stream_grad_bf16_kernel).  The stream holds bf16
 // weights (ns_pack_kernel, p.bf) and one step covers 32 k x 64 columns -- the same 4 KiB per wave and step, so the ring,
 // its four 1-KiB loads and the counted waits keep their shape and a segment takes half the steps.  Activations stay fp32
 // in LDS and are rounded to bf16 (nearest-even) where the A operand is read: two ds_read_b128 per step (8 k per lane).
@@ -307,7 +307,8 @@ __device__ __forceinline__ float ns_prior_theta(float z, int flat, float a1, flo
 // run inside the same stream -- both formats move 4 KiB per wave and step, so only the consumer differs.  It is chosen
 // once per run (begin_run: f32run); inside `step` the choice selects between two MFMA sequences and touches no memory.
 // The kernel body is net_stream_body.inc, the text of the kernels below: the whole-network kernel, the opt-in bf16 slice
-// evaluation (MOVE == 2 on a bf16 stream, described at net_stream_slice_bf16_kernel), and the opt-in bf16
+// evaluation (MOVE == 2 on a bf16 stream, described at net_stream_slice_bf16_kernel), the opt-in bf16 one-launch gradient
+// (described at net_stream_grad_bf16_kernel), and the opt-in bf16
 // training step (linna_net_set_train_precision) -- the merged training launch (GRAD + STORE == 3, 4-row engine) on a bf16
 // stream whose loss segment stays fp32, a kernel of its own rather than a net_stream_kernel specialisation.  (One text
 // included twice instead of a device function both call: inlined into a wrapper, the same body compiles to other
@@ -332,6 +333,20 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_slice_bf16_kernel(Ns
 #define NS_BODY_SLICE_BF16
 #include "net_stream_body.inc"
 #undef NS_BODY_SLICE_BF16
+}
+// BF + GRAD + STORE == 2: lnP and d lnP / d z in one launch on the bf16 engine (linna_logprob_set_grad_precision; 16-, 8-
+// and 4-row engines).  The forward half is the bf16 serving step with the signs of the activations kept as bits in LDS,
+// as the fp32 one-launch gradient keeps them; the turnaround (d lnP / d out from the fp32 output map and the diagonal
+// likelihood) is fp32 and leaves its rows in LDS; the dX chain consumes bf16 steps as the bf16 training step's chain does
+// -- the transposed weights rounded after the same folding as the forward ones, delta rounded where the A operand is read,
+// fp32 accumulators, fp32 epilogues gated by the LDS bits -- and the finish (the prior map's derivative, the leapfrog's
+// kick and drift) is the fp32 gradient's.  No SIDE segments.  A kernel of its own for the same reason as the two above.
+template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF>
+__global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_grad_bf16_kernel(NsArgs a) {
+    static_assert(BF && GRAD && STORE == 2 && MOVE == 0, "the bf16 one-launch gradient only");
+#define NS_BODY_GRAD_BF16
+#include "net_stream_body.inc"
+#undef NS_BODY_GRAD_BF16
 }
 
 // ---------------------------------------------------------------------------- host side: the launches
@@ -668,12 +683,12 @@ int launch_net_stream_store(const linna_layer_t* layers, int nl, int in_size, co
 // the caller's workspace: 40 MB written and read back per 4096-chain launch of ChtoModelv2(33,33), in bursts at the run
 // ends of 256 workgroups in step, each read an exposed L2 round trip behind a drained weight ring), the turnaround forms
 // d lnP / d out, the dX chain runs down to the network input gating on those signs, the finish applies the prior map's
-// derivative.  Diagonal covariance.
+// derivative.  Diagonal covariance.  bf: the same on a bf16 stream (NS_GRAD_INPUT_BF16, net_stream_grad_bf16_kernel).
 int launch_net_stream_grad2(const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* Z, int ldz, int B,
                             int nin, const int* is_flat, const float* a1, const float* a2, const int* lg, const float* xmean,
                             const float* xstd, const float* cscale, const float* cshift, const float* w, float T, float* lnP,
-                            const NsGrad& gr, int rows, hipStream_t s) {
-    const NsProgramRef pref = ns_program(NS_GRAD_INPUT, layers, nl, in_size, nullptr, rows);
+                            const NsGrad& gr, int rows, hipStream_t s, bool bf) {
+    const NsProgramRef pref = ns_program(bf ? NS_GRAD_INPUT_BF16 : NS_GRAD_INPUT, layers, nl, in_size, nullptr, rows);
     const NsProgram& p = *pref;
     if (!p.ok || !p.dxi_ok) { set_error("net_stream: no forward + dX program for this network"); return LINNA_ERR_UNSUPPORTED; }
     if (!w || !lnP || !gr.gscale || !gr.G) { set_error("net_stream: the one-launch gradient needs a diagonal covariance"); return LINNA_ERR_INVALID; }
@@ -688,6 +703,18 @@ int launch_net_stream_grad2(const linna_layer_t* layers, int nl, int in_size, co
     if (!ns_set_gates(a, g, p, rows, &lds_extra)) {
         set_error(g.ok ? "net_stream: the one-launch gradient's sign bits do not fit the LDS" : "net_stream: a gate of the one-launch gradient has no producer");
         return LINNA_ERR_UNSUPPORTED;
+    }
+    if (bf) {
+#ifdef NS_STAMPS
+        set_error("net_stream: the NS_STAMPS build has no bf16 gradient"); return LINNA_ERR_UNSUPPORTED;
+#endif
+        const size_t lds = p.lds_for(rows, true) + lds_extra;
+        const char* const what = "net_stream bf16 gradient launch";
+        if (rows == 4) return ns_launch<net_stream_grad_bf16_kernel<NS_R, 0, true, 2, 4, true>>(a, (B + 3) / 4, lds, s, what);
+        if (rows == 8) return ns_launch<net_stream_grad_bf16_kernel<NS_R, 0, true, 2, 8, true>>(a, (B + 7) / 8, lds, s, what);
+        if (rows == 16) return ns_launch<net_stream_grad_bf16_kernel<NS_R, 0, true, 2, 16, true>>(a, (B + 15) / 16, lds, s, what);
+        set_error("net_stream: %d rows per workgroup", rows);
+        return LINNA_ERR_INVALID;
     }
     return ns_launch_kernel<0, true, 2>(a, B, p, rows, s, 0, lds_extra);
 }

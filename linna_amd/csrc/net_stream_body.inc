@@ -1,5 +1,5 @@
 // The body of the whole-network kernels (net_stream.hip: net_stream_kernel, net_stream_train_bf16_kernel,
-// net_stream_slice_bf16_kernel), included
+// net_stream_slice_bf16_kernel, net_stream_grad_bf16_kernel), included
 // inside each kernel's braces; its template parameters R, MOVE, GRAD, STORE, ROWS, BF and its argument NsArgs a are theirs.
     constexpr int NT = NS_NT, NW = NS_NW;
     constexpr int RG = 32;                         // threads per walker row in prologue / reduce / finish
@@ -9,6 +9,8 @@
     constexpr int NACC = SM ? 4 * RS : NT;
 #ifdef NS_BODY_SLICE_BF16                          // (defined around the include by net_stream_slice_bf16_kernel alone)
     static_assert(BF && !GRAD && STORE == 0 && MOVE == 2, "bf16: the slice evaluation");
+#elif defined(NS_BODY_GRAD_BF16)                   // (... by net_stream_grad_bf16_kernel alone)
+    static_assert(BF && GRAD && STORE == 2 && MOVE == 0, "bf16: lnP and its gradient in one launch");
 #else
     static_assert(!BF || (!GRAD && STORE == 0 && MOVE != 2) || (GRAD && STORE == 3 && MOVE == 0 && ROWS == 4),
                   "bf16: serving, the fused stretch move and the merged training step (4-row engine)");

@@ -469,3 +469,15 @@ def describe_program(model, rows=16, dense_nout=0):
     if n < 0:
         _lib.check(n)
     return n, buf.value.decode()
+
+
+def describe_grad_bf16_program(model, rows=16):
+    """The program of the bf16 one-launch gradient (``Log_prob(precision="bf16", grad_precision="bf16")``) for ``model`` on the
+    engine of ``rows`` rows per workgroup, as text (``linna_program_describe_grad_bf16``: host-side planning, no GPU
+    needed).  0 segments: the network has no such program."""
+    arr = program_layers(model)
+    buf = C.create_string_buffer(8192)
+    n = _lib.load().linna_program_describe_grad_bf16(arr, len(model.ops), model.in_size, int(rows), buf, len(buf))
+    if n < 0:
+        _lib.check(n)
+    return n, buf.value.decode()

@@ -1360,7 +1360,13 @@ class SliceEnsembleSampler(EnsembleSampler):
 # ------------------------------------------------------------------ batched per-walker HMC
 class BatchedHMC(object):
     """``linna/HMCSampler.py:19-68`` for B independent chains: p ~ N(0, m); half kick; ``num_steps``
-    x (drift, gradient, kick); final half kick; Metropolis test on H = p^2/2m - lnP."""
+    x (drift, gradient, kick); final half kick; Metropolis test on H = p^2/2m - lnP.
+
+    ``log_prob`` may be a ``Log_prob(precision="bf16", grad_precision="bf16")``: lnP and its gradient then come from the one
+    bf16 launch (``linna_logprob_set_grad_precision``), in both the fused and the piecewise form.  The leapfrog with any
+    deterministic force that depends on q alone is reversible and volume-preserving, and lnP at the start and at the end
+    of a trajectory both come from the gradient launch: the chain samples the density that launch returns, the rounded
+    force costs acceptance rate only.  A ``precision="bf16"`` object without the second opt-in raises here."""
 
     def __init__(self, log_prob, x0, mass=None, seed=0, fused=True):
         self.fused = fused                      # kick + drift in the gradient launch's finish (False: the separate entries)

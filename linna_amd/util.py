@@ -323,13 +323,25 @@ class Log_prob(object):
     ``SliceEnsembleSampler``'s one-call half step).  Serving only: ``evaluate_with_grad`` raises.  A network or likelihood the
     bf16 engine cannot serve (a dense covariance, a layer wider than 1024, ...) raises ``ValueError`` naming the reason
     when the object is first used.
+
+    ``grad_precision="bf16"`` (a second opt-in, on top of ``precision="bf16"``; default ``"fp32"``) makes
+    ``evaluate_with_grad`` -- and with it ``BatchedHMC`` / ``HMCSampler`` -- run lnP and its gradient in one launch on a bf16
+    weight stream (linna_logprob_set_grad_precision says what is rounded where).  The gradient is approximate, lnP is the
+    bf16 surface ``__call__`` serves: HMC's Metropolis test samples that surface exactly, the rounding of the force costs
+    acceptance rate only.  A network without such a program (an input skip, an exp output map, more than 64 inputs or
+    outputs, ...) raises ``ValueError`` with the reason when the object is first used.
     """
 
     def __init__(self, data_new, invcov_new, model, y_invtransform_data, transform, temperature, loglikelihoodfunc=None,
-                 nograd=False, externalloglike=None, precision="fp32"):
+                 nograd=False, externalloglike=None, precision="fp32", grad_precision="fp32"):
         if precision not in _lib.PRECISION:
             raise ValueError("Log_prob: precision must be 'fp32' or 'bf16', not %r" % (precision,))
+        if grad_precision not in _lib.PRECISION:
+            raise ValueError("Log_prob: grad_precision must be 'fp32' or 'bf16', not %r" % (grad_precision,))
+        if grad_precision == "bf16" and precision != "bf16":
+            raise ValueError("Log_prob: grad_precision='bf16' needs precision='bf16' (one lnP surface per object)")
         self.precision = precision
+        self._grad_precision = grad_precision
         self.data_new = data_new
         self.invcov_new = invcov_new
         self.model = model
@@ -412,6 +424,14 @@ class Log_prob(object):
             if rc == _lib.ERR_UNSUPPORTED:
                 raise ValueError("Log_prob(precision=%r): %s" % (self.precision, msg))
             _lib.check(rc)
+        if self._grad_precision != "fp32":
+            rc = _lib.load().linna_logprob_set_grad_precision(h, _lib.PRECISION[self._grad_precision])
+            if rc != 0:
+                msg = _lib.load().linna_last_error().decode()
+                _lib.load().linna_logprob_destroy(h)
+                if rc in (_lib.ERR_UNSUPPORTED, _lib.ERR_INVALID):
+                    raise ValueError("Log_prob(grad_precision=%r): %s" % (self._grad_precision, msg))
+                _lib.check(rc)
         self._plan = dict(handle=h, keep=k, desc=d, dev=dev, nin=nin, nout=nout, net_sig=net._net_sig)
         self._ws = {}
 
@@ -473,7 +493,7 @@ class Log_prob(object):
     def evaluate_with_grad(self, z, out=None, grad=None):
         """``(lnP[B], d lnP/d z [B, nin])`` -- what ``torch.autograd.grad(lnP, x)`` yields in
         HMCSampler.py:32, batched per walker."""
-        if self.precision != "fp32":
+        if self.precision != "fp32" and self._grad_precision == "fp32":
             raise ValueError("Log_prob.evaluate_with_grad: no gradient in %s (serving only); use precision='fp32'" % self.precision)
         p = self._ensure()
         self._check_rows(z, p)
@@ -486,6 +506,11 @@ class Log_prob(object):
                   _lib.ptr(self._workspace(B, True)), _lib.ptr(out), C.c_void_p(grad.data_ptr()), grad.stride(0),
                   _lib.stream())
         return out, grad
+
+    @property
+    def grad_precision(self):
+        """``"fp32"`` or ``"bf16"``: the form ``evaluate_with_grad`` runs (fixed when the object is created)."""
+        return self._grad_precision
 
     @property
     def device_only(self):

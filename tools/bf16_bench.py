@@ -6,10 +6,14 @@
   emcee128  emcee iterations per second at 128 walkers on ChtoModelv2(33,33) (linna_stretch_run blocks)
   slice128 / slice4096   zeus iterations per second (SliceEnsembleSampler.run) on ChtoModelv2(33,33) at 128 walkers and
             on the MLP at 4096: fp32 one-call, bf16 one-call, bf16 round loop, alternating, mu fixed (slice_rates)
+  grad4096  one gradient launch (Log_prob.evaluate_with_grad) at 4096 rows, the MLP and ChtoModelv2(33,33): the fp32 one-launch
+            gradient against the bf16 one (grad_precision="bf16"), alternating in one process, five runs each
+  hmc       one BatchedHMC.step(5, eps) at 1024 and 4096 chains on both networks, the same way (grad_rates)
 Prints ONE JSON line.  --only-slice / --no-slice: the slice objects alone / left out; --slice-trace: the bf16 one-call
-route at 128 walkers alone (the process to put under a kernel trace).  FLOP/s count 2 x multiply-adds of the network per walker, against the bf16 dense peak (2.5 PF spec);
+route at 128 walkers alone (the process to put under a kernel trace); --grad: grad4096 and hmc alone; --grad-trace: a
+short run of both forms of both (the process to put under a kernel trace).  FLOP/s count 2 x multiply-adds of the network per walker, against the bf16 dense peak (2.5 PF spec);
 bytes = the weight stream each workgroup reads per launch (padded fragment layout) x workgroups.
-usage: python tools/bf16_bench.py [--reps N] [--only-slice | --no-slice | --slice-trace]"""
+usage: python tools/bf16_bench.py [--reps N] [--only-slice | --no-slice | --slice-trace | --grad | --grad-trace]"""
 import json
 import os
 import sys
@@ -119,11 +123,51 @@ def slice_rates(lp32, nw, iters, repeats, only=None):
     return out
 
 
+def _stats(us):
+    us = np.asarray(us)
+    return {"us": round(float(np.median(us)), 2), "us_min": round(float(us.min()), 2), "us_max": round(float(us.max()), 2),
+            "spread_pct": round(100.0 * float(us.max() - us.min()) / float(np.median(us)), 2)}
+
+
+def grad_rates(lps, reps, repeats=5):
+    """grad4096 and hmc: the fp32 object against the bf16 one with the bf16 gradient, alternating in one process, `repeats`
+    timed runs of `reps` calls each; median and spread, and the ratio fp32 / bf16 of the medians."""
+    out = {"grad4096": {}, "hmc": {}, "repeats": repeats}
+    for net, lp32 in lps.items():
+        forms = {"fp32": lp32, "bf16": util.Log_prob(lp32.data_new, lp32.invcov_new, lp32.model, lp32.y_invtransform_data, lp32.transform,
+                                                      lp32.T, lp32.loglikelihoodfunc, nograd=True, precision="bf16", grad_precision="bf16")}
+        z = torch.randn(4096, 33, device="cuda") * 0.5
+        lnp, g = torch.empty(4096, device="cuda"), torch.empty(4096, 33, device="cuda")
+        t = {k: [] for k in forms}
+        for _ in range(repeats):
+            for k, lp in forms.items():
+                t[k].append(timed(lambda: lp.evaluate_with_grad(z, out=lnp, grad=g), reps))
+        r = {k: _stats(v) for k, v in t.items()}
+        r["fp32_over_bf16"] = round(r["fp32"]["us"] / r["bf16"]["us"], 3)
+        out["grad4096"][net] = r
+        for B in (1024, 4096):
+            x0 = (0.2 * np.random.RandomState(B).standard_normal((B, 33))).astype(np.float32)
+            hm = {k: sampler.BatchedHMC(lp, x0, seed=5) for k, lp in forms.items()}
+            t = {k: [] for k in forms}
+            for _ in range(repeats):
+                for k, h in hm.items():
+                    t[k].append(timed(lambda: h.step(5, 1e-3), max(1, reps // 5)))
+            r = {k: dict(_stats(v), acceptance=round(float(hm[k].naccept.float().mean()) / max(1, int(hm[k].step_dev.item())), 4)) for k, v in t.items()}
+            r["fp32_over_bf16"] = round(r["fp32"]["us"] / r["bf16"]["us"], 3)
+            out["hmc"]["%s_%d" % (net, B)] = r
+    return out
+
+
 def main():
     dev = torch.device("cuda", 0)
     res = {"tool": "bf16_bench", "reps": REPS, "bf16_peak_flops": BF16_PEAK}
     lp_mlp, _, _ = bench.build_problem(dev)
     lp_v2 = v2_problem(dev)
+    if "--grad" in sys.argv or "--grad-trace" in sys.argv:
+        trace = "--grad-trace" in sys.argv
+        res.update(grad_rates({"mlp_4x512": lp_mlp, "ChtoModelv2_33_33": lp_v2}, 20 if trace else REPS, 1 if trace else 5))
+        print(json.dumps(res))
+        return
     if "--slice-trace" in sys.argv:                          # the bf16 one-call route at 128 walkers alone (for a kernel trace)
         print(json.dumps({"tool": "bf16_bench", "slice128": slice_rates(lp_v2, 128, 600, 3, only="bf16_one_call")}))
         return
