@@ -253,7 +253,11 @@ int linna_gauss_loglike_dense(linna_ctx_t* ctx, const float* D, int ldd, int B, 
 /* ------------------------------------------------------------------ full serving pipeline
  * One call = Log_prob.__call__ (util.py:990-1021) for B walkers: prior map -> X transform
  * -> network -> Y transform -> *sigma -> log-likelihood/T + ln prior.  The struct holds
- * device pointers to constants (all caller-owned). */
+ * device pointers to constants (all caller-owned).
+ * Non-finite points: a row whose transformed input holds a NaN or an infinity (log10 of a parameter <= 0, a NaN in z)
+ * comes out lnP = -inf on every path -- a rejected point, as util.py:1013-1016 -- and leaves the other rows alone; its
+ * gradient is unspecified.  LINNA_DISABLE_FUSED=1 in the environment when an object is created: no whole-network kernel
+ * for that object (the layer-by-layer launches serve it; bf16 objects return LINNA_ERR_UNSUPPORTED). */
 typedef struct {
     uint32_t struct_size;   /* = sizeof of this struct in the CALLER's header; checked by every entry that takes it (LINNA_ERR_INVALID otherwise) */
     int nin, nout;

@@ -906,6 +906,7 @@ struct linna_logprob {
     StreamCopy packed_g2;                    // forward + dX chain down to the input in one stream (any network: residual blocks, ...)
     bool grad2 = false;
     bool dense_fused = false;                // the streams end in the dense inverse covariance (output map folded in)
+    bool fused_on = true;                    // LINNA_DISABLE_FUSED at creation (fused_switch)
     int dense_tri = 2;                       // NsDense::tri, fixed when the object is created (the stream's size depends on it)
     NsDense dense() const { return NsDense{d.Sfac ? d.Sfac : d.S, d.lds, d.outmap.cscale, d.outmap.cshift, d.Sfac ? 1 : 0, dense_tri}; }
     int precision = LINNA_PRECISION_FP32;    // linna_logprob_set_precision
@@ -936,10 +937,9 @@ static LpLayout lp_layout(const linna_logprob* lp, int B, int with_grad) {
     return L;
 }
 
-static bool fused_enabled() {
-    static const bool on = !(getenv("LINNA_DISABLE_FUSED") && getenv("LINNA_DISABLE_FUSED")[0] == '1');
-    return on;
-}
+// LINNA_DISABLE_FUSED=1: no whole-network kernel.  Read when a log-probability object is created, as the other switches
+// are (a process-wide cached value made the switch dead for every object created after the first evaluation).
+static bool fused_switch() { return !(getenv("LINNA_DISABLE_FUSED") && getenv("LINNA_DISABLE_FUSED")[0] == '1'); }
 static int stream_copy_refresh(StreamCopy& sc, const linna_net* n, int rows, void* stream, const float** out, NsKind kind,
                                const NsDense* dn) {
     const int k = rows < 16 ? 1 : 0;
@@ -986,7 +986,7 @@ static int lp_forward(linna_logprob* lp, const float* Z, int ldz, int B, float* 
     const int ldx = ld4(d.nin), ldd = ld4(d.nout);
     if (lp->bf16()) {
         // bf16 runs the whole-network kernel or nothing: never silently fp32
-        if (keep_activations || !fused_enabled() || !lp->packed_bf.ready() || !d.w || (d.outmap.cexp && (!d.outmap.cpost || !d.outmap.cshift2))) {
+        if (keep_activations || !lp->fused_on || !lp->packed_bf.ready() || !d.w || (d.outmap.cexp && (!d.outmap.cpost || !d.outmap.cshift2))) {
             set_error("logprob: this bf16 log-probability cannot run the whole-network kernel here (LINNA_DISABLE_FUSED, or no diagonal likelihood)");
             return LINNA_ERR_UNSUPPORTED;
         }
@@ -994,7 +994,7 @@ static int lp_forward(linna_logprob* lp, const float* Z, int ldz, int B, float* 
         TRY(lp_refresh_stream(lp, B, stream, &packed, &rows));
         return lp_launch(lp, packed, rows, Z, ldz, B, lnP, nullptr, 0, TH, ldt, nullptr, nullptr, gate, stream);
     }
-    if (!keep_activations && fused_enabled() && lp->packed.ready() && (!d.outmap.cexp || (d.outmap.cpost && d.outmap.cshift2 && !lp->dense_fused))) {
+    if (!keep_activations && lp->fused_on && lp->packed.ready() && (!d.outmap.cexp || (d.outmap.cpost && d.outmap.cshift2 && !lp->dense_fused))) {
         // whole-network kernel (net_stream.hip): prior map -> every layer -> output transform -> diagonal
         // log-likelihood in ONE launch, weights streamed from the fragment-order copy
         const float* packed = nullptr; int rows = 16;
@@ -1028,6 +1028,7 @@ int linna_logprob_create(linna_ctx_t* ctx, linna_net_t* net, const linna_logprob
     if (!(desc->temperature > 0.f)) { set_error("logprob_create: temperature must be > 0"); return LINNA_ERR_INVALID; }
     linna_logprob* lp = new linna_logprob{ctx, net, *desc};
     lp->dense_tri = net_stream_dense_tri(-1);
+    lp->fused_on = fused_switch();
     const NsDense dn = lp->dense();
     const bool want_dense = !desc->w && desc->S && !desc->outmap.cexp &&
                             !(getenv("LINNA_DENSE_FUSED") && getenv("LINNA_DENSE_FUSED")[0] == '0');
@@ -1194,7 +1195,7 @@ static int lp_eval_slice_points(linna_logprob_t* lp, const float* coords, int ld
     const linna_logprob_desc_t& d = lp->d;
     if (ndim != d.nin) { set_error("logprob_eval_slice_points: ndim %d, log-probability has %d parameters", ndim, d.nin); return LINNA_ERR_INVALID; }
     // (a bf16 handle runs the bf16 stream or nothing: where this refuses, the caller's fallback evaluates in bf16 too)
-    if (!fused_enabled() || !(lp->bf16() ? lp->packed_bf.ready() : lp->packed.ready()) || (d.outmap.cexp && (!d.w || !d.outmap.cpost || !d.outmap.cshift2)) ||
+    if (!lp->fused_on || !(lp->bf16() ? lp->packed_bf.ready() : lp->packed.ready()) || (d.outmap.cexp && (!d.w || !d.outmap.cpost || !d.outmap.cshift2)) ||
         (!d.w && !lp->dense_fused) || d.nin > 64) {
         set_error("logprob_eval_slice_points: this log-probability does not run the whole-network kernel");
         return LINNA_ERR_UNSUPPORTED;          // the caller falls back to linna_slice_points + linna_logprob_eval_if
@@ -1234,7 +1235,7 @@ int linna_slice_half_step(linna_logprob_t* lp, float* coords, int ldc, int ndim,
     for (int r = 0; r < nshr_rounds; ++r) if (nt_sched[r] < 1) { set_error("slice_half_step: nt_sched[%d] = %d", r, nt_sched[r]); return LINNA_ERR_INVALID; }
     const linna_logprob_desc_t& d = lp->d;
     if (ndim != d.nin) { set_error("slice_half_step: ndim %d, log-probability has %d parameters", ndim, d.nin); return LINNA_ERR_INVALID; }
-    if (!fused_enabled() || !(lp->bf16() ? lp->packed_bf.ready() : lp->packed.ready()) || (d.outmap.cexp && (!d.w || !d.outmap.cpost || !d.outmap.cshift2)) ||
+    if (!lp->fused_on || !(lp->bf16() ? lp->packed_bf.ready() : lp->packed.ready()) || (d.outmap.cexp && (!d.w || !d.outmap.cpost || !d.outmap.cshift2)) ||
         (!d.w && !lp->dense_fused) || d.nin > 64) {
         set_error("slice_half_step: this log-probability does not run the whole-network kernel");
         return LINNA_ERR_UNSUPPORTED;          // the caller falls back to the round-by-round entries
@@ -1295,7 +1296,7 @@ int linna_stretch_half_step(linna_logprob_t* lp, float* coords, int ldc, int ndi
     }
     const linna_logprob_desc_t& d = lp->d;
     if (ndim != d.nin) { set_error("stretch_half_step: ndim %d, log-probability has %d parameters", ndim, d.nin); return LINNA_ERR_INVALID; }
-    if (!fused_enabled() || !(lp->bf16() ? lp->packed_bf.ready() : lp->packed.ready()) ||
+    if (!lp->fused_on || !(lp->bf16() ? lp->packed_bf.ready() : lp->packed.ready()) ||
         (d.outmap.cexp && (!d.w || !d.outmap.cpost || !d.outmap.cshift2)) || (!d.w && !lp->dense_fused) || d.nin > 64) {
         set_error("stretch_half_step: this log-probability does not run the whole-network kernel");
         return LINNA_ERR_UNSUPPORTED;          // the caller falls back to propose / eval / accept
@@ -1316,7 +1317,7 @@ int linna_stretch_run(linna_logprob_t* lp, float* coords, int ldc, int ndim, flo
     }
     const linna_logprob_desc_t& d = lp->d;
     if (ndim != d.nin) { set_error("stretch_run: ndim %d, log-probability has %d parameters", ndim, d.nin); return LINNA_ERR_INVALID; }
-    if (!fused_enabled() || !(lp->bf16() ? lp->packed_bf.ready() : lp->packed.ready()) ||
+    if (!lp->fused_on || !(lp->bf16() ? lp->packed_bf.ready() : lp->packed.ready()) ||
         (d.outmap.cexp && (!d.w || !d.outmap.cpost || !d.outmap.cshift2)) || (!d.w && !lp->dense_fused) || d.nin > 64) {
         set_error("stretch_run: this log-probability does not run the whole-network kernel");
         return LINNA_ERR_UNSUPPORTED;          // the caller loops over linna_stretch_half_step / the three-launch form
@@ -1388,7 +1389,7 @@ static int logprob_grad_impl(linna_logprob_t* lp, const float* Z, int ldz, int B
     const linna_logprob_desc_t& d = lp->d;
     if (lp->bf16()) {
         // the bf16 one-launch program or nothing: never a layered or fp32 form
-        if (!fused_enabled() || !lp->packed_gbf.ready() || !d.w || !d.gscale || d.outmap.cexp) {
+        if (!lp->fused_on || !lp->packed_gbf.ready() || !d.w || !d.gscale || d.outmap.cexp) {
             set_error("logprob_grad: this bf16 log-probability cannot run its one-launch gradient here (LINNA_DISABLE_FUSED, or no bf16 gradient stream)");
             return LINNA_ERR_UNSUPPORTED;
         }
@@ -1406,7 +1407,7 @@ static int logprob_grad_impl(linna_logprob_t* lp, const float* Z, int ldz, int B
     if (!d.gscale || (!d.w && !d.Ssym)) { set_error("logprob_grad: descriptor lacks gscale / Ssym"); return LINNA_ERR_INVALID; }
     NsGrad gr{d.gscale, G, ldg, nullptr, 0, nullptr, nullptr, 0.f, 0.f};
     if (leap) { gr.hm_p = leap->hm_p; gr.hm_ldp = leap->hm_ldp; gr.hm_q = leap->hm_q; gr.hm_mass = leap->hm_mass; gr.hm_ek = leap->hm_ek; gr.hm_ed = leap->hm_ed; }
-    if (fused_enabled() && lp->packed.ready() && lp->grad_fused && d.w) {
+    if (lp->fused_on && lp->packed.ready() && lp->grad_fused && d.w) {
         // lnP and d lnP / d z in ONE launch: forward segments, turnaround, backward segments over W^T (net_stream.hip)
         const float* packed = nullptr; int rows = 16;
         TRY(lp_refresh_stream(lp, B, stream, &packed, &rows));
@@ -1415,7 +1416,7 @@ static int logprob_grad_impl(linna_logprob_t* lp, const float* Z, int ldz, int B
     const LpLayout L = lp_layout(lp, B, 1);
     float* w = static_cast<float*>(ws);
     const int ldx = ld4(d.nin), ldd = ld4(d.nout);
-    if (fused_enabled() && lp->grad2 && lp->packed_g2.ready() && d.w) {
+    if (lp->fused_on && lp->grad2 && lp->packed_g2.ready() && d.w) {
         // ONE launch for any network: forward segments (the signs the gates need kept as bits in LDS), turnaround, dX chain
         // down to the input, prior map's derivative (net_stream.hip, GRAD + STORE == 2) -- six launches otherwise
         const linna_net* n = lp->net;

@@ -552,7 +552,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& a, const int block_all
                 float v = acc[i][j][e];
                 v = two ? (v + b_last) : a.alpha0 * (v + b_first);
                 if (a.R) v += a.R[(size_t)row * a.ldr + col];
-                if (a.relu) v = fmaxf(v, 0.f);
+                if (a.relu) v = isnan(v) ? v : fmaxf(v, 0.f);   // torch.relu keeps a NaN (fmaxf alone returns 0)
                 if (a.mask) v = (a.mask[(size_t)row * a.ldmask + col] > 0.f) ? v : 0.f;
                 if (a.cscale || a.cshift) v = v * cs + ct;
                 if (a.cexp) v = expf(v) * cp + ct2;

@@ -222,7 +222,10 @@ struct NsShaper {                      // the segment list so far: bias block in
     int bias_off = 0, G = 0, zero_off = -1, zero_pad = 0;
 };
 struct NsShapeCtx { const NsBuildOpts& o; const NsDense* dn; int nfwd, f32seg;
-                    bool last_side; };   // the last forward segment may be a SIDE one: nothing follows it in the launch
+                    bool last_side;      // the last forward segment may be a SIDE one: nothing follows it in the launch
+                    int x0_seg; };       // the input-skip segment (-1: none).  Its predecessor is never a SIDE one: the kernel copies the kept
+                                         // input rows behind a segment's input at the end of the step-loop run before it, and a SIDE run in
+                                         // between would leave that segment without them (and overwrite the columns with zeros)
 static bool ns_shape(NsShaper& sh, const Lin& L, const NsShapeCtx& c) {
     const int i = (int)sh.seg.size();
     // k per step: 32 in a bf16 stream, but for the training step's loss segment (the dense inverse covariance behind the
@@ -249,7 +252,7 @@ static bool ns_shape(NsShaper& sh, const Lin& L, const NsShapeCtx& c) {
     const bool side_bwd = c.o.bwd == NS_BWD_INPUT && i > c.nfwd && !L.Wa && L.Wb && L.transB && L.Kapad == 0 && !L.relu;
     const bool side_pays = split || (side_fwd && !L.force_wide && side_steps < ksteps * passes);   // (a short WIDE run of <= 64 columns)
     const bool side = c.o.side && side_pays && ncg == 1 && side_steps <= 2 && i > 0 && (side_fwd || side_bwd) && sh.seg.back().type != NS_SIDE &&
-                      !L.rscale && !L.rshift && !L.b2 && !L.x0_col;
+                      !L.rscale && !L.rshift && !L.b2 && !L.x0_col && i + 1 != c.x0_seg;
     int in_ext;
     if (side) {
         s.type = NS_SIDE; s.steps = side_steps; s.passes = 1; s.kslice = 16 * kc * s.steps;
@@ -380,7 +383,9 @@ static NsProgram ns_build_one(const linna_layer_t* layers, int nl, int in_size, 
     p.x0_keep = lo.x0_keep; p.dense = lo.dense; p.u_col = lo.u_col; p.u_same = lo.u_same;
     if (!lo.ok) return p;
     const int nfwd = lo.nfwd;
-    const NsShapeCtx ctx{o, o.dense ? dn : nullptr, nfwd, lo.f32seg, o.forward && !lo.mlp_grad && o.bwd != NS_BWD_INPUT && o.bwd != NS_BWD_TRAIN};
+    int x0_seg = -1;
+    for (int i = 0; i < (int)lo.lins.size(); ++i) if (lo.lins[i].x0_col) x0_seg = i;
+    const NsShapeCtx ctx{o, o.dense ? dn : nullptr, nfwd, lo.f32seg, o.forward && !lo.mlp_grad && o.bwd != NS_BWD_INPUT && o.bwd != NS_BWD_TRAIN, x0_seg};
     NsShaper sh;
     for (const Lin& L : lo.lins) if (!ns_shape(sh, L, ctx)) return p;
     const int slots = lo.mlp_grad ? ns_append_mlp_grad(sh, lo.lins, ctx) : -1;

@@ -32,6 +32,13 @@
     // gate loads are not what its run ends wait for, the ballots and bit writes of every forward epilogue are extra) -- off.
     constexpr bool LB = G2;
     constexpr bool LATE_REFILL = true;             // see `step`
+    // Non-finite inputs.  Serving and the one-launch gradient poison the row's prior term where x is formed (`zz` in the
+    // prologue): lnP = NaN -> -inf whatever the layers make of the row, at no instruction in the layer loop -- their ReLU
+    // stays fmaxf, which returns 0 on a NaN.  The forward with stored activations (STORE == 1) has no prior term: its rows
+    // arrive transformed (a non-finite x is a NaN there, prior_map_fwd_kernel) and its ReLU keeps the NaN, as torch.relu
+    // does, down to the output rows the likelihood launch reads.
+    constexpr bool RNAN = STORE == 1;
+    auto relu_f = [](float v) { if constexpr (RNAN) return isnan(v) ? v : fmaxf(v, 0.f); else return fmaxf(v, 0.f); };
     static_assert(ROWS == 16 || ROWS == 8 || ROWS == 4, "rows per workgroup");
     static_assert(R % 2 == 0, "the A double buffer alternates with the ring slot parity");
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -287,6 +294,7 @@
         theta[i] = th;
         const float t = (a.lg && zlg[i]) ? lt : th;
         float x = in ? (t - zxm[i]) / zxs[i] : 0.f;
+        zz += 0.f * x;                              // a non-finite input (log10 of theta <= 0) poisons the row's prior term: lnP = -inf
         if constexpr ((STORE == 1 || STORE == 2) && !GRAD) x = z;   // rows arrive transformed
         if constexpr (STORE == 3) {                 // X_transform of a gathered row (util.py:483-497), as linna_gather_xform
             float lz = log10f(z);
@@ -344,6 +352,7 @@
             const float th = ns_prior_theta(z, a.is_flat[c], a.a1[c], a.a2[c]);
             const float t = (a.lg && a.lg[c]) ? log10f(th) : th;
             x = (t - a.xmean[c]) / a.xstd[c];
+            zz += 0.f * x;
             if constexpr ((STORE == 1 || STORE == 2) && !GRAD) x = z;
             if constexpr (STORE == 3) {
                 const float zz3 = a.Z[(size_t)zsrc * a.ldz + c];
@@ -694,7 +703,7 @@
                     for (int e = 0; e < 4; ++e) {  // 16x16x4 C/D layout: col = lane&15, row = 4*(lane>>4) + e; 4x4x1: col = lane, row = 4 t + e
                         float v = fin[t][e];
                         if constexpr (GRAD) v = ((mbits >> (4 * t + e)) & 1u) ? v : 0.f;
-                        v = s_relu ? fmaxf(v, 0.f) : v;
+                        v = s_relu ? relu_f(v) : v;
                         if constexpr (LB) {
                             if (s_mbit >= 0 && !((gw[SM ? t : 0][e] >> (SM ? lane : 16 * t + li)) & 1ull)) v = 0.f;
                         } else if constexpr (DXE) {
@@ -860,7 +869,7 @@
                             v += x0; v += x1;
                         }
                         v += lbias[s_bias + c];
-                        if (s_relu) v = fmaxf(v, 0.f);
+                        if (s_relu) v = relu_f(v);
                         if constexpr (LB) {
                             if (s_mbit >= 0 && !(c < ((s_gn + 63) & ~63) && ((lbits[sr * nbw + ((s_mbit + c) >> 5)] >> (c & 31)) & 1u))) v = 0.f;
                         } else if constexpr (DXE) {
@@ -1204,7 +1213,7 @@
         auto column = [&](int c, float cs, float ct, float ww) {
             float d = F[c] * cs + ct;
             if (a.cpost) d = expf(d) * a.cpost[c] + a.cshift2[c];
-            if (a.D && rok) a.D[(size_t)(row0 + pr) * a.ldd + c] = d;
+            if (a.D && rok) a.D[(size_t)(row0 + pr) * a.ldd + c] = isnan(zz) ? zz : d;   // (a poisoned row stays one for a later likelihood launch)
             chi += (d * ww) * d;
         };
         if (a.dense) {
@@ -1214,7 +1223,7 @@
             const bool fac = a.dense == 2;      // the segment multiplied by L (S = L L^T): chi2 = |d L|^2, a sum of squares
             for (int c = pc0; c < nout; c += RG) {
                 const float d = Dv[c];
-                if (a.D && rok) a.D[(size_t)(row0 + pr) * a.ldd + c] = d;
+                if (a.D && rok) a.D[(size_t)(row0 + pr) * a.ldd + c] = isnan(zz) ? zz : d;
                 const float u = U[c];
                 chi += (fac ? u : d) * u;
             }

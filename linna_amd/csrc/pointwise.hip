@@ -36,7 +36,8 @@ __global__ void prior_map_fwd_kernel(const float* __restrict__ Z, int ldz, int B
     const float th = prior_theta(z, is_flat[col], a1[col], a2[col]);
     if (TH) TH[(size_t)row * ldt + col] = th;
     const float t = (lg && lg[col]) ? log10f(th) : th;
-    X[idx] = (t - xmean[col]) / xstd[col];
+    const float x = (t - xmean[col]) / xstd[col];
+    X[idx] = isfinite(x) ? x : __builtin_nanf("");   // log10 of theta <= 0: a NaN reaches every output of the row (lnP = -inf)
 }
 
 __global__ void prior_map_bwd_kernel(const float* __restrict__ Z, int ldz, int B, int nin,
@@ -512,7 +513,8 @@ __global__ void hmc_accept_kernel(int B, int ndim, const float* __restrict__ mas
     const float ln = lnp_new[b];
     const float H1 = 0.5f * ke - ln;
     const U4 r = walker_bits(seed, (uint32_t)b, (uint32_t)step_dev[0], 2u, 0u);
-    const float ratio = expf(fminf(H0[b] - H1, 0.f));
+    const float dH = H0[b] - H1;
+    const float ratio = expf(dH > 0.f ? 0.f : dH);   // a NaN energy stays NaN and rejects (np.minimum; fminf would return 0)
     const float u = U ? U[b] : u01(r.x);
     if (isfinite(ln) && u < ratio) {
         for (int d = lane; d < ndim; d += 64) {

@@ -118,6 +118,25 @@ def test_serving_programs_are_planned_on_the_host_without_a_gpu():
     assert nm == 10 and "SIDE" not in tm and " grad 1" in tm.splitlines()[0]                       # forward + backward half
 
 
+@pytest.mark.parametrize("nin,nout", [(5, 3), (26, 40), (33, 33)])
+def test_no_side_segment_in_front_of_the_input_skip(nin, nout):
+    """``ChtoModelv2_linear``: the kept input rows are copied behind the input of the last layer's segment at the end of the
+    step-loop run before it.  A SIDE segment runs between two such runs, so one directly in front of the input-skip segment
+    would leave it without its second K part (the 16-row engine lost the 1e-3 linearlayer(x) branch that way: (5, 3) has a
+    48 -> 3 layer there, which pays as a SIDE segment).  The planner keeps that segment in the weight stream; the SIDE
+    segments of the residual blocks stay."""
+    import torch  # noqa: F401
+    from linna_amd import nn
+    m = nn.ChtoModelv2_linear(nin, nout, None)
+    n16, t16 = nn.describe_program(m, 16)
+    n4, t4 = nn.describe_program(m, 4)
+    kinds16 = [ln.split()[0] for ln in t16.splitlines()[1:1 + n16]]
+    kinds4 = [ln.split()[0] for ln in t4.splitlines()[1:1 + n4]]
+    assert n16 == n4 == 10 and "SIDE" not in kinds4
+    assert kinds16[-1] != "SIDE" and kinds16[-2] != "SIDE", t16          # [h ; x0] -> out, and the segment in front of it
+    assert kinds16[1] == kinds16[3] == kinds16[5] == "SIDE", t16
+
+
 def test_dense_factor_planning_without_a_gpu():
     """``linna_program_describe(dense_nout < -1)``: the dense log-likelihood segment in its factored form under the three
     ``linna_dense_tri`` modes -- ChtoModelv2(40,1000) on the 16-row engine: 416 steps with the full factor, 384 with the

@@ -119,9 +119,10 @@ class Replay(object):
         self.before = (xg.copy(), lg.copy(), step, mu)
 
 
-def _run(name, T, nw, seed, iters, x_scale, prepare, **kw):
+def _run(name, T, nw, seed, iters, x_scale, prepare, prob=None, **kw):
+    """``prob``: a problem of its own in place of ``cases.serving_problem(name)`` (tests/test_gpu_nonfinite.py)."""
     from linna_amd import sampler
-    lp, pred, yinv, prob = build_logprob(name, T)
+    lp, pred, yinv, prob = build_logprob(name, T, prob=prob)
     nd = prob["nin"]
     x0 = (x_scale * np.random.RandomState(nw + 7).standard_normal((nw, nd))).astype(np.float32)
     ens = sampler.SliceEnsembleSampler(nw, nd, lp, seed=seed, **kw)
