@@ -48,6 +48,27 @@ static inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); 
         set_error("%s: " #T "::struct_size is %u, this library's sizeof is %zu -- set it to sizeof(" #T ") of the header you built against; " \
                   "a mismatch means that header is not this library's (LINNA_ABI_VERSION %d)", who, (unsigned)(ptr)->struct_size, sizeof(T), LINNA_ABI_VERSION); \
         return LINNA_ERR_INVALID; } } while (0)
+// every element of a caller's layer array (the first entry's size is the array's stride: it is checked before walking on)
+static int check_layers(const linna_layer_t* layers, int n, const char* who) {
+    for (int i = 0; i < n; ++i) CHECK_STRUCT(layers + i, linna_layer_t, who);
+    return LINNA_OK;
+}
+static int check_precision(int precision, const char* who) {
+    if (precision == LINNA_PRECISION_FP32 || precision == LINNA_PRECISION_BF16) return LINNA_OK;
+    set_error("%s: unknown precision %d (LINNA_PRECISION_FP32 0, LINNA_PRECISION_BF16 1)", who, precision);
+    return LINNA_ERR_INVALID;
+}
+static bool capturing(void* stream) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(S(stream), &cap);
+    return cap != hipStreamCaptureStatusNone;
+}
+// An environment switch reads `c` ('0' off, '1' on) NOW.  Every caller asks at the moment its object is created or first
+// used; a process-wide cached value once made LINNA_DISABLE_FUSED dead for every object created after the first evaluation.
+static bool env_is(const char* name, char c) {
+    const char* e = getenv(name);
+    return e && e[0] == c;
+}
 static GemmArgs gemm_zero() {
     GemmArgs a;
     std::memset(&a, 0, sizeof a);
@@ -81,8 +102,16 @@ struct linna_ctx {
 void** linna_ctx_comm_slot(linna_ctx_t* ctx) { return &ctx->comm; }
 int linna_ctx_device(const linna_ctx_t* ctx) { return ctx->device; }
 struct linna_graph { hipGraph_t graph; hipGraphExec_t exec; };
-// zeroed, self-resetting arrival counters of the context (allocated by linna_ctx_create)
-static unsigned* ctx_counters(linna_ctx* ctx, hipStream_t) { return ctx ? ctx->counters : nullptr; }
+// the auxiliary stream and the 2 * nl + 4 fork/join events a backward over nl ops uses
+static int ctx_ensure_aux(linna_ctx* ctx, int nl) {
+    if (!ctx->aux) TRY(check_hip(hipStreamCreateWithFlags(&ctx->aux, hipStreamNonBlocking), "hipStreamCreate"));
+    while ((int)ctx->events.size() < 2 * nl + 4) {
+        hipEvent_t e;
+        TRY(check_hip(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate"));
+        ctx->events.push_back(e);
+    }
+    return LINNA_OK;
+}
 
 // The whole-network kernel (net_stream.hip) reads the weights from a copy in MFMA fragment order.  Its 16-row
 // engine and its small-batch engines (8 / 4 rows per workgroup) read different orders, so there are two copies,
@@ -103,6 +132,14 @@ struct StreamCopy {
     }
 };
 
+// What a training step of B rows trains through (net_train_mode): the weight streams an update has to write
+enum TrainMode {
+    TRAIN_NONE,          // no pair of whole-network streams (the step, where it runs, re-lays what it reads)
+    TRAIN_FWD_DX,        // packed_loss (forward + loss) and packed_dx[0] (dX chain): two launches
+    TRAIN_MERGED,        // packed_tb: forward + loss + dX chain in one launch (4-row engine)
+    TRAIN_MERGED_BF16,   // packed_tbf: the same in bf16 (linna_net_set_train_precision)
+};
+
 struct linna_net {
     linna_ctx* ctx;
 
@@ -114,7 +151,7 @@ struct linna_net {
     StreamCopy packed_dx[2];                 // ... for the one-launch dX chain of the backward ([1]: down to the network input)
     StreamCopy packed_tb;                    // ... for forward + loss + dX chain in ONE launch (linna_net_train_step on the small-batch engines)
     int stream_tb = -1;                      // -1 unknown, 0 no (not eligible / LINNA_BWD_STREAM=0), 1 yes
-    int as_merged = -1;                      // which streams as_args describes: 1 = packed_tb, 0 = packed_loss + packed_dx[0], 2 = packed_tbf
+    TrainMode as_mode = TRAIN_NONE;          // which streams as_args describes (TRAIN_NONE: none yet)
     int train_prec = LINNA_PRECISION_FP32;   // linna_net_set_train_precision: the form of the training step's network launch
     StreamCopy packed_tbf;                   // LINNA_PRECISION_BF16: the bf16 training stream (NS_TRAIN_STEP_BF16; [1] only, the 4-row engine)
     AsArgs as_args;                          // linna_net_adamw_step's descriptor table, valid for (as_params, as_n, as_k)
@@ -126,11 +163,29 @@ struct linna_net {
     int in_size, out_size;
     bool has_inskip;
     linna_layer_t inskip;
-    int max_w, max_c;
 };
+// the op list the programs of `kind` are planned from (ns_kind_full_layers), for the launchers
+static NsNet net_layers(const linna_net* n, NsKind kind) {
+    const std::vector<linna_layer_t>& L = ns_kind_full_layers(kind) ? n->Lfull : n->L;
+    return NsNet{L.data(), (int)L.size(), n->in_size};
+}
 
+// The copy of `sc` that the engine of `rows` rows per workgroup reads, re-laid when the weights moved since it was made.
 static int stream_copy_refresh(StreamCopy& sc, const linna_net* n, int rows, void* stream, const float** out, NsKind kind,
-                               const NsDense* dn = nullptr);
+                               const NsDense* dn = nullptr) {
+    const int k = rows < 16 ? 1 : 0;
+    const unsigned long long epoch = g_weights_epoch.load();
+    const bool cap = capturing(stream);
+    if (cap || sc.epoch[k] != epoch) {
+        // a captured launch carries its own re-layout, so that every replay sees the weights of that
+        // moment; the copy is not valid for direct launches until they redo it (epoch 0)
+        const NsNet net = net_layers(n, kind);
+        TRY(launch_net_stream_pack(kind, net.layers, net.nl, net.in_size, sc.buf[k], rows, dn, S(stream)));
+        sc.epoch[k] = cap ? 0 : epoch;
+    }
+    *out = sc.buf[k];
+    return LINNA_OK;
+}
 
 // forward workspace: per op, the hidden h of a residual block, then the op's output (the last op's is the caller's)
 static size_t fwd_floats(const linna_net* n, int B) {
@@ -314,10 +369,9 @@ int linna_linear_bwd(linna_ctx_t*, const float* dY, int lddy, const float* X, in
 // ------------------------------------------------------------------ network
 int linna_net_create(linna_ctx_t* ctx, const linna_layer_t* layers, int nlayers, int in_size, linna_net_t** out) try {
     if (!layers || nlayers < 1 || !out) { set_error("net_create: bad arguments"); return LINNA_ERR_INVALID; }
-    CHECK_STRUCT(layers, linna_layer_t, "net_create");          // (the first entry's size is the array's stride: check it before walking)
-    for (int i = 1; i < nlayers; ++i) CHECK_STRUCT(layers + i, linna_layer_t, "net_create");
+    TRY(check_layers(layers, nlayers, "net_create"));
     linna_net* n = new linna_net();
-    n->ctx = ctx; n->in_size = in_size; n->has_inskip = false; n->max_w = in_size; n->max_c = 4;
+    n->ctx = ctx; n->in_size = in_size; n->has_inskip = false;
     int width = in_size;
     for (int i = 0; i < nlayers; ++i) {
         const linna_layer_t& l = layers[i];
@@ -332,10 +386,8 @@ int linna_net_create(linna_ctx_t* ctx, const linna_layer_t* layers, int nlayers,
         if (l.K != width) { set_error("net_create: op %d expects K=%d, got %d", i, width, l.K); delete n; return LINNA_ERR_INVALID; }
         if (l.op == LINNA_OP_RESBLOCK) {
             if (!l.Ws && l.K != l.N) { set_error("net_create: op %d identity skip with K != N", i); delete n; return LINNA_ERR_INVALID; }
-            if (l.C > n->max_c) n->max_c = l.C;
         } else if (l.op != LINNA_OP_LINEAR) { set_error("net_create: unknown op %d", l.op); delete n; return LINNA_ERR_INVALID; }
         width = l.N;
-        if (width > n->max_w) n->max_w = width;
         n->L.push_back(l);
     }
     const linna_layer_t& last = n->L.back();
@@ -365,8 +417,7 @@ int linna_net_destroy(linna_net_t* net) try {
 static void net_ensure_fwd(linna_net* n, bool may_alloc) {
     const int nl = (int)n->L.size();
     if (n->stream_fwd < 0) {
-        const char* e = getenv("LINNA_FWD_STREAM");
-        n->stream_fwd = !n->has_inskip && !(e && e[0] == '0') && net_stream_plan(NS_STORE, n->L.data(), nl, n->in_size).ok ? 1 : 0;
+        n->stream_fwd = !n->has_inskip && !env_is("LINNA_FWD_STREAM", '0') && net_stream_plan(NS_STORE, n->L.data(), nl, n->in_size).ok ? 1 : 0;
     }
     if (n->stream_fwd == 1 && !n->packed.ready() && may_alloc) {
         if (n->packed.alloc(net_stream_plan(NS_STORE, n->L.data(), nl, n->in_size).packed_floats) != LINNA_OK) n->stream_fwd = 0;
@@ -376,8 +427,7 @@ static void net_ensure_dx(linna_net* n, int wi, bool may_alloc) {
     const int nl = (int)n->L.size();
     const NsKind kind = wi ? NS_DX_INPUT : NS_DX;
     if (n->stream_bwd[wi] < 0) {
-        const char* e = getenv("LINNA_BWD_STREAM");
-        n->stream_bwd[wi] = !n->has_inskip && (nl >= 2 || wi) && !(e && e[0] == '0') &&
+        n->stream_bwd[wi] = !n->has_inskip && (nl >= 2 || wi) && !env_is("LINNA_BWD_STREAM", '0') &&
                             net_stream_plan(kind, n->L.data(), nl, n->in_size).ok ? 1 : 0;
     }
     StreamCopy& sc = n->packed_dx[wi];
@@ -389,15 +439,7 @@ int linna_net_prepare(linna_net_t* n, int backward, int input_grad) try {
     if (!n) { set_error("net_prepare: null network"); return LINNA_ERR_INVALID; }
     net_ensure_fwd(n, true);
     if (backward) net_ensure_dx(n, input_grad ? 1 : 0, true);
-    if (n->ctx && backward) {                                // the auxiliary stream and its events, for the same reason
-        linna_ctx* ctx = n->ctx;
-        if (!ctx->aux) TRY(check_hip(hipStreamCreateWithFlags(&ctx->aux, hipStreamNonBlocking), "hipStreamCreate"));
-        while ((int)ctx->events.size() < 2 * (int)n->L.size() + 4) {
-            hipEvent_t e;
-            TRY(check_hip(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate"));
-            ctx->events.push_back(e);
-        }
-    }
+    if (n->ctx && backward) TRY(ctx_ensure_aux(n->ctx, (int)n->L.size()));      // for the same reason
     return LINNA_OK;
 } LINNA_CATCH_INT
 
@@ -425,14 +467,12 @@ int linna_net_forward(linna_net_t* n, const float* X, int ldx, int B, void* ws, 
     if ((!om || !om->cexp) && !n->has_inskip) {
         // ONE launch (net_stream.hip, STORE): at batch 500 the ten layer GEMMs are 10-30 us of latency each.  The
         // fragment-order weight copy is re-laid whenever the weights moved (every optimiser step: ~10 us).
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        (void)hipStreamIsCapturing(S(stream), &cap);
-        net_ensure_fwd(n, cap == hipStreamCaptureStatusNone);
+        net_ensure_fwd(n, !capturing(stream));
         if (n->stream_fwd == 1 && n->packed.ready()) {
             const int rows = net_stream_rows(B);
             const float* packed = nullptr;
             TRY(stream_copy_refresh(n->packed, n, rows, stream, &packed, NS_STORE));
-            return launch_net_stream_store(n->L.data(), nl, n->in_size, packed, X, ldx, B, ops.data(), om ? om->cscale : nullptr,
+            return launch_net_stream_store(net_layers(n, NS_STORE), packed, X, ldx, B, ops.data(), om ? om->cscale : nullptr,
                                            om ? om->cshift : nullptr, rows, S(stream));
         }
     }
@@ -469,6 +509,7 @@ int linna_net_forward(linna_net_t* n, const float* X, int ldx, int B, void* ws, 
     return LINNA_OK;
 } LINNA_CATCH_INT
 
+static bool net_loss_stale(const linna_net* n, const NsDense& dn) { return n->stream_loss < 0 || n->loss_dn.S != dn.S || n->loss_dn.lds != dn.lds; }
 static void net_ensure_loss(linna_net* n, const NsDense& dn) {
     const int nl = (int)n->L.size();
     const NsPlan loss = net_stream_plan(NS_TRAIN_FWD, n->L.data(), nl, n->in_size, &dn);
@@ -477,29 +518,62 @@ static void net_ensure_loss(linna_net* n, const NsDense& dn) {
     n->stream_loss = 0; n->loss_dn = dn;
     if (ok && n->packed_loss.alloc(loss.packed_floats) == LINNA_OK) n->stream_loss = 1;
     // the same loss behind the one-launch training step (forward + loss + dX chain in one weight stream)
-    const char* b = getenv("LINNA_BWD_STREAM");
-    const NsPlan merged = ok && n->stream_loss == 1 && !(b && b[0] == '0') && nl >= 2 ? net_stream_plan(NS_TRAIN_STEP, n->L.data(), nl, n->in_size, &dn)
-                                                                                   : NsPlan{false, 0, false, nullptr};
+    const NsPlan merged = ok && n->stream_loss == 1 && !env_is("LINNA_BWD_STREAM", '0') && nl >= 2 ? net_stream_plan(NS_TRAIN_STEP, n->L.data(), nl, n->in_size, &dn)
+                                                                                            : NsPlan{false, 0, false, nullptr};
     n->packed_tb.release();
     n->packed_tbf.epoch[0] = n->packed_tbf.epoch[1] = 0;     // (the bf16 stream holds the loss's inverse covariance too)
-    n->stream_tb = 0; n->as_merged = -1; n->as_state = -1;
+    n->stream_tb = 0; n->as_mode = TRAIN_NONE; n->as_state = -1;
     if (merged.ok && n->packed_tb.alloc(merged.packed_floats) == LINNA_OK) n->stream_tb = 1;
 }
-// The one-launch training step serves this batch size (the 4-row engine only) -- decided the same way by every entry
-// that touches the training streams of a step (train_step, train_step_update, adamw_step)
-static bool net_tb_usable(const linna_net* n, int B) {
-    return n->stream_tb == 1 && n->packed_tb.ready() && net_stream_rows(B) == 4;     // (batches of up to 1024 rows)
+// The streams must end in the loss `d`: (re)built when it is not the one they were built for -- outside a stream capture only
+static int net_loss_current(linna_net* n, const linna_loss_desc_t* d, void* stream, const char* who) {
+    const NsDense dn{d->Cinv, d->ldc, nullptr, nullptr};
+    if (!net_loss_stale(n, dn)) return LINNA_OK;
+    if (capturing(stream)) {
+        set_error("%s: first use inside a stream capture (call linna_net_prepare_loss before)", who); return LINNA_ERR_UNSUPPORTED;
+    }
+    net_ensure_loss(n, dn);
+    return LINNA_OK;
 }
 // A bf16 net (linna_net_set_train_precision): the training entries run the bf16 step or return LINNA_ERR_UNSUPPORTED with the
 // reason -- never the fp32 one
 static bool net_bf16(const linna_net* n) { return n->train_prec == LINNA_PRECISION_BF16; }
-static int net_tbf_check(const linna_net* n, int B, const char* who) {
+// THE decision of what a step of B rows trains through, for every entry that touches the training streams (train_launches,
+// train_step, train_step_update, adamw_step).  The merged forms serve the 4-row engine only (batches of up to 1024 rows).
+static TrainMode net_train_mode(const linna_net* n, int B) {
+    const bool four = net_stream_rows(B) == 4;
+    if (net_bf16(n)) return n->packed_tbf.ready() && four && n->loss_dn.S ? TRAIN_MERGED_BF16 : TRAIN_NONE;
+    if (n->stream_loss != 1) return TRAIN_NONE;
+    if (n->stream_tb == 1 && n->packed_tb.ready() && four) return TRAIN_MERGED;
+    return n->stream_bwd[0] == 1 ? TRAIN_FWD_DX : TRAIN_NONE;
+}
+// why a bf16 net has no mode for this batch, in the entry's name (an fp32 net, or a bf16 one with its mode: fine)
+static int net_bf16_mode_check(const linna_net* n, int B, const char* who) {
+    if (!net_bf16(n) || net_train_mode(n, B) == TRAIN_MERGED_BF16) return LINNA_OK;
     if (!n->packed_tbf.ready()) { set_error("%s: bf16 training stream not allocated", who); return LINNA_ERR_UNSUPPORTED; }
     if (net_stream_rows(B) != 4) {
         set_error("%s: the bf16 training step runs on the 4-row engine only; a batch of %d rows needs the %d-row engine", who, B, net_stream_rows(B));
         return LINNA_ERR_UNSUPPORTED;
     }
-    return LINNA_OK;
+    set_error("%s: bf16 training stream: no loss seen yet (linna_net_prepare_loss)", who);
+    return LINNA_ERR_UNSUPPORTED;
+}
+// The streams of a mode: `fwd` of program `kind` (forward + loss, with the dX chain when merged), `dx` the dX chain's own or null
+struct TrainStreams { StreamCopy* fwd; NsKind kind; StreamCopy* dx; };
+static TrainStreams net_train_streams(linna_net* n, TrainMode mode) {
+    if (mode == TRAIN_MERGED_BF16) return TrainStreams{&n->packed_tbf, NS_TRAIN_STEP_BF16, nullptr};
+    if (mode == TRAIN_MERGED) return TrainStreams{&n->packed_tb, NS_TRAIN_STEP, nullptr};
+    return TrainStreams{&n->packed_loss, NS_TRAIN_FWD, &n->packed_dx[0]};
+}
+// An update has just written the mode's streams for the engine of B rows: they hold the new weights.  (A captured update
+// stamps nothing: every replay's launches carry their own re-layout.)
+static void net_stamp_updated(linna_net* n, TrainMode mode, int B, void* stream) {
+    const unsigned long long epoch = g_weights_epoch.fetch_add(1) + 1;
+    if (capturing(stream)) return;
+    const int k = net_stream_rows(B) < 16 ? 1 : 0;
+    const TrainStreams ts = net_train_streams(n, mode);
+    ts.fwd->epoch[k] = epoch;
+    if (ts.dx) ts.dx->epoch[k] = epoch;
 }
 int linna_loss_targets(linna_ctx_t*, const linna_loss_desc_t* d, const float* Y, int ldy, int nrows, float* YN, int ldyn, void* stream) try {
     if (!d || !Y || !YN || nrows < 1) { set_error("loss_targets: bad arguments"); return LINNA_ERR_INVALID; }
@@ -511,185 +585,45 @@ int linna_net_prepare_loss(linna_net_t* n, const linna_loss_desc_t* d) try {
     if (!n || !d) { set_error("net_prepare_loss: null argument"); return LINNA_ERR_INVALID; }
     CHECK_STRUCT(d, linna_loss_desc_t, "net_prepare_loss");
     const NsDense dn{d->Cinv, d->ldc, nullptr, nullptr};
-    if (n->stream_loss < 0 || n->loss_dn.S != dn.S || n->loss_dn.lds != dn.lds) net_ensure_loss(n, dn);
-    return LINNA_OK;
-} LINNA_CATCH_INT
-// Forward pass of a training step AND its loss in ONE launch (net_stream.hip, STORE == 3): the batch rows are gathered
-// from the resident set and X-transformed in the kernel's prologue, every activation the backward needs is stored, the
-// network's normalised-space inverse covariance is the program's last segment and the finish writes the per-row loss and
-// d loss / d pred.  Replaces linna_gather_xform + linna_net_forward + linna_chi2_ratio_loss_fwd_bwd (seven launches for
-// nout > 64) when the network + loss fit the whole-network kernel; LINNA_ERR_UNSUPPORTED otherwise (the caller then
-// runs that sequence).  The batch mean is a second, tiny launch (fixed summation order).
-struct NetUpdate { float* params; float* m; float* v; size_t n; float* hyper; float b1, b2, eps; bool bf; };   // bf: the bf16 training stream's writer
-static int net_backward_impl(linna_net_t* n, const float* X, int ldx, int B, void* fwd_ws, void* bwd_ws, const float* dOUT,
-                             int lddo, float* dX, int lddx, int pg, void* stream, const NsPost* post, const NetUpdate* upd = nullptr,
-                             bool dx_done = false, const GemmPost* gpost = nullptr);
-static int net_forward_loss_impl(linna_net_t* n, const linna_loss_desc_t* d, const float* X, int ldx, const int* ROWS, int B,
-                                 const int* lg, const float* xmean, const float* xstd, float* XB, int ldxb, void* ws, float* PRED,
-                                 int ldp, const float* YN, int ldyn, const float* den, float inv_batch, float* loss_rows,
-                                 float* loss_mean, float* dPRED, int lddp, float* hyper, int* step_dev, float b1, float b2,
-                                 void* stream, bool defer_post);
-int linna_net_forward_loss(linna_net_t* n, const linna_loss_desc_t* d, const float* X, int ldx, const int* ROWS, int B,
-                           const int* lg, const float* xmean, const float* xstd, float* XB, int ldxb, void* ws, float* PRED,
-                           int ldp, const float* YN, int ldyn, const float* den, float inv_batch, float* loss_rows,
-                           float* loss_mean, float* dPRED, int lddp, float* hyper, int* step_dev, float b1, float b2,
-                           void* stream) try {
-    if (!d) { set_error("net_forward_loss: null loss descriptor"); return LINNA_ERR_INVALID; }
-    CHECK_STRUCT(d, linna_loss_desc_t, "net_forward_loss");
-    return net_forward_loss_impl(n, d, X, ldx, ROWS, B, lg, xmean, xstd, XB, ldxb, ws, PRED, ldp, YN, ldyn, den, inv_batch, loss_rows,
-                                 loss_mean, dPRED, lddp, hyper, step_dev, b1, b2, stream, false);
-} LINNA_CATCH_INT
-// One optimiser step up to the gradients in ONE call: linna_net_forward_loss followed by linna_net_backward(param_grads = 1)
-// on the rows it gathered, with the step's two single-thread jobs (batch mean of the loss, AdamW step counter and bias
-// corrections) riding in the backward's dX-chain launch as one extra workgroup instead of a launch of their own between
-// the two whole-network launches.  LINNA_ERR_UNSUPPORTED exactly when linna_net_forward_loss is.
-// Forward + loss + dX chain of a training step in ONE launch (net_stream.hip TRB); the caller has checked net_tb_usable.
-static int net_train_merged_impl(linna_net_t* n, const linna_loss_desc_t* d, const float* X, int ldx, const int* ROWS, int B,
-                                 const int* lg, const float* xmean, const float* xstd, float* XB, int ldxb, void* fwd_ws, float* PRED,
-                                 int ldp, const float* YN, int ldyn, const float* den, float inv_batch, float* loss_rows,
-                                 float* dPRED, int lddp, void* bwd_ws, float* hyper, int* step_dev, float b1, float b2, void* stream) {
-    const bool bf = net_bf16(n);
-    if (!n || !d || !X || !xmean || !xstd || !XB || !PRED || !YN || !den || !loss_rows || !dPRED || !fwd_ws || !bwd_ws || B < 1) {
-        set_error("net_train_step: bad arguments"); return LINNA_ERR_INVALID;
-    }
-    if (d->nout != n->out_size) { set_error("net_train_step: loss for %d outputs, network has %d", d->nout, n->out_size); return LINNA_ERR_INVALID; }
-    const int rows = net_stream_rows(B);
-    const float* packed = nullptr;
-    TRY(stream_copy_refresh(bf ? n->packed_tbf : n->packed_tb, n, rows, stream, &packed, bf ? NS_TRAIN_STEP_BF16 : NS_TRAIN_STEP, &n->loss_dn));
-    const std::vector<NsOpBufs> ops = net_bufs(n, B, XB, ldxb, fwd_ws, PRED, ldp, bwd_ws);   // (no input gradient)
-    const NsTrainLoss L{YN, ldyn, den, inv_batch, loss_rows, dPRED, lddp};
-    const bool prep = hyper && step_dev;
-    const NsPost post{nullptr, 0, 0.f, nullptr, prep ? step_dev : nullptr, prep ? hyper : nullptr, b1, b2};
-    return launch_net_stream_train_bwd(n->L.data(), (int)n->L.size(), n->in_size, packed, X, ldx, ROWS, B, lg, xmean, xstd, XB, ldxb,
-                                       ops.data(), L, n->loss_dn, rows, S(stream), prep ? &post : nullptr, bf);
-}
-// (the loss descriptor's stream state, as net_forward_loss_impl establishes it)
-static int net_train_ensure_loss(linna_net_t* n, const linna_loss_desc_t* d, void* stream) {
-    if (!n || !d) { set_error("net_train_step: null argument"); return LINNA_ERR_INVALID; }
-    const NsDense dn{d->Cinv, d->ldc, nullptr, nullptr};
-    if (n->stream_loss < 0 || n->loss_dn.S != dn.S || n->loss_dn.lds != dn.lds) {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        (void)hipStreamIsCapturing(S(stream), &cap);
-        if (cap != hipStreamCaptureStatusNone) {
-            set_error("net_train_step: first use inside a stream capture (call linna_net_prepare_loss before)"); return LINNA_ERR_UNSUPPORTED;
-        }
-        net_ensure_loss(n, dn);
-    }
-    return LINNA_OK;
-}
-int linna_net_train_step(linna_net_t* n, const linna_loss_desc_t* d, const float* X, int ldx, const int* ROWS, int B,
-                         const int* lg, const float* xmean, const float* xstd, float* XB, int ldxb, void* fwd_ws, float* PRED,
-                         int ldp, const float* YN, int ldyn, const float* den, float inv_batch, float* loss_rows,
-                         float* loss_mean, float* dPRED, int lddp, void* bwd_ws, float* hyper, int* step_dev, float b1, float b2,
-                         void* stream) try {
-    if (!bwd_ws) { set_error("net_train_step: backward workspace required"); return LINNA_ERR_INVALID; }
-    if (!d) { set_error("net_train_step: null loss descriptor"); return LINNA_ERR_INVALID; }
-    CHECK_STRUCT(d, linna_loss_desc_t, "net_train_step");
-    TRY(net_train_ensure_loss(n, d, stream));
-    if (net_bf16(n)) TRY(net_tbf_check(n, B, "net_train_step"));
-    if (net_bf16(n) || net_tb_usable(n, B)) {
-        // two launches: forward + loss + dX chain, then every parameter gradient (the batch mean of the loss riding in it)
-        TRY(net_train_merged_impl(n, d, X, ldx, ROWS, B, lg, xmean, xstd, XB, ldxb, fwd_ws, PRED, ldp, YN, ldyn, den, inv_batch,
-                                  loss_rows, dPRED, lddp, bwd_ws, hyper, step_dev, b1, b2, stream));
-        const GemmPost gp{loss_rows, loss_mean ? B : 0, inv_batch, loss_mean};
-        return net_backward_impl(n, XB, ldxb, B, fwd_ws, bwd_ws, dPRED, lddp, nullptr, 0, 1, stream, nullptr, nullptr, true, &gp);
-    }
-    TRY(net_forward_loss_impl(n, d, X, ldx, ROWS, B, lg, xmean, xstd, XB, ldxb, fwd_ws, PRED, ldp, YN, ldyn, den, inv_batch,
-                              loss_rows, loss_mean, dPRED, lddp, hyper, step_dev, b1, b2, stream, true));
-    const bool prep = hyper && step_dev;
-    const NsPost post{loss_rows, (loss_mean || prep) ? B : 0, inv_batch, loss_mean, prep ? step_dev : nullptr, prep ? hyper : nullptr, b1, b2};
-    return net_backward_impl(n, XB, ldxb, B, fwd_ws, bwd_ws, dPRED, lddp, nullptr, 0, 1, stream, post.n ? &post : nullptr);
-} LINNA_CATCH_INT
-static int net_forward_loss_impl(linna_net_t* n, const linna_loss_desc_t* d, const float* X, int ldx, const int* ROWS, int B,
-                                 const int* lg, const float* xmean, const float* xstd, float* XB, int ldxb, void* ws, float* PRED,
-                                 int ldp, const float* YN, int ldyn, const float* den, float inv_batch, float* loss_rows,
-                                 float* loss_mean, float* dPRED, int lddp, float* hyper, int* step_dev, float b1, float b2,
-                                 void* stream, bool defer_post) {
-    if (!n || !d || !X || !xmean || !xstd || !XB || !PRED || !YN || !den || !loss_rows || !dPRED || B < 1) {
-        set_error("net_forward_loss: bad arguments"); return LINNA_ERR_INVALID;
-    }
-    if (d->nout != n->out_size) { set_error("net_forward_loss: loss for %d outputs, network has %d", d->nout, n->out_size); return LINNA_ERR_INVALID; }
-    const int nl = (int)n->L.size();
-    const NsDense dn{d->Cinv, d->ldc, nullptr, nullptr};
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(S(stream), &cap);
-    if (n->stream_loss < 0 || n->loss_dn.S != dn.S || n->loss_dn.lds != dn.lds) {
-        if (cap != hipStreamCaptureStatusNone) {
-            set_error("net_forward_loss: first use inside a stream capture (call linna_net_prepare_loss before)"); return LINNA_ERR_UNSUPPORTED;
-        }
-        net_ensure_loss(n, dn);
-    }
-    if (n->stream_loss != 1) { set_error("net_forward_loss: this network / loss does not run the whole-network kernel"); return LINNA_ERR_UNSUPPORTED; }
-    if (nl > 1 && !ws) { set_error("net_forward_loss: workspace required"); return LINNA_ERR_INVALID; }
-    const int rows = net_stream_rows(B);
-    const float* packed = nullptr;
-    TRY(stream_copy_refresh(n->packed_loss, n, rows, stream, &packed, NS_TRAIN_FWD, &n->loss_dn));
-    const std::vector<NsOpBufs> ops = net_bufs(n, B, XB, ldxb, ws, PRED, ldp);
-    const NsTrainLoss L{YN, ldyn, den, inv_batch, loss_rows, dPRED, lddp};
-    TRY(launch_net_stream_train(n->L.data(), nl, n->in_size, packed, X, ldx, ROWS, B, lg, xmean, xstd, XB, ldxb, ops.data(), L,
-                                n->loss_dn, rows, S(stream)));
-    if (defer_post) return LINNA_OK;                 // linna_net_train_step: they ride in the backward's dX launch
-    // the batch mean -- and, when the caller hands in its AdamW state, the step counter and bias corrections of the
-    // update that will follow this step's backward (linna_adamw_step(prepared = 1)): two single-thread jobs, one launch
-    if (loss_mean && hyper && step_dev) return launch_sum_scale_prepare(loss_rows, B, inv_batch, loss_mean, step_dev, hyper, b1, b2, S(stream));
-    if (hyper && step_dev) TRY(launch_adamw_prepare(hyper, step_dev, b1, b2, S(stream)));
-    if (loss_mean) TRY(launch_sum_scale(loss_rows, B, inv_batch, loss_mean, S(stream)));
-    return LINNA_OK;
-}
-
-int linna_net_train_launches(const linna_net_t* n, int B) try {
-    if (!n || B < 1) { set_error("net_train_launches: bad arguments"); return LINNA_ERR_INVALID; }
-    if (net_bf16(n)) return n->loss_dn.S && n->packed_tbf.ready() && net_stream_rows(B) == 4 ? 2 : 0;
-    if (n->stream_loss != 1) return 0;
-    if (net_tb_usable(n, B)) return 2;
-    return n->stream_bwd[0] == 1 ? 3 : 0;
-} LINNA_CATCH_INT
-// The bf16 training step (linna_hip.h).  Checks first (no GPU), then the bf16 stream is allocated; its size depends on the
-// network and the loss's width only, so a placeholder inverse covariance plans it before the loss is known.
-int linna_net_set_train_precision(linna_net_t* n, int precision) try {
-    if (!n) { set_error("net_set_train_precision: null handle"); return LINNA_ERR_INVALID; }
-    if (precision != LINNA_PRECISION_FP32 && precision != LINNA_PRECISION_BF16) {
-        set_error("net_set_train_precision: unknown precision %d (LINNA_PRECISION_FP32 0, LINNA_PRECISION_BF16 1)", precision);
-        return LINNA_ERR_INVALID;
-    }
-    if (precision == LINNA_PRECISION_FP32) { n->train_prec = precision; n->as_state = -1; return LINNA_OK; }
-    if (n->has_inskip) { set_error("net_set_train_precision: no bf16 training step for an input-skip network (it has no merged training step)"); return LINNA_ERR_UNSUPPORTED; }
-    const NsDense dn = n->loss_dn.S ? n->loss_dn : NsDense{n->L.back().W, (int)ld4(n->out_size), nullptr, nullptr};
-    const NsPlan plan = net_stream_plan(NS_TRAIN_STEP_BF16, n->L.data(), (int)n->L.size(), n->in_size, &dn);
-    if (!plan.ok) { set_error("net_set_train_precision: no bf16 training step for this network: %s", plan.why ? plan.why : "not eligible"); return LINNA_ERR_UNSUPPORTED; }
-    if (!n->packed_tbf.ready() || n->packed_tbf.floats != plan.packed_floats) {
-        n->packed_tbf.release();
-        if (n->packed_tbf.alloc(plan.packed_floats) != LINNA_OK) { set_error("net_set_train_precision: hipMalloc(bf16 training stream) failed"); return LINNA_ERR_HIP; }
-    }
-    n->train_prec = precision; n->as_state = -1;
-    return LINNA_OK;
-} LINNA_CATCH_INT
-int linna_net_train_precision(const linna_net_t* n, int* out) try {
-    if (!n || !out) { set_error("net_train_precision: null argument"); return LINNA_ERR_INVALID; }
-    *out = n->train_prec;
-    return LINNA_OK;
-} LINNA_CATCH_INT
-int linna_net_stream_state(const linna_net_t* n, int* fwd, int* dx, int* dx_input) try {
-    if (!n) { set_error("net_stream_state: null network"); return LINNA_ERR_INVALID; }
-    if (fwd) *fwd = n->stream_fwd;
-    if (dx) *dx = n->stream_bwd[0];
-    if (dx_input) *dx_input = n->stream_bwd[1];
+    if (net_loss_stale(n, dn)) net_ensure_loss(n, dn);
     return LINNA_OK;
 } LINNA_CATCH_INT
 
-int linna_net_backward(linna_net_t* n, const float* X, int ldx, int B, void* fwd_ws, void* bwd_ws, const float* dOUT,
-                       int lddo, float* dX, int lddx, int pg, void* stream) try {
-    return net_backward_impl(n, X, ldx, B, fwd_ws, bwd_ws, dOUT, lddo, dX, lddx, pg, stream, nullptr);
-} LINNA_CATCH_INT
+// The arguments the three training-step entries share, filled once per call: the batch, the loss and where its results go,
+// the workspaces (bwd_ws: null for linna_net_forward_loss), the network output PRED, the batch mean's slot and the AdamW
+// state whose step constants the step advances (hyper / step_dev null: none).
+struct TrainStep {
+    NsBatch b; NsTrainLoss loss;
+    void* fwd_ws; void* bwd_ws; float* PRED; int ldp;
+    float* loss_mean; float* hyper; int* step_dev; float b1, b2;
+};
+// the step's two single-thread jobs (NsPost): the batch mean of the loss rows, AdamW's step counter and bias corrections
+static NsPost train_riders(const TrainStep& t) {
+    const bool prep = t.hyper && t.step_dev;
+    return NsPost{t.loss.loss_rows, t.b.B, t.loss.inv_batch, t.loss_mean, prep ? t.step_dev : nullptr, prep ? t.hyper : nullptr, t.b1, t.b2};
+}
+// ... as a launch of their own, where no whole-network launch carries them (both jobs: one launch)
+static int launch_riders(const NsPost& p, hipStream_t st) {
+    if (p.out && p.step) return launch_sum_scale_prepare(p.rows, p.n, p.scale, p.out, p.step, p.hyper, p.b1, p.b2, st);
+    if (p.out) return launch_sum_scale(p.rows, p.n, p.scale, p.out, st);
+    if (p.step) return launch_adamw_prepare(p.hyper, p.step, p.b1, p.b2, st);
+    return LINNA_OK;
+}
+
+struct NetUpdate { float* params; float* m; float* v; float* hyper; float b1, b2, eps; bool bf; };   // bf: the bf16 training stream's writer
+// What rides with a backward:
 // `post`: the loss mean / AdamW step constants of this step (linna_net_train_step): they ride in the one-launch dX chain
 // as an extra workgroup, or run as the launch of their own they otherwise are, in front of the GEMM chain
 // `upd`: the optimiser rides in the grouped parameter-gradient launch (linna_net_train_step_update; the caller has checked
-// net_update_supported: every parameter gradient of the step goes into that launch)
+// upd_state: every parameter gradient of the step goes into that launch)
 // `dx_done`: the dX chain already ran (inside the one-launch training step): only the parameter gradients are left;
 // `gpost`: the batch mean of the loss rows rides in the grouped parameter-gradient launch as one extra workgroup
+struct BwdRiders { const NsPost* post = nullptr; const NetUpdate* upd = nullptr; bool dx_done = false; const GemmPost* gpost = nullptr; };
 static int net_backward_impl(linna_net_t* n, const float* X, int ldx, int B, void* fwd_ws, void* bwd_ws, const float* dOUT,
-                             int lddo, float* dX, int lddx, int pg, void* stream, const NsPost* post, const NetUpdate* upd,
-                             bool dx_done, const GemmPost* gpost) {
+                             int lddo, float* dX, int lddx, int pg, void* stream, const BwdRiders& riders) {
+    const NsPost* const post = riders.post;
+    const NetUpdate* const upd = riders.upd;
+    const GemmPost* gpost = riders.gpost;     // (handed to the first launch that can carry it)
     if (!n || !X || !dOUT || !bwd_ws || B < 1) { set_error("net_backward: bad arguments"); return LINNA_ERR_INVALID; }
     const std::vector<NsOpBufs> ops = net_bufs(n, B, X, ldx, fwd_ws, nullptr, 0, bwd_ws, dX, lddx);
     const int nl = (int)n->L.size();
@@ -701,14 +635,7 @@ static int net_backward_impl(linna_net_t* n, const float* X, int ldx, int B, voi
     // goes to the auxiliary stream as it becomes possible.
     linna_ctx* ctx = n->ctx;
     const bool overlap = pg && ctx;
-    if (overlap) {
-        if (!ctx->aux) TRY(check_hip(hipStreamCreateWithFlags(&ctx->aux, hipStreamNonBlocking), "hipStreamCreate"));
-        while ((int)ctx->events.size() < 2 * nl + 4) {
-            hipEvent_t e;
-            TRY(check_hip(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate"));
-            ctx->events.push_back(e);
-        }
-    }
+    if (overlap) TRY(ctx_ensure_aux(ctx, nl));
     int next_event = 0;
     void* aux = overlap ? (void*)ctx->aux : stream;
     GemmGroupArgs grp;                  // the grouped parameter-gradient launch: descriptors by value, filled as we go
@@ -776,26 +703,20 @@ static int net_backward_impl(linna_net_t* n, const float* X, int ldx, int B, voi
     // The dX chain -- one GEMM per op, each waiting for the one before (140 us of 300 at batch 500) -- as ONE launch of
     // the whole-network kernel over the transposed weights (net_stream.hip, STORE == 2), when the network has such a
     // program.  The loop below then only collects the parameter gradients.
-    bool fused_dx = dx_done;
+    bool fused_dx = riders.dx_done;
     const int wi = dX ? 1 : 0;
-    if (!dx_done && !n->has_inskip && (nl >= 2 || dX)) {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        (void)hipStreamIsCapturing(st, &cap);
-        net_ensure_dx(n, wi, cap == hipStreamCaptureStatusNone);
+    if (!riders.dx_done && !n->has_inskip && (nl >= 2 || dX)) {
+        net_ensure_dx(n, wi, !capturing(stream));
         StreamCopy& sc = n->packed_dx[wi];
         if (n->stream_bwd[wi] == 1 && sc.ready()) {
             const int rows = net_stream_rows(B);
             const float* packed = nullptr;
             TRY(stream_copy_refresh(sc, n, rows, stream, &packed, wi ? NS_DX_INPUT : NS_DX));
-            TRY(launch_net_stream_dx(n->L.data(), nl, n->in_size, packed, dOUT, lddo, B, ops.data(), wi, rows, st, post));
+            TRY(launch_net_stream_dx(net_layers(n, NS_DX), packed, dOUT, lddo, B, ops.data(), wi, rows, st, post));
             fused_dx = true;
         }
     }
-    if (post && !fused_dx) {
-        if (post->out && post->step) TRY(launch_sum_scale_prepare(post->rows, post->n, post->scale, post->out, post->step, post->hyper, post->b1, post->b2, st));
-        else if (post->out) TRY(launch_sum_scale(post->rows, post->n, post->scale, post->out, st));
-        else if (post->step) TRY(launch_adamw_prepare(post->hyper, post->step, post->b1, post->b2, st));
-    }
+    if (post && !fused_dx) TRY(launch_riders(*post, st));
     const float* dcur = dOUT; int ldd = lddo;
     for (int i = nl - 1; i >= 0; --i) {
         const linna_layer_t& l = n->L[i];
@@ -859,6 +780,134 @@ static int net_backward_impl(linna_net_t* n, const float* X, int ldx, int B, voi
     }
     return LINNA_OK;
 }
+// the backward of a training step on the rows its forward gathered: every parameter gradient, no input gradient
+static int net_train_backward(linna_net_t* n, const TrainStep& t, void* stream, const BwdRiders& riders) {
+    return net_backward_impl(n, t.b.XB, t.b.ldxb, t.b.B, t.fwd_ws, t.bwd_ws, t.loss.dP, t.loss.lddp, nullptr, 0, 1, stream, riders);
+}
+
+// linna_net_forward_loss (linna_hip.h): the batch rows are gathered from the resident set and X-transformed in the kernel's
+// prologue, every activation the backward needs is stored, the network's normalised-space inverse covariance is the
+// program's last segment and the finish writes the per-row loss and d loss / d pred (net_stream.hip, STORE == 3).  The
+// riders are a second, tiny launch (fixed summation order) -- or, `defer_post`, left to the backward's dX launch.
+static int net_forward_loss_impl(linna_net_t* n, const linna_loss_desc_t* d, const TrainStep& t, void* stream, bool defer_post) {
+    const NsBatch& b = t.b;
+    if (!n || !d || !b.X || !b.xmean || !b.xstd || !b.XB || !t.PRED || !t.loss.YN || !t.loss.den || !t.loss.loss_rows || !t.loss.dP || b.B < 1) {
+        set_error("net_forward_loss: bad arguments"); return LINNA_ERR_INVALID;
+    }
+    if (d->nout != n->out_size) { set_error("net_forward_loss: loss for %d outputs, network has %d", d->nout, n->out_size); return LINNA_ERR_INVALID; }
+    TRY(net_loss_current(n, d, stream, "net_forward_loss"));
+    if (n->stream_loss != 1) { set_error("net_forward_loss: this network / loss does not run the whole-network kernel"); return LINNA_ERR_UNSUPPORTED; }
+    if (n->L.size() > 1 && !t.fwd_ws) { set_error("net_forward_loss: workspace required"); return LINNA_ERR_INVALID; }
+    const int rows = net_stream_rows(b.B);
+    const float* packed = nullptr;
+    TRY(stream_copy_refresh(n->packed_loss, n, rows, stream, &packed, NS_TRAIN_FWD, &n->loss_dn));
+    const std::vector<NsOpBufs> ops = net_bufs(n, b.B, b.XB, b.ldxb, t.fwd_ws, t.PRED, t.ldp);
+    TRY(launch_net_stream_train(net_layers(n, NS_TRAIN_FWD), packed, b, ops.data(), t.loss, n->loss_dn, rows, S(stream)));
+    if (defer_post) return LINNA_OK;
+    // the batch mean -- and, when the caller hands in its AdamW state, the step counter and bias corrections of the
+    // update that will follow this step's backward (linna_adamw_step(prepared = 1))
+    return launch_riders(train_riders(t), S(stream));
+}
+// Forward + loss + dX chain of a training step in ONE launch (net_stream.hip TRB), AdamW's step constants riding in it;
+// the caller has found the mode TRAIN_MERGED or TRAIN_MERGED_BF16.
+static int net_train_merged_impl(linna_net_t* n, const linna_loss_desc_t* d, const TrainStep& t, TrainMode mode, void* stream) {
+    const NsBatch& b = t.b;
+    if (!n || !d || !b.X || !b.xmean || !b.xstd || !b.XB || !t.PRED || !t.loss.YN || !t.loss.den || !t.loss.loss_rows || !t.loss.dP || !t.fwd_ws ||
+        !t.bwd_ws || b.B < 1) {
+        set_error("net_train_step: bad arguments"); return LINNA_ERR_INVALID;
+    }
+    if (d->nout != n->out_size) { set_error("net_train_step: loss for %d outputs, network has %d", d->nout, n->out_size); return LINNA_ERR_INVALID; }
+    const int rows = net_stream_rows(b.B);
+    const TrainStreams ts = net_train_streams(n, mode);
+    const float* packed = nullptr;
+    TRY(stream_copy_refresh(*ts.fwd, n, rows, stream, &packed, ts.kind, &n->loss_dn));
+    const std::vector<NsOpBufs> ops = net_bufs(n, b.B, b.XB, b.ldxb, t.fwd_ws, t.PRED, t.ldp, t.bwd_ws);   // (no input gradient)
+    const NsPost post = train_riders(t);          // (only the step constants ride here: launch_net_stream_train_bwd)
+    return launch_net_stream_train_bwd(net_layers(n, ts.kind), packed, b, ops.data(), t.loss, n->loss_dn, rows, S(stream),
+                                       post.step ? &post : nullptr, mode == TRAIN_MERGED_BF16);
+}
+// (the loss descriptor's stream state, as net_forward_loss_impl establishes it)
+static int net_train_ensure_loss(linna_net_t* n, const linna_loss_desc_t* d, void* stream) {
+    if (!n || !d) { set_error("net_train_step: null argument"); return LINNA_ERR_INVALID; }
+    return net_loss_current(n, d, stream, "net_train_step");
+}
+int linna_net_forward_loss(linna_net_t* n, const linna_loss_desc_t* d, const float* X, int ldx, const int* ROWS, int B,
+                           const int* lg, const float* xmean, const float* xstd, float* XB, int ldxb, void* ws, float* PRED,
+                           int ldp, const float* YN, int ldyn, const float* den, float inv_batch, float* loss_rows,
+                           float* loss_mean, float* dPRED, int lddp, float* hyper, int* step_dev, float b1, float b2,
+                           void* stream) try {
+    if (!d) { set_error("net_forward_loss: null loss descriptor"); return LINNA_ERR_INVALID; }
+    CHECK_STRUCT(d, linna_loss_desc_t, "net_forward_loss");
+    const TrainStep t{{X, ldx, ROWS, B, lg, xmean, xstd, XB, ldxb}, {YN, ldyn, den, inv_batch, loss_rows, dPRED, lddp},
+                      ws, nullptr, PRED, ldp, loss_mean, hyper, step_dev, b1, b2};
+    return net_forward_loss_impl(n, d, t, stream, false);
+} LINNA_CATCH_INT
+// linna_net_train_step (linna_hip.h): linna_net_forward_loss followed by linna_net_backward(param_grads = 1) on the rows it
+// gathered, the riders carried by the whole-network launches instead of a launch of their own between them.
+int linna_net_train_step(linna_net_t* n, const linna_loss_desc_t* d, const float* X, int ldx, const int* ROWS, int B,
+                         const int* lg, const float* xmean, const float* xstd, float* XB, int ldxb, void* fwd_ws, float* PRED,
+                         int ldp, const float* YN, int ldyn, const float* den, float inv_batch, float* loss_rows,
+                         float* loss_mean, float* dPRED, int lddp, void* bwd_ws, float* hyper, int* step_dev, float b1, float b2,
+                         void* stream) try {
+    if (!bwd_ws) { set_error("net_train_step: backward workspace required"); return LINNA_ERR_INVALID; }
+    if (!d) { set_error("net_train_step: null loss descriptor"); return LINNA_ERR_INVALID; }
+    CHECK_STRUCT(d, linna_loss_desc_t, "net_train_step");
+    const TrainStep t{{X, ldx, ROWS, B, lg, xmean, xstd, XB, ldxb}, {YN, ldyn, den, inv_batch, loss_rows, dPRED, lddp},
+                      fwd_ws, bwd_ws, PRED, ldp, loss_mean, hyper, step_dev, b1, b2};
+    TRY(net_train_ensure_loss(n, d, stream));
+    TRY(net_bf16_mode_check(n, B, "net_train_step"));
+    const TrainMode mode = net_train_mode(n, B);
+    if (mode == TRAIN_MERGED || mode == TRAIN_MERGED_BF16) {
+        // two launches: forward + loss + dX chain, then every parameter gradient (the batch mean of the loss riding in it)
+        TRY(net_train_merged_impl(n, d, t, mode, stream));
+        const GemmPost gp{loss_rows, loss_mean ? B : 0, inv_batch, loss_mean};
+        return net_train_backward(n, t, stream, BwdRiders{nullptr, nullptr, true, &gp});
+    }
+    // forward + loss, then the backward with the riders in its dX-chain launch (a launch of their own without one)
+    TRY(net_forward_loss_impl(n, d, t, stream, true));
+    const NsPost post = train_riders(t);
+    return net_train_backward(n, t, stream, BwdRiders{post.out || post.step ? &post : nullptr});
+} LINNA_CATCH_INT
+
+int linna_net_train_launches(const linna_net_t* n, int B) try {
+    if (!n || B < 1) { set_error("net_train_launches: bad arguments"); return LINNA_ERR_INVALID; }
+    const TrainMode mode = net_train_mode(n, B);
+    return mode == TRAIN_NONE ? 0 : mode == TRAIN_FWD_DX ? 3 : 2;
+} LINNA_CATCH_INT
+// The bf16 training step (linna_hip.h).  Checks first (no GPU), then the bf16 stream is allocated; its size depends on the
+// network and the loss's width only, so a placeholder inverse covariance plans it before the loss is known.
+int linna_net_set_train_precision(linna_net_t* n, int precision) try {
+    if (!n) { set_error("net_set_train_precision: null handle"); return LINNA_ERR_INVALID; }
+    TRY(check_precision(precision, "net_set_train_precision"));
+    if (precision == LINNA_PRECISION_FP32) { n->train_prec = precision; n->as_state = -1; return LINNA_OK; }
+    if (n->has_inskip) { set_error("net_set_train_precision: no bf16 training step for an input-skip network (it has no merged training step)"); return LINNA_ERR_UNSUPPORTED; }
+    const NsDense dn = n->loss_dn.S ? n->loss_dn : NsDense{n->L.back().W, (int)ld4(n->out_size), nullptr, nullptr};
+    const NsPlan plan = net_stream_plan(NS_TRAIN_STEP_BF16, n->L.data(), (int)n->L.size(), n->in_size, &dn);
+    if (!plan.ok) { set_error("net_set_train_precision: no bf16 training step for this network: %s", plan.why ? plan.why : "not eligible"); return LINNA_ERR_UNSUPPORTED; }
+    if (!n->packed_tbf.ready() || n->packed_tbf.floats != plan.packed_floats) {
+        n->packed_tbf.release();
+        if (n->packed_tbf.alloc(plan.packed_floats) != LINNA_OK) { set_error("net_set_train_precision: hipMalloc(bf16 training stream) failed"); return LINNA_ERR_HIP; }
+    }
+    n->train_prec = precision; n->as_state = -1;
+    return LINNA_OK;
+} LINNA_CATCH_INT
+int linna_net_train_precision(const linna_net_t* n, int* out) try {
+    if (!n || !out) { set_error("net_train_precision: null argument"); return LINNA_ERR_INVALID; }
+    *out = n->train_prec;
+    return LINNA_OK;
+} LINNA_CATCH_INT
+int linna_net_stream_state(const linna_net_t* n, int* fwd, int* dx, int* dx_input) try {
+    if (!n) { set_error("net_stream_state: null network"); return LINNA_ERR_INVALID; }
+    if (fwd) *fwd = n->stream_fwd;
+    if (dx) *dx = n->stream_bwd[0];
+    if (dx_input) *dx_input = n->stream_bwd[1];
+    return LINNA_OK;
+} LINNA_CATCH_INT
+
+int linna_net_backward(linna_net_t* n, const float* X, int ldx, int B, void* fwd_ws, void* bwd_ws, const float* dOUT,
+                       int lddo, float* dX, int lddx, int pg, void* stream) try {
+    return net_backward_impl(n, X, ldx, B, fwd_ws, bwd_ws, dOUT, lddo, dX, lddx, pg, stream, BwdRiders{});
+} LINNA_CATCH_INT
 
 // ------------------------------------------------------------------ prior map
 int linna_prior_map_fwd(linna_ctx_t*, const float* Z, int ldz, int B, int nin, const int* is_flat, const float* a1,
@@ -878,20 +927,20 @@ int linna_gauss_loglike_diag(linna_ctx_t*, const float* D, int ldd, int B, int n
                              int ldz, int nin, float T, float* out, void* stream) try {
     return launch_loglike_diag(D, ldd, B, nout, w, Z, ldz, nin, T, out, S(stream));
 } LINNA_CATCH_INT
-// factored: Sm holds L with S = L L^T and the row-dot is |d L|^2 (linna_logprob_desc_t::Sfac)
-static int loglike_dense_impl(const float* D, int ldd, int B, int nout, const float* Sm, int lds, bool factored,
-                              const float* Z, int ldz, int nin, float T, float* scratch, float* out, void* stream) {
+// cov: the inverse covariance S[nout][lds] -- or, factored, L with S = L L^T and the row-dot is |d L|^2 (linna_logprob_desc_t::Sfac)
+static int loglike_dense_impl(const float* D, int ldd, int B, int nout, const NsDense& cov, const float* Z, int ldz, int nin, float T,
+                              float* scratch, float* out, void* stream) {
     const int slots = gemm_slots(B, nout);
     GemmArgs a = gemm_zero();          // rows of (D S) dotted with D (or with themselves), no C store
-    set_pair(a, 0, D, ldd, LAY_K, Sm, lds, LAY_MN, nout);
+    set_pair(a, 0, D, ldd, LAY_K, cov.S, cov.lds, LAY_MN, nout);
     a.M = B; a.N = nout; a.dotwith = D; a.lddot = ldd; a.dot_partial = scratch; a.dot_slots = slots;
-    if (factored) a.flags |= LINNA_GEMM_DOT_SELF;
+    if (cov.factored) a.flags |= LINNA_GEMM_DOT_SELF;
     TRY(gemm_launch(a, S(stream)));
     return launch_loglike_finish(scratch, slots, slots, B, Z, ldz, nin, T, out, S(stream));
 }
 int linna_gauss_loglike_dense(linna_ctx_t*, const float* D, int ldd, int B, int nout, const float* Sm, int lds,
                               const float* Z, int ldz, int nin, float T, float* scratch, float* out, void* stream) try {
-    return loglike_dense_impl(D, ldd, B, nout, Sm, lds, false, Z, ldz, nin, T, scratch, out, stream);
+    return loglike_dense_impl(D, ldd, B, nout, NsDense{Sm, lds, nullptr, nullptr}, Z, ldz, nin, T, scratch, out, stream);
 } LINNA_CATCH_INT
 
 }  // extern "C"
@@ -906,7 +955,7 @@ struct linna_logprob {
     StreamCopy packed_g2;                    // forward + dX chain down to the input in one stream (any network: residual blocks, ...)
     bool grad2 = false;
     bool dense_fused = false;                // the streams end in the dense inverse covariance (output map folded in)
-    bool fused_on = true;                    // LINNA_DISABLE_FUSED at creation (fused_switch)
+    bool fused_on = true;                    // LINNA_DISABLE_FUSED, read at creation
     int dense_tri = 2;                       // NsDense::tri, fixed when the object is created (the stream's size depends on it)
     NsDense dense() const { return NsDense{d.Sfac ? d.Sfac : d.S, d.lds, d.outmap.cscale, d.outmap.cshift, d.Sfac ? 1 : 0, dense_tri}; }
     int precision = LINNA_PRECISION_FP32;    // linna_logprob_set_precision
@@ -937,28 +986,6 @@ static LpLayout lp_layout(const linna_logprob* lp, int B, int with_grad) {
     return L;
 }
 
-// LINNA_DISABLE_FUSED=1: no whole-network kernel.  Read when a log-probability object is created, as the other switches
-// are (a process-wide cached value made the switch dead for every object created after the first evaluation).
-static bool fused_switch() { return !(getenv("LINNA_DISABLE_FUSED") && getenv("LINNA_DISABLE_FUSED")[0] == '1'); }
-static int stream_copy_refresh(StreamCopy& sc, const linna_net* n, int rows, void* stream, const float** out, NsKind kind,
-                               const NsDense* dn) {
-    const int k = rows < 16 ? 1 : 0;
-    const unsigned long long epoch = g_weights_epoch.load();
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(S(stream), &cap);
-    const std::vector<linna_layer_t>& LL = ns_kind_full_layers(kind) ? n->Lfull : n->L;
-    if (cap != hipStreamCaptureStatusNone) {
-        // a captured launch carries its own re-layout, so that every replay sees the weights of that
-        // moment; the copy is not valid for direct launches until they redo it
-        TRY(launch_net_stream_pack(kind, LL.data(), (int)LL.size(), n->in_size, sc.buf[k], rows, dn, S(stream)));
-        sc.epoch[k] = 0;
-    } else if (sc.epoch[k] != epoch) {
-        TRY(launch_net_stream_pack(kind, LL.data(), (int)LL.size(), n->in_size, sc.buf[k], rows, dn, S(stream)));
-        sc.epoch[k] = epoch;
-    }
-    *out = sc.buf[k];
-    return LINNA_OK;
-}
 // The copy the engine for `B` rows reads, re-laid if the weights moved since it was made; *rows: that engine.
 static int lp_refresh_stream(linna_logprob* lp, int B, void* stream, const float** packed, int* rows) {
     *rows = net_stream_rows(B);
@@ -966,24 +993,45 @@ static int lp_refresh_stream(linna_logprob* lp, int B, void* stream, const float
     return stream_copy_refresh(lp->bf16() ? lp->packed_bf : lp->packed, lp->net, *rows, stream, packed, lp->kind(),
                                lp->kind() == NS_SERVE_DENSE ? &dn : nullptr);
 }
-// One launch of the serving program on the copy for `rows`: the descriptor's prior map, input transform, output map and
-// likelihood (the dense program carries the output map and the covariance in its stream); the rest is what the entries vary.
-static int lp_launch(const linna_logprob* lp, const float* packed, int rows, const float* Z, int ldz, int B, float* lnP, float* D,
-                     int ldd, float* TH, int ldt, const NsMove* mv, const NsGrad* gr, const int* gate, void* stream) {
+// The descriptor's prior map and input transform, and its output map and diagonal likelihood, as the launchers take them.
+// The dense program carries the output map and the covariance in its stream: it gets none of the latter; the second half
+// of the exp output map is passed only when the map has one (cexp).
+static NsInput lp_input(const linna_logprob_desc_t& d) { return NsInput{d.nin, d.is_flat, d.a1, d.a2, d.log10_flag, d.xmean, d.xstd}; }
+static NsOutput lp_output(const linna_logprob* lp) {
     const linna_logprob_desc_t& d = lp->d;
-    const linna_net* n = lp->net;
+    if (lp->kind() == NS_SERVE_DENSE) return NsOutput{nullptr, nullptr, nullptr, nullptr, nullptr, d.temperature};
+    return NsOutput{d.outmap.cscale, d.outmap.cshift, d.outmap.cexp ? d.outmap.cpost : nullptr, d.outmap.cexp ? d.outmap.cshift2 : nullptr,
+                    d.w, d.temperature};
+}
+// What the entries vary in a serving launch: the rows Z[B][ldz], lnP[B], the device gate (linna_logprob_eval_if), the
+// physical parameters TH and the residuals D (null: not written)
+struct LpRun { const float* Z; int ldz; int B; float* lnP; const int* gate = nullptr; float* TH = nullptr; int ldt = 0; float* D = nullptr; int ldd = 0; };
+// One launch of the serving program on the copy for `rows`, around a sampler move `mv` or with the fused gradient `gr` (or null)
+static int lp_launch(const linna_logprob* lp, const float* packed, int rows, const LpRun& r, const NsMove* mv, const NsGrad* gr, void* stream) {
     const NsDense dn = lp->dense();
-    const bool df = lp->kind() == NS_SERVE_DENSE;
-    return launch_net_stream(lp->kind(), n->Lfull.data(), (int)n->Lfull.size(), n->in_size, packed, Z, ldz, B, d.nin, d.is_flat, d.a1,
-                             d.a2, d.log10_flag, d.xmean, d.xstd, df ? nullptr : d.outmap.cscale, df ? nullptr : d.outmap.cshift,
-                             df ? nullptr : d.w, d.temperature, lnP, D, ldd, TH, ldt, mv, gr, gate, rows, df ? &dn : nullptr, S(stream),
-                             d.outmap.cexp ? d.outmap.cpost : nullptr, d.outmap.cexp ? d.outmap.cshift2 : nullptr);
+    return launch_net_stream(lp->kind(), net_layers(lp->net, lp->kind()), packed, r.Z, r.ldz, r.B, lp_input(lp->d), lp_output(lp), r.lnP, r.D,
+                             r.ldd, r.TH, r.ldt, mv, gr, r.gate, rows, lp->kind() == NS_SERVE_DENSE ? &dn : nullptr, S(stream));
+}
+// Whether this log-probability runs the whole-network kernel around a sampler move (a bf16 handle runs the bf16 stream or
+// nothing: where this refuses, the caller's fallback evaluates in bf16 too)
+static bool lp_runs_fused_move(const linna_logprob* lp) {
+    const linna_logprob_desc_t& d = lp->d;
+    return lp->fused_on && (lp->bf16() ? lp->packed_bf.ready() : lp->packed.ready()) &&
+           !(d.outmap.cexp && (!d.w || !d.outmap.cpost || !d.outmap.cshift2)) && (d.w || lp->dense_fused) && d.nin <= 64;
+}
+// the likelihood of the residuals in the workspace as launches of their own: diagonal, or the dense row-dot
+static int lp_likelihood(const linna_logprob* lp, const LpRun& r, float* w, const LpLayout& L, void* stream) {
+    const linna_logprob_desc_t& d = lp->d;
+    const int ldd = ld4(d.nout);
+    if (d.w) return launch_loglike_diag(w + L.d, ldd, r.B, d.nout, d.w, r.Z, r.ldz, d.nin, d.temperature, r.lnP, S(stream));
+    return loglike_dense_impl(w + L.d, ldd, r.B, d.nout, lp->dense(), r.Z, r.ldz, d.nin, d.temperature, w + L.part, r.lnP, stream);
 }
 
-static int lp_forward(linna_logprob* lp, const float* Z, int ldz, int B, float* w, const LpLayout& L, float* lnP,
-                      float* TH, int ldt, void* stream, bool keep_activations, const int* gate = nullptr) {
+// lnP (and TH) of the rows `r` in the workspace w laid out as L: one launch, or -- `keep_activations`, or no such program --
+// prior map, the network's forward and the likelihood as launches of their own
+static int lp_forward(linna_logprob* lp, const LpRun& r, float* w, const LpLayout& L, void* stream, bool keep_activations) {
     const linna_logprob_desc_t& d = lp->d;
-    const int ldx = ld4(d.nin), ldd = ld4(d.nout);
+    const int ldx = ld4(d.nin), ldd = ld4(d.nout), B = r.B;
     if (lp->bf16()) {
         // bf16 runs the whole-network kernel or nothing: never silently fp32
         if (keep_activations || !lp->fused_on || !lp->packed_bf.ready() || !d.w || (d.outmap.cexp && (!d.outmap.cpost || !d.outmap.cshift2))) {
@@ -992,7 +1040,7 @@ static int lp_forward(linna_logprob* lp, const float* Z, int ldz, int B, float* 
         }
         const float* packed = nullptr; int rows = 16;
         TRY(lp_refresh_stream(lp, B, stream, &packed, &rows));
-        return lp_launch(lp, packed, rows, Z, ldz, B, lnP, nullptr, 0, TH, ldt, nullptr, nullptr, gate, stream);
+        return lp_launch(lp, packed, rows, r, nullptr, nullptr, stream);
     }
     if (!keep_activations && lp->fused_on && lp->packed.ready() && (!d.outmap.cexp || (d.outmap.cpost && d.outmap.cshift2 && !lp->dense_fused))) {
         // whole-network kernel (net_stream.hip): prior map -> every layer -> output transform -> diagonal
@@ -1001,18 +1049,13 @@ static int lp_forward(linna_logprob* lp, const float* Z, int ldz, int B, float* 
         TRY(lp_refresh_stream(lp, B, stream, &packed, &rows));
         // dense covariance: the output map is folded into the stream's last layer and the inverse covariance is its last
         // segment -- lnP comes out of the same launch
-        if (lp->dense_fused) return lp_launch(lp, packed, rows, Z, ldz, B, lnP, nullptr, 0, TH, ldt, nullptr, nullptr, gate, stream);
-        TRY(lp_launch(lp, packed, rows, Z, ldz, B, d.w ? lnP : nullptr, d.w ? nullptr : w + L.d, ldd, TH, ldt, nullptr, nullptr, gate, stream));
-        if (d.w) return LINNA_OK;
-        return loglike_dense_impl(w + L.d, ldd, B, d.nout, d.Sfac ? d.Sfac : d.S, d.lds, d.Sfac != nullptr, Z, ldz, d.nin, d.temperature,
-                                         w + L.part, lnP, stream);
+        if (lp->dense_fused) return lp_launch(lp, packed, rows, r, nullptr, nullptr, stream);
+        TRY(lp_launch(lp, packed, rows, LpRun{r.Z, r.ldz, B, d.w ? r.lnP : nullptr, r.gate, r.TH, r.ldt, d.w ? nullptr : w + L.d, ldd}, nullptr, nullptr, stream));
+        return d.w ? LINNA_OK : lp_likelihood(lp, r, w, L, stream);
     }
-    TRY(launch_prior_map_fwd(Z, ldz, B, d.nin, d.is_flat, d.a1, d.a2, d.log10_flag, d.xmean, d.xstd, w + L.x0, ldx, TH,
-                             ldt, S(stream)));
+    TRY(launch_prior_map_fwd(r.Z, r.ldz, B, d.nin, d.is_flat, d.a1, d.a2, d.log10_flag, d.xmean, d.xstd, w + L.x0, ldx, r.TH, r.ldt, S(stream)));
     TRY(linna_net_forward(lp->net, w + L.x0, ldx, B, w + L.fwd, w + L.d, ldd, &d.outmap, stream));
-    if (d.w) return launch_loglike_diag(w + L.d, ldd, B, d.nout, d.w, Z, ldz, d.nin, d.temperature, lnP, S(stream));
-    return loglike_dense_impl(w + L.d, ldd, B, d.nout, d.Sfac ? d.Sfac : d.S, d.lds, d.Sfac != nullptr, Z, ldz, d.nin, d.temperature,
-                                     w + L.part, lnP, stream);
+    return lp_likelihood(lp, r, w, L, stream);
 }
 
 extern "C" {
@@ -1028,10 +1071,9 @@ int linna_logprob_create(linna_ctx_t* ctx, linna_net_t* net, const linna_logprob
     if (!(desc->temperature > 0.f)) { set_error("logprob_create: temperature must be > 0"); return LINNA_ERR_INVALID; }
     linna_logprob* lp = new linna_logprob{ctx, net, *desc};
     lp->dense_tri = net_stream_dense_tri(-1);
-    lp->fused_on = fused_switch();
+    lp->fused_on = !env_is("LINNA_DISABLE_FUSED", '1');     // 1: no whole-network kernel
     const NsDense dn = lp->dense();
-    const bool want_dense = !desc->w && desc->S && !desc->outmap.cexp &&
-                            !(getenv("LINNA_DENSE_FUSED") && getenv("LINNA_DENSE_FUSED")[0] == '0');
+    const bool want_dense = !desc->w && desc->S && !desc->outmap.cexp && !env_is("LINNA_DENSE_FUSED", '0');
     const NsPlan dense = want_dense ? net_stream_plan(NS_SERVE_DENSE, net->Lfull.data(), (int)net->Lfull.size(), net->in_size, &dn)
                                     : NsPlan{false, 0, false, nullptr};
     const NsPlan serve = net_stream_plan(NS_SERVE, net->Lfull.data(), (int)net->Lfull.size(), net->in_size);
@@ -1042,8 +1084,7 @@ int linna_logprob_create(linna_ctx_t* ctx, linna_net_t* net, const linna_logprob
             delete lp; return LINNA_ERR_HIP;
         }
     } else if (serve.ok) {
-        lp->grad_fused = serve.grad_ok && !desc->outmap.cexp &&
-                         !(getenv("LINNA_DISABLE_FUSED_GRAD") && getenv("LINNA_DISABLE_FUSED_GRAD")[0] == '1');
+        lp->grad_fused = serve.grad_ok && !desc->outmap.cexp && !env_is("LINNA_DISABLE_FUSED_GRAD", '1');
         if (lp->packed.alloc(serve.packed_floats) != LINNA_OK) {
             set_error("logprob_create: hipMalloc(weight stream) failed");
             delete lp; return LINNA_ERR_HIP;
@@ -1051,8 +1092,7 @@ int linna_logprob_create(linna_ctx_t* ctx, linna_net_t* net, const linna_logprob
     }
     // lnP + gradient in one launch for the networks the MLP-only fused gradient does not cover (residual blocks, SPLIT
     // segments): forward program + dX chain in one weight stream, gates from the activations the same launch stored
-    if (!lp->grad_fused && desc->w && desc->gscale && !desc->outmap.cexp && !net->has_inskip &&
-        !(getenv("LINNA_DISABLE_FUSED_GRAD") && getenv("LINNA_DISABLE_FUSED_GRAD")[0] == '1')) {
+    if (!lp->grad_fused && desc->w && desc->gscale && !desc->outmap.cexp && !net->has_inskip && !env_is("LINNA_DISABLE_FUSED_GRAD", '1')) {
         const NsPlan g2 = net_stream_plan(NS_GRAD_INPUT, net->L.data(), (int)net->L.size(), net->in_size);
         if (g2.ok && lp->packed_g2.alloc(g2.packed_floats) == LINNA_OK) lp->grad2 = true;
     }
@@ -1069,10 +1109,7 @@ int linna_weights_changed(linna_ctx_t*) try { g_weights_epoch.fetch_add(1); retu
 // graph capture -- and laid out by the first launch that reads them, like the fp32 copy (weight epoch).
 int linna_logprob_set_precision(linna_logprob_t* lp, int precision) try {
     if (!lp) { set_error("logprob_set_precision: null handle"); return LINNA_ERR_INVALID; }
-    if (precision != LINNA_PRECISION_FP32 && precision != LINNA_PRECISION_BF16) {
-        set_error("logprob_set_precision: unknown precision %d (LINNA_PRECISION_FP32 0, LINNA_PRECISION_BF16 1)", precision);
-        return LINNA_ERR_INVALID;
-    }
+    TRY(check_precision(precision, "logprob_set_precision"));
     if (precision == LINNA_PRECISION_FP32) { lp->precision = precision; lp->grad_precision = LINNA_PRECISION_FP32; return LINNA_OK; }
     const linna_net* n = lp->net;
     if (!lp->d.w) { set_error("logprob_set_precision: bf16 needs a diagonal likelihood (a dense covariance is served in fp32 only)"); return LINNA_ERR_UNSUPPORTED; }
@@ -1097,10 +1134,7 @@ int linna_logprob_precision(const linna_logprob_t* lp, int* out) try {
 // then the third stream copy is allocated here and laid out by the first launch that reads it (weight epoch).
 int linna_logprob_set_grad_precision(linna_logprob_t* lp, int precision) try {
     if (!lp) { set_error("logprob_set_grad_precision: null handle"); return LINNA_ERR_INVALID; }
-    if (precision != LINNA_PRECISION_FP32 && precision != LINNA_PRECISION_BF16) {
-        set_error("logprob_set_grad_precision: unknown precision %d (LINNA_PRECISION_FP32 0, LINNA_PRECISION_BF16 1)", precision);
-        return LINNA_ERR_INVALID;
-    }
+    TRY(check_precision(precision, "logprob_set_grad_precision"));
     if (precision == LINNA_PRECISION_FP32) { lp->grad_precision = precision; return LINNA_OK; }
     if (!lp->bf16()) {
         set_error("logprob_set_grad_precision: a bf16 gradient needs a bf16 handle (linna_logprob_set_precision first): lnP has one surface per handle");
@@ -1128,13 +1162,12 @@ int linna_logprob_grad_precision(const linna_logprob_t* lp, int* out) try {
 } LINNA_CATCH_INT
 int linna_program_describe_grad_bf16(const linna_layer_t* layers, int nlayers, int in_size, int rows, char* buf, size_t n) try {
     if (!layers || nlayers < 1 || !buf || !n) { set_error("program_describe_grad_bf16: bad arguments"); return LINNA_ERR_INVALID; }
-    for (int i = 0; i < nlayers; ++i) CHECK_STRUCT(layers + i, linna_layer_t, "program_describe_grad_bf16");
+    TRY(check_layers(layers, nlayers, "program_describe_grad_bf16"));
     return net_stream_describe(NS_GRAD_INPUT_BF16, layers, nlayers, in_size, nullptr, rows, buf, n);
 } LINNA_CATCH_INT
 int linna_program_describe(const linna_layer_t* layers, int nlayers, int in_size, int rows, int dense_nout, char* buf, size_t n) try {
     if (!layers || nlayers < 1 || !buf || !n) { set_error("program_describe: bad arguments"); return LINNA_ERR_INVALID; }
-    CHECK_STRUCT(layers, linna_layer_t, "program_describe");
-    for (int i = 1; i < nlayers; ++i) CHECK_STRUCT(layers + i, linna_layer_t, "program_describe");
+    TRY(check_layers(layers, nlayers, "program_describe"));
     // (pointers are only compared, never read: a placeholder stands for the dense inverse covariance)
     static float dummy;
     if (dense_nout == -1) return net_stream_describe(NS_GRAD_INPUT, layers, nlayers, in_size, nullptr, rows, buf, n);   // the one-launch gradient's program
@@ -1170,50 +1203,48 @@ size_t linna_logprob_ws_bytes(const linna_logprob_t* lp, int B, int with_grad) t
 int linna_logprob_eval(linna_logprob_t* lp, const float* Z, int ldz, int B, void* ws, float* lnP, float* TH, int ldt,
                        void* stream) try {
     if (!lp || !Z || !ws || !lnP || B < 1) { set_error("logprob_eval: bad arguments"); return LINNA_ERR_INVALID; }
-    const LpLayout L = lp_layout(lp, B, 0);
-    return lp_forward(lp, Z, ldz, B, static_cast<float*>(ws), L, lnP, TH, ldt, stream, false);
+    return lp_forward(lp, LpRun{Z, ldz, B, lnP, nullptr, TH, ldt}, static_cast<float*>(ws), lp_layout(lp, B, 0), stream, false);
 } LINNA_CATCH_INT
 
 int linna_logprob_eval_if(linna_logprob_t* lp, const float* Z, int ldz, int B, void* ws, float* lnP, float* TH, int ldt,
                           const int* gate, void* stream) try {
     if (!lp || !Z || !ws || !lnP || B < 1) { set_error("logprob_eval_if: bad arguments"); return LINNA_ERR_INVALID; }
-    const LpLayout L = lp_layout(lp, B, 0);
-    return lp_forward(lp, Z, ldz, B, static_cast<float*>(ws), L, lnP, TH, ldt, stream, false, gate);
+    return lp_forward(lp, LpRun{Z, ldz, B, lnP, gate, TH, ldt}, static_cast<float*>(ws), lp_layout(lp, B, 0), stream, false);
 } LINNA_CATCH_INT
 
-// `list` / `count` / `mul`: only the trial points list[0 .. count[0] * mul) are evaluated (device-side count; the launch is
-// sized for all nrep * ns); `b_engine`: the batch size the engine is chosen for (the expected number of live rows)
 // the first shrinking round behind one stepping-out round: what the evaluation needs to place its own trials (NsArgs::sl_*)
 struct SliceDerive { const float* Z0; const float* L; const float* R; const float* Ze; int m, nt; uint64_t seed; const int* step_dev; int stream_id; const int* flags; };
-static int lp_eval_slice_points(linna_logprob_t* lp, const float* coords, int ldc, int ndim, const int* S_idx, int ns,
-                                const float* DIR, int ldd, const float* w, int nrep, float* lnP, const int* gate,
+// the walkers of a half step and their directions: trial point (j, k) = coords[S_idx[k]] + w[j * ns + k] * DIR[k]
+struct SlicePoints { const float* coords; int ldc, ndim; const int* S_idx; int ns; const float* DIR; int ldd; };
+// lnP[nrep * ns] at the trial points of weights w[nrep * ns], formed in the launch's prologue.
+// `list` / `count` / `mul`: only the trial points list[0 .. count[0] * mul) are evaluated (device-side count; the launch is
+// sized for all nrep * ns); `b_engine`: the batch size the engine is chosen for (the expected number of live rows);
+// `sd` / `sb`: this evaluation derives its own trials (SliceDerive) / sets the half step up (SliceBegin)
+static int lp_eval_slice_points(linna_logprob_t* lp, const SlicePoints& pt, const float* w, int nrep, float* lnP, const int* gate,
                                 const int* list, const int* count, int mul, int b_engine, void* stream, const SliceDerive* sd = nullptr,
                                 const SliceBegin* sb = nullptr) {
-    if (!lp || !coords || !S_idx || !DIR || !w || !lnP || ns < 1 || nrep < 1) {
+    if (!lp || !pt.coords || !pt.S_idx || !pt.DIR || !w || !lnP || pt.ns < 1 || nrep < 1) {
         set_error("logprob_eval_slice_points: bad arguments"); return LINNA_ERR_INVALID;
     }
-    const linna_logprob_desc_t& d = lp->d;
-    if (ndim != d.nin) { set_error("logprob_eval_slice_points: ndim %d, log-probability has %d parameters", ndim, d.nin); return LINNA_ERR_INVALID; }
-    // (a bf16 handle runs the bf16 stream or nothing: where this refuses, the caller's fallback evaluates in bf16 too)
-    if (!lp->fused_on || !(lp->bf16() ? lp->packed_bf.ready() : lp->packed.ready()) || (d.outmap.cexp && (!d.w || !d.outmap.cpost || !d.outmap.cshift2)) ||
-        (!d.w && !lp->dense_fused) || d.nin > 64) {
+    if (pt.ndim != lp->d.nin) { set_error("logprob_eval_slice_points: ndim %d, log-probability has %d parameters", pt.ndim, lp->d.nin); return LINNA_ERR_INVALID; }
+    if (!lp_runs_fused_move(lp)) {
         set_error("logprob_eval_slice_points: this log-probability does not run the whole-network kernel");
         return LINNA_ERR_UNSUPPORTED;          // the caller falls back to linna_slice_points + linna_logprob_eval_if
     }
     const float* packed = nullptr; int rows = 16;
-    TRY(lp_refresh_stream(lp, b_engine > 0 ? b_engine : nrep * ns, stream, &packed, &rows));
-    NsMove mv{const_cast<float*>(coords), ldc, nullptr, S_idx, w, 0, list, ns, 0ull, count, mul, 0, 0.f, nullptr, 1};
+    TRY(lp_refresh_stream(lp, b_engine > 0 ? b_engine : nrep * pt.ns, stream, &packed, &rows));
+    NsMove mv{const_cast<float*>(pt.coords), pt.ldc, nullptr, pt.S_idx, w, 0, list, pt.ns, 0ull, count, mul, 0, 0.f, nullptr, 1};
     mv.sb = sb;
     if (sd) {
         mv.sl_Z0 = sd->Z0; mv.sl_L = sd->L; mv.sl_R = sd->R; mv.sl_Zt = sd->Ze; mv.sl_m = sd->m; mv.sl_nt = sd->nt;
         mv.sl_seed = sd->seed; mv.sl_step = sd->step_dev; mv.sl_stream = sd->stream_id; mv.sl_flags = sd->flags;
     }
-    return lp_launch(lp, packed, rows, DIR, ldd, nrep * ns, lnP, nullptr, 0, nullptr, 0, &mv, nullptr, gate, stream);
+    return lp_launch(lp, packed, rows, LpRun{pt.DIR, pt.ldd, nrep * pt.ns, lnP, gate}, &mv, nullptr, stream);
 }
 int linna_logprob_eval_slice_points(linna_logprob_t* lp, const float* coords, int ldc, int ndim, const int* S_idx, int ns,
                                     const float* DIR, int ldd, const float* w, int nrep, float* lnP, const int* gate,
                                     void* stream) try {
-    return lp_eval_slice_points(lp, coords, ldc, ndim, S_idx, ns, DIR, ldd, w, nrep, lnP, gate, nullptr, nullptr, 0, 0, stream);
+    return lp_eval_slice_points(lp, SlicePoints{coords, ldc, ndim, S_idx, ns, DIR, ldd}, w, nrep, lnP, gate, nullptr, nullptr, 0, 0, stream);
 } LINNA_CATCH_INT
 
 // One half step of the ensemble slice sampler (zeus behind sampler.py:728-735) in ONE call: the differential-move directions
@@ -1233,16 +1264,15 @@ int linna_slice_half_step(linna_logprob_t* lp, float* coords, int ldc, int ndim,
     if (maxsteps < 1) { set_error("slice_half_step: maxsteps %d < 1", maxsteps); return LINNA_ERR_INVALID; }
     for (int r = 0; r < nexp_rounds; ++r) if (m_sched[r] < 1) { set_error("slice_half_step: m_sched[%d] = %d", r, m_sched[r]); return LINNA_ERR_INVALID; }
     for (int r = 0; r < nshr_rounds; ++r) if (nt_sched[r] < 1) { set_error("slice_half_step: nt_sched[%d] = %d", r, nt_sched[r]); return LINNA_ERR_INVALID; }
-    const linna_logprob_desc_t& d = lp->d;
-    if (ndim != d.nin) { set_error("slice_half_step: ndim %d, log-probability has %d parameters", ndim, d.nin); return LINNA_ERR_INVALID; }
-    if (!lp->fused_on || !(lp->bf16() ? lp->packed_bf.ready() : lp->packed.ready()) || (d.outmap.cexp && (!d.w || !d.outmap.cpost || !d.outmap.cshift2)) ||
-        (!d.w && !lp->dense_fused) || d.nin > 64) {
+    if (ndim != lp->d.nin) { set_error("slice_half_step: ndim %d, log-probability has %d parameters", ndim, lp->d.nin); return LINNA_ERR_INVALID; }
+    if (!lp_runs_fused_move(lp)) {
         set_error("slice_half_step: this log-probability does not run the whole-network kernel");
         return LINNA_ERR_UNSUPPORTED;          // the caller falls back to the round-by-round entries
     }
     float* const Z0 = state; float* const L = state + ns; float* const R = state + 2 * ns;
     float* const Wacc = state + 3 * ns; float* const Zacc = state + 4 * ns;
     hipStream_t st = S(stream);
+    const SlicePoints pt{coords, ldc, ndim, S_idx, ns, DIR, ldd};
     // the set-up of the half step: a launch of its own, or done by the first evaluation in its prologue (SliceBegin)
     const bool begin_fused = (g_slice_fusion.load() & 2) != 0;
     const SliceBegin sb{logp, ccoords, ldcc, C_idx, nc, mu, seed, step_dev, half, m_sched[0], DIR, ldd, Z0, L, R, flags, counters,
@@ -1263,8 +1293,8 @@ int linna_slice_half_step(linna_logprob_t* lp, float* coords, int ldc, int ndim,
     // further ahead for nothing (m_sched / nt_sched grow) and the call needs few rounds.
     for (int r = 0; r < nexp_rounds; ++r, ++slot) {
         const int m = m_sched[r], m_next = r + 1 < nexp_rounds ? m_sched[r + 1] : 0;
-        TRY(lp_eval_slice_points(lp, coords, ldc, ndim, S_idx, ns, DIR, ldd, W, 2 * m, Zt, nullptr, r > 0 ? list : nullptr,
-                                 r > 0 ? counters + slot - 1 : nullptr, 2 * m, expect_rows && r > 0 ? std::max(1, expect_rows[r]) : std::max(1, (2 * m * ns) >> (2 * r)), stream, nullptr,
+        TRY(lp_eval_slice_points(lp, pt, W, 2 * m, Zt, nullptr, r > 0 ? list : nullptr, r > 0 ? counters + slot - 1 : nullptr, 2 * m,
+                                 expect_rows && r > 0 ? std::max(1, expect_rows[r]) : std::max(1, (2 * m * ns) >> (2 * r)), stream, nullptr,
                                  r == 0 && begin_fused ? &sb : nullptr));
         if (!derive)
             TRY(launch_slice_expand_multi(Z0, Zt, L, R, S_idx, flags, ns, m, m_next, counters, slot, r > 0 ? slot - 1 : -1, W, Wd, list, seed,
@@ -1276,8 +1306,7 @@ int linna_slice_half_step(linna_logprob_t* lp, float* coords, int ldc, int ndim,
         trials += nt;
         const bool dv = derive && r == 0;
         SliceDerive sd{Z0, L, R, Zt, m_sched[0], nt, seed, step_dev, 2 + half, flags};
-        TRY(lp_eval_slice_points(lp, coords, ldc, ndim, S_idx, ns, DIR, ldd, Wd, nt, dv ? W : Zt, nullptr, r > 0 ? list : nullptr,
-                                 r > 0 ? counters + slot - 1 : nullptr, nt,
+        TRY(lp_eval_slice_points(lp, pt, Wd, nt, dv ? W : Zt, nullptr, r > 0 ? list : nullptr, r > 0 ? counters + slot - 1 : nullptr, nt,
                                  expect_rows && r > 0 ? std::max(1, expect_rows[nexp_rounds + r]) : std::max(1, (nt * ns) >> (2 * r)), stream, dv ? &sd : nullptr));
         const bool last = r + 1 == nshr_rounds;         // the commit (and the step counter) ride in the last round's logic kernel
         SliceRound sr{Z0, dv ? W : Zt, L, R, S_idx, Wd, flags, Wacc, Zacc, ns, counters, slot, r > 0 ? slot - 1 : -1, nt, nt_next, trials, list,
@@ -1294,17 +1323,15 @@ int linna_stretch_half_step(linna_logprob_t* lp, float* coords, int ldc, int ndi
     if (!lp || !coords || !logp || !S_idx || !ccoords || !C_idx || !step_dev || ns < 1 || nc < 1) {
         set_error("stretch_half_step: bad arguments"); return LINNA_ERR_INVALID;
     }
-    const linna_logprob_desc_t& d = lp->d;
-    if (ndim != d.nin) { set_error("stretch_half_step: ndim %d, log-probability has %d parameters", ndim, d.nin); return LINNA_ERR_INVALID; }
-    if (!lp->fused_on || !(lp->bf16() ? lp->packed_bf.ready() : lp->packed.ready()) ||
-        (d.outmap.cexp && (!d.w || !d.outmap.cpost || !d.outmap.cshift2)) || (!d.w && !lp->dense_fused) || d.nin > 64) {
+    if (ndim != lp->d.nin) { set_error("stretch_half_step: ndim %d, log-probability has %d parameters", ndim, lp->d.nin); return LINNA_ERR_INVALID; }
+    if (!lp_runs_fused_move(lp)) {
         set_error("stretch_half_step: this log-probability does not run the whole-network kernel");
         return LINNA_ERR_UNSUPPORTED;          // the caller falls back to propose / eval / accept
     }
     const float* packed = nullptr; int rows = 16;
     TRY(lp_refresh_stream(lp, ns, stream, &packed, &rows));
     NsMove mv{coords, ldc, logp, S_idx, ccoords, ldcc, C_idx, nc, seed, step_dev, step_offset, stream_id, a, naccept, 0};
-    return lp_launch(lp, packed, rows, nullptr, 0, ns, nullptr, nullptr, 0, nullptr, 0, &mv, nullptr, nullptr, stream);
+    return lp_launch(lp, packed, rows, LpRun{nullptr, 0, ns, nullptr}, &mv, nullptr, stream);
 } LINNA_CATCH_INT
 
 
@@ -1315,10 +1342,8 @@ int linna_stretch_run(linna_logprob_t* lp, float* coords, int ldc, int ndim, flo
         (chain != nullptr) != (logps != nullptr)) {
         set_error("stretch_run: bad arguments"); return LINNA_ERR_INVALID;
     }
-    const linna_logprob_desc_t& d = lp->d;
-    if (ndim != d.nin) { set_error("stretch_run: ndim %d, log-probability has %d parameters", ndim, d.nin); return LINNA_ERR_INVALID; }
-    if (!lp->fused_on || !(lp->bf16() ? lp->packed_bf.ready() : lp->packed.ready()) ||
-        (d.outmap.cexp && (!d.w || !d.outmap.cpost || !d.outmap.cshift2)) || (!d.w && !lp->dense_fused) || d.nin > 64) {
+    if (ndim != lp->d.nin) { set_error("stretch_run: ndim %d, log-probability has %d parameters", ndim, lp->d.nin); return LINNA_ERR_INVALID; }
+    if (!lp_runs_fused_move(lp)) {
         set_error("stretch_run: this log-probability does not run the whole-network kernel");
         return LINNA_ERR_UNSUPPORTED;          // the caller loops over linna_stretch_half_step / the three-launch form
     }
@@ -1330,7 +1355,7 @@ int linna_stretch_run(linna_logprob_t* lp, float* coords, int ldc, int ndim, flo
         for (int h = 0; h < 2; ++h) {
             NsMove mv{coords, ldc, logp, sp + h * ns, coords, ldc, sp + (1 - h) * ns, ns, seed, step_dev, step_offset + i, h, a, naccept, 0};
             if (chain) { mv.chain = chain + (size_t)i * nw * ndim; mv.lps = logps + (size_t)i * nw; }
-            TRY(lp_launch(lp, packed, rows, nullptr, 0, ns, nullptr, nullptr, 0, nullptr, 0, &mv, nullptr, nullptr, stream));
+            TRY(lp_launch(lp, packed, rows, LpRun{nullptr, 0, ns, nullptr}, &mv, nullptr, stream));
         }
     }
     return LINNA_OK;
@@ -1377,8 +1402,22 @@ int linna_chain_meanstd(linna_ctx_t*, const float* CT, int ndim, int nwp, int nw
 
 }  // extern "C"
 
-// lnP and its gradient at Z; `leap` (hm_* of an NsGrad, the rest unset): the leapfrog's kick and drift behind it -- in the
-// finish of the one-launch forms, as a launch of its own behind the others
+// the gradient's destination and, with `leap` (hm_* of an NsGrad, the rest unset), the leapfrog's kick and drift behind it
+static NsGrad lp_grad_args(const linna_logprob_desc_t& d, float* G, int ldg, const NsGrad* leap) {
+    NsGrad g{d.gscale, G, ldg, nullptr, 0, nullptr, nullptr, 0.f, 0.f};
+    if (leap) { g.hm_p = leap->hm_p; g.hm_ldp = leap->hm_ldp; g.hm_q = leap->hm_q; g.hm_mass = leap->hm_mass; g.hm_ek = leap->hm_ek; g.hm_ed = leap->hm_ed; }
+    return g;
+}
+// forward + dX chain down to the input in one launch on the stream copy `sc` (NS_GRAD_INPUT, or its bf16 form)
+static int lp_launch_grad2(linna_logprob* lp, StreamCopy& sc, bool bf, const float* Z, int ldz, int B, float* lnP, const NsGrad& gr, void* stream) {
+    const NsKind kind = bf ? NS_GRAD_INPUT_BF16 : NS_GRAD_INPUT;
+    const int rows = net_stream_rows(B);
+    const float* packed = nullptr;
+    TRY(stream_copy_refresh(sc, lp->net, rows, stream, &packed, kind));
+    return launch_net_stream_grad2(net_layers(lp->net, kind), packed, Z, ldz, B, lp_input(lp->d), lp_output(lp), lnP, gr, rows, S(stream), bf);
+}
+// lnP and its gradient at Z; `leap`: the leapfrog's kick and drift -- in the finish of the one-launch forms, as a launch of
+// its own behind the others
 static int logprob_grad_impl(linna_logprob_t* lp, const float* Z, int ldz, int B, void* ws, float* lnP, float* G, int ldg,
                              const NsGrad* leap, void* stream) {
     if (!lp || !Z || !ws || !lnP || !G || B < 1) { set_error("logprob_grad: bad arguments"); return LINNA_ERR_INVALID; }
@@ -1393,25 +1432,16 @@ static int logprob_grad_impl(linna_logprob_t* lp, const float* Z, int ldz, int B
             set_error("logprob_grad: this bf16 log-probability cannot run its one-launch gradient here (LINNA_DISABLE_FUSED, or no bf16 gradient stream)");
             return LINNA_ERR_UNSUPPORTED;
         }
-        NsGrad gb{d.gscale, G, ldg, nullptr, 0, nullptr, nullptr, 0.f, 0.f};
-        if (leap) { gb.hm_p = leap->hm_p; gb.hm_ldp = leap->hm_ldp; gb.hm_q = leap->hm_q; gb.hm_mass = leap->hm_mass; gb.hm_ek = leap->hm_ek; gb.hm_ed = leap->hm_ed; }
-        const linna_net* n = lp->net;
-        const int rows = net_stream_rows(B);
-        const float* packed = nullptr;
-        TRY(stream_copy_refresh(lp->packed_gbf, n, rows, stream, &packed, NS_GRAD_INPUT_BF16));
-        return launch_net_stream_grad2(n->L.data(), (int)n->L.size(), n->in_size, packed, Z, ldz, B, d.nin, d.is_flat, d.a1, d.a2,
-                                       d.log10_flag, d.xmean, d.xstd, d.outmap.cscale, d.outmap.cshift, d.w, d.temperature, lnP, gb,
-                                       rows, S(stream), true);
+        return lp_launch_grad2(lp, lp->packed_gbf, true, Z, ldz, B, lnP, lp_grad_args(d, G, ldg, leap), stream);
     }
     if (d.outmap.cexp) { set_error("logprob_grad: ypositive (exp) output map has no gradient path"); return LINNA_ERR_UNSUPPORTED; }
     if (!d.gscale || (!d.w && !d.Ssym)) { set_error("logprob_grad: descriptor lacks gscale / Ssym"); return LINNA_ERR_INVALID; }
-    NsGrad gr{d.gscale, G, ldg, nullptr, 0, nullptr, nullptr, 0.f, 0.f};
-    if (leap) { gr.hm_p = leap->hm_p; gr.hm_ldp = leap->hm_ldp; gr.hm_q = leap->hm_q; gr.hm_mass = leap->hm_mass; gr.hm_ek = leap->hm_ek; gr.hm_ed = leap->hm_ed; }
+    const NsGrad gr = lp_grad_args(d, G, ldg, leap);
     if (lp->fused_on && lp->packed.ready() && lp->grad_fused && d.w) {
         // lnP and d lnP / d z in ONE launch: forward segments, turnaround, backward segments over W^T (net_stream.hip)
         const float* packed = nullptr; int rows = 16;
         TRY(lp_refresh_stream(lp, B, stream, &packed, &rows));
-        return lp_launch(lp, packed, rows, Z, ldz, B, lnP, nullptr, 0, nullptr, 0, nullptr, &gr, nullptr, stream);
+        return lp_launch(lp, packed, rows, LpRun{Z, ldz, B, lnP}, nullptr, &gr, stream);
     }
     const LpLayout L = lp_layout(lp, B, 1);
     float* w = static_cast<float*>(ws);
@@ -1419,15 +1449,9 @@ static int logprob_grad_impl(linna_logprob_t* lp, const float* Z, int ldz, int B
     if (lp->fused_on && lp->grad2 && lp->packed_g2.ready() && d.w) {
         // ONE launch for any network: forward segments (the signs the gates need kept as bits in LDS), turnaround, dX chain
         // down to the input, prior map's derivative (net_stream.hip, GRAD + STORE == 2) -- six launches otherwise
-        const linna_net* n = lp->net;
-        const int rows = net_stream_rows(B);
-        const float* packed = nullptr;
-        TRY(stream_copy_refresh(lp->packed_g2, n, rows, stream, &packed, NS_GRAD_INPUT));
-        return launch_net_stream_grad2(n->L.data(), (int)n->L.size(), n->in_size, packed, Z, ldz, B, d.nin, d.is_flat, d.a1, d.a2,
-                                       d.log10_flag, d.xmean, d.xstd, d.outmap.cscale, d.outmap.cshift, d.w, d.temperature, lnP, gr,
-                                       rows, S(stream));
+        return lp_launch_grad2(lp, lp->packed_g2, false, Z, ldz, B, lnP, gr, stream);
     }
-    TRY(lp_forward(lp, Z, ldz, B, w, L, lnP, nullptr, 0, stream, true));
+    TRY(lp_forward(lp, LpRun{Z, ldz, B, lnP}, w, L, stream, true));
     if (d.w) {
         TRY(launch_loglike_diag_grad(w + L.d, ldd, B, d.nout, d.w, d.gscale, d.temperature, w + L.dh, ldd, S(stream)));
     } else {   // dH = -(1/T) * (D Ssym) * gscale
@@ -1497,11 +1521,8 @@ int linna_chi2_ratio_loss_fwd_bwd(linna_ctx_t* ctx, const linna_loss_desc_t* d, 
     hipStream_t st = S(stream);
     if (ctx && d->nout <= 64 && lddp >= 0) {
         // five launches of 5-14 us each (delta, U = delta Cinv, row sums, mean, gradient) for 2 MFLOP: one kernel
-        if (ctx->loss_fused < 0) {
-            const char* e = getenv("LINNA_LOSS_FUSED");
-            ctx->loss_fused = (e && e[0] == '0') ? 0 : 1;
-        }
-        unsigned* const cnt = ctx->loss_fused == 1 ? ctx_counters(ctx, st) : nullptr;
+        if (ctx->loss_fused < 0) ctx->loss_fused = env_is("LINNA_LOSS_FUSED", '0') ? 0 : 1;
+        unsigned* const cnt = ctx->loss_fused == 1 ? ctx->counters : nullptr;     // (zeroed, self-resetting: linna_ctx_create)
         if (cnt)
             return launch_loss_fused_small(PRED, ldp, Y, ldy, ROWS, B, *d, den, inv_batch, loss_rows, loss_mean, dPRED, lddp,
                                            cnt, st);
@@ -1548,67 +1569,47 @@ int linna_adamw_step(linna_ctx_t*, float* p, const float* g, float* m, float* v,
     return launch_adamw(p, g, m, v, n, hyper, prepared ? nullptr : step_dev, b1, b2, eps, S(stream));
 } LINNA_CATCH_INT
 
-// AdamW over the network's flat parameter buffer AND the re-layout of the updated weights into the two weight streams a
-// training step reads (linna_net_forward_loss's and the backward's dX chain), in ONE launch: what linna_adamw_step
-// followed by the two lazy re-layouts of the next step does in three.  `B`: the batch size the step runs at (it
-// selects the engine, hence the stream layout).  LINNA_ERR_UNSUPPORTED when the network does not train through those
-// two streams, or `params[n]` is not exactly its tensors back to back: the caller then uses linna_adamw_step.
-// The placement tables of the flat parameter buffer `p[n]` in the two training streams (net_stream_adamw_args), cached.
+// The placement tables of the flat parameter buffer `p[n]` in the streams a step of B rows trains through
+// (net_stream_adamw_args), cached; the mode they describe is left in net->as_mode.
 static int net_ensure_as_args(linna_net_t* net, int B, const float* p, size_t n) {
-    const bool bf = net_bf16(net);
-    if (bf) {
-        TRY(net_tbf_check(net, B, "net_adamw_step"));
-        if (!net->loss_dn.S) { set_error("net_adamw_step: bf16 training stream: no loss seen yet (linna_net_prepare_loss)"); return LINNA_ERR_UNSUPPORTED; }
-    }
-    const int merged = bf ? 2 : net_tb_usable(net, B) ? 1 : 0;
-    if (!bf && (net->stream_loss != 1 || (!merged && (net->stream_bwd[0] != 1 || !net->packed_loss.ready() || !net->packed_dx[0].ready())))) {
+    TRY(net_bf16_mode_check(net, B, "net_adamw_step"));
+    const TrainMode mode = net_train_mode(net, B);
+    const TrainStreams ts = net_train_streams(net, mode);
+    if (mode == TRAIN_NONE || !ts.fwd->ready() || (ts.dx && !ts.dx->ready())) {
         set_error("the network does not train through the whole-network streams"); return LINNA_ERR_UNSUPPORTED;
     }
     const int rows = net_stream_rows(B), k = rows < 16 ? 1 : 0;
-    if (net->as_state < 0 || net->as_params != p || net->as_n != n || net->as_k != k || net->as_merged != merged) {
-        net->as_params = p; net->as_n = n; net->as_k = k; net->as_merged = merged;
-        net->as_state = (merged ? net_stream_adamw_args(net->L.data(), (int)net->L.size(), net->in_size, rows, p, n,
-                                                        (bf ? net->packed_tbf : net->packed_tb).buf[k], &net->loss_dn, nullptr, &net->as_args, merged)
-                                : net_stream_adamw_args(net->L.data(), (int)net->L.size(), net->in_size, rows, p, n, net->packed_loss.buf[k],
-                                                        &net->loss_dn, net->packed_dx[0].buf[k], &net->as_args)) == LINNA_OK ? 1 : 0;
+    if (net->as_state < 0 || net->as_params != p || net->as_n != n || net->as_k != k || net->as_mode != mode) {
+        net->as_params = p; net->as_n = n; net->as_k = k; net->as_mode = mode;
+        const int merged = mode == TRAIN_MERGED_BF16 ? 2 : mode == TRAIN_MERGED ? 1 : 0;      // (net_stream_adamw_args' name for the mode)
+        net->as_state = net_stream_adamw_args(net->L.data(), (int)net->L.size(), net->in_size, rows, p, n, ts.fwd->buf[k], &net->loss_dn,
+                                              ts.dx ? ts.dx->buf[k] : nullptr, &net->as_args, merged) == LINNA_OK ? 1 : 0;
         net->upd_state = -1;
     }
     return net->as_state == 1 ? LINNA_OK : LINNA_ERR_UNSUPPORTED;   // (the error text is net_stream_adamw_args')
 }
 
+// linna_net_adamw_step (linna_hip.h): AdamW over the flat parameter buffer AND the re-layout of the updated weights into the
+// streams a training step of B rows reads, in ONE launch.
 int linna_net_adamw_step(linna_net_t* net, int B, float* p, const float* g, float* m, float* v, size_t n, float* hyper,
                          int* step_dev, float b1, float b2, float eps, int prepared, void* stream) try {
     if (!net || !p || !g || !m || !v || !hyper || !step_dev || B < 1) { set_error("net_adamw_step: bad arguments"); return LINNA_ERR_INVALID; }
     TRY(net_ensure_as_args(net, B, p, n));
-    const int rows = net_stream_rows(B), k = rows < 16 ? 1 : 0;
-    // both streams must hold the CURRENT weights and their constant parts before they are patched in place
+    // the streams must hold the CURRENT weights and their constant parts before they are patched in place
+    const int rows = net_stream_rows(B);
+    const TrainStreams ts = net_train_streams(net, net->as_mode);
     const float* dummy = nullptr;
-    const bool merged = net->as_merged >= 1, bf = net->as_merged == 2;
-    if (merged) {
-        TRY(stream_copy_refresh(bf ? net->packed_tbf : net->packed_tb, net, rows, stream, &dummy, bf ? NS_TRAIN_STEP_BF16 : NS_TRAIN_STEP, &net->loss_dn));
-    } else {
-        TRY(stream_copy_refresh(net->packed_loss, net, rows, stream, &dummy, NS_TRAIN_FWD, &net->loss_dn));
-        TRY(stream_copy_refresh(net->packed_dx[0], net, rows, stream, &dummy, NS_DX));
-    }
+    TRY(stream_copy_refresh(*ts.fwd, net, rows, stream, &dummy, ts.kind, &net->loss_dn));
+    if (ts.dx) TRY(stream_copy_refresh(*ts.dx, net, rows, stream, &dummy, NS_DX));
     if (!prepared) TRY(launch_adamw_prepare(hyper, step_dev, b1, b2, S(stream)));
-    TRY(launch_adamw_streams(net->as_args, p, g, m, v, hyper, b1, b2, eps, S(stream), bf));
-    const unsigned long long epoch = g_weights_epoch.fetch_add(1) + 1;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(S(stream), &cap);
-    if (cap == hipStreamCaptureStatusNone) {
-        if (bf) net->packed_tbf.epoch[k] = epoch;
-        else if (merged) net->packed_tb.epoch[k] = epoch;
-        else { net->packed_loss.epoch[k] = epoch; net->packed_dx[0].epoch[k] = epoch; }
-    }
+    TRY(launch_adamw_streams(net->as_args, p, g, m, v, hyper, b1, b2, eps, S(stream), net->as_mode == TRAIN_MERGED_BF16));
+    net_stamp_updated(net, net->as_mode, B, stream);
     return LINNA_OK;
 } LINNA_CATCH_INT
 
-// ONE optimiser step in ONE call and THREE launches: linna_net_train_step with AdamW in the epilogue of its grouped
-// parameter-gradient launch -- every 64 x 64 gradient tile updates its block of the weight matrix (and its moments) as soon as
-// it exists and writes the updated block into the two weight streams the next step reads.  For one rank (data-parallel
-// training all-reduces the gradients between backward and update: linna_net_train_step + linna_net_adamw_step).
-// LINNA_ERR_UNSUPPORTED -- before anything is launched -- when the network does not train through the streams, `params[n]`
-// is not its tensors back to back, or some parameter gradient of the step falls outside the grouped launch.
+// linna_net_train_step_update (linna_hip.h): linna_net_train_step with AdamW in the epilogue of its grouped parameter-gradient
+// launch -- every 64 x 64 gradient tile updates its block of the weight matrix (and its moments) as soon as it exists and
+// writes the updated block into the weight streams the next step reads.  LINNA_ERR_UNSUPPORTED before anything is launched.
 int linna_net_train_step_update(linna_net_t* net, const linna_loss_desc_t* d, const float* X, int ldx, const int* ROWS, int B,
                                 const int* lg, const float* xmean, const float* xstd, float* XB, int ldxb, void* fwd_ws, float* PRED,
                                 int ldp, const float* YN, int ldyn, const float* den, float inv_batch, float* loss_rows,
@@ -1618,8 +1619,10 @@ int linna_net_train_step_update(linna_net_t* net, const linna_loss_desc_t* d, co
     if (!d) { set_error("net_train_step_update: null loss descriptor"); return LINNA_ERR_INVALID; }
     CHECK_STRUCT(d, linna_loss_desc_t, "net_train_step_update");
     if (net->has_inskip) { set_error("net_train_step_update: input-skip network"); return LINNA_ERR_UNSUPPORTED; }
+    const TrainStep t{{X, ldx, ROWS, B, lg, xmean, xstd, XB, ldxb}, {YN, ldyn, den, inv_batch, loss_rows, dPRED, lddp},
+                      fwd_ws, bwd_ws, PRED, ldp, loss_mean, hyper, step_dev, b1, b2};
     TRY(net_train_ensure_loss(net, d, stream));
-    if (net_bf16(net)) TRY(net_tbf_check(net, B, "net_train_step_update"));
+    TRY(net_bf16_mode_check(net, B, "net_train_step_update"));
     TRY(net_ensure_as_args(net, B, params, n));
     if (net->upd_state < 0 || net->upd_B != B) {
         // every parameter gradient of the step must be a problem of the grouped launch, and the gradient pointers of the layer
@@ -1648,30 +1651,20 @@ int linna_net_train_step_update(linna_net_t* net, const linna_loss_desc_t* d, co
         set_error("net_train_step_update: a parameter gradient of this network falls outside the grouped launch%s", net_bf16(net) ? " (bf16 step)" : "");
         return LINNA_ERR_UNSUPPORTED;
     }
-    const bool merged = net->as_merged >= 1, bf = net->as_merged == 2;
-    const NetUpdate upd{params, m, v, n, hyper, b1, b2, eps, bf};
-    if (merged) {
+    const TrainMode mode = net->as_mode;
+    const NetUpdate upd{params, m, v, hyper, b1, b2, eps, mode == TRAIN_MERGED_BF16};
+    if (mode != TRAIN_FWD_DX) {
         // TWO launches: forward + loss + dX chain (AdamW's step constants riding in it), then every parameter gradient with the
         // optimiser in the tiles' epilogue (the batch mean of the loss riding in it)
-        TRY(net_train_merged_impl(net, d, X, ldx, ROWS, B, lg, xmean, xstd, XB, ldxb, fwd_ws, PRED, ldp, YN, ldyn, den, inv_batch,
-                                  loss_rows, dPRED, lddp, bwd_ws, hyper, step_dev, b1, b2, stream));
+        TRY(net_train_merged_impl(net, d, t, mode, stream));
         const GemmPost gp{loss_rows, loss_mean ? B : 0, inv_batch, loss_mean};
-        TRY(net_backward_impl(net, XB, ldxb, B, fwd_ws, bwd_ws, dPRED, lddp, nullptr, 0, 1, stream, nullptr, &upd, true, &gp));
+        TRY(net_train_backward(net, t, stream, BwdRiders{nullptr, &upd, true, &gp}));
     } else {
-        TRY(net_forward_loss_impl(net, d, X, ldx, ROWS, B, lg, xmean, xstd, XB, ldxb, fwd_ws, PRED, ldp, YN, ldyn, den, inv_batch,
-                                  loss_rows, loss_mean, dPRED, lddp, hyper, step_dev, b1, b2, stream, true));
-        const NsPost post{loss_rows, B, inv_batch, loss_mean, step_dev, hyper, b1, b2};
-        TRY(net_backward_impl(net, XB, ldxb, B, fwd_ws, bwd_ws, dPRED, lddp, nullptr, 0, 1, stream, &post, &upd));
+        TRY(net_forward_loss_impl(net, d, t, stream, true));
+        const NsPost post = train_riders(t);
+        TRY(net_train_backward(net, t, stream, BwdRiders{&post, &upd}));
     }
-    const int k = net_stream_rows(B) < 16 ? 1 : 0;
-    const unsigned long long epoch = g_weights_epoch.fetch_add(1) + 1;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(S(stream), &cap);
-    if (cap == hipStreamCaptureStatusNone) {
-        if (bf) net->packed_tbf.epoch[k] = epoch;
-        else if (merged) net->packed_tb.epoch[k] = epoch;
-        else { net->packed_loss.epoch[k] = epoch; net->packed_dx[0].epoch[k] = epoch; }
-    }
+    net_stamp_updated(net, mode, B, stream);
     return LINNA_OK;
 } LINNA_CATCH_INT
 

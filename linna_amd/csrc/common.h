@@ -416,6 +416,13 @@ int net_stream_force_rows(int rows);   // 0 automatic, 4 / 8 / 16 forced; return
 int launch_net_stream_pack(NsKind kind, const linna_layer_t* layers, int nl, int in_size, float* packed, int rows, const NsDense* dn,
                            hipStream_t s);
 int net_stream_describe(NsKind kind, const linna_layer_t* layers, int nl, int in_size, const NsDense* dn, int rows, char* buf, size_t n);
+// What always travels together into the launchers of the whole-network kernel: plain records, copied field by field into
+// NsArgs.  NsNet: the op list a program is planned from (with or without the trailing input skip: ns_kind_full_layers) and
+// the network's input width.  NsInput: the prior map and the input transform.  NsOutput: the output map and the diagonal
+// likelihood (cpost / cshift2: the exp output map's second half, or null).
+struct NsNet { const linna_layer_t* layers; int nl, in_size; };
+struct NsInput { int nin; const int* is_flat; const float* a1; const float* a2; const int* lg; const float* xmean; const float* xstd; };
+struct NsOutput { const float* cscale; const float* cshift; const float* cpost; const float* cshift2; const float* w; float T; };
 // Where a training step's activations and their gradients live, per op (api.hip: net_bufs): y its output, t the hidden h
 // of a residual block, x its input and `gate` = x where x went through a ReLU (else null; leading dimension ldx); dprev
 // d/d(op input), dt d/dh of a residual block.
@@ -423,8 +430,8 @@ struct NsOpBufs { float* y; int ldy; float* t; int ldt; const float* x; int ldx;
 // A small job that rides in the dX-chain launch as one extra workgroup (linna_net_train_step): the batch mean of the loss
 // rows (out = scale * sum rows[n], sum_scale_prepare_kernel's order) and AdamW's step counter / bias corrections
 struct NsPost { const float* rows; int n; float scale; float* out; int* step; float* hyper; float b1, b2; };
-int launch_net_stream_dx(const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* dOUT, int lddo,
-                         int B, const NsOpBufs* ops, int with_input, int rows, hipStream_t s, const NsPost* post = nullptr);
+int launch_net_stream_dx(const NsNet& net, const float* packed, const float* dOUT, int lddo, int B, const NsOpBufs* ops, int with_input,
+                         int rows, hipStream_t s, const NsPost* post = nullptr);
 // sampler moves fused around the evaluation.  slice == 0: stretch half step, rows of the batch are the walkers
 // S[0..B).  slice == 1: rows are the slice sampler's trial points coords[S[k]] + cc[row] * DIR[k], k = row % nc
 // (DIR is passed as the launch's Z / ldz; cc = w[nrep * ns], nc = ns; nothing is written back).
@@ -441,20 +448,20 @@ struct NsMove {
     const SliceBegin* sb = nullptr;                     // slice == 1: this evaluation is the half step's first and sets it up (SliceBegin)
 };
 // training / validation forward: every op's output stored for the backward (STORE instantiation)
-int launch_net_stream_store(const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* X, int ldx,
-                            int B, const NsOpBufs* ops, const float* cscale, const float* cshift, int rows, hipStream_t s);
+int launch_net_stream_store(const NsNet& net, const float* packed, const float* X, int ldx, int B, const NsOpBufs* ops,
+                            const float* cscale, const float* cshift, int rows, hipStream_t s);
 // training forward + chi^2-ratio loss in one launch (STORE == 3)
 struct NsTrainLoss { const float* YN; int ldyn;      // normalised targets of the whole set, NaN where masked
                      const float* den; float inv_batch; float* loss_rows; float* dP; int lddp; };
+// the batch of a training step: rows ROWS[B] (null: 0..B-1) of the resident set X, gathered and X-transformed into XB
+struct NsBatch { const float* X; int ldx; const int* ROWS; int B; const int* lg; const float* xmean; const float* xstd; float* XB; int ldxb; };
 int launch_loss_targets(const float* Y, int ldy, int n, const linna_loss_desc_t& d, float* YN, int ldyn, hipStream_t s);
-int launch_net_stream_train(const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* X, int ldx,
-                            const int* ROWS, int B, const int* lg, const float* xmean, const float* xstd, float* XB, int ldxb,
-                            const NsOpBufs* ops, const NsTrainLoss& L, const NsDense& dn, int rows, hipStream_t s);
+int launch_net_stream_train(const NsNet& net, const float* packed, const NsBatch& b, const NsOpBufs* ops, const NsTrainLoss& L,
+                            const NsDense& dn, int rows, hipStream_t s);
 // the same followed by the dX chain down to op 1 in the SAME launch (GRAD + STORE == 3; NS_TRAIN_STEP)
-int launch_net_stream_train_bwd(const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* X, int ldx,
-                                const int* ROWS, int B, const int* lg, const float* xmean, const float* xstd, float* XB, int ldxb,
-                                const NsOpBufs* ops, const NsTrainLoss& L, const NsDense& dn, int rows, hipStream_t s,
-                                const NsPost* post, bool bf = false);     // bf: NS_TRAIN_STEP_BF16 (net_stream_train_bf16_kernel)
+int launch_net_stream_train_bwd(const NsNet& net, const float* packed, const NsBatch& b, const NsOpBufs* ops, const NsTrainLoss& L,
+                                const NsDense& dn, int rows, hipStream_t s, const NsPost* post,
+                                bool bf = false);     // bf: NS_TRAIN_STEP_BF16 (net_stream_train_bf16_kernel)
 // gradient fused behind the evaluation (plain ReLU MLPs, diagonal covariance): G = d lnP / d z
 // hm_*: a leapfrog kick and drift riding in the gradient's finish (HMCSampler.py:35-49): P += ek G; Q += ed P / mass, Q the
 // launch's own input rows (hm_p == nullptr: none)
@@ -503,16 +510,12 @@ int net_stream_adamw_args(const linna_layer_t* layers, int nl, int in_size, int 
 int launch_adamw_streams(const AsArgs& a, float* p, const float* g, float* m, float* v, const float* hyper, float b1, float b2,
                          float eps, hipStream_t s, bool bf = false);
 // forward + dX chain down to the input in one launch (NS_GRAD_INPUT, or bf: NS_GRAD_INPUT_BF16; diagonal covariance)
-int launch_net_stream_grad2(const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* Z, int ldz, int B,
-                            int nin, const int* is_flat, const float* a1, const float* a2, const int* lg, const float* xmean,
-                            const float* xstd, const float* cscale, const float* cshift, const float* w, float T, float* lnP,
-                            const NsGrad& gr, int rows, hipStream_t s, bool bf = false);
+int launch_net_stream_grad2(const NsNet& net, const float* packed, const float* Z, int ldz, int B, const NsInput& in, const NsOutput& out,
+                            float* lnP, const NsGrad& gr, int rows, hipStream_t s, bool bf = false);
 // a serving launch (kind NS_SERVE, NS_SERVE_DENSE with dn, or NS_SERVE_BF16)
-int launch_net_stream(NsKind kind, const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* Z, int ldz, int B,
-                      int nin, const int* is_flat, const float* a1, const float* a2, const int* lg, const float* xmean,
-                      const float* xstd, const float* cscale, const float* cshift, const float* w, float T, float* lnP,
-                      float* D, int ldd, float* TH, int ldt, const NsMove* mv, const NsGrad* gr, const int* gate, int rows,
-                      const NsDense* dn, hipStream_t s, const float* cpost = nullptr, const float* cshift2 = nullptr);
+int launch_net_stream(NsKind kind, const NsNet& net, const float* packed, const float* Z, int ldz, int B, const NsInput& in,
+                      const NsOutput& out, float* lnP, float* D, int ldd, float* TH, int ldt, const NsMove* mv, const NsGrad* gr,
+                      const int* gate, int rows, const NsDense* dn, hipStream_t s);
 
 // autocorr.hip: convergence statistics of a walker chain (running lagged products, emcee's estimator, checkmeanstd's moments)
 int launch_chain_append_t(const float* block, int ldb, int nsteps, int nw, int ndim, int wstride, float* CT, int nwp,

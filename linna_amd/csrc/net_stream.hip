@@ -590,13 +590,13 @@ static NsArgs ns_args(const NsProgram& p, const float* packed, const float* Z, i
 // The store table of segments [lo, hi) from the caller's per-op buffers: forward segments (dx = false) write op i's output
 // y or the hidden h t of its residual block; dX-chain segments write d/d(op input) dprev gated by that input (`gate`), or
 // d/dh dt gated by h.  The loss segment stores nothing.
-static void ns_store_table(NsArgs& a, const NsProgram& p, const linna_layer_t* layers, int nl, const NsOpBufs* ops, int lo, int hi,
-                           bool dx) {
+static void ns_store_table(NsArgs& a, const NsProgram& p, const NsNet& net, const NsOpBufs* ops, int lo, int hi, bool dx) {
     for (int i = lo; i < hi; ++i) {
         const int op = p.seg_op[i];
-        if (op >= nl) continue;
+        if (op >= net.nl) continue;
         const NsOpBufs& b = ops[op];
-        a.gn[i] = p.seg_hidden[i] ? layers[op].C : dx ? layers[op].K : layers[op].N;   // (a dX-chain program's segments are all nseg_f)
+        const linna_layer_t& l = net.layers[op];
+        a.gn[i] = p.seg_hidden[i] ? l.C : dx ? l.K : l.N;   // (a dX-chain program's segments are all nseg_f)
         if (!dx) { a.gout[i] = p.seg_hidden[i] ? b.t : b.y; a.gld[i] = p.seg_hidden[i] ? b.ldt : b.ldy; }
         else if (p.seg_hidden[i]) { a.gout[i] = b.dt; a.gld[i] = b.lddt; a.gmask[i] = b.t; a.gmld[i] = b.ldt; }
         else { a.gout[i] = b.dprev; a.gld[i] = b.ldp; a.gmask[i] = b.gate; a.gmld[i] = b.ldx; }
@@ -611,29 +611,34 @@ static bool ns_set_gates(NsArgs& a, const NsGates& g, const NsProgram& p, int ro
     *lds_extra = g.lds - p.lds_for(rows, true);
     return g.ok && g.lds <= (size_t)NS_LDS_BYTES;
 }
+static void ns_set_input(NsArgs& a, const NsInput& in) {
+    a.is_flat = in.is_flat; a.a1 = in.a1; a.a2 = in.a2; a.lg = in.lg; a.xmean = in.xmean; a.xstd = in.xstd;
+}
+static void ns_set_grad(NsArgs& a, const NsGrad& gr) {
+    a.gscale = gr.gscale; a.Gout = gr.G; a.ldg = gr.ldg;
+    a.hm_p = gr.hm_p; a.hm_ldp = gr.hm_ldp; a.hm_q = gr.hm_q; a.hm_mass = gr.hm_mass; a.hm_ek = gr.hm_ek; a.hm_ed = gr.hm_ed;
+}
 
-int launch_net_stream(NsKind kind, const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* Z, int ldz, int B,
-                      int nin, const int* is_flat, const float* a1, const float* a2, const int* lg, const float* xmean,
-                      const float* xstd, const float* cscale, const float* cshift, const float* w, float T, float* lnP,
-                      float* D, int ldd, float* TH, int ldt, const NsMove* mv, const NsGrad* gr, const int* gate, int rows,
-                      const NsDense* dn, hipStream_t s, const float* cpost, const float* cshift2) {
+int launch_net_stream(NsKind kind, const NsNet& net, const float* packed, const float* Z, int ldz, int B, const NsInput& in,
+                      const NsOutput& out, float* lnP, float* D, int ldd, float* TH, int ldt, const NsMove* mv, const NsGrad* gr,
+                      const int* gate, int rows, const NsDense* dn, hipStream_t s) {
     const bool bf = kind == NS_SERVE_BF16;
     if ((kind == NS_SERVE_DENSE) != (dn != nullptr) || !(kind == NS_SERVE || kind == NS_SERVE_DENSE || bf)) {
         set_error("net_stream: not a serving program"); return LINNA_ERR_INVALID;
     }
-    const NsProgramRef pref = ns_program(kind, layers, nl, in_size, dn, rows);
+    const NsProgramRef pref = ns_program(kind, net.layers, net.nl, net.in_size, dn, rows);
     const NsProgram& p = *pref;
-    if ((cpost != nullptr) != (cshift2 != nullptr) || (cpost && (dn || gr))) {
+    if ((out.cpost != nullptr) != (out.cshift2 != nullptr) || (out.cpost && (dn || gr))) {
         set_error("net_stream: the exp output map needs cpost and cshift2, and has no dense / gradient program"); return LINNA_ERR_INVALID;
     }
     if (!p.ok) { set_error("net_stream: network not eligible"); return LINNA_ERR_UNSUPPORTED; }
-    if (dn && (w || gr || cscale || cshift)) { set_error("net_stream: the dense program carries its own output map and has no fused gradient"); return LINNA_ERR_INVALID; }
-    if (mv && (nin > 64 || (!w && !dn))) { set_error("net_stream: fused sampler moves need <= 64 parameters and a log-likelihood in the launch"); return LINNA_ERR_UNSUPPORTED; }
-    if (gr && (!p.grad_ok || !w || !lnP || !gr->gscale || !gr->G || mv)) { set_error("net_stream: no fused gradient for this network / likelihood"); return LINNA_ERR_UNSUPPORTED; }
-    NsArgs a = ns_args(p, packed, Z, ldz, B, nin, gr != nullptr);    // forward only: stop after the forward segments
-    a.is_flat = is_flat; a.a1 = a1; a.a2 = a2; a.lg = lg; a.xmean = xmean; a.xstd = xstd;
-    a.cscale = cscale; a.cshift = cshift; a.w = w; a.T = T;
-    a.cpost = cpost; a.cshift2 = cshift2;
+    if (dn && (out.w || gr || out.cscale || out.cshift)) { set_error("net_stream: the dense program carries its own output map and has no fused gradient"); return LINNA_ERR_INVALID; }
+    if (mv && (in.nin > 64 || (!out.w && !dn))) { set_error("net_stream: fused sampler moves need <= 64 parameters and a log-likelihood in the launch"); return LINNA_ERR_UNSUPPORTED; }
+    if (gr && (!p.grad_ok || !out.w || !lnP || !gr->gscale || !gr->G || mv)) { set_error("net_stream: no fused gradient for this network / likelihood"); return LINNA_ERR_UNSUPPORTED; }
+    NsArgs a = ns_args(p, packed, Z, ldz, B, in.nin, gr != nullptr);    // forward only: stop after the forward segments
+    ns_set_input(a, in);
+    a.cscale = out.cscale; a.cshift = out.cshift; a.w = out.w; a.T = out.T;
+    a.cpost = out.cpost; a.cshift2 = out.cshift2;
     a.dense = p.dense ? (dn && dn->factored ? 2 : 1) : 0; a.u_col = p.u_col; a.u_same = p.u_same; a.x0_keep = p.x0_keep;
     a.lnP = lnP; a.D = D; a.ldd = ldd; a.TH = TH; a.ldt = ldt;
     a.gate = gate;
@@ -655,8 +660,7 @@ int launch_net_stream(NsKind kind, const linna_layer_t* layers, int nl, int in_s
     if (bf && gr) { set_error("net_stream: no bf16 gradient"); return LINNA_ERR_UNSUPPORTED; }
     if (bf) return ns_launch_kernel<0, false, 0, true>(a, B, p, rows, s);
     if (gr) {
-        a.gscale = gr->gscale; a.Gout = gr->G; a.ldg = gr->ldg;
-        a.hm_p = gr->hm_p; a.hm_ldp = gr->hm_ldp; a.hm_q = gr->hm_q; a.hm_mass = gr->hm_mass; a.hm_ek = gr->hm_ek; a.hm_ed = gr->hm_ed;
+        ns_set_grad(a, *gr);
         return ns_launch_kernel<0, true>(a, B, p, rows, s);
     }
     return ns_launch_kernel<0, false>(a, B, p, rows, s);
@@ -664,16 +668,16 @@ int launch_net_stream(NsKind kind, const linna_layer_t* layers, int nl, int in_s
 
 // Training / validation forward: X[B][ldx] (transformed inputs) -> every op's output (`ops[i].y`, the hidden h of a
 // residual block `ops[i].t`) in global memory.
-int launch_net_stream_store(const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* X, int ldx,
-                            int B, const NsOpBufs* ops, const float* cscale, const float* cshift, int rows, hipStream_t s) {
-    const NsProgramRef pref = ns_program(NS_STORE, layers, nl, in_size, nullptr, rows);
+int launch_net_stream_store(const NsNet& net, const float* packed, const float* X, int ldx, int B, const NsOpBufs* ops,
+                            const float* cscale, const float* cshift, int rows, hipStream_t s) {
+    const NsProgramRef pref = ns_program(NS_STORE, net.layers, net.nl, net.in_size, nullptr, rows);
     const NsProgram& p = *pref;
     if (!p.ok) { set_error("net_stream: network not eligible"); return LINNA_ERR_UNSUPPORTED; }
-    NsArgs a = ns_args(p, packed, X, ldx, B, in_size, false);
+    NsArgs a = ns_args(p, packed, X, ldx, B, net.in_size, false);
     // the prologue's transform constants are loaded (and ignored): any readable arrays of >= in_size entries
     a.is_flat = reinterpret_cast<const int*>(X); a.a1 = X; a.a2 = X; a.lg = nullptr; a.xmean = X; a.xstd = X;
     a.cscale = cscale; a.cshift = cshift;                   // column affine of the last output (Y transforms), or null
-    ns_store_table(a, p, layers, nl, ops, 0, p.nseg_f, false);
+    ns_store_table(a, p, net, ops, 0, p.nseg_f, false);
     return ns_launch_kernel<0, false, 1>(a, B, p, rows, s);
 }
 
@@ -684,21 +688,18 @@ int launch_net_stream_store(const linna_layer_t* layers, int nl, int in_size, co
 // ends of 256 workgroups in step, each read an exposed L2 round trip behind a drained weight ring), the turnaround forms
 // d lnP / d out, the dX chain runs down to the network input gating on those signs, the finish applies the prior map's
 // derivative.  Diagonal covariance.  bf: the same on a bf16 stream (NS_GRAD_INPUT_BF16, net_stream_grad_bf16_kernel).
-int launch_net_stream_grad2(const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* Z, int ldz, int B,
-                            int nin, const int* is_flat, const float* a1, const float* a2, const int* lg, const float* xmean,
-                            const float* xstd, const float* cscale, const float* cshift, const float* w, float T, float* lnP,
-                            const NsGrad& gr, int rows, hipStream_t s, bool bf) {
-    const NsProgramRef pref = ns_program(bf ? NS_GRAD_INPUT_BF16 : NS_GRAD_INPUT, layers, nl, in_size, nullptr, rows);
+int launch_net_stream_grad2(const NsNet& net, const float* packed, const float* Z, int ldz, int B, const NsInput& in, const NsOutput& out,
+                            float* lnP, const NsGrad& gr, int rows, hipStream_t s, bool bf) {
+    const NsProgramRef pref = ns_program(bf ? NS_GRAD_INPUT_BF16 : NS_GRAD_INPUT, net.layers, net.nl, net.in_size, nullptr, rows);
     const NsProgram& p = *pref;
     if (!p.ok || !p.dxi_ok) { set_error("net_stream: no forward + dX program for this network"); return LINNA_ERR_UNSUPPORTED; }
-    if (!w || !lnP || !gr.gscale || !gr.G) { set_error("net_stream: the one-launch gradient needs a diagonal covariance"); return LINNA_ERR_INVALID; }
-    NsArgs a = ns_args(p, packed, Z, ldz, B, nin, true);
-    a.is_flat = is_flat; a.a1 = a1; a.a2 = a2; a.lg = lg; a.xmean = xmean; a.xstd = xstd;
-    a.cscale = cscale; a.cshift = cshift; a.w = w; a.T = T; a.lnP = lnP;
-    a.gscale = gr.gscale; a.Gout = gr.G; a.ldg = gr.ldg;
-    a.hm_p = gr.hm_p; a.hm_ldp = gr.hm_ldp; a.hm_q = gr.hm_q; a.hm_mass = gr.hm_mass; a.hm_ek = gr.hm_ek; a.hm_ed = gr.hm_ed;
-    const NsGates g = ns_gates(p, layers, nl, rows);
-    for (int i = 0; i < (int)p.seg.size(); ++i) if (i >= p.nseg_f || g.gbit[i] >= 0) a.gn[i] = ns_seg_cols(p, layers, i);
+    if (!out.w || !lnP || !gr.gscale || !gr.G) { set_error("net_stream: the one-launch gradient needs a diagonal covariance"); return LINNA_ERR_INVALID; }
+    NsArgs a = ns_args(p, packed, Z, ldz, B, in.nin, true);
+    ns_set_input(a, in);
+    a.cscale = out.cscale; a.cshift = out.cshift; a.w = out.w; a.T = out.T; a.lnP = lnP;     // (no exp output map here)
+    ns_set_grad(a, gr);
+    const NsGates g = ns_gates(p, net.layers, net.nl, rows);
+    for (int i = 0; i < (int)p.seg.size(); ++i) if (i >= p.nseg_f || g.gbit[i] >= 0) a.gn[i] = ns_seg_cols(p, net.layers, i);
     size_t lds_extra = 0;
     if (!ns_set_gates(a, g, p, rows, &lds_extra)) {
         set_error(g.ok ? "net_stream: the one-launch gradient's sign bits do not fit the LDS" : "net_stream: a gate of the one-launch gradient has no producer");
@@ -721,15 +722,14 @@ int launch_net_stream_grad2(const linna_layer_t* layers, int nl, int in_size, co
 
 // the forward + loss half of a training launch (STORE == 3): the batch rows ROWS (null: 0..B-1) of X gathered and
 // X-transformed into XB, every activation stored, the loss rows and d loss / d pred written
-static NsArgs ns_train_args(const NsProgram& p, bool full, const linna_layer_t* layers, int nl, int in_size, const float* packed,
-                            const float* X, int ldx, const int* ROWS, int B, const int* lg, const float* xmean, const float* xstd,
-                            float* XB, int ldxb, const NsOpBufs* ops, const NsTrainLoss& L) {
-    NsArgs a = ns_args(p, packed, X, ldx, B, in_size, full);
-    a.is_flat = reinterpret_cast<const int*>(xmean); a.a1 = xmean; a.a2 = xmean;     // loaded and ignored
-    a.lg = lg; a.xmean = xmean; a.xstd = xstd;
+static NsArgs ns_train_args(const NsProgram& p, bool full, const NsNet& net, const float* packed, const NsBatch& b, const NsOpBufs* ops,
+                            const NsTrainLoss& L) {
+    NsArgs a = ns_args(p, packed, b.X, b.ldx, b.B, net.in_size, full);
+    a.is_flat = reinterpret_cast<const int*>(b.xmean); a.a1 = b.xmean; a.a2 = b.xmean;     // loaded and ignored
+    a.lg = b.lg; a.xmean = b.xmean; a.xstd = b.xstd;
     a.dense = p.dense; a.u_col = p.u_col; a.u_same = p.u_same;
-    ns_store_table(a, p, layers, nl, ops, 0, p.nseg_f, false);
-    a.t_rows = ROWS; a.t_xb = XB; a.t_ldxb = ldxb;
+    ns_store_table(a, p, net, ops, 0, p.nseg_f, false);
+    a.t_rows = b.ROWS; a.t_xb = b.XB; a.t_ldxb = b.ldxb;
     a.t_Y = L.YN; a.t_ldy = L.ldyn;
     a.t_den = L.den; a.t_inv_batch = L.inv_batch; a.t_loss_rows = L.loss_rows; a.t_dP = L.dP; a.t_lddp = L.lddp;
     return a;
@@ -737,14 +737,13 @@ static NsArgs ns_train_args(const NsProgram& p, bool full, const linna_layer_t* 
 
 // Training forward + loss in one launch (STORE == 3); `dn` = {Cinv, ldc, null, null}: the inverse covariance in the
 // network's normalised output space as the last segment.
-int launch_net_stream_train(const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* X, int ldx,
-                            const int* ROWS, int B, const int* lg, const float* xmean, const float* xstd, float* XB, int ldxb,
-                            const NsOpBufs* ops, const NsTrainLoss& L, const NsDense& dn, int rows, hipStream_t s) {
-    const NsProgramRef pref = ns_program(NS_TRAIN_FWD, layers, nl, in_size, &dn, rows);
+int launch_net_stream_train(const NsNet& net, const float* packed, const NsBatch& b, const NsOpBufs* ops, const NsTrainLoss& L,
+                            const NsDense& dn, int rows, hipStream_t s) {
+    const NsProgramRef pref = ns_program(NS_TRAIN_FWD, net.layers, net.nl, net.in_size, &dn, rows);
     const NsProgram& p = *pref;
     if (!p.ok || !p.dense) { set_error("net_stream: network + loss not eligible"); return LINNA_ERR_UNSUPPORTED; }
-    const NsArgs a = ns_train_args(p, false, layers, nl, in_size, packed, X, ldx, ROWS, B, lg, xmean, xstd, XB, ldxb, ops, L);
-    return ns_launch_kernel<0, false, 3>(a, B, p, rows, s);
+    const NsArgs a = ns_train_args(p, false, net, packed, b, ops, L);
+    return ns_launch_kernel<0, false, 3>(a, b.B, p, rows, s);
 }
 
 // A training step's network work in ONE launch (TRB: GRAD + STORE == 3): launch_net_stream_train's forward + loss, its
@@ -752,18 +751,16 @@ int launch_net_stream_train(const linna_layer_t* layers, int nl, int in_size, co
 // of the backward half are sign bits in LDS (ns_gates: the activations go to memory all the same, the parameter
 // gradients read them, but no gate is read back from there).  `post`: only the AdamW step constants ride here (the loss
 // rows are not complete before every workgroup's turnaround: the batch mean rides in the parameter-gradient launch instead).
-int launch_net_stream_train_bwd(const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* X, int ldx,
-                                const int* ROWS, int B, const int* lg, const float* xmean, const float* xstd, float* XB, int ldxb,
-                                const NsOpBufs* ops, const NsTrainLoss& L, const NsDense& dn, int rows, hipStream_t s,
-                                const NsPost* post, bool bf) {
-    const NsProgramRef pref = ns_program(bf ? NS_TRAIN_STEP_BF16 : NS_TRAIN_STEP, layers, nl, in_size, &dn, rows);
+int launch_net_stream_train_bwd(const NsNet& net, const float* packed, const NsBatch& b, const NsOpBufs* ops, const NsTrainLoss& L,
+                                const NsDense& dn, int rows, hipStream_t s, const NsPost* post, bool bf) {
+    const NsProgramRef pref = ns_program(bf ? NS_TRAIN_STEP_BF16 : NS_TRAIN_STEP, net.layers, net.nl, net.in_size, &dn, rows);
     const NsProgram& p = *pref;
     if (!p.ok || !p.train_ok || !p.dense) { set_error("net_stream: network + loss have no one-launch training program"); return LINNA_ERR_UNSUPPORTED; }
     if (rows != 4) { set_error(bf ? "net_stream: the bf16 training step runs on the 4-row engine (batches of up to 1024 rows)"
                                   : "net_stream: the one-launch training step runs on the 4-row engine"); return LINNA_ERR_UNSUPPORTED; }
-    NsArgs a = ns_train_args(p, true, layers, nl, in_size, packed, X, ldx, ROWS, B, lg, xmean, xstd, XB, ldxb, ops, L);
-    ns_store_table(a, p, layers, nl, ops, p.nseg_f, (int)p.seg.size(), true);
-    const NsGates g = ns_gates(p, layers, nl, rows);
+    NsArgs a = ns_train_args(p, true, net, packed, b, ops, L);
+    ns_store_table(a, p, net, ops, p.nseg_f, (int)p.seg.size(), true);
+    const NsGates g = ns_gates(p, net.layers, net.nl, rows);
     size_t lds_extra = 0;
     if (!ns_set_gates(a, g, p, rows, &lds_extra)) {
         set_error(g.ok ? "net_stream: the training step's sign bits do not fit the LDS" : "net_stream: a gate of the one-launch training step has no producer");
@@ -775,23 +772,23 @@ int launch_net_stream_train_bwd(const linna_layer_t* layers, int nl, int in_size
 #ifdef NS_STAMPS
         set_error("net_stream: the NS_STAMPS build has no bf16 training step"); return LINNA_ERR_UNSUPPORTED;
 #endif
-        return ns_launch<net_stream_train_bf16_kernel<NS_R, 0, true, 3, 4, true>>(a, (B + 3) / 4 + extra, p.lds_for(rows, true) + lds_extra, s,
+        return ns_launch<net_stream_train_bf16_kernel<NS_R, 0, true, 3, 4, true>>(a, (b.B + 3) / 4 + extra, p.lds_for(rows, true) + lds_extra, s,
                                                                                   "net_stream bf16 training launch");
     }
-    return ns_launch_kernel<0, true, 3>(a, B, p, rows, s, extra, lds_extra);
+    return ns_launch_kernel<0, true, 3>(a, b.B, p, rows, s, extra, lds_extra);
 }
 
 // The dX chain of a training step in one launch (what linna_net_backward otherwise runs as one GEMM per op):
 // dOUT[B][lddo] -> for every op i >= first (1, or 0 with_input) the gradient with respect to its input, gated by that input
 // where it went through a ReLU, into ops[i].dprev; for residual blocks also d/dh into ops[i].dt, gated by the stored h.
-int launch_net_stream_dx(const linna_layer_t* layers, int nl, int in_size, const float* packed, const float* dOUT, int lddo,
-                         int B, const NsOpBufs* ops, int with_input, int rows, hipStream_t s, const NsPost* post) {
-    const NsProgramRef pref = ns_program(with_input ? NS_DX_INPUT : NS_DX, layers, nl, in_size, nullptr, rows);
+int launch_net_stream_dx(const NsNet& net, const float* packed, const float* dOUT, int lddo, int B, const NsOpBufs* ops, int with_input,
+                         int rows, hipStream_t s, const NsPost* post) {
+    const NsProgramRef pref = ns_program(with_input ? NS_DX_INPUT : NS_DX, net.layers, net.nl, net.in_size, nullptr, rows);
     const NsProgram& p = *pref;
     if (!p.ok) { set_error("net_stream: no dX-chain program for this network"); return LINNA_ERR_UNSUPPORTED; }
-    NsArgs a = ns_args(p, packed, dOUT, lddo, B, layers[nl - 1].N, false);
+    NsArgs a = ns_args(p, packed, dOUT, lddo, B, net.layers[net.nl - 1].N, false);
     a.is_flat = reinterpret_cast<const int*>(dOUT); a.a1 = dOUT; a.a2 = dOUT; a.lg = nullptr; a.xmean = dOUT; a.xstd = dOUT;
-    ns_store_table(a, p, layers, nl, ops, 0, p.nseg_f, true);
+    ns_store_table(a, p, net, ops, 0, p.nseg_f, true);
     if (post && post->n > 0) {                    // the rider (see NsArgs::p_rows): one more workgroup
         a.p_rows = post->rows; a.p_n = post->n; a.p_scale = post->scale; a.p_out = post->out;
         a.p_step = post->step; a.p_hyper = post->hyper; a.p_b1 = post->b1; a.p_b2 = post->b2;

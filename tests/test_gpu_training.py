@@ -482,3 +482,57 @@ def test_one_launch_dx_chain_equals_gemm_chain(kind, nin, nout, kw, monkeypatch)
     _lib.engine_rows(0)
     # the two objects took different routes: the fused one holds a weight stream for the dX chain
     assert fused.uses_dx_stream() and not chain.uses_dx_stream()
+
+
+@pytest.mark.parametrize("with_opt", [True, False])
+def test_train_step_riders_as_their_own_launch(with_opt, monkeypatch):
+    """``linna_net_train_step`` with ``LINNA_BWD_STREAM=0``: forward + loss in one launch, the riders (batch mean of the loss,
+    AdamW's step constants) as a launch of their own and the dX chain as one GEMM per op -- against the same entry with the
+    switch unset, where the riders are carried by the whole-network launches.  Loss rows, batch mean, step counter and bias
+    corrections bit for bit (the forward + loss arithmetic is the same, the riders keep sum_scale_prepare_kernel's order);
+    the gradients within the tolerance of the two dX routes (test_one_launch_dx_chain_equals_gemm_chain)."""
+    from linna_amd import nn, util, predictor_gpu, trainer
+    from linna_amd.predictor_gpu import _AdamWState
+    p = cases.training_problem("train_v2_12_40")
+    t = lambda a: torch.as_tensor(np.asarray(a, np.float32))
+    X = p["X"].reshape(-1, p["nin"]); Y = p["Y"].reshape(-1, p["nout"])
+    B = 50
+
+    def run(dx_stream):
+        if dx_stream:
+            monkeypatch.delenv("LINNA_BWD_STREAM", raising=False)
+        else:
+            monkeypatch.setenv("LINNA_BWD_STREAM", "0")       # read when the engine prepares the network and its loss
+        model = nn.ChtoModelv2(p["nin"], p["nout"], None)
+        model.load_state_dict(p["weights"])
+        pred = predictor_gpu.Predictor(p["nin"], p["nout"], model=model, device="cuda",
+                                       X_transform=util.X_transform_class(t(p["X_mean"]), t(p["X_std"]), "cpu", None),
+                                       y_transform=util.Y_transform_class(t(p["y_mean"]), t(p["y_std"]), "cpu"))
+        ytd = util.Y_transform_data(p["sigma"], "cpu")
+        yinv = util.Y_invtransform_class(t(p["y_mean"]), t(p["y_std"]), t(p["data"]), "cpu")
+        lf = util.Loss_fn(t(p["data"]), torch.tensor(p["cov"], dtype=torch.float64),
+                          torch.tensor(np.linalg.inv(p["cov"]), dtype=torch.float64), ytd, yinv, "cpu")
+        loader = predictor_gpu.BatchLoader(util.ArrayDataset(X, Y), B, shuffle=False, drop_last=True)
+        eng = trainer.TrainEngine(pred, loader, lf, None, use_graph=False)
+        opt = _AdamWState(model, 1e-3) if with_opt else None
+        rows = torch.arange(B, 2 * B, dtype=torch.int32, device="cuda")
+        out = torch.zeros(1, device="cuda")
+        for _ in range(2):                                    # (twice: the second step finds the counter at 1)
+            eng._forward_loss_backward(rows, out, opt)
+        torch.cuda.synchronize()
+        assert eng.one_launch is True                         # not the layered path
+        assert model.stream_state()[1] == (1 if dx_stream else 0)
+        res = [eng.loss_rows.cpu().numpy().copy(), out.cpu().numpy().copy()]
+        if with_opt:
+            res += [opt.step_dev.cpu().numpy().copy(), opt.hyper.cpu().numpy().copy()]
+        return res, model.flat_grads().cpu().numpy().copy()
+
+    own, g_own = run(False)
+    ref, g_ref = run(True)
+    assert np.isfinite(ref[1]).all()
+    if with_opt:
+        assert int(own[2][0]) == 2 and int(ref[2][0]) == 2
+    for a, b in zip(own, ref):
+        np.testing.assert_array_equal(a, b)
+    assert np.abs(g_ref).max() > 0 and np.abs(g_own).max() > 0
+    np.testing.assert_allclose(g_own, g_ref, rtol=1e-3, atol=1e-5 * np.abs(g_ref).max() + 1e-9)
