@@ -530,6 +530,63 @@ int linna_hmc_accept(linna_ctx_t* ctx, int B, int ndim, const float* mass, uint6
                      const int* step_dev, const float* H0, const float* P, int ldp, const float* Qnew,
                      int ldq, const float* lnp_new, const float* Gnew, int ldg, const float* U, float* X,
                      int ldx, float* lnp, float* G, int* naccept, void* stream);
+
+/* ---- a step size per chain, in device memory (EPS[B]).
+ * The three leapfrog entries above with EPS in place of the step sizes: mul_kick / mul_drift are the multipliers of EPS[b]
+ * (1, 0.5 or 0; 0 = no kick / no drift, as a zero step size above), so that P += mul_kick EPS[b] G and
+ * Q += mul_drift EPS[b] P / mass.  A constant EPS gives bit for bit what the scalar entries give for that step size.
+ * step_offset is added to step_dev[0] in the Philox counter (an entry that enqueues several transitions passes i). */
+int linna_hmc_start_eps(linna_ctx_t* ctx, int B, int ndim, const float* mass, uint64_t seed, const int* step_dev,
+                        int step_offset, const float* lnp, const float* P0, int ldp0, const float* G, int ldg,
+                        const float* EPS, float mul_kick, float mul_drift, const float* X, int ldx, float* P, int ldp,
+                        float* Q, int ldq, float* H0, void* stream);
+int linna_hmc_kick_drift_eps(linna_ctx_t* ctx, int B, int ndim, const float* mass, const float* EPS, float mul_kick,
+                             float mul_drift, const float* G, int ldg, float* P, int ldp, float* Q, int ldq, void* stream);
+int linna_logprob_grad_leapfrog_eps(linna_logprob_t* lp, float* Q, int ldq, int B, void* ws, float* lnP, float* G, int ldg,
+                                    float* P, int ldp, const float* mass, const float* EPS, float mul_kick, float mul_drift,
+                                    void* stream);
+/* linna_hmc_accept (the same arithmetic, the same decisions; Philox step step_dev[0] + step_offset) and, behind the test:
+ *  alpha[B] (optional) = exp(min(H0 - H1, 0)), 0 where lnp_new or an energy is not finite;
+ *  chain[B][ndim] / logps[B] (optional): every chain's row and log-probability after the test;
+ *  M[B] (optional) += 1, and for Madapt > 0 the dual averaging of the step size per chain as the reference's NUTSMove runs
+ *  it (sampler.py:198-240; gamma 0.05, t0 10, kappa 0.75, alpha / nalpha with nalpha = 1): while M <= Madapt
+ *    HBAR = (1 - 1/(M + t0)) HBAR + (delta - alpha)/(M + t0); EPS = exp(MU - sqrt(M)/gamma HBAR);
+ *    EPSBAR = exp((1 - M^-kappa) log EPSBAR + M^-kappa log EPS);
+ *  at M == Madapt + 1 EPS = EPSBAR; afterwards nothing.  Madapt = 0: EPS is not written (the state may then be NULL). */
+int linna_hmc_accept_adapt(linna_ctx_t* ctx, int B, int ndim, const float* mass, uint64_t seed, const int* step_dev,
+                           int step_offset, const float* H0, const float* P, int ldp, const float* Qnew, int ldq,
+                           const float* lnp_new, const float* Gnew, int ldg, const float* U, float* X, int ldx, float* lnp,
+                           float* G, int* naccept, float* alpha, float* EPS, float* EPSBAR, float* HBAR, const float* MU,
+                           int* M, int Madapt, float delta, float* chain, float* logps, void* stream);
+
+/* The device state of B independent HMC chains (linna_hmc_run, linna_hmc_find_epsilon): every matrix is [B][ld] floats. */
+typedef struct linna_hmc_state {
+    uint32_t struct_size;            /* sizeof(linna_hmc_state_t) */
+    int B, ld;
+    uint64_t seed;
+    const int* step_dev;             /* the Philox step counter, one int */
+    const float* mass;               /* [ndim] diagonal mass */
+    float* X; float* lnp; float* G;  /* the chains: position, lnP [B] and d lnP / d z at it */
+    float* P; float* Q; float* lnp_new; float* Gnew; float* H0;   /* a trajectory's momenta, end point, lnP / gradient there, start energy [B] */
+} linna_hmc_state_t;
+/* ntrans whole transitions in ONE call: per transition linna_hmc_start_eps (momentum draw, half kick, drift), num_steps >= 1
+ * launches of linna_logprob_grad_leapfrog_eps and linna_hmc_accept_adapt, transition i at Philox step
+ * step_dev[0] + step_offset + i (step_dev is not advanced, as in linna_stretch_run) and with its chain row in
+ * chain[i][B][ndim] / logps[i][B] (both or neither).  Bit for bit the loop of those entries.  ws: linna_logprob_ws_bytes
+ * (B, grad).  LINNA_ERR_UNSUPPORTED where linna_logprob_grad returns it, before anything is launched. */
+int linna_hmc_run(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, float* EPS, float* EPSBAR, float* HBAR,
+                  const float* MU, int* M, int Madapt, float delta, int step_offset, int num_steps, int ntrans, int* naccept,
+                  float* alpha, float* chain, float* logps, void* stream);
+/* A first step size per chain: find_reasonable_epsilon of the reference (sampler.py:151-184) for all chains at once in
+ * max_rounds rounds, none of them read back.  Per chain: eps = 1 and ONE momentum draw r0 (Philox stream 3 at step
+ * step_dev[0] + step_offset, to R0[B][ld]) for every trial; a trial is one leapfrog step from X (linna_hmc_start_eps with
+ * P0 = R0, then one gradient launch with the closing half kick); eps halves while lnP or the gradient there is not finite,
+ * halves once more, then doubles (logaccept > log 0.5) or halves until logaccept crosses log 0.5 from that side.  A chain
+ * that has finished keeps its EPS (state[b] == 2); nactive[0] = the chains not finished after the last round, which keep
+ * the EPS they have reached.  X, lnp, G are read only.  The trial momenta are R0 sqrt(mass) and the kinetic energy P^2 / mass,
+ * as in linna_hmc_start (the reference's search uses R0 itself and R0^2 / mass: the same at unit mass). */
+int linna_hmc_find_epsilon(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, float* R0, float* EPS, int* state,
+                           int* nactive, int step_offset, int max_rounds, void* stream);
 int linna_step_increment(linna_ctx_t* ctx, int* step_dev, void* stream);
 
 /* Ensemble slice sampling (zeus DifferentialMove behind sampler.py:728-735): per active walker a

@@ -68,6 +68,12 @@ class LogprobDesc(_Sized):
                 ("temperature", C.c_float), ("Sfac", C.c_void_p)]
 
 
+class HmcState(_Sized):
+    _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int), ("ld", C.c_int), ("seed", C.c_uint64), ("step_dev", C.c_void_p),
+                ("mass", C.c_void_p), ("X", C.c_void_p), ("lnp", C.c_void_p), ("G", C.c_void_p), ("P", C.c_void_p),
+                ("Q", C.c_void_p), ("lnp_new", C.c_void_p), ("Gnew", C.c_void_p), ("H0", C.c_void_p)]
+
+
 class LossDesc(_Sized):
     _fields_ = [("struct_size", C.c_uint32), ("nout", C.c_int), ("sigma", C.c_void_p), ("ymean", C.c_void_p), ("ystd", C.c_void_p),
                 ("data_norm", C.c_void_p), ("Cinv", C.c_void_p), ("ldc", C.c_int), ("ylog", C.c_int)]
@@ -171,6 +177,13 @@ _SIGNATURES = {
     "linna_hmc_start": (_I, [_V, _I, _I, _V, _U64, _V, _V, _V, _I, _V, _I, _F, _F, _V, _I, _V, _I, _V, _I, _V, _V]),
     "linna_hmc_kick_drift": (_I, [_V, _I, _I, _V, _F, _F, _V, _I, _V, _I, _V, _I, _V]),
     "linna_hmc_accept": (_I, [_V, _I, _I, _V, _U64, _V, _V, _V, _I, _V, _I, _V, _V, _I, _V, _V, _I, _V, _V, _V, _V]),
+    "linna_hmc_start_eps": (_I, [_V, _I, _I, _V, _U64, _V, _I, _V, _V, _I, _V, _I, _V, _F, _F, _V, _I, _V, _I, _V, _I, _V, _V]),
+    "linna_hmc_kick_drift_eps": (_I, [_V, _I, _I, _V, _V, _F, _F, _V, _I, _V, _I, _V, _I, _V]),
+    "linna_logprob_grad_leapfrog_eps": (_I, [_V, _V, _I, _I, _V, _V, _V, _I, _V, _I, _V, _V, _F, _F, _V]),
+    "linna_hmc_accept_adapt": (_I, [_V, _I, _I, _V, _U64, _V, _I, _V, _V, _I, _V, _I, _V, _V, _I, _V, _V, _I, _V, _V, _V, _V,
+                                    _V, _V, _V, _V, _V, _I, _F, _V, _V, _V]),
+    "linna_hmc_run": (_I, [_V, _V, _V, _V, _V, _V, _V, _V, _I, _F, _I, _I, _I, _V, _V, _V, _V, _V]),
+    "linna_hmc_find_epsilon": (_I, [_V, _V, _V, _V, _V, _V, _V, _I, _I, _V]),
     "linna_step_increment": (_I, [_V, _V, _V]),
     "linna_slice_init": (_I, [_V, _V, _V, _I, _V, _I, _V, _I, _I, _V, _U64, _V, _I, _V, _I, _V, _V, _V, _V, _I, _V]),
     "linna_slice_points": (_I, [_V, _V, _I, _I, _V, _I, _V, _I, _V, _V, _I, _I, _V]),
@@ -189,8 +202,10 @@ class LinnaHipError(RuntimeError):
     pass
 
 
-def load():
-    """dlopen the library once; raises LinnaHipError if it is not built."""
+def load(missing_ok=False):
+    """dlopen the library once; raises LinnaHipError if it is not built.  ``missing_ok``: entries the library does not
+    export are left unbound instead of raising (an A/B against an older build of the library through LINNA_LIB_PATH,
+    tools/hmc_run_bench.py); calling one of them raises AttributeError."""
     global _lib
     if _lib is not None:
         return _lib
@@ -199,6 +214,8 @@ def load():
                             "(hipcc --offload-arch=gfx950); there is no CPU fallback" % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in _SIGNATURES.items():
+        if missing_ok and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)      # AttributeError if a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args

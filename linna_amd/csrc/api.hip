@@ -1404,8 +1404,8 @@ int linna_chain_meanstd(linna_ctx_t*, const float* CT, int ndim, int nwp, int nw
 
 // the gradient's destination and, with `leap` (hm_* of an NsGrad, the rest unset), the leapfrog's kick and drift behind it
 static NsGrad lp_grad_args(const linna_logprob_desc_t& d, float* G, int ldg, const NsGrad* leap) {
-    NsGrad g{d.gscale, G, ldg, nullptr, 0, nullptr, nullptr, 0.f, 0.f};
-    if (leap) { g.hm_p = leap->hm_p; g.hm_ldp = leap->hm_ldp; g.hm_q = leap->hm_q; g.hm_mass = leap->hm_mass; g.hm_ek = leap->hm_ek; g.hm_ed = leap->hm_ed; }
+    NsGrad g{d.gscale, G, ldg, nullptr, 0, nullptr, nullptr, 0.f, 0.f, nullptr};
+    if (leap) { g.hm_p = leap->hm_p; g.hm_ldp = leap->hm_ldp; g.hm_q = leap->hm_q; g.hm_mass = leap->hm_mass; g.hm_ek = leap->hm_ek; g.hm_ed = leap->hm_ed; g.hm_eps = leap->hm_eps; }
     return g;
 }
 // forward + dX chain down to the input in one launch on the stream copy `sc` (NS_GRAD_INPUT, or its bf16 form)
@@ -1416,11 +1416,9 @@ static int lp_launch_grad2(linna_logprob* lp, StreamCopy& sc, bool bf, const flo
     TRY(stream_copy_refresh(sc, lp->net, rows, stream, &packed, kind));
     return launch_net_stream_grad2(net_layers(lp->net, kind), packed, Z, ldz, B, lp_input(lp->d), lp_output(lp), lnP, gr, rows, S(stream), bf);
 }
-// lnP and its gradient at Z; `leap`: the leapfrog's kick and drift -- in the finish of the one-launch forms, as a launch of
-// its own behind the others
-static int logprob_grad_impl(linna_logprob_t* lp, const float* Z, int ldz, int B, void* ws, float* lnP, float* G, int ldg,
-                             const NsGrad* leap, void* stream) {
-    if (!lp || !Z || !ws || !lnP || !G || B < 1) { set_error("logprob_grad: bad arguments"); return LINNA_ERR_INVALID; }
+// whether this object has a gradient at all: what logprob_grad_impl refuses before it launches anything (the entries that
+// enqueue other launches in front of the first gradient ask first)
+static int logprob_grad_ready(const linna_logprob_t* lp) {
     if (lp->bf16() && lp->grad_precision != LINNA_PRECISION_BF16) {
         set_error("logprob_grad: this log-probability is set to bf16, which serves lnP only (no bf16 gradient); set it back to fp32");
         return LINNA_ERR_UNSUPPORTED;
@@ -1432,10 +1430,20 @@ static int logprob_grad_impl(linna_logprob_t* lp, const float* Z, int ldz, int B
             set_error("logprob_grad: this bf16 log-probability cannot run its one-launch gradient here (LINNA_DISABLE_FUSED, or no bf16 gradient stream)");
             return LINNA_ERR_UNSUPPORTED;
         }
-        return lp_launch_grad2(lp, lp->packed_gbf, true, Z, ldz, B, lnP, lp_grad_args(d, G, ldg, leap), stream);
+        return LINNA_OK;
     }
     if (d.outmap.cexp) { set_error("logprob_grad: ypositive (exp) output map has no gradient path"); return LINNA_ERR_UNSUPPORTED; }
     if (!d.gscale || (!d.w && !d.Ssym)) { set_error("logprob_grad: descriptor lacks gscale / Ssym"); return LINNA_ERR_INVALID; }
+    return LINNA_OK;
+}
+// lnP and its gradient at Z; `leap`: the leapfrog's kick and drift -- in the finish of the one-launch forms, as a launch of
+// its own behind the others
+static int logprob_grad_impl(linna_logprob_t* lp, const float* Z, int ldz, int B, void* ws, float* lnP, float* G, int ldg,
+                             const NsGrad* leap, void* stream) {
+    if (!lp || !Z || !ws || !lnP || !G || B < 1) { set_error("logprob_grad: bad arguments"); return LINNA_ERR_INVALID; }
+    TRY(logprob_grad_ready(lp));
+    const linna_logprob_desc_t& d = lp->d;
+    if (lp->bf16()) return lp_launch_grad2(lp, lp->packed_gbf, true, Z, ldz, B, lnP, lp_grad_args(d, G, ldg, leap), stream);
     const NsGrad gr = lp_grad_args(d, G, ldg, leap);
     if (lp->fused_on && lp->packed.ready() && lp->grad_fused && d.w) {
         // lnP and d lnP / d z in ONE launch: forward segments, turnaround, backward segments over W^T (net_stream.hip)
@@ -1462,7 +1470,7 @@ static int logprob_grad_impl(linna_logprob_t* lp, const float* Z, int ldz, int B
     }
     TRY(linna_net_backward(lp->net, w + L.x0, ldx, B, w + L.fwd, w + L.bwd, w + L.dh, ldd, w + L.dx, ldx, 0, stream));
     TRY(launch_prior_map_bwd(Z, ldz, B, d.nin, d.is_flat, d.a1, d.a2, d.log10_flag, d.xstd, w + L.dx, ldx, G, ldg, S(stream)));
-    if (leap) return launch_hmc_kick_drift(B, d.nin, leap->hm_mass, leap->hm_ek, leap->hm_ed, G, ldg, leap->hm_p, leap->hm_ldp, leap->hm_q, ldz, S(stream));
+    if (leap) return launch_hmc_kick_drift(B, d.nin, leap->hm_mass, leap->hm_ek, leap->hm_ed, G, ldg, leap->hm_p, leap->hm_ldp, leap->hm_q, ldz, S(stream), leap->hm_eps);
     return LINNA_OK;
 }
 
@@ -1478,8 +1486,74 @@ int linna_logprob_grad(linna_logprob_t* lp, const float* Z, int ldz, int B, void
 int linna_logprob_grad_leapfrog(linna_logprob_t* lp, float* Q, int ldq, int B, void* ws, float* lnP, float* G, int ldg, float* P,
                                 int ldp, const float* mass, float eps_kick, float eps_drift, void* stream) try {
     if (!P || !mass || !Q) { set_error("logprob_grad_leapfrog: bad arguments"); return LINNA_ERR_INVALID; }
-    NsGrad leap{nullptr, nullptr, 0, P, ldp, Q, mass, eps_kick, eps_drift};
+    NsGrad leap{nullptr, nullptr, 0, P, ldp, Q, mass, eps_kick, eps_drift, nullptr};
     return logprob_grad_impl(lp, Q, ldq, B, ws, lnP, G, ldg, &leap, stream);
+} LINNA_CATCH_INT
+
+int linna_logprob_grad_leapfrog_eps(linna_logprob_t* lp, float* Q, int ldq, int B, void* ws, float* lnP, float* G, int ldg, float* P,
+                                    int ldp, const float* mass, const float* EPS, float mul_kick, float mul_drift, void* stream) try {
+    if (!P || !mass || !Q || !EPS) { set_error("logprob_grad_leapfrog_eps: bad arguments"); return LINNA_ERR_INVALID; }
+    NsGrad leap{nullptr, nullptr, 0, P, ldp, Q, mass, mul_kick, mul_drift, EPS};
+    return logprob_grad_impl(lp, Q, ldq, B, ws, lnP, G, ldg, &leap, stream);
+} LINNA_CATCH_INT
+
+// ---- whole HMC transitions per call (linna_hip.h)
+static bool hmc_state_ok(const linna_hmc_state_t* st) {
+    return st && st->B >= 1 && st->ld >= 1 && st->X && st->lnp && st->G && st->P && st->Q && st->lnp_new && st->Gnew && st->H0 &&
+           st->mass && st->step_dev;
+}
+// one trajectory from st->X with the momenta hmc_start draws (P0 == nullptr) or is given: start, num_steps gradient launches
+static int hmc_trajectory(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, const float* P0, const float* EPS, int step_off,
+                          int num_steps, void* stream) {
+    const int B = st->B, nd = lp->d.nin, ld = st->ld;
+    TRY(launch_hmc_start(B, nd, st->mass, st->seed, st->step_dev, st->lnp, P0, ld, st->G, ld, 0.5f, 1.f, st->X, ld, st->P, ld, st->Q, ld,
+                         st->H0, S(stream), EPS, step_off));
+    for (int i = 0; i < num_steps; ++i) {
+        const bool last = i == num_steps - 1;                                      // a half kick behind the last step, no drift
+        NsGrad leap{nullptr, nullptr, 0, st->P, ld, st->Q, st->mass, last ? 0.5f : 1.f, last ? 0.f : 1.f, EPS};
+        TRY(logprob_grad_impl(lp, st->Q, ld, B, ws, st->lnp_new, st->Gnew, ld, &leap, stream));
+    }
+    return LINNA_OK;
+}
+
+int linna_hmc_run(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, float* EPS, float* EPSBAR, float* HBAR, const float* MU,
+                  int* M, int Madapt, float delta, int step_offset, int num_steps, int ntrans, int* naccept, float* alpha,
+                  float* chain, float* logps, void* stream) try {
+    if (!lp || !st || !ws || !EPS || num_steps < 1 || ntrans < 1 || Madapt < 0 || (chain != nullptr) != (logps != nullptr)) {
+        set_error("hmc_run: bad arguments"); return LINNA_ERR_INVALID;
+    }
+    CHECK_STRUCT(st, linna_hmc_state_t, "hmc_run");
+    if (!hmc_state_ok(st)) { set_error("hmc_run: incomplete state"); return LINNA_ERR_INVALID; }
+    if (st->ld < lp->d.nin) { set_error("hmc_run: ld %d < %d parameters", st->ld, lp->d.nin); return LINNA_ERR_INVALID; }
+    if (Madapt > 0 && (!EPSBAR || !HBAR || !MU || !M)) { set_error("hmc_run: Madapt > 0 needs the adaptation state"); return LINNA_ERR_INVALID; }
+    TRY(logprob_grad_ready(lp));
+    const int B = st->B, nd = lp->d.nin, ld = st->ld;
+    const HmcAdapt ad{EPS, EPSBAR, HBAR, MU, M, Madapt, delta};
+    for (int i = 0; i < ntrans; ++i) {
+        TRY(hmc_trajectory(lp, st, ws, nullptr, EPS, step_offset + i, num_steps, stream));
+        TRY(launch_hmc_accept_adapt(B, nd, st->mass, st->seed, st->step_dev, step_offset + i, st->H0, st->P, ld, st->Q, ld, st->lnp_new,
+                                    st->Gnew, ld, nullptr, st->X, ld, st->lnp, st->G, naccept, alpha, ad,
+                                    chain ? chain + (size_t)i * B * nd : nullptr, logps ? logps + (size_t)i * B : nullptr, S(stream)));
+    }
+    return LINNA_OK;
+} LINNA_CATCH_INT
+
+int linna_hmc_find_epsilon(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, float* R0, float* EPS, int* state, int* nactive,
+                           int step_offset, int max_rounds, void* stream) try {
+    if (!lp || !st || !ws || !R0 || !EPS || !state || !nactive || max_rounds < 1) { set_error("hmc_find_epsilon: bad arguments"); return LINNA_ERR_INVALID; }
+    CHECK_STRUCT(st, linna_hmc_state_t, "hmc_find_epsilon");
+    if (!hmc_state_ok(st)) { set_error("hmc_find_epsilon: incomplete state"); return LINNA_ERR_INVALID; }
+    if (st->ld < lp->d.nin) { set_error("hmc_find_epsilon: ld %d < %d parameters", st->ld, lp->d.nin); return LINNA_ERR_INVALID; }
+    TRY(logprob_grad_ready(lp));
+    const int B = st->B, nd = lp->d.nin, ld = st->ld;
+    TRY(check_hip(hipMemsetAsync(nactive, 0, sizeof(int), S(stream)), "hipMemsetAsync"));
+    TRY(launch_hmc_find_eps_init(B, nd, st->seed, st->step_dev, step_offset, R0, ld, EPS, state, S(stream)));
+    for (int r = 0; r < max_rounds; ++r) {
+        TRY(hmc_trajectory(lp, st, ws, R0, EPS, step_offset, 1, stream));
+        TRY(launch_hmc_find_eps(B, nd, st->mass, st->H0, st->P, ld, st->lnp_new, st->Gnew, ld, EPS, state,
+                                r + 1 == max_rounds ? nactive : nullptr, S(stream)));
+    }
+    return LINNA_OK;
 } LINNA_CATCH_INT
 
 // ------------------------------------------------------------------ training
@@ -1694,6 +1768,31 @@ int linna_hmc_start(linna_ctx_t*, int B, int ndim, const float* mass, uint64_t s
 int linna_hmc_kick_drift(linna_ctx_t*, int B, int ndim, const float* mass, float ek, float ed, const float* G, int ldg,
                          float* P, int ldp, float* Q, int ldq, void* stream) try {
     return launch_hmc_kick_drift(B, ndim, mass, ek, ed, G, ldg, P, ldp, Q, ldq, S(stream));
+} LINNA_CATCH_INT
+int linna_hmc_start_eps(linna_ctx_t*, int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, int step_offset,
+                        const float* lnp, const float* P0, int ldp0, const float* G, int ldg, const float* EPS, float mul_kick,
+                        float mul_drift, const float* X, int ldx, float* P, int ldp, float* Q, int ldq, float* H0, void* stream) try {
+    if (B < 1 || ndim < 1 || !mass || !step_dev || !lnp || !G || !EPS || !X || !P || !Q || !H0) { set_error("hmc_start_eps: bad arguments"); return LINNA_ERR_INVALID; }
+    return launch_hmc_start(B, ndim, mass, seed, step_dev, lnp, P0, ldp0, G, ldg, mul_kick, mul_drift, X, ldx, P, ldp, Q, ldq, H0, S(stream),
+                            EPS, step_offset);
+} LINNA_CATCH_INT
+int linna_hmc_kick_drift_eps(linna_ctx_t*, int B, int ndim, const float* mass, const float* EPS, float mul_kick, float mul_drift,
+                             const float* G, int ldg, float* P, int ldp, float* Q, int ldq, void* stream) try {
+    if (B < 1 || ndim < 1 || !mass || !EPS || !G || !P || !Q) { set_error("hmc_kick_drift_eps: bad arguments"); return LINNA_ERR_INVALID; }
+    return launch_hmc_kick_drift(B, ndim, mass, mul_kick, mul_drift, G, ldg, P, ldp, Q, ldq, S(stream), EPS);
+} LINNA_CATCH_INT
+int linna_hmc_accept_adapt(linna_ctx_t*, int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, int step_offset,
+                           const float* H0, const float* P, int ldp, const float* Qn, int ldq, const float* lnp_new, const float* Gn,
+                           int ldg, const float* U, float* X, int ldx, float* lnp, float* G, int* naccept, float* alpha, float* EPS,
+                           float* EPSBAR, float* HBAR, const float* MU, int* M, int Madapt, float delta, float* chain, float* logps,
+                           void* stream) try {
+    if (B < 1 || ndim < 1 || !mass || !step_dev || !H0 || !P || !Qn || !lnp_new || !Gn || !X || !lnp || !G || Madapt < 0 ||
+        (Madapt > 0 && (!EPS || !EPSBAR || !HBAR || !MU || !M))) {
+        set_error("hmc_accept_adapt: bad arguments"); return LINNA_ERR_INVALID;
+    }
+    const HmcAdapt ad{EPS, EPSBAR, HBAR, MU, M, Madapt, delta};
+    return launch_hmc_accept_adapt(B, ndim, mass, seed, step_dev, step_offset, H0, P, ldp, Qn, ldq, lnp_new, Gn, ldg, U, X, ldx, lnp, G,
+                                   naccept, alpha, ad, chain, logps, S(stream));
 } LINNA_CATCH_INT
 int linna_hmc_accept(linna_ctx_t*, int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, const float* H0,
                      const float* P, int ldp, const float* Qn, int ldq, const float* lnp_new, const float* Gn, int ldg,

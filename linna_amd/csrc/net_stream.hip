@@ -122,6 +122,7 @@ struct NsArgs {
     unsigned long long sl_seed; const int* sl_step; int sl_stream; const int* sl_flags;
     SliceBegin sb;                      // MOVE == 2, sb.logp != null: the half step's set-up in this launch's prologue (common.h)
     NsSeg seg[NS_MAXSEG];
+    const float* hm_eps;                // GRAD: the leapfrog in the finish with a step size per row (the EPS instantiations: hm_ek, hm_ed then multiply it)
 };
 
 // ------------------------------------------------------------------ weight re-layout
@@ -315,11 +316,23 @@ __device__ __forceinline__ float ns_prior_theta(float z, int flat, float a1, flo
 // instructions for every existing instantiation.)
 template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF = false>
 __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_kernel(NsArgs a) {
+    constexpr bool EPS = false;
+#include "net_stream_body.inc"
+}
+// EPS: the fp32 gradient programs (GRAD, STORE 0 or 2) whose finish runs the leapfrog with a step size per row, a.hm_eps
+// (linna_logprob_grad_leapfrog_eps).  Kernels of their own, here and for the bf16 gradient below: a run-time test of the
+// pointer in the shared finish slowed the launches without one (net_stream_body.inc), and the instantiations
+// above keep their names.
+template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF>
+__global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_eps_kernel(NsArgs a) {
+    static_assert(!BF && GRAD && (STORE == 0 || STORE == 2) && MOVE == 0, "the fp32 one-launch gradients only");
+    constexpr bool EPS = true;
 #include "net_stream_body.inc"
 }
 template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF>
 __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_train_bf16_kernel(NsArgs a) {
     static_assert(BF && GRAD && STORE == 3 && ROWS == 4 && MOVE == 0, "the bf16 training step only");
+    constexpr bool EPS = false;
 #include "net_stream_body.inc"
 }
 // BF + MOVE == 2: the ensemble slice move's evaluation on the bf16 serving engine (linna_slice_half_step,
@@ -330,6 +343,7 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_train_bf16_kernel(Ns
 template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF>
 __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_slice_bf16_kernel(NsArgs a) {
     static_assert(BF && !GRAD && STORE == 0 && MOVE == 2, "the bf16 slice evaluation only");
+    constexpr bool EPS = false;
 #define NS_BODY_SLICE_BF16
 #include "net_stream_body.inc"
 #undef NS_BODY_SLICE_BF16
@@ -344,6 +358,15 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_slice_bf16_kernel(Ns
 template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF>
 __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_grad_bf16_kernel(NsArgs a) {
     static_assert(BF && GRAD && STORE == 2 && MOVE == 0, "the bf16 one-launch gradient only");
+    constexpr bool EPS = false;
+#define NS_BODY_GRAD_BF16
+#include "net_stream_body.inc"
+#undef NS_BODY_GRAD_BF16
+}
+template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF>
+__global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_eps_bf16_kernel(NsArgs a) {      // ... with a step size per row (EPS)
+    static_assert(BF && GRAD && STORE == 2 && MOVE == 0, "the bf16 one-launch gradient only");
+    constexpr bool EPS = true;
 #define NS_BODY_GRAD_BF16
 #include "net_stream_body.inc"
 #undef NS_BODY_GRAD_BF16
@@ -409,11 +432,12 @@ static int ns_launch(const NsArgs& a, int nblocks, size_t lds_bytes, hipStream_t
     hipLaunchKernelGGL(Kernel, dim3(nblocks), dim3(64 * NS_NW), lds_bytes, s, a);
     return check_hip(hipGetLastError(), what);
 }
-template <int MOVE, bool GRAD, int STORE, int ROWS, bool BF = false>
+template <int MOVE, bool GRAD, int STORE, int ROWS, bool BF = false, bool EPS = false>
 static int ns_launch_rows(const NsArgs& a, int B, size_t lds_bytes, hipStream_t s, int extra = 0) {
-    return ns_launch<net_stream_kernel<NS_R, MOVE, GRAD, STORE, ROWS, BF>>(a, (B + ROWS - 1) / ROWS + extra, lds_bytes, s, "net_stream launch");
+    if constexpr (EPS) return ns_launch<net_stream_eps_kernel<NS_R, MOVE, GRAD, STORE, ROWS, BF>>(a, (B + ROWS - 1) / ROWS + extra, lds_bytes, s, "net_stream launch");
+    else return ns_launch<net_stream_kernel<NS_R, MOVE, GRAD, STORE, ROWS, BF>>(a, (B + ROWS - 1) / ROWS + extra, lds_bytes, s, "net_stream launch");
 }
-template <int MOVE, bool GRAD, int STORE = 0, bool BF = false>
+template <int MOVE, bool GRAD, int STORE = 0, bool BF = false, bool EPS = false>
 static int ns_launch_kernel(const NsArgs& a0, int B, const NsProgram& p, int rows, hipStream_t s, int extra = 0, size_t lds_extra = 0) {
     const size_t lds = p.lds_for(rows, GRAD) + lds_extra;
 #ifdef NS_STAMPS
@@ -424,16 +448,16 @@ static int ns_launch_kernel(const NsArgs& a0, int B, const NsProgram& p, int row
 #else
     const NsArgs& a = a0;
 #endif
-    if (rows == 4) return ns_launch_rows<MOVE, GRAD, STORE, 4, BF>(a, B, lds, s, extra);
+    if (rows == 4) return ns_launch_rows<MOVE, GRAD, STORE, 4, BF, EPS>(a, B, lds, s, extra);
     if constexpr (BF) {
-        if (rows == 8) return ns_launch_rows<MOVE, GRAD, STORE, 8, BF>(a, B, lds, s, extra);
-        if (rows == 16) return ns_launch_rows<MOVE, GRAD, STORE, 16, BF>(a, B, lds, s, extra);
+        if (rows == 8) return ns_launch_rows<MOVE, GRAD, STORE, 8, BF, EPS>(a, B, lds, s, extra);
+        if (rows == 16) return ns_launch_rows<MOVE, GRAD, STORE, 16, BF, EPS>(a, B, lds, s, extra);
     } else if constexpr (STORE == 3 && GRAD) {
         // the one-launch training step exists for the 4-row engine only (batches up to 1024 rows; the caller checks): on the
         // 8-row engine it was measured SLOWER than its two halves (batch 1500 at (26,457): 218.5 against 210.9 us per step)
     } else {
-        if (rows == 8) return ns_launch_rows<MOVE, GRAD, STORE, 8>(a, B, lds, s, extra);
-        if (rows == 16) return ns_launch_rows<MOVE, GRAD, STORE, 16>(a, B, lds, s, extra);
+        if (rows == 8) return ns_launch_rows<MOVE, GRAD, STORE, 8, false, EPS>(a, B, lds, s, extra);
+        if (rows == 16) return ns_launch_rows<MOVE, GRAD, STORE, 16, false, EPS>(a, B, lds, s, extra);
     }
     set_error("net_stream: %d rows per workgroup", rows);
     return LINNA_ERR_INVALID;
@@ -617,6 +641,7 @@ static void ns_set_input(NsArgs& a, const NsInput& in) {
 static void ns_set_grad(NsArgs& a, const NsGrad& gr) {
     a.gscale = gr.gscale; a.Gout = gr.G; a.ldg = gr.ldg;
     a.hm_p = gr.hm_p; a.hm_ldp = gr.hm_ldp; a.hm_q = gr.hm_q; a.hm_mass = gr.hm_mass; a.hm_ek = gr.hm_ek; a.hm_ed = gr.hm_ed;
+    a.hm_eps = gr.hm_eps;
 }
 
 int launch_net_stream(NsKind kind, const NsNet& net, const float* packed, const float* Z, int ldz, int B, const NsInput& in,
@@ -661,6 +686,7 @@ int launch_net_stream(NsKind kind, const NsNet& net, const float* packed, const 
     if (bf) return ns_launch_kernel<0, false, 0, true>(a, B, p, rows, s);
     if (gr) {
         ns_set_grad(a, *gr);
+        if (a.hm_p && a.hm_eps) return ns_launch_kernel<0, true, 0, false, true>(a, B, p, rows, s);
         return ns_launch_kernel<0, true>(a, B, p, rows, s);
     }
     return ns_launch_kernel<0, false>(a, B, p, rows, s);
@@ -711,12 +737,18 @@ int launch_net_stream_grad2(const NsNet& net, const float* packed, const float* 
 #endif
         const size_t lds = p.lds_for(rows, true) + lds_extra;
         const char* const what = "net_stream bf16 gradient launch";
+        if (a.hm_p && a.hm_eps) {
+            if (rows == 4) return ns_launch<net_stream_eps_bf16_kernel<NS_R, 0, true, 2, 4, true>>(a, (B + 3) / 4, lds, s, what);
+            if (rows == 8) return ns_launch<net_stream_eps_bf16_kernel<NS_R, 0, true, 2, 8, true>>(a, (B + 7) / 8, lds, s, what);
+            if (rows == 16) return ns_launch<net_stream_eps_bf16_kernel<NS_R, 0, true, 2, 16, true>>(a, (B + 15) / 16, lds, s, what);
+        }
         if (rows == 4) return ns_launch<net_stream_grad_bf16_kernel<NS_R, 0, true, 2, 4, true>>(a, (B + 3) / 4, lds, s, what);
         if (rows == 8) return ns_launch<net_stream_grad_bf16_kernel<NS_R, 0, true, 2, 8, true>>(a, (B + 7) / 8, lds, s, what);
         if (rows == 16) return ns_launch<net_stream_grad_bf16_kernel<NS_R, 0, true, 2, 16, true>>(a, (B + 15) / 16, lds, s, what);
         set_error("net_stream: %d rows per workgroup", rows);
         return LINNA_ERR_INVALID;
     }
+    if (a.hm_p && a.hm_eps) return ns_launch_kernel<0, true, 2, false, true>(a, B, p, rows, s, 0, lds_extra);
     return ns_launch_kernel<0, true, 2>(a, B, p, rows, s, 0, lds_extra);
 }
 

@@ -1180,6 +1180,11 @@
         const float* const F = act + P * ABUF + pr * LD;
         const bool rok = prow && row0 + pr < a.B;
         if (rok) {
+            // the leapfrog's step sizes: the launch's own, or -- EPS, an instantiation of its own -- the multipliers of this
+            // row's (a chain's adapted step size).  A run-time test of a.hm_eps here cost the launches WITHOUT one 0.3-0.5 us:
+            // its argument loads were hoisted into a prologue that has no scalar register left (DESIGN 3.10).
+            float hm_ek = a.hm_ek, hm_ed = a.hm_ed;
+            if constexpr (EPS) { const float e = a.hm_eps[row0 + pr]; hm_ek *= e; hm_ed *= e; }
 #pragma unroll
             for (int j = 0; j < ZPRE; ++j) {
                 const int c = pc0 + j * RG;
@@ -1195,8 +1200,8 @@
                         // arithmetic: the launch between two gradient evaluations it replaces was 4.5 us of nothing)
                         float* const pp = a.hm_p + (size_t)(row0 + pr) * a.hm_ldp + c;
                         float pm = *pp;
-                        if (a.hm_ek != 0.f) { pm += a.hm_ek * gz; *pp = pm; }
-                        if (a.hm_ed != 0.f) a.hm_q[(size_t)(row0 + pr) * a.ldz + c] = z + a.hm_ed * (pm / a.hm_mass[c]);
+                        if (a.hm_ek != 0.f) { pm += hm_ek * gz; *pp = pm; }
+                        if (a.hm_ed != 0.f) a.hm_q[(size_t)(row0 + pr) * a.ldz + c] = z + hm_ed * (pm / a.hm_mass[c]);
                     }
                 }
             }

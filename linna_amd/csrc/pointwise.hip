@@ -453,27 +453,30 @@ __device__ __forceinline__ float wave_ordered_sum(float t, int n) {
 }
 
 // P ~ N(0, m), H0 = P^2 / 2m - lnP; G != nullptr: also the first half kick and the first drift of the leapfrog,
-// P += ek G, Q = X + ed P / m (hmc_kick_drift_kernel's arithmetic)
+// P += ek G, Q = X + ed P / m (hmc_kick_drift_kernel's arithmetic).  eps != nullptr: a step size per chain, ek and ed are
+// its multipliers (1, 0.5 or 0); the Philox step is step_dev[0] + step_off.
 __global__ void hmc_start_kernel(int B, int ndim, const float* __restrict__ mass, uint64_t seed,
                                  const int* __restrict__ step_dev, const float* __restrict__ lnp,
                                  const float* __restrict__ P0, int ldp0, const float* __restrict__ G, int ldg, float ek, float ed,
                                  const float* __restrict__ X, int ldx, float* __restrict__ P, int ldp, float* __restrict__ Q,
-                                 int ldq, float* __restrict__ H0) {
+                                 int ldq, float* __restrict__ H0, const float* __restrict__ eps, int step_off) {
     const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (b >= B) return;
+    const bool kick = ek != 0.f, drift = ed != 0.f;
+    if (eps) { const float e = eps[b]; ek *= e; ed *= e; }
     float ke = 0.f;
     for (int d0 = 0; d0 < ndim; d0 += 64) {
         const int d = d0 + lane;
         float t = 0.f;
         if (d < ndim) {
             const float m = mass[d];
-            const float n01 = P0 ? P0[(size_t)b * ldp0 + d] : normal_draw(seed, (uint32_t)b, (uint32_t)step_dev[0], 1u, d);
+            const float n01 = P0 ? P0[(size_t)b * ldp0 + d] : normal_draw(seed, (uint32_t)b, (uint32_t)(step_dev[0] + step_off), 1u, d);
             float p = n01 * sqrtf(m);
             t = p * p / m;
             if (G) {
-                if (ek != 0.f) p += ek * G[(size_t)b * ldg + d];
+                if (kick) p += ek * G[(size_t)b * ldg + d];
                 const float x = X[(size_t)b * ldx + d];
-                Q[(size_t)b * ldq + d] = ed != 0.f ? x + ed * (p / m) : x;
+                Q[(size_t)b * ldq + d] = drift ? x + ed * (p / m) : x;
             }
             P[(size_t)b * ldp + d] = p;
         }
@@ -482,16 +485,18 @@ __global__ void hmc_start_kernel(int B, int ndim, const float* __restrict__ mass
     if (lane == 0) H0[b] = 0.5f * ke - lnp[b];
 }
 
-// P += eps_kick * G ; Q += eps_drift * P / m   (either eps may be 0)
+// P += eps_kick * G ; Q += eps_drift * P / m   (either eps may be 0); eps != nullptr: eps_kick = ek eps[b], eps_drift = ed eps[b]
 __global__ void hmc_kick_drift_kernel(int B, int ndim, const float* __restrict__ mass, float ek, float ed,
                                       const float* __restrict__ G, int ldg, float* __restrict__ P, int ldp,
-                                      float* __restrict__ Q, int ldq) {
+                                      float* __restrict__ Q, int ldq, const float* __restrict__ eps) {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (size_t)B * ndim) return;
     const int b = (int)(idx / ndim), d = (int)(idx % ndim);
+    const bool kick = ek != 0.f, drift = ed != 0.f;
+    if (eps) { const float e = eps[b]; ek *= e; ed *= e; }
     float p = P[(size_t)b * ldp + d];
-    if (ek != 0.f) { p += ek * G[(size_t)b * ldg + d]; P[(size_t)b * ldp + d] = p; }
-    if (ed != 0.f) Q[(size_t)b * ldq + d] += ed * (p / mass[d]);
+    if (kick) { p += ek * G[(size_t)b * ldg + d]; P[(size_t)b * ldp + d] = p; }
+    if (drift) Q[(size_t)b * ldq + d] += ed * (p / mass[d]);
 }
 
 __global__ void hmc_accept_kernel(int B, int ndim, const float* __restrict__ mass, uint64_t seed,
@@ -526,6 +531,132 @@ __global__ void hmc_accept_kernel(int B, int ndim, const float* __restrict__ mas
             if (naccept) atomicAdd(naccept + b, 1);
         }
     }
+}
+
+// hmc_accept_kernel's Metropolis test (the same arithmetic, the same decisions) at Philox step step_dev[0] + step_off, and
+// behind it what a run of transitions enqueued in one go needs from the host otherwise:
+//  * alpha[b] = exp(min(H0 - H1, 0)), 0 where lnp_new or an energy is not finite;
+//  * chain / logps != nullptr: the chain's row and log-probability after the test, to chain[b][ndim] / logps[b];
+//  * ad.m != nullptr: m += 1, and for ad.Madapt > 0 the dual averaging of the step size per chain (Hoffman & Gelman 2014,
+//    algorithm 5, as the reference's NUTSMove runs it at sampler.py:229-240 with nalpha = 1): while m <= Madapt
+//      Hbar = (1 - 1/(m + t0)) Hbar + (delta - alpha) / (m + t0);  eps = exp(mu - sqrt(m) / gamma Hbar);
+//      epsbar = exp((1 - m^-kappa) log epsbar + m^-kappa log eps),
+//    at m == Madapt + 1 eps = epsbar, later nothing.  This launch follows every leapfrog launch of its transition: eps[b]
+//    has no reader left.
+__global__ void hmc_accept_adapt_kernel(int B, int ndim, const float* __restrict__ mass, uint64_t seed,
+                                        const int* __restrict__ step_dev, int step_off, const float* __restrict__ H0,
+                                        const float* __restrict__ P, int ldp, const float* __restrict__ Qn, int ldq,
+                                        const float* __restrict__ lnp_new, const float* __restrict__ Gn, int ldg,
+                                        const float* __restrict__ U,
+                                        float* __restrict__ X, int ldx, float* __restrict__ lnp, float* __restrict__ G,
+                                        int* __restrict__ naccept, float* __restrict__ alpha, HmcAdapt ad,
+                                        float* __restrict__ chain, float* __restrict__ logps) {
+    const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;   // a wave per chain
+    if (b >= B) return;
+    float ke = 0.f;
+    for (int d0 = 0; d0 < ndim; d0 += 64) {
+        const int d = d0 + lane;
+        float t = 0.f;
+        if (d < ndim) { const float p = P[(size_t)b * ldp + d]; t = p * p / mass[d]; }
+        ke += wave_ordered_sum(t, min(64, ndim - d0));
+    }
+    const float ln = lnp_new[b];
+    const float H1 = 0.5f * ke - ln;
+    const U4 r = walker_bits(seed, (uint32_t)b, (uint32_t)(step_dev[0] + step_off), 2u, 0u);
+    const float dH = H0[b] - H1;
+    const float ratio = expf(dH > 0.f ? 0.f : dH);   // a NaN energy stays NaN and rejects (np.minimum; fminf would return 0)
+    const float u = U ? U[b] : u01(r.x);
+    const bool acc = isfinite(ln) && u < ratio;
+    for (int d = lane; d < ndim; d += 64) {
+        float x = 0.f;
+        if (acc) {
+            x = Qn[(size_t)b * ldq + d];
+            X[(size_t)b * ldx + d] = x;
+            G[(size_t)b * ldg + d] = Gn[(size_t)b * ldg + d];
+        } else if (chain) x = X[(size_t)b * ldx + d];
+        if (chain) chain[(size_t)b * ndim + d] = x;
+    }
+    if (lane != 0) return;
+    if (acc) {
+        lnp[b] = ln;
+        if (naccept) atomicAdd(naccept + b, 1);
+    }
+    if (logps) logps[b] = acc ? ln : lnp[b];
+    const float al = isfinite(ln) && isfinite(dH) ? ratio : 0.f;
+    if (alpha) alpha[b] = al;
+    if (!ad.m) return;
+    const int m = ad.m[b];
+    ad.m[b] = m + 1;
+    if (ad.Madapt <= 0) return;
+    if (m <= ad.Madapt) {
+        const float fm = (float)m, sm = sqrtf(fm);
+        float eta = 1.f / (fm + 10.f);                                  // t0 = 10
+        const float Hb = (1.f - eta) * ad.Hbar[b] + eta * (ad.delta - al);
+        const float e = expf(ad.mu[b] - sm / 0.05f * Hb);               // gamma = 0.05
+        eta = 1.f / (sm * sqrtf(sm));                                   // m^-kappa, kappa = 0.75
+        ad.Hbar[b] = Hb;
+        ad.eps[b] = e;
+        ad.epsbar[b] = expf((1.f - eta) * logf(ad.epsbar[b]) + eta * logf(e));
+    } else if (m == ad.Madapt + 1) {
+        ad.eps[b] = ad.epsbar[b];
+    }
+}
+
+// find_reasonable_epsilon of the reference (sampler.py:151-184), every chain at once and in a bounded number of rounds.
+// A chain's state: 0 = still halving eps from 1 until the one-step leapfrog gives a finite lnP' and gradient; +1 / -1 = the
+// direction a in which eps doubles / halves while a logaccept > -a log 2; 2 = finished (nothing of it changes any more).
+// The set-up: eps = 1, state 0, and the ONE momentum draw r0 ~ N(0, 1) every trial of the chain uses (Philox stream 3).
+__global__ void hmc_find_eps_init_kernel(int B, int ndim, uint64_t seed, const int* __restrict__ step_dev, int step_off,
+                                         float* __restrict__ R0, int ldr, float* __restrict__ eps, int* __restrict__ state) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (size_t)B * ndim) return;
+    const int b = (int)(idx / ndim), d = (int)(idx % ndim);
+    R0[(size_t)b * ldr + d] = normal_draw(seed, (uint32_t)b, (uint32_t)(step_dev[0] + step_off), 3u, d);
+    if (d == 0) { eps[b] = 1.f; state[b] = 0; }
+}
+// One round: the trial of every chain was hmc_start_kernel with P0 = r0, a half kick and a drift of eps[b], then the
+// gradient at Q with the closing half kick -- H0, P, lnp_new, Gn are what they left.  logaccept = H0 - H1 (sampler.py:172).
+// A comparison with a NaN is false, as in numpy: such a chain stops where it is.  nactive != nullptr (the last round):
+// += the chains this round leaves unfinished.
+__global__ void hmc_find_eps_kernel(int B, int ndim, const float* __restrict__ mass, const float* __restrict__ H0,
+                                    const float* __restrict__ P, int ldp, const float* __restrict__ lnp_new,
+                                    const float* __restrict__ Gn, int ldg, float* __restrict__ eps, int* __restrict__ state,
+                                    int* __restrict__ nactive) {
+    const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;   // a wave per chain
+    if (b >= B) return;
+    int st = state[b];
+    if (st == 2) return;
+    float ke = 0.f;
+    int bad = 0;
+    for (int d0 = 0; d0 < ndim; d0 += 64) {
+        const int d = d0 + lane;
+        float t = 0.f;
+        if (d < ndim) {
+            const float p = P[(size_t)b * ldp + d];
+            t = p * p / mass[d];
+            bad |= !isfinite(Gn[(size_t)b * ldg + d]);
+        }
+        ke += wave_ordered_sum(t, min(64, ndim - d0));
+    }
+    const float ln = lnp_new[b];
+    bad = __any(bad) || !isfinite(ln);
+    if (lane != 0) return;
+    const float la = H0[b] - (0.5f * ke - ln);
+    const float LN2 = 0.693147180559945f;
+    float e = eps[b];
+    if (st == 0) {
+        if (bad) e *= 0.5f;                                   // k *= 0.5 (:165)
+        else {
+            e *= 0.5f;                                        // epsilon = 0.5 k epsilon (:168)
+            st = la > -LN2 ? 1 : -1;                          // (:173)
+            if ((float)st * la > -(float)st * LN2) e = st > 0 ? e * 2.f : e * 0.5f;   // the loop's first pass rests on this trial (:176)
+            else st = 2;
+        }
+    } else if ((float)st * la > -(float)st * LN2) e = st > 0 ? e * 2.f : e * 0.5f;
+    else st = 2;
+    eps[b] = e;
+    state[b] = st;
+    if (nactive && st != 2) atomicAdd(nactive, 1);
 }
 
 __global__ void step_increment_kernel(int* step) { step[0] += 1; }
@@ -897,21 +1028,42 @@ int launch_stretch_accept(float* coords, int ldc, int ndim, float* logp, const i
 int launch_hmc_init(int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, const float* lnp,
                     const float* P0, int ldp0, float* P, int ldp, float* H0, hipStream_t s) {
     hipLaunchKernelGGL(hmc_start_kernel, dim3((B + 3) / 4), dim3(256), 0, s, B, ndim, mass, seed, step_dev, lnp, P0, ldp0,
-                       (const float*)nullptr, 0, 0.f, 0.f, (const float*)nullptr, 0, P, ldp, (float*)nullptr, 0, H0);
+                       (const float*)nullptr, 0, 0.f, 0.f, (const float*)nullptr, 0, P, ldp, (float*)nullptr, 0, H0,
+                       (const float*)nullptr, 0);
     LAUNCH_CHECK("hmc_init");
 }
 int launch_hmc_start(int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, const float* lnp, const float* P0,
                      int ldp0, const float* G, int ldg, float ek, float ed, const float* X, int ldx, float* P, int ldp, float* Q,
-                     int ldq, float* H0, hipStream_t s) {
+                     int ldq, float* H0, hipStream_t s, const float* eps, int step_off) {
     hipLaunchKernelGGL(hmc_start_kernel, dim3((B + 3) / 4), dim3(256), 0, s, B, ndim, mass, seed, step_dev, lnp, P0, ldp0, G, ldg, ek,
-                       ed, X, ldx, P, ldp, Q, ldq, H0);
+                       ed, X, ldx, P, ldp, Q, ldq, H0, eps, step_off);
     LAUNCH_CHECK("hmc_start");
 }
 int launch_hmc_kick_drift(int B, int ndim, const float* mass, float ek, float ed, const float* G, int ldg, float* P,
-                          int ldp, float* Q, int ldq, hipStream_t s) {
+                          int ldp, float* Q, int ldq, hipStream_t s, const float* eps) {
     hipLaunchKernelGGL(hmc_kick_drift_kernel, grid1d((size_t)B * ndim, 256), dim3(256), 0, s, B, ndim, mass, ek, ed, G,
-                       ldg, P, ldp, Q, ldq);
+                       ldg, P, ldp, Q, ldq, eps);
     LAUNCH_CHECK("hmc_kick_drift");
+}
+int launch_hmc_accept_adapt(int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, int step_off, const float* H0,
+                            const float* P, int ldp, const float* Qn, int ldq, const float* lnp_new, const float* Gn, int ldg,
+                            const float* U, float* X, int ldx, float* lnp, float* G, int* naccept, float* alpha,
+                            const HmcAdapt& ad, float* chain, float* logps, hipStream_t s) {
+    hipLaunchKernelGGL(hmc_accept_adapt_kernel, dim3((B + 3) / 4), dim3(256), 0, s, B, ndim, mass, seed, step_dev, step_off, H0, P,
+                       ldp, Qn, ldq, lnp_new, Gn, ldg, U, X, ldx, lnp, G, naccept, alpha, ad, chain, logps);
+    LAUNCH_CHECK("hmc_accept_adapt");
+}
+int launch_hmc_find_eps_init(int B, int ndim, uint64_t seed, const int* step_dev, int step_off, float* R0, int ldr, float* eps,
+                             int* state, hipStream_t s) {
+    hipLaunchKernelGGL(hmc_find_eps_init_kernel, grid1d((size_t)B * ndim, 256), dim3(256), 0, s, B, ndim, seed, step_dev, step_off,
+                       R0, ldr, eps, state);
+    LAUNCH_CHECK("hmc_find_eps_init");
+}
+int launch_hmc_find_eps(int B, int ndim, const float* mass, const float* H0, const float* P, int ldp, const float* lnp_new,
+                        const float* Gn, int ldg, float* eps, int* state, int* nactive, hipStream_t s) {
+    hipLaunchKernelGGL(hmc_find_eps_kernel, dim3((B + 3) / 4), dim3(256), 0, s, B, ndim, mass, H0, P, ldp, lnp_new, Gn, ldg, eps,
+                       state, nactive);
+    LAUNCH_CHECK("hmc_find_eps");
 }
 int launch_hmc_accept(int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, const float* H0,
                       const float* P, int ldp, const float* Qn, int ldq, const float* lnp_new, const float* Gn, int ldg,

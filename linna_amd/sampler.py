@@ -1366,9 +1366,15 @@ class BatchedHMC(object):
     bf16 launch (``linna_logprob_set_grad_precision``), in both the fused and the piecewise form.  The leapfrog with any
     deterministic force that depends on q alone is reversible and volume-preserving, and lnP at the start and at the end
     of a trajectory both come from the gradient launch: the chain samples the density that launch returns, the rounded
-    force costs acceptance rate only.  A ``precision="bf16"`` object without the second opt-in raises here."""
+    force costs acceptance rate only.  A ``precision="bf16"`` object without the second opt-in raises here.
 
-    def __init__(self, log_prob, x0, mass=None, seed=0, fused=True):
+    ``step`` / ``sample`` take one scalar step size and enqueue a transition launch by launch.  ``run`` enqueues a block of
+    transitions in one C call with a step size per chain (``self.eps``, device), which ``find_reasonable_epsilon`` chooses
+    and ``run(..., Madapt=n)`` adapts by dual averaging (``self.epsbar``, ``Hbar``, ``mu``, ``m``): what ``HMCSampler.sample(
+    method="hmc")`` drives.  Both routes share one Philox sequence (``iteration``)."""
+
+    def __init__(self, log_prob, x0, mass=None, seed=0, fused=True, dist_group=None):
+        self.group = dist_group                 # the process group a driver gathers chain blocks over (gather_chain); chains never exchange
         self.fused = fused                      # kick + drift in the gradient launch's finish (False: the separate entries)
         if not getattr(log_prob, "device_only", True):
             raise NotImplementedError("HMC needs the gradient of the log-probability: a user loglikelihoodfunc / "
@@ -1389,7 +1395,64 @@ class BatchedHMC(object):
         self.naccept = torch.zeros(self.B, dtype=torch.int32, device=self.dev)
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=self.dev)
         self.seed = int(seed)
+        # run(): a step size per chain and the dual-averaging state of its adaptation (sampler.py:198-211 of the reference)
+        self.eps, self.alpha = z(self.B), z(self.B)
+        self.epsbar, self.Hbar, self.mu = torch.ones_like(self.eps), z(self.B), z(self.B)
+        self.m = torch.ones(self.B, dtype=torch.int32, device=self.dev)
+        self.num_steps = 5                      # run()'s default (HMCSampler.sample sets it)
+        self.nw, self.iteration, self._dev_steps = self.B, 0, 0     # (what _run_blocks / _Ranks.gather read; Philox step = iteration)
+        self._state = None
         self.lp.evaluate_with_grad(self.x, out=self.lnp, grad=self.g)
+
+    theta_of = EnsembleSampler.theta_of
+    gather_chain = EnsembleSampler.gather_chain
+
+    def _hmc_state(self):
+        if self._state is None:
+            self._state = _lib.HmcState(B=self.B, ld=self.ld, seed=self.seed, step_dev=self.step_dev.data_ptr(),
+                                        mass=self.mass.data_ptr(), X=self.x.data_ptr(), lnp=self.lnp.data_ptr(), G=self.g.data_ptr(),
+                                        P=self.p.data_ptr(), Q=self.q.data_ptr(), lnp_new=self.lnp_new.data_ptr(),
+                                        Gnew=self.g_new.data_ptr(), H0=self.H0.data_ptr())
+        return C.byref(self._state)
+
+    def find_reasonable_epsilon(self, max_rounds=40):
+        """A first step size per chain (``self.eps``): the reference's ``find_reasonable_epsilon`` (sampler.py:151-184) for all
+        chains at once -- ``max_rounds`` one-step trials of every chain enqueued in one C call, nothing read back between them
+        (linna_hmc_find_epsilon); then the dual averaging starts over from it (mu = log 10 eps, :202-208).  Returns the number of
+        chains that were still searching after the last round (they keep the step size reached; a warning says so)."""
+        r0 = torch.empty((self.B, self.ld), dtype=torch.float32, device=self.dev)
+        state = torch.empty(self.B, dtype=torch.int32, device=self.dev)
+        left = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        h, ws = self.lp._ensure()["handle"], _lib.ptr(self.lp._workspace(self.B, True))
+        _lib.call("linna_hmc_find_epsilon", h, self._hmc_state(), ws, _lib.ptr(r0), _lib.ptr(self.eps), _lib.iptr(state),
+                  _lib.iptr(left), self.iteration - self._dev_steps, int(max_rounds), _lib.stream())
+        torch.log(10.0 * self.eps, out=self.mu)
+        self.epsbar.fill_(1.0); self.Hbar.zero_(); self.m.fill_(1)
+        n = int(left.item())
+        if n:
+            import warnings
+            warnings.warn("find_reasonable_epsilon: %d of %d chains had not settled after %d rounds; they keep the step size "
+                          "they reached" % (n, self.B, max_rounds))
+        return n
+
+    def run(self, ntrans, num_steps=None, store=True, Madapt=0, target_accept=0.65):
+        """``ntrans`` transitions of ``num_steps`` leapfrog steps with the per-chain step sizes ``self.eps``, enqueued by ONE C
+        call (linna_hmc_run: 2 + num_steps launches per transition, the chain rows written by the Metropolis launch); returns
+        (chain[ntrans, B, ndim], lnp[ntrans, B]) as device tensors, (None, None) without ``store``.  Bit for bit a loop of
+        ``step()`` at that step size.  ``Madapt`` > 0: every chain whose transition count ``self.m`` is <= Madapt adapts its
+        step size by dual averaging towards the acceptance ``target_accept`` and freezes it at the averaged one on transition
+        Madapt + 1 (the count carries over from call to call)."""
+        num_steps = self.num_steps if num_steps is None else int(num_steps)
+        chain = torch.empty((ntrans, self.B, self.ndim), dtype=torch.float32, device=self.dev) if store else None
+        lps = torch.empty((ntrans, self.B), dtype=torch.float32, device=self.dev) if store else None
+        if ntrans > 0:
+            h, ws = self.lp._ensure()["handle"], _lib.ptr(self.lp._workspace(self.B, True))
+            _lib.call("linna_hmc_run", h, self._hmc_state(), ws, _lib.ptr(self.eps), _lib.ptr(self.epsbar), _lib.ptr(self.Hbar),
+                      _lib.ptr(self.mu), _lib.iptr(self.m), int(Madapt), float(target_accept), self.iteration - self._dev_steps,
+                      num_steps, int(ntrans), _lib.iptr(self.naccept), _lib.ptr(self.alpha), _lib.ptr(chain), _lib.ptr(lps),
+                      _lib.stream())
+            self.iteration += ntrans
+        return chain, lps
 
     def step(self, num_steps, step_size, p0=None, u=None):
         """One HMC transition per chain.  ``p0[B, ndim]`` (standard-normal draws) and ``u[B]`` replace
@@ -1397,6 +1460,9 @@ class BatchedHMC(object):
         st, eps = _lib.stream(), float(step_size)
         seed = C.c_uint64(self.seed)
         args = (self.ctx, self.B, self.ndim, _lib.ptr(self.mass))
+        if self._dev_steps != self.iteration:       # run() counts its transitions on the host: the entries here read the device counter
+            self.step_dev.fill_(self.iteration)
+            self._dev_steps = self.iteration
         p0d = None if p0 is None else torch.as_tensor(np.ascontiguousarray(p0, np.float32), device=self.dev)
         ud = None if u is None else torch.as_tensor(np.ascontiguousarray(u, np.float32), device=self.dev)
         if self.fused and num_steps >= 1:
@@ -1433,6 +1499,8 @@ class BatchedHMC(object):
                   _lib.ptr(ud) if ud is not None else None, _lib.ptr(self.x), self.ld, _lib.ptr(self.lnp), _lib.ptr(self.g),
                   _lib.iptr(self.naccept), st)
         _lib.call("linna_step_increment", self.ctx, _lib.iptr(self.step_dev), st)
+        self.iteration += 1
+        self._dev_steps += 1
 
     def sample(self, num_samps, num_steps, step_size):
         chain = torch.empty((num_samps, self.B, self.ndim), dtype=torch.float32, device=self.dev)
@@ -1608,7 +1676,9 @@ def _run_blocks(ens, rk, store, dchain, done, nsamp, ncheck, incremental, begin_
 
 class HMCSampler(object):
     """The reference's emcee driver (sampler.py:389-554): burn-in, restart from the best region,
-    sample until the integrated autocorrelation time and the mean/std drift have converged.
+    sample until the integrated autocorrelation time and the mean/std drift have converged.  ``method="hmc"`` runs the same
+    burn-in, restart and convergence loop with per-walker HMC chains (``BatchedHMC.run``) in place of the stretch move and
+    writes ``chhmc.h5`` (``_hmc_chains``); ``"nuts"`` is not built.
     Multi-rank runs give every rank a sub-ensemble of ``nwalkers / world`` walkers and gather the chain once per convergence
     check (``_Ranks``); every rank of the run must make the call (``dist.enter`` raises within two minutes otherwise)."""
 
@@ -1624,16 +1694,20 @@ class HMCSampler(object):
     def sample(self, pool, nsamp, samp_steps=0, samp_eps=0, Madapt=1000, outdir="./", progress=False, overwrite=False,
                ntimes=10, tautol=0.01, method="emcee", incremental=True, meanshift=0.1, stdshift=0.1, nk=2, ncheck=100,
                burnin=100, profile=None):
-        if method != "emcee":
-            # sampler.py's "hmc"/"nuts" branches are unreachable in the reference
+        if method not in ("emcee", "hmc"):
+            # sampler.py's "nuts" branch is unreachable in the reference and not built here
             raise NotImplementedError(method)
+        hmc = method == "hmc"
+        if hmc and not getattr(self.lnp, "device_only", True):
+            raise NotImplementedError("HMC needs the gradient of the log-probability: a user loglikelihoodfunc / "
+                                      "externalloglike is host code without one")
         import time
         t_start = time.perf_counter()
         prof = _Prof(profile)
         from . import dist as ldist
         ldist.enter("sampler.HMCSampler.sample", self.group)
         rk = _Ranks(self.nwalkers, self.group, self.nparams, self.exchange)
-        filename = os.path.join(outdir, "chemcee_256.h5")
+        filename = os.path.join(outdir, "chhmc.h5" if hmc else "chemcee_256.h5")       # sampler.py:466-469
         store = ChainStore(filename, self.transform)
         if not rk.active:                                    # ("root": the whole ensemble runs on rank 0)
             rk.barrier()
@@ -1668,7 +1742,11 @@ class HMCSampler(object):
                 x0 = rk.bcast(x0)
             print("burnin done...", flush=True)
             ens.naccept.zero_()
-        ens.set_state(rk.mine(x0))
+        if hmc:
+            ens = self._hmc_chains(rk, x0, samp_steps, samp_eps, Madapt, prof)
+            self.sampler = ens
+        else:
+            ens.set_state(rk.mine(x0))
         st = {"old_tau": np.inf}
         done = 0 if not resume else sum(len(c) for c in store.chain)
         done = rk.bcast(done)
@@ -1710,6 +1788,37 @@ class HMCSampler(object):
                     lag_growths=dchain.lag_growths)
         self.sampler = None
         return store
+
+
+    def _hmc_chains(self, rk, x0, samp_steps, samp_eps, Madapt, prof):
+        """The chains of ``method="hmc"`` (sampler.py:491-493: ``HamiltonianMove(dlnp, samp_steps, samp_eps, m)``), one per
+        walker of this rank, ready for ``_run_blocks``.  ``m`` is the move's ``cov``: momenta ~ N(0, m), drift p / m
+        (``_hmc_matrix``, sampler.py:311-320; tests/golden/hmc_move.npz).  ``samp_eps`` > 0: that step size for every chain,
+        the reference's semantics.  ``samp_eps`` 0 / None: a step size per chain from ``find_reasonable_epsilon`` and
+        ``Madapt`` transitions of dual averaging (NUTSMove's scheme, sampler.py:198-240) plus the one on which that scheme
+        puts the averaged step size in place -- none of them stored or counted; the convergence loop then runs on frozen
+        step sizes.  ``samp_steps`` 0 means 5."""
+        if samp_eps is not None and samp_eps < 0:
+            raise ValueError("samp_eps = %r: a step size is positive (0 or None: found and adapted per chain)" % (samp_eps,))
+        m = np.asarray(self.m, np.float64)
+        if m.ndim != 1 or len(m) != self.nparams:
+            raise ValueError("HMC needs a diagonal mass: m[ndim]")
+        lib_seed = self.seed + 0x9E3779B97F4A7C15 * rk.rank & 0xFFFFFFFFFFFFFFFF       # (every rank its own momenta)
+        ens = BatchedHMC(self.lnp, rk.mine(x0), mass=m, seed=lib_seed, dist_group=self.group)
+        if not bool(torch.isfinite(ens.lnp).all()):
+            raise ValueError("initial state has non-finite log-probability")
+        ens.num_steps = int(samp_steps) if samp_steps else 5
+        if samp_eps:
+            ens.eps.fill_(float(samp_eps))
+            return ens
+        with prof.host("adapt"), _lib.stage("run_mcmc.hmc_adapt"):
+            ens.find_reasonable_epsilon()
+            if Madapt > 0:
+                ens.run(int(Madapt) + 1, store=False, Madapt=int(Madapt))
+            ens.naccept.zero_()
+        e = ens.eps.cpu().numpy()
+        print("hmc step sizes after %d adaptive transitions: min %.3g median %.3g max %.3g" % (Madapt, e.min(), np.median(e), e.max()), flush=True)
+        return ens
 
 
 class ZeusSampler(object):

@@ -1,0 +1,114 @@
+#!/usr/bin/env python
+"""HMC transitions per second: ``BatchedHMC.run`` (linna_hmc_run: one C call per block of transitions, the step sizes in a device
+array) against a loop of ``BatchedHMC.step`` (3 + num_steps ctypes calls per transition, the step size a scalar), at 128 and
+4096 chains, on ChtoModelv2(33,33) and the 4x512 MLP (bench.py's problem), fp32 and bf16 gradient engine, 5 leapfrog steps.
+Host clock around work that ends in a device synchronise (the host's share is what differs), the two routes alternating
+in one process, `--repeats` timed windows each; median and spread.  Prints ONE JSON line.
+
+  python tools/hmc_run_bench.py [--repeats N] [--trans N]
+  python tools/hmc_run_bench.py --scalar-only          only the step() loop (what the A/B below runs in its children)
+  python tools/hmc_run_bench.py --ab OTHER_LIB.so      the scalar step() loop under this tree's library and under another
+        build of it (the parent commit's: the nullable per-row step size pointer in the gradient launch's finish must cost
+        nothing), alternating, each in a fresh process (LINNA_LIB_PATH), `--rounds` of both; prints the medians and ratios
+"""
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+
+def _arg(name, default):
+    return type(default)(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
+
+
+REPEATS, TRANS, ROUNDS = _arg("--repeats", 5), _arg("--trans", 200), _arg("--rounds", 3)
+NLEAP, EPS = 5, 1e-3
+
+
+def _stats(v):
+    v = sorted(v)
+    return {"per_s": round(v[len(v) // 2], 1), "min": round(v[0], 1), "max": round(v[-1], 1)}
+
+
+def measure(scalar_only):
+    import numpy as np
+    import torch
+    import bench
+    import bf16_bench
+    from linna_amd import _lib, sampler, util
+    if os.environ.get("LINNA_LIB_PATH"):                      # another build of the library: bind what it exports
+        _lib.load(missing_ok=True)
+    dev = torch.device("cuda", 0)
+    nets = {"ChtoModelv2_33_33": bf16_bench.v2_problem(dev), "mlp_4x512": bench.build_problem(dev)[0]}
+    out = {}
+    for net, lp32 in nets.items():
+        forms = {"fp32": lp32, "bf16": util.Log_prob(lp32.data_new, lp32.invcov_new, lp32.model, lp32.y_invtransform_data, lp32.transform,
+                                                      lp32.T, lp32.loglikelihoodfunc, nograd=True, precision="bf16", grad_precision="bf16")}
+        for prec, lp in forms.items():
+            for B in (128, 4096):
+                x0 = (0.2 * np.random.RandomState(B).standard_normal((B, 33))).astype(np.float32)
+                h = sampler.BatchedHMC(lp, x0, seed=5)
+                h.eps.fill_(EPS)
+
+                def loop():
+                    for _ in range(TRANS):
+                        h.step(NLEAP, EPS)
+
+                def block():
+                    h.run(TRANS, NLEAP, store=False)
+                routes = {"step_loop": loop} if scalar_only else {"step_loop": loop, "run": block}
+                for fn in routes.values():                    # warm-up: every shape, both routes
+                    fn()
+                torch.cuda.synchronize()
+                t = {k: [] for k in routes}
+                for _ in range(REPEATS):
+                    for k, fn in routes.items():
+                        t0 = time.perf_counter()
+                        fn()
+                        torch.cuda.synchronize()
+                        t[k].append(TRANS / (time.perf_counter() - t0))
+                r = {k: _stats(v) for k, v in t.items()}
+                if not scalar_only:
+                    r["run_over_step_loop"] = round(r["run"]["per_s"] / r["step_loop"]["per_s"], 3)
+                out["%s_%s_%d" % (net, prec, B)] = r
+    return out
+
+
+def ab(other):
+    runs = {"this": [], "other": []}
+    for rnd in range(ROUNDS):
+        for tag in (("other", "this") if rnd % 2 == 0 else ("this", "other")):      # (neither build always runs second)
+            env = dict(os.environ)
+            env.pop("LINNA_LIB_PATH", None)
+            if tag == "other":
+                env["LINNA_LIB_PATH"] = os.path.abspath(other)
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--scalar-only", "--repeats", str(REPEATS), "--trans", str(TRANS)],
+                               env=env, stdout=subprocess.PIPE, universal_newlines=True, timeout=600)
+            if p.returncode != 0:
+                raise SystemExit("child (%s) failed with %d" % (tag, p.returncode))
+            runs[tag].append(json.loads(p.stdout.strip().splitlines()[-1])["rates"])
+    res = {}
+    for key in runs["this"][0]:
+        a = sorted(r[key]["step_loop"]["per_s"] for r in runs["this"])
+        b = sorted(r[key]["step_loop"]["per_s"] for r in runs["other"])
+        res[key] = {"this_per_s": a, "other_per_s": b, "this_over_other": round(a[len(a) // 2] / b[len(b) // 2], 4)}
+    return res
+
+
+def main():
+    if "--ab" in sys.argv:
+        print(json.dumps({"tool": "hmc_run_bench", "mode": "ab", "other": sys.argv[sys.argv.index("--ab") + 1], "rounds": ROUNDS,
+                          "trans": TRANS, "repeats": REPEATS, "scalar_step_loop": ab(sys.argv[sys.argv.index("--ab") + 1])}))
+        return
+    scalar_only = "--scalar-only" in sys.argv
+    print(json.dumps({"tool": "hmc_run_bench", "leapfrog_steps": NLEAP, "trans": TRANS, "repeats": REPEATS,
+                      "scalar_only": scalar_only, "rates": measure(scalar_only)}))
+
+
+if __name__ == "__main__":
+    main()
