@@ -545,7 +545,7 @@ int linna_hmc_kick_drift_eps(linna_ctx_t* ctx, int B, int ndim, const float* mas
 int linna_logprob_grad_leapfrog_eps(linna_logprob_t* lp, float* Q, int ldq, int B, void* ws, float* lnP, float* G, int ldg,
                                     float* P, int ldp, const float* mass, const float* EPS, float mul_kick, float mul_drift,
                                     void* stream);
-/* linna_hmc_accept (the same arithmetic, the same decisions; Philox step step_dev[0] + step_offset) and, behind the test:
+/* linna_hmc_accept's test (one kernel runs behind both entries; Philox step step_dev[0] + step_offset) and, behind the test:
  *  alpha[B] (optional) = exp(min(H0 - H1, 0)), 0 where lnp_new or an energy is not finite;
  *  chain[B][ndim] / logps[B] (optional): every chain's row and log-probability after the test;
  *  M[B] (optional) += 1, and for Madapt > 0 the dual averaging of the step size per chain as the reference's NUTSMove runs

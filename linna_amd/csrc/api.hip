@@ -1402,11 +1402,9 @@ int linna_chain_meanstd(linna_ctx_t*, const float* CT, int ndim, int nwp, int nw
 
 }  // extern "C"
 
-// the gradient's destination and, with `leap` (hm_* of an NsGrad, the rest unset), the leapfrog's kick and drift behind it
-static NsGrad lp_grad_args(const linna_logprob_desc_t& d, float* G, int ldg, const NsGrad* leap) {
-    NsGrad g{d.gscale, G, ldg, nullptr, 0, nullptr, nullptr, 0.f, 0.f, nullptr};
-    if (leap) { g.hm_p = leap->hm_p; g.hm_ldp = leap->hm_ldp; g.hm_q = leap->hm_q; g.hm_mass = leap->hm_mass; g.hm_ek = leap->hm_ek; g.hm_ed = leap->hm_ed; g.hm_eps = leap->hm_eps; }
-    return g;
+// the gradient's destination and, with `leap`, the leapfrog's kick and drift behind it (none: an NsLeap of nulls)
+static NsGrad lp_grad_args(const linna_logprob_desc_t& d, float* G, int ldg, const NsLeap* leap) {
+    return NsGrad{d.gscale, G, ldg, leap ? *leap : NsLeap{}};
 }
 // forward + dX chain down to the input in one launch on the stream copy `sc` (NS_GRAD_INPUT, or its bf16 form)
 static int lp_launch_grad2(linna_logprob* lp, StreamCopy& sc, bool bf, const float* Z, int ldz, int B, float* lnP, const NsGrad& gr, void* stream) {
@@ -1439,7 +1437,7 @@ static int logprob_grad_ready(const linna_logprob_t* lp) {
 // lnP and its gradient at Z; `leap`: the leapfrog's kick and drift -- in the finish of the one-launch forms, as a launch of
 // its own behind the others
 static int logprob_grad_impl(linna_logprob_t* lp, const float* Z, int ldz, int B, void* ws, float* lnP, float* G, int ldg,
-                             const NsGrad* leap, void* stream) {
+                             const NsLeap* leap, void* stream) {
     if (!lp || !Z || !ws || !lnP || !G || B < 1) { set_error("logprob_grad: bad arguments"); return LINNA_ERR_INVALID; }
     TRY(logprob_grad_ready(lp));
     const linna_logprob_desc_t& d = lp->d;
@@ -1470,7 +1468,7 @@ static int logprob_grad_impl(linna_logprob_t* lp, const float* Z, int ldz, int B
     }
     TRY(linna_net_backward(lp->net, w + L.x0, ldx, B, w + L.fwd, w + L.bwd, w + L.dh, ldd, w + L.dx, ldx, 0, stream));
     TRY(launch_prior_map_bwd(Z, ldz, B, d.nin, d.is_flat, d.a1, d.a2, d.log10_flag, d.xstd, w + L.dx, ldx, G, ldg, S(stream)));
-    if (leap) return launch_hmc_kick_drift(B, d.nin, leap->hm_mass, leap->hm_ek, leap->hm_ed, G, ldg, leap->hm_p, leap->hm_ldp, leap->hm_q, ldz, S(stream), leap->hm_eps);
+    if (leap) return launch_hmc_kick_drift(B, d.nin, leap->mass, leap->ek, leap->ed, G, ldg, leap->P, leap->ldp, leap->Q, ldz, S(stream), leap->eps);
     return LINNA_OK;
 }
 
@@ -1486,14 +1484,14 @@ int linna_logprob_grad(linna_logprob_t* lp, const float* Z, int ldz, int B, void
 int linna_logprob_grad_leapfrog(linna_logprob_t* lp, float* Q, int ldq, int B, void* ws, float* lnP, float* G, int ldg, float* P,
                                 int ldp, const float* mass, float eps_kick, float eps_drift, void* stream) try {
     if (!P || !mass || !Q) { set_error("logprob_grad_leapfrog: bad arguments"); return LINNA_ERR_INVALID; }
-    NsGrad leap{nullptr, nullptr, 0, P, ldp, Q, mass, eps_kick, eps_drift, nullptr};
+    const NsLeap leap{P, ldp, Q, mass, eps_kick, eps_drift, nullptr};
     return logprob_grad_impl(lp, Q, ldq, B, ws, lnP, G, ldg, &leap, stream);
 } LINNA_CATCH_INT
 
 int linna_logprob_grad_leapfrog_eps(linna_logprob_t* lp, float* Q, int ldq, int B, void* ws, float* lnP, float* G, int ldg, float* P,
                                     int ldp, const float* mass, const float* EPS, float mul_kick, float mul_drift, void* stream) try {
     if (!P || !mass || !Q || !EPS) { set_error("logprob_grad_leapfrog_eps: bad arguments"); return LINNA_ERR_INVALID; }
-    NsGrad leap{nullptr, nullptr, 0, P, ldp, Q, mass, mul_kick, mul_drift, EPS};
+    const NsLeap leap{P, ldp, Q, mass, mul_kick, mul_drift, EPS};
     return logprob_grad_impl(lp, Q, ldq, B, ws, lnP, G, ldg, &leap, stream);
 } LINNA_CATCH_INT
 
@@ -1501,6 +1499,13 @@ int linna_logprob_grad_leapfrog_eps(linna_logprob_t* lp, float* Q, int ldq, int 
 static bool hmc_state_ok(const linna_hmc_state_t* st) {
     return st && st->B >= 1 && st->ld >= 1 && st->X && st->lnp && st->G && st->P && st->Q && st->lnp_new && st->Gnew && st->H0 &&
            st->mass && st->step_dev;
+}
+// what the entries that run whole transitions check of their state before they enqueue anything
+static int hmc_entry_check(const linna_logprob_t* lp, const linna_hmc_state_t* st, const char* who) {
+    CHECK_STRUCT(st, linna_hmc_state_t, who);
+    if (!hmc_state_ok(st)) { set_error("%s: incomplete state", who); return LINNA_ERR_INVALID; }
+    if (st->ld < lp->d.nin) { set_error("%s: ld %d < %d parameters", who, st->ld, lp->d.nin); return LINNA_ERR_INVALID; }
+    return logprob_grad_ready(lp);
 }
 // one trajectory from st->X with the momenta hmc_start draws (P0 == nullptr) or is given: start, num_steps gradient launches
 static int hmc_trajectory(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, const float* P0, const float* EPS, int step_off,
@@ -1510,7 +1515,7 @@ static int hmc_trajectory(linna_logprob_t* lp, const linna_hmc_state_t* st, void
                          st->H0, S(stream), EPS, step_off));
     for (int i = 0; i < num_steps; ++i) {
         const bool last = i == num_steps - 1;                                      // a half kick behind the last step, no drift
-        NsGrad leap{nullptr, nullptr, 0, st->P, ld, st->Q, st->mass, last ? 0.5f : 1.f, last ? 0.f : 1.f, EPS};
+        const NsLeap leap{st->P, ld, st->Q, st->mass, last ? 0.5f : 1.f, last ? 0.f : 1.f, EPS};
         TRY(logprob_grad_impl(lp, st->Q, ld, B, ws, st->lnp_new, st->Gnew, ld, &leap, stream));
     }
     return LINNA_OK;
@@ -1522,18 +1527,15 @@ int linna_hmc_run(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, fl
     if (!lp || !st || !ws || !EPS || num_steps < 1 || ntrans < 1 || Madapt < 0 || (chain != nullptr) != (logps != nullptr)) {
         set_error("hmc_run: bad arguments"); return LINNA_ERR_INVALID;
     }
-    CHECK_STRUCT(st, linna_hmc_state_t, "hmc_run");
-    if (!hmc_state_ok(st)) { set_error("hmc_run: incomplete state"); return LINNA_ERR_INVALID; }
-    if (st->ld < lp->d.nin) { set_error("hmc_run: ld %d < %d parameters", st->ld, lp->d.nin); return LINNA_ERR_INVALID; }
     if (Madapt > 0 && (!EPSBAR || !HBAR || !MU || !M)) { set_error("hmc_run: Madapt > 0 needs the adaptation state"); return LINNA_ERR_INVALID; }
-    TRY(logprob_grad_ready(lp));
+    TRY(hmc_entry_check(lp, st, "hmc_run"));
     const int B = st->B, nd = lp->d.nin, ld = st->ld;
     const HmcAdapt ad{EPS, EPSBAR, HBAR, MU, M, Madapt, delta};
     for (int i = 0; i < ntrans; ++i) {
         TRY(hmc_trajectory(lp, st, ws, nullptr, EPS, step_offset + i, num_steps, stream));
-        TRY(launch_hmc_accept_adapt(B, nd, st->mass, st->seed, st->step_dev, step_offset + i, st->H0, st->P, ld, st->Q, ld, st->lnp_new,
-                                    st->Gnew, ld, nullptr, st->X, ld, st->lnp, st->G, naccept, alpha, ad,
-                                    chain ? chain + (size_t)i * B * nd : nullptr, logps ? logps + (size_t)i * B : nullptr, S(stream)));
+        TRY(launch_hmc_accept(B, nd, st->mass, st->seed, st->step_dev, step_offset + i, st->H0, st->P, ld, st->Q, ld, st->lnp_new,
+                              st->Gnew, ld, nullptr, st->X, ld, st->lnp, st->G, naccept, alpha, ad,
+                              chain ? chain + (size_t)i * B * nd : nullptr, logps ? logps + (size_t)i * B : nullptr, S(stream)));
     }
     return LINNA_OK;
 } LINNA_CATCH_INT
@@ -1541,10 +1543,7 @@ int linna_hmc_run(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, fl
 int linna_hmc_find_epsilon(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, float* R0, float* EPS, int* state, int* nactive,
                            int step_offset, int max_rounds, void* stream) try {
     if (!lp || !st || !ws || !R0 || !EPS || !state || !nactive || max_rounds < 1) { set_error("hmc_find_epsilon: bad arguments"); return LINNA_ERR_INVALID; }
-    CHECK_STRUCT(st, linna_hmc_state_t, "hmc_find_epsilon");
-    if (!hmc_state_ok(st)) { set_error("hmc_find_epsilon: incomplete state"); return LINNA_ERR_INVALID; }
-    if (st->ld < lp->d.nin) { set_error("hmc_find_epsilon: ld %d < %d parameters", st->ld, lp->d.nin); return LINNA_ERR_INVALID; }
-    TRY(logprob_grad_ready(lp));
+    TRY(hmc_entry_check(lp, st, "hmc_find_epsilon"));
     const int B = st->B, nd = lp->d.nin, ld = st->ld;
     TRY(check_hip(hipMemsetAsync(nactive, 0, sizeof(int), S(stream)), "hipMemsetAsync"));
     TRY(launch_hmc_find_eps_init(B, nd, st->seed, st->step_dev, step_offset, R0, ld, EPS, state, S(stream)));
@@ -1757,7 +1756,7 @@ int linna_stretch_accept(linna_ctx_t*, float* coords, int ldc, int ndim, float* 
 } LINNA_CATCH_INT
 int linna_hmc_init(linna_ctx_t*, int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, const float* lnp,
                    const float* P0, int ldp0, float* P, int ldp, float* H0, void* stream) try {
-    return launch_hmc_init(B, ndim, mass, seed, step_dev, lnp, P0, ldp0, P, ldp, H0, S(stream));
+    return launch_hmc_start(B, ndim, mass, seed, step_dev, lnp, P0, ldp0, nullptr, 0, 0.f, 0.f, nullptr, 0, P, ldp, nullptr, 0, H0, S(stream));
 } LINNA_CATCH_INT
 int linna_hmc_start(linna_ctx_t*, int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, const float* lnp,
                     const float* P0, int ldp0, const float* G, int ldg, float eps_kick, float eps_drift, const float* X, int ldx,
@@ -1791,13 +1790,15 @@ int linna_hmc_accept_adapt(linna_ctx_t*, int B, int ndim, const float* mass, uin
         set_error("hmc_accept_adapt: bad arguments"); return LINNA_ERR_INVALID;
     }
     const HmcAdapt ad{EPS, EPSBAR, HBAR, MU, M, Madapt, delta};
-    return launch_hmc_accept_adapt(B, ndim, mass, seed, step_dev, step_offset, H0, P, ldp, Qn, ldq, lnp_new, Gn, ldg, U, X, ldx, lnp, G,
-                                   naccept, alpha, ad, chain, logps, S(stream));
+    return launch_hmc_accept(B, ndim, mass, seed, step_dev, step_offset, H0, P, ldp, Qn, ldq, lnp_new, Gn, ldg, U, X, ldx, lnp, G,
+                             naccept, alpha, ad, chain, logps, S(stream));
 } LINNA_CATCH_INT
 int linna_hmc_accept(linna_ctx_t*, int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, const float* H0,
                      const float* P, int ldp, const float* Qn, int ldq, const float* lnp_new, const float* Gn, int ldg,
                      const float* U, float* X, int ldx, float* lnp, float* G, int* naccept, void* stream) try {
-    return launch_hmc_accept(B, ndim, mass, seed, step_dev, H0, P, ldp, Qn, ldq, lnp_new, Gn, ldg, U, X, ldx, lnp, G, naccept, S(stream));
+    // the Metropolis test alone: no acceptance rate, no chain row, no adaptation state
+    return launch_hmc_accept(B, ndim, mass, seed, step_dev, 0, H0, P, ldp, Qn, ldq, lnp_new, Gn, ldg, U, X, ldx, lnp, G, naccept, nullptr,
+                             HmcAdapt{}, nullptr, nullptr, S(stream));
 } LINNA_CATCH_INT
 int linna_step_increment(linna_ctx_t*, int* step_dev, void* stream) try { return launch_step_increment(step_dev, S(stream)); } LINNA_CATCH_INT
 

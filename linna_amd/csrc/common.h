@@ -347,27 +347,24 @@ int launch_stretch_propose(const float* coords, int ldc, int ndim, const int* S,
 int launch_stretch_accept(float* coords, int ldc, int ndim, float* logp, const int* S, int ns, const float* Q, int ldq,
                           const float* lp_new, const float* factors, uint64_t seed, const int* step_dev, int stream_id,
                           int* naccept, hipStream_t s);
-int launch_hmc_init(int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, const float* lnp,
-                    const float* P0, int ldp0, float* P, int ldp, float* H0, hipStream_t s);
-// eps (nullable, here and below): a step size per chain in device memory, ek / ed then multiply it; step_off: added to step_dev[0]
+// eps (nullable, here and below): a step size per chain in device memory, ek / ed then multiply it; step_off: added to step_dev[0].
+// G == nullptr (X, Q then unused): only the momenta and H0, what linna_hmc_init asks for
 int launch_hmc_start(int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, const float* lnp, const float* P0,
                      int ldp0, const float* G, int ldg, float ek, float ed, const float* X, int ldx, float* P, int ldp, float* Q,
                      int ldq, float* H0, hipStream_t s, const float* eps = nullptr, int step_off = 0);
 int launch_hmc_kick_drift(int B, int ndim, const float* mass, float ek, float ed, const float* G, int ldg, float* P,
                           int ldp, float* Q, int ldq, hipStream_t s, const float* eps = nullptr);
-// the dual-averaging state of hmc_accept_adapt_kernel, one entry per chain (sampler.py:198-240 of the reference)
+// the dual-averaging state of hmc_accept_kernel, one entry per chain (sampler.py:198-240 of the reference)
 struct HmcAdapt { float* eps; float* epsbar; float* Hbar; const float* mu; int* m; int Madapt; float delta; };
-int launch_hmc_accept_adapt(int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, int step_off, const float* H0,
-                            const float* P, int ldp, const float* Qn, int ldq, const float* lnp_new, const float* Gn, int ldg,
-                            const float* U, float* X, int ldx, float* lnp, float* G, int* naccept, float* alpha,
-                            const HmcAdapt& ad, float* chain, float* logps, hipStream_t s);
+// the one Metropolis launcher: alpha, chain, logps and ad.m are each nullable (linna_hmc_accept passes all of them null)
+int launch_hmc_accept(int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, int step_off, const float* H0,
+                      const float* P, int ldp, const float* Qn, int ldq, const float* lnp_new, const float* Gn, int ldg,
+                      const float* U, float* X, int ldx, float* lnp, float* G, int* naccept, float* alpha,
+                      const HmcAdapt& ad, float* chain, float* logps, hipStream_t s);
 int launch_hmc_find_eps_init(int B, int ndim, uint64_t seed, const int* step_dev, int step_off, float* R0, int ldr, float* eps,
                              int* state, hipStream_t s);
 int launch_hmc_find_eps(int B, int ndim, const float* mass, const float* H0, const float* P, int ldp, const float* lnp_new,
                         const float* Gn, int ldg, float* eps, int* state, int* nactive, hipStream_t s);
-int launch_hmc_accept(int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, const float* H0,
-                      const float* P, int ldp, const float* Qn, int ldq, const float* lnp_new, const float* Gn, int ldg,
-                      const float* U, float* X, int ldx, float* lnp, float* G, int* naccept, hipStream_t s);
 int launch_slice_init(const float* logp, const int* S, int ns, const float* cc, int ldcc, const int* C, int nc, int ndim,
                       const float* mu, uint64_t seed, const int* step_dev, int stream_id, float* DIR, int ldd, float* Z0,
                       float* L, float* R, int* flags, int maxsteps, hipStream_t s);
@@ -474,9 +471,10 @@ int launch_net_stream_train_bwd(const NsNet& net, const float* packed, const NsB
                                 const NsDense& dn, int rows, hipStream_t s, const NsPost* post,
                                 bool bf = false);     // bf: NS_TRAIN_STEP_BF16 (net_stream_train_bf16_kernel)
 // gradient fused behind the evaluation (plain ReLU MLPs, diagonal covariance): G = d lnP / d z
-// hm_*: a leapfrog kick and drift riding in the gradient's finish (HMCSampler.py:35-49): P += ek G; Q += ed P / mass, Q the
-// launch's own input rows (hm_p == nullptr: none); hm_eps (nullable): a step size per row, ek and ed are then its multipliers
-struct NsGrad { const float* gscale; float* G; int ldg; float* hm_p; int hm_ldp; float* hm_q; const float* hm_mass; float hm_ek, hm_ed; const float* hm_eps; };
+// NsLeap: a leapfrog kick and drift riding behind the gradient (HMCSampler.py:35-49): P += ek G; Q += ed P / mass, Q the
+// launch's own input rows (P == nullptr: none rides); eps (nullable): a step size per row, ek and ed are then its multipliers
+struct NsLeap { float* P; int ldp; float* Q; const float* mass; float ek, ed; const float* eps; };
+struct NsGrad { const float* gscale; float* G; int ldg; NsLeap leap; };
 // AdamW that also writes the two weight streams of a training step (net_stream.hip: adamw_streams_kernel; gemm.hip: the
 // update epilogue of the grouped parameter-gradient launch).  An AsPlace says where the elements of a weight matrix sit
 // in one fragment-order stream (segment type 0 = WIDE, 1 = SPLIT; see net_stream.hip).

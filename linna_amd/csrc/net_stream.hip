@@ -640,8 +640,8 @@ static void ns_set_input(NsArgs& a, const NsInput& in) {
 }
 static void ns_set_grad(NsArgs& a, const NsGrad& gr) {
     a.gscale = gr.gscale; a.Gout = gr.G; a.ldg = gr.ldg;
-    a.hm_p = gr.hm_p; a.hm_ldp = gr.hm_ldp; a.hm_q = gr.hm_q; a.hm_mass = gr.hm_mass; a.hm_ek = gr.hm_ek; a.hm_ed = gr.hm_ed;
-    a.hm_eps = gr.hm_eps;
+    const NsLeap& l = gr.leap;          // the one place that writes NsArgs::hm_*
+    a.hm_p = l.P; a.hm_ldp = l.ldp; a.hm_q = l.Q; a.hm_mass = l.mass; a.hm_ek = l.ek; a.hm_ed = l.ed; a.hm_eps = l.eps;
 }
 
 int launch_net_stream(NsKind kind, const NsNet& net, const float* packed, const float* Z, int ldz, int B, const NsInput& in,

@@ -452,6 +452,21 @@ __device__ __forceinline__ float wave_ordered_sum(float t, int n) {
     return acc;
 }
 
+// sum_d P[b][d]^2 / mass[d] of chain b, by the chain's wave: the ONE place this sum is written, since its order (64
+// dimensions at a time, each group in dimension order) is what makes every route through the Metropolis test bit-equal.
+// hmc_start_kernel keeps a loop of its own: it forms t from the momentum it has just drawn.
+__device__ __forceinline__ float wave_kinetic(const float* __restrict__ P, int ldp, const float* __restrict__ mass, int ndim,
+                                              int b, int lane) {
+    float ke = 0.f;
+    for (int d0 = 0; d0 < ndim; d0 += 64) {
+        const int d = d0 + lane;
+        float t = 0.f;
+        if (d < ndim) { const float p = P[(size_t)b * ldp + d]; t = p * p / mass[d]; }
+        ke += wave_ordered_sum(t, min(64, ndim - d0));
+    }
+    return ke;
+}
+
 // P ~ N(0, m), H0 = P^2 / 2m - lnP; G != nullptr: also the first half kick and the first drift of the leapfrog,
 // P += ek G, Q = X + ed P / m (hmc_kick_drift_kernel's arithmetic).  eps != nullptr: a step size per chain, ek and ed are
 // its multipliers (1, 0.5 or 0); the Philox step is step_dev[0] + step_off.
@@ -499,42 +514,10 @@ __global__ void hmc_kick_drift_kernel(int B, int ndim, const float* __restrict__
     if (drift) Q[(size_t)b * ldq + d] += ed * (p / mass[d]);
 }
 
-__global__ void hmc_accept_kernel(int B, int ndim, const float* __restrict__ mass, uint64_t seed,
-                                  const int* __restrict__ step_dev, const float* __restrict__ H0,
-                                  const float* __restrict__ P, int ldp, const float* __restrict__ Qn, int ldq,
-                                  const float* __restrict__ lnp_new, const float* __restrict__ Gn, int ldg,
-                                  const float* __restrict__ U,
-                                  float* __restrict__ X, int ldx, float* __restrict__ lnp, float* __restrict__ G,
-                                  int* __restrict__ naccept) {
-    const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;   // a wave per chain
-    if (b >= B) return;
-    float ke = 0.f;
-    for (int d0 = 0; d0 < ndim; d0 += 64) {
-        const int d = d0 + lane;
-        float t = 0.f;
-        if (d < ndim) { const float p = P[(size_t)b * ldp + d]; t = p * p / mass[d]; }
-        ke += wave_ordered_sum(t, min(64, ndim - d0));
-    }
-    const float ln = lnp_new[b];
-    const float H1 = 0.5f * ke - ln;
-    const U4 r = walker_bits(seed, (uint32_t)b, (uint32_t)step_dev[0], 2u, 0u);
-    const float dH = H0[b] - H1;
-    const float ratio = expf(dH > 0.f ? 0.f : dH);   // a NaN energy stays NaN and rejects (np.minimum; fminf would return 0)
-    const float u = U ? U[b] : u01(r.x);
-    if (isfinite(ln) && u < ratio) {
-        for (int d = lane; d < ndim; d += 64) {
-            X[(size_t)b * ldx + d] = Qn[(size_t)b * ldq + d];
-            G[(size_t)b * ldg + d] = Gn[(size_t)b * ldg + d];
-        }
-        if (lane == 0) {
-            lnp[b] = ln;
-            if (naccept) atomicAdd(naccept + b, 1);
-        }
-    }
-}
-
-// hmc_accept_kernel's Metropolis test (the same arithmetic, the same decisions) at Philox step step_dev[0] + step_off, and
-// behind it what a run of transitions enqueued in one go needs from the host otherwise:
+// The Metropolis test of one transition at Philox step step_dev[0] + step_off (U != nullptr: the uniforms given), a wave
+// per chain: accept where lnp_new is finite and u < exp(min(H0 - H1, 0)); X, G, lnp and naccept change on acceptance only.
+// Behind it what a run of transitions enqueued in one go needs from the host otherwise, each part off when its pointer is
+// null (linna_hmc_accept runs this kernel with all of them null and step_off 0):
 //  * alpha[b] = exp(min(H0 - H1, 0)), 0 where lnp_new or an energy is not finite;
 //  * chain / logps != nullptr: the chain's row and log-probability after the test, to chain[b][ndim] / logps[b];
 //  * ad.m != nullptr: m += 1, and for ad.Madapt > 0 the dual averaging of the step size per chain (Hoffman & Gelman 2014,
@@ -543,23 +526,17 @@ __global__ void hmc_accept_kernel(int B, int ndim, const float* __restrict__ mas
 //      epsbar = exp((1 - m^-kappa) log epsbar + m^-kappa log eps),
 //    at m == Madapt + 1 eps = epsbar, later nothing.  This launch follows every leapfrog launch of its transition: eps[b]
 //    has no reader left.
-__global__ void hmc_accept_adapt_kernel(int B, int ndim, const float* __restrict__ mass, uint64_t seed,
-                                        const int* __restrict__ step_dev, int step_off, const float* __restrict__ H0,
-                                        const float* __restrict__ P, int ldp, const float* __restrict__ Qn, int ldq,
-                                        const float* __restrict__ lnp_new, const float* __restrict__ Gn, int ldg,
-                                        const float* __restrict__ U,
-                                        float* __restrict__ X, int ldx, float* __restrict__ lnp, float* __restrict__ G,
-                                        int* __restrict__ naccept, float* __restrict__ alpha, HmcAdapt ad,
-                                        float* __restrict__ chain, float* __restrict__ logps) {
+__global__ void hmc_accept_kernel(int B, int ndim, const float* __restrict__ mass, uint64_t seed,
+                                  const int* __restrict__ step_dev, int step_off, const float* __restrict__ H0,
+                                  const float* __restrict__ P, int ldp, const float* __restrict__ Qn, int ldq,
+                                  const float* __restrict__ lnp_new, const float* __restrict__ Gn, int ldg,
+                                  const float* __restrict__ U,
+                                  float* __restrict__ X, int ldx, float* __restrict__ lnp, float* __restrict__ G,
+                                  int* __restrict__ naccept, float* __restrict__ alpha, HmcAdapt ad,
+                                  float* __restrict__ chain, float* __restrict__ logps) {
     const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;   // a wave per chain
     if (b >= B) return;
-    float ke = 0.f;
-    for (int d0 = 0; d0 < ndim; d0 += 64) {
-        const int d = d0 + lane;
-        float t = 0.f;
-        if (d < ndim) { const float p = P[(size_t)b * ldp + d]; t = p * p / mass[d]; }
-        ke += wave_ordered_sum(t, min(64, ndim - d0));
-    }
+    const float ke = wave_kinetic(P, ldp, mass, ndim, b, lane);
     const float ln = lnp_new[b];
     const float H1 = 0.5f * ke - ln;
     const U4 r = walker_bits(seed, (uint32_t)b, (uint32_t)(step_dev[0] + step_off), 2u, 0u);
@@ -626,18 +603,9 @@ __global__ void hmc_find_eps_kernel(int B, int ndim, const float* __restrict__ m
     if (b >= B) return;
     int st = state[b];
     if (st == 2) return;
-    float ke = 0.f;
+    const float ke = wave_kinetic(P, ldp, mass, ndim, b, lane);
     int bad = 0;
-    for (int d0 = 0; d0 < ndim; d0 += 64) {
-        const int d = d0 + lane;
-        float t = 0.f;
-        if (d < ndim) {
-            const float p = P[(size_t)b * ldp + d];
-            t = p * p / mass[d];
-            bad |= !isfinite(Gn[(size_t)b * ldg + d]);
-        }
-        ke += wave_ordered_sum(t, min(64, ndim - d0));
-    }
+    for (int d = lane; d < ndim; d += 64) bad |= !isfinite(Gn[(size_t)b * ldg + d]);
     const float ln = lnp_new[b];
     bad = __any(bad) || !isfinite(ln);
     if (lane != 0) return;
@@ -1025,13 +993,6 @@ int launch_stretch_accept(float* coords, int ldc, int ndim, float* logp, const i
                        lp_new, factors, seed, step_dev, stream_id, naccept);
     LAUNCH_CHECK("stretch_accept");
 }
-int launch_hmc_init(int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, const float* lnp,
-                    const float* P0, int ldp0, float* P, int ldp, float* H0, hipStream_t s) {
-    hipLaunchKernelGGL(hmc_start_kernel, dim3((B + 3) / 4), dim3(256), 0, s, B, ndim, mass, seed, step_dev, lnp, P0, ldp0,
-                       (const float*)nullptr, 0, 0.f, 0.f, (const float*)nullptr, 0, P, ldp, (float*)nullptr, 0, H0,
-                       (const float*)nullptr, 0);
-    LAUNCH_CHECK("hmc_init");
-}
 int launch_hmc_start(int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, const float* lnp, const float* P0,
                      int ldp0, const float* G, int ldg, float ek, float ed, const float* X, int ldx, float* P, int ldp, float* Q,
                      int ldq, float* H0, hipStream_t s, const float* eps, int step_off) {
@@ -1045,13 +1006,13 @@ int launch_hmc_kick_drift(int B, int ndim, const float* mass, float ek, float ed
                        ldg, P, ldp, Q, ldq, eps);
     LAUNCH_CHECK("hmc_kick_drift");
 }
-int launch_hmc_accept_adapt(int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, int step_off, const float* H0,
-                            const float* P, int ldp, const float* Qn, int ldq, const float* lnp_new, const float* Gn, int ldg,
-                            const float* U, float* X, int ldx, float* lnp, float* G, int* naccept, float* alpha,
-                            const HmcAdapt& ad, float* chain, float* logps, hipStream_t s) {
-    hipLaunchKernelGGL(hmc_accept_adapt_kernel, dim3((B + 3) / 4), dim3(256), 0, s, B, ndim, mass, seed, step_dev, step_off, H0, P,
+int launch_hmc_accept(int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, int step_off, const float* H0,
+                      const float* P, int ldp, const float* Qn, int ldq, const float* lnp_new, const float* Gn, int ldg,
+                      const float* U, float* X, int ldx, float* lnp, float* G, int* naccept, float* alpha,
+                      const HmcAdapt& ad, float* chain, float* logps, hipStream_t s) {
+    hipLaunchKernelGGL(hmc_accept_kernel, dim3((B + 3) / 4), dim3(256), 0, s, B, ndim, mass, seed, step_dev, step_off, H0, P,
                        ldp, Qn, ldq, lnp_new, Gn, ldg, U, X, ldx, lnp, G, naccept, alpha, ad, chain, logps);
-    LAUNCH_CHECK("hmc_accept_adapt");
+    LAUNCH_CHECK("hmc_accept");
 }
 int launch_hmc_find_eps_init(int B, int ndim, uint64_t seed, const int* step_dev, int step_off, float* R0, int ldr, float* eps,
                              int* state, hipStream_t s) {
@@ -1064,13 +1025,6 @@ int launch_hmc_find_eps(int B, int ndim, const float* mass, const float* H0, con
     hipLaunchKernelGGL(hmc_find_eps_kernel, dim3((B + 3) / 4), dim3(256), 0, s, B, ndim, mass, H0, P, ldp, lnp_new, Gn, ldg, eps,
                        state, nactive);
     LAUNCH_CHECK("hmc_find_eps");
-}
-int launch_hmc_accept(int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, const float* H0,
-                      const float* P, int ldp, const float* Qn, int ldq, const float* lnp_new, const float* Gn, int ldg,
-                      const float* U, float* X, int ldx, float* lnp, float* G, int* naccept, hipStream_t s) {
-    hipLaunchKernelGGL(hmc_accept_kernel, dim3((B + 3) / 4), dim3(256), 0, s, B, ndim, mass, seed, step_dev, H0, P, ldp, Qn,
-                       ldq, lnp_new, Gn, ldg, U, X, ldx, lnp, G, naccept);
-    LAUNCH_CHECK("hmc_accept");
 }
 int launch_slice_init(const float* logp, const int* S, int ns, const float* cc, int ldcc, const int* C, int nc, int ndim,
                       const float* mu, uint64_t seed, const int* step_dev, int stream_id, float* DIR, int ldd, float* Z0,

@@ -4,7 +4,7 @@ tests/test_gpu_hmc_adapt.py (not a test module).
 * ``transition``: one transition of every chain with a step size per chain -- ``oracle.sampling.hmc_batched_step`` with
   ``step_size[B, 1]`` in float32 (bit for bit, pinned by the host test), any dtype otherwise, and the acceptance
   probability ``alpha`` the dual averaging feeds on.
-* ``dual_average``: hmc_accept_adapt_kernel's update of (eps, epsbar, Hbar, m) -- the reference's NUTSMove.propose,
+* ``dual_average``: hmc_accept_kernel's update of (eps, epsbar, Hbar, m) -- the reference's NUTSMove.propose,
   sampler.py:229-240, with nalpha = 1, gamma 0.05, t0 10, kappa 0.75.
 * ``find_eps``: hmc_find_eps_kernel's state machine, the reference's find_reasonable_epsilon (sampler.py:151-184) for all
   chains at once in a bounded number of rounds.
@@ -41,7 +41,7 @@ def _normals(seed, step, stream, B, ndim):
 
 
 def uniforms(seed, step, B):
-    """The Metropolis uniforms of hmc_accept(_adapt)_kernel (stream 2, sub 0, first word)."""
+    """The Metropolis uniforms of hmc_accept_kernel (stream 2, sub 0, first word)."""
     return sampling.u01(sampling.walker_bits(seed, np.arange(B), step, 2, 0))[:, 0]
 
 

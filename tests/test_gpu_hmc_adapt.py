@@ -151,7 +151,8 @@ def _bits(t):
 def test_accept_adapt_acceptance_table(ndim):
     """linna_hmc_accept_adapt on tests/poison.py ``hmc_table`` (test_hmc_acceptance_table's rows and sizes): accepted exactly
     where numpy says, rejected rows untouched, alpha = exp(min(H0 - H1, 0)) -- 0 where lnp_new or an energy is not finite --
-    and the chain row of every chain is its state after the test."""
+    and the chain row of every chain is its state after the test.  linna_hmc_accept on the same inputs leaves X, lnp, G and naccept
+    equal to it bit for bit (ndim = 70: the second pass of the 64-lane kinetic-energy loop)."""
     t = poison.hmc_table(ndim)
     want = poison.hmc_table_expected(t)
     B, ld = 11, _lib.ld4(ndim)
@@ -162,6 +163,11 @@ def test_accept_adapt_acceptance_table(ndim):
     alpha = torch.full((B,), -1.0, device="cuda")
     chain, logps = torch.full((B, ndim), 7.0, device="cuda"), torch.full((B,), 7.0, device="cuda")
     X0, G0, lnp0 = _bits(X).copy(), _bits(G).copy(), _bits(lnp).copy()
+    # linna_hmc_accept on clones of the same inputs, same seed and step: the Metropolis test alone is the same test, bit for bit
+    Xs, Gs, lnps, naccs = X.clone(), G.clone(), lnp.clone(), nacc.clone()
+    _lib.call("linna_hmc_accept", _lib.ctx(), B, ndim, _lib.ptr(mass), C.c_uint64(1), _lib.iptr(step), _lib.ptr(H0), _lib.ptr(P), ld,
+              _lib.ptr(Qn), ld, _lib.ptr(lnp_new), _lib.ptr(Gn), ld, _lib.ptr(U), _lib.ptr(Xs), ld, _lib.ptr(lnps), _lib.ptr(Gs),
+              _lib.iptr(naccs), _lib.stream())
     _lib.call("linna_hmc_accept_adapt", _lib.ctx(), B, ndim, _lib.ptr(mass), C.c_uint64(1), _lib.iptr(step), 0, _lib.ptr(H0), _lib.ptr(P),
               ld, _lib.ptr(Qn), ld, _lib.ptr(lnp_new), _lib.ptr(Gn), ld, _lib.ptr(U), _lib.ptr(X), ld, _lib.ptr(lnp), _lib.ptr(G),
               _lib.iptr(nacc), _lib.ptr(alpha), None, None, None, None, None, 0, 0.65, _lib.ptr(chain), _lib.ptr(logps), _lib.stream())
@@ -174,6 +180,9 @@ def test_accept_adapt_acceptance_table(ndim):
         np.testing.assert_array_equal(_bits(now)[want], _bits(new)[want])
     np.testing.assert_array_equal(_bits(chain), _bits(X[:, :ndim]))
     np.testing.assert_array_equal(_bits(logps), _bits(lnp))
+    for plain, adapt in ((Xs, X), (lnps, lnp), (Gs, G)):
+        np.testing.assert_array_equal(_bits(plain), _bits(adapt))
+    np.testing.assert_array_equal(naccs.cpu().numpy(), nacc.cpu().numpy())
     f = np.float32
     with np.errstate(invalid="ignore", over="ignore"):
         ke = f(0.5) * np.sum(t["P"] * t["P"] / t["mass"][None, :], -1, dtype=f)
