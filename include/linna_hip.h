@@ -609,7 +609,7 @@ int linna_slice_points(linna_ctx_t* ctx, const float* coords, int ldc, int ndim,
 /* counters: [0] expansions, [1] contractions (zeus' mu tuning), [slot] walkers still active after this call */
 int linna_slice_expand(linna_ctx_t* ctx, const float* Z0, const float* ZL, const float* ZR, float* L, float* R,
                        int* flags, int ns, int* counters, int slot, void* stream);
-/* `ntrial` shrink trials per call, placed as the sequential procedure would place them if every
+/* `ntrial` (1 to 64) shrink trials per call, placed as the sequential procedure would place them if every
  * earlier one were rejected (the bracket after a rejection depends on where the trial fell, not on
  * its density): W[j*ns + k], Ztrial[j*ns + k]; Philox sub-counters round+1 .. round+ntrial.  Two
  * trials per round fill the GPU (2 x nw/2 points per launch) and halve the number of rounds; the
@@ -633,7 +633,9 @@ int linna_slice_commit(linna_ctx_t* ctx, float* coords, int ldc, int ndim, float
  * synchronisation.  The accepted points are those of the one-point-per-round procedure.
  * Rounds after the first evaluate only the walkers still active (listed and counted on the device), so a schedule that
  * looks further ahead each round (1, 2, 4, 8 ...) costs little and keeps the number of rounds small; rounds behind the one
- * that finished the last walker leave at once.  m_sched / nt_sched: HOST arrays; M = max m_sched, T = max nt_sched:
+ * that finished the last walker leave at once.  m_sched / nt_sched: HOST arrays, 1 <= m_sched[r] <= 32 and
+ * 1 <= nt_sched[r] <= 64 (the logic kernels hold a round's bracket ends and trials in one wavefront's lanes; anything else is
+ * LINNA_ERR_INVALID before any launch); M = max m_sched, T = max nt_sched:
  *   state[5 ns]  : Z0 | L | R | Wacc | Zacc;  flags[3 ns];  W[2 M ns], Wd[T ns], Zt[max(2 M, T) ns],
  *   list[max(2 M, T) ns] (the trial points of the walkers still active, for the rounds after the first): scratch
  *   counters[5 + 2 (nexp_rounds + nshr_rounds)]: [0] expansions, [1] contractions (zeroed first when zero_totals),

@@ -1262,8 +1262,11 @@ int linna_slice_half_step(linna_logprob_t* lp, float* coords, int ldc, int ndim,
         set_error("slice_half_step: bad arguments"); return LINNA_ERR_INVALID;
     }
     if (maxsteps < 1) { set_error("slice_half_step: maxsteps %d < 1", maxsteps); return LINNA_ERR_INVALID; }
-    for (int r = 0; r < nexp_rounds; ++r) if (m_sched[r] < 1) { set_error("slice_half_step: m_sched[%d] = %d", r, m_sched[r]); return LINNA_ERR_INVALID; }
-    for (int r = 0; r < nshr_rounds; ++r) if (nt_sched[r] < 1) { set_error("slice_half_step: nt_sched[%d] = %d", r, nt_sched[r]); return LINNA_ERR_INVALID; }
+    // (a round's bracket ends, 32 per side, and trials are held in one wave's lanes by the logic kernels: common.h)
+    for (int r = 0; r < nexp_rounds; ++r)
+        if (m_sched[r] < 1 || m_sched[r] > 32) { set_error("slice_half_step: m_sched[%d] = %d (1 to 32 bracket ends per side)", r, m_sched[r]); return LINNA_ERR_INVALID; }
+    for (int r = 0; r < nshr_rounds; ++r)
+        if (nt_sched[r] < 1 || nt_sched[r] > 64) { set_error("slice_half_step: nt_sched[%d] = %d (1 to 64 trials)", r, nt_sched[r]); return LINNA_ERR_INVALID; }
     if (ndim != lp->d.nin) { set_error("slice_half_step: ndim %d, log-probability has %d parameters", ndim, lp->d.nin); return LINNA_ERR_INVALID; }
     if (!lp_runs_fused_move(lp)) {
         set_error("slice_half_step: this log-probability does not run the whole-network kernel");
@@ -1278,8 +1281,7 @@ int linna_slice_half_step(linna_logprob_t* lp, float* coords, int ldc, int ndim,
     const SliceBegin sb{logp, ccoords, ldcc, C_idx, nc, mu, seed, step_dev, half, m_sched[0], DIR, ldd, Z0, L, R, flags, counters,
                         nexp_rounds + nshr_rounds, zero_totals, maxsteps};
     if (!begin_fused)
-        TRY(launch_slice_begin(logp, S_idx, ns, ccoords, ldcc, C_idx, nc, ndim, mu, seed, step_dev, half, DIR, ldd, Z0, L, R, flags, W, m_sched[0],
-                               counters, nexp_rounds + nshr_rounds, zero_totals, maxsteps, st));
+        TRY(launch_slice_begin(sb, S_idx, ns, ndim, W, st));
     int slot = 4;
     // ONE stepping-out round (small ensembles): its logic kernel is not launched -- the first shrinking round's evaluation
     // derives its trial points from the stepping-out round's results in its prologue (NsArgs::sl_*), and the first shrinking
@@ -1807,8 +1809,9 @@ int linna_slice_init(linna_ctx_t*, const float* logp, const int* S_idx, int ns, 
                      int ldd, float* Z0, float* L, float* R, int* flags, int maxsteps, void* stream) try {
     if (ns < 1 || nc < 2) { set_error("slice_init: need >= 2 complementary walkers"); return LINNA_ERR_INVALID; }
     if (maxsteps < 1) { set_error("slice_init: maxsteps %d < 1", maxsteps); return LINNA_ERR_INVALID; }
-    return launch_slice_init(logp, S_idx, ns, cc, ldcc, C_idx, nc, ndim, mu, seed, step_dev, stream_id, DIR, ldd, Z0, L, R,
-                             flags, maxsteps, S(stream));
+    // the set-up kernel of linna_slice_half_step without its first round's bracket ends and its usage counters
+    const SliceBegin sb{logp, cc, ldcc, C_idx, nc, mu, seed, step_dev, stream_id, 0, DIR, ldd, Z0, L, R, flags, nullptr, 0, 0, maxsteps};
+    return launch_slice_begin(sb, S_idx, ns, ndim, nullptr, S(stream));
 } LINNA_CATCH_INT
 int linna_slice_points(linna_ctx_t*, const float* coords, int ldc, int ndim, const int* S_idx, int ns, const float* DIR,
                        int ldd, const float* w, float* Q, int ldq, int nrep, void* stream) try {
@@ -1821,12 +1824,12 @@ int linna_slice_expand(linna_ctx_t*, const float* Z0, const float* ZL, const flo
 } LINNA_CATCH_INT
 int linna_slice_draw(linna_ctx_t*, const float* L, const float* R, const int* S_idx, float* W, const int* flags, int ns,
                      uint64_t seed, const int* step_dev, int stream_id, int round, int ntrial, void* stream) try {
-    if (ntrial < 1) { set_error("slice_draw: ntrial < 1"); return LINNA_ERR_INVALID; }
+    if (ntrial < 1 || ntrial > 64) { set_error("slice_draw: ntrial %d (1 to 64)", ntrial); return LINNA_ERR_INVALID; }
     return launch_slice_draw(L, R, S_idx, W, flags, ns, seed, step_dev, stream_id, round, ntrial, S(stream));
 } LINNA_CATCH_INT
 int linna_slice_shrink(linna_ctx_t*, const float* Z0, const float* Zt, float* L, float* R, const float* W, int* flags,
                        float* Wacc, float* Zacc, int ns, int* counters, int slot, int ntrial, void* stream) try {
-    if (ntrial < 1) { set_error("slice_shrink: ntrial < 1"); return LINNA_ERR_INVALID; }
+    if (ntrial < 1 || ntrial > 64) { set_error("slice_shrink: ntrial %d (1 to 64)", ntrial); return LINNA_ERR_INVALID; }
     return launch_slice_shrink(Z0, Zt, L, R, W, flags, Wacc, Zacc, ns, counters, slot, ntrial, S(stream));
 } LINNA_CATCH_INT
 int linna_slice_commit(linna_ctx_t*, float* coords, int ldc, int ndim, float* logp, const int* S_idx, int ns,

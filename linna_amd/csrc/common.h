@@ -37,14 +37,19 @@ __device__ __forceinline__ U4 walker_bits(uint64_t seed, uint32_t w, uint32_t st
     return philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
 }
 
-// ---- the logic of one shrinking round of linna_slice_half_step for walker k of the half ensemble (pointwise.hip's comment
-// block "one-call half step" has the procedure).  Shared by slice_shrink_multi_kernel and by the tail of the whole-network
-// kernel (net_stream.hip: the last workgroup of a round's evaluation runs this over the walkers, no launch of its own).
+// ---- ensemble slice sampling: the rules of one half step, each written ONCE below with a WAVE per walker -- the set-up
+// (slice_setup_wave), stepping out (slice_expand_wave), trial placement (slice_draw_wave), judging a round's trials
+// (slice_judge_wave) and the commit (slice_commit_wave).  Every slice logic kernel of pointwise.hip is a thin wrapper of them:
+// those of the round-by-round entries and those of linna_slice_half_step (pointwise.hip's comment block "one-call half step"
+// has its procedure; slice_round_wave below is one of its shrinking rounds).  The ONLY other statements of these rules are the
+// per-row forms in the prologue of the whole-network kernel (net_stream_body.inc, MOVE == 2), which forms its trial points
+// itself: the set-up at lines 153-188 (row j ns + k forms its walker's direction and bracket end; the rows j = 0 also write
+// them for the later launches) and, for the first shrinking round behind ONE stepping-out round, stepping out and trial
+// placement at lines 190-215 (NsArgs::sl_*).  A change to a rule is made here and there.
 // counters: [0] expansions, [1] contractions, [2] walkers left unfinished by the rounds of a call (sticky),
 //           [3] evaluated points, [4 + r] walkers still active after round r (expand rounds first, then shrink rounds)
-// The set-up of a half step (slice_begin_kernel: differential-move direction, slice height, initial bracket, flags, the usage
-// counters' roll) as the first stepping-out round's evaluation does it in its own prologue (net_stream.hip, MOVE == 2): row
-// j ns + k forms its walker's direction and bracket end itself; the rows j = 0 also write them for the later launches.
+// What a set-up needs besides the walkers (S, ns, ndim) and, where a launch of its own does it, the first round's bracket ends
+// W; `m`, `counters` (with nslots, zero_totals: the usage counters' roll) are used by linna_slice_half_step only.
 struct SliceBegin {
     const float* logp; const float* cc; int ldcc; const int* C; int nc; const float* mu; uint64_t seed; const int* step; int half, m;
     float* DIR; int ldd; float* Z0; float* L; float* R; int* flags; int* counters; int nslots, zero_totals;
@@ -75,98 +80,6 @@ struct SliceRound {
     // was not launched (the evaluation derived its trials itself, NsArgs::sl_*): its bookkeeping is done here first, from Ze
     const float* Ze; int m_derive, eslot;
 };
-__device__ __forceinline__ void slice_draw_dev(int k, int wk, float l, float r, float* __restrict__ W, int ns, uint64_t seed,
-                                               uint32_t step, int stream_id, int round, int ntrial) {
-    for (int j = 0; j < ntrial; ++j) {
-        const U4 b = walker_bits(seed, (uint32_t)wk, step, (uint32_t)stream_id, (uint32_t)(round + j + 1));
-        const float w = l + u01(b.x) * (r - l);
-        W[(size_t)j * ns + k] = w;
-        if (w < 0.f) l = w; else r = w;
-    }
-}
-// stepping out over the m ends per side one round evaluated (Zt[j ns + k]: lnP at L - j, j < m, and at R + (j - m)); returns
-// whether the walker is still stepping out
-__device__ __forceinline__ bool slice_expand_walker(int k, int ns, int m, float z0, const float* __restrict__ Zt, float& l, float& r,
-                                                    int* __restrict__ flags, int* __restrict__ counters) {
-    int n = 0;
-    int fl = flags[3 * k], fr = flags[3 * k + 1];
-    if (fl) {
-        int j = 0;
-        for (; j < m; ++j) { if (!(Zt[(size_t)j * ns + k] > z0)) break; }
-        const int nl = slice_side_steps(fl, j, m);
-        for (int i = 0; i < nl; ++i) l -= 1.f;
-        n += nl;
-        flags[3 * k] = fl;
-    }
-    if (fr) {
-        int j = 0;
-        for (; j < m; ++j) { if (!(Zt[(size_t)(m + j) * ns + k] > z0)) break; }
-        const int nr = slice_side_steps(fr, j, m);
-        for (int i = 0; i < nr; ++i) r += 1.f;
-        n += nr;
-        flags[3 * k + 1] = fr;
-    }
-    if (n) atomicAdd(counters + 0, n);
-    return (flags[3 * k] | flags[3 * k + 1]) != 0;
-}
-__device__ __forceinline__ void slice_round_walker(const SliceRound& a, int k) {
-    const int ns = a.ns;
-    if (k == 0) {
-        if (a.m_derive) atomicAdd(a.counters + 3, 2 * a.m_derive * ns);
-        atomicAdd(a.counters + 3, a.ntrial * (a.prev_slot < 0 ? ns : a.counters[a.prev_slot]));      // the points this round evaluated
-    }
-    if (k >= ns) return;
-    const uint32_t step = (uint32_t)a.step_dev[0];
-    if (a.m_derive) {
-        float l = a.L[k], r = a.R[k];
-        const bool out = slice_expand_walker(k, ns, a.m_derive, a.Z0[k], a.Ze, l, r, a.flags, a.counters);
-        a.L[k] = l; a.R[k] = r;
-        if (out) atomicAdd(a.counters + a.eslot, 1);
-        else slice_draw_dev(k, a.S[k], l, r, a.W, ns, a.seed, step, a.stream_id, 0, a.ntrial);   // the trials the evaluation derived
-    }
-    const bool mine = a.flags[3 * k + 2] && !(a.flags[3 * k] | a.flags[3 * k + 1]) &&      // not done, and its bracket closed
-                      !(a.prev_slot >= 0 && a.counters[a.prev_slot] == 0);
-    if (mine) {
-        int ncon = 0;
-        bool active = true;
-        float l = a.L[k], r = a.R[k];
-        const float z0 = a.Z0[k];
-        for (int j = 0; j < a.ntrial && active; ++j) {
-            const float zt = a.Zt[(size_t)j * ns + k], w = a.W[(size_t)j * ns + k];
-            if (!(z0 < zt)) {                               // zeus accepts iff Z0 < lnP(x'); NaN rejects
-                if (w < 0.f) l = w; else r = w;
-                ++ncon;
-                if (r - l < 1e-30f) { active = false; a.Wacc[k] = 0.f; a.Zacc[k] = z0; }   // degenerate: stay put
-            } else {
-                active = false; a.Wacc[k] = w; a.Zacc[k] = zt;
-            }
-        }
-        a.L[k] = l; a.R[k] = r;
-        if (ncon) atomicAdd(a.counters + 1, ncon);
-        if (active) {
-            const int pos = atomicAdd(a.counters + a.slot, 1);
-            slice_draw_dev(k, a.S[k], l, r, a.W, ns, a.seed, step, a.stream_id, a.trials_so_far, a.nt_next);   // the next round's trials
-            for (int j = 0; j < a.nt_next; ++j) a.list[(size_t)pos * a.nt_next + j] = j * ns + k;
-        } else {
-            a.flags[3 * k + 2] = 0;
-        }
-    }
-    if (a.coords) {
-        // the move of every finished walker (slice_commit_checked_kernel's arithmetic); a walker the rounds of the call left
-        // unfinished stays where it is and is counted; `bump` advances the device step counter behind an iteration's second half step
-        if (a.flags[3 * k] | a.flags[3 * k + 1] | a.flags[3 * k + 2]) {
-            atomicAdd(a.counters + 2, 1);
-        } else if (a.Wacc[k] != 0.f) {
-            const int wk = a.S[k];
-            const float wa = a.Wacc[k];
-            for (int d = 0; d < a.ndim; ++d) a.coords[(size_t)wk * a.ldc + d] += wa * a.DIR[(size_t)k * a.ldd + d];
-            a.logp[wk] = a.Zacc[k];
-        }
-        // (the last round draws no further trials: no thread of this launch uses the counter's value, whichever it reads)
-        if (a.bump && k == 0) a.step_dev[0] = (int)step + 1;
-    }
-}
-
 // counters[i] += the sum over the block's waves of v (wave-uniform); every thread of the block calls
 __device__ __forceinline__ void block_add_counter(int* __restrict__ counter, int v, int* lds_slot) {
     if (threadIdx.x == 0) *lds_slot = 0;
@@ -175,12 +88,39 @@ __device__ __forceinline__ void block_add_counter(int* __restrict__ counter, int
     __syncthreads();
     if (threadIdx.x == 0 && *lds_slot) atomicAdd(counter, *lds_slot);
 }
-// ---- the same logic with a WAVE per walker (all 64 lanes call with the same k): the bracket ends / trials of a round are loaded,
-// and the Philox draws of the next round made, one per lane; what is sequential in the procedure (a bracket shrinking trial by
-// trial) is a short uniform loop over register values.  One thread per walker ran 16-32 dependent Philox draws and as many
-// dependent loads: 5-10 us per logic kernel, a third of a 128-walker iteration.  Same arithmetic in the same order: same chain.
+// ---- the rules, a WAVE per walker (all 64 lanes call with the same k, in wave-uniform control flow): the bracket ends / trials of
+// a round are loaded, and the Philox draws of the next round made, one per lane; what is sequential in the procedure (a bracket
+// shrinking trial by trial) is a short uniform loop over register values.  One thread per walker ran 16-32 dependent Philox
+// draws and as many dependent loads: 5-10 us per logic kernel, a third of a 128-walker iteration.  A round therefore holds at
+// most 32 bracket ends per side and 64 trials (the entries reject more).
 __device__ __forceinline__ float wave_lane_f(float v, int j) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), j)); }
-// trial j + 1 of (round0 ...) placed as if its predecessors were rejected (slice_draw_dev); lane j < cnt returns w_j
+// the set-up of walker k: the differential move's direction between two DISTINCT complementary walkers, a uniform height under
+// the density, a unit bracket placed uniformly around 0, the stepping-out budget into the flags; W (nullable): the b.m bracket
+// ends per side the first stepping-out round evaluates, L - j and R + j
+__device__ __forceinline__ void slice_setup_wave(const SliceBegin& b, const int* __restrict__ S, int ns, int ndim, float* __restrict__ W,
+                                                 int k, int lane) {
+    const int wk = S[k];
+    const uint32_t step = (uint32_t)b.step[0];
+    const U4 r = walker_bits(b.seed, (uint32_t)wk, step, (uint32_t)b.half, 0u);
+    const int ia = (int)(((uint64_t)r.x * (uint64_t)b.nc) >> 32);
+    int ib = (int)(((uint64_t)r.y * (uint64_t)(b.nc - 1)) >> 32);
+    ib += (ib >= ia);
+    const float* ca = b.cc + (size_t)b.C[ia] * b.ldcc;
+    const float* cb = b.cc + (size_t)b.C[ib] * b.ldcc;
+    const float mu = b.mu[0];
+    for (int d = lane; d < b.ldd; d += 64) b.DIR[(size_t)k * b.ldd + d] = d < ndim ? mu * (ca[d] - cb[d]) : 0.f;
+    const float l = -u01(r.w);
+    if (lane == 0) {
+        b.Z0[k] = b.logp[wk] + logf(u01(r.z));           // log of a uniform height under the density
+        b.L[k] = l; b.R[k] = l + 1.f;
+        int J, K;
+        slice_budget(b.seed, (uint32_t)wk, step, (uint32_t)b.half, b.maxsteps, J, K);
+        b.flags[3 * k] = J; b.flags[3 * k + 1] = K; b.flags[3 * k + 2] = 1;
+    }
+    if (W && lane < b.m) { W[(size_t)lane * ns + k] = l - (float)lane; W[(size_t)(b.m + lane) * ns + k] = l + 1.f + (float)lane; }
+}
+// trial placement: trial j + 1 of (round0 ...) placed as if its predecessors were rejected -- the bracket after a rejection depends
+// on where the trial fell, not on its density; Philox sub-counter round0 + j + 1; lane j < cnt returns w_j
 __device__ __forceinline__ float slice_draw_wave(int lane, int wk, float l, float r, uint64_t seed, uint32_t step, int stream_id,
                                                  int round0, int cnt) {
     const U4 b = walker_bits(seed, (uint32_t)wk, step, (uint32_t)stream_id, (uint32_t)(round0 + lane + 1));
@@ -193,11 +133,14 @@ __device__ __forceinline__ float slice_draw_wave(int lane, int wk, float l, floa
     }
     return mine;
 }
-// stepping out over m <= 32 ends per side: lanes 0..m-1 the left ends, 32..32+m-1 the right ones; fl / fr updated
-__device__ __forceinline__ void slice_expand_wave(int lane, int k, int ns, int m, float z0, const float* __restrict__ Zt, float& l, float& r,
-                                                  int& fl, int& fr, int* __restrict__ flags, int& nexp) {
+// stepping out over the m <= 32 ends per side one round evaluated (ZL[j ns + k]: lnP at L - j, ZR[j ns + k]: at R + j): an end
+// moves out by one unit while the density there is above the slice and its budget lasts.  Lanes 0..m-1 the left ends,
+// 32..32+m-1 the right ones; l / r, fl / fr (and the flags in memory) updated, the steps taken added to nexp
+__device__ __forceinline__ void slice_expand_wave(int lane, int k, int ns, int m, float z0, const float* __restrict__ ZL,
+                                                  const float* __restrict__ ZR, float& l, float& r, int& fl, int& fr,
+                                                  int* __restrict__ flags, int& nexp) {
     const int side = lane >> 5, j = lane & 31;
-    const float ze = j < m ? Zt[(size_t)(side * m + j) * ns + k] : 0.f;
+    const float ze = j < m ? (side ? ZR : ZL)[(size_t)j * ns + k] : 0.f;
     const unsigned long long bal = __ballot(j < m && ze > z0);
     const int fl0 = fl, fr0 = fr;
     const int nl = slice_side_steps(fl, __builtin_ctzll(~(unsigned long long)(uint32_t)bal), m);
@@ -208,14 +151,40 @@ __device__ __forceinline__ void slice_expand_wave(int lane, int k, int ns, int m
     if (lane == 0 && fr != fr0) flags[3 * k + 1] = fr;
     nexp += nl + nr;
 }
-// nexp / ncon: this walker's expansions / contractions, which the caller adds to counters[0] / [1] (summed over the block first:
-// one atomic per walker on one address cost 10-15 us of a 4096-walker round)
-__device__ __forceinline__ void slice_round_wave(const SliceRound& a, int k, int lane, int& nexp, int& ncon_out) {
-    const int ns = a.ns;
-    if (a.ntrial > 64 || a.nt_next > 64 || a.m_derive > 32) {       // (schedules beyond a wave's lanes: one lane, the plain procedure)
-        if (lane == 0) slice_round_walker(a, k);                    //  -- counts itself
-        return;
+// judging a round's trials (lane j < ntrial holds trial j: its weight w and lnP zt): the bracket is pulled in to every trial
+// before the first one inside the slice (counted in ncon).  Returns whether the walker is still shrinking; if not, wacc / zacc
+// are the accepted weight and its lnP -- 0 and z0 where the bracket became degenerate (the walker stays put)
+__device__ __forceinline__ bool slice_judge_wave(int lane, int ntrial, float z0, float w, float zt, float& l, float& r, int& ncon,
+                                                 float& wacc, float& zacc) {
+    const unsigned long long okm = __ballot(lane < ntrial && z0 < zt);       // zeus accepts iff Z0 < lnP(x'); NaN rejects
+    const int ja = okm ? __builtin_ctzll(okm) : ntrial;                      // the first trial inside the slice
+    for (int j = 0; j < ja; ++j) {
+        const float wj = wave_lane_f(w, j);
+        if (wj < 0.f) l = wj; else r = wj;
+        ++ncon;
+        if (r - l < 1e-30f) { wacc = 0.f; zacc = z0; return false; }
     }
+    if (ja == ntrial) return true;
+    wacc = wave_lane_f(w, ja); zacc = wave_lane_f(zt, ja);
+    return false;
+}
+// the commit of walker k (= walker wk of the ensemble): x += Wacc DIR and its lnP; Wacc == 0 stays put.  `unfinished` (a caller
+// with flags: one of the walker's is still set): the walker stays where it is and is counted in counters[2]
+__device__ __forceinline__ void slice_commit_wave(int lane, int k, int wk, bool unfinished, int* __restrict__ counters, float wacc,
+                                                  float zacc, float* __restrict__ coords, int ldc, int ndim, float* __restrict__ logp,
+                                                  const float* __restrict__ DIR, int ldd) {
+    if (unfinished) {
+        if (lane == 0) atomicAdd(counters + 2, 1);
+    } else if (wacc != 0.f) {
+        for (int d = lane; d < ndim; d += 64) coords[(size_t)wk * ldc + d] += wacc * DIR[(size_t)k * ldd + d];
+        if (lane == 0) logp[wk] = zacc;
+    }
+}
+// one shrinking round of linna_slice_half_step for walker k.  nexp / ncon: this walker's expansions / contractions, which the
+// caller adds to counters[0] / [1] (summed over the block first: one atomic per walker on one address cost 10-15 us of a
+// 4096-walker round)
+__device__ __forceinline__ void slice_round_wave(const SliceRound& a, int k, int lane, int& nexp, int& ncon) {
+    const int ns = a.ns;
     if (k == 0 && lane == 0) {
         if (a.m_derive) atomicAdd(a.counters + 3, 2 * a.m_derive * ns);
         atomicAdd(a.counters + 3, a.ntrial * (a.prev_slot < 0 ? ns : a.counters[a.prev_slot]));      // the points this round evaluated
@@ -229,7 +198,7 @@ __device__ __forceinline__ void slice_round_wave(const SliceRound& a, int k, int
     float w = 0.f;                                     // lane j: trial j of this round
     bool have_w = false;
     if (a.m_derive) {
-        slice_expand_wave(lane, k, ns, a.m_derive, z0, a.Ze, l, r, fl, fr, a.flags, nexp);
+        slice_expand_wave(lane, k, ns, a.m_derive, z0, a.Ze, a.Ze + (size_t)a.m_derive * ns, l, r, fl, fr, a.flags, nexp);
         if (lane == 0) { a.L[k] = l; a.R[k] = r; }
         if (fl | fr) {
             if (lane == 0) atomicAdd(a.counters + a.eslot, 1);
@@ -246,19 +215,8 @@ __device__ __forceinline__ void slice_round_wave(const SliceRound& a, int k, int
         const bool in = lane < a.ntrial;
         const float zt = in ? a.Zt[(size_t)lane * ns + k] : 0.f;
         if (!have_w) w = in ? a.W[(size_t)lane * ns + k] : 0.f;
-        const unsigned long long okm = __ballot(in && z0 < zt);          // zeus accepts iff Z0 < lnP(x'); NaN rejects
-        const int ja = okm ? __builtin_ctzll(okm) : a.ntrial;          // the first trial inside the slice
-        int ncon = 0;
-        bool active = true;
-        for (int j = 0; j < ja; ++j) {
-            const float wj = wave_lane_f(w, j);
-            if (wj < 0.f) l = wj; else r = wj;
-            ++ncon;
-            if (r - l < 1e-30f) { active = false; wacc = 0.f; zacc = z0; break; }   // degenerate: stay put
-        }
-        if (active && ja < a.ntrial) { active = false; wacc = wave_lane_f(w, ja); zacc = wave_lane_f(zt, ja); }
+        const bool active = slice_judge_wave(lane, a.ntrial, z0, w, zt, l, r, ncon, wacc, zacc);
         if (lane == 0) { a.L[k] = l; a.R[k] = r; }
-        ncon_out += ncon;
         if (active) {
             int pos = 0;
             if (lane == 0) pos = atomicAdd(a.counters + a.slot, 1);
@@ -275,15 +233,10 @@ __device__ __forceinline__ void slice_round_wave(const SliceRound& a, int k, int
         }
     }
     if (a.coords) {
-        if (fl | fr | fs) {
-            if (lane == 0) atomicAdd(a.counters + 2, 1);
-        } else {
-            if (!done_now) { wacc = a.Wacc[k]; zacc = a.Zacc[k]; }
-            if (wacc != 0.f) {
-                for (int d = lane; d < a.ndim; d += 64) a.coords[(size_t)wk * a.ldc + d] += wacc * a.DIR[(size_t)k * a.ldd + d];
-                if (lane == 0) a.logp[wk] = zacc;
-            }
-        }
+        // the call's last round: the move of every finished walker (the last round draws no further trials: no thread of this
+        // launch uses the step counter's value, whichever it reads, so `bump` may advance it here)
+        if (!done_now) { wacc = a.Wacc[k]; zacc = a.Zacc[k]; }
+        slice_commit_wave(lane, k, wk, (fl | fr | fs) != 0, a.counters, wacc, zacc, a.coords, a.ldc, a.ndim, a.logp, a.DIR, a.ldd);
         if (a.bump && k == 0 && lane == 0) a.step_dev[0] = (int)step + 1;
     }
 }
@@ -365,9 +318,6 @@ int launch_hmc_find_eps_init(int B, int ndim, uint64_t seed, const int* step_dev
                              int* state, hipStream_t s);
 int launch_hmc_find_eps(int B, int ndim, const float* mass, const float* H0, const float* P, int ldp, const float* lnp_new,
                         const float* Gn, int ldg, float* eps, int* state, int* nactive, hipStream_t s);
-int launch_slice_init(const float* logp, const int* S, int ns, const float* cc, int ldcc, const int* C, int nc, int ndim,
-                      const float* mu, uint64_t seed, const int* step_dev, int stream_id, float* DIR, int ldd, float* Z0,
-                      float* L, float* R, int* flags, int maxsteps, hipStream_t s);
 int launch_slice_points(const float* coords, int ldc, int ndim, const int* S, int ns, const float* DIR, int ldd,
                         const float* w, float* Q, int ldq, int nrep, hipStream_t s);
 int launch_slice_expand(const float* Z0, const float* ZL, const float* ZR, float* L, float* R, int* flags, int ns,
@@ -376,15 +326,12 @@ int launch_slice_draw(const float* L, const float* R, const int* S, float* W, co
                       const int* step_dev, int stream_id, int round, int ntrial, hipStream_t s);
 int launch_slice_shrink(const float* Z0, const float* Zt, float* L, float* R, const float* W, int* flags, float* Wacc,
                         float* Zacc, int ns, int* counters, int slot, int ntrial, hipStream_t s);
-int launch_slice_begin(const float* logp, const int* S, int ns, const float* cc, int ldcc, const int* C, int nc, int ndim,
-                       const float* mu, uint64_t seed, const int* step_dev, int stream_id, float* DIR, int ldd, float* Z0, float* L,
-                       float* R, int* flags, float* W, int m, int* counters, int nslots, int zero_totals, int maxsteps, hipStream_t s);
+// the one set-up launcher: W (the first round's bracket ends) and b.counters (the usage counters' roll) are each nullable
+int launch_slice_begin(const SliceBegin& b, const int* S, int ns, int ndim, float* W, hipStream_t s);
 int launch_slice_expand_multi(const float* Z0, const float* Zt, float* L, float* R, const int* S, int* flags, int ns, int m,
                               int m_next, int* counters, int slot, int prev_slot, float* W, float* Wd, int* list, uint64_t seed,
                               const int* step_dev, int stream_id_shrink, int ntrial, hipStream_t s);
 int launch_slice_shrink_multi(const SliceRound& a, hipStream_t s);
-int launch_slice_commit_checked(float* coords, int ldc, int ndim, float* logp, const int* S, int ns, const float* DIR, int ldd,
-                                const float* Wacc, const float* Zacc, const int* flags, int* counters, hipStream_t s);
 int launch_slice_commit(float* coords, int ldc, int ndim, float* logp, const int* S, int ns, const float* DIR, int ldd,
                         const float* Wacc, const float* Zacc, hipStream_t s);
 int launch_step_increment(int* step, hipStream_t s);

@@ -117,7 +117,7 @@ struct NsArgs {
     // MOVE == 2, sl_Zt != null: the FIRST shrinking round of a half step whose stepping-out was one round of sl_m bracket ends per
     // side -- the trial weight of row j ns + k is derived here from that round's results instead of being read: bracket
     // [L, R] pushed out while lnP at the ends exceeds Z0 (slice_expand_multi_kernel), then trial j placed as if its
-    // predecessors were rejected (slice_draw_dev: Philox (walker, step, stream, sub j + 1)).  Saves the launch between them.
+    // predecessors were rejected (slice_draw_wave's rule: Philox (walker, step, stream, sub j + 1)).  Saves the launch between them.
     const float* sl_Z0; const float* sl_L; const float* sl_R; const float* sl_Zt; int sl_m, sl_nt;
     unsigned long long sl_seed; const int* sl_step; int sl_stream; const int* sl_flags;
     SliceBegin sb;                      // MOVE == 2, sb.logp != null: the half step's set-up in this launch's prologue (common.h)

@@ -631,31 +631,24 @@ __global__ void step_increment_kernel(int* step) { step[0] += 1; }
 
 // ------------------------------------------------------------------ ensemble slice sampling (zeus, Karamanis & Beutler 2021)
 // state per active walker k: direction DIR[k][:], slice height Z0, bracket [L, R] in units of the
-// direction, flags aL/aR (still stepping out) and aS (still shrinking).
-__global__ void slice_init_kernel(const float* __restrict__ logp, const int* __restrict__ S, int ns,
-                                  const float* __restrict__ cc, int ldcc, const int* __restrict__ C, int nc, int ndim,
-                                  const float* __restrict__ mu, uint64_t seed, const int* __restrict__ step_dev,
-                                  int stream_id, float* __restrict__ DIR, int ldd, float* __restrict__ Z0,
-                                  float* __restrict__ L, float* __restrict__ R, int* __restrict__ flags, int maxsteps) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (size_t)ns * ldd) return;
-    const int k = (int)(idx / ldd), d = (int)(idx % ldd);
-    const int wk = S[k];
-    const U4 r = walker_bits(seed, (uint32_t)wk, (uint32_t)step_dev[0], (uint32_t)stream_id, 0u);
-    // differential move: two DISTINCT complementary walkers
-    const int ia = (int)(((uint64_t)r.x * (uint64_t)nc) >> 32);
-    int ib = (int)(((uint64_t)r.y * (uint64_t)(nc - 1)) >> 32);
-    ib += (ib >= ia);
-    if (d < ndim) DIR[idx] = mu[0] * (cc[(size_t)C[ia] * ldcc + d] - cc[(size_t)C[ib] * ldcc + d]);
-    else DIR[idx] = 0.f;
-    if (d == 0) {
-        Z0[k] = logp[wk] + logf(u01(r.z));           // log of a uniform height under the density
-        const float l = -u01(r.w);
-        L[k] = l; R[k] = l + 1.f;
-        int J, K;
-        slice_budget(seed, (uint32_t)wk, (uint32_t)step_dev[0], (uint32_t)stream_id, maxsteps, J, K);
-        flags[3 * k] = J; flags[3 * k + 1] = K; flags[3 * k + 2] = 1;
+// direction, flags aL/aR (still stepping out) and aS (still shrinking).  The rules are common.h's wave-per-walker routines;
+// every logic kernel below gives each wave of a block one walker and sums the block's counts before they reach the counters.
+constexpr int SLICE_WAVES = 16;                        // waves (walkers) per block of the slice logic kernels
+static dim3 slice_grid(int ns) { return dim3((ns + SLICE_WAVES - 1) / SLICE_WAVES); }
+
+// the set-up of a half step: linna_slice_init, and linna_slice_half_step where its first evaluation does not do it in its
+// prologue; with b.counters also the roll of that entry's usage counters
+__global__ void slice_begin_kernel(const SliceBegin b, const int* __restrict__ S, int ns, int ndim, float* __restrict__ W) {
+    const int k = blockIdx.x * SLICE_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (b.counters && blockIdx.x == 0 && threadIdx.x == 0) {
+        for (int i = 0; i < b.nslots; ++i) {           // [4 + nslots + i]: the same counts summed over the calls so far (usage statistics)
+            b.counters[4 + b.nslots + i] += b.counters[4 + i];
+            b.counters[4 + i] = 0;
+        }
+        b.counters[4 + 2 * b.nslots] += 1;             // calls
+        if (b.zero_totals) { b.counters[0] = 0; b.counters[1] = 0; }
     }
+    if (k < ns) slice_setup_wave(b, S, ns, ndim, W, k, lane);
 }
 
 // Q[j*ns + k][:] = X[S[k]][:] + w[j*ns + k] * DIR[k][:]   for j < nrep
@@ -668,36 +661,35 @@ __global__ void slice_points_kernel(const float* __restrict__ coords, int ldc, i
     Q[idx] = d < ndim ? coords[(size_t)S[k] * ldc + d] + w[row] * DIR[(size_t)k * ldd + d] : 0.f;
 }
 
+// ---- the round-by-round entries: one bracket end per side, or `ntrial` trials, per launch; the host loops on counters[slot]
 // stepping out: while the density at an end is above the slice, push that end out by one unit
 __global__ void slice_expand_kernel(const float* __restrict__ Z0, const float* __restrict__ ZL, const float* __restrict__ ZR,
                                     float* __restrict__ L, float* __restrict__ R, int* __restrict__ flags, int ns,
                                     int* __restrict__ counters, int slot) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= ns) return;
-    int n = 0;
-    int fl = flags[3 * k], fr = flags[3 * k + 1];                           // steps left of the budget; 0: that side is closed
-    if (fl) { const int s = slice_side_steps(fl, ZL[k] > Z0[k] ? 1 : 0, 1); if (s) L[k] -= 1.f; n += s; flags[3 * k] = fl; }
-    if (fr) { const int s = slice_side_steps(fr, ZR[k] > Z0[k] ? 1 : 0, 1); if (s) R[k] += 1.f; n += s; flags[3 * k + 1] = fr; }
-    if (n) atomicAdd(counters + 0, n);                                      // [0] expansions
-    if (fl | fr) atomicAdd(counters + slot, 1);                             // [slot] still-active count
+    __shared__ int sums[2];
+    const int k = blockIdx.x * SLICE_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    int nexp = 0, active = 0;
+    if (k < ns) {
+        int fl = flags[3 * k], fr = flags[3 * k + 1];                       // steps left of the budget; 0: that side is closed
+        if (fl | fr) {
+            float l = L[k], r = R[k];
+            slice_expand_wave(lane, k, ns, 1, Z0[k], ZL, ZR, l, r, fl, fr, flags, nexp);
+            if (lane == 0) { L[k] = l; R[k] = r; }
+            active = (fl | fr) != 0;
+        }
+    }
+    block_add_counter(counters + 0, nexp, sums);                            // [0] expansions
+    block_add_counter(counters + slot, active, sums + 1);                   // [slot] still-active count
 }
 
-// ntrial trials per launch, drawn as the SEQUENTIAL procedure would draw them if every earlier one
-// were rejected: the bracket after a rejection depends on where the trial fell, not on its density,
-// so trial j+1 can be placed before trial j has been evaluated.  W[j*ns + k]; Philox sub-counter
-// round + j + 1 (the stream of single-trial rounds).
+// ntrial <= 64 trials per launch, W[j*ns + k]; Philox sub-counter round + j + 1 (the stream of single-trial rounds)
 __global__ void slice_draw_kernel(const float* __restrict__ L, const float* __restrict__ R, const int* __restrict__ S,
                                   float* __restrict__ W, const int* __restrict__ flags, int ns, uint64_t seed,
                                   const int* __restrict__ step_dev, int stream_id, int round, int ntrial) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    const int k = blockIdx.x * SLICE_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (k >= ns || !flags[3 * k + 2]) return;
-    float l = L[k], r = R[k];
-    for (int j = 0; j < ntrial; ++j) {
-        const U4 b = walker_bits(seed, (uint32_t)S[k], (uint32_t)step_dev[0], (uint32_t)stream_id, (uint32_t)(round + j + 1));
-        const float w = l + u01(b.x) * (r - l);
-        W[(size_t)j * ns + k] = w;
-        if (w < 0.f) l = w; else r = w;
-    }
+    const float w = slice_draw_wave(lane, S[k], L[k], R[k], seed, (uint32_t)step_dev[0], stream_id, round, ntrial);
+    if (lane < ntrial) W[(size_t)lane * ns + k] = w;
 }
 
 // shrinking: accept the first trial inside the slice, otherwise pull the bracket in to each rejected trial
@@ -705,84 +697,40 @@ __global__ void slice_shrink_kernel(const float* __restrict__ Z0, const float* _
                                     float* __restrict__ R, const float* __restrict__ W, int* __restrict__ flags,
                                     float* __restrict__ Wacc, float* __restrict__ Zacc, int ns, int* __restrict__ counters,
                                     int slot, int ntrial) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= ns || !flags[3 * k + 2]) return;
-    int ncon = 0;
-    bool active = true;
-    for (int j = 0; j < ntrial && active; ++j) {
-        const float zt = Zt[(size_t)j * ns + k], w = W[(size_t)j * ns + k];
-        if (!(Z0[k] < zt)) {                                 // zeus accepts iff Z0 < lnP(x'); NaN rejects
-            if (w < 0.f) L[k] = w; else R[k] = w;
-            ++ncon;
-            if (R[k] - L[k] < 1e-30f) { active = false; Wacc[k] = 0.f; Zacc[k] = Z0[k]; }   // degenerate: stay put
-        } else {
-            active = false; Wacc[k] = w; Zacc[k] = zt;
+    __shared__ int sums[2];
+    const int k = blockIdx.x * SLICE_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    int ncon = 0, active = 0;
+    if (k < ns && flags[3 * k + 2]) {
+        const bool in = lane < ntrial;
+        const float w = in ? W[(size_t)lane * ns + k] : 0.f, zt = in ? Zt[(size_t)lane * ns + k] : 0.f;
+        float l = L[k], r = R[k], wacc = 0.f, zacc = 0.f;
+        active = slice_judge_wave(lane, ntrial, Z0[k], w, zt, l, r, ncon, wacc, zacc);
+        if (lane == 0) {
+            L[k] = l; R[k] = r;
+            if (!active) { flags[3 * k + 2] = 0; Wacc[k] = wacc; Zacc[k] = zacc; }
         }
     }
-    if (ncon) atomicAdd(counters + 1, ncon);              // [1] contractions
-    if (active) atomicAdd(counters + slot, 1);            // [slot] still-active count
-    else flags[3 * k + 2] = 0;
+    block_add_counter(counters + 1, ncon, sums);                            // [1] contractions
+    block_add_counter(counters + slot, active, sums + 1);                   // [slot] still-active count
 }
 
 __global__ void slice_commit_kernel(float* __restrict__ coords, int ldc, int ndim, float* __restrict__ logp,
                                     const int* __restrict__ S, int ns, const float* __restrict__ DIR, int ldd,
                                     const float* __restrict__ Wacc, const float* __restrict__ Zacc) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (size_t)ns * ndim) return;
-    const int k = (int)(idx / ndim), d = (int)(idx % ndim);
-    const int wk = S[k];
-    if (Wacc[k] != 0.f) {
-        coords[(size_t)wk * ldc + d] += Wacc[k] * DIR[(size_t)k * ldd + d];
-        if (d == 0) logp[wk] = Zacc[k];
-    }
+    const int k = blockIdx.x * SLICE_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (k < ns) slice_commit_wave(lane, k, S[k], false, nullptr, Wacc[k], Zacc[k], coords, ldc, ndim, logp, DIR, ldd);
 }
 
 // ---- one-call half step (linna_slice_half_step): the same procedure with SPECULATIVE rounds, so that a half step is a
 // fixed sequence of launches the host enqueues in one call and never waits for.  Stepping out: a round evaluates the
 // bracket ends the sequential loop would visit next, L, L-1, ..., L-(m-1) and R, R+1, ..., R+(m-1), in ONE launch, and
 // the logic below walks them in the loop's order; shrinking: `ntrial` trials per round, each placed as if its
-// predecessors were rejected (slice_draw_kernel's rule).  Same Philox counters, same comparisons, same accepted point
+// predecessors were rejected (slice_draw_wave's rule).  Same Philox counters, same comparisons, same accepted point
 // as the one-point-per-round procedure -- only the count of evaluated-and-discarded points differs.  Rounds after the
 // one that finishes the last walker are gated off on the device (the evaluation leaves at once on a zero count, the logic
 // kernels return per walker on its flags).
 // counters: [0] expansions, [1] contractions, [2] walkers left unfinished by the rounds of a call (sticky),
 //           [3] evaluated points, [4 + r] walkers still active after round r (expand rounds first, then shrink rounds)
-__global__ void slice_begin_kernel(const float* __restrict__ logp, const int* __restrict__ S, int ns,
-                                   const float* __restrict__ cc, int ldcc, const int* __restrict__ C, int nc, int ndim,
-                                   const float* __restrict__ mu, uint64_t seed, const int* __restrict__ step_dev,
-                                   int stream_id, float* __restrict__ DIR, int ldd, float* __restrict__ Z0,
-                                   float* __restrict__ L, float* __restrict__ R, int* __restrict__ flags,
-                                   float* __restrict__ W, int m, int* __restrict__ counters, int nslots, int zero_totals,
-                                   int maxsteps) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx == 0) {
-        for (int i = 0; i < nslots; ++i) {             // [4 + nslots + i]: the same counts summed over the calls so far (usage statistics)
-            counters[4 + nslots + i] += counters[4 + i];
-            counters[4 + i] = 0;
-        }
-        counters[4 + 2 * nslots] += 1;                 // calls
-        if (zero_totals) { counters[0] = 0; counters[1] = 0; }
-    }
-    if (idx >= (size_t)ns * ldd) return;
-    const int k = (int)(idx / ldd), d = (int)(idx % ldd);
-    const int wk = S[k];
-    const U4 r = walker_bits(seed, (uint32_t)wk, (uint32_t)step_dev[0], (uint32_t)stream_id, 0u);
-    const int ia = (int)(((uint64_t)r.x * (uint64_t)nc) >> 32);
-    int ib = (int)(((uint64_t)r.y * (uint64_t)(nc - 1)) >> 32);
-    ib += (ib >= ia);
-    if (d < ndim) DIR[idx] = mu[0] * (cc[(size_t)C[ia] * ldcc + d] - cc[(size_t)C[ib] * ldcc + d]);
-    else DIR[idx] = 0.f;
-    if (d == 0) {
-        Z0[k] = logp[wk] + logf(u01(r.z));
-        const float l = -u01(r.w);
-        L[k] = l; R[k] = l + 1.f;
-        int J, K;
-        slice_budget(seed, (uint32_t)wk, (uint32_t)step_dev[0], (uint32_t)stream_id, maxsteps, J, K);
-        flags[3 * k] = J; flags[3 * k + 1] = K; flags[3 * k + 2] = 1;
-        for (int j = 0; j < m; ++j) { W[(size_t)j * ns + k] = l - (float)j; W[(size_t)(m + j) * ns + k] = l + 1.f + (float)j; }
-    }
-}
-
 // Zt[j*ns + k]: lnP at L - j (j < m) and at R + (j - m) (m <= j < 2m) of the bracket this round started from; the next
 // round looks at m_next ends per side (0: this is the last stepping-out round)
 __device__ __forceinline__ int slice_expand_multi_wave(const float* __restrict__ Z0, const float* __restrict__ Zt, float* __restrict__ L,
@@ -797,21 +745,8 @@ __device__ __forceinline__ int slice_expand_multi_wave(const float* __restrict__
     if (prev_slot >= 0 && counters[prev_slot] == 0) return 0;     // (never: a walker with a flag set was counted)
     const float z0 = Z0[k];
     float l = L[k], r = R[k];
-    if (m > 32 || m_next > 32 || ntrial > 64) {                     // (schedules beyond a wave's lanes: one lane, the plain procedure)
-        if (lane) return 0;
-        const bool out = slice_expand_walker(k, ns, m, z0, Zt, l, r, flags, counters);        // (counts itself)
-        L[k] = l; R[k] = r;
-        if (out) {
-            const int pos = atomicAdd(counters + slot, 1);
-            for (int j = 0; j < m_next; ++j) { W[(size_t)j * ns + k] = l - (float)j; W[(size_t)(m_next + j) * ns + k] = r + (float)j; }
-            for (int j = 0; j < 2 * m_next; ++j) list[(size_t)pos * 2 * m_next + j] = j * ns + k;
-        } else {
-            slice_draw_dev(k, S[k], l, r, Wd, ns, seed, (uint32_t)step_dev[0], stream_id_shrink, 0, ntrial);
-        }
-        return 0;
-    }
     int nexp = 0;
-    slice_expand_wave(lane, k, ns, m, z0, Zt, l, r, fl, fr, flags, nexp);
+    slice_expand_wave(lane, k, ns, m, z0, Zt, Zt + (size_t)m * ns, l, r, fl, fr, flags, nexp);
     if (lane == 0) { L[k] = l; R[k] = r; }
     if (fl | fr) {
         int pos = 0;
@@ -832,39 +767,20 @@ __global__ void slice_expand_multi_kernel(const float* __restrict__ Z0, const fl
                                           float* __restrict__ Wd, int* __restrict__ list, uint64_t seed,
                                           const int* __restrict__ step_dev, int stream_id_shrink, int ntrial) {
     __shared__ int sums[1];
-    const int k = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;      // a wave per walker
+    const int k = blockIdx.x * SLICE_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int nexp = slice_expand_multi_wave(Z0, Zt, L, R, S, flags, ns, m, m_next, counters, slot, prev_slot, W, Wd, list, seed, step_dev,
                                              stream_id_shrink, ntrial, k, lane);
     block_add_counter(counters + 0, nexp, sums);
 }
 
-// one shrinking round (SliceRound / slice_round_walker in common.h); with `coords` the call's LAST one: the move of every
+// one shrinking round (SliceRound / slice_round_wave in common.h); with `coords` the call's LAST one: the move of every
 // finished walker is applied and `bump` advances the device step counter -- two launches less per iteration
 __global__ void slice_shrink_multi_kernel(const SliceRound a) {
     __shared__ int sums[2];
     int nexp = 0, ncon = 0;
-    slice_round_wave(a, blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), threadIdx.x & 63, nexp, ncon);     // a wave per walker
+    slice_round_wave(a, blockIdx.x * SLICE_WAVES + (threadIdx.x >> 6), threadIdx.x & 63, nexp, ncon);
     block_add_counter(a.counters + 0, nexp, sums);
     block_add_counter(a.counters + 1, ncon, sums + 1);
-}
-
-// the move of every finished walker; a walker the rounds of the call left unfinished stays where it is and is counted
-__global__ void slice_commit_checked_kernel(float* __restrict__ coords, int ldc, int ndim, float* __restrict__ logp,
-                                            const int* __restrict__ S, int ns, const float* __restrict__ DIR, int ldd,
-                                            const float* __restrict__ Wacc, const float* __restrict__ Zacc,
-                                            const int* __restrict__ flags, int* __restrict__ counters) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (size_t)ns * ndim) return;
-    const int k = (int)(idx / ndim), d = (int)(idx % ndim);
-    if (flags[3 * k] | flags[3 * k + 1] | flags[3 * k + 2]) {
-        if (d == 0) atomicAdd(counters + 2, 1);
-        return;
-    }
-    const int wk = S[k];
-    if (Wacc[k] != 0.f) {
-        coords[(size_t)wk * ldc + d] += Wacc[k] * DIR[(size_t)k * ldd + d];
-        if (d == 0) logp[wk] = Zacc[k];
-    }
 }
 
 // ------------------------------------------------------------------ host-side launchers (namespace-internal)
@@ -1026,65 +942,47 @@ int launch_hmc_find_eps(int B, int ndim, const float* mass, const float* H0, con
                        state, nactive);
     LAUNCH_CHECK("hmc_find_eps");
 }
-int launch_slice_init(const float* logp, const int* S, int ns, const float* cc, int ldcc, const int* C, int nc, int ndim,
-                      const float* mu, uint64_t seed, const int* step_dev, int stream_id, float* DIR, int ldd, float* Z0,
-                      float* L, float* R, int* flags, int maxsteps, hipStream_t s) {
-    hipLaunchKernelGGL(slice_init_kernel, grid1d((size_t)ns * ldd, 256), dim3(256), 0, s, logp, S, ns, cc, ldcc, C, nc, ndim,
-                       mu, seed, step_dev, stream_id, DIR, ldd, Z0, L, R, flags, maxsteps);
-    LAUNCH_CHECK("slice_init");
-}
 int launch_slice_points(const float* coords, int ldc, int ndim, const int* S, int ns, const float* DIR, int ldd,
                         const float* w, float* Q, int ldq, int nrep, hipStream_t s) {
     hipLaunchKernelGGL(slice_points_kernel, grid1d((size_t)nrep * ns * ldq, 256), dim3(256), 0, s, coords, ldc, ndim, S, ns, DIR,
                        ldd, w, Q, ldq, nrep);
     LAUNCH_CHECK("slice_points");
 }
+#define SLICE_LAUNCH(kernel, ns, ...) hipLaunchKernelGGL(kernel, slice_grid(ns), dim3(64 * SLICE_WAVES), 0, s, __VA_ARGS__)
+int launch_slice_begin(const SliceBegin& b, const int* S, int ns, int ndim, float* W, hipStream_t s) {
+    SLICE_LAUNCH(slice_begin_kernel, ns, b, S, ns, ndim, W);
+    LAUNCH_CHECK("slice_begin");
+}
 int launch_slice_expand(const float* Z0, const float* ZL, const float* ZR, float* L, float* R, int* flags, int ns,
                         int* counters, int slot, hipStream_t s) {
-    hipLaunchKernelGGL(slice_expand_kernel, grid1d(ns, 256), dim3(256), 0, s, Z0, ZL, ZR, L, R, flags, ns, counters, slot);
+    SLICE_LAUNCH(slice_expand_kernel, ns, Z0, ZL, ZR, L, R, flags, ns, counters, slot);
     LAUNCH_CHECK("slice_expand");
 }
 int launch_slice_draw(const float* L, const float* R, const int* S, float* W, const int* flags, int ns, uint64_t seed,
                       const int* step_dev, int stream_id, int round, int ntrial, hipStream_t s) {
-    hipLaunchKernelGGL(slice_draw_kernel, grid1d(ns, 256), dim3(256), 0, s, L, R, S, W, flags, ns, seed, step_dev,
-                       stream_id, round, ntrial);
+    SLICE_LAUNCH(slice_draw_kernel, ns, L, R, S, W, flags, ns, seed, step_dev, stream_id, round, ntrial);
     LAUNCH_CHECK("slice_draw");
 }
 int launch_slice_shrink(const float* Z0, const float* Zt, float* L, float* R, const float* W, int* flags, float* Wacc,
                         float* Zacc, int ns, int* counters, int slot, int ntrial, hipStream_t s) {
-    hipLaunchKernelGGL(slice_shrink_kernel, grid1d(ns, 256), dim3(256), 0, s, Z0, Zt, L, R, W, flags, Wacc, Zacc, ns,
-                       counters, slot, ntrial);
+    SLICE_LAUNCH(slice_shrink_kernel, ns, Z0, Zt, L, R, W, flags, Wacc, Zacc, ns, counters, slot, ntrial);
     LAUNCH_CHECK("slice_shrink");
 }
-int launch_slice_begin(const float* logp, const int* S, int ns, const float* cc, int ldcc, const int* C, int nc, int ndim,
-                       const float* mu, uint64_t seed, const int* step_dev, int stream_id, float* DIR, int ldd, float* Z0, float* L,
-                       float* R, int* flags, float* W, int m, int* counters, int nslots, int zero_totals, int maxsteps, hipStream_t s) {
-    hipLaunchKernelGGL(slice_begin_kernel, grid1d((size_t)ns * ldd, 256), dim3(256), 0, s, logp, S, ns, cc, ldcc, C, nc, ndim, mu,
-                       seed, step_dev, stream_id, DIR, ldd, Z0, L, R, flags, W, m, counters, nslots, zero_totals, maxsteps);
-    LAUNCH_CHECK("slice_begin");
+int launch_slice_commit(float* coords, int ldc, int ndim, float* logp, const int* S, int ns, const float* DIR, int ldd,
+                        const float* Wacc, const float* Zacc, hipStream_t s) {
+    SLICE_LAUNCH(slice_commit_kernel, ns, coords, ldc, ndim, logp, S, ns, DIR, ldd, Wacc, Zacc);
+    LAUNCH_CHECK("slice_commit");
 }
 int launch_slice_expand_multi(const float* Z0, const float* Zt, float* L, float* R, const int* S, int* flags, int ns, int m,
                               int m_next, int* counters, int slot, int prev_slot, float* W, float* Wd, int* list, uint64_t seed,
                               const int* step_dev, int stream_id_shrink, int ntrial, hipStream_t s) {
-    hipLaunchKernelGGL(slice_expand_multi_kernel, dim3((ns + 15) / 16), dim3(1024), 0, s, Z0, Zt, L, R, S, flags, ns, m, m_next, counters, slot,
-                       prev_slot, W, Wd, list, seed, step_dev, stream_id_shrink, ntrial);
+    SLICE_LAUNCH(slice_expand_multi_kernel, ns, Z0, Zt, L, R, S, flags, ns, m, m_next, counters, slot, prev_slot, W, Wd, list, seed,
+                 step_dev, stream_id_shrink, ntrial);
     LAUNCH_CHECK("slice_expand_multi");
 }
 int launch_slice_shrink_multi(const SliceRound& a, hipStream_t s) {
-    hipLaunchKernelGGL(slice_shrink_multi_kernel, dim3((a.ns + 15) / 16), dim3(1024), 0, s, a);
+    SLICE_LAUNCH(slice_shrink_multi_kernel, a.ns, a);
     LAUNCH_CHECK("slice_shrink_multi");
-}
-int launch_slice_commit_checked(float* coords, int ldc, int ndim, float* logp, const int* S, int ns, const float* DIR, int ldd,
-                                const float* Wacc, const float* Zacc, const int* flags, int* counters, hipStream_t s) {
-    hipLaunchKernelGGL(slice_commit_checked_kernel, grid1d((size_t)ns * ndim, 256), dim3(256), 0, s, coords, ldc, ndim, logp, S, ns,
-                       DIR, ldd, Wacc, Zacc, flags, counters);
-    LAUNCH_CHECK("slice_commit_checked");
-}
-int launch_slice_commit(float* coords, int ldc, int ndim, float* logp, const int* S, int ns, const float* DIR, int ldd,
-                        const float* Wacc, const float* Zacc, hipStream_t s) {
-    hipLaunchKernelGGL(slice_commit_kernel, grid1d((size_t)ns * ndim, 256), dim3(256), 0, s, coords, ldc, ndim, logp, S,
-                       ns, DIR, ldd, Wacc, Zacc);
-    LAUNCH_CHECK("slice_commit");
 }
 int launch_step_increment(int* step, hipStream_t s) {
     hipLaunchKernelGGL(step_increment_kernel, dim3(1), dim3(1), 0, s, step);

@@ -824,9 +824,7 @@ class EnsembleSampler(object):
         lib_seed = C.c_uint64(self.seed + 0x9E3779B97F4A7C15 * (self.rank + 1) & 0xFFFFFFFFFFFFFFFF)
         for h in (0, 1):
             S, Cc = halves[h], halves[1 - h]
-            comp, ldc, cidx, nc = self.coords, self.ld, Cc, self.half
-            if self.exchange == "allgather" and self.world > 1:
-                comp, cidx, nc = self._allgather_complement(Cc)
+            comp, ldc, cidx, nc = self._complement(Cc)
             if self.fused is not False:
                 # propose + log-probability + accept in ONE launch (bit-identical to the three below)
                 rc = _lib.load().linna_stretch_half_step(
@@ -850,6 +848,14 @@ class EnsembleSampler(object):
             _lib.call("linna_step_increment", self.ctx, _lib.iptr(self.step_dev), st)
             self._dev_steps += 1
         self.iteration += 1
+
+    def _complement(self, Cc):
+        """The complementary set of a half step as (coords, row stride, device indices, count): this rank's other half, or
+        with ``exchange="allgather"`` over several ranks the other halves of all of them."""
+        if self.exchange == "allgather" and self.world > 1:
+            comp, cidx, nc = self._allgather_complement(Cc)
+            return comp, self.ld, cidx, nc
+        return self.coords, self.ld, Cc, self.half
 
     def _allgather_complement(self, Cc):
         """Complementary walkers of ALL ranks: gather this rank's complementary half."""
@@ -946,6 +952,7 @@ class SliceEnsembleSampler(EnsembleSampler):
     FAST_TRIALS = 32                # at least so many shrinking trials per walker and half step (each halves the bracket)
     FAST_FIRST = None               # bracket ends per side in the first stepping-out round (None: by ensemble size, below)
     FAST_CAP = (8, 32)              # most ends per side / trials a later round looks ahead
+    MAX_ENDS, MAX_TRIALS = 32, 64   # most a round may hold: a wave's lanes in the logic kernels (linna_slice_half_step rejects more)
 
     def __init__(self, nwalkers, ndim, log_prob, mu=1.0, seed=0, tune=True, tolerance=0.05, patience=5, maxsteps=10000,
                  maxiter=100000, dist_group=None, exchange="none", fast=None):
@@ -1001,7 +1008,7 @@ class SliceEnsembleSampler(EnsembleSampler):
 
     def set_schedule(self, m_sched, nt_sched):
         """Bracket ends per side of each stepping-out round and trials of each shrinking round of the one-call path."""
-        self.m_sched, self.nt_sched = [int(v) for v in m_sched], [int(v) for v in nt_sched]
+        self.m_sched, self.nt_sched = self.check_schedule(m_sched, nt_sched)
         self.m, self.nt_fast = max(self.m_sched), max(self.nt_sched)         # (scratch sizes)
         self._expect, self._expect_base, self._expect_seen, self.expected_rows = None, (0.0, np.zeros(0)), -1, None
         self.nexp_rounds, self.nshr_rounds = len(self.m_sched), len(self.nt_sched)
@@ -1010,6 +1017,15 @@ class SliceEnsembleSampler(EnsembleSampler):
         if getattr(self, "_fast_bufs", None) is not None:              # (a schedule change mid-run: keep the evaluation count)
             self._neval_host += int(self._fast_bufs["counters"][3].item())
         self._fast_bufs = None
+
+    @staticmethod
+    def check_schedule(m_sched, nt_sched):
+        """The two schedules as lists of ints; ValueError for a round linna_slice_half_step would reject."""
+        m_sched, nt_sched = [int(v) for v in m_sched], [int(v) for v in nt_sched]
+        for name, sched, cap in (("m_sched", m_sched, SliceEnsembleSampler.MAX_ENDS), ("nt_sched", nt_sched, SliceEnsembleSampler.MAX_TRIALS)):
+            if not sched or min(sched) < 1 or max(sched) > cap:
+                raise ValueError("%s = %s: every round needs 1 to %d" % (name, sched, cap))
+        return m_sched, nt_sched
 
     @staticmethod
     def _schedule(first, total, cap):
@@ -1127,9 +1143,7 @@ class SliceEnsembleSampler(EnsembleSampler):
         self._refresh_expectation()
         for h in (0, 1):
             S, Cc = halves[h], halves[1 - h]
-            comp, ldc, cidx, nc = self.coords, self.ld, Cc, self.half
-            if self.exchange == "allgather" and self.world > 1:
-                comp, cidx, nc = self._allgather_complement(Cc)
+            comp, ldc, cidx, nc = self._complement(Cc)
             rc = _lib.load().linna_slice_half_step(
                 self.lp._ensure()["handle"], P(self.coords), self.ld, self.ndim, P(self.logp), I(S), ns, P(comp), ldc, I(cidx), nc,
                 P(self.mu_dev), seed, I(self.step_dev), h, self._m_arr, self.nexp_rounds, self._nt_arr, self.nshr_rounds, P(self.DIR), self.ld,
@@ -1318,9 +1332,7 @@ class SliceEnsembleSampler(EnsembleSampler):
         nt = self.ntrial
         for h in (0, 1):
             S, Cc = halves[h], halves[1 - h]
-            comp, ldc, cidx, nc = self.coords, self.ld, Cc, self.half
-            if self.exchange == "allgather" and self.world > 1:
-                comp, cidx, nc = self._allgather_complement(Cc)
+            comp, ldc, cidx, nc = self._complement(Cc)
             _lib.call("linna_slice_init", self.ctx, P(self.logp), _lib.iptr(S), ns, P(comp), ldc, _lib.iptr(cidx), nc, ndim,
                       P(self.mu_dev), seed, _lib.iptr(self.step_dev), h, P(self.DIR), self.ld, P(self.Z0), P(self.L),
                       P(self.R), _lib.iptr(self.flags), int(self.maxsteps), st)

@@ -654,3 +654,32 @@ def test_one_call_slice_half_step_equals_the_round_loop(name, nw):
     assert c.noverflow == 1 and d.noverflow == 0
     assert torch.equal(cc, dc) and torch.equal(cl, dl) and torch.equal(c.coords, d.coords) and c.iteration == d.iteration == 3
     assert int(c.step_dev.item()) == int(d.step_dev.item())
+
+
+@pytest.mark.parametrize("m_sched,nt_sched,text", [([33], [16], "m_sched[0] = 33"), ([8], [65], "nt_sched[0] = 65")])
+def test_slice_half_step_rejects_a_schedule_beyond_a_wave(m_sched, nt_sched, text):
+    """The logic kernels of linna_slice_half_step hold a round's bracket ends (32 per side) and trials (64) in one wave's
+    lanes: a longer round is LINNA_ERR_INVALID before anything is launched -- positions, lnP and counters untouched."""
+    import ctypes as C
+    from linna_amd import sampler
+    lp, pred, yinv, prob = build_logprob("mlp_7_5_small", 16.0)
+    nd, ns = prob["nin"], 2
+    ens = sampler.SliceEnsembleSampler(2 * ns, nd, lp, seed=1, tune=False, mu=0.7)
+    ens.set_state((0.3 * np.random.RandomState(3).standard_normal((2 * ns, nd))).astype(np.float32))
+    halves = ens._splits()
+    z = lambda n: torch.zeros(n, dtype=torch.float32, device=ens.dev)
+    nrep = max(2 * m_sched[0], nt_sched[0])
+    state, W, Wd, Zt = z(5 * ns), z(2 * m_sched[0] * ns), z(nt_sched[0] * ns), z(nrep * ns)
+    lst = torch.zeros(nrep * ns, dtype=torch.int32, device=ens.dev)
+    counters = torch.arange(100, 109, dtype=torch.int32, device=ens.dev)
+    coords0, logp0, counters0 = ens.coords.clone(), ens.logp.clone(), counters.clone()
+    P, I = _lib.ptr, _lib.iptr
+    rc = _lib.load().linna_slice_half_step(
+        lp._ensure()["handle"], P(ens.coords), ens.ld, nd, P(ens.logp), I(halves[0]), ns, P(ens.coords), ens.ld, I(halves[1]), ns,
+        P(ens.mu_dev), C.c_uint64(5), I(ens.step_dev), 0, (C.c_int * 1)(*m_sched), 1, (C.c_int * 1)(*nt_sched), 1, P(ens.DIR), ens.ld,
+        P(state), I(ens.flags), P(W), P(Wd), P(Zt), I(lst), I(counters), 1, 0, None, 10000, _lib.stream())
+    msg = _lib.load().linna_last_error().decode()
+    torch.cuda.synchronize()
+    assert rc == _lib.ERR_INVALID, (rc, msg)
+    assert "slice_half_step" in msg and text in msg, msg
+    assert torch.equal(ens.coords, coords0) and torch.equal(ens.logp, logp0) and torch.equal(counters, counters0)

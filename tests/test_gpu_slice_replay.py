@@ -27,10 +27,13 @@ GOLDEN = 0x9E3779B97F4A7C15
 class Replay(object):
     """Drives one SliceEnsembleSampler in lockstep with the oracle and keeps the tallies."""
 
-    def __init__(self, ens, prob, temperature, seed):
+    def __init__(self, ens, prob, temperature, seed, f=None):
+        """``f``: the oracle's log-probability function in place of the oracle emulator of ``prob``."""
         from oracle import likelihood
-        emu = cases.oracle_emulator(prob)
-        self.f = lambda q: likelihood.log_prob(q, emu, prob["priors"], prob["data"], prob["invcov"], temperature)
+        if f is None:
+            emu = cases.oracle_emulator(prob)
+            f = lambda q: likelihood.log_prob(q, emu, prob["priors"], prob["data"], prob["invcov"], temperature)
+        self.f = f
         self.ens, self.nd = ens, ens.ndim
         self.lib_seed = (seed + GOLDEN * 1) & 0xFFFFFFFFFFFFFFFF
         self.before = None
@@ -212,3 +215,60 @@ def test_the_stepping_out_budget_binds_on_the_device_as_in_the_oracle():
         ens, rp, _ = _run("mlp_33_33", 2.0, 128, seed=3, iters=6, x_scale=0.3, prepare=prepare, tune=False, mu=0.02, maxsteps=4, **kw)
         assert rp.max_expansions <= 3 and rp.budget_bound > 0.5 * rp.walker_half_steps, (rp.max_expansions, rp.budget_bound)
         assert rp.exempt <= 0.03 * rp.walker_half_steps + 2
+
+
+class GaussianLnP(object):
+    """A host log-probability (``device_only = False``: what a user ``loglikelihoodfunc`` looks like to the samplers) of any
+    dimension: a zero-mean correlated Gaussian, lnP = -q P q / 2, computed in float64 on the host from the float32 points
+    and cast to float32 -- by ``f`` for the oracle and by ``evaluate_any`` for the sampler, the same arithmetic."""
+    device_only = False
+
+    def __init__(self, nd, dev=None):
+        A = np.random.RandomState(100 + nd).standard_normal((nd, nd))
+        self.P = A @ A.T / nd + np.eye(nd)               # (precision matrix; off-diagonal terms of order 1 / sqrt(nd))
+        self.nd, self.dev = nd, dev
+
+    def _ensure(self):
+        return {"dev": self.dev}
+
+    def f(self, q):
+        q = np.asarray(q, np.float64)[:, :self.nd]
+        return (-0.5 * np.einsum("bi,ij,bj->b", q, self.P, q)).astype(np.float32)
+
+    def evaluate_any(self, Q):
+        return torch.as_tensor(self.f(Q.cpu().numpy()), device=self.dev)
+
+
+SLICE_WAVES = 16                     # walkers (one wave each) per block of the slice logic kernels (pointwise.hip)
+STUB_SEED, STUB_MU, STUB_ITERS = 31, 0.45, 10
+
+
+def stub_start(nd, nw):
+    return (0.3 * np.random.RandomState(nw + 7).standard_normal((nw, nd))).astype(np.float32)
+
+
+@pytest.mark.parametrize("nd,nw", [(70, 6), (70, 2 * (SLICE_WAVES + 1)), (3, 4)])
+def test_round_loop_kernels_at_shapes_the_network_problems_do_not_reach(nd, nw):
+    """The round-by-round entries (linna_slice_init / _points / _expand / _draw / _shrink / _commit) driven by a host
+    log-probability, so that they run at any dimension: 70 parameters (a padded row of 72 floats, longer than a wave) with 3
+    walkers per half ensemble (less than one block of the logic kernels) and with one walker more than a block holds, and 3
+    parameters with 4 walkers (two complementary walkers: the second index of the differential move has one choice).  10
+    iterations at a fixed mu in lockstep with the oracle, ``Replay``'s tolerances and exemption rule.
+    Checked on the CPU before any GPU run (the oracle alone over the same start, splits and seed): its comparisons with a
+    margin below the tolerance exempt 0 of 60, 0 of 340 and 0 of 40 walker half steps -- under the cap of 0.02 x walker half
+    steps + 2 in every case."""
+    from linna_amd import sampler
+    dev = torch.device("cuda:0")
+    lp = GaussianLnP(nd, dev)
+    ens = sampler.SliceEnsembleSampler(nw, nd, lp, seed=STUB_SEED, tune=False, mu=STUB_MU)
+    ens.set_state(stub_start(nd, nw))
+    rp = Replay(ens, None, None, STUB_SEED, f=lp.f)
+    for _ in range(STUB_ITERS):
+        ens._step()
+    torch.cuda.synchronize()
+    assert rp.paths == {"rounds"}, rp.paths
+    assert rp.walker_half_steps == STUB_ITERS * nw
+    print("ndim %d nw %d: exempt %d of %d walker half steps, expansions %d / contractions %d (oracle %d / %d)"
+          % (nd, nw, rp.exempt, rp.walker_half_steps, rp.gpu_counts[0], rp.gpu_counts[1], rp.ora_counts[0], rp.ora_counts[1]))
+    assert rp.exempt <= 0.02 * rp.walker_half_steps + 2, (rp.exempt, rp.walker_half_steps)
+    assert rp.gpu_counts[0] > 0 and rp.gpu_counts[1] > 0

@@ -662,6 +662,17 @@ def test_slice_round_expectation_from_usage_counters():
     assert rows4 == [1, 1, 1 << 20]
 
 
+def test_slice_schedule_is_limited_to_a_waves_lanes():
+    """``SliceEnsembleSampler.check_schedule`` (what ``set_schedule`` accepts): at most 32 bracket ends per side and 64 trials
+    in a round, the limit of linna_slice_half_step."""
+    import torch  # noqa: F401  (the module imports it)
+    from linna_amd.sampler import SliceEnsembleSampler as S
+    assert S.check_schedule([1, 32], (4, 64)) == ([1, 32], [4, 64])
+    for m_sched, nt_sched in [([8, 33], [16]), ([8], [16, 65]), ([0], [16]), ([8], [0])]:
+        with pytest.raises(ValueError):
+            S.check_schedule(m_sched, nt_sched)
+
+
 
 def test_sample_text_files_are_parsed_once_and_reparsed_when_they_change(tmp_path):
     """``util._loadtxt_cached`` (train_NN re-reads the ``*_samples_x.txt`` of every earlier iteration, util.py:1346-1373): the
