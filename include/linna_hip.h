@@ -587,6 +587,23 @@ int linna_hmc_run(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, fl
  * as in linna_hmc_start (the reference's search uses R0 itself and R0^2 / mass: the same at unit mass). */
 int linna_hmc_find_epsilon(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, float* R0, float* EPS, int* state,
                            int* nactive, int step_offset, int max_rounds, void* stream);
+
+/* ---- a diagonal mass adapted on the device (Stan's windowed warm-up; BatchedHMC.adapt).
+ * Running moments of the chain positions, pooled over chains: mom = {n, mean[ndim], M2[ndim]}, 1 + 2 ndim doubles in device
+ * memory (zeros = empty).  linna_hmc_moments merges the B rows of X[B][ldx] (columns < ndim; nothing of the pad is read)
+ * into them: the batch mean and the batch M2 about that mean in float64, then Chan's merge
+ *   delta = mean_b - mean; n' = n + B; mean += delta B / n'; M2 += M2_b + delta^2 n B / n'.
+ * No floating-point atomics and a fixed summation order: the same input gives the same bits. */
+int linna_hmc_moments(linna_ctx_t* ctx, int B, int ndim, const float* X, int ldx, double* mom, void* stream);
+/* mass[d] = (float)(1 / var') with var = M2[d] / (n - 1) and Stan's shrinkage var' = var n / (n + 5) + 1e-3 * 5 / (n + 5),
+ * written only where that is finite and positive; elsewhere, and for n < 2, mass[d] is kept.  reset != 0: mom is zeroed
+ * behind it. */
+int linna_hmc_mass_from_moments(linna_ctx_t* ctx, int ndim, double* mom, float* mass, int reset, void* stream);
+/* linna_hmc_run (which is this entry with mom == NULL) and, for mom != NULL, one linna_hmc_moments launch on st->X behind
+ * every transition's Metropolis launch.  The chains do not notice: bit for bit linna_hmc_run's. */
+int linna_hmc_run_moments(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, float* EPS, float* EPSBAR, float* HBAR,
+                          const float* MU, int* M, int Madapt, float delta, int step_offset, int num_steps, int ntrans,
+                          int* naccept, float* alpha, float* chain, float* logps, double* mom, void* stream);
 int linna_step_increment(linna_ctx_t* ctx, int* step_dev, void* stream);
 
 /* Ensemble slice sampling (zeus DifferentialMove behind sampler.py:728-735): per active walker a

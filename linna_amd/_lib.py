@@ -184,6 +184,9 @@ _SIGNATURES = {
                                     _V, _V, _V, _V, _V, _I, _F, _V, _V, _V]),
     "linna_hmc_run": (_I, [_V, _V, _V, _V, _V, _V, _V, _V, _I, _F, _I, _I, _I, _V, _V, _V, _V, _V]),
     "linna_hmc_find_epsilon": (_I, [_V, _V, _V, _V, _V, _V, _V, _I, _I, _V]),
+    "linna_hmc_moments": (_I, [_V, _I, _I, _V, _I, _V, _V]),
+    "linna_hmc_mass_from_moments": (_I, [_V, _I, _V, _V, _I, _V]),
+    "linna_hmc_run_moments": (_I, [_V, _V, _V, _V, _V, _V, _V, _V, _I, _F, _I, _I, _I, _V, _V, _V, _V, _V, _V]),
     "linna_step_increment": (_I, [_V, _V, _V]),
     "linna_slice_init": (_I, [_V, _V, _V, _I, _V, _I, _V, _I, _I, _V, _U64, _V, _I, _V, _I, _V, _V, _V, _V, _I, _V]),
     "linna_slice_points": (_I, [_V, _V, _I, _I, _V, _I, _V, _I, _V, _V, _I, _I, _V]),

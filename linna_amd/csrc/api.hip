@@ -1523,9 +1523,10 @@ static int hmc_trajectory(linna_logprob_t* lp, const linna_hmc_state_t* st, void
     return LINNA_OK;
 }
 
-int linna_hmc_run(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, float* EPS, float* EPSBAR, float* HBAR, const float* MU,
-                  int* M, int Madapt, float delta, int step_offset, int num_steps, int ntrans, int* naccept, float* alpha,
-                  float* chain, float* logps, void* stream) try {
+// linna_hmc_run and linna_hmc_run_moments: mom != nullptr adds the moments launch on st->X behind every Metropolis launch
+static int hmc_run_impl(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, float* EPS, float* EPSBAR, float* HBAR, const float* MU,
+                        int* M, int Madapt, float delta, int step_offset, int num_steps, int ntrans, int* naccept, float* alpha,
+                        float* chain, float* logps, double* mom, void* stream) {
     if (!lp || !st || !ws || !EPS || num_steps < 1 || ntrans < 1 || Madapt < 0 || (chain != nullptr) != (logps != nullptr)) {
         set_error("hmc_run: bad arguments"); return LINNA_ERR_INVALID;
     }
@@ -1538,8 +1539,23 @@ int linna_hmc_run(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, fl
         TRY(launch_hmc_accept(B, nd, st->mass, st->seed, st->step_dev, step_offset + i, st->H0, st->P, ld, st->Q, ld, st->lnp_new,
                               st->Gnew, ld, nullptr, st->X, ld, st->lnp, st->G, naccept, alpha, ad,
                               chain ? chain + (size_t)i * B * nd : nullptr, logps ? logps + (size_t)i * B : nullptr, S(stream)));
+        if (mom) TRY(launch_hmc_moments(B, nd, st->X, ld, mom, S(stream)));
     }
     return LINNA_OK;
+}
+
+int linna_hmc_run(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, float* EPS, float* EPSBAR, float* HBAR, const float* MU,
+                  int* M, int Madapt, float delta, int step_offset, int num_steps, int ntrans, int* naccept, float* alpha,
+                  float* chain, float* logps, void* stream) try {
+    return hmc_run_impl(lp, st, ws, EPS, EPSBAR, HBAR, MU, M, Madapt, delta, step_offset, num_steps, ntrans, naccept, alpha, chain,
+                        logps, nullptr, stream);
+} LINNA_CATCH_INT
+
+int linna_hmc_run_moments(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, float* EPS, float* EPSBAR, float* HBAR,
+                          const float* MU, int* M, int Madapt, float delta, int step_offset, int num_steps, int ntrans,
+                          int* naccept, float* alpha, float* chain, float* logps, double* mom, void* stream) try {
+    return hmc_run_impl(lp, st, ws, EPS, EPSBAR, HBAR, MU, M, Madapt, delta, step_offset, num_steps, ntrans, naccept, alpha, chain,
+                        logps, mom, stream);
 } LINNA_CATCH_INT
 
 int linna_hmc_find_epsilon(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, float* R0, float* EPS, int* state, int* nactive,
@@ -1769,6 +1785,14 @@ int linna_hmc_start(linna_ctx_t*, int B, int ndim, const float* mass, uint64_t s
 int linna_hmc_kick_drift(linna_ctx_t*, int B, int ndim, const float* mass, float ek, float ed, const float* G, int ldg,
                          float* P, int ldp, float* Q, int ldq, void* stream) try {
     return launch_hmc_kick_drift(B, ndim, mass, ek, ed, G, ldg, P, ldp, Q, ldq, S(stream));
+} LINNA_CATCH_INT
+int linna_hmc_moments(linna_ctx_t*, int B, int ndim, const float* X, int ldx, double* mom, void* stream) try {
+    if (B < 1 || ndim < 1 || !X || ldx < ndim || !mom) { set_error("hmc_moments: bad arguments"); return LINNA_ERR_INVALID; }
+    return launch_hmc_moments(B, ndim, X, ldx, mom, S(stream));
+} LINNA_CATCH_INT
+int linna_hmc_mass_from_moments(linna_ctx_t*, int ndim, double* mom, float* mass, int reset, void* stream) try {
+    if (ndim < 1 || !mom || !mass) { set_error("hmc_mass_from_moments: bad arguments"); return LINNA_ERR_INVALID; }
+    return launch_hmc_mass_from_moments(ndim, mom, mass, reset, S(stream));
 } LINNA_CATCH_INT
 int linna_hmc_start_eps(linna_ctx_t*, int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, int step_offset,
                         const float* lnp, const float* P0, int ldp0, const float* G, int ldg, const float* EPS, float mul_kick,

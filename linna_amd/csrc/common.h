@@ -318,6 +318,9 @@ int launch_hmc_find_eps_init(int B, int ndim, uint64_t seed, const int* step_dev
                              int* state, hipStream_t s);
 int launch_hmc_find_eps(int B, int ndim, const float* mass, const float* H0, const float* P, int ldp, const float* lnp_new,
                         const float* Gn, int ldg, float* eps, int* state, int* nactive, hipStream_t s);
+// running moments of the chain positions, mom = {n, mean[ndim], M2[ndim]} (float64), and the diagonal mass they give
+int launch_hmc_moments(int B, int ndim, const float* X, int ldx, double* mom, hipStream_t s);
+int launch_hmc_mass_from_moments(int ndim, double* mom, float* mass, int reset, hipStream_t s);
 int launch_slice_points(const float* coords, int ldc, int ndim, const int* S, int ns, const float* DIR, int ldd,
                         const float* w, float* Q, int ldq, int nrep, hipStream_t s);
 int launch_slice_expand(const float* Z0, const float* ZL, const float* ZR, float* L, float* R, int* flags, int ns,

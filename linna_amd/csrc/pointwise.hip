@@ -627,6 +627,82 @@ __global__ void hmc_find_eps_kernel(int B, int ndim, const float* __restrict__ m
     if (nactive && st != 2) atomicAdd(nactive, 1);
 }
 
+// Running moments of the chain positions pooled over chains, mom = {n, mean[ndim], M2[ndim]} in float64 (linna_hip.h): what
+// the windowed mass adaptation accumulates behind every transition.  ONE workgroup of 16 waves: every merge reads n and one
+// thread writes it, which workgroups of their own could not order.  Lane = parameter (a row is one coalesced read), 64
+// parameters at a time; the waves stride over the chains 16 rows at a time.  The 16 loads of a round are unconditional -- row
+// and column indices clamped into the matrix, the value masked afterwards -- so that all of them are in flight before the
+// first add: behind a bounds test each load waited for the one before it, a cache miss of latency per row (126 us per launch
+// at 4096 chains).  Two passes over X, the batch mean and then the batch M2 about it; the per-wave partials meet in LDS and
+// are added in wave order by every thread alike.  The order of every sum is fixed by (B, ndim) alone: no atomics, the same bits each time.
+constexpr int MOM_WAVES = 16, MOM_ROWS = 16;
+
+__device__ __forceinline__ double mom_block_sum(double (*part)[64], double s, int wave, int lane) {
+    __syncthreads();                                          // (the totals of the pass before have been read)
+    part[wave][lane] = s;
+    __syncthreads();
+    double t = 0.0;
+    for (int w = 0; w < MOM_WAVES; ++w) t += part[w][lane];
+    return t;
+}
+// rows b0 .. b0 + MOM_ROWS - 1 of column dc (< ndim); a row past the end re-reads the last one
+__device__ __forceinline__ void mom_load(float (&v)[MOM_ROWS], const float* __restrict__ X, int ldx, int B, int b0, int dc) {
+#pragma unroll
+    for (int u = 0; u < MOM_ROWS; ++u) v[u] = X[(size_t)min(b0 + u, B - 1) * ldx + dc];
+}
+
+__global__ __launch_bounds__(MOM_WAVES * 64) void hmc_moments_kernel(int B, int ndim, const float* __restrict__ X, int ldx,
+                                                                     double* __restrict__ mom) {
+    __shared__ double part[MOM_WAVES][64];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const double n = mom[0], nb = (double)B, n1 = n + nb;
+    for (int d0 = 0; d0 < ndim; d0 += 64) {
+        const int d = d0 + lane, dc = min(d, ndim - 1);       // (the pad of a row is never read)
+        const bool on = d < ndim;
+        float v[MOM_ROWS];
+        double s = 0.0;
+        for (int b0 = wave * MOM_ROWS; b0 < B; b0 += MOM_WAVES * MOM_ROWS) {
+            mom_load(v, X, ldx, B, b0, dc);
+#pragma unroll
+            for (int u = 0; u < MOM_ROWS; ++u) s += on && b0 + u < B ? (double)v[u] : 0.0;
+        }
+        const double mb = mom_block_sum(part, s, wave, lane) / nb;
+        s = 0.0;
+        for (int b0 = wave * MOM_ROWS; b0 < B; b0 += MOM_WAVES * MOM_ROWS) {
+            mom_load(v, X, ldx, B, b0, dc);
+#pragma unroll
+            for (int u = 0; u < MOM_ROWS; ++u) {
+                const double t = on && b0 + u < B ? (double)v[u] - mb : 0.0;
+                s += t * t;
+            }
+        }
+        const double M2b = mom_block_sum(part, s, wave, lane);
+        if (wave == 0 && on) {                                // Chan, Golub & LeVeque's merge of (nb, mb, M2b) into (n, mean, M2)
+            const double mean = mom[1 + d], delta = mb - mean;
+            mom[1 + d] = mean + delta * nb / n1;
+            mom[1 + ndim + d] += M2b + delta * delta * n * nb / n1;
+        }
+    }
+    if (threadIdx.x == 0) mom[0] = n1;                        // (behind the barriers above: every thread has read n)
+}
+
+// mass = 1 / variance of the moments, with Stan's shrinkage towards 1e-3 (var n / (n + 5) + 1e-3 * 5 / (n + 5)); a parameter
+// whose result is not finite and positive keeps its mass, and so does every parameter while n < 2.  One workgroup: the zeroing
+// of mom (reset) follows a barrier behind every read of it.
+__global__ void hmc_mass_from_moments_kernel(int ndim, double* __restrict__ mom, float* __restrict__ mass, int reset) {
+    const double n = mom[0];
+    if (n >= 2.0) {
+        for (int d = threadIdx.x; d < ndim; d += blockDim.x) {
+            const double var = mom[1 + ndim + d] / (n - 1.0);
+            const double shrunk = var * n / (n + 5.0) + 1e-3 * 5.0 / (n + 5.0);
+            const float m = (float)(1.0 / shrunk);
+            if (isfinite(m) && m > 0.f) mass[d] = m;
+        }
+    }
+    __syncthreads();
+    if (reset) for (int i = threadIdx.x; i < 1 + 2 * ndim; i += blockDim.x) mom[i] = 0.0;
+}
+
 __global__ void step_increment_kernel(int* step) { step[0] += 1; }
 
 // ------------------------------------------------------------------ ensemble slice sampling (zeus, Karamanis & Beutler 2021)
@@ -941,6 +1017,14 @@ int launch_hmc_find_eps(int B, int ndim, const float* mass, const float* H0, con
     hipLaunchKernelGGL(hmc_find_eps_kernel, dim3((B + 3) / 4), dim3(256), 0, s, B, ndim, mass, H0, P, ldp, lnp_new, Gn, ldg, eps,
                        state, nactive);
     LAUNCH_CHECK("hmc_find_eps");
+}
+int launch_hmc_moments(int B, int ndim, const float* X, int ldx, double* mom, hipStream_t s) {
+    hipLaunchKernelGGL(hmc_moments_kernel, dim3(1), dim3(MOM_WAVES * 64), 0, s, B, ndim, X, ldx, mom);
+    LAUNCH_CHECK("hmc_moments");
+}
+int launch_hmc_mass_from_moments(int ndim, double* mom, float* mass, int reset, hipStream_t s) {
+    hipLaunchKernelGGL(hmc_mass_from_moments_kernel, dim3(1), dim3(256), 0, s, ndim, mom, mass, reset);
+    LAUNCH_CHECK("hmc_mass_from_moments");
 }
 int launch_slice_points(const float* coords, int ldc, int ndim, const int* S, int ns, const float* DIR, int ldd,
                         const float* w, float* Q, int ldq, int nrep, hipStream_t s) {

@@ -1383,7 +1383,9 @@ class BatchedHMC(object):
     ``step`` / ``sample`` take one scalar step size and enqueue a transition launch by launch.  ``run`` enqueues a block of
     transitions in one C call with a step size per chain (``self.eps``, device), which ``find_reasonable_epsilon`` chooses
     and ``run(..., Madapt=n)`` adapts by dual averaging (``self.epsbar``, ``Hbar``, ``mu``, ``m``): what ``HMCSampler.sample(
-    method="hmc")`` drives.  Both routes share one Philox sequence (``iteration``)."""
+    method="hmc")`` drives.  Both routes share one Philox sequence (``iteration``).  ``adapt`` is the whole warm-up, with
+    the diagonal mass adapted from the positions of all chains on request (``mass_windows``, ``run(moments=True)``,
+    ``mass_from_moments``): ``self.mass`` is rewritten in place on the device."""
 
     def __init__(self, log_prob, x0, mass=None, seed=0, fused=True, dist_group=None):
         self.group = dist_group                 # the process group a driver gathers chain blocks over (gather_chain); chains never exchange
@@ -1411,7 +1413,8 @@ class BatchedHMC(object):
         self.eps, self.alpha = z(self.B), z(self.B)
         self.epsbar, self.Hbar, self.mu = torch.ones_like(self.eps), z(self.B), z(self.B)
         self.m = torch.ones(self.B, dtype=torch.int32, device=self.dev)
-        self.num_steps = 5                      # run()'s default (HMCSampler.sample sets it)
+        self.mom = None                         # run(moments=True): {n, mean[ndim], M2[ndim]} of the positions, device float64
+        self.num_steps = 5                     # run()'s default (HMCSampler.sample sets it)
         self.nw, self.iteration, self._dev_steps = self.B, 0, 0     # (what _run_blocks / _Ranks.gather read; Philox step = iteration)
         self._state = None
         self.lp.evaluate_with_grad(self.x, out=self.lnp, grad=self.g)
@@ -1447,24 +1450,87 @@ class BatchedHMC(object):
                           "they reached" % (n, self.B, max_rounds))
         return n
 
-    def run(self, ntrans, num_steps=None, store=True, Madapt=0, target_accept=0.65):
+    def run(self, ntrans, num_steps=None, store=True, Madapt=0, target_accept=0.65, moments=False):
         """``ntrans`` transitions of ``num_steps`` leapfrog steps with the per-chain step sizes ``self.eps``, enqueued by ONE C
         call (linna_hmc_run: 2 + num_steps launches per transition, the chain rows written by the Metropolis launch); returns
         (chain[ntrans, B, ndim], lnp[ntrans, B]) as device tensors, (None, None) without ``store``.  Bit for bit a loop of
         ``step()`` at that step size.  ``Madapt`` > 0: every chain whose transition count ``self.m`` is <= Madapt adapts its
         step size by dual averaging towards the acceptance ``target_accept`` and freezes it at the averaged one on transition
-        Madapt + 1 (the count carries over from call to call)."""
+        Madapt + 1 (the count carries over from call to call).  ``moments``: one more launch per transition merges the B
+        positions behind it into ``self.mom`` = {n, mean[ndim], M2[ndim]} (device float64, linna_hmc_run_moments); the
+        chains are bit for bit the same."""
         num_steps = self.num_steps if num_steps is None else int(num_steps)
         chain = torch.empty((ntrans, self.B, self.ndim), dtype=torch.float32, device=self.dev) if store else None
         lps = torch.empty((ntrans, self.B), dtype=torch.float32, device=self.dev) if store else None
         if ntrans > 0:
             h, ws = self.lp._ensure()["handle"], _lib.ptr(self.lp._workspace(self.B, True))
-            _lib.call("linna_hmc_run", h, self._hmc_state(), ws, _lib.ptr(self.eps), _lib.ptr(self.epsbar), _lib.ptr(self.Hbar),
-                      _lib.ptr(self.mu), _lib.iptr(self.m), int(Madapt), float(target_accept), self.iteration - self._dev_steps,
-                      num_steps, int(ntrans), _lib.iptr(self.naccept), _lib.ptr(self.alpha), _lib.ptr(chain), _lib.ptr(lps),
-                      _lib.stream())
+            args = (h, self._hmc_state(), ws, _lib.ptr(self.eps), _lib.ptr(self.epsbar), _lib.ptr(self.Hbar),
+                    _lib.ptr(self.mu), _lib.iptr(self.m), int(Madapt), float(target_accept), self.iteration - self._dev_steps,
+                    num_steps, int(ntrans), _lib.iptr(self.naccept), _lib.ptr(self.alpha), _lib.ptr(chain), _lib.ptr(lps))
+            if moments:
+                _lib.call("linna_hmc_run_moments", *args, _lib.ptr(self._moments(), torch.float64), _lib.stream())
+            else:
+                _lib.call("linna_hmc_run", *args, _lib.stream())
             self.iteration += ntrans
         return chain, lps
+
+    def _moments(self):
+        if self.mom is None:
+            self.mom = torch.zeros(1 + 2 * self.ndim, dtype=torch.float64, device=self.dev)
+        return self.mom
+
+    @staticmethod
+    def mass_windows(Madapt, init_buffer=75, term_buffer=50, base_window=25):
+        """Stan's warm-up schedule: the "slow" windows [(start, end), ...] of ``Madapt`` adaptive transitions in which the
+        positions are accumulated for the mass, between an initial buffer and a closing one that adapt the step size alone.
+        Windows double in length; one whose successor would not fit in front of the closing buffer runs up to it.  A warm-up
+        too short for 75 + 25 + 50 splits 15 % / 75 % / 10 %; fewer than 20 transitions: no window."""
+        Madapt = int(Madapt)
+        if Madapt < 20:
+            return []
+        init, term, base = int(init_buffer), int(term_buffer), int(base_window)
+        if init + base + term > Madapt:
+            init, term = int(0.15 * Madapt), int(0.1 * Madapt)
+            base = Madapt - init - term
+        out, start, size, last = [], init, base, Madapt - term
+        while start < last:
+            end = start + size
+            if end + 2 * size > last:
+                end = last
+            out.append((start, end))
+            start, size = end, 2 * size
+        return out
+
+    def mass_from_moments(self, reset=True):
+        """``self.mass`` <- 1 / the pooled variance in ``self.mom`` with Stan's shrinkage, in place on the device
+        (linna_hmc_mass_from_moments: the pointer the kernels hold stays the same); ``reset`` empties the moments."""
+        _lib.call("linna_hmc_mass_from_moments", self.ctx, self.ndim, _lib.ptr(self._moments(), torch.float64), _lib.ptr(self.mass),
+                  int(bool(reset)), _lib.stream())
+
+    def adapt(self, Madapt, target_accept=0.65, adapt_mass=True):
+        """The whole warm-up: ``find_reasonable_epsilon()`` and ``Madapt`` transitions of dual averaging plus the one that puts
+        the averaged step size in place.  ``adapt_mass``: Stan's windowed scheme around them -- in every window of
+        ``mass_windows(Madapt)`` the positions of all chains are accumulated on the device; at its end
+        mass[d] <- 1 / var[d], the step-size search runs again under the new mass and the dual averaging starts over, so that
+        only the last segment freezes.  Without windows (or ``adapt_mass=False``): the plain sequence.  Nothing is read back
+        inside a segment; ``self.naccept`` counts the warm-up's transitions too."""
+        Madapt = int(Madapt)
+        self.find_reasonable_epsilon()
+        windows = self.mass_windows(Madapt) if adapt_mass else []
+        if not windows:
+            if Madapt > 0:
+                self.run(Madapt + 1, store=False, Madapt=Madapt, target_accept=target_accept)
+            return windows
+        never = 2 ** 30                                   # (dual averaging that does not freeze inside the segment)
+        self.run(windows[0][0], store=False, Madapt=never, target_accept=target_accept)
+        self._moments().zero_()
+        for start, end in windows:
+            self.run(end - start, store=False, Madapt=never, target_accept=target_accept, moments=True)
+            self.mass_from_moments(reset=True)
+            self.find_reasonable_epsilon()                # (under the new mass; mu, epsbar, Hbar, m start over)
+        left = Madapt - windows[-1][1]
+        self.run(left + 1, store=False, Madapt=left, target_accept=target_accept)
+        return windows
 
     def step(self, num_steps, step_size, p0=None, u=None):
         """One HMC transition per chain.  ``p0[B, ndim]`` (standard-normal draws) and ``u[B]`` replace
@@ -1692,7 +1758,16 @@ class HMCSampler(object):
     burn-in, restart and convergence loop with per-walker HMC chains (``BatchedHMC.run``) in place of the stretch move and
     writes ``chhmc.h5`` (``_hmc_chains``); ``"nuts"`` is not built.
     Multi-rank runs give every rank a sub-ensemble of ``nwalkers / world`` walkers and gather the chain once per convergence
-    check (``_Ranks``); every rank of the run must make the call (``dist.enter`` raises within two minutes otherwise)."""
+    check (``_Ranks``); every rank of the run must make the call (``dist.enter`` raises within two minutes otherwise).
+
+    ``sample(method="hmc", adapt_mass=True)`` also adapts the diagonal mass during the warm-up (``BatchedHMC.adapt``; ``m``
+    is then the starting mass) and, in a single-rank run, writes the result -- ``mass[ndim]``, ``eps[nwalkers]``,
+    ``num_steps``, ``Madapt`` -- to ``chhmc_adapt.npz`` next to ``chhmc.h5``: a resumed run with ``adapt_mass=True`` whose
+    file matches ``ndim`` / ``nwalkers`` loads it and skips the search and the adaptation; ``overwrite=True`` removes it.
+    Multi-rank runs adapt per rank from their own chains and neither write nor read that file.  ``self.mass`` is the mass
+    the chains of the last hmc run ended up with."""
+
+    ADAPT_FILE = "chhmc_adapt.npz"
 
     def __init__(self, lnp, dlnp, ddlnp, ndim, nwalkers, x0=None, m=None, transform=None, torchspeed=False, seed=0,
                  dist_group=None, exchange=None):
@@ -1700,12 +1775,13 @@ class HMCSampler(object):
         self.exchange = exchange                             # how a multi-rank run splits the ensemble (_Ranks); None: automatic
         self.transform, self.x0, self.nparams, self.nwalkers = transform, x0, ndim, nwalkers
         self.m = np.ones(ndim) if m is None else m
+        self.mass = None
         self.sampler = None
         self.seed, self.group = seed, dist_group
 
     def sample(self, pool, nsamp, samp_steps=0, samp_eps=0, Madapt=1000, outdir="./", progress=False, overwrite=False,
                ntimes=10, tautol=0.01, method="emcee", incremental=True, meanshift=0.1, stdshift=0.1, nk=2, ncheck=100,
-               burnin=100, profile=None):
+               burnin=100, profile=None, adapt_mass=False):
         if method not in ("emcee", "hmc"):
             # sampler.py's "nuts" branch is unreachable in the reference and not built here
             raise NotImplementedError(method)
@@ -1713,6 +1789,9 @@ class HMCSampler(object):
         if hmc and not getattr(self.lnp, "device_only", True):
             raise NotImplementedError("HMC needs the gradient of the log-probability: a user loglikelihoodfunc / "
                                       "externalloglike is host code without one")
+        if hmc and adapt_mass and samp_eps:
+            raise ValueError("adapt_mass with a fixed samp_eps = %r: the mass is adapted together with the step sizes "
+                             "(samp_eps 0 or None)" % (samp_eps,))
         import time
         t_start = time.perf_counter()
         prof = _Prof(profile)
@@ -1726,6 +1805,10 @@ class HMCSampler(object):
             return store
         x0 = self.x0
         resume = False
+        # the warm-up's result next to the chain file (single-rank runs; written and read with adapt_mass only, removed with the chain)
+        sidecar = os.path.join(outdir, self.ADAPT_FILE) if hmc and rk.real_world == 1 else None
+        if sidecar and overwrite and os.path.exists(sidecar):
+            os.remove(sidecar)
         if rk.rank == 0 and store.exists():
             if overwrite:
                 store.remove()
@@ -1755,7 +1838,8 @@ class HMCSampler(object):
             print("burnin done...", flush=True)
             ens.naccept.zero_()
         if hmc:
-            ens = self._hmc_chains(rk, x0, samp_steps, samp_eps, Madapt, prof)
+            ens = self._hmc_chains(rk, x0, samp_steps, samp_eps, Madapt, prof, adapt_mass=adapt_mass,
+                                   sidecar=sidecar if adapt_mass else None, resume=resume)
             self.sampler = ens
         else:
             ens.set_state(rk.mine(x0))
@@ -1802,14 +1886,16 @@ class HMCSampler(object):
         return store
 
 
-    def _hmc_chains(self, rk, x0, samp_steps, samp_eps, Madapt, prof):
+    def _hmc_chains(self, rk, x0, samp_steps, samp_eps, Madapt, prof, adapt_mass=False, sidecar=None, resume=False):
         """The chains of ``method="hmc"`` (sampler.py:491-493: ``HamiltonianMove(dlnp, samp_steps, samp_eps, m)``), one per
         walker of this rank, ready for ``_run_blocks``.  ``m`` is the move's ``cov``: momenta ~ N(0, m), drift p / m
         (``_hmc_matrix``, sampler.py:311-320; tests/golden/hmc_move.npz).  ``samp_eps`` > 0: that step size for every chain,
         the reference's semantics.  ``samp_eps`` 0 / None: a step size per chain from ``find_reasonable_epsilon`` and
         ``Madapt`` transitions of dual averaging (NUTSMove's scheme, sampler.py:198-240) plus the one on which that scheme
         puts the averaged step size in place -- none of them stored or counted; the convergence loop then runs on frozen
-        step sizes.  ``samp_steps`` 0 means 5."""
+        step sizes.  ``samp_steps`` 0 means 5.  ``adapt_mass``: ``m`` is the starting mass of ``BatchedHMC.adapt``'s windowed
+        scheme; ``sidecar`` (a file name): where its result is kept, and taken from in place of a warm-up when ``resume`` says
+        the chain file was continued and the file holds ``ndim`` masses and one step size per walker."""
         if samp_eps is not None and samp_eps < 0:
             raise ValueError("samp_eps = %r: a step size is positive (0 or None: found and adapted per chain)" % (samp_eps,))
         m = np.asarray(self.m, np.float64)
@@ -1821,16 +1907,42 @@ class HMCSampler(object):
             raise ValueError("initial state has non-finite log-probability")
         ens.num_steps = int(samp_steps) if samp_steps else 5
         if samp_eps:
+            if adapt_mass:
+                raise ValueError("adapt_mass with a fixed samp_eps = %r" % (samp_eps,))
             ens.eps.fill_(float(samp_eps))
+            self.mass = m.copy()
             return ens
-        with prof.host("adapt"), _lib.stage("run_mcmc.hmc_adapt"):
-            ens.find_reasonable_epsilon()
-            if Madapt > 0:
-                ens.run(int(Madapt) + 1, store=False, Madapt=int(Madapt))
-            ens.naccept.zero_()
-        e = ens.eps.cpu().numpy()
-        print("hmc step sizes after %d adaptive transitions: min %.3g median %.3g max %.3g" % (Madapt, e.min(), np.median(e), e.max()), flush=True)
+        kept = self._load_adaptation(sidecar, ens) if resume and sidecar else None
+        if kept is not None:
+            ens.mass.copy_(torch.as_tensor(kept["mass"], device=ens.dev))
+            ens.eps.copy_(torch.as_tensor(kept["eps"], device=ens.dev))
+            ens.epsbar.copy_(ens.eps)
+            print("hmc step sizes and mass from %s" % sidecar, flush=True)
+        else:
+            with prof.host("adapt"), _lib.stage("run_mcmc.hmc_adapt"):
+                ens.adapt(int(Madapt), adapt_mass=bool(adapt_mass))
+                ens.naccept.zero_()
+        e, mm = ens.eps.cpu().numpy(), ens.mass.cpu().numpy()
+        self.mass = mm.astype(np.float64)
+        if sidecar and kept is None:
+            np.savez(sidecar, mass=mm, eps=e, num_steps=np.int64(ens.num_steps), Madapt=np.int64(Madapt))
+        print("hmc step sizes %s: min %.3g median %.3g max %.3g; mass min %.3g median %.3g max %.3g"
+              % ("after %d adaptive transitions" % Madapt if kept is None else "kept", e.min(), np.median(e), e.max(),
+                 mm.min(), np.median(mm), mm.max()), flush=True)
         return ens
+
+    @staticmethod
+    def _load_adaptation(name, ens):
+        """{mass, eps} of ``chhmc_adapt.npz`` if it is there and fits these chains, else None."""
+        if not os.path.exists(name):
+            return None
+        with np.load(name) as f:
+            if not {"mass", "eps"} <= set(f.files):
+                return None
+            mass, eps = np.asarray(f["mass"], np.float32), np.asarray(f["eps"], np.float32)
+        ok = mass.shape == (ens.ndim,) and eps.shape == (ens.B,) and np.isfinite(mass).all() and (mass > 0).all() \
+            and np.isfinite(eps).all() and (eps > 0).all()
+        return dict(mass=mass, eps=eps) if ok else None
 
 
 class ZeusSampler(object):

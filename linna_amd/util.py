@@ -895,16 +895,17 @@ class NN_samplerv1(object):
                            incremental=True, progress=False, tautol=tautol, meanshift=meanshift, stdshift=stdshift, nk=nk)
 
     def _HMC_sample(self, log_prob, dlnp, ddlnp, ndim, nwalkers, init, pool, transform, samp_steps=5, samp_eps=None, Madapt=1000,
-                    max_n=1000000):
+                    max_n=1000000, adapt_mass=False):
         """util.py:940-945 with the argument order its signature states (its caller passes ``transform`` twice, SURVEY §8
         a18).  ``samp_eps=None``: a step size per chain, found and adapted on the device (``sampler.HMCSampler.sample``) --
         the reference's 0.1 is in latent units and accepts nothing on a posterior much narrower than its prior.  The
-        Hessian mass matrix of :944 is not built: unit mass."""
+        Hessian mass matrix of :944 is not built: unit mass, or with ``adapt_mass`` a diagonal one adapted from the chains
+        during the warm-up (``sampler.BatchedHMC.adapt``)."""
         from . import sampler
         x0 = init + 0.1 * np.random.randn(nwalkers, ndim)                 # util.py:942
         samp = sampler.HMCSampler(log_prob, dlnp, ddlnp, ndim, nwalkers, x0=x0, m=None, transform=transform)
         return samp.sample(pool, max_n, samp_steps, samp_eps or 0, Madapt, outdir=self.outdir, overwrite=True, ntimes=50,
-                           method="hmc", incremental=True, progress=True)
+                           method="hmc", incremental=True, progress=True, adapt_mass=adapt_mass)
 
     def Zeus_sample(self, log_prob, ndim, nwalkers, init, pool, transform, ntimes=50, tautol=0.01, dlnp=None, ddlnp=None,
                     meanshift=0.1, stdshift=0.1, nk=1, max_n=1000000):
@@ -1133,15 +1134,16 @@ def read_chain_and_cut(chainname, nk, ntimes=20, walkercut=False, method="emcee"
 
 
 def run_mcmc(nnsampler, outdir, method, ndim, nwalkers, init, log_prob, dlnp=None, ddlnp=None, pool=None, transform=None,
-             ntimes=50, tautol=0.01, meanshift=0.1, stdshift=0.1, nk=2, max_n=None):
+             ntimes=50, tautol=0.01, meanshift=0.1, stdshift=0.1, nk=2, max_n=None, adapt_mass=False):
     """util.py:1474-1504.  "hmc": per-walker HMC with step sizes adapted on the device (``_HMC_sample``; the reference's own
     branch cannot run); "nuts" is not built.  ``max_n`` (not in the reference): a cap on the iterations of
-    the hmc run, 1000000 as there when None."""
+    the hmc run, 1000000 as there when None.  ``adapt_mass`` (hmc only, not in the reference): also adapt a diagonal mass
+    from the chains during the warm-up."""
     kw = dict(ntimes=ntimes, tautol=tautol, transform=transform, dlnp=dlnp, ddlnp=ddlnp, meanshift=meanshift,
               stdshift=stdshift, nk=nk)
     if method == "hmc":
         return nnsampler._HMC_sample(log_prob, dlnp, ddlnp, ndim, nwalkers, init, pool, transform, samp_steps=5, samp_eps=None,
-                                     Madapt=1000, **({} if max_n is None else {"max_n": max_n}))
+                                     Madapt=1000, adapt_mass=adapt_mass, **({} if max_n is None else {"max_n": max_n}))
     if method == "emcee":
         return nnsampler.emcee_sample(log_prob, ndim, nwalkers, init, pool, **kw)
     if method == "zeus":

@@ -10,6 +10,9 @@ in one process, `--repeats` timed windows each; median and spread.  Prints ONE J
   python tools/hmc_run_bench.py --ab OTHER_LIB.so      the scalar step() loop under this tree's library and under another
         build of it (the parent commit's: the nullable per-row step size pointer in the gradient launch's finish must cost
         nothing), alternating, each in a fresh process (LINNA_LIB_PATH), `--rounds` of both; prints the medians and ratios
+  python tools/hmc_run_bench.py --moments              ``run(moments=True)`` (linna_hmc_run_moments: one launch more per transition,
+        the positions of all chains merged into running float64 moments -- what the mass adaptation's windows enqueue) against
+        ``run()``, alternating in one process, ChtoModelv2(33,33) only; prints both rates and their ratio
 """
 import json
 import os
@@ -79,6 +82,40 @@ def measure(scalar_only):
     return out
 
 
+def measure_moments():
+    import numpy as np
+    import torch
+    import bf16_bench
+    from linna_amd import sampler, util
+    dev = torch.device("cuda", 0)
+    lp32 = bf16_bench.v2_problem(dev)
+    forms = {"fp32": lp32, "bf16": util.Log_prob(lp32.data_new, lp32.invcov_new, lp32.model, lp32.y_invtransform_data, lp32.transform,
+                                                  lp32.T, lp32.loglikelihoodfunc, nograd=True, precision="bf16", grad_precision="bf16")}
+    out = {}
+    for prec, lp in forms.items():
+        for B in (128, 4096):
+            x0 = (0.2 * np.random.RandomState(B).standard_normal((B, 33))).astype(np.float32)
+            h = sampler.BatchedHMC(lp, x0, seed=5)
+            h.eps.fill_(EPS)
+            routes = {"run": lambda: h.run(TRANS, NLEAP, store=False),
+                      "run_moments": lambda: h.run(TRANS, NLEAP, store=False, moments=True)}
+            for fn in routes.values():
+                fn()
+            torch.cuda.synchronize()
+            t = {k: [] for k in routes}
+            for _ in range(REPEATS):
+                for k, fn in routes.items():
+                    t0 = time.perf_counter()
+                    fn()
+                    torch.cuda.synchronize()
+                    t[k].append(TRANS / (time.perf_counter() - t0))
+            r = {k: _stats(v) for k, v in t.items()}
+            r["run_moments_over_run"] = round(r["run_moments"]["per_s"] / r["run"]["per_s"], 4)
+            r["moments_us_per_transition"] = round(1e6 / r["run_moments"]["per_s"] - 1e6 / r["run"]["per_s"], 2)
+            out["ChtoModelv2_33_33_%s_%d" % (prec, B)] = r
+    return out
+
+
 def ab(other):
     runs = {"this": [], "other": []}
     for rnd in range(ROUNDS):
@@ -105,7 +142,11 @@ def main():
         print(json.dumps({"tool": "hmc_run_bench", "mode": "ab", "other": sys.argv[sys.argv.index("--ab") + 1], "rounds": ROUNDS,
                           "trans": TRANS, "repeats": REPEATS, "scalar_step_loop": ab(sys.argv[sys.argv.index("--ab") + 1])}))
         return
-    scalar_only = "--scalar-only" in sys.argv
+    if "--moments" in sys.argv:
+        print(json.dumps({"tool": "hmc_run_bench", "mode": "moments", "leapfrog_steps": NLEAP, "trans": TRANS, "repeats": REPEATS,
+                          "rates": measure_moments()}))
+        return
+    scalar_only ="--scalar-only" in sys.argv
     print(json.dumps({"tool": "hmc_run_bench", "leapfrog_steps": NLEAP, "trans": TRANS, "repeats": REPEATS,
                       "scalar_only": scalar_only, "rates": measure(scalar_only)}))
 
