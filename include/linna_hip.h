@@ -604,6 +604,44 @@ int linna_hmc_mass_from_moments(linna_ctx_t* ctx, int ndim, double* mom, float* 
 int linna_hmc_run_moments(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, float* EPS, float* EPSBAR, float* HBAR,
                           const float* MU, int* M, int Madapt, float delta, int step_offset, int num_steps, int ntrans,
                           int* naccept, float* alpha, float* chain, float* logps, double* mom, void* stream);
+
+/* ---- a dense mass adapted on the device (BatchedHMC.adapt(adapt_mass="dense")), 1 <= ndim <= LINNA_HMC_DENSE_MAX_NDIM;
+ * beyond it every entry below returns LINNA_ERR_UNSUPPORTED.
+ * With cov = C C^T (C lower triangular) the pooled covariance of the positions and the mass M = cov^-1, the chains carry the
+ * whitened momentum w = C^T p where the diagonal route carries p: the draw is w ~ N(0, I), the kinetic energy |w|^2 / 2, the
+ * kick w += eps C^T g and the drift q += eps C w.  Every kernel of the diagonal route therefore runs unchanged on a mass
+ * array of ones; only the kick and the drift are a launch of their own behind the gradient launch.
+ * The factor: Cm = {C[ndim][ldc], C^T[ndim][ldc]}, 2 ndim ldc floats, zeros outside the triangles and in the pad columns.
+ * The co-moments: mom = {n, c[ndim], LINNA_HMC_COMOMENT_SLOTS x {S1[ndim], S2[ndim][ndim]}} doubles (zeros = empty, c a shift
+ * the caller chooses close to the mean), S1[i] += sum_b t_bi and S2[i][j] += sum_b t_bi t_bj for j <= i with
+ * t = (double)X - c; slot s takes rows [s per, (s + 1) per), per = ceil(B / SLOTS).  The order of every sum is fixed by
+ * (B, ndim): the same input gives the same bits.  The error of the covariance they give, relative to sqrt(var_i var_j), is
+ * below 64 N 2^-53 (1 + max_d (mean_d - c_d)^2 / var_d) for N rows merged. */
+#define LINNA_HMC_COMOMENT_SLOTS 8
+#define LINNA_HMC_DENSE_MAX_NDIM 128
+size_t linna_hmc_comoments_doubles(int ndim);   /* 1 + ndim + SLOTS (ndim + ndim ndim); 0 if unsupported */
+int linna_hmc_comoments(linna_ctx_t* ctx, int B, int ndim, const float* X, int ldx, double* mom, void* stream);
+/* cov = (S2 - S1 S1^T / n) / (n - 1) of the slots summed in slot order, Stan's shrinkage cov n / (n + 5) + 1e-3 * 5 / (n + 5) I,
+ * and its Cholesky factor in float64, written to Cm as float32.  info[0] (device) = 0: written; k + 1: pivot k was not
+ * finite and positive, Cm untouched; -1: n < 2 or NaN, Cm untouched.  reset != 0: behind it c <- the mean of the rows merged
+ * (kept where n < 1), n and the slots <- 0, whatever info says. */
+int linna_hmc_chol_from_comoments(linna_ctx_t* ctx, int ndim, double* mom, float* Cm, int ldc, int* info, int reset, void* stream);
+/* W[b] += (mul_kick e) C^T G[b], then Q[b] = (X ? X[b] : Q[b]) + (mul_drift e) C W[b], e = EPS ? EPS[b] : 1.  A multiplier of 0
+ * switches its half off (no drift: Q = X where X is given, untouched otherwise).  Both products run over the triangle only,
+ * j ascending, in float32 without contraction.  Pad columns are not written. */
+int linna_hmc_kick_drift_dense(linna_ctx_t* ctx, int B, int ndim, const float* Cm, int ldc, const float* EPS, float mul_kick,
+                               float mul_drift, const float* G, int ldg, float* W, int ldw, const float* X, int ldx, float* Q,
+                               int ldq, void* stream);
+/* linna_hmc_run_moments under the factor Cm: st->mass must be an array of ones and st->P carries w.  Per transition
+ * linna_hmc_init (draw, H0), linna_hmc_kick_drift_dense (0.5, 1) from st->X, num_steps x {linna_logprob_grad,
+ * linna_hmc_kick_drift_dense (1, 1); (0.5, 0) behind the last}, linna_hmc_accept_adapt, and for mom != NULL
+ * linna_hmc_comoments on st->X.  Bit for bit the loop of those entries. */
+int linna_hmc_run_dense(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, const float* Cm, int ldc, float* EPS,
+                        float* EPSBAR, float* HBAR, const float* MU, int* M, int Madapt, float delta, int step_offset, int num_steps,
+                        int ntrans, int* naccept, float* alpha, float* chain, float* logps, double* mom, void* stream);
+/* linna_hmc_find_epsilon with the same trajectories. */
+int linna_hmc_find_epsilon_dense(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, const float* Cm, int ldc, float* R0,
+                                 float* EPS, int* state, int* nactive, int step_offset, int max_rounds, void* stream);
 int linna_step_increment(linna_ctx_t* ctx, int* step_dev, void* stream);
 
 /* Ensemble slice sampling (zeus DifferentialMove behind sampler.py:728-735): per active walker a

@@ -187,6 +187,12 @@ _SIGNATURES = {
     "linna_hmc_moments": (_I, [_V, _I, _I, _V, _I, _V, _V]),
     "linna_hmc_mass_from_moments": (_I, [_V, _I, _V, _V, _I, _V]),
     "linna_hmc_run_moments": (_I, [_V, _V, _V, _V, _V, _V, _V, _V, _I, _F, _I, _I, _I, _V, _V, _V, _V, _V, _V]),
+    "linna_hmc_comoments_doubles": (_SZ, [_I]),
+    "linna_hmc_comoments": (_I, [_V, _I, _I, _V, _I, _V, _V]),
+    "linna_hmc_chol_from_comoments": (_I, [_V, _I, _V, _V, _I, _V, _I, _V]),
+    "linna_hmc_kick_drift_dense": (_I, [_V, _I, _I, _V, _I, _V, _F, _F, _V, _I, _V, _I, _V, _I, _V, _I, _V]),
+    "linna_hmc_run_dense": (_I, [_V, _V, _V, _V, _I, _V, _V, _V, _V, _V, _I, _F, _I, _I, _I, _V, _V, _V, _V, _V, _V]),
+    "linna_hmc_find_epsilon_dense": (_I, [_V, _V, _V, _V, _I, _V, _V, _V, _V, _I, _I, _V]),
     "linna_step_increment": (_I, [_V, _V, _V]),
     "linna_slice_init": (_I, [_V, _V, _V, _I, _V, _I, _V, _I, _I, _V, _U64, _V, _I, _V, _I, _V, _V, _V, _V, _I, _V]),
     "linna_slice_points": (_I, [_V, _V, _I, _I, _V, _I, _V, _I, _V, _V, _I, _I, _V]),

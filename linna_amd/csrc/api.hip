@@ -1509,10 +1509,33 @@ static int hmc_entry_check(const linna_logprob_t* lp, const linna_hmc_state_t* s
     if (st->ld < lp->d.nin) { set_error("%s: ld %d < %d parameters", who, st->ld, lp->d.nin); return LINNA_ERR_INVALID; }
     return logprob_grad_ready(lp);
 }
-// one trajectory from st->X with the momenta hmc_start draws (P0 == nullptr) or is given: start, num_steps gradient launches
+// a dense mass's factor {C, C^T} (linna_hip.h); C == nullptr: the diagonal route
+struct HmcDense { const float* C; int ldc; };
+static int hmc_dense_check(const linna_logprob_t* lp, const HmcDense& dn, const char* who) {
+    if (lp->d.nin > LINNA_HMC_DENSE_MAX_NDIM) {
+        set_error("%s: a dense mass holds at most %d parameters, not %d", who, LINNA_HMC_DENSE_MAX_NDIM, lp->d.nin); return LINNA_ERR_UNSUPPORTED;
+    }
+    if (dn.ldc < lp->d.nin) { set_error("%s: ldc %d < %d parameters", who, dn.ldc, lp->d.nin); return LINNA_ERR_INVALID; }
+    return LINNA_OK;
+}
+// one trajectory from st->X with the momenta hmc_start draws (P0 == nullptr) or is given: start, num_steps gradient launches.
+// dn.C: st->P is the whitened momentum (st->mass an array of ones), the gradient launch runs without a leapfrog in its finish
+// and the dense kick and drift follow it as a launch of their own
 static int hmc_trajectory(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, const float* P0, const float* EPS, int step_off,
-                          int num_steps, void* stream) {
+                          int num_steps, void* stream, const HmcDense& dn = HmcDense{nullptr, 0}) {
     const int B = st->B, nd = lp->d.nin, ld = st->ld;
+    if (dn.C) {
+        TRY(launch_hmc_start(B, nd, st->mass, st->seed, st->step_dev, st->lnp, P0, ld, nullptr, 0, 0.f, 0.f, nullptr, 0, st->P, ld,
+                             nullptr, 0, st->H0, S(stream), nullptr, step_off));
+        TRY(launch_hmc_kick_drift_dense(B, nd, dn.C, dn.ldc, EPS, 0.5f, 1.f, st->G, ld, st->P, ld, st->X, ld, st->Q, ld, S(stream)));
+        for (int i = 0; i < num_steps; ++i) {
+            const bool last = i == num_steps - 1;
+            TRY(logprob_grad_impl(lp, st->Q, ld, B, ws, st->lnp_new, st->Gnew, ld, nullptr, stream));
+            TRY(launch_hmc_kick_drift_dense(B, nd, dn.C, dn.ldc, EPS, last ? 0.5f : 1.f, last ? 0.f : 1.f, st->Gnew, ld, st->P, ld,
+                                            nullptr, 0, st->Q, ld, S(stream)));
+        }
+        return LINNA_OK;
+    }
     TRY(launch_hmc_start(B, nd, st->mass, st->seed, st->step_dev, st->lnp, P0, ld, st->G, ld, 0.5f, 1.f, st->X, ld, st->P, ld, st->Q, ld,
                          st->H0, S(stream), EPS, step_off));
     for (int i = 0; i < num_steps; ++i) {
@@ -1523,23 +1546,25 @@ static int hmc_trajectory(linna_logprob_t* lp, const linna_hmc_state_t* st, void
     return LINNA_OK;
 }
 
-// linna_hmc_run and linna_hmc_run_moments: mom != nullptr adds the moments launch on st->X behind every Metropolis launch
+// linna_hmc_run, linna_hmc_run_moments and linna_hmc_run_dense: mom != nullptr adds the moments launch on st->X behind every
+// Metropolis launch (under a dense mass the co-moments launch)
 static int hmc_run_impl(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, float* EPS, float* EPSBAR, float* HBAR, const float* MU,
                         int* M, int Madapt, float delta, int step_offset, int num_steps, int ntrans, int* naccept, float* alpha,
-                        float* chain, float* logps, double* mom, void* stream) {
+                        float* chain, float* logps, double* mom, void* stream, const HmcDense& dn = HmcDense{nullptr, 0}) {
     if (!lp || !st || !ws || !EPS || num_steps < 1 || ntrans < 1 || Madapt < 0 || (chain != nullptr) != (logps != nullptr)) {
         set_error("hmc_run: bad arguments"); return LINNA_ERR_INVALID;
     }
     if (Madapt > 0 && (!EPSBAR || !HBAR || !MU || !M)) { set_error("hmc_run: Madapt > 0 needs the adaptation state"); return LINNA_ERR_INVALID; }
     TRY(hmc_entry_check(lp, st, "hmc_run"));
+    if (dn.C) TRY(hmc_dense_check(lp, dn, "hmc_run_dense"));
     const int B = st->B, nd = lp->d.nin, ld = st->ld;
     const HmcAdapt ad{EPS, EPSBAR, HBAR, MU, M, Madapt, delta};
     for (int i = 0; i < ntrans; ++i) {
-        TRY(hmc_trajectory(lp, st, ws, nullptr, EPS, step_offset + i, num_steps, stream));
+        TRY(hmc_trajectory(lp, st, ws, nullptr, EPS, step_offset + i, num_steps, stream, dn));
         TRY(launch_hmc_accept(B, nd, st->mass, st->seed, st->step_dev, step_offset + i, st->H0, st->P, ld, st->Q, ld, st->lnp_new,
                               st->Gnew, ld, nullptr, st->X, ld, st->lnp, st->G, naccept, alpha, ad,
                               chain ? chain + (size_t)i * B * nd : nullptr, logps ? logps + (size_t)i * B : nullptr, S(stream)));
-        if (mom) TRY(launch_hmc_moments(B, nd, st->X, ld, mom, S(stream)));
+        if (mom) TRY(dn.C ? launch_hmc_comoments(B, nd, st->X, ld, mom, S(stream)) : launch_hmc_moments(B, nd, st->X, ld, mom, S(stream)));
     }
     return LINNA_OK;
 }
@@ -1558,19 +1583,39 @@ int linna_hmc_run_moments(linna_logprob_t* lp, const linna_hmc_state_t* st, void
                         logps, mom, stream);
 } LINNA_CATCH_INT
 
-int linna_hmc_find_epsilon(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, float* R0, float* EPS, int* state, int* nactive,
-                           int step_offset, int max_rounds, void* stream) try {
+static int hmc_find_epsilon_impl(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, float* R0, float* EPS, int* state, int* nactive,
+                                 int step_offset, int max_rounds, void* stream, const HmcDense& dn) {
     if (!lp || !st || !ws || !R0 || !EPS || !state || !nactive || max_rounds < 1) { set_error("hmc_find_epsilon: bad arguments"); return LINNA_ERR_INVALID; }
     TRY(hmc_entry_check(lp, st, "hmc_find_epsilon"));
+    if (dn.C) TRY(hmc_dense_check(lp, dn, "hmc_find_epsilon_dense"));
     const int B = st->B, nd = lp->d.nin, ld = st->ld;
     TRY(check_hip(hipMemsetAsync(nactive, 0, sizeof(int), S(stream)), "hipMemsetAsync"));
     TRY(launch_hmc_find_eps_init(B, nd, st->seed, st->step_dev, step_offset, R0, ld, EPS, state, S(stream)));
     for (int r = 0; r < max_rounds; ++r) {
-        TRY(hmc_trajectory(lp, st, ws, R0, EPS, step_offset, 1, stream));
+        TRY(hmc_trajectory(lp, st, ws, R0, EPS, step_offset, 1, stream, dn));
         TRY(launch_hmc_find_eps(B, nd, st->mass, st->H0, st->P, ld, st->lnp_new, st->Gnew, ld, EPS, state,
                                 r + 1 == max_rounds ? nactive : nullptr, S(stream)));
     }
     return LINNA_OK;
+}
+
+int linna_hmc_find_epsilon(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, float* R0, float* EPS, int* state, int* nactive,
+                           int step_offset, int max_rounds, void* stream) try {
+    return hmc_find_epsilon_impl(lp, st, ws, R0, EPS, state, nactive, step_offset, max_rounds, stream, HmcDense{nullptr, 0});
+} LINNA_CATCH_INT
+
+int linna_hmc_run_dense(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, const float* Cm, int ldc, float* EPS, float* EPSBAR,
+                        float* HBAR, const float* MU, int* M, int Madapt, float delta, int step_offset, int num_steps, int ntrans,
+                        int* naccept, float* alpha, float* chain, float* logps, double* mom, void* stream) try {
+    if (!Cm) { set_error("hmc_run_dense: no factor"); return LINNA_ERR_INVALID; }
+    return hmc_run_impl(lp, st, ws, EPS, EPSBAR, HBAR, MU, M, Madapt, delta, step_offset, num_steps, ntrans, naccept, alpha, chain,
+                        logps, mom, stream, HmcDense{Cm, ldc});
+} LINNA_CATCH_INT
+
+int linna_hmc_find_epsilon_dense(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, const float* Cm, int ldc, float* R0,
+                                 float* EPS, int* state, int* nactive, int step_offset, int max_rounds, void* stream) try {
+    if (!Cm) { set_error("hmc_find_epsilon_dense: no factor"); return LINNA_ERR_INVALID; }
+    return hmc_find_epsilon_impl(lp, st, ws, R0, EPS, state, nactive, step_offset, max_rounds, stream, HmcDense{Cm, ldc});
 } LINNA_CATCH_INT
 
 // ------------------------------------------------------------------ training
@@ -1793,6 +1838,34 @@ int linna_hmc_moments(linna_ctx_t*, int B, int ndim, const float* X, int ldx, do
 int linna_hmc_mass_from_moments(linna_ctx_t*, int ndim, double* mom, float* mass, int reset, void* stream) try {
     if (ndim < 1 || !mom || !mass) { set_error("hmc_mass_from_moments: bad arguments"); return LINNA_ERR_INVALID; }
     return launch_hmc_mass_from_moments(ndim, mom, mass, reset, S(stream));
+} LINNA_CATCH_INT
+static int hmc_dense_ndim(int ndim, const char* who) {
+    if (ndim > LINNA_HMC_DENSE_MAX_NDIM) {
+        set_error("%s: a dense mass holds at most %d parameters, not %d", who, LINNA_HMC_DENSE_MAX_NDIM, ndim); return LINNA_ERR_UNSUPPORTED;
+    }
+    return LINNA_OK;
+}
+size_t linna_hmc_comoments_doubles(int ndim) try {
+    if (ndim < 1 || ndim > LINNA_HMC_DENSE_MAX_NDIM) return 0;
+    return 1 + (size_t)ndim + LINNA_HMC_COMOMENT_SLOTS * ((size_t)ndim + (size_t)ndim * ndim);
+} LINNA_CATCH_SIZE
+int linna_hmc_comoments(linna_ctx_t*, int B, int ndim, const float* X, int ldx, double* mom, void* stream) try {
+    if (B < 1 || ndim < 1 || !X || ldx < ndim || !mom) { set_error("hmc_comoments: bad arguments"); return LINNA_ERR_INVALID; }
+    TRY(hmc_dense_ndim(ndim, "hmc_comoments"));
+    return launch_hmc_comoments(B, ndim, X, ldx, mom, S(stream));
+} LINNA_CATCH_INT
+int linna_hmc_chol_from_comoments(linna_ctx_t*, int ndim, double* mom, float* Cm, int ldc, int* info, int reset, void* stream) try {
+    if (ndim < 1 || !mom || !Cm || ldc < ndim || !info) { set_error("hmc_chol_from_comoments: bad arguments"); return LINNA_ERR_INVALID; }
+    TRY(hmc_dense_ndim(ndim, "hmc_chol_from_comoments"));
+    return launch_hmc_chol_from_comoments(ndim, mom, Cm, ldc, info, reset, S(stream));
+} LINNA_CATCH_INT
+int linna_hmc_kick_drift_dense(linna_ctx_t*, int B, int ndim, const float* Cm, int ldc, const float* EPS, float mul_kick, float mul_drift,
+                               const float* G, int ldg, float* W, int ldw, const float* X, int ldx, float* Q, int ldq, void* stream) try {
+    if (B < 1 || ndim < 1 || !Cm || ldc < ndim || !G || ldg < ndim || !W || ldw < ndim || !Q || ldq < ndim || (X && ldx < ndim)) {
+        set_error("hmc_kick_drift_dense: bad arguments"); return LINNA_ERR_INVALID;
+    }
+    TRY(hmc_dense_ndim(ndim, "hmc_kick_drift_dense"));
+    return launch_hmc_kick_drift_dense(B, ndim, Cm, ldc, EPS, mul_kick, mul_drift, G, ldg, W, ldw, X, ldx, Q, ldq, S(stream));
 } LINNA_CATCH_INT
 int linna_hmc_start_eps(linna_ctx_t*, int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, int step_offset,
                         const float* lnp, const float* P0, int ldp0, const float* G, int ldg, const float* EPS, float mul_kick,

@@ -321,6 +321,12 @@ int launch_hmc_find_eps(int B, int ndim, const float* mass, const float* H0, con
 // running moments of the chain positions, mom = {n, mean[ndim], M2[ndim]} (float64), and the diagonal mass they give
 int launch_hmc_moments(int B, int ndim, const float* X, int ldx, double* mom, hipStream_t s);
 int launch_hmc_mass_from_moments(int ndim, double* mom, float* mass, int reset, hipStream_t s);
+// a dense mass (ndim <= LINNA_HMC_DENSE_MAX_NDIM): shifted co-moments of the positions, the Cholesky factor {C, C^T} of their
+// shrunk covariance, and the leapfrog's kick and drift in the whitened momentum (eps nullable: a step size per chain)
+int launch_hmc_comoments(int B, int ndim, const float* X, int ldx, double* mom, hipStream_t s);
+int launch_hmc_chol_from_comoments(int ndim, double* mom, float* Cm, int ldc, int* info, int reset, hipStream_t s);
+int launch_hmc_kick_drift_dense(int B, int ndim, const float* Cm, int ldc, const float* eps, float ek, float ed, const float* G,
+                                int ldg, float* W, int ldw, const float* X, int ldx, float* Q, int ldq, hipStream_t s);
 int launch_slice_points(const float* coords, int ldc, int ndim, const int* S, int ns, const float* DIR, int ldd,
                         const float* w, float* Q, int ldq, int nrep, hipStream_t s);
 int launch_slice_expand(const float* Z0, const float* ZL, const float* ZR, float* L, float* R, int* flags, int ns,

@@ -703,6 +703,195 @@ __global__ void hmc_mass_from_moments_kernel(int ndim, double* __restrict__ mom,
     if (reset) for (int i = threadIdx.x; i < 1 + 2 * ndim; i += blockDim.x) mom[i] = 0.0;
 }
 
+// ------------------------------------------------------------------ a dense mass: co-moments, their Cholesky factor, the whitened leapfrog
+// Shifted raw sums of the chain positions, mom = {n, c[nd], SLOTS x {S1[nd], S2[nd][nd] (j <= i)}} in float64 (linna_hip.h),
+// t = (double)X - c.  Every output word depends on its own old value, X and c alone, so the grid is (tile of the lower
+// triangle, slot): a tile is 8 x 8 pairs (lane = pair), a slot a fixed share of the rows, ceil(B / SLOTS) of them in row
+// order.  The four waves of a workgroup stride over the slot's rows 16 at a time; the loads of a round are unconditional
+// (indices clamped, values masked: hmc_moments_kernel's lesson); the per-wave partials meet in LDS and are added in wave
+// order.  n is written by one thread of the launch and read by none.  No atomics: the same input gives the same bits.
+constexpr int COMOM_SLOTS = LINNA_HMC_COMOMENT_SLOTS, COMOM_T = 8, COMOM_WAVES = 4, COMOM_ROWS = 16;
+static_assert(COMOM_T * COMOM_T == 64, "a lane per pair of a tile");
+
+__global__ __launch_bounds__(COMOM_WAVES * 64) void hmc_comoments_kernel(int B, int ndim, const float* __restrict__ X, int ldx,
+                                                                         double* __restrict__ mom) {
+    __shared__ double part[2][COMOM_WAVES][64];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    // tile blockIdx.x of the lower triangle, rows of tiles in order: (ti, tj), tj <= ti
+    int ti = 0;
+    while ((ti + 1) * (ti + 2) / 2 <= (int)blockIdx.x) ++ti;
+    const int tj = (int)blockIdx.x - ti * (ti + 1) / 2;
+    const int i = ti * COMOM_T + (lane >> 3), j = tj * COMOM_T + (lane & 7);
+    const int ic = min(i, ndim - 1), jc = min(j, ndim - 1);   // (the pad of a row is never read)
+    const bool on = i < ndim && j <= i;
+    const int per = (B + COMOM_SLOTS - 1) / COMOM_SLOTS, slot = blockIdx.y;
+    const int lo = min(slot * per, B), hi = min(lo + per, B);
+    const double ci = mom[1 + ic], cj = mom[1 + jc];
+    double s1 = 0.0, s2 = 0.0;
+    for (int b0 = lo + wave * COMOM_ROWS; b0 < hi; b0 += COMOM_WAVES * COMOM_ROWS) {
+        float vi[COMOM_ROWS], vj[COMOM_ROWS];
+#pragma unroll
+        for (int u = 0; u < COMOM_ROWS; ++u) {
+            const size_t row = (size_t)min(b0 + u, B - 1) * ldx;
+            vi[u] = X[row + ic];
+            vj[u] = X[row + jc];
+        }
+#pragma unroll
+        for (int u = 0; u < COMOM_ROWS; ++u) {
+            const bool in = b0 + u < hi;
+            const double a = in ? (double)vi[u] - ci : 0.0, b = in ? (double)vj[u] - cj : 0.0;
+            s1 += a;
+            s2 += a * b;
+        }
+    }
+    part[0][wave][lane] = s1;
+    part[1][wave][lane] = s2;
+    __syncthreads();
+    if (wave == 0 && on) {
+        double t1 = 0.0, t2 = 0.0;
+        for (int w = 0; w < COMOM_WAVES; ++w) { t1 += part[0][w][lane]; t2 += part[1][w][lane]; }
+        double* S = mom + 1 + ndim + (size_t)slot * ((size_t)ndim + (size_t)ndim * ndim);
+        if (i == j) S[i] += t1;
+        S[ndim + (size_t)i * ndim + j] += t2;
+    }
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) mom[0] += (double)B;
+}
+
+// One workgroup: the slots summed in slot order, cov = (S2 - S1 S1^T / n) / (n - 1), Stan's shrinkage for a dense metric
+// (cov n / (n + 5) + 1e-3 * 5 / (n + 5) I) and its Cholesky factor in float64 -- the packed lower triangle in LDS, 66 KB at
+// ndim = 128.  Right-looking with ONE barrier per column: step k subtracts L[i][k] L[j][k] / pivot_k from the trailing
+// triangle and leaves column k unscaled (C[i][k] = L[i][k] / sqrt(pivot_k) at the end), so that a step reads only what the
+// step before wrote.  info[0] = 0: C as float32 into Cm[nd][ldc] and C^T behind it, zeros outside the triangles and in the
+// pad; a pivot k that is not finite and positive: info[0] = k + 1, Cm untouched; n < 2 (or NaN): info[0] = -1, Cm untouched.
+// reset: behind a barrier after the last read of mom, c <- the mean (kept where n < 1), n and the slots <- 0.
+constexpr int CHOL_MAX = LINNA_HMC_DENSE_MAX_NDIM, CHOL_THREADS = 1024;
+__device__ __forceinline__ int tri(int i, int j) { return i * (i + 1) / 2 + j; }
+
+__global__ __launch_bounds__(CHOL_THREADS) void hmc_chol_from_comoments_kernel(int ndim, double* __restrict__ mom, float* __restrict__ Cm,
+                                                                               int ldc, int* __restrict__ info, int reset) {
+    __shared__ double L[CHOL_MAX * (CHOL_MAX + 1) / 2];
+    __shared__ double s1[CHOL_MAX];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, nwaves = CHOL_THREADS / 64;
+    const size_t slotw = (size_t)ndim + (size_t)ndim * ndim;
+    const double* slots = mom + 1 + ndim;
+    const double n = mom[0];
+    const bool have = n >= 2.0;                               // (false for a NaN)
+    for (int d = tid; d < ndim; d += CHOL_THREADS) {
+        double t = 0.0;
+        for (int s = 0; s < COMOM_SLOTS; ++s) t += slots[s * slotw + d];
+        s1[d] = t;
+    }
+    __syncthreads();
+    int fail = have ? 0 : -1;
+    if (have) {
+        const double shr = n / (n + 5.0), add = 1e-3 * 5.0 / (n + 5.0);
+        for (int i = wave; i < ndim; i += nwaves)
+            for (int j = lane; j <= i; j += 64) {
+                double t = 0.0;
+                for (int s = 0; s < COMOM_SLOTS; ++s) t += slots[s * slotw + ndim + (size_t)i * ndim + j];
+                const double cov = (t - s1[i] * s1[j] / n) / (n - 1.0);
+                L[tri(i, j)] = cov * shr + (i == j ? add : 0.0);
+            }
+        for (int k = 0; k < ndim; ++k) {
+            __syncthreads();
+            const double piv = L[tri(k, k)];                  // (every thread reads the same word: the branch is uniform)
+            if (!(piv > 0.0 && isfinite(piv))) { fail = k + 1; break; }
+            const double inv = 1.0 / piv;
+            for (int i = k + 1 + wave; i < ndim; i += nwaves) {
+                const double lik = L[tri(i, k)] * inv;
+                for (int j = k + 1 + lane; j <= i; j += 64) L[tri(i, j)] -= lik * L[tri(j, k)];
+            }
+        }
+        __syncthreads();
+        if (!fail) {
+            for (int i = wave; i < ndim; i += nwaves)
+                for (int j = lane; j < ldc; j += 64) {
+                    const float c = j <= i ? (float)(L[tri(i, j)] / sqrt(L[tri(j, j)])) : 0.f;
+                    Cm[(size_t)i * ldc + j] = c;
+                    if (j < ndim) Cm[((size_t)ndim + j) * ldc + i] = c;
+                    else Cm[((size_t)ndim + i) * ldc + j] = 0.f;
+                }
+        }
+    }
+    if (tid == 0) info[0] = fail;
+    if (!reset) return;
+    __syncthreads();                                          // (every read of mom is behind us)
+    if (n >= 1.0) for (int d = tid; d < ndim; d += CHOL_THREADS) mom[1 + d] += s1[d] / n;
+    for (size_t e = tid; e < COMOM_SLOTS * slotw; e += CHOL_THREADS) mom[1 + ndim + e] = 0.0;
+    if (tid == 0) mom[0] = 0.0;
+}
+
+// The leapfrog's kick and drift under the dense mass M = (C C^T)^-1 in the whitened momentum w = C^T p:
+//   W[b] += (ek e) C^T G[b];   Q[b] = (X ? X[b] : Q[b]) + (ed e) C W[b],   e = EPS ? EPS[b] : 1
+// (either multiplier may be 0: that half is off; without a drift Q = X where X is given and is left alone otherwise).
+// A wave per chain, lane = dimension, a lane holds dimensions lane and lane + 64 (ndim <= 128).  Both matrix-vector
+// products read rows -- (C^T g)_d = sum_{j >= d} Ct[d][j] g_j from the transposed copy behind C, (C w)_d = sum_{j <= d}
+// C[d][j] w_j -- over the triangle only, j ascending, a float32 product and then a float32 add.  Pad columns are not written.
+__device__ __forceinline__ float wave_pick(float v0, float v1, int j) { return j < 64 ? __shfl(v0, j, 64) : __shfl(v1, j - 64, 64); }
+// a0 / a1 = the triangle product of rows r0 / r1 (dimensions d0 / d1 of this lane) with the wave's vector {v0, v1}: j <= d
+// (LOWER) or j >= d.  Eight columns a round, their loads unconditional (the column index clamped into the row, the product
+// masked) so that all of them are in flight before the first add: one load a column waited out a cache access each.
+template <bool LOWER>
+__device__ __forceinline__ void wave_tri_dot(const float* __restrict__ r0, const float* __restrict__ r1, float v0, float v1, int d0,
+                                             int d1, bool on0, bool on1, int ndim, float& a0, float& a1) {
+    constexpr int U = 8;
+    a0 = 0.f; a1 = 0.f;
+    for (int j0 = 0; j0 < ndim; j0 += U) {
+        float c0[U], c1[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int jc = min(j0 + u, ndim - 1);
+            c0[u] = r0[jc];
+            c1[u] = ndim > 64 ? r1[jc] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = j0 + u;
+            const float vj = wave_pick(v0, v1, min(j, ndim - 1));
+            if (j < ndim && on0 && (LOWER ? j <= d0 : j >= d0)) a0 += c0[u] * vj;
+            if (j < ndim && on1 && (LOWER ? j <= d1 : j >= d1)) a1 += c1[u] * vj;
+        }
+    }
+}
+
+__global__ void hmc_kick_drift_dense_kernel(int B, int ndim, const float* __restrict__ Cm, int ldc, const float* __restrict__ eps,
+                                            float ek, float ed, const float* __restrict__ G, int ldg, float* __restrict__ W, int ldw,
+                                            const float* __restrict__ X, int ldx, float* __restrict__ Q, int ldq) {
+    const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (b >= B) return;
+    const bool kick = ek != 0.f, drift = ed != 0.f;
+    if (eps) { const float e = eps[b]; ek *= e; ed *= e; }
+    const int d0 = lane, d1 = lane + 64;
+    const bool on0 = d0 < ndim, on1 = d1 < ndim;
+    float w0 = on0 ? W[(size_t)b * ldw + d0] : 0.f, w1 = on1 ? W[(size_t)b * ldw + d1] : 0.f;
+    if (kick) {
+        const float* Ct = Cm + (size_t)ndim * ldc;
+        const float g0 = on0 ? G[(size_t)b * ldg + d0] : 0.f, g1 = on1 ? G[(size_t)b * ldg + d1] : 0.f;
+        const float* r0 = Ct + (size_t)min(d0, ndim - 1) * ldc;
+        const float* r1 = Ct + (size_t)min(d1, ndim - 1) * ldc;
+        float a0, a1;
+        wave_tri_dot<false>(r0, r1, g0, g1, d0, d1, on0, on1, ndim, a0, a1);
+        w0 += ek * a0;
+        w1 += ek * a1;
+        if (on0) W[(size_t)b * ldw + d0] = w0;
+        if (on1) W[(size_t)b * ldw + d1] = w1;
+    }
+    if (!drift && !X) return;
+    float q0 = 0.f, q1 = 0.f;
+    if (on0) q0 = X ? X[(size_t)b * ldx + d0] : Q[(size_t)b * ldq + d0];
+    if (on1) q1 = X ? X[(size_t)b * ldx + d1] : Q[(size_t)b * ldq + d1];
+    if (drift) {
+        const float* r0 = Cm + (size_t)min(d0, ndim - 1) * ldc;
+        const float* r1 = Cm + (size_t)min(d1, ndim - 1) * ldc;
+        float a0, a1;
+        wave_tri_dot<true>(r0, r1, w0, w1, d0, d1, on0, on1, ndim, a0, a1);
+        q0 += ed * a0;
+        q1 += ed * a1;
+    }
+    if (on0) Q[(size_t)b * ldq + d0] = q0;
+    if (on1) Q[(size_t)b * ldq + d1] = q1;
+}
+
 __global__ void step_increment_kernel(int* step) { step[0] += 1; }
 
 // ------------------------------------------------------------------ ensemble slice sampling (zeus, Karamanis & Beutler 2021)
@@ -1025,6 +1214,21 @@ int launch_hmc_moments(int B, int ndim, const float* X, int ldx, double* mom, hi
 int launch_hmc_mass_from_moments(int ndim, double* mom, float* mass, int reset, hipStream_t s) {
     hipLaunchKernelGGL(hmc_mass_from_moments_kernel, dim3(1), dim3(256), 0, s, ndim, mom, mass, reset);
     LAUNCH_CHECK("hmc_mass_from_moments");
+}
+int launch_hmc_comoments(int B, int ndim, const float* X, int ldx, double* mom, hipStream_t s) {
+    const int nt = (ndim + COMOM_T - 1) / COMOM_T;
+    hipLaunchKernelGGL(hmc_comoments_kernel, dim3(nt * (nt + 1) / 2, COMOM_SLOTS), dim3(COMOM_WAVES * 64), 0, s, B, ndim, X, ldx, mom);
+    LAUNCH_CHECK("hmc_comoments");
+}
+int launch_hmc_chol_from_comoments(int ndim, double* mom, float* Cm, int ldc, int* info, int reset, hipStream_t s) {
+    hipLaunchKernelGGL(hmc_chol_from_comoments_kernel, dim3(1), dim3(CHOL_THREADS), 0, s, ndim, mom, Cm, ldc, info, reset);
+    LAUNCH_CHECK("hmc_chol_from_comoments");
+}
+int launch_hmc_kick_drift_dense(int B, int ndim, const float* Cm, int ldc, const float* eps, float ek, float ed, const float* G,
+                                int ldg, float* W, int ldw, const float* X, int ldx, float* Q, int ldq, hipStream_t s) {
+    hipLaunchKernelGGL(hmc_kick_drift_dense_kernel, dim3((B + 3) / 4), dim3(256), 0, s, B, ndim, Cm, ldc, eps, ek, ed, G, ldg, W,
+                       ldw, X, ldx, Q, ldq);
+    LAUNCH_CHECK("hmc_kick_drift_dense");
 }
 int launch_slice_points(const float* coords, int ldc, int ndim, const int* S, int ns, const float* DIR, int ldd,
                         const float* w, float* Q, int ldq, int nrep, hipStream_t s) {

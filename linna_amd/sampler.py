@@ -1385,7 +1385,15 @@ class BatchedHMC(object):
     and ``run(..., Madapt=n)`` adapts by dual averaging (``self.epsbar``, ``Hbar``, ``mu``, ``m``): what ``HMCSampler.sample(
     method="hmc")`` drives.  Both routes share one Philox sequence (``iteration``).  ``adapt`` is the whole warm-up, with
     the diagonal mass adapted from the positions of all chains on request (``mass_windows``, ``run(moments=True)``,
-    ``mass_from_moments``): ``self.mass`` is rewritten in place on the device."""
+    ``mass_from_moments``): ``self.mass`` is rewritten in place on the device.
+
+    A 2-D ``mass[ndim][ndim]`` (symmetric positive definite, ``ndim`` <= 128) or ``adapt(adapt_mass="dense")`` puts the
+    object in dense mode: with C = chol(M^-1) the chains carry the whitened momentum w = C^T p -- the draw is w ~ N(0, I), the
+    kinetic energy |w|^2 / 2, the kick w += eps C^T g and the drift q += eps C w -- so ``self.mass`` is an array of ones,
+    ``self.chol`` the device pair {C, C^T} ``[2][ndim][ld]``, and every route (``step``, ``run``, ``find_reasonable_epsilon``,
+    ``run(moments=True)`` with the co-moments in ``self.comom``) enqueues the dense launches (linna_hmc_run_dense)."""
+
+    DENSE_MAX_NDIM = 128                        # LINNA_HMC_DENSE_MAX_NDIM
 
     def __init__(self, log_prob, x0, mass=None, seed=0, fused=True, dist_group=None):
         self.group = dist_group                 # the process group a driver gathers chain blocks over (gather_chain); chains never exchange
@@ -1402,8 +1410,15 @@ class BatchedHMC(object):
         z = lambda *s: torch.zeros(s, dtype=torch.float32, device=self.dev)
         self.x, self.q, self.p = z(self.B, self.ld), z(self.B, self.ld), z(self.B, self.ld)
         self.x[:, :self.ndim].copy_(x0)
+        self._info = 0
+        self.chol, self.comom, self._cnt = None, None, None     # dense mode: {C, C^T}, the co-moments, {unsettled chains, info}
+        chol = None
+        if mass is not None and np.ndim(mass) == 2:
+            chol, mass = self.chol_of_mass(mass, self.ndim), None
         self.mass = torch.ones(self.ndim, dtype=torch.float32, device=self.dev) if mass is None else \
             torch.as_tensor(np.asarray(mass, np.float32), device=self.dev)
+        if chol is not None:
+            self._set_chol(chol)
         self.lnp, self.lnp_new, self.H0 = z(self.B), z(self.B), z(self.B)
         self.g, self.g_new = z(self.B, self.ld), z(self.B, self.ld)
         self.naccept = torch.zeros(self.B, dtype=torch.int32, device=self.dev)
@@ -1430,6 +1445,41 @@ class BatchedHMC(object):
                                         Gnew=self.g_new.data_ptr(), H0=self.H0.data_ptr())
         return C.byref(self._state)
 
+    @staticmethod
+    def chol_of_mass(mass, ndim):
+        """C = chol(M^-1) in float64 of a dense mass ``M[ndim][ndim]``; ``ValueError`` unless M is symmetric positive definite
+        and ``ndim`` within the dense kernels' limit."""
+        M = np.asarray(mass, np.float64)
+        if M.shape != (ndim, ndim):
+            raise ValueError("a dense mass is m[ndim][ndim] = [%d][%d], not %r" % (ndim, ndim, M.shape))
+        if ndim > BatchedHMC.DENSE_MAX_NDIM:
+            raise ValueError("a dense mass holds at most %d parameters, not %d" % (BatchedHMC.DENSE_MAX_NDIM, ndim))
+        if not np.isfinite(M).all() or not np.allclose(M, M.T, rtol=1e-10, atol=0.0):
+            raise ValueError("a dense mass must be a finite symmetric matrix")
+        try:
+            np.linalg.cholesky(M)
+            return np.linalg.cholesky(np.linalg.inv(M))
+        except np.linalg.LinAlgError:
+            raise ValueError("a dense mass must be positive definite")
+
+    def _set_chol(self, Cl):
+        """Dense mode with the lower-triangular factor ``Cl`` of the inverse mass: {C, C^T} to the device (in place once
+        allocated), ones into ``self.mass`` in place -- the pointers the kernels hold stay the same."""
+        if self.ndim > self.DENSE_MAX_NDIM:
+            raise ValueError("a dense mass holds at most %d parameters, not %d" % (self.DENSE_MAX_NDIM, self.ndim))
+        Cl = np.tril(np.asarray(Cl, np.float64)).astype(np.float32)
+        pair = np.zeros((2, self.ndim, self.ld), np.float32)
+        pair[0, :, :self.ndim], pair[1, :, :self.ndim] = Cl, Cl.T
+        if self.chol is None:
+            self.chol = torch.zeros((2, self.ndim, self.ld), dtype=torch.float32, device=self.dev)
+        self.chol.copy_(torch.as_tensor(pair))
+        self.mass.fill_(1.0)
+
+    def cov(self):
+        """C C^T of dense mode in float64 (the inverse of the mass the chains run under)."""
+        Cl = self.chol[0, :, :self.ndim].cpu().numpy().astype(np.float64)
+        return Cl @ Cl.T
+
     def find_reasonable_epsilon(self, max_rounds=40):
         """A first step size per chain (``self.eps``): the reference's ``find_reasonable_epsilon`` (sampler.py:151-184) for all
         chains at once -- ``max_rounds`` one-step trials of every chain enqueued in one C call, nothing read back between them
@@ -1437,13 +1487,17 @@ class BatchedHMC(object):
         chains that were still searching after the last round (they keep the step size reached; a warning says so)."""
         r0 = torch.empty((self.B, self.ld), dtype=torch.float32, device=self.dev)
         state = torch.empty(self.B, dtype=torch.int32, device=self.dev)
-        left = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        if self._cnt is None:                   # {chains left searching, info of the last factorisation}: one read for both
+            self._cnt = torch.zeros(2, dtype=torch.int32, device=self.dev)
+        left = self._cnt
         h, ws = self.lp._ensure()["handle"], _lib.ptr(self.lp._workspace(self.B, True))
-        _lib.call("linna_hmc_find_epsilon", h, self._hmc_state(), ws, _lib.ptr(r0), _lib.ptr(self.eps), _lib.iptr(state),
-                  _lib.iptr(left), self.iteration - self._dev_steps, int(max_rounds), _lib.stream())
+        dense = () if self.chol is None else (_lib.ptr(self.chol), self.ld)
+        _lib.call("linna_hmc_find_epsilon_dense" if dense else "linna_hmc_find_epsilon", h, self._hmc_state(), ws, *dense,
+                  _lib.ptr(r0), _lib.ptr(self.eps), _lib.iptr(state), _lib.iptr(left), self.iteration - self._dev_steps,
+                  int(max_rounds), _lib.stream())
         torch.log(10.0 * self.eps, out=self.mu)
         self.epsbar.fill_(1.0); self.Hbar.zero_(); self.m.fill_(1)
-        n = int(left.item())
+        n, self._info = (int(v) for v in left.tolist())
         if n:
             import warnings
             warnings.warn("find_reasonable_epsilon: %d of %d chains had not settled after %d rounds; they keep the step size "
@@ -1464,9 +1518,15 @@ class BatchedHMC(object):
         lps = torch.empty((ntrans, self.B), dtype=torch.float32, device=self.dev) if store else None
         if ntrans > 0:
             h, ws = self.lp._ensure()["handle"], _lib.ptr(self.lp._workspace(self.B, True))
-            args = (h, self._hmc_state(), ws, _lib.ptr(self.eps), _lib.ptr(self.epsbar), _lib.ptr(self.Hbar),
+            args = (_lib.ptr(self.eps), _lib.ptr(self.epsbar), _lib.ptr(self.Hbar),
                     _lib.ptr(self.mu), _lib.iptr(self.m), int(Madapt), float(target_accept), self.iteration - self._dev_steps,
                     num_steps, int(ntrans), _lib.iptr(self.naccept), _lib.ptr(self.alpha), _lib.ptr(chain), _lib.ptr(lps))
+            if self.chol is not None:
+                _lib.call("linna_hmc_run_dense", h, self._hmc_state(), ws, _lib.ptr(self.chol), self.ld, *args,
+                          _lib.ptr(self._comoments(), torch.float64) if moments else None, _lib.stream())
+                self.iteration += ntrans
+                return chain, lps
+            args = (h, self._hmc_state(), ws) + args
             if moments:
                 _lib.call("linna_hmc_run_moments", *args, _lib.ptr(self._moments(), torch.float64), _lib.stream())
             else:
@@ -1478,6 +1538,18 @@ class BatchedHMC(object):
         if self.mom is None:
             self.mom = torch.zeros(1 + 2 * self.ndim, dtype=torch.float64, device=self.dev)
         return self.mom
+
+    def _comoments(self):
+        """``self.comom`` = {n, c[ndim], 8 x {S1[ndim], S2[ndim][ndim]}} (device float64, include/linna_hip.h)."""
+        if self.comom is None:
+            self.comom = torch.zeros(int(_lib.load().linna_hmc_comoments_doubles(self.ndim)), dtype=torch.float64, device=self.dev)
+        return self.comom
+
+    def chol_from_comoments(self, reset=True):
+        """``self.chol`` <- the Cholesky factor of the pooled covariance in ``self.comom`` with Stan's shrinkage, on the device
+        (linna_hmc_chol_from_comoments); its info word lands in ``self._cnt[1]``, which ``find_reasonable_epsilon`` reads."""
+        _lib.call("linna_hmc_chol_from_comoments", self.ctx, self.ndim, _lib.ptr(self._comoments(), torch.float64),
+                  _lib.ptr(self.chol), self.ld, C.c_void_p(self._cnt.data_ptr() + 4), int(bool(reset)), _lib.stream())
 
     @staticmethod
     def mass_windows(Madapt, init_buffer=75, term_buffer=50, base_window=25):
@@ -1513,8 +1585,19 @@ class BatchedHMC(object):
         ``mass_windows(Madapt)`` the positions of all chains are accumulated on the device; at its end
         mass[d] <- 1 / var[d], the step-size search runs again under the new mass and the dual averaging starts over, so that
         only the last segment freezes.  Without windows (or ``adapt_mass=False``): the plain sequence.  Nothing is read back
-        inside a segment; ``self.naccept`` counts the warm-up's transitions too."""
+        inside a segment; ``self.naccept`` counts the warm-up's transitions too.
+
+        ``adapt_mass="dense"`` (``True`` and ``"diag"`` are the scheme above): the same windows and segments for a dense mass.
+        The object enters dense mode from its diagonal mass (C = diag(1 / sqrt(m))); the windows accumulate co-moments about
+        the first chain's position; at a window's end ``self.chol`` <- the Cholesky factor of the pooled covariance
+        (``chol_from_comoments``).  A covariance that cannot be factored keeps the factor before it, with a warning."""
         Madapt = int(Madapt)
+        adapt_mass = self.adapt_mass_mode(adapt_mass)
+        dense = adapt_mass == "dense"
+        if dense and self.chol is None:
+            self._set_chol(np.diag(1.0 / np.sqrt(self.mass.cpu().numpy().astype(np.float64))))
+        elif adapt_mass and not dense and self.chol is not None:
+            raise ValueError("adapt_mass = %r: this object runs under a dense mass (adapt_mass=\"dense\")" % (adapt_mass,))
         self.find_reasonable_epsilon()
         windows = self.mass_windows(Madapt) if adapt_mass else []
         if not windows:
@@ -1523,14 +1606,35 @@ class BatchedHMC(object):
             return windows
         never = 2 ** 30                                   # (dual averaging that does not freeze inside the segment)
         self.run(windows[0][0], store=False, Madapt=never, target_accept=target_accept)
-        self._moments().zero_()
+        if dense:
+            self._comoments().zero_()
+            self.comom[1:1 + self.ndim].copy_(self.x[0, :self.ndim])      # the shift c: a point of the cloud
+        else:
+            self._moments().zero_()
         for start, end in windows:
             self.run(end - start, store=False, Madapt=never, target_accept=target_accept, moments=True)
-            self.mass_from_moments(reset=True)
+            if dense:
+                self.chol_from_comoments(reset=True)
+            else:
+                self.mass_from_moments(reset=True)
             self.find_reasonable_epsilon()                # (under the new mass; mu, epsbar, Hbar, m start over)
+            if dense and self._info:
+                import warnings
+                warnings.warn("adapt: the pooled covariance of window (%d, %d) could not be factored (info %d); the factor "
+                              "before it stays" % (start, end, self._info))
         left = Madapt - windows[-1][1]
         self.run(left + 1, store=False, Madapt=left, target_accept=target_accept)
         return windows
+
+    @staticmethod
+    def adapt_mass_mode(adapt_mass):
+        """``adapt_mass`` as one of False, "diag", "dense" (True is "diag"); anything else is a ``ValueError``."""
+        if isinstance(adapt_mass, str):
+            if adapt_mass in ("diag", "dense"):
+                return adapt_mass
+        elif isinstance(adapt_mass, (bool, np.bool_)) or adapt_mass is None:
+            return "diag" if adapt_mass else False
+        raise ValueError("adapt_mass = %r: False, True / \"diag\" or \"dense\"" % (adapt_mass,))
 
     def step(self, num_steps, step_size, p0=None, u=None):
         """One HMC transition per chain.  ``p0[B, ndim]`` (standard-normal draws) and ``u[B]`` replace
@@ -1543,6 +1647,21 @@ class BatchedHMC(object):
             self._dev_steps = self.iteration
         p0d = None if p0 is None else torch.as_tensor(np.ascontiguousarray(p0, np.float32), device=self.dev)
         ud = None if u is None else torch.as_tensor(np.ascontiguousarray(u, np.float32), device=self.dev)
+        if self.chol is not None:
+            # dense mode, launch by launch what linna_hmc_run_dense enqueues: draw + H0 on the unit mass; half kick and drift
+            # from x; per step the gradient and the dense kick and drift behind it (a half kick, no drift behind the last)
+            dn = (self.ctx, self.B, self.ndim, _lib.ptr(self.chol), self.ld, None)
+            _lib.call("linna_hmc_init", *args, seed, _lib.iptr(self.step_dev), _lib.ptr(self.lnp),
+                      _lib.ptr(p0d) if p0d is not None else None, self.ndim, _lib.ptr(self.p), self.ld, _lib.ptr(self.H0), st)
+            _lib.call("linna_hmc_kick_drift_dense", *dn, 0.5 * eps, eps, _lib.ptr(self.g), self.ld, _lib.ptr(self.p), self.ld,
+                      _lib.ptr(self.x), self.ld, _lib.ptr(self.q), self.ld, st)
+            for i in range(num_steps):
+                last = i == num_steps - 1
+                self.lp.evaluate_with_grad(self.q, out=self.lnp_new, grad=self.g_new)
+                _lib.call("linna_hmc_kick_drift_dense", *dn, 0.5 * eps if last else eps, 0.0 if last else eps,
+                          _lib.ptr(self.g_new), self.ld, _lib.ptr(self.p), self.ld, None, 0, _lib.ptr(self.q), self.ld, st)
+            self._accept(args, seed, ud, st)
+            return
         if self.fused and num_steps >= 1:
             # 3 + num_steps launches: momentum draw + first half kick + first drift; per leapfrog step the gradient with the
             # next kick (a half one behind the last step, :51) and drift in its finish; Metropolis test; counter
@@ -1765,7 +1884,13 @@ class HMCSampler(object):
     ``num_steps``, ``Madapt`` -- to ``chhmc_adapt.npz`` next to ``chhmc.h5``: a resumed run with ``adapt_mass=True`` whose
     file matches ``ndim`` / ``nwalkers`` loads it and skips the search and the adaptation; ``overwrite=True`` removes it.
     Multi-rank runs adapt per rank from their own chains and neither write nor read that file.  ``self.mass`` is the mass
-    the chains of the last hmc run ended up with."""
+    the chains of the last hmc run ended up with.
+
+    ``adapt_mass="dense"`` adapts a dense mass instead (``ndim`` <= 128), and ``m`` may be a symmetric positive definite
+    ``m[ndim][ndim]`` (the starting mass, or with a fixed ``samp_eps`` the mass of the run).  After such a run ``self.cov`` is
+    C C^T (float64), the inverse of the mass, and ``self.mass`` = 1 / diag(cov); the file then also holds
+    ``metric="dense"`` and ``chol[ndim][ndim]``, and is handed only to a run of the same metric (files without ``metric``
+    are diagonal)."""
 
     ADAPT_FILE = "chhmc_adapt.npz"
 
@@ -1775,7 +1900,7 @@ class HMCSampler(object):
         self.exchange = exchange                             # how a multi-rank run splits the ensemble (_Ranks); None: automatic
         self.transform, self.x0, self.nparams, self.nwalkers = transform, x0, ndim, nwalkers
         self.m = np.ones(ndim) if m is None else m
-        self.mass = None
+        self.mass, self.cov = None, None
         self.sampler = None
         self.seed, self.group = seed, dist_group
 
@@ -1786,6 +1911,7 @@ class HMCSampler(object):
             # sampler.py's "nuts" branch is unreachable in the reference and not built here
             raise NotImplementedError(method)
         hmc = method == "hmc"
+        adapt_mass = BatchedHMC.adapt_mass_mode(adapt_mass)
         if hmc and not getattr(self.lnp, "device_only", True):
             raise NotImplementedError("HMC needs the gradient of the log-probability: a user loglikelihoodfunc / "
                                       "externalloglike is host code without one")
@@ -1898,9 +2024,15 @@ class HMCSampler(object):
         the chain file was continued and the file holds ``ndim`` masses and one step size per walker."""
         if samp_eps is not None and samp_eps < 0:
             raise ValueError("samp_eps = %r: a step size is positive (0 or None: found and adapted per chain)" % (samp_eps,))
+        adapt_mass = BatchedHMC.adapt_mass_mode(adapt_mass)
         m = np.asarray(self.m, np.float64)
-        if m.ndim != 1 or len(m) != self.nparams:
-            raise ValueError("HMC needs a diagonal mass: m[ndim]")
+        if m.shape not in ((self.nparams,), (self.nparams, self.nparams)):
+            raise ValueError("HMC needs a mass m[ndim] (diagonal) or m[ndim][ndim] (dense)")
+        if m.ndim == 2:
+            BatchedHMC.chol_of_mass(m, self.nparams)           # (ValueError before anything is built)
+            if adapt_mass == "diag":
+                raise ValueError("adapt_mass = True with a dense m[ndim][ndim]: adapt_mass=\"dense\"")
+        self.cov = None
         lib_seed = self.seed + 0x9E3779B97F4A7C15 * rk.rank & 0xFFFFFFFFFFFFFFFF       # (every rank its own momenta)
         ens = BatchedHMC(self.lnp, rk.mine(x0), mass=m, seed=lib_seed, dist_group=self.group)
         if not bool(torch.isfinite(ens.lnp).all()):
@@ -1910,38 +2042,65 @@ class HMCSampler(object):
             if adapt_mass:
                 raise ValueError("adapt_mass with a fixed samp_eps = %r" % (samp_eps,))
             ens.eps.fill_(float(samp_eps))
-            self.mass = m.copy()
+            self._keep_mass(ens, m)
+            if ens.chol is None:
+                self.mass = m.copy()
             return ens
-        kept = self._load_adaptation(sidecar, ens) if resume and sidecar else None
+        metric = "dense" if adapt_mass == "dense" or ens.chol is not None else "diag"
+        kept = self._load_adaptation(sidecar, ens, metric) if resume and sidecar else None
         if kept is not None:
-            ens.mass.copy_(torch.as_tensor(kept["mass"], device=ens.dev))
+            if metric == "dense":
+                ens._set_chol(kept["chol"])
+            else:
+                ens.mass.copy_(torch.as_tensor(kept["mass"], device=ens.dev))
             ens.eps.copy_(torch.as_tensor(kept["eps"], device=ens.dev))
             ens.epsbar.copy_(ens.eps)
             print("hmc step sizes and mass from %s" % sidecar, flush=True)
         else:
             with prof.host("adapt"), _lib.stage("run_mcmc.hmc_adapt"):
-                ens.adapt(int(Madapt), adapt_mass=bool(adapt_mass))
+                ens.adapt(int(Madapt), adapt_mass=adapt_mass)
                 ens.naccept.zero_()
-        e, mm = ens.eps.cpu().numpy(), ens.mass.cpu().numpy()
-        self.mass = mm.astype(np.float64)
+        e = ens.eps.cpu().numpy()
+        self._keep_mass(ens, m)
+        mm = self.mass.astype(np.float32)
+        extra = {}
+        if ens.chol is not None:
+            extra = dict(metric="dense", chol=ens.chol[0, :, :ens.ndim].cpu().numpy())
         if sidecar and kept is None:
-            np.savez(sidecar, mass=mm, eps=e, num_steps=np.int64(ens.num_steps), Madapt=np.int64(Madapt))
-        print("hmc step sizes %s: min %.3g median %.3g max %.3g; mass min %.3g median %.3g max %.3g"
+            np.savez(sidecar, mass=mm, eps=e, num_steps=np.int64(ens.num_steps), Madapt=np.int64(Madapt), **extra)
+        print("hmc step sizes %s: min %.3g median %.3g max %.3g; mass min %.3g median %.3g max %.3g%s"
               % ("after %d adaptive transitions" % Madapt if kept is None else "kept", e.min(), np.median(e), e.max(),
-                 mm.min(), np.median(mm), mm.max()), flush=True)
+                 mm.min(), np.median(mm), mm.max(),
+                 "" if self.cov is None else "; dense, condition number of C C^T %.3g" % np.linalg.cond(self.cov)), flush=True)
         return ens
 
+    def _keep_mass(self, ens, m):
+        """``self.mass`` / ``self.cov`` of the chains as they run now (dense mode: C C^T and 1 / its diagonal)."""
+        if ens.chol is not None:
+            self.cov = ens.cov()
+            self.mass = 1.0 / np.diag(self.cov)
+        else:
+            self.mass = ens.mass.cpu().numpy().astype(np.float64)
+
     @staticmethod
-    def _load_adaptation(name, ens):
-        """{mass, eps} of ``chhmc_adapt.npz`` if it is there and fits these chains, else None."""
+    def _load_adaptation(name, ens, metric="diag"):
+        """{mass, eps} (``metric`` "dense": and chol) of ``chhmc_adapt.npz`` if it is there, holds that metric (a file
+        without the word is diagonal) and fits these chains, else None."""
         if not os.path.exists(name):
             return None
         with np.load(name) as f:
             if not {"mass", "eps"} <= set(f.files):
                 return None
+            if (str(f["metric"]) if "metric" in f.files else "diag") != metric:
+                return None
             mass, eps = np.asarray(f["mass"], np.float32), np.asarray(f["eps"], np.float32)
+            chol = np.asarray(f["chol"], np.float32) if metric == "dense" and "chol" in f.files else None
         ok = mass.shape == (ens.ndim,) and eps.shape == (ens.B,) and np.isfinite(mass).all() and (mass > 0).all() \
             and np.isfinite(eps).all() and (eps > 0).all()
+        if metric == "dense":
+            ok = ok and chol is not None and chol.shape == (ens.ndim, ens.ndim) and bool(np.isfinite(chol).all()) \
+                and bool((np.diag(chol) > 0).all())
+            return dict(mass=mass, eps=eps, chol=chol) if ok else None
         return dict(mass=mass, eps=eps) if ok else None
 
 

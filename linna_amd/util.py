@@ -899,8 +899,8 @@ class NN_samplerv1(object):
         """util.py:940-945 with the argument order its signature states (its caller passes ``transform`` twice, SURVEY §8
         a18).  ``samp_eps=None``: a step size per chain, found and adapted on the device (``sampler.HMCSampler.sample``) --
         the reference's 0.1 is in latent units and accepts nothing on a posterior much narrower than its prior.  The
-        Hessian mass matrix of :944 is not built: unit mass, or with ``adapt_mass`` a diagonal one adapted from the chains
-        during the warm-up (``sampler.BatchedHMC.adapt``)."""
+        Hessian mass matrix of :944 is not built: unit mass, or with ``adapt_mass`` a diagonal one (``True``) or a dense one
+        (``"dense"``) adapted from the chains during the warm-up (``sampler.BatchedHMC.adapt``)."""
         from . import sampler
         x0 = init + 0.1 * np.random.randn(nwalkers, ndim)                 # util.py:942
         samp = sampler.HMCSampler(log_prob, dlnp, ddlnp, ndim, nwalkers, x0=x0, m=None, transform=transform)
@@ -1138,7 +1138,7 @@ def run_mcmc(nnsampler, outdir, method, ndim, nwalkers, init, log_prob, dlnp=Non
     """util.py:1474-1504.  "hmc": per-walker HMC with step sizes adapted on the device (``_HMC_sample``; the reference's own
     branch cannot run); "nuts" is not built.  ``max_n`` (not in the reference): a cap on the iterations of
     the hmc run, 1000000 as there when None.  ``adapt_mass`` (hmc only, not in the reference): also adapt a diagonal mass
-    from the chains during the warm-up."""
+    (``True``) or a dense one (``"dense"``) from the chains during the warm-up."""
     kw = dict(ntimes=ntimes, tautol=tautol, transform=transform, dlnp=dlnp, ddlnp=ddlnp, meanshift=meanshift,
               stdshift=stdshift, nk=nk)
     if method == "hmc":
