@@ -340,6 +340,20 @@ int linna_engine_rows(int rows);
  * the balanced assignment: wave w takes the 64-column blocks w and 15 - w, each from its first non-zero row.  Same sums in
  * the same order in every mode (the skipped products are zeros).  -1 queries.  Returns the previous mode (tests, A/B). */
 int linna_dense_tri(int mode);
+/* The lean ("plain") instantiation of the whole-network serving kernel.  A linna_logprob_eval launch takes it when its
+ * program is plain -- fp32 on the 16-row engine, every segment WIDE or SPLIT: no SIDE segment, no input skip, no dense
+ * segment (a ReLU MLP: linna_program_plain) -- and the launch has a diagonal likelihood with cscale and cshift, no exp
+ * (ypositive) map, no THETA output and no gate.  The same kernel body with everything such a launch never uses compiled
+ * out; lnP is bit-identical to the generic instantiation's.  linna_serve_plain: 1 (default) eligible launches take it, 0
+ * every launch runs the generic instantiation, -1 queries; returns the previous value (tests, interleaved A/B).
+ * Process-wide: the launch path reads one atomic. */
+int linna_serve_plain(int on);
+/* 1 when the serving program of this op list on the engine of `rows` rows per workgroup is plain (dense_nout != 0: with a
+ * dense inverse covariance, never), else 0.  Host-side planning only, like linna_program_describe. */
+int linna_program_plain(const linna_layer_t* layers, int nlayers, int in_size, int rows, int dense_nout);
+/* *out = 1 when linna_logprob_eval(lp, ..., B rows, THETA = null) would launch the plain instantiation under the current
+ * linna_serve_plain and linna_engine_rows settings, else 0. */
+int linna_logprob_serve_plain(linna_logprob_t* lp, int B, int* out);
 /* Which launches of linna_slice_half_step are folded into their neighbours, as a mask (default: all that apply): bit 0 -- with ONE
  * stepping-out round, its logic kernel is not launched: the first shrinking round's evaluation derives its trial points from
  * the bracket ends' lnP in its prologue and that round's logic kernel does the bookkeeping of both; bit 1 -- the set-up of the

@@ -136,6 +136,9 @@ _SIGNATURES = {
     "linna_logprob_grad_precision": (_I, [_V, _V]),
     "linna_engine_rows": (_I, [_I]),
     "linna_dense_tri": (_I, [_I]),
+    "linna_serve_plain": (_I, [_I]),
+    "linna_program_plain": (_I, [_V, _I, _I, _I, _I]),
+    "linna_logprob_serve_plain": (_I, [_V, _I, _V]),
     "linna_slice_fusion": (_I, [_I]),
     "linna_net_train_launches": (_I, [_V, _I]),
     "linna_net_set_train_precision": (_I, [_V, _I]),
@@ -358,6 +361,15 @@ def slice_fusion(mask=-1):
     """Which launches of linna_slice_half_step are folded into their neighbours (a mask, include/linna_hip.h); -1 queries.
     Returns the previous mask (tests and measurements: the chain is the same under every mask)."""
     prev = load().linna_slice_fusion(int(mask))
+    if prev < 0:
+        check(prev)
+    return prev
+
+
+def serve_plain(on=-1):
+    """The lean ("plain") instantiation of the serving kernel for plain-MLP launches: 1 on (default), 0 off (every launch
+    runs the generic instantiation), -1 queries.  Returns the previous value (tests, interleaved A/B measurements)."""
+    prev = load().linna_serve_plain(int(on))
     if prev < 0:
         check(prev)
     return prev

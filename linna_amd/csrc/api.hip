@@ -1029,6 +1029,17 @@ static int lp_likelihood(const linna_logprob* lp, const LpRun& r, float* w, cons
 
 // lnP (and TH) of the rows `r` in the workspace w laid out as L: one launch, or -- `keep_activations`, or no such program --
 // prior map, the network's forward and the likelihood as launches of their own
+// Whether an fp32 evaluation runs the whole-network kernel (lp_forward and linna_logprob_serve_plain ask the same question)
+static bool lp_serves_fused(const linna_logprob* lp, bool keep_activations) {
+    const linna_logprob_desc_t& d = lp->d;
+    return !keep_activations && lp->fused_on && lp->packed.ready() && (!d.outmap.cexp || (d.outmap.cpost && d.outmap.cshift2 && !lp->dense_fused));
+}
+// ... and what it launches with when the covariance is not dense-fused: lnP from the launch for a diagonal likelihood, else
+// the residuals into the workspace for a likelihood launch of its own
+static LpRun lp_fused_run(const linna_logprob* lp, const LpRun& r, float* w, const LpLayout& L) {
+    const linna_logprob_desc_t& d = lp->d;
+    return LpRun{r.Z, r.ldz, r.B, d.w ? r.lnP : nullptr, r.gate, r.TH, r.ldt, d.w ? nullptr : w + L.d, ld4(d.nout)};
+}
 static int lp_forward(linna_logprob* lp, const LpRun& r, float* w, const LpLayout& L, void* stream, bool keep_activations) {
     const linna_logprob_desc_t& d = lp->d;
     const int ldx = ld4(d.nin), ldd = ld4(d.nout), B = r.B;
@@ -1042,7 +1053,7 @@ static int lp_forward(linna_logprob* lp, const LpRun& r, float* w, const LpLayou
         TRY(lp_refresh_stream(lp, B, stream, &packed, &rows));
         return lp_launch(lp, packed, rows, r, nullptr, nullptr, stream);
     }
-    if (!keep_activations && lp->fused_on && lp->packed.ready() && (!d.outmap.cexp || (d.outmap.cpost && d.outmap.cshift2 && !lp->dense_fused))) {
+    if (lp_serves_fused(lp, keep_activations)) {
         // whole-network kernel (net_stream.hip): prior map -> every layer -> output transform -> diagonal
         // log-likelihood in ONE launch, weights streamed from the fragment-order copy
         const float* packed = nullptr; int rows = 16;
@@ -1050,7 +1061,7 @@ static int lp_forward(linna_logprob* lp, const LpRun& r, float* w, const LpLayou
         // dense covariance: the output map is folded into the stream's last layer and the inverse covariance is its last
         // segment -- lnP comes out of the same launch
         if (lp->dense_fused) return lp_launch(lp, packed, rows, r, nullptr, nullptr, stream);
-        TRY(lp_launch(lp, packed, rows, LpRun{r.Z, r.ldz, B, d.w ? r.lnP : nullptr, r.gate, r.TH, r.ldt, d.w ? nullptr : w + L.d, ldd}, nullptr, nullptr, stream));
+        TRY(lp_launch(lp, packed, rows, lp_fused_run(lp, r, w, L), nullptr, nullptr, stream));
         return d.w ? LINNA_OK : lp_likelihood(lp, r, w, L, stream);
     }
     TRY(launch_prior_map_fwd(r.Z, r.ldz, B, d.nin, d.is_flat, d.a1, d.a2, d.log10_flag, d.xmean, d.xstd, w + L.x0, ldx, r.TH, r.ldt, S(stream)));
@@ -1175,6 +1186,27 @@ int linna_program_describe(const linna_layer_t* layers, int nlayers, int in_size
     NsDense dn{&dummy, (dn_cols + 3) & ~3, nullptr, nullptr, dense_nout < -1 ? 1 : 0, net_stream_dense_tri(-1)};
     if (dn_cols > 0) return net_stream_describe(NS_SERVE_DENSE, layers, nlayers, in_size, &dn, rows, buf, n);
     return net_stream_describe(NS_SERVE, layers, nlayers, in_size, nullptr, rows, buf, n);
+} LINNA_CATCH_INT
+int linna_serve_plain(int on) try {
+    if (on < -1 || on > 1) { set_error("linna_serve_plain: %d (-1 query, 0 or 1)", on); return LINNA_ERR_INVALID; }
+    return net_stream_serve_plain(on);
+} LINNA_CATCH_INT
+int linna_program_plain(const linna_layer_t* layers, int nlayers, int in_size, int rows, int dense_nout) try {
+    if (!layers || nlayers < 1) { set_error("program_plain: bad arguments"); return LINNA_ERR_INVALID; }
+    TRY(check_layers(layers, nlayers, "program_plain"));
+    if (dense_nout != 0) return 0;                                          // a dense segment: never plain
+    return net_stream_program_plain(NS_SERVE, layers, nlayers, in_size, nullptr, rows) ? 1 : 0;
+} LINNA_CATCH_INT
+int linna_logprob_serve_plain(linna_logprob_t* lp, int B, int* out) try {
+    if (!lp || !out || B < 1) { set_error("logprob_serve_plain: bad arguments"); return LINNA_ERR_INVALID; }
+    // linna_logprob_eval's own route (lp_forward) with the arguments it would launch with, put to the launcher's own decision
+    static float dummy[4];                                  // (stands for the caller's lnP and workspace: only tested for null)
+    const LpRun r = lp_fused_run(lp, LpRun{dummy, 0, B, dummy}, dummy, LpLayout{});
+    const NsDense dn = lp->dense();
+    *out = !lp->bf16() && lp_serves_fused(lp, false) && !lp->dense_fused &&
+           net_stream_takes_plain(lp->kind(), net_layers(lp->net, lp->kind()), lp_output(lp), r.lnP, r.D, r.TH, nullptr, nullptr, r.gate,
+                                  net_stream_rows(B), lp->kind() == NS_SERVE_DENSE ? &dn : nullptr);
+    return LINNA_OK;
 } LINNA_CATCH_INT
 int linna_dense_tri(int mode) try {
     if (mode < -1 || mode > 2) { set_error("linna_dense_tri: %d (-1 query, 0, 1 or 2)", mode); return LINNA_ERR_INVALID; }

@@ -380,6 +380,14 @@ int net_stream_force_rows(int rows);   // 0 automatic, 4 / 8 / 16 forced; return
 int launch_net_stream_pack(NsKind kind, const linna_layer_t* layers, int nl, int in_size, float* packed, int rows, const NsDense* dn,
                            hipStream_t s);
 int net_stream_describe(NsKind kind, const linna_layer_t* layers, int nl, int in_size, const NsDense* dn, int rows, char* buf, size_t n);
+// The PLAIN instantiation of the serving kernel (net_stream_plain_kernel).  net_stream_serve_plain: the process-wide switch
+// (1 default: eligible launches take it; 0: every launch the generic instantiation; -1 queries; returns the previous value).
+// net_stream_program_plain: whether the serving program of this op list on the engine of `rows` rows is a plain one
+// (ns_program_plain, net_program.hip: host-side planning only).  net_stream_launch_plain_ok: whether a launch of that program
+// with this output map and these outputs takes it when the switch is on.
+int net_stream_serve_plain(int on);
+bool net_stream_program_plain(NsKind kind, const linna_layer_t* layers, int nl, int in_size, const NsDense* dn, int rows);
+bool net_stream_launch_plain_ok(bool cscale, bool cshift, bool w, bool cexp, bool lnP, bool D, bool TH, bool gate);
 // What always travels together into the launchers of the whole-network kernel: plain records, copied field by field into
 // NsArgs.  NsNet: the op list a program is planned from (with or without the trailing input skip: ns_kind_full_layers) and
 // the network's input width.  NsInput: the prior map and the input transform.  NsOutput: the output map and the diagonal
@@ -478,6 +486,8 @@ int launch_adamw_streams(const AsArgs& a, float* p, const float* g, float* m, fl
 int launch_net_stream_grad2(const NsNet& net, const float* packed, const float* Z, int ldz, int B, const NsInput& in, const NsOutput& out,
                             float* lnP, const NsGrad& gr, int rows, hipStream_t s, bool bf = false);
 // a serving launch (kind NS_SERVE, NS_SERVE_DENSE with dn, or NS_SERVE_BF16)
+bool net_stream_takes_plain(NsKind kind, const NsNet& net, const NsOutput& out, const float* lnP, const float* D, const float* TH,
+                            const NsMove* mv, const NsGrad* gr, const int* gate, int rows, const NsDense* dn);   // what launch_net_stream decides
 int launch_net_stream(NsKind kind, const NsNet& net, const float* packed, const float* Z, int ldz, int B, const NsInput& in,
                       const NsOutput& out, float* lnP, float* D, int ldd, float* TH, int ldt, const NsMove* mv, const NsGrad* gr,
                       const int* gate, int rows, const NsDense* dn, hipStream_t s);

@@ -80,6 +80,10 @@ int ns_forced_rows_resolved();   // linna_engine_rows / LINNA_NS_ROWS: 0 automat
 typedef std::shared_ptr<const NsProgram> NsProgramRef;
 NsProgramRef ns_program(NsKind kind, const linna_layer_t* layers, int nl, int in_size, const NsDense* dn, int rows);
 
+// A serving program is PLAIN when the lean instantiation of the kernel (net_stream_plain_kernel) can run its forward half:
+// fp32, every forward segment WIDE or SPLIT with no short or balanced second pass, no SIDE block, no kept input rows (input
+// skip), no dense segment.  The launch adds its own conditions (net_stream_launch_plain_ok).
+bool ns_program_plain(const NsProgram& p);
 // columns of what segment i of a one-launch forward + backward program (NS_GRAD_INPUT, NS_TRAIN_STEP) writes: the hidden h
 // of a residual block, a forward op's output, or (the backward half) d/d(op input)
 int ns_seg_cols(const NsProgram& p, const linna_layer_t* layers, int i);

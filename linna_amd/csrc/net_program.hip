@@ -470,6 +470,26 @@ NsProgramRef ns_program(NsKind kind, const linna_layer_t* layers, int nl, int in
     return p;
 }
 
+bool ns_program_plain(const NsProgram& p) {
+    if (!p.ok || p.bf || p.dense || p.x0_keep || p.side_f4 || p.nseg_f < 1) return false;
+    for (int i = 0; i < p.nseg_f; ++i) {
+        const NsSeg& g = p.seg[i];
+        if (g.type != NS_WIDE && g.type != NS_SPLIT) return false;
+        if (g.x0_col || (g.type == NS_WIDE && (g.zext || g.kslice))) return false;
+    }
+    return true;
+}
+bool net_stream_program_plain(NsKind kind, const linna_layer_t* layers, int nl, int in_size, const NsDense* dn, int rows) {
+    return kind == NS_SERVE && rows == 16 && ns_program_plain(*ns_program(kind, layers, nl, in_size, dn, rows));
+}
+// A plain launch has the diagonal likelihood with both halves of the linear output map (nothing optional left to select in
+// the kernel), no exp map, lnP as its only output and no gate.
+bool net_stream_launch_plain_ok(bool cscale, bool cshift, bool w, bool cexp, bool lnP, bool D, bool TH, bool gate) {
+    return cscale && cshift && w && !cexp && lnP && !D && !TH && !gate;
+}
+static std::atomic<int> g_serve_plain{1};
+int net_stream_serve_plain(int on) { return on < 0 ? g_serve_plain.load() : g_serve_plain.exchange(on ? 1 : 0); }
+
 int ns_seg_cols(const NsProgram& p, const linna_layer_t* layers, int i) {
     const linna_layer_t& l = layers[p.seg_op[i]];
     return p.seg_hidden[i] ? l.C : i < p.nseg_f ? l.N : l.K;

@@ -316,7 +316,7 @@ __device__ __forceinline__ float ns_prior_theta(float z, int flat, float a1, flo
 // instructions for every existing instantiation.)
 template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF = false>
 __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_kernel(NsArgs a) {
-    constexpr bool EPS = false;
+    constexpr bool EPS = false, PLAIN = false;
 #include "net_stream_body.inc"
 }
 // EPS: the fp32 gradient programs (GRAD, STORE 0 or 2) whose finish runs the leapfrog with a step size per row, a.hm_eps
@@ -326,13 +326,25 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_kernel(NsArgs a) {
 template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF>
 __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_eps_kernel(NsArgs a) {
     static_assert(!BF && GRAD && (STORE == 0 || STORE == 2) && MOVE == 0, "the fp32 one-launch gradients only");
-    constexpr bool EPS = true;
+    constexpr bool EPS = true, PLAIN = false;
+#include "net_stream_body.inc"
+}
+// PLAIN: the serving launch of a plain MLP (ns_program_plain, net_program.hip: WIDE and SPLIT segments only, diagonal
+// likelihood with its whole output map, lnP the only output, no gate) on the 16-row fp32 engine.  The same body with
+// everything such a launch never uses compiled out -- SIDE prefetch and its register zeroing at every run end, the input
+// skip, the dense and exp finishes, the gate test, the selects on optional pointers -- and the next segment's descriptor
+// requested at the START of a run, so that no run end begins with a scalar round trip.  Same MFMAs on the same fragments in
+// the same order: lnP is bit-identical to net_stream_kernel<R, 0, false, 0, 16>'s (linna_serve_plain switches between them).
+template <int R>
+__global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_plain_kernel(NsArgs a) {
+    constexpr int MOVE = 0, STORE = 0, ROWS = 16;
+    constexpr bool GRAD = false, BF = false, EPS = false, PLAIN = true;
 #include "net_stream_body.inc"
 }
 template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF>
 __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_train_bf16_kernel(NsArgs a) {
     static_assert(BF && GRAD && STORE == 3 && ROWS == 4 && MOVE == 0, "the bf16 training step only");
-    constexpr bool EPS = false;
+    constexpr bool EPS = false, PLAIN = false;
 #include "net_stream_body.inc"
 }
 // BF + MOVE == 2: the ensemble slice move's evaluation on the bf16 serving engine (linna_slice_half_step,
@@ -343,7 +355,7 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_train_bf16_kernel(Ns
 template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF>
 __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_slice_bf16_kernel(NsArgs a) {
     static_assert(BF && !GRAD && STORE == 0 && MOVE == 2, "the bf16 slice evaluation only");
-    constexpr bool EPS = false;
+    constexpr bool EPS = false, PLAIN = false;
 #define NS_BODY_SLICE_BF16
 #include "net_stream_body.inc"
 #undef NS_BODY_SLICE_BF16
@@ -358,7 +370,7 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_slice_bf16_kernel(Ns
 template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF>
 __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_grad_bf16_kernel(NsArgs a) {
     static_assert(BF && GRAD && STORE == 2 && MOVE == 0, "the bf16 one-launch gradient only");
-    constexpr bool EPS = false;
+    constexpr bool EPS = false, PLAIN = false;
 #define NS_BODY_GRAD_BF16
 #include "net_stream_body.inc"
 #undef NS_BODY_GRAD_BF16
@@ -366,7 +378,7 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_grad_bf16_kernel(NsA
 template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF>
 __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_eps_bf16_kernel(NsArgs a) {      // ... with a step size per row (EPS)
     static_assert(BF && GRAD && STORE == 2 && MOVE == 0, "the bf16 one-launch gradient only");
-    constexpr bool EPS = true;
+    constexpr bool EPS = true, PLAIN = false;
 #define NS_BODY_GRAD_BF16
 #include "net_stream_body.inc"
 #undef NS_BODY_GRAD_BF16
@@ -437,8 +449,10 @@ static int ns_launch_rows(const NsArgs& a, int B, size_t lds_bytes, hipStream_t 
     if constexpr (EPS) return ns_launch<net_stream_eps_kernel<NS_R, MOVE, GRAD, STORE, ROWS, BF>>(a, (B + ROWS - 1) / ROWS + extra, lds_bytes, s, "net_stream launch");
     else return ns_launch<net_stream_kernel<NS_R, MOVE, GRAD, STORE, ROWS, BF>>(a, (B + ROWS - 1) / ROWS + extra, lds_bytes, s, "net_stream launch");
 }
+// plain: the PLAIN instantiation (net_stream_plain_kernel; the caller has checked ns_program_plain and the launch's own conditions)
 template <int MOVE, bool GRAD, int STORE = 0, bool BF = false, bool EPS = false>
-static int ns_launch_kernel(const NsArgs& a0, int B, const NsProgram& p, int rows, hipStream_t s, int extra = 0, size_t lds_extra = 0) {
+static int ns_launch_kernel(const NsArgs& a0, int B, const NsProgram& p, int rows, hipStream_t s, int extra = 0, size_t lds_extra = 0,
+                            bool plain = false) {
     const size_t lds = p.lds_for(rows, GRAD) + lds_extra;
 #ifdef NS_STAMPS
     // diagnostic build: every launch writes its phase stamps to the buffer LINNA_FUSED_STAMPS names (tools/ns_stamps*.py)
@@ -448,6 +462,9 @@ static int ns_launch_kernel(const NsArgs& a0, int B, const NsProgram& p, int row
 #else
     const NsArgs& a = a0;
 #endif
+    if constexpr (MOVE == 0 && !GRAD && STORE == 0 && !BF && !EPS) {
+        if (plain && rows == 16) return ns_launch<net_stream_plain_kernel<NS_R>>(a, (B + 15) / 16, lds, s, "net_stream plain launch");
+    }
     if (rows == 4) return ns_launch_rows<MOVE, GRAD, STORE, 4, BF, EPS>(a, B, lds, s, extra);
     if constexpr (BF) {
         if (rows == 8) return ns_launch_rows<MOVE, GRAD, STORE, 8, BF, EPS>(a, B, lds, s, extra);
@@ -644,6 +661,15 @@ static void ns_set_grad(NsArgs& a, const NsGrad& gr) {
     a.hm_p = l.P; a.hm_ldp = l.ldp; a.hm_q = l.Q; a.hm_mass = l.mass; a.hm_ek = l.ek; a.hm_ed = l.ed; a.hm_eps = l.eps;
 }
 
+// Whether a serving launch with these arguments takes the plain instantiation: the one decision, made here for the launch
+// below and for whoever asks what it would do (linna_logprob_serve_plain).
+bool net_stream_takes_plain(NsKind kind, const NsNet& net, const NsOutput& out, const float* lnP, const float* D, const float* TH,
+                            const NsMove* mv, const NsGrad* gr, const int* gate, int rows, const NsDense* dn) {
+    if (kind != NS_SERVE || rows != 16 || mv || gr || dn || !net_stream_serve_plain(-1)) return false;
+    if (!net_stream_launch_plain_ok(out.cscale, out.cshift, out.w, out.cpost, lnP, D, TH, gate)) return false;
+    return ns_program_plain(*ns_program(kind, net.layers, net.nl, net.in_size, dn, rows));
+}
+
 int launch_net_stream(NsKind kind, const NsNet& net, const float* packed, const float* Z, int ldz, int B, const NsInput& in,
                       const NsOutput& out, float* lnP, float* D, int ldd, float* TH, int ldt, const NsMove* mv, const NsGrad* gr,
                       const int* gate, int rows, const NsDense* dn, hipStream_t s) {
@@ -689,7 +715,10 @@ int launch_net_stream(NsKind kind, const NsNet& net, const float* packed, const 
         if (a.hm_p && a.hm_eps) return ns_launch_kernel<0, true, 0, false, true>(a, B, p, rows, s);
         return ns_launch_kernel<0, true>(a, B, p, rows, s);
     }
-    return ns_launch_kernel<0, false>(a, B, p, rows, s);
+    // the plain MLP's serving launch: its own lean instantiation (net_stream_plain_kernel), unless linna_serve_plain(0)
+    const bool plain = net_stream_takes_plain(kind, net, out, lnP, D, TH, mv, gr, gate, rows, dn);
+    if (plain) for (int i = 0; i < a.nseg; ++i) a.seg[i].type |= a.seg[i].ncg_log2 << 8;      // (the eight fields it reads: net_stream_body.inc)
+    return ns_launch_kernel<0, false>(a, B, p, rows, s, 0, 0, plain);
 }
 
 // Training / validation forward: X[B][ldx] (transformed inputs) -> every op's output (`ops[i].y`, the hidden h of a

@@ -59,7 +59,9 @@
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, kq = lane >> 4;
     const int row0 = blockIdx.x * ROWS;
-    if (a.gate && a.gate[0] == 0) return;
+    if constexpr (!PLAIN) {
+        if (a.gate && a.gate[0] == 0) return;
+    }
     // MOVE == 2 with a row list (the later rounds of linna_slice_half_step): only the trial points of the walkers still
     // active are evaluated -- row r of the launch is trial point mv_C[r] (= j ns + k), mv_step[0] * mv_step_off rows in
     // all, counted on the device; the workgroups behind them leave at once
@@ -122,6 +124,14 @@
         zden = a.t_den[zsrc];
     }
     const int kpad0 = a.kpad0, nin = a.nin, nout = a.nout, nseg = a.nseg;
+    // PLAIN: the first descriptors of the segment table are touched here, among the argument loads.  A run's request for the
+    // next descriptor (plain_request) is the first access to its cache line otherwise, and the miss -- ~500 cycles, measured
+    // with the fine stamps -- sits in front of the run's first MFMA with nothing to hide under.
+    int seg_warm = 0;
+    if constexpr (PLAIN) {
+#pragma unroll
+        for (int i = 1; i < 8; ++i) seg_warm |= a.seg[i].type | a.seg[i].zext;     // (both 64-byte lines an 8-dword descriptor can span)
+    }
     const int nlast = (TRB ? a.nseg_f : nseg) - 2;  // STORE == 3: the network's last layer (the loss segment follows it)
     constexpr int ZPRE = 2;
     float zr[ZPRE], za1[ZPRE], za2[ZPRE], zxm[ZPRE], zxs[ZPRE]; int zfl[ZPRE], zlg[ZPRE];
@@ -248,9 +258,13 @@
     for (int i = 0; i < FIN; ++i) {
         const int cc = min(pc0 + i * RG, nout - 1);
         if constexpr (GRAD && !TRB) fgs[i] = a.gscale[cc]; else fgs[i] = 0.f;
+        if constexpr (PLAIN) {                     // (the launcher hands over all three)
+            fcs[i] = a.cscale[cc]; fct[i] = a.cshift[cc]; fw[i] = a.w[cc];
+        } else {
         const int c1 = a.cscale ? cc : 0, c2 = a.cshift ? cc : 0, c3 = a.w ? cc : 0;
         const float cs = csp[c1], ct = ctp[c2], ww = wtp[c3];
         fcs[i] = a.cscale ? cs : 1.f; fct[i] = a.cshift ? ct : 0.f; fw[i] = a.w ? ww : 0.f;
+        }
     }
 
     // ---- 2. weight stream: wave-uniform base + 32-bit per-lane offset + immediate
@@ -392,6 +406,7 @@
         if (prow && pc0 == 0) { lsrc[pr] = zsrc; lden[pr] = zden; }
     }
     float* const lx0 = lden + 16;                  // [ROWS][64]: the input rows, for a later input-skip segment
+    if constexpr (!PLAIN) {
     if (a.x0_keep && prow) {
 #pragma unroll
         for (int i = 0; i < ZPRE; ++i) {
@@ -399,6 +414,7 @@
             if constexpr (BF) lx0[pr * 64 + c] = c < nin ? act[pr * LD + c] + act[pr * LD + nin + c] : 0.f;   // x_hi + x_lo = x exactly
             else lx0[pr * 64 + c] = (c < kpad0) ? act[pr * LD + c] : 0.f;
         }
+    }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                  // raw: __syncthreads() would drain the weight stream
@@ -438,13 +454,23 @@
         if constexpr (DXE) { const int j = __builtin_amdgcn_readfirstlane(si); s_gmask = ka->gmask[j]; s_gmld = ka->gmld[j]; }
         if constexpr (LB) { const int j = __builtin_amdgcn_readfirstlane(si); s_gbit = ka->gbit[j]; s_mbit = ka->mbit[j]; }
     };
+    // PLAIN: the NEXT segment's descriptor sits in scalar registers from the start of the current run (requested behind the
+    // run's first A read; the wait of the next step for that fragment covers it), so no run end waits for a scalar load.
+    // Eight fields: a plain program reads nothing else, and the launcher folds ncg_log2 into the upper bits of `type`.
+    NsSeg nxp;
+    auto plain_request = [&]() { nxp = ka->seg[__builtin_amdgcn_readfirstlane(min(si + 1, nseg - 1))]; };
+    auto plain_take = [&](const NsSeg& X) {
+        s_type = X.type & 255; s_ncgl = X.type >> 8; kleft = s_steps = X.steps; s_passes = X.passes; s_bias = X.bias_off;
+        s_dst = X.dst_col; s_relu = X.relu; s_kslice = X.kslice; s_zext = X.zext;
+    };
     auto begin_run = [&]() {                       // accumulators and A pointer of run (si, pass)
         const int arow = SM ? sm_arow : li, ak = AK * (SM ? 4 * sm_achunk : 4 * kq);
 #pragma unroll
         for (int t = 0; t < NACC; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
         if (s_type == NS_WIDE) {
             // the wave's 64-column block of this run: 8 pass + wave -- or, balanced triangular factor (zext < 0), w then 15 - w
-            const int blk = s_zext < 0 ? (pass ? 15 - wave : wave) : 8 * pass + wave;
+            // (PLAIN: a plain program has neither the triangular factor nor a short second pass)
+            const int blk = !PLAIN && s_zext < 0 ? (pass ? 15 - wave : wave) : 8 * pass + wave;
             if constexpr (SM) {
                 const float b = lbias[s_bias + 64 * blk + lane];
 #pragma unroll
@@ -456,8 +482,8 @@
                     acc[t] = f32x4{b, b, b, b};
                 }
             }
-            if (s_zext < 0) kleft = s_steps - 4 * blk;             // its rows start at 64 blk
-            ap = act_lds + 4u * (uint32_t)(P * ABUF + arow * LD + ak + (s_zext < 0 ? 64 * blk : (pass ? s_kslice : 0)));   // (kslice: 0 but for a short second pass)
+            if (!PLAIN && s_zext < 0) kleft = s_steps - 4 * blk;             // its rows start at 64 blk
+            ap = act_lds + 4u * (uint32_t)(P * ABUF + arow * LD + ak + (PLAIN ? 0 : s_zext < 0 ? 64 * blk : (pass ? s_kslice : 0)));   // (kslice: 0 but for a short second pass)
         } else {
             ap = act_lds + 4u * (uint32_t)(P * ABUF + arow * LD + ak + (wave >> s_ncgl) * s_kslice);
         }
@@ -470,9 +496,15 @@
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
     };
+    if constexpr (PLAIN) {
+        asm volatile("" :: "s"(seg_warm));          // (the touches above are loads nobody else waits for)
+        plain_take(ka->seg[0]); begin_run(); a_read(Aq[0]); plain_request();
+    }
+    else {
     load_seg();
     begin_run();
     a_read(Aq[0]);
+    }
 
     auto step = [&](auto Uc, auto Refill) {
         constexpr int U = decltype(Uc)::value;
@@ -571,8 +603,10 @@
         }
         if constexpr (refill) wadvance();
         if (--kleft == 0) {
-            // ---- end of run (si, pass).  The next segment's descriptor is requested first: the scalar
-            // load's latency then hides under the epilogue stores and the barrier.
+            // ---- end of run (si, pass).  The next segment's descriptor is requested first.  (Meant to hide under the
+            // epilogue stores and the barrier; in the compiled code it does not: the descriptor's first use -- NX.type, for the
+            // SIDE prefetch -- waits for it at once, ~500 cycles of scalar-cache miss per run end.  PLAIN requests it a run
+            // ahead instead, plain_request.)
             const int nxi = __builtin_amdgcn_readfirstlane(min(si + 1, nseg - 1));
             const NsSeg NX = ka->seg[nxi];
             float* nx_gout = nullptr; int nx_gld = 0, nx_gn = 0;
@@ -590,6 +624,7 @@
                 kleft = X.steps;
             };
             auto take_next = [&]() {
+                if constexpr (PLAIN) { plain_take(nxp); return; }
                 take_seg(NX);
                 if constexpr (STORE) { s_gout = nx_gout; s_gld = nx_gld; s_gn = nx_gn; }
                 if constexpr (DXE) { s_gmask = nx_gmask; s_gmld = nx_gmld; }
@@ -599,7 +634,7 @@
             // does not see, so that they fly under this segment's epilogue and barrier
             f32x4 sdw[2][NT];
             bool side_next = false;
-            if constexpr (K4) {
+            if constexpr (K4 && !PLAIN) {
 #pragma unroll
                 for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
@@ -631,7 +666,7 @@
 #define q_row(q, e) (SM ? 4 * (q) + (e) : 4 * kq + (e))
 #define q_col(q) (SM ? lane : 16 * (q) + li)
             if (s_type == NS_WIDE) {
-                float* const nxt = act + (P ^ 1) * ABUF + s_dst + (s_zext < 0 ? 64 * (pass ? 15 - wave : wave) : 512 * pass + 64 * wave);
+                float* const nxt = act + (P ^ 1) * ABUF + s_dst + (!PLAIN && s_zext < 0 ? 64 * (pass ? 15 - wave : wave) : 512 * pass + 64 * wave);
                 // STORE == 3, last network layer: the targets and the per-column constants of delta, fetched by inline-asm
                 // loads the compiler does not count (a visible load in this loop body would turn its counted vmcnt waits
                 // for the weight ring into vmcnt(0) in EVERY step); one explicit wait for all of them
@@ -750,7 +785,7 @@
                     P ^= 1; pass = 0; ++si;
                     take_next();
                 } else {
-                    kleft = s_zext > 0 ? s_zext : cur_steps;    // (a short second pass: NsSeg::zext)
+                    kleft = !PLAIN && s_zext > 0 ? s_zext : cur_steps;    // (a short second pass: NsSeg::zext)
                     seg_done = false;
                 }
             } else {
@@ -991,7 +1026,7 @@
 #undef fin
 #undef q_row
 #undef q_col
-            if (seg_done && si < nseg && s_x0col > 0) {
+            if (!PLAIN && seg_done && si < nseg && s_x0col > 0) {
                 // input skip: the kept input rows go behind this segment's regular input (one GEMM over [h ; x0])
                 if (prow) {
                     float* const dstp = act + P * ABUF + pr * LD + s_x0col;
@@ -1001,7 +1036,7 @@
                 }
                 lds_barrier();
             }
-            if constexpr (K4) {
+            if constexpr (K4 && !PLAIN) {
                 if (side_next && seg_done) {
                     // ---- SIDE run: the segment now in s_* (taken above), whole, right here.  Wave w owns the k range
                     // [w kslice, (w + 1) kslice) (ncg = 1); a step covers kc chunks of 16 k: tile t of the weights is
@@ -1113,6 +1148,7 @@
             if (si < nseg) {
                 begin_run();
                 a_read(Aq[(U + 1) & 1]);           // replaces the speculative fragment
+                if constexpr (PLAIN) { if (seg_done) plain_request(); }
             }
 #ifdef NS_STAMPS_FINE
             if (fine) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); NS_STAMP(); }   // next run ready to issue
@@ -1211,17 +1247,19 @@
         return;
     }
     // ---- 5. output rows are in buffer P (bias added, no ReLU): output transform, d, log-likelihood
+    // (PLAIN: the launcher has checked that there is no exp map, no dense segment, no D / TH output, and that cscale,
+    // cshift, w and lnP are all there -- every test of them below is decided at compile time)
     {
         const float* const F = act + P * ABUF + pr * LD;
         const bool rok = prow && row0 + pr < a.B;
         float chi = 0.f;
         auto column = [&](int c, float cs, float ct, float ww) {
             float d = F[c] * cs + ct;
-            if (a.cpost) d = expf(d) * a.cpost[c] + a.cshift2[c];
-            if (a.D && rok) a.D[(size_t)(row0 + pr) * a.ldd + c] = isnan(zz) ? zz : d;   // (a poisoned row stays one for a later likelihood launch)
+            if (!PLAIN && a.cpost) d = expf(d) * a.cpost[c] + a.cshift2[c];
+            if (!PLAIN && a.D && rok) a.D[(size_t)(row0 + pr) * a.ldd + c] = isnan(zz) ? zz : d;   // (a poisoned row stays one for a later likelihood launch)
             chi += (d * ww) * d;
         };
-        if (a.dense) {
+        if (!PLAIN && a.dense) {
             // the last segment multiplied d (output map folded into the last layer) by the dense inverse covariance
             const float* const Dv = a.u_same ? F : act + (P ^ 1) * ABUF + pr * LD;
             const float* const U = a.u_same ? F + a.u_col : F;
@@ -1237,7 +1275,7 @@
             for (int i = 0; i < FIN; ++i)
                 if (pc0 + i * RG < nout) column(pc0 + i * RG, fcs[i], fct[i], fw[i]);
             for (int c = pc0 + FIN * RG; c < nout; c += RG)        // wide outputs: constants straight from memory
-                column(c, a.cscale ? a.cscale[c] : 1.f, a.cshift ? a.cshift[c] : 0.f, a.w ? a.w[c] : 0.f);
+                column(c, PLAIN || a.cscale ? a.cscale[c] : 1.f, PLAIN || a.cshift ? a.cshift[c] : 0.f, PLAIN || a.w ? a.w[c] : 0.f);
         }
 #pragma unroll
         for (int o = RG / 2; o >= 1; o >>= 1) chi += __shfl_xor(chi, o, 64);
@@ -1246,7 +1284,7 @@
         if constexpr (MOVE == 2) {
             if (a.lnP && pc0 == 0 && prow && row0 + pr < mv_rows) a.lnP[a.mv_C ? grow : row0 + pr] = lnp_new;
         } else {
-            if (a.lnP && (a.w || a.dense) && pc0 == 0 && rok) a.lnP[row0 + pr] = lnp_new;
+            if ((PLAIN || (a.lnP && (a.w || a.dense))) && pc0 == 0 && rok) a.lnP[row0 + pr] = lnp_new;
         }
         if constexpr (MOVE == 1) {
             // Metropolis test of the stretch move (linna_stretch_accept); every lane of the row agrees
@@ -1270,7 +1308,7 @@
                 if (pc0 == 0) a.mv_lps[mv_wk] = mv_acc ? lnp_new : mv_lnp_old;
             }
         }
-        if (a.TH && rok) {
+        if (!PLAIN && a.TH && rok) {
 #pragma unroll
             for (int j = 0; j < ZPRE; ++j)
                 if (pc0 + j * RG < nin) a.TH[(size_t)(row0 + pr) * a.ldt + pc0 + j * RG] = theta[j];

@@ -471,6 +471,16 @@ def describe_program(model, rows=16, dense_nout=0):
     return n, buf.value.decode()
 
 
+def program_is_plain(model, rows=16, dense_nout=0):
+    """Whether the serving program of ``model`` on the engine of ``rows`` rows per workgroup is a plain one -- WIDE and SPLIT
+    segments only, what the lean instantiation of the whole-network kernel runs (``linna_program_plain``: host-side planning,
+    no GPU needed)."""
+    n = _lib.load().linna_program_plain(program_layers(model), len(model.ops), model.in_size, int(rows), int(dense_nout))
+    if n < 0:
+        _lib.check(n)
+    return bool(n)
+
+
 def describe_grad_bf16_program(model, rows=16):
     """The program of the bf16 one-launch gradient (``Log_prob(precision="bf16", grad_precision="bf16")``) for ``model`` on the
     engine of ``rows`` rows per workgroup, as text (``linna_program_describe_grad_bf16``: host-side planning, no GPU

@@ -490,6 +490,13 @@ class Log_prob(object):
                   theta.stride(0) if theta is not None else 0, _lib.stream())
         return out
 
+    def serves_plain(self, B):
+        """Whether ``evaluate`` of ``B`` rows (no ``theta``) launches the lean ("plain") instantiation of the whole-network
+        kernel under the current ``_lib.serve_plain`` / ``_lib.engine_rows`` settings (``linna_logprob_serve_plain``)."""
+        out = C.c_int(0)
+        _lib.call("linna_logprob_serve_plain", self._ensure()["handle"], int(B), C.byref(out))
+        return bool(out.value)
+
     def evaluate_with_grad(self, z, out=None, grad=None):
         """``(lnP[B], d lnP/d z [B, nin])`` -- what ``torch.autograd.grad(lnP, x)`` yields in
         HMCSampler.py:32, batched per walker."""

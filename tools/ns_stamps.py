@@ -21,6 +21,9 @@ else:
     nin, nout = (33, 33) if which == "v2" else (26, 457)
     p = bench_paths.problem("ChtoModelv2", nin, nout, which != "v2")
     lp = p["lp"]
+if os.environ.get("NS_STAMPS_PLAIN"):                # 0: the generic instantiation for a plain MLP's serving launch too (linna_serve_plain)
+    from linna_amd import _lib
+    _lib.serve_plain(int(os.environ["NS_STAMPS_PLAIN"]))
 z = torch.randn(B, nin, device="cuda"); out = torch.empty(B, device="cuda")
 if os.environ.get("NS_STAMPS_STRETCH"):              # the one-launch stretch half step of an ensemble of 2 B walkers instead
     from linna_amd import sampler
