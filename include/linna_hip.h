@@ -407,6 +407,8 @@ int linna_logprob_grad_leapfrog(linna_logprob_t* lp, float* Q, int ldq, int B, v
  *   loss_b = chi2 / den_b ; L = inv_batch * sum_b loss_b ;  dPRED = -2 (delta Cinv) inv_batch/den_b
  *   (Cinv symmetric; inv_batch = 1/global batch so data-parallel shards sum to the mean)
  * den_b = max(chisqMd_b, nout/2) is precomputed per dataset row (linna_chi2_md).
+ * dPRED is written over its whole rows: the pad columns nout .. lddp - 1 come out zero (as those of XB, YN and
+ * the X of linna_prior_map_fwd do).
  * ROWS (int32, may be NULL = identity) selects minibatch rows out of the resident dataset. */
 typedef struct {
     uint32_t struct_size;   /* = sizeof of this struct in the CALLER's header; checked by every entry that takes it (LINNA_ERR_INVALID otherwise) */

@@ -229,6 +229,7 @@ __global__ __launch_bounds__(256) void loss_fused_small_kernel(
         const float dr = den[r];
         if (lane == 0) loss_rows[b] = chi / dr;
         if (dP && lane < lddp) dP[(size_t)b * lddp + lane] = masked ? 0.f : (-2.f * u) * inv_batch / dr;
+        if (dP) for (int c = 64 + lane; c < lddp; c += 64) dP[(size_t)b * lddp + c] = 0.f;   // pad columns past the wave: zero, as loss_grad_kernel leaves them
     }
     if (!loss_mean) return;
     __threadfence();
