@@ -354,6 +354,14 @@ int linna_program_plain(const linna_layer_t* layers, int nlayers, int in_size, i
 /* *out = 1 when linna_logprob_eval(lp, ..., B rows, THETA = null) would launch the plain instantiation under the current
  * linna_serve_plain and linna_engine_rows settings, else 0. */
 int linna_logprob_serve_plain(linna_logprob_t* lp, int B, int* out);
+/* *out = 1 when linna_logprob_grad / linna_logprob_grad_leapfrog* of B rows run lnP and d lnP / d z as ONE launch of the
+ * whole-network kernel under the current linna_engine_rows setting, else 0 (the layered route: forward with stored
+ * activations, likelihood gradient, dX chain, prior map, kick and drift as launches of their own).  The fp32 one-launch
+ * gradient of a network with more than 64 outputs is fitted to the LDS per engine, and a batch whose engine (its own, or
+ * linna_engine_rows') the program does not fit takes the layered route: ChtoModelv2(26,457) and (40,1000) run the one launch
+ * on the 8- and 4-row engines, i.e. up to 2048 rows on 256 CUs, and the layered route beyond (a smaller engine's two rounds
+ * of workgroups were measured slower than it).  Host only: nothing is launched. */
+int linna_logprob_grad_launches(linna_logprob_t* lp, int B, int* out);
 /* Which launches of linna_slice_half_step are folded into their neighbours, as a mask (default: all that apply): bit 0 -- with ONE
  * stepping-out round, its logic kernel is not launched: the first shrinking round's evaluation derives its trial points from
  * the bracket ends' lnP in its prologue and that round's logic kernel does the bookkeeping of both; bit 1 -- the set-up of the
@@ -392,7 +400,10 @@ int linna_logprob_eval_if(linna_logprob_t* lp, const float* Z, int ldz, int B, v
 int linna_logprob_eval_slice_points(linna_logprob_t* lp, const float* coords, int ldc, int ndim, const int* S_idx,
                                     int ns, const float* DIR, int ldd, const float* w, int nrep, float* lnP,
                                     const int* gate, void* stream);
-/* lnP[B] and d lnP / d z [B][ldg]  (intended semantics of util.py:1023-1035; HMCSampler.py:32). */
+/* lnP[B] and d lnP / d z [B][ldg]  (intended semantics of util.py:1023-1035; HMCSampler.py:32).  In fp32 with a diagonal
+ * covariance it is ONE launch of the whole-network kernel for networks of up to 64 inputs and any number of outputs the
+ * kernel serves (<= 1024) whose program fits an engine's LDS: linna_logprob_grad_launches tells.  A dense covariance, more
+ * than 64 inputs, or LINNA_DISABLE_FUSED_GRAD=1 at creation: the layered route. */
 int linna_logprob_grad(linna_logprob_t* lp, const float* Z, int ldz, int B, void* ws, float* lnP,
                        float* G, int ldg, void* stream);
 /* One leapfrog step's gradient, kick and drift (HMCSampler.py:35-49: p += eps dlnp(q); q += eps p / m): lnP and G at Q, then

@@ -139,6 +139,7 @@ _SIGNATURES = {
     "linna_serve_plain": (_I, [_I]),
     "linna_program_plain": (_I, [_V, _I, _I, _I, _I]),
     "linna_logprob_serve_plain": (_I, [_V, _I, _V]),
+    "linna_logprob_grad_launches": (_I, [_V, _I, _V]),
     "linna_slice_fusion": (_I, [_I]),
     "linna_net_train_launches": (_I, [_V, _I]),
     "linna_net_set_train_precision": (_I, [_V, _I]),

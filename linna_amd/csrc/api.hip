@@ -954,6 +954,7 @@ struct linna_logprob {
     bool grad_fused = false;                 // the streams also hold the backward segments (ReLU MLPs)
     StreamCopy packed_g2;                    // forward + dX chain down to the input in one stream (any network: residual blocks, ...)
     bool grad2 = false;
+    bool g2_fits[3] = {true, true, true};    // packed_g2's program fits the LDS of the 16- / 8- / 4-row engine (net_stream_grad_fits)
     bool dense_fused = false;                // the streams end in the dense inverse covariance (output map folded in)
     bool fused_on = true;                    // LINNA_DISABLE_FUSED, read at creation
     int dense_tri = 2;                       // NsDense::tri, fixed when the object is created (the stream's size depends on it)
@@ -1104,8 +1105,10 @@ int linna_logprob_create(linna_ctx_t* ctx, linna_net_t* net, const linna_logprob
     // lnP + gradient in one launch for the networks the MLP-only fused gradient does not cover (residual blocks, SPLIT
     // segments): forward program + dX chain in one weight stream, gates from the activations the same launch stored
     if (!lp->grad_fused && desc->w && desc->gscale && !desc->outmap.cexp && !net->has_inskip && !env_is("LINNA_DISABLE_FUSED_GRAD", '1')) {
-        const NsPlan g2 = net_stream_plan(NS_GRAD_INPUT, net->L.data(), (int)net->L.size(), net->in_size);
+        const NsPlan g2 = net_stream_plan(ns_grad_kind(net->L.data(), (int)net->L.size()), net->L.data(), (int)net->L.size(), net->in_size);
         if (g2.ok && lp->packed_g2.alloc(g2.packed_floats) == LINNA_OK) lp->grad2 = true;
+        // (fitted per engine once, here: wide outputs may not fit the LDS of the 16-row one)
+        for (int e = 0; e < 3; ++e) lp->g2_fits[e] = net_stream_grad_fits(net->L.data(), (int)net->L.size(), net->in_size, 16 >> e);
     }
     *out = lp;
     return LINNA_OK;
@@ -1181,7 +1184,7 @@ int linna_program_describe(const linna_layer_t* layers, int nlayers, int in_size
     TRY(check_layers(layers, nlayers, "program_describe"));
     // (pointers are only compared, never read: a placeholder stands for the dense inverse covariance)
     static float dummy;
-    if (dense_nout == -1) return net_stream_describe(NS_GRAD_INPUT, layers, nlayers, in_size, nullptr, rows, buf, n);   // the one-launch gradient's program
+    if (dense_nout == -1) return net_stream_describe(ns_grad_kind(layers, nlayers), layers, nlayers, in_size, nullptr, rows, buf, n);   // the one-launch gradient's program
     const int dn_cols = dense_nout < -1 ? -dense_nout : dense_nout;         // < -1: the factored form (chi^2 = |d L|^2) of -dense_nout columns
     NsDense dn{&dummy, (dn_cols + 3) & ~3, nullptr, nullptr, dense_nout < -1 ? 1 : 0, net_stream_dense_tri(-1)};
     if (dn_cols > 0) return net_stream_describe(NS_SERVE_DENSE, layers, nlayers, in_size, &dn, rows, buf, n);
@@ -1440,10 +1443,23 @@ int linna_chain_meanstd(linna_ctx_t*, const float* CT, int ndim, int nwp, int nw
 static NsGrad lp_grad_args(const linna_logprob_desc_t& d, float* G, int ldg, const NsLeap* leap) {
     return NsGrad{d.gscale, G, ldg, leap ? *leap : NsLeap{}};
 }
+// The engine the fp32 one-launch gradient (packed_g2) takes for B rows: the batch's own (or linna_engine_rows') where the
+// program fits its LDS; 0: it does not -- the layered route, which was measured faster than a smaller engine's two rounds of
+// workgroups (net_stream_grad_fits, net_program.hip)
+static int lp_grad2_rows(const linna_logprob* lp, int B) {
+    const int want = net_stream_rows(B);
+    return lp->g2_fits[want == 16 ? 0 : want == 8 ? 1 : 2] ? want : 0;
+}
+// Whether lnP and its gradient of B rows are ONE launch (logprob_grad_impl's own decision, and linna_logprob_grad_launches')
+static bool lp_grad_one_launch(const linna_logprob* lp, int B) {
+    if (lp->bf16()) return lp->grad_precision == LINNA_PRECISION_BF16 && lp->fused_on && lp->packed_gbf.ready();
+    if (lp->fused_on && lp->packed.ready() && lp->grad_fused && lp->d.w) return true;
+    return lp->fused_on && lp->grad2 && lp->packed_g2.ready() && lp->d.w && lp_grad2_rows(lp, B) != 0;
+}
 // forward + dX chain down to the input in one launch on the stream copy `sc` (NS_GRAD_INPUT, or its bf16 form)
 static int lp_launch_grad2(linna_logprob* lp, StreamCopy& sc, bool bf, const float* Z, int ldz, int B, float* lnP, const NsGrad& gr, void* stream) {
-    const NsKind kind = bf ? NS_GRAD_INPUT_BF16 : NS_GRAD_INPUT;
-    const int rows = net_stream_rows(B);
+    const NsKind kind = bf ? NS_GRAD_INPUT_BF16 : ns_grad_kind(lp->net->L.data(), (int)lp->net->L.size());
+    const int rows = bf ? net_stream_rows(B) : lp_grad2_rows(lp, B);
     const float* packed = nullptr;
     TRY(stream_copy_refresh(sc, lp->net, rows, stream, &packed, kind));
     return launch_net_stream_grad2(net_layers(lp->net, kind), packed, Z, ldz, B, lp_input(lp->d), lp_output(lp), lnP, gr, rows, S(stream), bf);
@@ -1486,7 +1502,7 @@ static int logprob_grad_impl(linna_logprob_t* lp, const float* Z, int ldz, int B
     const LpLayout L = lp_layout(lp, B, 1);
     float* w = static_cast<float*>(ws);
     const int ldx = ld4(d.nin), ldd = ld4(d.nout);
-    if (lp->fused_on && lp->grad2 && lp->packed_g2.ready() && d.w) {
+    if (lp->fused_on && lp->grad2 && lp->packed_g2.ready() && d.w && lp_grad2_rows(lp, B) != 0) {
         // ONE launch for any network: forward segments (the signs the gates need kept as bits in LDS), turnaround, dX chain
         // down to the input, prior map's derivative (net_stream.hip, GRAD + STORE == 2) -- six launches otherwise
         return lp_launch_grad2(lp, lp->packed_g2, false, Z, ldz, B, lnP, gr, stream);
@@ -1511,6 +1527,12 @@ extern "C" {
 int linna_logprob_grad(linna_logprob_t* lp, const float* Z, int ldz, int B, void* ws, float* lnP, float* G, int ldg,
                        void* stream) try {
     return logprob_grad_impl(lp, Z, ldz, B, ws, lnP, G, ldg, nullptr, stream);
+} LINNA_CATCH_INT
+// Whether that call is ONE launch for B rows under the current linna_engine_rows (host only: logprob_grad_impl's own decision)
+int linna_logprob_grad_launches(linna_logprob_t* lp, int B, int* out) try {
+    if (!lp || !out || B < 1) { set_error("logprob_grad_launches: bad arguments"); return LINNA_ERR_INVALID; }
+    *out = lp_grad_one_launch(lp, B) ? 1 : 0;
+    return LINNA_OK;
 } LINNA_CATCH_INT
 
 // One leapfrog step's gradient, kick and drift (HMCSampler.py:35-49): lnP and G = d lnP / d z at Q, then P += eps_kick G and

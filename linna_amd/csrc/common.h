@@ -365,6 +365,7 @@ enum NsKind {
     NS_TRAIN_STEP,     // forward + loss + dX chain down to op 1: the merged training step (4-row engine)
     NS_TRAIN_STEP_BF16,   // ... in bf16 (linna_net_set_train_precision): bf16 runs, the loss segment an fp32 run, first layer [W | W]
     NS_GRAD_INPUT_BF16,   // NS_GRAD_INPUT in bf16 (linna_logprob_set_grad_precision): every run bf16, first layer [W | W], no SIDE segments
+    NS_GRAD_INPUT_WIDE,   // NS_GRAD_INPUT for networks of MORE than 64 outputs (net_stream_wide_kernel): the same program, fitted to the LDS per engine
 };
 // the serving programs are built from the layer list with the trailing input skip, the training ones from the list without
 inline bool ns_kind_full_layers(NsKind k) { return k == NS_SERVE || k == NS_SERVE_DENSE || k == NS_SERVE_BF16; }
@@ -377,6 +378,12 @@ NsPlan net_stream_plan(NsKind kind, const linna_layer_t* layers, int nl, int in_
 // workgroups would leave CUs idle.  The 16-row engine and the small ones read different orders of the weight stream.
 int net_stream_rows(int B);
 int net_stream_force_rows(int rows);   // 0 automatic, 4 / 8 / 16 forced; returns the previous setting, -1 for an invalid value
+// The fp32 one-launch gradient's program kind for this op list: NS_GRAD_INPUT up to 64 outputs (it fits every engine or
+// none), NS_GRAD_INPUT_WIDE beyond
+inline NsKind ns_grad_kind(const linna_layer_t* layers, int nl) { return nl >= 1 && layers[nl - 1].N > 64 ? NS_GRAD_INPUT_WIDE : NS_GRAD_INPUT; }
+// Whether that program runs on the engine of `rows` rows: it and its sign bits fit the LDS (host-side planning only).  A
+// batch whose engine it does not fit takes the layered route.
+bool net_stream_grad_fits(const linna_layer_t* layers, int nl, int in_size, int rows);
 int launch_net_stream_pack(NsKind kind, const linna_layer_t* layers, int nl, int in_size, float* packed, int rows, const NsDense* dn,
                            hipStream_t s);
 int net_stream_describe(NsKind kind, const linna_layer_t* layers, int nl, int in_size, const NsDense* dn, int rows, char* buf, size_t n);

@@ -73,6 +73,8 @@ struct NsBuildOpts {
     // the bf16 programs (serving without a dense segment, the merged training step, the one-launch gradient; no SIDE segments): a step is 32 k, and the
     // first layer (a plain linear map) is [W | W] over K' = 2 nin -- its input rows are x_hi = bf16(x) and x_lo = x - x_hi
     bool bf = false;
+    // NS_GRAD_INPUT_WIDE: more than 64 network outputs behind the forward half of an NS_BWD_INPUT program
+    bool wide_out = false;
 };
 
 // One linear map of a program: [Wa | alpha Wb] over K = [Kapad ; Kb], N outputs, written to dst_col (same_buf: into the
@@ -201,7 +203,9 @@ static NsLowered ns_lower(const linna_layer_t* layers, int nl, int in_size, cons
     r.nfwd = (int)lins.size();
     if (o.bf && train) r.f32seg = r.nfwd - 1;
     if (dxi) {
-        if (in_size > 64 || lins.back().N > 64) return r;      // (prologue / turnaround constants are held for <= 64 columns)
+        // the prologue / turnaround constants are held for <= 64 columns; the wide-output instantiations of the fp32 kernel
+        // (net_stream_wide_kernel) read the output's beyond 64 from memory -- a program kind of its own
+        if (in_size > 64 || (lins.back().N > 64) != o.wide_out) return r;
         ns_push_dx(lins, layers, nl, 0);
     }
     if (train) {                                               // the turnaround works on the rows in LDS: any width
@@ -362,7 +366,9 @@ static bool ns_written_columns(NsProgram& p, const std::vector<int>& in_ext, int
 static bool ns_sizes(NsProgram& p, int maxext) {
     p.LD = std::max(((maxext + 63) & ~63) + 4, 516);        // >= 516: SPLIT partials need [8][rows][64] floats in one buffer
     if (p.bias_total > 3 * 64 * NS_NW * 4) return false;    // BMAX rounds of float4 per thread
-    if (p.lds_for(NS_ROWS, true) > (size_t)NS_LDS_BYTES) return false;   // (the sign-bit slots' share: never for the eligible shapes)
+    // (the sign-bit slots' share: never for the eligible shapes.  The wide-output one-launch gradient is fitted per engine, with its
+    // sign bits, by net_stream_grad_fits: here it only has to fit the smallest one)
+    if (p.lds_for(p.dxi_ok && p.nout > 64 ? 4 : NS_ROWS, true) > (size_t)NS_LDS_BYTES) return false;
     int nrun = 0;
     for (const NsSeg& s : p.seg) nrun += s.passes;
     if (nrun > NS_MAXRUN) return false;
@@ -420,7 +426,7 @@ int net_stream_force_rows(int rows) {
 // as sign bits in LDS and the per-segment tables read through the kernel-argument segment (without that the instantiation
 // spilled 2.5 KB per lane): 151.4 -> 148.7 us at ChtoModelv2(33,33), 4096 chains (NOTES R4).  Not in bf16.
 static bool ns_side(NsKind kind, int rows) {
-    return rows == 16 && (kind == NS_SERVE || kind == NS_SERVE_DENSE || kind == NS_GRAD_INPUT);
+    return rows == 16 && (kind == NS_SERVE || kind == NS_SERVE_DENSE || kind == NS_GRAD_INPUT || kind == NS_GRAD_INPUT_WIDE);
 }
 
 static NsProgram ns_build_kind(NsKind kind, const linna_layer_t* layers, int nl, int in_size, const NsDense* dn, bool side) {
@@ -433,6 +439,7 @@ static NsProgram ns_build_kind(NsKind kind, const linna_layer_t* layers, int nl,
     case NS_DX: o.forward = false; break;
     case NS_DX_INPUT: o.forward = false; o.dx_first = 0; break;
     case NS_GRAD_INPUT: o.bwd = NS_BWD_INPUT; break;
+    case NS_GRAD_INPUT_WIDE: o.bwd = NS_BWD_INPUT; o.wide_out = true; break;
     case NS_GRAD_INPUT_BF16: o.bwd = NS_BWD_INPUT; o.bf = true; if (dn) return NsProgram(); break;
     case NS_TRAIN_STEP: case NS_TRAIN_STEP_BF16: o.dense = true; o.bwd = NS_BWD_TRAIN; o.bf = kind == NS_TRAIN_STEP_BF16; break;
     }
@@ -442,7 +449,7 @@ static NsProgram ns_build_kind(NsKind kind, const linna_layer_t* layers, int nl,
         p = ns_build_one(layers, nl, in_size, o, dn);
     }
     // the SIDE program where it fits, the plain one otherwise
-    if (side && !(p.ok && (kind != NS_GRAD_INPUT || p.dxi_ok))) return ns_build_kind(kind, layers, nl, in_size, dn, false);
+    if (side && !(p.ok && ((kind != NS_GRAD_INPUT && kind != NS_GRAD_INPUT_WIDE) || p.dxi_ok))) return ns_build_kind(kind, layers, nl, in_size, dn, false);
     return p;
 }
 NsProgramRef ns_program(NsKind kind, const linna_layer_t* layers, int nl, int in_size, const NsDense* dn, int rows) {
@@ -518,6 +525,22 @@ NsGates ns_gates(const NsProgram& p, const linna_layer_t* layers, int nl, int ro
     return g;
 }
 
+// LDS of the fp32 one-launch gradient on the `rows` engine, sign bits included (0: no such program).  Each engine has its
+// own figure: the activations and the bits scale with the rows, and the 16-row engine reads the SIDE program.
+static size_t ns_grad_lds(const linna_layer_t* layers, int nl, int in_size, int rows) {
+    const NsProgramRef pref = ns_program(ns_grad_kind(layers, nl), layers, nl, in_size, nullptr, rows);
+    return pref->ok && pref->dxi_ok ? ns_gates(*pref, layers, nl, rows).lds : 0;
+}
+// Whether the fp32 one-launch gradient runs on the `rows` engine: program and sign bits within its LDS.  Networks of <= 64
+// outputs fit every engine; wide outputs may not fit 16 rows (ChtoModelv2(26,457): 165 632 B with 3136 sign-bit columns).
+// A batch whose engine the program does not fit takes the layered route, NOT a smaller engine: a smaller engine means more
+// workgroups than CUs, i.e. two rounds of them -- measured at 4096 rows on the 8-row engine against the layered route on
+// the 16-row one: 259.7 against 230.6 us at (26,457), 438.0 against 371.2 us at (40,1000) (wide outputs).
+bool net_stream_grad_fits(const linna_layer_t* layers, int nl, int in_size, int rows) {
+    const size_t lds = ns_grad_lds(layers, nl, in_size, rows);
+    return lds && lds <= (size_t)NS_LDS_BYTES;
+}
+
 // why the bf16 program does not exist for this network (null: it does)
 static const char* ns_bf16_refusal(const NsProgram& p, const linna_layer_t* layers, int nl, int in_size) {
     int width = 0;
@@ -538,8 +561,10 @@ NsPlan net_stream_plan(NsKind kind, const linna_layer_t* layers, int nl, int in_
         if (!r.why && !p.train_ok) r.why = "the network has no merged training step (one layer only)";
         r.ok = r.why == nullptr;
     }
-    if (kind == NS_GRAD_INPUT) {
+    if (kind == NS_GRAD_INPUT || kind == NS_GRAD_INPUT_WIDE) {
         r.ok = p.ok && p.dxi_ok && ns_gates(p, layers, nl, NS_ROWS).lds <= (size_t)NS_LDS_BYTES;
+        // wide outputs: on SOME engine -- a launch asks for its own (net_stream_grad_fits)
+        for (int rows = 8; kind == NS_GRAD_INPUT_WIDE && rows >= 4; rows >>= 1) r.ok = r.ok || net_stream_grad_fits(layers, nl, in_size, rows);
         // one copy serves every engine: the 16-row one reads the SIDE program
         r.packed_floats = std::max(r.packed_floats, ns_program(kind, layers, nl, in_size, dn, 16)->packed_floats);
     }
@@ -574,11 +599,25 @@ int net_stream_describe(NsKind kind, const linna_layer_t* layers, int nl, int in
                  g.zext, p.pack[i].N);
         out += line;
     }
-    if (p.ok && (kind == NS_GRAD_INPUT || kind == NS_GRAD_INPUT_BF16)) {            // the one-launch gradient: its LDS with the sign-bit matrix, on the 16-row engine
+    if (p.ok && (kind == NS_GRAD_INPUT || kind == NS_GRAD_INPUT_BF16 || kind == NS_GRAD_INPUT_WIDE)) {            // the one-launch gradient: its LDS with the sign-bit matrix, on the 16-row engine
         const NsGates g = ns_gates(p, layers, nl, NS_ROWS);
-        snprintf(line, sizeof line, "lds %zu of %d bytes with %d sign-bit columns: %s\n", g.lds, NS_LDS_BYTES, g.ncols,
-                 g.lds <= (size_t)NS_LDS_BYTES && p.dxi_ok ? "one launch" : "layered");
-        out += line;
+        size_t lds[3]; int fits = 0;                        // the wide-output program is fitted per engine (net_stream_grad_fits)
+        for (int e = 0; e < 3; ++e) {
+            lds[e] = kind == NS_GRAD_INPUT_WIDE ? ns_grad_lds(layers, nl, in_size, 16 >> e) : 0;
+            fits += lds[e] && lds[e] <= (size_t)NS_LDS_BYTES;
+        }
+        if (kind != NS_GRAD_INPUT_WIDE || fits == 3) {
+            snprintf(line, sizeof line, "lds %zu of %d bytes with %d sign-bit columns: %s\n", g.lds, NS_LDS_BYTES, g.ncols,
+                     g.lds <= (size_t)NS_LDS_BYTES && p.dxi_ok ? "one launch" : "layered");
+            out += line;
+        } else {                                            // not on every engine: each engine's bytes, then the engines that fit
+            snprintf(line, sizeof line, "lds 16:%zu 8:%zu 4:%zu of %d bytes with %d sign-bit columns: %s", lds[0], lds[1], lds[2], NS_LDS_BYTES,
+                     g.ncols, fits ? "one launch (rows" : "layered");
+            out += line;
+            for (int e = 0; fits && e < 3; ++e)
+                if (lds[e] && lds[e] <= (size_t)NS_LDS_BYTES) { snprintf(line, sizeof line, " %d", 16 >> e); out += line; }
+            out += fits ? ")\n" : "\n";
+        }
     }
     if (buf && n) { snprintf(buf, n, "%s", out.c_str()); }
     return p.ok ? (int)p.seg.size() : 0;

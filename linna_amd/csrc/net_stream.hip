@@ -316,7 +316,7 @@ __device__ __forceinline__ float ns_prior_theta(float z, int flat, float a1, flo
 // instructions for every existing instantiation.)
 template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF = false>
 __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_kernel(NsArgs a) {
-    constexpr bool EPS = false, PLAIN = false;
+    constexpr bool EPS = false, PLAIN = false, WOUT = false;
 #include "net_stream_body.inc"
 }
 // EPS: the fp32 gradient programs (GRAD, STORE 0 or 2) whose finish runs the leapfrog with a step size per row, a.hm_eps
@@ -326,7 +326,18 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_kernel(NsArgs a) {
 template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF>
 __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_eps_kernel(NsArgs a) {
     static_assert(!BF && GRAD && (STORE == 0 || STORE == 2) && MOVE == 0, "the fp32 one-launch gradients only");
-    constexpr bool EPS = true, PLAIN = false;
+    constexpr bool EPS = true, PLAIN = false, WOUT = false;
+#include "net_stream_body.inc"
+}
+// WOUT: the fp32 one-launch gradient (GRAD + STORE == 2) of a network with MORE than 64 outputs, with and without EPS.  The
+// turnaround holds the output map, the likelihood weights and gscale of 64 columns per row in registers, loaded up front;
+// here it walks the rest of the row with those constants read from memory (net_stream_body.inc).  Kernels of their own for
+// the same reason as EPS: the <= 64-output instantiations keep their instructions.  Everything else -- the poisoned prior
+// term of a non-finite row, the dX chain, the leapfrog in the finish -- is the shared text.
+template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF, bool EPSV>
+__global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_wide_kernel(NsArgs a) {
+    static_assert(!BF && GRAD && STORE == 2 && MOVE == 0, "the fp32 one-launch gradient of any network only");
+    constexpr bool EPS = EPSV, PLAIN = false, WOUT = true;
 #include "net_stream_body.inc"
 }
 // PLAIN: the serving launch of a plain MLP (ns_program_plain, net_program.hip: WIDE and SPLIT segments only, diagonal
@@ -338,13 +349,13 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_eps_kernel(NsArgs a)
 template <int R>
 __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_plain_kernel(NsArgs a) {
     constexpr int MOVE = 0, STORE = 0, ROWS = 16;
-    constexpr bool GRAD = false, BF = false, EPS = false, PLAIN = true;
+    constexpr bool GRAD = false, BF = false, EPS = false, PLAIN = true, WOUT = false;
 #include "net_stream_body.inc"
 }
 template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF>
 __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_train_bf16_kernel(NsArgs a) {
     static_assert(BF && GRAD && STORE == 3 && ROWS == 4 && MOVE == 0, "the bf16 training step only");
-    constexpr bool EPS = false, PLAIN = false;
+    constexpr bool EPS = false, PLAIN = false, WOUT = false;
 #include "net_stream_body.inc"
 }
 // BF + MOVE == 2: the ensemble slice move's evaluation on the bf16 serving engine (linna_slice_half_step,
@@ -355,7 +366,7 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_train_bf16_kernel(Ns
 template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF>
 __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_slice_bf16_kernel(NsArgs a) {
     static_assert(BF && !GRAD && STORE == 0 && MOVE == 2, "the bf16 slice evaluation only");
-    constexpr bool EPS = false, PLAIN = false;
+    constexpr bool EPS = false, PLAIN = false, WOUT = false;
 #define NS_BODY_SLICE_BF16
 #include "net_stream_body.inc"
 #undef NS_BODY_SLICE_BF16
@@ -370,7 +381,7 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_slice_bf16_kernel(Ns
 template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF>
 __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_grad_bf16_kernel(NsArgs a) {
     static_assert(BF && GRAD && STORE == 2 && MOVE == 0, "the bf16 one-launch gradient only");
-    constexpr bool EPS = false, PLAIN = false;
+    constexpr bool EPS = false, PLAIN = false, WOUT = false;
 #define NS_BODY_GRAD_BF16
 #include "net_stream_body.inc"
 #undef NS_BODY_GRAD_BF16
@@ -378,7 +389,7 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_grad_bf16_kernel(NsA
 template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF>
 __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_eps_bf16_kernel(NsArgs a) {      // ... with a step size per row (EPS)
     static_assert(BF && GRAD && STORE == 2 && MOVE == 0, "the bf16 one-launch gradient only");
-    constexpr bool EPS = true, PLAIN = false;
+    constexpr bool EPS = true, PLAIN = false, WOUT = false;
 #define NS_BODY_GRAD_BF16
 #include "net_stream_body.inc"
 #undef NS_BODY_GRAD_BF16
@@ -452,7 +463,7 @@ static int ns_launch_rows(const NsArgs& a, int B, size_t lds_bytes, hipStream_t 
 // plain: the PLAIN instantiation (net_stream_plain_kernel; the caller has checked ns_program_plain and the launch's own conditions)
 template <int MOVE, bool GRAD, int STORE = 0, bool BF = false, bool EPS = false>
 static int ns_launch_kernel(const NsArgs& a0, int B, const NsProgram& p, int rows, hipStream_t s, int extra = 0, size_t lds_extra = 0,
-                            bool plain = false) {
+                            bool plain = false, bool wide = false) {
     const size_t lds = p.lds_for(rows, GRAD) + lds_extra;
 #ifdef NS_STAMPS
     // diagnostic build: every launch writes its phase stamps to the buffer LINNA_FUSED_STAMPS names (tools/ns_stamps*.py)
@@ -464,6 +475,12 @@ static int ns_launch_kernel(const NsArgs& a0, int B, const NsProgram& p, int row
 #endif
     if constexpr (MOVE == 0 && !GRAD && STORE == 0 && !BF && !EPS) {
         if (plain && rows == 16) return ns_launch<net_stream_plain_kernel<NS_R>>(a, (B + 15) / 16, lds, s, "net_stream plain launch");
+    }
+    if constexpr (MOVE == 0 && GRAD && STORE == 2 && !BF) {     // wide: more than 64 outputs (net_stream_wide_kernel; the caller has checked the engine)
+        const char* const what = "net_stream wide-output gradient launch";
+        if (wide && rows == 4) return ns_launch<net_stream_wide_kernel<NS_R, 0, true, 2, 4, false, EPS>>(a, (B + 3) / 4, lds, s, what);
+        if (wide && rows == 8) return ns_launch<net_stream_wide_kernel<NS_R, 0, true, 2, 8, false, EPS>>(a, (B + 7) / 8, lds, s, what);
+        if (wide && rows == 16) return ns_launch<net_stream_wide_kernel<NS_R, 0, true, 2, 16, false, EPS>>(a, (B + 15) / 16, lds, s, what);
     }
     if (rows == 4) return ns_launch_rows<MOVE, GRAD, STORE, 4, BF, EPS>(a, B, lds, s, extra);
     if constexpr (BF) {
@@ -745,7 +762,7 @@ int launch_net_stream_store(const NsNet& net, const float* packed, const float* 
 // derivative.  Diagonal covariance.  bf: the same on a bf16 stream (NS_GRAD_INPUT_BF16, net_stream_grad_bf16_kernel).
 int launch_net_stream_grad2(const NsNet& net, const float* packed, const float* Z, int ldz, int B, const NsInput& in, const NsOutput& out,
                             float* lnP, const NsGrad& gr, int rows, hipStream_t s, bool bf) {
-    const NsProgramRef pref = ns_program(bf ? NS_GRAD_INPUT_BF16 : NS_GRAD_INPUT, net.layers, net.nl, net.in_size, nullptr, rows);
+    const NsProgramRef pref = ns_program(bf ? NS_GRAD_INPUT_BF16 : ns_grad_kind(net.layers, net.nl), net.layers, net.nl, net.in_size, nullptr, rows);
     const NsProgram& p = *pref;
     if (!p.ok || !p.dxi_ok) { set_error("net_stream: no forward + dX program for this network"); return LINNA_ERR_UNSUPPORTED; }
     if (!out.w || !lnP || !gr.gscale || !gr.G) { set_error("net_stream: the one-launch gradient needs a diagonal covariance"); return LINNA_ERR_INVALID; }
@@ -777,8 +794,9 @@ int launch_net_stream_grad2(const NsNet& net, const float* packed, const float* 
         set_error("net_stream: %d rows per workgroup", rows);
         return LINNA_ERR_INVALID;
     }
-    if (a.hm_p && a.hm_eps) return ns_launch_kernel<0, true, 2, false, true>(a, B, p, rows, s, 0, lds_extra);
-    return ns_launch_kernel<0, true, 2>(a, B, p, rows, s, 0, lds_extra);
+    const bool wide = p.nout > 64;                          // the turnaround's tail over the columns past its registers
+    if (a.hm_p && a.hm_eps) return ns_launch_kernel<0, true, 2, false, true>(a, B, p, rows, s, 0, lds_extra, false, wide);
+    return ns_launch_kernel<0, true, 2>(a, B, p, rows, s, 0, lds_extra, false, wide);
 }
 
 // the forward + loss half of a training launch (STORE == 3): the batch rows ROWS (null: 0..B-1) of X gathered and

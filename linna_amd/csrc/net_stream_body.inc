@@ -1,6 +1,7 @@
 // The body of the whole-network kernels (net_stream.hip: net_stream_kernel, net_stream_train_bf16_kernel,
-// net_stream_slice_bf16_kernel, net_stream_grad_bf16_kernel), included
-// inside each kernel's braces; its template parameters R, MOVE, GRAD, STORE, ROWS, BF and its argument NsArgs a are theirs.
+// net_stream_slice_bf16_kernel, net_stream_grad_bf16_kernel, the EPS / PLAIN / WOUT instantiations), included
+// inside each kernel's braces; its template parameters R, MOVE, GRAD, STORE, ROWS, BF, its compile-time flags EPS, PLAIN and
+// WOUT, and its argument NsArgs a are theirs.
     constexpr int NT = NS_NT, NW = NS_NW;
     constexpr int RG = 32;                         // threads per walker row in prologue / reduce / finish
     constexpr bool SM = ROWS < 16;                 // 4x4x1 engine: ROWS / 4 row sets, lane = column
@@ -1015,6 +1016,17 @@
                             chi += (d * fw[i]) * d;
                             F[c] = -(d * fw[i]) * fgs[i] / a.T;
                         }
+                    }
+                    if constexpr (WOUT) {
+                        // wide outputs (an instantiation of its own, as EPS is): the columns past the FIN register-held ones,
+                        // their constants straight from memory -- here in the turnaround, once per launch, outside `step`
+                        if (prow)
+                            for (int c = pc0 + FIN * RG; c < nout; c += RG) {
+                                const float d = F[c] * (a.cscale ? a.cscale[c] : 1.f) + (a.cshift ? a.cshift[c] : 0.f);
+                                const float dw = d * a.w[c];
+                                chi += dw * d;
+                                F[c] = -dw * a.gscale[c] / a.T;
+                            }
                     }
 #pragma unroll
                     for (int o = RG / 2; o >= 1; o >>= 1) chi += __shfl_xor(chi, o, 64);

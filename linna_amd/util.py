@@ -497,6 +497,14 @@ class Log_prob(object):
         _lib.call("linna_logprob_serve_plain", self._ensure()["handle"], int(B), C.byref(out))
         return bool(out.value)
 
+    def grad_launches(self, B):
+        """1 when ``evaluate_with_grad`` (and every leapfrog step of ``BatchedHMC``) of ``B`` rows is ONE launch of the
+        whole-network kernel under the current ``_lib.engine_rows`` setting, 0 when it is the layered route
+        (``linna_logprob_grad_launches``)."""
+        out = C.c_int(0)
+        _lib.call("linna_logprob_grad_launches", self._ensure()["handle"], int(B), C.byref(out))
+        return int(out.value)
+
     def evaluate_with_grad(self, z, out=None, grad=None):
         """``(lnP[B], d lnP/d z [B, nin])`` -- what ``torch.autograd.grad(lnP, x)`` yields in
         HMCSampler.py:32, batched per walker."""
