@@ -348,6 +348,12 @@ int linna_dense_tri(int mode);
  * every launch runs the generic instantiation, -1 queries; returns the previous value (tests, interleaved A/B).
  * Process-wide: the launch path reads one atomic. */
 int linna_serve_plain(int on);
+/* Which step a plain launch runs: 1 (default) the step placed by hand -- the same sixteen MFMAs, four refill loads, A read
+ * and counted waits as one block of assembly, at most one filler per MFMA gap, the stream address on the scalar unit
+ * (net_stream_placed_kernel) -- 0 the compiler-scheduled step (net_stream_plain_kernel), -1 queries; returns the previous
+ * value, refuses anything else.  lnP is bit-identical either way (tests, interleaved A/B).  Process-wide, one atomic read on
+ * the launch path; without effect on launches that are not plain. */
+int linna_serve_plain_sched(int hand);
 /* 1 when the serving program of this op list on the engine of `rows` rows per workgroup is plain (dense_nout != 0: with a
  * dense inverse covariance, never), else 0.  Host-side planning only, like linna_program_describe. */
 int linna_program_plain(const linna_layer_t* layers, int nlayers, int in_size, int rows, int dense_nout);

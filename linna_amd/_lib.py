@@ -137,6 +137,7 @@ _SIGNATURES = {
     "linna_engine_rows": (_I, [_I]),
     "linna_dense_tri": (_I, [_I]),
     "linna_serve_plain": (_I, [_I]),
+    "linna_serve_plain_sched": (_I, [_I]),
     "linna_program_plain": (_I, [_V, _I, _I, _I, _I]),
     "linna_logprob_serve_plain": (_I, [_V, _I, _V]),
     "linna_logprob_grad_launches": (_I, [_V, _I, _V]),
@@ -362,6 +363,15 @@ def slice_fusion(mask=-1):
     """Which launches of linna_slice_half_step are folded into their neighbours (a mask, include/linna_hip.h); -1 queries.
     Returns the previous mask (tests and measurements: the chain is the same under every mask)."""
     prev = load().linna_slice_fusion(int(mask))
+    if prev < 0:
+        check(prev)
+    return prev
+
+
+def serve_plain_sched(hand=-1):
+    """The step of a plain launch: 1 placed by hand (default), 0 compiler-scheduled, -1 queries.  Returns the previous value
+    (tests, interleaved A/B measurements); lnP is bit-identical either way."""
+    prev = load().linna_serve_plain_sched(int(hand))
     if prev < 0:
         check(prev)
     return prev

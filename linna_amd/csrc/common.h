@@ -393,6 +393,9 @@ int net_stream_describe(NsKind kind, const linna_layer_t* layers, int nl, int in
 // (ns_program_plain, net_program.hip: host-side planning only).  net_stream_launch_plain_ok: whether a launch of that program
 // with this output map and these outputs takes it when the switch is on.
 int net_stream_serve_plain(int on);
+// The step of a plain launch: 1 (default) net_stream_placed_kernel, the step placed by hand; 0 net_stream_plain_kernel, the
+// compiler-scheduled one (same lnP bit for bit; interleaved A/B); -1 queries; returns the previous value.
+int net_stream_serve_plain_sched(int hand);
 bool net_stream_program_plain(NsKind kind, const linna_layer_t* layers, int nl, int in_size, const NsDense* dn, int rows);
 bool net_stream_launch_plain_ok(bool cscale, bool cshift, bool w, bool cexp, bool lnP, bool D, bool TH, bool gate);
 // What always travels together into the launchers of the whole-network kernel: plain records, copied field by field into

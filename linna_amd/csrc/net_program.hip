@@ -496,6 +496,8 @@ bool net_stream_launch_plain_ok(bool cscale, bool cshift, bool w, bool cexp, boo
 }
 static std::atomic<int> g_serve_plain{1};
 int net_stream_serve_plain(int on) { return on < 0 ? g_serve_plain.load() : g_serve_plain.exchange(on ? 1 : 0); }
+static std::atomic<int> g_serve_plain_sched{1};
+int net_stream_serve_plain_sched(int hand) { return hand < 0 ? g_serve_plain_sched.load() : g_serve_plain_sched.exchange(hand ? 1 : 0); }
 
 int ns_seg_cols(const NsProgram& p, const linna_layer_t* layers, int i) {
     const linna_layer_t& l = layers[p.seg_op[i]];

@@ -352,6 +352,23 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_plain_kernel(NsArgs 
     constexpr bool GRAD = false, BF = false, EPS = false, PLAIN = true, WOUT = false;
 #include "net_stream_body.inc"
 }
+// The plain instantiation with its step placed by hand (net_stream_body.inc, HAND): the sixteen MFMAs, four refill loads, the
+// A read and the counted waits of a step as one block of assembly text, at most one filler per MFMA gap, the stream address
+// advanced on the scalar unit.  Prologue, run ends and finish are the compiled text of the kernel above; same MFMAs on the
+// same fragments in the same order, so lnP is bit-identical to both.  The default of a plain launch;
+// linna_serve_plain_sched(0) keeps net_stream_plain_kernel, whose instructions this kernel's existence does not change.  (A
+// kernel of its own name rather than a flag of the one above: that one's symbol is part of what the host tests pin.)
+#if NS_R == 6
+#define NS_HAVE_PLACED 1
+template <int R>
+__global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_placed_kernel(NsArgs a) {
+    constexpr int MOVE = 0, STORE = 0, ROWS = 16;
+    constexpr bool GRAD = false, BF = false, EPS = false, PLAIN = true, WOUT = false;
+#define NS_BODY_HAND
+#include "net_stream_body.inc"
+#undef NS_BODY_HAND
+}
+#endif
 template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF>
 __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_train_bf16_kernel(NsArgs a) {
     static_assert(BF && GRAD && STORE == 3 && ROWS == 4 && MOVE == 0, "the bf16 training step only");
@@ -474,6 +491,10 @@ static int ns_launch_kernel(const NsArgs& a0, int B, const NsProgram& p, int row
     const NsArgs& a = a0;
 #endif
     if constexpr (MOVE == 0 && !GRAD && STORE == 0 && !BF && !EPS) {
+#ifdef NS_HAVE_PLACED
+        if (plain && rows == 16 && net_stream_serve_plain_sched(-1))      // the hand-placed step, unless linna_serve_plain_sched(0)
+            return ns_launch<net_stream_placed_kernel<NS_R>>(a, (B + 15) / 16, lds, s, "net_stream plain launch (hand-placed step)");
+#endif
         if (plain && rows == 16) return ns_launch<net_stream_plain_kernel<NS_R>>(a, (B + 15) / 16, lds, s, "net_stream plain launch");
     }
     if constexpr (MOVE == 0 && GRAD && STORE == 2 && !BF) {     // wide: more than 64 outputs (net_stream_wide_kernel; the caller has checked the engine)

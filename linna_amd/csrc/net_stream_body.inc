@@ -1,5 +1,5 @@
 // The body of the whole-network kernels (net_stream.hip: net_stream_kernel, net_stream_train_bf16_kernel,
-// net_stream_slice_bf16_kernel, net_stream_grad_bf16_kernel, the EPS / PLAIN / WOUT instantiations), included
+// net_stream_slice_bf16_kernel, net_stream_grad_bf16_kernel, the EPS / PLAIN / WOUT instantiations, net_stream_placed_kernel), included
 // inside each kernel's braces; its template parameters R, MOVE, GRAD, STORE, ROWS, BF, its compile-time flags EPS, PLAIN and
 // WOUT, and its argument NsArgs a are theirs.
     constexpr int NT = NS_NT, NW = NS_NW;
@@ -33,6 +33,25 @@
     // gate loads are not what its run ends wait for, the ballots and bit writes of every forward epilogue are extra) -- off.
     constexpr bool LB = G2;
     constexpr bool LATE_REFILL = true;             // see `step`
+    // HAND: the step of the plain serving launch with every instruction placed by hand (net_stream_placed_kernel alone
+    // defines NS_BODY_HAND around the include; described at `step`).  The ring, both A fragments and the accumulators then
+    // live in FIXED registers -- the asm text names single registers of them -- and are in/out operands of every block.
+#ifdef NS_BODY_HAND
+    constexpr bool HAND = true;
+    static_assert(PLAIN && !BF && ROWS == 16 && R == 6 && NS_NT == 4 && LATE_REFILL, "the hand-placed step: plain fp32 serving, 16 rows, six slots");
+#else
+    constexpr bool HAND = false;
+#endif
+    // slot u, tile t: v[128 + 16 u + 4 t ..]; A fragment i: v[224 + 4 i ..]; accumulator t: v[232 + 4 t ..]
+#define NS_HAND_RING \
+    "+{v[128:131]}"(Bq[0][0]), "+{v[132:135]}"(Bq[0][1]), "+{v[136:139]}"(Bq[0][2]), "+{v[140:143]}"(Bq[0][3]), \
+    "+{v[144:147]}"(Bq[1][0]), "+{v[148:151]}"(Bq[1][1]), "+{v[152:155]}"(Bq[1][2]), "+{v[156:159]}"(Bq[1][3]), \
+    "+{v[160:163]}"(Bq[2][0]), "+{v[164:167]}"(Bq[2][1]), "+{v[168:171]}"(Bq[2][2]), "+{v[172:175]}"(Bq[2][3]), \
+    "+{v[176:179]}"(Bq[3][0]), "+{v[180:183]}"(Bq[3][1]), "+{v[184:187]}"(Bq[3][2]), "+{v[188:191]}"(Bq[3][3]), \
+    "+{v[192:195]}"(Bq[4][0]), "+{v[196:199]}"(Bq[4][1]), "+{v[200:203]}"(Bq[4][2]), "+{v[204:207]}"(Bq[4][3]), \
+    "+{v[208:211]}"(Bq[5][0]), "+{v[212:215]}"(Bq[5][1]), "+{v[216:219]}"(Bq[5][2]), "+{v[220:223]}"(Bq[5][3])
+#define NS_HAND_A "+{v[224:227]}"(Aq[0][0]), "+{v[228:231]}"(Aq[1][0])
+#define NS_HAND_ACC "+{v[232:235]}"(acc[0]), "+{v[236:239]}"(acc[1]), "+{v[240:243]}"(acc[2]), "+{v[244:247]}"(acc[3])
     // Non-finite inputs.  Serving and the one-launch gradient poison the row's prior term where x is formed (`zz` in the
     // prologue): lnP = NaN -> -inf whatever the layers make of the row, at no instruction in the layer loop -- their ReLU
     // stays fmaxf, which returns 0 on a NaN.  The forward with stored activations (STORE == 1) has no prior term: its rows
@@ -422,6 +441,15 @@
     asm volatile("" ::: "memory");
     NS_STAMP();
 
+    if constexpr (HAND) {
+        // From here on the compiler sees no vector-memory instruction and counts none: every later wait for the ring is
+        // written out in the step's text.  The prologue's own loads (compiled C++) are waited for HERE, once, outside the
+        // loop -- as operands of the first step they would put a compiler-made vmcnt(0) at the loop's head.  They were
+        // requested in front of the bias copy and the barrier, a thousand cycles and more ago.
+#pragma unroll
+        for (int t = 0; t < NT; ++t) Bq[R - 1][t] = f32x4{0.f, 0.f, 0.f, 0.f};      // (the slot the first step refills)
+        asm volatile("" : NS_HAND_RING :: "memory");
+    }
     // ---- 4. the step loop
     const uint32_t act_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)act;
     f32x4 acc[NACC];
@@ -439,6 +467,10 @@
     uint32_t ap;
     // BFT: the run of segment nseg_f - 1 (the loss segment) is fp32, 16 k per step: one fragment, 64 bytes per step
     auto a_read = [&](f32x4* dst) {
+        if constexpr (HAND) {                      // straight into the fragment's fixed registers: no copy of a value still in flight
+            if (dst == Aq[0]) asm volatile("ds_read_b128 %0, %1" : "={v[224:227]}"(Aq[0][0]) : "v"(ap) : "memory");
+            else asm volatile("ds_read_b128 %0, %1" : "={v[228:231]}"(Aq[1][0]) : "v"(ap) : "memory");
+        } else
         asm volatile("ds_read_b128 %0, %1" : "=v"(dst[0]) : "v"(ap) : "memory");
         if constexpr (BF) asm volatile("ds_read_b128 %0, %1 offset:16" : "=v"(dst[1]) : "v"(ap) : "memory");
         if constexpr (BFT) ap += si == a.nseg_f - 1 ? 64 : 64 * AK;
@@ -491,6 +523,9 @@
         if constexpr (BFT) {
             if (si == a.nseg_f - 1) ap -= 4u * (uint32_t)(ak / 2);     // the fp32 loss run: 4 k per lane and step, not 8
         }
+        // HAND: the run's first MFMAs sit in asm text, where the compiler's hazard recogniser pads nothing: the wait states
+        // between the vector writes of the accumulators above and an MFMA that reads them are spent here
+        if constexpr (HAND) asm volatile("s_nop 3" : NS_HAND_ACC);
     };
     auto lds_barrier = [&]() {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -515,6 +550,75 @@
         // steps are in flight instead of R).  Not in the merged training launch: its register allocation does not survive
         // the longer slot lifetimes (2.3 KB of scratch per lane, +40 % on the step).
         constexpr int RU = LATE_REFILL ? (U + R - 1) % R : U;
+        if constexpr (HAND) {
+            // The same step -- the same sixteen MFMAs on the same fragments in the same order, the same four loads from the
+            // same addresses into the slot the previous step consumed, the same A read -- as ONE block of text, at most one
+            // vector-issue filler per MFMA gap: the A read behind the first MFMA, one refill load behind the third, fifth,
+            // seventh and ninth, the A pointer's add behind the eleventh, and each counted wait directly in front of the first
+            // MFMA that reads its tile.  An MFMA holds the SIMD's vector issue for 8 of its 32 cycles; the compiled step of the
+            // plain instantiation issues the four loads as one block behind its twelfth MFMA, an s_nop 7 in front of them, and
+            // pads in front of loads spread from C++ (NOTES 3.1b R3, "Hand-placed step").  The wave's stream address is an SGPR pair (base + the step's offset, advanced on the scalar
+            // unit between the blocks), the lane's 16 bytes a constant VGPR, the tile the immediate: no vector add for it.
+            // vmcnt: 5 slots = 20 loads are in flight at the start of every step, the oldest four this step's (the
+            // prologue requests R - 1 slots, every step of the main loop refills one -- past the end the last one again --
+            // and tail step U, which refills nothing, starts with 20 - 4 U).  Tile t with j refills of this step issued:
+            // all but the youngest 19 - t + j.
+            // Hazards the text owns: the first load reads the SGPR pair seven instructions into the block (five wait states
+            // after a scalar write); the accumulators' vector writes and reads are kept away from the MFMAs by the s_nop of
+            // begin_run and of the run end below.
+            constexpr int BU = 128 + 16 * U, BR = 128 + 16 * RU, AC = 224 + 4 * (U & 1), AN = 224 + 4 * ((U + 1) & 1);
+            constexpr int TW = refill ? 0 : 4 * U;       // loads a tail step does not find in flight
+#define NS_HM(t, s) "v_mfma_f32_16x16x4_f32 v[232+4*" #t ":235+4*" #t "], v[%[ac]+" #s "], v[%[bu]+4*" #t "+" #s "], v[232+4*" #t ":235+4*" #t "]\n\t"
+#define NS_HL(t, off) "global_load_dwordx4 v[%[ru]+4*" #t ":%[ru]+4*" #t "+3], %[vo], %[sb] offset:" #off "\n\t"
+#define NS_HAND_TEXT(HEAD, L0, L1, L2, L3) HEAD \
+            "s_waitcnt lgkmcnt(0)\n\t" \
+            "s_waitcnt vmcnt(%[w0])\n\t" \
+            NS_HM(0, 0) "ds_read_b128 v[%[an]:%[an]+3], %[ap]\n\t" \
+            "s_waitcnt vmcnt(%[w1])\n\t" \
+            NS_HM(1, 0) \
+            NS_HM(0, 1) L0 \
+            NS_HM(1, 1) \
+            NS_HM(0, 2) L1 \
+            NS_HM(1, 2) \
+            NS_HM(0, 3) L2 \
+            NS_HM(1, 3) \
+            "s_waitcnt vmcnt(%[w2])\n\t" \
+            NS_HM(2, 0) L3 \
+            "s_waitcnt vmcnt(%[w3])\n\t" \
+            NS_HM(3, 0) \
+            NS_HM(2, 1) "v_add_u32 %[ap], 64, %[ap]\n\t" \
+            NS_HM(3, 1) NS_HM(2, 2) NS_HM(3, 2) NS_HM(2, 3) NS_HM(3, 3)
+            if constexpr (refill) {
+                const char* const sb = wbase + woff;
+                // the loop's head is 8-byte aligned: hand-written streams are sensitive to a 4-byte phase of their code
+                // (-DNS_HAND_PHASE4, a diagnostic build: the same stream 4 bytes on -- NOTES has both)
+#ifdef NS_HAND_PHASE4
+#define NS_HAND_HEAD ".p2align 3\n\ts_nop 0\n\t"
+#else
+#define NS_HAND_HEAD ".p2align 3\n\t"
+#endif
+                if constexpr (U == 0)
+                    asm volatile(NS_HAND_TEXT(NS_HAND_HEAD, NS_HL(0, 0), NS_HL(1, 1024), NS_HL(2, 2048), NS_HL(3, 3072))
+                                 : NS_HAND_RING, NS_HAND_A, NS_HAND_ACC, [ap] "+v"(ap)
+                                 : [vo] "v"(voff), [sb] "s"(sb), [bu] "n"(BU), [ru] "n"(BR), [ac] "n"(AC), [an] "n"(AN),
+                                   [w0] "n"(19), [w1] "n"(18), [w2] "n"(20), [w3] "n"(20) : "memory");
+                else
+                    asm volatile(NS_HAND_TEXT("", NS_HL(0, 0), NS_HL(1, 1024), NS_HL(2, 2048), NS_HL(3, 3072))
+                                 : NS_HAND_RING, NS_HAND_A, NS_HAND_ACC, [ap] "+v"(ap)
+                                 : [vo] "v"(voff), [sb] "s"(sb), [bu] "n"(BU), [ru] "n"(BR), [ac] "n"(AC), [an] "n"(AN),
+                                   [w0] "n"(19), [w1] "n"(18), [w2] "n"(20), [w3] "n"(20) : "memory");
+                wadvance();
+            } else {
+                asm volatile(NS_HAND_TEXT("", "", "", "", "")
+                             : NS_HAND_RING, NS_HAND_A, NS_HAND_ACC, [ap] "+v"(ap)
+                             : [bu] "n"(BU), [ac] "n"(AC), [an] "n"(AN),
+                               [w0] "n"(19 - TW), [w1] "n"(18 - TW), [w2] "n"(17 - TW), [w3] "n"(16 - TW) : "memory");
+            }
+#undef NS_HAND_TEXT
+#undef NS_HAND_HEAD
+#undef NS_HL
+#undef NS_HM
+        } else {
         if constexpr (BF) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(Aq[U & 1][0]), "+v"(Aq[U & 1][AK - 1]) :: "memory");
         else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(Aq[U & 1][0]) :: "memory");
         a_read(Aq[(U + 1) & 1]);                   // next step's A (speculative at a run end)
@@ -603,7 +707,12 @@
             }
         }
         if constexpr (refill) wadvance();
+        }
         if (--kleft == 0) {
+            // HAND: the run's last MFMA left the text above a few scalar instructions ago, and the compiler's hazard
+            // recogniser has not seen it: sixteen wait states (eleven are required behind this 8-pass MFMA) before the
+            // epilogue's vector instructions and LDS writes read the accumulators
+            if constexpr (HAND) asm volatile("s_nop 15" : NS_HAND_ACC);
             // ---- end of run (si, pass).  The next segment's descriptor is requested first.  (Meant to hide under the
             // epilogue stores and the barrier; in the compiled code it does not: the descriptor's first use -- NX.type, for the
             // SIDE prefetch -- waits for it at once, ~500 cycles of scalar-cache miss per run end.  PLAIN requests it a run
@@ -1328,7 +1437,13 @@
                 a.TH[(size_t)(row0 + pr) * a.ldt + c] = ns_prior_theta(a.Z[(size_t)grow * a.ldz + c], a.is_flat[c], a.a1[c], a.a2[c]);
         }
     }
+    // HAND: the last refills (the stream's last step again, never used) may still be on their way into the ring, and the
+    // compiler knows of no load: the ring stays an operand to the end, so that the finish above was given none of its registers
+    if constexpr (HAND) asm volatile("" : NS_HAND_RING);
     NS_STAMP();
     NS_STAMPS_FLUSH();
 #undef NS_STAMP
 #undef NS_STAMPS_FLUSH
+#undef NS_HAND_RING
+#undef NS_HAND_A
+#undef NS_HAND_ACC

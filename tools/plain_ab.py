@@ -1,10 +1,13 @@
 #!/usr/bin/env python
-"""A/B of the plain against the generic instantiation of the serving kernel on the bench's headline (33 -> 512 x 4 -> 33,
-4096 walkers, fp32), INTERLEAVED IN ONE PROCESS through linna_serve_plain -- the first configuration timed in a process
-reads slow (NOTES), so the two alternate: sample = HIP events around N back-to-back launches, after a 0.5 s clock ramp.
+"""A/B of the three instantiations of the serving kernel a plain launch can take on the bench's headline (33 -> 512 x 4 -> 33,
+4096 walkers, fp32): the plain one with the step placed by hand ("hand", the default), the plain one with the
+compiler-scheduled step ("plain", linna_serve_plain_sched(0)) and the generic one ("generic", linna_serve_plain(0)),
+INTERLEAVED IN ONE PROCESS -- the first configuration timed in a process reads slow (NOTES), so they alternate, the order
+rotating from round to round: sample = HIP events around N back-to-back launches, after a 0.5 s clock ramp.
 Usage: python tools/plain_ab.py [samples=9] [launches=2000] [out.json]
-Prints the samples, medians, p10-p90 spreads and the verdict of the project's criterion: the plain median must beat the
-generic median by more than twice the generic samples' p10-p90 spread."""
+Prints the samples, medians, p10-p90 spreads and the verdict of the project's criterion for each step: the faster median
+must beat the baseline's median by more than twice the baseline samples' p10-p90 spread (hand against plain, plain against
+generic)."""
 import json, os, sys, time
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,13 +20,21 @@ nl = int(sys.argv[2]) if len(sys.argv) > 2 else 2000
 lp, model, consts = bench.build_problem(torch.device("cuda", 0))
 z = torch.as_tensor(np.random.RandomState(100).standard_normal((bench.NWALKERS, bench.NIN)).astype(np.float32), device="cuda")
 out = torch.empty(bench.NWALKERS, dtype=torch.float32, device="cuda")
+VARIANTS = {"hand": (1, 1), "plain": (1, 0), "generic": (0, 1)}      # (linna_serve_plain, linna_serve_plain_sched)
+
+
+def select(v):
+    _lib.serve_plain(VARIANTS[v][0])
+    _lib.serve_plain_sched(VARIANTS[v][1])
+
+
 res = {}
-for on in (1, 0):                               # both instantiations launched once, results compared
-    _lib.serve_plain(on)
-    assert lp.serves_plain(bench.NWALKERS) == bool(on)
+for v in VARIANTS:                              # every instantiation launched once, results compared
+    select(v)
+    assert lp.serves_plain(bench.NWALKERS) == bool(VARIANTS[v][0])
     lp.evaluate(z, out=out)
-    res[on] = out.cpu().numpy().copy()
-assert np.array_equal(res[0], res[1]), "plain and generic lnP differ"
+    res[v] = out.cpu().numpy().copy()
+assert np.array_equal(res["hand"], res["plain"]) and np.array_equal(res["plain"], res["generic"]), "lnP differs between the instantiations"
 t_ramp = time.perf_counter() + 0.5
 while time.perf_counter() < t_ramp:
     for _ in range(64):
@@ -31,8 +42,8 @@ while time.perf_counter() < t_ramp:
     torch.cuda.synchronize()
 
 
-def sample(on):
-    _lib.serve_plain(on)
+def sample(v):
+    select(v)
     for _ in range(50):
         lp.evaluate(z, out=out)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -44,22 +55,26 @@ def sample(on):
     return e0.elapsed_time(e1) * 1e3 / nl      # us per launch
 
 
-sample(1); sample(0)                            # one untimed round of each
-us = {1: [], 0: []}
+names = list(VARIANTS)
+for v in names:                                 # one untimed round of each
+    sample(v)
+us = {v: [] for v in names}
 for i in range(nsamp):
-    for on in ((1, 0) if i % 2 == 0 else (0, 1)):
-        us[on].append(sample(on))
-_lib.serve_plain(1)
+    for v in names[i % 3:] + names[:i % 3]:
+        us[v].append(sample(v))
+select("hand")
 med = {k: float(np.median(v)) for k, v in us.items()}
 spread = {k: float(np.percentile(v, 90) - np.percentile(v, 10)) for k, v in us.items()}
-gain = med[0] - med[1]
-r = {"launches_per_sample": nl, "plain_us": us[1], "generic_us": us[0], "plain_median_us": med[1], "generic_median_us": med[0],
-     "plain_p10_p90_us": spread[1], "generic_p10_p90_us": spread[0], "gain_us": gain, "gain_percent": 100 * gain / med[0],
-     "clearly_faster": bool(gain > 2 * spread[0]), "bit_identical": True}
-print("generic us/launch: " + " ".join("%.2f" % v for v in us[0]))
-print("plain   us/launch: " + " ".join("%.2f" % v for v in us[1]))
-print("median generic %.2f (p10-p90 %.2f)  plain %.2f (p10-p90 %.2f)  gain %.2f us = %.2f %%  clearly faster: %s" % (
-    med[0], spread[0], med[1], spread[1], gain, r["gain_percent"], r["clearly_faster"]))
+r = {"launches_per_sample": nl, "bit_identical": True}
+for v in names:
+    r[v + "_us"] = us[v]; r[v + "_median_us"] = med[v]; r[v + "_p10_p90_us"] = spread[v]
+    print("%-7s us/launch: " % v + " ".join("%.2f" % x for x in us[v]))
+for new, base in (("hand", "plain"), ("plain", "generic")):
+    gain = med[base] - med[new]
+    ok = bool(gain > 2 * spread[base])
+    r["%s_vs_%s" % (new, base)] = {"gain_us": gain, "gain_percent": 100 * gain / med[base], "clearly_faster": ok}
+    print("%s %.2f (p10-p90 %.2f) against %s %.2f (p10-p90 %.2f): gain %.2f us = %.2f %%  clearly faster: %s" % (
+        new, med[new], spread[new], base, med[base], spread[base], gain, 100 * gain / med[base], ok))
 if len(sys.argv) > 3:
     os.makedirs(os.path.dirname(os.path.abspath(sys.argv[3])), exist_ok=True)
     json.dump(r, open(sys.argv[3], "w"), indent=1)
