@@ -994,80 +994,115 @@ static int lp_refresh_stream(linna_logprob* lp, int B, void* stream, const float
     return stream_copy_refresh(lp->bf16() ? lp->packed_bf : lp->packed, lp->net, *rows, stream, packed, lp->kind(),
                                lp->kind() == NS_SERVE_DENSE ? &dn : nullptr);
 }
+// THE output-map predicate: the map is complete (the exp map, cexp, has both halves) and, `with_likelihood`, this covariance
+// rides in the launch (diagonal, or the last segment of a dense-fused stream).  0: no; 1: yes, the affine map; 2: yes, the exp map
+static int lp_outmap_rides(const linna_logprob* lp, bool with_likelihood) {
+    const linna_logprob_desc_t& d = lp->d;
+    if (d.outmap.cexp && (!d.outmap.cpost || !d.outmap.cshift2)) return 0;
+    if (with_likelihood && !d.w && !lp->dense_fused) return 0;
+    return d.outmap.cexp ? 2 : 1;
+}
 // The descriptor's prior map and input transform, and its output map and diagonal likelihood, as the launchers take them.
 // The dense program carries the output map and the covariance in its stream: it gets none of the latter; the second half
-// of the exp output map is passed only when the map has one (cexp).
+// of the exp output map is passed only when the map has one.
 static NsInput lp_input(const linna_logprob_desc_t& d) { return NsInput{d.nin, d.is_flat, d.a1, d.a2, d.log10_flag, d.xmean, d.xstd}; }
 static NsOutput lp_output(const linna_logprob* lp) {
     const linna_logprob_desc_t& d = lp->d;
     if (lp->kind() == NS_SERVE_DENSE) return NsOutput{nullptr, nullptr, nullptr, nullptr, nullptr, d.temperature};
-    return NsOutput{d.outmap.cscale, d.outmap.cshift, d.outmap.cexp ? d.outmap.cpost : nullptr, d.outmap.cexp ? d.outmap.cshift2 : nullptr,
-                    d.w, d.temperature};
+    const bool ex = lp_outmap_rides(lp, false) == 2;
+    return NsOutput{d.outmap.cscale, d.outmap.cshift, ex ? d.outmap.cpost : nullptr, ex ? d.outmap.cshift2 : nullptr, d.w, d.temperature};
 }
-// What the entries vary in a serving launch: the rows Z[B][ldz], lnP[B], the device gate (linna_logprob_eval_if), the
-// physical parameters TH and the residuals D (null: not written)
-struct LpRun { const float* Z; int ldz; int B; float* lnP; const int* gate = nullptr; float* TH = nullptr; int ldt = 0; float* D = nullptr; int ldd = 0; };
 // One launch of the serving program on the copy for `rows`, around a sampler move `mv` or with the fused gradient `gr` (or null)
-static int lp_launch(const linna_logprob* lp, const float* packed, int rows, const LpRun& r, const NsMove* mv, const NsGrad* gr, void* stream) {
+static int lp_launch(const linna_logprob* lp, const float* packed, int rows, const NsRun& r, const NsMove* mv, const NsGrad* gr, void* stream) {
     const NsDense dn = lp->dense();
-    return launch_net_stream(lp->kind(), net_layers(lp->net, lp->kind()), packed, r.Z, r.ldz, r.B, lp_input(lp->d), lp_output(lp), r.lnP, r.D,
-                             r.ldd, r.TH, r.ldt, mv, gr, r.gate, rows, lp->kind() == NS_SERVE_DENSE ? &dn : nullptr, S(stream));
+    return launch_net_stream(lp->kind(), net_layers(lp->net, lp->kind()), packed, r, lp_input(lp->d), lp_output(lp), mv, gr, rows,
+                             lp->kind() == NS_SERVE_DENSE ? &dn : nullptr, S(stream));
 }
+// the serving stream of this handle's precision is there and switched on
+static bool lp_stream_on(const linna_logprob* lp) { return lp->fused_on && (lp->bf16() ? lp->packed_bf.ready() : lp->packed.ready()); }
 // Whether this log-probability runs the whole-network kernel around a sampler move (a bf16 handle runs the bf16 stream or
 // nothing: where this refuses, the caller's fallback evaluates in bf16 too)
-static bool lp_runs_fused_move(const linna_logprob* lp) {
-    const linna_logprob_desc_t& d = lp->d;
-    return lp->fused_on && (lp->bf16() ? lp->packed_bf.ready() : lp->packed.ready()) &&
-           !(d.outmap.cexp && (!d.w || !d.outmap.cpost || !d.outmap.cshift2)) && (d.w || lp->dense_fused) && d.nin <= 64;
-}
+static bool lp_runs_fused_move(const linna_logprob* lp) { return lp_stream_on(lp) && lp_outmap_rides(lp, true) && lp->d.nin <= 64; }
 // the likelihood of the residuals in the workspace as launches of their own: diagonal, or the dense row-dot
-static int lp_likelihood(const linna_logprob* lp, const LpRun& r, float* w, const LpLayout& L, void* stream) {
+static int lp_likelihood(const linna_logprob* lp, const NsRun& r, float* w, const LpLayout& L, void* stream) {
     const linna_logprob_desc_t& d = lp->d;
     const int ldd = ld4(d.nout);
     if (d.w) return launch_loglike_diag(w + L.d, ldd, r.B, d.nout, d.w, r.Z, r.ldz, d.nin, d.temperature, r.lnP, S(stream));
     return loglike_dense_impl(w + L.d, ldd, r.B, d.nout, lp->dense(), r.Z, r.ldz, d.nin, d.temperature, w + L.part, r.lnP, stream);
 }
 
-// lnP (and TH) of the rows `r` in the workspace w laid out as L: one launch, or -- `keep_activations`, or no such program --
-// prior map, the network's forward and the likelihood as launches of their own
-// Whether an fp32 evaluation runs the whole-network kernel (lp_forward and linna_logprob_serve_plain ask the same question)
-static bool lp_serves_fused(const linna_logprob* lp, bool keep_activations) {
-    const linna_logprob_desc_t& d = lp->d;
-    return !keep_activations && lp->fused_on && lp->packed.ready() && (!d.outmap.cexp || (d.outmap.cpost && d.outmap.cshift2 && !lp->dense_fused));
-}
-// ... and what it launches with when the covariance is not dense-fused: lnP from the launch for a diagonal likelihood, else
-// the residuals into the workspace for a likelihood launch of its own
-static LpRun lp_fused_run(const linna_logprob* lp, const LpRun& r, float* w, const LpLayout& L) {
-    const linna_logprob_desc_t& d = lp->d;
-    return LpRun{r.Z, r.ldz, r.B, d.w ? r.lnP : nullptr, r.gate, r.TH, r.ldt, d.w ? nullptr : w + L.d, ld4(d.nout)};
-}
-static int lp_forward(linna_logprob* lp, const LpRun& r, float* w, const LpLayout& L, void* stream, bool keep_activations) {
-    const linna_logprob_desc_t& d = lp->d;
-    const int ldx = ld4(d.nin), ldd = ld4(d.nout), B = r.B;
+// THE decision of what a call runs through, made once per call: the route, the engine where the route fixes it, for a refusal
+// the code and the text behind the entry's name.  lp_forward and logprob_grad_impl switch on it, the queries read the same record.
+enum LpRoute {
+    LP_REFUSE,
+    LP_EVAL_ONE,        // one whole-network launch, lnP from it (diagonal likelihood, dense-fused, every bf16 evaluation)
+    LP_EVAL_FORWARD,    // the whole-network forward, then a likelihood launch of its own (dense covariance, not dense-fused)
+    LP_EVAL_LAYERED,    // prior map, linna_net_forward, likelihood
+    LP_GRAD_BF16,       // the bf16 one-launch program (packed_gbf)
+    LP_GRAD_MLP,        // the MLP one-launch gradient of the serving stream (grad_fused)
+    LP_GRAD_ANY,        // the any-network one-launch gradient (packed_g2) on the engine `rows`
+    LP_GRAD_LAYERED,    // layered forward, likelihood gradient, linna_net_backward, prior map's derivative
+};
+struct LpRouted { LpRoute route; int rows = 0; int err = LINNA_OK; const char* why = nullptr; };
+// an evaluation; keep_activations: the layered gradient needs the forward's activations in the workspace
+static LpRouted lp_eval_route(const linna_logprob* lp, bool keep_activations) {
     if (lp->bf16()) {
         // bf16 runs the whole-network kernel or nothing: never silently fp32
-        if (keep_activations || !lp->fused_on || !lp->packed_bf.ready() || !d.w || (d.outmap.cexp && (!d.outmap.cpost || !d.outmap.cshift2))) {
-            set_error("logprob: this bf16 log-probability cannot run the whole-network kernel here (LINNA_DISABLE_FUSED, or no diagonal likelihood)");
-            return LINNA_ERR_UNSUPPORTED;
-        }
-        const float* packed = nullptr; int rows = 16;
+        if (!keep_activations && lp_stream_on(lp) && lp->d.w && lp_outmap_rides(lp, true)) return LpRouted{LP_EVAL_ONE};
+        return LpRouted{LP_REFUSE, 0, LINNA_ERR_UNSUPPORTED,
+                        "this bf16 log-probability cannot run the whole-network kernel here (LINNA_DISABLE_FUSED, or no diagonal likelihood)"};
+    }
+    if (keep_activations || !lp_stream_on(lp) || !lp_outmap_rides(lp, false)) return LpRouted{LP_EVAL_LAYERED};
+    return LpRouted{lp_outmap_rides(lp, true) ? LP_EVAL_ONE : LP_EVAL_FORWARD};
+}
+// The engine the fp32 one-launch gradient (packed_g2) takes for B rows: the batch's own (or linna_engine_rows') where the
+// program fits its LDS; 0: it does not -- the layered route, which was measured faster than a smaller engine's two rounds of
+// workgroups (net_stream_grad_fits, net_program.hip)
+static int lp_grad2_rows(const linna_logprob* lp, int B) {
+    const int want = net_stream_rows(B);
+    return lp->g2_fits[want == 16 ? 0 : want == 8 ? 1 : 2] ? want : 0;
+}
+// lnP and its gradient of B rows
+static LpRouted lp_grad_route(const linna_logprob* lp, int B) {
+    const linna_logprob_desc_t& d = lp->d;
+    if (lp->bf16()) {
+        if (lp->grad_precision != LINNA_PRECISION_BF16)
+            return LpRouted{LP_REFUSE, 0, LINNA_ERR_UNSUPPORTED, "this log-probability is set to bf16, which serves lnP only (no bf16 gradient); set it back to fp32"};
+        // the bf16 one-launch program or nothing: never a layered or fp32 form
+        if (lp->fused_on && lp->packed_gbf.ready() && d.w && d.gscale && !d.outmap.cexp) return LpRouted{LP_GRAD_BF16, net_stream_rows(B)};
+        return LpRouted{LP_REFUSE, 0, LINNA_ERR_UNSUPPORTED,
+                        "this bf16 log-probability cannot run its one-launch gradient here (LINNA_DISABLE_FUSED, or no bf16 gradient stream)"};
+    }
+    if (d.outmap.cexp) return LpRouted{LP_REFUSE, 0, LINNA_ERR_UNSUPPORTED, "ypositive (exp) output map has no gradient path"};
+    if (!d.gscale || (!d.w && !d.Ssym)) return LpRouted{LP_REFUSE, 0, LINNA_ERR_INVALID, "descriptor lacks gscale / Ssym"};
+    if (lp_stream_on(lp) && lp->grad_fused && d.w) return LpRouted{LP_GRAD_MLP};
+    const int rows = lp->fused_on && lp->grad2 && lp->packed_g2.ready() && d.w ? lp_grad2_rows(lp, B) : 0;
+    return rows ? LpRouted{LP_GRAD_ANY, rows} : LpRouted{LP_GRAD_LAYERED};
+}
+
+// lnP (and TH) of the rows `r` in the workspace w laid out as L, by the evaluation's route
+static int lp_forward(linna_logprob* lp, const NsRun& r, float* w, const LpLayout& L, void* stream, bool keep_activations) {
+    const linna_logprob_desc_t& d = lp->d;
+    const int ldx = ld4(d.nin), ldd = ld4(d.nout), B = r.B;
+    const LpRouted rt = lp_eval_route(lp, keep_activations);
+    const float* packed = nullptr; int rows = 16;
+    switch (rt.route) {
+    case LP_EVAL_ONE:
+        // whole-network kernel (net_stream.hip): prior map -> every layer -> output transform -> log-likelihood in ONE launch
+        // (dense-fused: the output map is folded into the stream's last layer and the inverse covariance is its last segment)
         TRY(lp_refresh_stream(lp, B, stream, &packed, &rows));
         return lp_launch(lp, packed, rows, r, nullptr, nullptr, stream);
-    }
-    if (lp_serves_fused(lp, keep_activations)) {
-        // whole-network kernel (net_stream.hip): prior map -> every layer -> output transform -> diagonal
-        // log-likelihood in ONE launch, weights streamed from the fragment-order copy
-        const float* packed = nullptr; int rows = 16;
+    case LP_EVAL_FORWARD:
+        // ... the residuals into the workspace instead of lnP, for a likelihood launch of its own
         TRY(lp_refresh_stream(lp, B, stream, &packed, &rows));
-        // dense covariance: the output map is folded into the stream's last layer and the inverse covariance is its last
-        // segment -- lnP comes out of the same launch
-        if (lp->dense_fused) return lp_launch(lp, packed, rows, r, nullptr, nullptr, stream);
-        TRY(lp_launch(lp, packed, rows, lp_fused_run(lp, r, w, L), nullptr, nullptr, stream));
-        return d.w ? LINNA_OK : lp_likelihood(lp, r, w, L, stream);
+        TRY(lp_launch(lp, packed, rows, NsRun{r.Z, r.ldz, B, nullptr, r.gate, r.TH, r.ldt, w + L.d, ldd}, nullptr, nullptr, stream));
+        return lp_likelihood(lp, r, w, L, stream);
+    case LP_EVAL_LAYERED:
+        TRY(launch_prior_map_fwd(r.Z, r.ldz, B, d.nin, d.is_flat, d.a1, d.a2, d.log10_flag, d.xmean, d.xstd, w + L.x0, ldx, r.TH, r.ldt, S(stream)));
+        TRY(linna_net_forward(lp->net, w + L.x0, ldx, B, w + L.fwd, w + L.d, ldd, &d.outmap, stream));
+        return lp_likelihood(lp, r, w, L, stream);
+    default: set_error("logprob: %s", rt.why); return rt.err;
     }
-    TRY(launch_prior_map_fwd(r.Z, r.ldz, B, d.nin, d.is_flat, d.a1, d.a2, d.log10_flag, d.xmean, d.xstd, w + L.x0, ldx, r.TH, r.ldt, S(stream)));
-    TRY(linna_net_forward(lp->net, w + L.x0, ldx, B, w + L.fwd, w + L.d, ldd, &d.outmap, stream));
-    return lp_likelihood(lp, r, w, L, stream);
 }
 
 extern "C" {
@@ -1206,13 +1241,11 @@ int linna_program_plain(const linna_layer_t* layers, int nlayers, int in_size, i
 } LINNA_CATCH_INT
 int linna_logprob_serve_plain(linna_logprob_t* lp, int B, int* out) try {
     if (!lp || !out || B < 1) { set_error("logprob_serve_plain: bad arguments"); return LINNA_ERR_INVALID; }
-    // linna_logprob_eval's own route (lp_forward) with the arguments it would launch with, put to the launcher's own decision
-    static float dummy[4];                                  // (stands for the caller's lnP and workspace: only tested for null)
-    const LpRun r = lp_fused_run(lp, LpRun{dummy, 0, B, dummy}, dummy, LpLayout{});
-    const NsDense dn = lp->dense();
-    *out = !lp->bf16() && lp_serves_fused(lp, false) && !lp->dense_fused &&
-           net_stream_takes_plain(lp->kind(), net_layers(lp->net, lp->kind()), lp_output(lp), r.lnP, r.D, r.TH, nullptr, nullptr, r.gate,
-                                  net_stream_rows(B), lp->kind() == NS_SERVE_DENSE ? &dn : nullptr);
+    // linna_logprob_eval's own route, and for the one launch that ends in lnP the launcher's own decision
+    static float lnP;                                       // (stands for the caller's: only tested for null)
+    *out = lp_eval_route(lp, false).route == LP_EVAL_ONE &&
+           net_stream_takes_plain(lp->kind(), net_layers(lp->net, lp->kind()), lp_output(lp), NsRun{nullptr, 0, B, &lnP}, nullptr, nullptr,
+                                  net_stream_rows(B), nullptr);
     return LINNA_OK;
 } LINNA_CATCH_INT
 int linna_dense_tri(int mode) try {
@@ -1242,13 +1275,13 @@ size_t linna_logprob_ws_bytes(const linna_logprob_t* lp, int B, int with_grad) t
 int linna_logprob_eval(linna_logprob_t* lp, const float* Z, int ldz, int B, void* ws, float* lnP, float* TH, int ldt,
                        void* stream) try {
     if (!lp || !Z || !ws || !lnP || B < 1) { set_error("logprob_eval: bad arguments"); return LINNA_ERR_INVALID; }
-    return lp_forward(lp, LpRun{Z, ldz, B, lnP, nullptr, TH, ldt}, static_cast<float*>(ws), lp_layout(lp, B, 0), stream, false);
+    return lp_forward(lp, NsRun{Z, ldz, B, lnP, nullptr, TH, ldt}, static_cast<float*>(ws), lp_layout(lp, B, 0), stream, false);
 } LINNA_CATCH_INT
 
 int linna_logprob_eval_if(linna_logprob_t* lp, const float* Z, int ldz, int B, void* ws, float* lnP, float* TH, int ldt,
                           const int* gate, void* stream) try {
     if (!lp || !Z || !ws || !lnP || B < 1) { set_error("logprob_eval_if: bad arguments"); return LINNA_ERR_INVALID; }
-    return lp_forward(lp, LpRun{Z, ldz, B, lnP, gate, TH, ldt}, static_cast<float*>(ws), lp_layout(lp, B, 0), stream, false);
+    return lp_forward(lp, NsRun{Z, ldz, B, lnP, gate, TH, ldt}, static_cast<float*>(ws), lp_layout(lp, B, 0), stream, false);
 } LINNA_CATCH_INT
 
 // the first shrinking round behind one stepping-out round: what the evaluation needs to place its own trials (NsArgs::sl_*)
@@ -1278,7 +1311,7 @@ static int lp_eval_slice_points(linna_logprob_t* lp, const SlicePoints& pt, cons
         mv.sl_Z0 = sd->Z0; mv.sl_L = sd->L; mv.sl_R = sd->R; mv.sl_Zt = sd->Ze; mv.sl_m = sd->m; mv.sl_nt = sd->nt;
         mv.sl_seed = sd->seed; mv.sl_step = sd->step_dev; mv.sl_stream = sd->stream_id; mv.sl_flags = sd->flags;
     }
-    return lp_launch(lp, packed, rows, LpRun{pt.DIR, pt.ldd, nrep * pt.ns, lnP, gate}, &mv, nullptr, stream);
+    return lp_launch(lp, packed, rows, NsRun{pt.DIR, pt.ldd, nrep * pt.ns, lnP, gate}, &mv, nullptr, stream);
 }
 int linna_logprob_eval_slice_points(linna_logprob_t* lp, const float* coords, int ldc, int ndim, const int* S_idx, int ns,
                                     const float* DIR, int ldd, const float* w, int nrep, float* lnP, const int* gate,
@@ -1372,7 +1405,7 @@ int linna_stretch_half_step(linna_logprob_t* lp, float* coords, int ldc, int ndi
     const float* packed = nullptr; int rows = 16;
     TRY(lp_refresh_stream(lp, ns, stream, &packed, &rows));
     NsMove mv{coords, ldc, logp, S_idx, ccoords, ldcc, C_idx, nc, seed, step_dev, step_offset, stream_id, a, naccept, 0};
-    return lp_launch(lp, packed, rows, LpRun{nullptr, 0, ns, nullptr}, &mv, nullptr, stream);
+    return lp_launch(lp, packed, rows, NsRun{nullptr, 0, ns, nullptr}, &mv, nullptr, stream);
 } LINNA_CATCH_INT
 
 
@@ -1396,7 +1429,7 @@ int linna_stretch_run(linna_logprob_t* lp, float* coords, int ldc, int ndim, flo
         for (int h = 0; h < 2; ++h) {
             NsMove mv{coords, ldc, logp, sp + h * ns, coords, ldc, sp + (1 - h) * ns, ns, seed, step_dev, step_offset + i, h, a, naccept, 0};
             if (chain) { mv.chain = chain + (size_t)i * nw * ndim; mv.lps = logps + (size_t)i * nw; }
-            TRY(lp_launch(lp, packed, rows, LpRun{nullptr, 0, ns, nullptr}, &mv, nullptr, stream));
+            TRY(lp_launch(lp, packed, rows, NsRun{nullptr, 0, ns, nullptr}, &mv, nullptr, stream));
         }
     }
     return LINNA_OK;
@@ -1447,71 +1480,49 @@ int linna_chain_meanstd(linna_ctx_t*, const float* CT, int ndim, int nwp, int nw
 static NsGrad lp_grad_args(const linna_logprob_desc_t& d, float* G, int ldg, const NsLeap* leap) {
     return NsGrad{d.gscale, G, ldg, leap ? *leap : NsLeap{}};
 }
-// The engine the fp32 one-launch gradient (packed_g2) takes for B rows: the batch's own (or linna_engine_rows') where the
-// program fits its LDS; 0: it does not -- the layered route, which was measured faster than a smaller engine's two rounds of
-// workgroups (net_stream_grad_fits, net_program.hip)
-static int lp_grad2_rows(const linna_logprob* lp, int B) {
-    const int want = net_stream_rows(B);
-    return lp->g2_fits[want == 16 ? 0 : want == 8 ? 1 : 2] ? want : 0;
-}
-// Whether lnP and its gradient of B rows are ONE launch (logprob_grad_impl's own decision, and linna_logprob_grad_launches')
-static bool lp_grad_one_launch(const linna_logprob* lp, int B) {
-    if (lp->bf16()) return lp->grad_precision == LINNA_PRECISION_BF16 && lp->fused_on && lp->packed_gbf.ready();
-    if (lp->fused_on && lp->packed.ready() && lp->grad_fused && lp->d.w) return true;
-    return lp->fused_on && lp->grad2 && lp->packed_g2.ready() && lp->d.w && lp_grad2_rows(lp, B) != 0;
-}
 // forward + dX chain down to the input in one launch on the stream copy `sc` (NS_GRAD_INPUT, or its bf16 form)
-static int lp_launch_grad2(linna_logprob* lp, StreamCopy& sc, bool bf, const float* Z, int ldz, int B, float* lnP, const NsGrad& gr, void* stream) {
+static int lp_launch_grad2(linna_logprob* lp, StreamCopy& sc, bool bf, const NsRun& r, const NsGrad& gr, int rows, void* stream) {
     const NsKind kind = bf ? NS_GRAD_INPUT_BF16 : ns_grad_kind(lp->net->L.data(), (int)lp->net->L.size());
-    const int rows = bf ? net_stream_rows(B) : lp_grad2_rows(lp, B);
     const float* packed = nullptr;
     TRY(stream_copy_refresh(sc, lp->net, rows, stream, &packed, kind));
-    return launch_net_stream_grad2(net_layers(lp->net, kind), packed, Z, ldz, B, lp_input(lp->d), lp_output(lp), lnP, gr, rows, S(stream), bf);
+    return launch_net_stream_grad2(net_layers(lp->net, kind), packed, r, lp_input(lp->d), lp_output(lp), gr, rows, S(stream), bf);
 }
-// whether this object has a gradient at all: what logprob_grad_impl refuses before it launches anything (the entries that
-// enqueue other launches in front of the first gradient ask first)
-static int logprob_grad_ready(const linna_logprob_t* lp) {
-    if (lp->bf16() && lp->grad_precision != LINNA_PRECISION_BF16) {
-        set_error("logprob_grad: this log-probability is set to bf16, which serves lnP only (no bf16 gradient); set it back to fp32");
-        return LINNA_ERR_UNSUPPORTED;
-    }
-    const linna_logprob_desc_t& d = lp->d;
-    if (lp->bf16()) {
-        // the bf16 one-launch program or nothing: never a layered or fp32 form
-        if (!lp->fused_on || !lp->packed_gbf.ready() || !d.w || !d.gscale || d.outmap.cexp) {
-            set_error("logprob_grad: this bf16 log-probability cannot run its one-launch gradient here (LINNA_DISABLE_FUSED, or no bf16 gradient stream)");
-            return LINNA_ERR_UNSUPPORTED;
-        }
-        return LINNA_OK;
-    }
-    if (d.outmap.cexp) { set_error("logprob_grad: ypositive (exp) output map has no gradient path"); return LINNA_ERR_UNSUPPORTED; }
-    if (!d.gscale || (!d.w && !d.Ssym)) { set_error("logprob_grad: descriptor lacks gscale / Ssym"); return LINNA_ERR_INVALID; }
-    return LINNA_OK;
+// the gradient's route is a refusal (the entries that enqueue other launches in front of the first gradient ask first: no
+// refusal depends on the batch)
+static int lp_grad_refused(const LpRouted& rt) {
+    if (rt.route != LP_REFUSE) return LINNA_OK;
+    set_error("logprob_grad: %s", rt.why);
+    return rt.err;
 }
+static int logprob_grad_ready(const linna_logprob_t* lp) { return lp_grad_refused(lp_grad_route(lp, 1)); }
 // lnP and its gradient at Z; `leap`: the leapfrog's kick and drift -- in the finish of the one-launch forms, as a launch of
 // its own behind the others
 static int logprob_grad_impl(linna_logprob_t* lp, const float* Z, int ldz, int B, void* ws, float* lnP, float* G, int ldg,
                              const NsLeap* leap, void* stream) {
     if (!lp || !Z || !ws || !lnP || !G || B < 1) { set_error("logprob_grad: bad arguments"); return LINNA_ERR_INVALID; }
-    TRY(logprob_grad_ready(lp));
+    const LpRouted rt = lp_grad_route(lp, B);
+    TRY(lp_grad_refused(rt));
     const linna_logprob_desc_t& d = lp->d;
-    if (lp->bf16()) return lp_launch_grad2(lp, lp->packed_gbf, true, Z, ldz, B, lnP, lp_grad_args(d, G, ldg, leap), stream);
     const NsGrad gr = lp_grad_args(d, G, ldg, leap);
-    if (lp->fused_on && lp->packed.ready() && lp->grad_fused && d.w) {
+    const NsRun r{Z, ldz, B, lnP};
+    switch (rt.route) {
+    case LP_GRAD_BF16: return lp_launch_grad2(lp, lp->packed_gbf, true, r, gr, rt.rows, stream);
+    case LP_GRAD_MLP: {
         // lnP and d lnP / d z in ONE launch: forward segments, turnaround, backward segments over W^T (net_stream.hip)
         const float* packed = nullptr; int rows = 16;
         TRY(lp_refresh_stream(lp, B, stream, &packed, &rows));
-        return lp_launch(lp, packed, rows, LpRun{Z, ldz, B, lnP}, nullptr, &gr, stream);
+        return lp_launch(lp, packed, rows, r, nullptr, &gr, stream);
+    }
+    case LP_GRAD_ANY:
+        // ONE launch for any network: forward segments (the signs the gates need kept as bits in LDS), turnaround, dX chain
+        // down to the input, prior map's derivative (net_stream.hip, GRAD + STORE == 2) -- six launches otherwise
+        return lp_launch_grad2(lp, lp->packed_g2, false, r, gr, rt.rows, stream);
+    default: break;                                         // LP_GRAD_LAYERED, below
     }
     const LpLayout L = lp_layout(lp, B, 1);
     float* w = static_cast<float*>(ws);
     const int ldx = ld4(d.nin), ldd = ld4(d.nout);
-    if (lp->fused_on && lp->grad2 && lp->packed_g2.ready() && d.w && lp_grad2_rows(lp, B) != 0) {
-        // ONE launch for any network: forward segments (the signs the gates need kept as bits in LDS), turnaround, dX chain
-        // down to the input, prior map's derivative (net_stream.hip, GRAD + STORE == 2) -- six launches otherwise
-        return lp_launch_grad2(lp, lp->packed_g2, false, Z, ldz, B, lnP, gr, stream);
-    }
-    TRY(lp_forward(lp, LpRun{Z, ldz, B, lnP}, w, L, stream, true));
+    TRY(lp_forward(lp, r, w, L, stream, true));
     if (d.w) {
         TRY(launch_loglike_diag_grad(w + L.d, ldd, B, d.nout, d.w, d.gscale, d.temperature, w + L.dh, ldd, S(stream)));
     } else {   // dH = -(1/T) * (D Ssym) * gscale
@@ -1535,7 +1546,8 @@ int linna_logprob_grad(linna_logprob_t* lp, const float* Z, int ldz, int B, void
 // Whether that call is ONE launch for B rows under the current linna_engine_rows (host only: logprob_grad_impl's own decision)
 int linna_logprob_grad_launches(linna_logprob_t* lp, int B, int* out) try {
     if (!lp || !out || B < 1) { set_error("logprob_grad_launches: bad arguments"); return LINNA_ERR_INVALID; }
-    *out = lp_grad_one_launch(lp, B) ? 1 : 0;
+    const LpRoute route = lp_grad_route(lp, B).route;
+    *out = route == LP_GRAD_BF16 || route == LP_GRAD_MLP || route == LP_GRAD_ANY ? 1 : 0;
     return LINNA_OK;
 } LINNA_CATCH_INT
 

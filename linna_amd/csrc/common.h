@@ -405,6 +405,9 @@ bool net_stream_launch_plain_ok(bool cscale, bool cshift, bool w, bool cexp, boo
 struct NsNet { const linna_layer_t* layers; int nl, in_size; };
 struct NsInput { int nin; const int* is_flat; const float* a1; const float* a2; const int* lg; const float* xmean; const float* xstd; };
 struct NsOutput { const float* cscale; const float* cshift; const float* cpost; const float* cshift2; const float* w; float T; };
+// What the entries vary in a serving launch: the rows Z[B][ldz], lnP[B], the device gate (linna_logprob_eval_if), the
+// physical parameters TH and the residuals D (null: not written)
+struct NsRun { const float* Z; int ldz; int B; float* lnP; const int* gate = nullptr; float* TH = nullptr; int ldt = 0; float* D = nullptr; int ldd = 0; };
 // Where a training step's activations and their gradients live, per op (api.hip: net_bufs): y its output, t the hidden h
 // of a residual block, x its input and `gate` = x where x went through a ReLU (else null; leading dimension ldx); dprev
 // d/d(op input), dt d/dh of a residual block.
@@ -493,14 +496,13 @@ int net_stream_adamw_args(const linna_layer_t* layers, int nl, int in_size, int 
 int launch_adamw_streams(const AsArgs& a, float* p, const float* g, float* m, float* v, const float* hyper, float b1, float b2,
                          float eps, hipStream_t s, bool bf = false);
 // forward + dX chain down to the input in one launch (NS_GRAD_INPUT, or bf: NS_GRAD_INPUT_BF16; diagonal covariance)
-int launch_net_stream_grad2(const NsNet& net, const float* packed, const float* Z, int ldz, int B, const NsInput& in, const NsOutput& out,
-                            float* lnP, const NsGrad& gr, int rows, hipStream_t s, bool bf = false);
+int launch_net_stream_grad2(const NsNet& net, const float* packed, const NsRun& r, const NsInput& in, const NsOutput& out, const NsGrad& gr,
+                            int rows, hipStream_t s, bool bf = false);
 // a serving launch (kind NS_SERVE, NS_SERVE_DENSE with dn, or NS_SERVE_BF16)
-bool net_stream_takes_plain(NsKind kind, const NsNet& net, const NsOutput& out, const float* lnP, const float* D, const float* TH,
-                            const NsMove* mv, const NsGrad* gr, const int* gate, int rows, const NsDense* dn);   // what launch_net_stream decides
-int launch_net_stream(NsKind kind, const NsNet& net, const float* packed, const float* Z, int ldz, int B, const NsInput& in,
-                      const NsOutput& out, float* lnP, float* D, int ldd, float* TH, int ldt, const NsMove* mv, const NsGrad* gr,
-                      const int* gate, int rows, const NsDense* dn, hipStream_t s);
+bool net_stream_takes_plain(NsKind kind, const NsNet& net, const NsOutput& out, const NsRun& r, const NsMove* mv, const NsGrad* gr, int rows,
+                            const NsDense* dn);   // what launch_net_stream decides
+int launch_net_stream(NsKind kind, const NsNet& net, const float* packed, const NsRun& r, const NsInput& in, const NsOutput& out,
+                      const NsMove* mv, const NsGrad* gr, int rows, const NsDense* dn, hipStream_t s);
 
 // autocorr.hip: convergence statistics of a walker chain (running lagged products, emcee's estimator, checkmeanstd's moments)
 int launch_chain_append_t(const float* block, int ldb, int nsteps, int nw, int ndim, int wstride, float* CT, int nwp,

@@ -458,30 +458,79 @@ int launch_net_stream_pack(NsKind kind, const linna_layer_t* layers, int nl, int
     return check_hip(hipGetLastError(), "net_stream pack launch");
 }
 
-// One launch of the whole-network kernel instantiation `Kernel`: 64 NS_NW threads per workgroup and `lds_bytes` of dynamic
-// LDS, which the instantiation is allowed up to the CU's whole LDS before its first launch.
-template <void (*Kernel)(NsArgs)>
-static int ns_launch(const NsArgs& a, int nblocks, size_t lds_bytes, hipStream_t s, const char* what) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        const int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, NS_LDS_BYTES),
+// ---- one table from launch variant to kernel.  A launcher names WHAT it launches, a variant and its flags; every
+// net_stream*_kernel instantiation of the library is named in this table and nowhere else.  A row: the 16-, 8- and 4-row
+// engines' kernels (null: no such engine -- the plain instantiations are 16-row kernels; the one-launch training step has the
+// 4-row engine only: on the 8-row one it was measured SLOWER than its two halves, batch 1500 at (26,457): 218.5 against 210.9 us
+// per step), the launch's name for the error text, and what the NS_STAMPS diagnostic build lacks it as (null: it has it).
+typedef void (*NsKernel)(NsArgs);
+enum NsVariant { NV_SERVE, NV_STRETCH, NV_SLICE, NV_GRAD_MLP, NV_GRAD2, NV_STORE, NV_DX, NV_TRAIN_FWD, NV_TRAIN_STEP };
+// a bf16 stream; the leapfrog in the finish with a step size per row; more than 64 outputs; the plain MLP's lean serving kernel; ... hand-placed
+enum : unsigned { NF_BF16 = 1, NF_EPS = 2, NF_WIDE = 4, NF_PLAIN = 8, NF_PLACED = 16 };
+struct NsEntry { NsVariant v; unsigned flags; NsKernel k[3]; const char* what; const char* stamps_lacks; bool attr_set[3]; };
+// the three engines of one kernel template: <R, MOVE, GRAD, STORE, rows, BF (, EPS)>
+#define NS_ENGINES(K, MOVE, GRAD, STORE, ...) \
+    {K<NS_R, MOVE, GRAD, STORE, 16, __VA_ARGS__>, K<NS_R, MOVE, GRAD, STORE, 8, __VA_ARGS__>, K<NS_R, MOVE, GRAD, STORE, 4, __VA_ARGS__>}
+static NsEntry ns_table[] = {
+    {NV_SERVE, 0, NS_ENGINES(net_stream_kernel, 0, false, 0, false), "net_stream launch"},
+    {NV_SERVE, NF_BF16, NS_ENGINES(net_stream_kernel, 0, false, 0, true), "net_stream launch"},
+    {NV_SERVE, NF_PLAIN, {net_stream_plain_kernel<NS_R>, nullptr, nullptr}, "net_stream plain launch"},
+#ifdef NS_HAVE_PLACED
+    {NV_SERVE, NF_PLAIN | NF_PLACED, {net_stream_placed_kernel<NS_R>, nullptr, nullptr}, "net_stream plain launch (hand-placed step)"},
+#endif
+    {NV_STRETCH, 0, NS_ENGINES(net_stream_kernel, 1, false, 0, false), "net_stream launch"},
+    {NV_STRETCH, NF_BF16, NS_ENGINES(net_stream_kernel, 1, false, 0, true), "net_stream launch"},
+    {NV_SLICE, 0, NS_ENGINES(net_stream_kernel, 2, false, 0, false), "net_stream launch"},
+    {NV_SLICE, NF_BF16, NS_ENGINES(net_stream_slice_bf16_kernel, 2, false, 0, true), "net_stream bf16 slice launch", "bf16 slice evaluation"},
+    {NV_GRAD_MLP, 0, NS_ENGINES(net_stream_kernel, 0, true, 0, false), "net_stream launch"},
+    {NV_GRAD_MLP, NF_EPS, NS_ENGINES(net_stream_eps_kernel, 0, true, 0, false), "net_stream launch"},
+    {NV_GRAD2, 0, NS_ENGINES(net_stream_kernel, 0, true, 2, false), "net_stream launch"},
+    {NV_GRAD2, NF_EPS, NS_ENGINES(net_stream_eps_kernel, 0, true, 2, false), "net_stream launch"},
+    {NV_GRAD2, NF_WIDE, NS_ENGINES(net_stream_wide_kernel, 0, true, 2, false, false), "net_stream wide-output gradient launch"},
+    {NV_GRAD2, NF_WIDE | NF_EPS, NS_ENGINES(net_stream_wide_kernel, 0, true, 2, false, true), "net_stream wide-output gradient launch"},
+    {NV_GRAD2, NF_BF16, NS_ENGINES(net_stream_grad_bf16_kernel, 0, true, 2, true), "net_stream bf16 gradient launch", "bf16 gradient"},
+    {NV_GRAD2, NF_BF16 | NF_EPS, NS_ENGINES(net_stream_eps_bf16_kernel, 0, true, 2, true), "net_stream bf16 gradient launch", "bf16 gradient"},
+    {NV_STORE, 0, NS_ENGINES(net_stream_kernel, 0, false, 1, false), "net_stream launch"},
+    {NV_DX, 0, NS_ENGINES(net_stream_kernel, 0, false, 2, false), "net_stream launch"},
+    {NV_TRAIN_FWD, 0, NS_ENGINES(net_stream_kernel, 0, false, 3, false), "net_stream launch"},
+    {NV_TRAIN_STEP, 0, {nullptr, nullptr, net_stream_kernel<NS_R, 0, true, 3, 4, false>}, "net_stream launch"},
+    {NV_TRAIN_STEP, NF_BF16, {nullptr, nullptr, net_stream_train_bf16_kernel<NS_R, 0, true, 3, 4, true>}, "net_stream bf16 training launch", "bf16 training step"},
+};
+#undef NS_ENGINES
+// the kernel of (variant, flags) on the engine of `rows` rows: its table row and the engine's slot in it
+static int ns_kernel(NsVariant v, unsigned flags, int rows, NsEntry** entry, int* slot) {
+    for (NsEntry& e : ns_table) {
+        if (e.v != v || e.flags != flags) continue;
+#ifdef NS_STAMPS
+        if (e.stamps_lacks) { set_error("net_stream: the NS_STAMPS build has no %s", e.stamps_lacks); return LINNA_ERR_UNSUPPORTED; }
+#endif
+        const int i = rows == 16 ? 0 : rows == 8 ? 1 : rows == 4 ? 2 : -1;
+        if (i < 0 || !e.k[i]) break;
+        *entry = &e; *slot = i;
+        return LINNA_OK;
+    }
+    set_error("net_stream: %d rows per workgroup", rows);
+    return LINNA_ERR_INVALID;
+}
+// One launch of the whole-network kernel instantiation in slot `i` of table row `e`: 64 NS_NW threads per workgroup and
+// `lds_bytes` of dynamic LDS, which the instantiation is allowed up to the CU's whole LDS before its first launch.
+static int ns_launch(NsEntry& e, int i, const NsArgs& a, int nblocks, size_t lds_bytes, hipStream_t s) {
+    if (!e.attr_set[i]) {
+        const int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(e.k[i]), hipFuncAttributeMaxDynamicSharedMemorySize, NS_LDS_BYTES),
                                  "hipFuncSetAttribute");
         if (rc != LINNA_OK) return rc;
-        attr_set = true;
+        e.attr_set[i] = true;
     }
-    hipLaunchKernelGGL(Kernel, dim3(nblocks), dim3(64 * NS_NW), lds_bytes, s, a);
-    return check_hip(hipGetLastError(), what);
+    hipLaunchKernelGGL(e.k[i], dim3(nblocks), dim3(64 * NS_NW), lds_bytes, s, a);
+    return check_hip(hipGetLastError(), e.what);
 }
-template <int MOVE, bool GRAD, int STORE, int ROWS, bool BF = false, bool EPS = false>
-static int ns_launch_rows(const NsArgs& a, int B, size_t lds_bytes, hipStream_t s, int extra = 0) {
-    if constexpr (EPS) return ns_launch<net_stream_eps_kernel<NS_R, MOVE, GRAD, STORE, ROWS, BF>>(a, (B + ROWS - 1) / ROWS + extra, lds_bytes, s, "net_stream launch");
-    else return ns_launch<net_stream_kernel<NS_R, MOVE, GRAD, STORE, ROWS, BF>>(a, (B + ROWS - 1) / ROWS + extra, lds_bytes, s, "net_stream launch");
-}
-// plain: the PLAIN instantiation (net_stream_plain_kernel; the caller has checked ns_program_plain and the launch's own conditions)
-template <int MOVE, bool GRAD, int STORE = 0, bool BF = false, bool EPS = false>
-static int ns_launch_kernel(const NsArgs& a0, int B, const NsProgram& p, int rows, hipStream_t s, int extra = 0, size_t lds_extra = 0,
-                            bool plain = false, bool wide = false) {
-    const size_t lds = p.lds_for(rows, GRAD) + lds_extra;
+// The launch of program `p` over B rows as (variant, flags) on the engine of `rows` rows: one workgroup per `rows` rows and
+// `extra` more (riders), the program's LDS (with the backward's masks for the variants that run one) and `lds_extra`.
+static int ns_launch_program(NsVariant v, unsigned flags, const NsArgs& a0, int B, const NsProgram& p, int rows, hipStream_t s, int extra = 0,
+                             size_t lds_extra = 0) {
+    NsEntry* e = nullptr; int i = 0;
+    const int rc = ns_kernel(v, flags, rows, &e, &i);
+    if (rc != LINNA_OK) return rc;
 #ifdef NS_STAMPS
     // diagnostic build: every launch writes its phase stamps to the buffer LINNA_FUSED_STAMPS names (tools/ns_stamps*.py)
     NsArgs a = a0;
@@ -490,48 +539,8 @@ static int ns_launch_kernel(const NsArgs& a0, int B, const NsProgram& p, int row
 #else
     const NsArgs& a = a0;
 #endif
-    if constexpr (MOVE == 0 && !GRAD && STORE == 0 && !BF && !EPS) {
-#ifdef NS_HAVE_PLACED
-        if (plain && rows == 16 && net_stream_serve_plain_sched(-1))      // the hand-placed step, unless linna_serve_plain_sched(0)
-            return ns_launch<net_stream_placed_kernel<NS_R>>(a, (B + 15) / 16, lds, s, "net_stream plain launch (hand-placed step)");
-#endif
-        if (plain && rows == 16) return ns_launch<net_stream_plain_kernel<NS_R>>(a, (B + 15) / 16, lds, s, "net_stream plain launch");
-    }
-    if constexpr (MOVE == 0 && GRAD && STORE == 2 && !BF) {     // wide: more than 64 outputs (net_stream_wide_kernel; the caller has checked the engine)
-        const char* const what = "net_stream wide-output gradient launch";
-        if (wide && rows == 4) return ns_launch<net_stream_wide_kernel<NS_R, 0, true, 2, 4, false, EPS>>(a, (B + 3) / 4, lds, s, what);
-        if (wide && rows == 8) return ns_launch<net_stream_wide_kernel<NS_R, 0, true, 2, 8, false, EPS>>(a, (B + 7) / 8, lds, s, what);
-        if (wide && rows == 16) return ns_launch<net_stream_wide_kernel<NS_R, 0, true, 2, 16, false, EPS>>(a, (B + 15) / 16, lds, s, what);
-    }
-    if (rows == 4) return ns_launch_rows<MOVE, GRAD, STORE, 4, BF, EPS>(a, B, lds, s, extra);
-    if constexpr (BF) {
-        if (rows == 8) return ns_launch_rows<MOVE, GRAD, STORE, 8, BF, EPS>(a, B, lds, s, extra);
-        if (rows == 16) return ns_launch_rows<MOVE, GRAD, STORE, 16, BF, EPS>(a, B, lds, s, extra);
-    } else if constexpr (STORE == 3 && GRAD) {
-        // the one-launch training step exists for the 4-row engine only (batches up to 1024 rows; the caller checks): on the
-        // 8-row engine it was measured SLOWER than its two halves (batch 1500 at (26,457): 218.5 against 210.9 us per step)
-    } else {
-        if (rows == 8) return ns_launch_rows<MOVE, GRAD, STORE, 8, false, EPS>(a, B, lds, s, extra);
-        if (rows == 16) return ns_launch_rows<MOVE, GRAD, STORE, 16, false, EPS>(a, B, lds, s, extra);
-    }
-    set_error("net_stream: %d rows per workgroup", rows);
-    return LINNA_ERR_INVALID;
-}
-// the slice evaluation of a bf16 serving program: net_stream_slice_bf16_kernel, one instantiation per engine
-template <int ROWS>
-static int ns_launch_slice_bf16_rows(const NsArgs& a, int B, size_t lds_bytes, hipStream_t s) {
-    return ns_launch<net_stream_slice_bf16_kernel<NS_R, 2, false, 0, ROWS, true>>(a, (B + ROWS - 1) / ROWS, lds_bytes, s, "net_stream bf16 slice launch");
-}
-static int ns_launch_slice_bf16(const NsArgs& a, int B, const NsProgram& p, int rows, hipStream_t s) {
-#ifdef NS_STAMPS
-    set_error("net_stream: the NS_STAMPS build has no bf16 slice evaluation"); return LINNA_ERR_UNSUPPORTED;
-#endif
-    const size_t lds = p.lds_for(rows, false);
-    if (rows == 4) return ns_launch_slice_bf16_rows<4>(a, B, lds, s);
-    if (rows == 8) return ns_launch_slice_bf16_rows<8>(a, B, lds, s);
-    if (rows == 16) return ns_launch_slice_bf16_rows<16>(a, B, lds, s);
-    set_error("net_stream: %d rows per workgroup", rows);
-    return LINNA_ERR_INVALID;
+    const bool grad = v == NV_GRAD_MLP || v == NV_GRAD2 || v == NV_TRAIN_STEP;
+    return ns_launch(*e, i, a, (B + rows - 1) / rows + extra, p.lds_for(rows, grad) + lds_extra, s);
 }
 
 // ------------------------------------------------------------------ AdamW that writes the weight streams itself
@@ -693,6 +702,11 @@ static bool ns_set_gates(NsArgs& a, const NsGates& g, const NsProgram& p, int ro
 static void ns_set_input(NsArgs& a, const NsInput& in) {
     a.is_flat = in.is_flat; a.a1 = in.a1; a.a2 = in.a2; a.lg = in.lg; a.xmean = in.xmean; a.xstd = in.xstd;
 }
+// a launch that takes its rows as they are: the prologue's transform constants are loaded and ignored -- `any` readable array
+// of at least as many entries as the rows have columns stands for all of them
+static void ns_set_input_ignored(NsArgs& a, const float* any) {
+    a.is_flat = reinterpret_cast<const int*>(any); a.a1 = any; a.a2 = any; a.lg = nullptr; a.xmean = any; a.xstd = any;
+}
 static void ns_set_grad(NsArgs& a, const NsGrad& gr) {
     a.gscale = gr.gscale; a.Gout = gr.G; a.ldg = gr.ldg;
     const NsLeap& l = gr.leap;          // the one place that writes NsArgs::hm_*
@@ -701,16 +715,15 @@ static void ns_set_grad(NsArgs& a, const NsGrad& gr) {
 
 // Whether a serving launch with these arguments takes the plain instantiation: the one decision, made here for the launch
 // below and for whoever asks what it would do (linna_logprob_serve_plain).
-bool net_stream_takes_plain(NsKind kind, const NsNet& net, const NsOutput& out, const float* lnP, const float* D, const float* TH,
-                            const NsMove* mv, const NsGrad* gr, const int* gate, int rows, const NsDense* dn) {
+bool net_stream_takes_plain(NsKind kind, const NsNet& net, const NsOutput& out, const NsRun& r, const NsMove* mv, const NsGrad* gr, int rows,
+                            const NsDense* dn) {
     if (kind != NS_SERVE || rows != 16 || mv || gr || dn || !net_stream_serve_plain(-1)) return false;
-    if (!net_stream_launch_plain_ok(out.cscale, out.cshift, out.w, out.cpost, lnP, D, TH, gate)) return false;
+    if (!net_stream_launch_plain_ok(out.cscale, out.cshift, out.w, out.cpost, r.lnP, r.D, r.TH, r.gate)) return false;
     return ns_program_plain(*ns_program(kind, net.layers, net.nl, net.in_size, dn, rows));
 }
 
-int launch_net_stream(NsKind kind, const NsNet& net, const float* packed, const float* Z, int ldz, int B, const NsInput& in,
-                      const NsOutput& out, float* lnP, float* D, int ldd, float* TH, int ldt, const NsMove* mv, const NsGrad* gr,
-                      const int* gate, int rows, const NsDense* dn, hipStream_t s) {
+int launch_net_stream(NsKind kind, const NsNet& net, const float* packed, const NsRun& r, const NsInput& in, const NsOutput& out,
+                      const NsMove* mv, const NsGrad* gr, int rows, const NsDense* dn, hipStream_t s) {
     const bool bf = kind == NS_SERVE_BF16;
     if ((kind == NS_SERVE_DENSE) != (dn != nullptr) || !(kind == NS_SERVE || kind == NS_SERVE_DENSE || bf)) {
         set_error("net_stream: not a serving program"); return LINNA_ERR_INVALID;
@@ -723,14 +736,15 @@ int launch_net_stream(NsKind kind, const NsNet& net, const float* packed, const 
     if (!p.ok) { set_error("net_stream: network not eligible"); return LINNA_ERR_UNSUPPORTED; }
     if (dn && (out.w || gr || out.cscale || out.cshift)) { set_error("net_stream: the dense program carries its own output map and has no fused gradient"); return LINNA_ERR_INVALID; }
     if (mv && (in.nin > 64 || (!out.w && !dn))) { set_error("net_stream: fused sampler moves need <= 64 parameters and a log-likelihood in the launch"); return LINNA_ERR_UNSUPPORTED; }
-    if (gr && (!p.grad_ok || !out.w || !lnP || !gr->gscale || !gr->G || mv)) { set_error("net_stream: no fused gradient for this network / likelihood"); return LINNA_ERR_UNSUPPORTED; }
-    NsArgs a = ns_args(p, packed, Z, ldz, B, in.nin, gr != nullptr);    // forward only: stop after the forward segments
+    if (gr && (!p.grad_ok || !out.w || !r.lnP || !gr->gscale || !gr->G || mv)) { set_error("net_stream: no fused gradient for this network / likelihood"); return LINNA_ERR_UNSUPPORTED; }
+    NsArgs a = ns_args(p, packed, r.Z, r.ldz, r.B, in.nin, gr != nullptr);    // forward only: stop after the forward segments
     ns_set_input(a, in);
     a.cscale = out.cscale; a.cshift = out.cshift; a.w = out.w; a.T = out.T;
     a.cpost = out.cpost; a.cshift2 = out.cshift2;
     a.dense = p.dense ? (dn && dn->factored ? 2 : 1) : 0; a.u_col = p.u_col; a.u_same = p.u_same; a.x0_keep = p.x0_keep;
-    a.lnP = lnP; a.D = D; a.ldd = ldd; a.TH = TH; a.ldt = ldt;
-    a.gate = gate;
+    a.lnP = r.lnP; a.D = r.D; a.ldd = r.ldd; a.TH = r.TH; a.ldt = r.ldt;
+    a.gate = r.gate;
+    const unsigned fbf = bf ? NF_BF16 : 0;
     if (mv) {
         a.mv_coords = mv->coords; a.mv_ldc = mv->ldc; a.mv_logp = mv->logp; a.mv_S = mv->S;
         a.mv_cc = mv->cc; a.mv_ldcc = mv->ldcc; a.mv_C = mv->C; a.mv_nc = mv->nc;
@@ -739,24 +753,22 @@ int launch_net_stream(NsKind kind, const NsNet& net, const float* packed, const 
         a.sl_Z0 = mv->sl_Z0; a.sl_L = mv->sl_L; a.sl_R = mv->sl_R; a.sl_Zt = mv->sl_Zt; a.sl_m = mv->sl_m; a.sl_nt = mv->sl_nt;
         a.sl_seed = mv->sl_seed; a.sl_step = mv->sl_step; a.sl_stream = mv->sl_stream; a.sl_flags = mv->sl_flags;
         if (mv->sb) a.sb = *mv->sb;
-        if (mv->slice) {
-            if (bf) return ns_launch_slice_bf16(a, B, p, rows, s);
-            return ns_launch_kernel<2, false>(a, B, p, rows, s);
-        }
-        if (bf) return ns_launch_kernel<1, false, 0, true>(a, B, p, rows, s);
-        return ns_launch_kernel<1, false>(a, B, p, rows, s);
+        return ns_launch_program(mv->slice ? NV_SLICE : NV_STRETCH, fbf, a, r.B, p, rows, s);
     }
     if (bf && gr) { set_error("net_stream: no bf16 gradient"); return LINNA_ERR_UNSUPPORTED; }
-    if (bf) return ns_launch_kernel<0, false, 0, true>(a, B, p, rows, s);
+    if (bf) return ns_launch_program(NV_SERVE, NF_BF16, a, r.B, p, rows, s);
     if (gr) {
         ns_set_grad(a, *gr);
-        if (a.hm_p && a.hm_eps) return ns_launch_kernel<0, true, 0, false, true>(a, B, p, rows, s);
-        return ns_launch_kernel<0, true>(a, B, p, rows, s);
+        return ns_launch_program(NV_GRAD_MLP, a.hm_p && a.hm_eps ? NF_EPS : 0, a, r.B, p, rows, s);
     }
-    // the plain MLP's serving launch: its own lean instantiation (net_stream_plain_kernel), unless linna_serve_plain(0)
-    const bool plain = net_stream_takes_plain(kind, net, out, lnP, D, TH, mv, gr, gate, rows, dn);
-    if (plain) for (int i = 0; i < a.nseg; ++i) a.seg[i].type |= a.seg[i].ncg_log2 << 8;      // (the eight fields it reads: net_stream_body.inc)
-    return ns_launch_kernel<0, false>(a, B, p, rows, s, 0, 0, plain);
+    // the plain MLP's serving launch: its own lean instantiation (net_stream_plain_kernel), unless linna_serve_plain(0) --
+    // with the step placed by hand (net_stream_placed_kernel) where the build has it, unless linna_serve_plain_sched(0)
+    if (!net_stream_takes_plain(kind, net, out, r, mv, gr, rows, dn)) return ns_launch_program(NV_SERVE, 0, a, r.B, p, rows, s);
+    for (int i = 0; i < a.nseg; ++i) a.seg[i].type |= a.seg[i].ncg_log2 << 8;      // (the eight fields it reads: net_stream_body.inc)
+#ifdef NS_HAVE_PLACED
+    if (net_stream_serve_plain_sched(-1)) return ns_launch_program(NV_SERVE, NF_PLAIN | NF_PLACED, a, r.B, p, rows, s);
+#endif
+    return ns_launch_program(NV_SERVE, NF_PLAIN, a, r.B, p, rows, s);
 }
 
 // Training / validation forward: X[B][ldx] (transformed inputs) -> every op's output (`ops[i].y`, the hidden h of a
@@ -767,11 +779,10 @@ int launch_net_stream_store(const NsNet& net, const float* packed, const float* 
     const NsProgram& p = *pref;
     if (!p.ok) { set_error("net_stream: network not eligible"); return LINNA_ERR_UNSUPPORTED; }
     NsArgs a = ns_args(p, packed, X, ldx, B, net.in_size, false);
-    // the prologue's transform constants are loaded (and ignored): any readable arrays of >= in_size entries
-    a.is_flat = reinterpret_cast<const int*>(X); a.a1 = X; a.a2 = X; a.lg = nullptr; a.xmean = X; a.xstd = X;
+    ns_set_input_ignored(a, X);
     a.cscale = cscale; a.cshift = cshift;                   // column affine of the last output (Y transforms), or null
     ns_store_table(a, p, net, ops, 0, p.nseg_f, false);
-    return ns_launch_kernel<0, false, 1>(a, B, p, rows, s);
+    return ns_launch_program(NV_STORE, 0, a, B, p, rows, s);
 }
 
 
@@ -781,15 +792,15 @@ int launch_net_stream_store(const NsNet& net, const float* packed, const float* 
 // ends of 256 workgroups in step, each read an exposed L2 round trip behind a drained weight ring), the turnaround forms
 // d lnP / d out, the dX chain runs down to the network input gating on those signs, the finish applies the prior map's
 // derivative.  Diagonal covariance.  bf: the same on a bf16 stream (NS_GRAD_INPUT_BF16, net_stream_grad_bf16_kernel).
-int launch_net_stream_grad2(const NsNet& net, const float* packed, const float* Z, int ldz, int B, const NsInput& in, const NsOutput& out,
-                            float* lnP, const NsGrad& gr, int rows, hipStream_t s, bool bf) {
+int launch_net_stream_grad2(const NsNet& net, const float* packed, const NsRun& r, const NsInput& in, const NsOutput& out, const NsGrad& gr,
+                            int rows, hipStream_t s, bool bf) {
     const NsProgramRef pref = ns_program(bf ? NS_GRAD_INPUT_BF16 : ns_grad_kind(net.layers, net.nl), net.layers, net.nl, net.in_size, nullptr, rows);
     const NsProgram& p = *pref;
     if (!p.ok || !p.dxi_ok) { set_error("net_stream: no forward + dX program for this network"); return LINNA_ERR_UNSUPPORTED; }
-    if (!out.w || !lnP || !gr.gscale || !gr.G) { set_error("net_stream: the one-launch gradient needs a diagonal covariance"); return LINNA_ERR_INVALID; }
-    NsArgs a = ns_args(p, packed, Z, ldz, B, in.nin, true);
+    if (!out.w || !r.lnP || !gr.gscale || !gr.G) { set_error("net_stream: the one-launch gradient needs a diagonal covariance"); return LINNA_ERR_INVALID; }
+    NsArgs a = ns_args(p, packed, r.Z, r.ldz, r.B, in.nin, true);
     ns_set_input(a, in);
-    a.cscale = out.cscale; a.cshift = out.cshift; a.w = out.w; a.T = out.T; a.lnP = lnP;     // (no exp output map here)
+    a.cscale = out.cscale; a.cshift = out.cshift; a.w = out.w; a.T = out.T; a.lnP = r.lnP;     // (no exp output map here)
     ns_set_grad(a, gr);
     const NsGates g = ns_gates(p, net.layers, net.nl, rows);
     for (int i = 0; i < (int)p.seg.size(); ++i) if (i >= p.nseg_f || g.gbit[i] >= 0) a.gn[i] = ns_seg_cols(p, net.layers, i);
@@ -798,26 +809,9 @@ int launch_net_stream_grad2(const NsNet& net, const float* packed, const float* 
         set_error(g.ok ? "net_stream: the one-launch gradient's sign bits do not fit the LDS" : "net_stream: a gate of the one-launch gradient has no producer");
         return LINNA_ERR_UNSUPPORTED;
     }
-    if (bf) {
-#ifdef NS_STAMPS
-        set_error("net_stream: the NS_STAMPS build has no bf16 gradient"); return LINNA_ERR_UNSUPPORTED;
-#endif
-        const size_t lds = p.lds_for(rows, true) + lds_extra;
-        const char* const what = "net_stream bf16 gradient launch";
-        if (a.hm_p && a.hm_eps) {
-            if (rows == 4) return ns_launch<net_stream_eps_bf16_kernel<NS_R, 0, true, 2, 4, true>>(a, (B + 3) / 4, lds, s, what);
-            if (rows == 8) return ns_launch<net_stream_eps_bf16_kernel<NS_R, 0, true, 2, 8, true>>(a, (B + 7) / 8, lds, s, what);
-            if (rows == 16) return ns_launch<net_stream_eps_bf16_kernel<NS_R, 0, true, 2, 16, true>>(a, (B + 15) / 16, lds, s, what);
-        }
-        if (rows == 4) return ns_launch<net_stream_grad_bf16_kernel<NS_R, 0, true, 2, 4, true>>(a, (B + 3) / 4, lds, s, what);
-        if (rows == 8) return ns_launch<net_stream_grad_bf16_kernel<NS_R, 0, true, 2, 8, true>>(a, (B + 7) / 8, lds, s, what);
-        if (rows == 16) return ns_launch<net_stream_grad_bf16_kernel<NS_R, 0, true, 2, 16, true>>(a, (B + 15) / 16, lds, s, what);
-        set_error("net_stream: %d rows per workgroup", rows);
-        return LINNA_ERR_INVALID;
-    }
-    const bool wide = p.nout > 64;                          // the turnaround's tail over the columns past its registers
-    if (a.hm_p && a.hm_eps) return ns_launch_kernel<0, true, 2, false, true>(a, B, p, rows, s, 0, lds_extra, false, wide);
-    return ns_launch_kernel<0, true, 2>(a, B, p, rows, s, 0, lds_extra, false, wide);
+    // wide: the turnaround's tail over the columns past its registers (fp32 only: the bf16 program keeps the 64-output limit)
+    const unsigned flags = (bf ? NF_BF16 : p.nout > 64 ? NF_WIDE : 0) | (a.hm_p && a.hm_eps ? NF_EPS : 0);
+    return ns_launch_program(NV_GRAD2, flags, a, r.B, p, rows, s, 0, lds_extra);
 }
 
 // the forward + loss half of a training launch (STORE == 3): the batch rows ROWS (null: 0..B-1) of X gathered and
@@ -825,8 +819,8 @@ int launch_net_stream_grad2(const NsNet& net, const float* packed, const float* 
 static NsArgs ns_train_args(const NsProgram& p, bool full, const NsNet& net, const float* packed, const NsBatch& b, const NsOpBufs* ops,
                             const NsTrainLoss& L) {
     NsArgs a = ns_args(p, packed, b.X, b.ldx, b.B, net.in_size, full);
-    a.is_flat = reinterpret_cast<const int*>(b.xmean); a.a1 = b.xmean; a.a2 = b.xmean;     // loaded and ignored
-    a.lg = b.lg; a.xmean = b.xmean; a.xstd = b.xstd;
+    ns_set_input_ignored(a, b.xmean);              // (the prior map's constants; the input transform is real)
+    a.lg = b.lg; a.xstd = b.xstd;
     a.dense = p.dense; a.u_col = p.u_col; a.u_same = p.u_same;
     ns_store_table(a, p, net, ops, 0, p.nseg_f, false);
     a.t_rows = b.ROWS; a.t_xb = b.XB; a.t_ldxb = b.ldxb;
@@ -843,7 +837,7 @@ int launch_net_stream_train(const NsNet& net, const float* packed, const NsBatch
     const NsProgram& p = *pref;
     if (!p.ok || !p.dense) { set_error("net_stream: network + loss not eligible"); return LINNA_ERR_UNSUPPORTED; }
     const NsArgs a = ns_train_args(p, false, net, packed, b, ops, L);
-    return ns_launch_kernel<0, false, 3>(a, b.B, p, rows, s);
+    return ns_launch_program(NV_TRAIN_FWD, 0, a, b.B, p, rows, s);
 }
 
 // A training step's network work in ONE launch (TRB: GRAD + STORE == 3): launch_net_stream_train's forward + loss, its
@@ -868,14 +862,7 @@ int launch_net_stream_train_bwd(const NsNet& net, const float* packed, const NsB
     }
     int extra = 0;
     if (post && post->step) { a.p_step = post->step; a.p_hyper = post->hyper; a.p_b1 = post->b1; a.p_b2 = post->b2; extra = 1; }
-    if (bf) {
-#ifdef NS_STAMPS
-        set_error("net_stream: the NS_STAMPS build has no bf16 training step"); return LINNA_ERR_UNSUPPORTED;
-#endif
-        return ns_launch<net_stream_train_bf16_kernel<NS_R, 0, true, 3, 4, true>>(a, (b.B + 3) / 4 + extra, p.lds_for(rows, true) + lds_extra, s,
-                                                                                  "net_stream bf16 training launch");
-    }
-    return ns_launch_kernel<0, true, 3>(a, b.B, p, rows, s, extra, lds_extra);
+    return ns_launch_program(NV_TRAIN_STEP, bf ? NF_BF16 : 0, a, b.B, p, rows, s, extra, lds_extra);
 }
 
 // The dX chain of a training step in one launch (what linna_net_backward otherwise runs as one GEMM per op):
@@ -887,13 +874,13 @@ int launch_net_stream_dx(const NsNet& net, const float* packed, const float* dOU
     const NsProgram& p = *pref;
     if (!p.ok) { set_error("net_stream: no dX-chain program for this network"); return LINNA_ERR_UNSUPPORTED; }
     NsArgs a = ns_args(p, packed, dOUT, lddo, B, net.layers[net.nl - 1].N, false);
-    a.is_flat = reinterpret_cast<const int*>(dOUT); a.a1 = dOUT; a.a2 = dOUT; a.lg = nullptr; a.xmean = dOUT; a.xstd = dOUT;
+    ns_set_input_ignored(a, dOUT);
     ns_store_table(a, p, net, ops, 0, p.nseg_f, true);
-    if (post && post->n > 0) {                    // the rider (see NsArgs::p_rows): one more workgroup
+    const bool rider = post && post->n > 0;       // the rider (see NsArgs::p_rows): one more workgroup
+    if (rider) {
         a.p_rows = post->rows; a.p_n = post->n; a.p_scale = post->scale; a.p_out = post->out;
         a.p_step = post->step; a.p_hyper = post->hyper; a.p_b1 = post->b1; a.p_b2 = post->b2;
-        return ns_launch_kernel<0, false, 2>(a, B, p, rows, s, 1);
     }
-    return ns_launch_kernel<0, false, 2>(a, B, p, rows, s);
+    return ns_launch_program(NV_DX, 0, a, B, p, rows, s, rider ? 1 : 0);
 }
 }  // namespace linna
