@@ -328,6 +328,20 @@ int linna_logprob_precision(const linna_logprob_t* lp, int* out);
  * the others.  linna_logprob_set_precision(lp, LINNA_PRECISION_FP32) resets the gradient precision to fp32 as well. */
 int linna_logprob_set_grad_precision(linna_logprob_t* lp, int precision);
 int linna_logprob_grad_precision(const linna_logprob_t* lp, int* out);
+/* The opt-in one-launch gradient of a DENSE inverse covariance (fp32; off by default).  on = 1: linna_logprob_grad, both
+ * leapfrog entries and linna_hmc_run* compute lnP and d lnP / d z -- with the leapfrog's kick and drift in the finish -- in
+ * ONE launch of the whole-network kernel instead of the layered route's thirty or so.  With S = L L^T
+ * (linna_logprob_desc_t::Sfac) the factor is one more bias-free layer behind the network: the forward half ends in U = d L,
+ * the output map folded into the last layer; chi^2 = sum U_c^2, so lnP is the factored surface linna_logprob_eval serves
+ * (no d S d^T cancellation); the backward half starts from -U / T with the transposed factor and runs the dX chain down to
+ * the input.  The program is fitted to the LDS per engine: a batch whose engine (its own, or linna_engine_rows') it does
+ * not fit takes the layered route, as does every batch with the option off -- linna_logprob_grad_launches tells.
+ * LINNA_ERR_UNSUPPORTED (-3), with the reason, when the handle is bf16, the covariance is diagonal, the output map is the
+ * exp (ypositive) one, there is no Sfac (S not positive definite, or LINNA_DENSE_FACTORED=0), the network has an input skip
+ * or more than 64 inputs, or the program fits no engine.  The checks need no GPU; the stream copy is allocated here (call
+ * it outside graph capture), laid out on first use, and follows the weights like the others.  on = 0 switches back. */
+int linna_logprob_set_dense_grad(linna_logprob_t* lp, int on);
+int linna_logprob_dense_grad(const linna_logprob_t* lp, int* out);
 /* Rows per workgroup of the whole-network kernel: 0 (default) = chosen per launch from the batch size -- the fewest
  * of 4 / 8 / 16 that still fit the batch into one workgroup per CU; 4, 8 or 16 = that engine for every launch of the
  * process (tests and measurements; results differ between engines in the last bits: another summation order over k).
@@ -389,6 +403,12 @@ int linna_program_describe(const linna_layer_t* layers, int nlayers, int in_size
  * [x_hi ; x_lo], then the dX chain down to the input, 32 k per step, no SIDE segments; the last line reports the sign-bit
  * columns.  Returns 0 segments where the network has no such program. */
 int linna_program_describe_grad_bf16(const linna_layer_t* layers, int nlayers, int in_size, int rows, char* buf, size_t n);
+/* The same text for the program of the dense one-launch gradient (linna_logprob_set_dense_grad) with a factored inverse
+ * covariance of `nout` columns (the network's outputs) under linna_dense_tri mode `tri`: forward segments, U = d L, the
+ * transposed factor, the dX chain; then a line "u_same .. u_col .." (where U sits) and the LDS of the 16-, 8- and 4-row
+ * engines with the engines it fits.  Returns 0 segments where the network has no such program. */
+int linna_program_describe_grad_dense(const linna_layer_t* layers, int nlayers, int in_size, int nout, int tri, int rows,
+                                      char* buf, size_t n);
 size_t linna_logprob_ws_bytes(const linna_logprob_t* lp, int B, int with_grad);
 /* lnP[B]; THETA[B][ldt] optional (physical parameters, for chain_transformed). */
 int linna_logprob_eval(linna_logprob_t* lp, const float* Z, int ldz, int B, void* ws, float* lnP,
@@ -408,8 +428,9 @@ int linna_logprob_eval_slice_points(linna_logprob_t* lp, const float* coords, in
                                     const int* gate, void* stream);
 /* lnP[B] and d lnP / d z [B][ldg]  (intended semantics of util.py:1023-1035; HMCSampler.py:32).  In fp32 with a diagonal
  * covariance it is ONE launch of the whole-network kernel for networks of up to 64 inputs and any number of outputs the
- * kernel serves (<= 1024) whose program fits an engine's LDS: linna_logprob_grad_launches tells.  A dense covariance, more
- * than 64 inputs, or LINNA_DISABLE_FUSED_GRAD=1 at creation: the layered route. */
+ * kernel serves (<= 1024) whose program fits an engine's LDS: linna_logprob_grad_launches tells.  A dense covariance
+ * (unless linna_logprob_set_dense_grad switched its one-launch form on), more than 64 inputs, or
+ * LINNA_DISABLE_FUSED_GRAD=1 at creation: the layered route. */
 int linna_logprob_grad(linna_logprob_t* lp, const float* Z, int ldz, int B, void* ws, float* lnP,
                        float* G, int ldg, void* stream);
 /* One leapfrog step's gradient, kick and drift (HMCSampler.py:35-49: p += eps dlnp(q); q += eps p / m): lnP and G at Q, then

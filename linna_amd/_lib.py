@@ -134,6 +134,8 @@ _SIGNATURES = {
     "linna_logprob_precision": (_I, [_V, _V]),
     "linna_logprob_set_grad_precision": (_I, [_V, _I]),
     "linna_logprob_grad_precision": (_I, [_V, _V]),
+    "linna_logprob_set_dense_grad": (_I, [_V, _I]),
+    "linna_logprob_dense_grad": (_I, [_V, _V]),
     "linna_engine_rows": (_I, [_I]),
     "linna_dense_tri": (_I, [_I]),
     "linna_serve_plain": (_I, [_I]),
@@ -147,6 +149,7 @@ _SIGNATURES = {
     "linna_net_train_precision": (_I, [_V, _V]),
     "linna_program_describe": (_I, [_V, _I, _I, _I, _I, _V, C.c_size_t]),
     "linna_program_describe_grad_bf16": (_I, [_V, _I, _I, _I, _V, C.c_size_t]),
+    "linna_program_describe_grad_dense": (_I, [_V, _I, _I, _I, _I, _I, _V, C.c_size_t]),
     "linna_logprob_ws_bytes": (_SZ, [_V, _I, _I]),
     "linna_logprob_eval": (_I, [_V, _V, _I, _I, _V, _V, _V, _I, _V]),
     "linna_logprob_grad": (_I, [_V, _V, _I, _I, _V, _V, _V, _I, _V]),

@@ -964,6 +964,9 @@ struct linna_logprob {
     bool bf16() const { return precision == LINNA_PRECISION_BF16; }
     int grad_precision = LINNA_PRECISION_FP32;   // linna_logprob_set_grad_precision (bf16 only on a bf16 handle)
     StreamCopy packed_gbf;                   // the bf16 forward + dX-chain streams (NS_GRAD_INPUT_BF16), allocated when it is first set
+    bool dense_grad = false;                 // linna_logprob_set_dense_grad: a dense covariance's lnP and gradient in one launch (NS_GRAD_INPUT_DENSE)
+    StreamCopy packed_gd;                    // ... its streams, allocated when it is first set
+    bool gd_fits[3] = {false, false, false}; // ... and the engines (16 / 8 / 4 rows) whose LDS its program fits (net_stream_grad_dense_fits)
     NsKind kind() const { return bf16() ? NS_SERVE_BF16 : dense_fused ? NS_SERVE_DENSE : NS_SERVE; }   // the serving program
 };
 
@@ -1041,6 +1044,7 @@ enum LpRoute {
     LP_GRAD_BF16,       // the bf16 one-launch program (packed_gbf)
     LP_GRAD_MLP,        // the MLP one-launch gradient of the serving stream (grad_fused)
     LP_GRAD_ANY,        // the any-network one-launch gradient (packed_g2) on the engine `rows`
+    LP_GRAD_DENSE,      // the dense covariance's one-launch gradient (packed_gd; opt-in) on the engine `rows`
     LP_GRAD_LAYERED,    // layered forward, likelihood gradient, linna_net_backward, prior map's derivative
 };
 struct LpRouted { LpRoute route; int rows = 0; int err = LINNA_OK; const char* why = nullptr; };
@@ -1076,6 +1080,11 @@ static LpRouted lp_grad_route(const linna_logprob* lp, int B) {
     if (d.outmap.cexp) return LpRouted{LP_REFUSE, 0, LINNA_ERR_UNSUPPORTED, "ypositive (exp) output map has no gradient path"};
     if (!d.gscale || (!d.w && !d.Ssym)) return LpRouted{LP_REFUSE, 0, LINNA_ERR_INVALID, "descriptor lacks gscale / Ssym"};
     if (lp_stream_on(lp) && lp->grad_fused && d.w) return LpRouted{LP_GRAD_MLP};
+    if (lp->dense_grad && lp->fused_on && lp->packed_gd.ready() && !d.w && d.Sfac) {
+        // the batch's own engine where the program fits it; otherwise the layered route, never a smaller engine (lp_grad2_rows)
+        const int want = net_stream_rows(B);
+        if (lp->gd_fits[want == 16 ? 0 : want == 8 ? 1 : 2]) return LpRouted{LP_GRAD_DENSE, want};
+    }
     const int rows = lp->fused_on && lp->grad2 && lp->packed_g2.ready() && d.w ? lp_grad2_rows(lp, B) : 0;
     return rows ? LpRouted{LP_GRAD_ANY, rows} : LpRouted{LP_GRAD_LAYERED};
 }
@@ -1149,7 +1158,7 @@ int linna_logprob_create(linna_ctx_t* ctx, linna_net_t* net, const linna_logprob
     return LINNA_OK;
 } LINNA_CATCH_INT
 int linna_logprob_destroy(linna_logprob_t* lp) try {
-    if (lp) { lp->packed.release(); lp->packed_g2.release(); lp->packed_bf.release(); lp->packed_gbf.release(); }
+    if (lp) { lp->packed.release(); lp->packed_g2.release(); lp->packed_bf.release(); lp->packed_gbf.release(); lp->packed_gd.release(); }
     delete lp;
     return LINNA_OK;
 } LINNA_CATCH_INT
@@ -1208,6 +1217,50 @@ int linna_logprob_grad_precision(const linna_logprob_t* lp, int* out) try {
     if (!lp || !out) { set_error("logprob_grad_precision: null argument"); return LINNA_ERR_INVALID; }
     *out = lp->grad_precision;
     return LINNA_OK;
+} LINNA_CATCH_INT
+// The opt-in one-launch gradient of a dense covariance.  Checks first (no GPU needed), then the stream copy is allocated here
+// -- outside any graph capture -- and laid out by the first launch that reads it (weight epoch).
+int linna_logprob_set_dense_grad(linna_logprob_t* lp, int on) try {
+    if (!lp) { set_error("logprob_set_dense_grad: null handle"); return LINNA_ERR_INVALID; }
+    if (on != 0 && on != 1) { set_error("logprob_set_dense_grad: %d (0 layered, 1 one launch)", on); return LINNA_ERR_INVALID; }
+    if (!on) { lp->dense_grad = false; return LINNA_OK; }
+    const linna_net* n = lp->net;
+    const linna_logprob_desc_t& d = lp->d;
+    if (lp->bf16()) { set_error("logprob_set_dense_grad: a bf16 handle has no dense-covariance gradient (fp32 only)"); return LINNA_ERR_UNSUPPORTED; }
+    if (d.w) { set_error("logprob_set_dense_grad: the covariance is diagonal: its gradient is one launch already where the network has the program"); return LINNA_ERR_UNSUPPORTED; }
+    if (d.outmap.cexp) { set_error("logprob_set_dense_grad: the ypositive (exp) output map has no gradient path"); return LINNA_ERR_UNSUPPORTED; }
+    if (!d.Sfac) {
+        set_error("logprob_set_dense_grad: no factored inverse covariance (Sfac): it is not positive definite, or LINNA_DENSE_FACTORED=0");
+        return LINNA_ERR_UNSUPPORTED;
+    }
+    if (n->has_inskip) { set_error("logprob_set_dense_grad: an input-skip network has no one-launch gradient"); return LINNA_ERR_UNSUPPORTED; }
+    const NsDense dn = lp->dense();
+    const NsPlan g = net_stream_plan(NS_GRAD_INPUT_DENSE, n->L.data(), (int)n->L.size(), n->in_size, &dn);
+    if (!g.ok) {
+        set_error("logprob_set_dense_grad: no one-launch dense gradient for this network: %s", g.why ? g.why : "not eligible");
+        return LINNA_ERR_UNSUPPORTED;
+    }
+    if (!lp->packed_gd.ready() && lp->packed_gd.alloc(g.packed_floats) != LINNA_OK) {
+        set_error("logprob_set_dense_grad: hipMalloc(dense gradient weight stream) failed");
+        return LINNA_ERR_HIP;
+    }
+    for (int e = 0; e < 3; ++e) lp->gd_fits[e] = net_stream_grad_dense_fits(n->L.data(), (int)n->L.size(), n->in_size, &dn, 16 >> e);
+    lp->dense_grad = true;
+    return LINNA_OK;
+} LINNA_CATCH_INT
+int linna_logprob_dense_grad(const linna_logprob_t* lp, int* out) try {
+    if (!lp || !out) { set_error("logprob_dense_grad: null argument"); return LINNA_ERR_INVALID; }
+    *out = lp->dense_grad ? 1 : 0;
+    return LINNA_OK;
+} LINNA_CATCH_INT
+int linna_program_describe_grad_dense(const linna_layer_t* layers, int nlayers, int in_size, int nout, int tri, int rows, char* buf, size_t n) try {
+    if (!layers || nlayers < 1 || !buf || !n || nout < 1 || tri < 0 || tri > 2) { set_error("program_describe_grad_dense: bad arguments"); return LINNA_ERR_INVALID; }
+    TRY(check_layers(layers, nlayers, "program_describe_grad_dense"));
+    if (layers[nlayers - 1].N != nout) { set_error("program_describe_grad_dense: %d columns for a network of %d outputs", nout, layers[nlayers - 1].N); return LINNA_ERR_INVALID; }
+    // (pointers are only compared, never read: placeholders stand for the factor and the folded output map)
+    static float dummy[2];
+    const NsDense dn{dummy, (nout + 3) & ~3, dummy + 1, dummy + 1, 1, tri};
+    return net_stream_describe(NS_GRAD_INPUT_DENSE, layers, nlayers, in_size, &dn, rows, buf, n);
 } LINNA_CATCH_INT
 int linna_program_describe_grad_bf16(const linna_layer_t* layers, int nlayers, int in_size, int rows, char* buf, size_t n) try {
     if (!layers || nlayers < 1 || !buf || !n) { set_error("program_describe_grad_bf16: bad arguments"); return LINNA_ERR_INVALID; }
@@ -1513,6 +1566,14 @@ static int logprob_grad_impl(linna_logprob_t* lp, const float* Z, int ldz, int B
         TRY(lp_refresh_stream(lp, B, stream, &packed, &rows));
         return lp_launch(lp, packed, rows, r, nullptr, &gr, stream);
     }
+    case LP_GRAD_DENSE: {
+        // ... and for a dense covariance (opt-in): the output map and the factor L of S = L L^T ride in the stream, the
+        // turnaround works in U = d L (net_stream.hip, net_stream_dense_kernel) -- some thirty launches otherwise
+        const NsDense dn = lp->dense();
+        const float* packed = nullptr;
+        TRY(stream_copy_refresh(lp->packed_gd, lp->net, rt.rows, stream, &packed, NS_GRAD_INPUT_DENSE, &dn));
+        return launch_net_stream_grad_dense(net_layers(lp->net, NS_GRAD_INPUT_DENSE), packed, r, lp_input(d), d.temperature, gr, rt.rows, dn, S(stream));
+    }
     case LP_GRAD_ANY:
         // ONE launch for any network: forward segments (the signs the gates need kept as bits in LDS), turnaround, dX chain
         // down to the input, prior map's derivative (net_stream.hip, GRAD + STORE == 2) -- six launches otherwise
@@ -1547,7 +1608,7 @@ int linna_logprob_grad(linna_logprob_t* lp, const float* Z, int ldz, int B, void
 int linna_logprob_grad_launches(linna_logprob_t* lp, int B, int* out) try {
     if (!lp || !out || B < 1) { set_error("logprob_grad_launches: bad arguments"); return LINNA_ERR_INVALID; }
     const LpRoute route = lp_grad_route(lp, B).route;
-    *out = route == LP_GRAD_BF16 || route == LP_GRAD_MLP || route == LP_GRAD_ANY ? 1 : 0;
+    *out = route == LP_GRAD_BF16 || route == LP_GRAD_MLP || route == LP_GRAD_ANY || route == LP_GRAD_DENSE ? 1 : 0;
     return LINNA_OK;
 } LINNA_CATCH_INT
 

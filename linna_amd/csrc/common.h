@@ -366,6 +366,9 @@ enum NsKind {
     NS_TRAIN_STEP_BF16,   // ... in bf16 (linna_net_set_train_precision): bf16 runs, the loss segment an fp32 run, first layer [W | W]
     NS_GRAD_INPUT_BF16,   // NS_GRAD_INPUT in bf16 (linna_logprob_set_grad_precision): every run bf16, first layer [W | W], no SIDE segments
     NS_GRAD_INPUT_WIDE,   // NS_GRAD_INPUT for networks of MORE than 64 outputs (net_stream_wide_kernel): the same program, fitted to the LDS per engine
+    NS_GRAD_INPUT_DENSE,  // lnP and its gradient for a DENSE inverse covariance S = L L^T (net_stream_dense_kernel; opt-in): forward with the
+                          // output map folded into the last layer, U = d L, turnaround in U-space, the transposed dense map, dX chain; any
+                          // number of outputs, fitted to the LDS per engine
 };
 // the serving programs are built from the layer list with the trailing input skip, the training ones from the list without
 inline bool ns_kind_full_layers(NsKind k) { return k == NS_SERVE || k == NS_SERVE_DENSE || k == NS_SERVE_BF16; }
@@ -384,6 +387,8 @@ inline NsKind ns_grad_kind(const linna_layer_t* layers, int nl) { return nl >= 1
 // Whether that program runs on the engine of `rows` rows: it and its sign bits fit the LDS (host-side planning only).  A
 // batch whose engine it does not fit takes the layered route.
 bool net_stream_grad_fits(const linna_layer_t* layers, int nl, int in_size, int rows);
+// The same for the dense one-launch gradient (NS_GRAD_INPUT_DENSE with the factored `dn`)
+bool net_stream_grad_dense_fits(const linna_layer_t* layers, int nl, int in_size, const NsDense* dn, int rows);
 int launch_net_stream_pack(NsKind kind, const linna_layer_t* layers, int nl, int in_size, float* packed, int rows, const NsDense* dn,
                            hipStream_t s);
 int net_stream_describe(NsKind kind, const linna_layer_t* layers, int nl, int in_size, const NsDense* dn, int rows, char* buf, size_t n);
@@ -498,6 +503,10 @@ int launch_adamw_streams(const AsArgs& a, float* p, const float* g, float* m, fl
 // forward + dX chain down to the input in one launch (NS_GRAD_INPUT, or bf: NS_GRAD_INPUT_BF16; diagonal covariance)
 int launch_net_stream_grad2(const NsNet& net, const float* packed, const NsRun& r, const NsInput& in, const NsOutput& out, const NsGrad& gr,
                             int rows, hipStream_t s, bool bf = false);
+// the same for a dense inverse covariance in its factored form (NS_GRAD_INPUT_DENSE: the output map and L are in the stream;
+// gr.gscale is not read)
+int launch_net_stream_grad_dense(const NsNet& net, const float* packed, const NsRun& r, const NsInput& in, float T, const NsGrad& gr,
+                                 int rows, const NsDense& dn, hipStream_t s);
 // a serving launch (kind NS_SERVE, NS_SERVE_DENSE with dn, or NS_SERVE_BF16)
 bool net_stream_takes_plain(NsKind kind, const NsNet& net, const NsOutput& out, const NsRun& r, const NsMove* mv, const NsGrad* gr, int rows,
                             const NsDense* dn);   // what launch_net_stream decides

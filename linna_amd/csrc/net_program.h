@@ -11,7 +11,8 @@ namespace linna {
 constexpr int NS_ROWS = 16;                // rows per workgroup of the large-batch engine (and the LDS layout bound)
 constexpr int NS_NW = 8;                 // waves per workgroup
 constexpr int NS_NT = 4;                 // 16-column tiles per wave and step
-constexpr int NS_MAXSEG = 20;
+constexpr int NS_MAXSEG = 20;              // segments of a program of every kind but NS_GRAD_INPUT_DENSE: what those kinds are checked against
+constexpr int NS_SEGCAP = 22;              // capacity of the per-segment tables (NsArgs, NsPackArgs, NsGates): ChtoModelv2's NS_GRAD_INPUT_DENSE program
 constexpr int NS_MAXRUN = 40;
 constexpr unsigned NS_STEP_B = NS_NT * 1024;
 constexpr int NS_LDS_BYTES = 160 * 1024;
@@ -43,6 +44,8 @@ struct NsPackSeg {
     const float* rscale; const float* rshift;     // per output column: weights and bias * rscale, bias + rshift (folded output map)
     int kc, side_off;                             // SIDE segments: k chunks per wave and step (2 or 4), float offset of their block
     int koff2;                                    // WIDE with a short second pass: k offset of pass 1 (NsSeg::kslice)
+    const float* kscale;                          // per contraction index of the first K part: Wa(n, k) * kscale[k] -- the transposed last
+                                                  // layer behind a folded output map (NS_GRAD_INPUT_DENSE: the forward one carries rscale)
 };
 
 // ---------------------------------------------------------------------------- host side: the program
@@ -60,6 +63,7 @@ struct NsProgram {
     bool ok = false, grad_ok = false;                       // grad_ok: backward segments appended (ReLU MLPs)
     bool dxi_ok = false;                                    // the dX chain down to the input appended (NS_GRAD_INPUT)
     bool train_ok = false;                                  // forward + loss + dX chain (NS_TRAIN_STEP)
+    int nops = 0;                                           // ops of the layer list: a segment of op index nops is a dense map, not a layer's
     std::vector<int> seg_op, seg_hidden;                    // forward segments: op index; 1 = the hidden h of a residual block
                                                             // (dX-chain program: 1 = d/dh of a residual block, else d/d(input) of the op)
     size_t lds_for(int rows, bool grad) const;              // dynamic LDS of a launch on the engine of `rows` rows per workgroup
@@ -93,7 +97,7 @@ int ns_seg_cols(const NsProgram& p, const linna_layer_t* layers, int i);
 // no gate asks for them; every tensor rounded up to 64 columns); mbit[i]: the columns backward segment i gates on (-1:
 // none).  ok = false when a gate has no producer.
 struct NsGates {
-    int gbit[NS_MAXSEG], mbit[NS_MAXSEG];
+    int gbit[NS_SEGCAP], mbit[NS_SEGCAP];
     int ncols = 0;
     bool ok = true;
     size_t lds0 = 0, lds = 0;                               // the program's LDS (8-byte aligned), and with the bits

@@ -87,6 +87,8 @@ struct Lin {
     int transA = 0, transB = 0, force_wide = 0, mask_apply_of = -1, op = -1;
     const float* rscale = nullptr; const float* rshift = nullptr;
     const float* b2 = nullptr; float b2scale = 0.f; int x0_col = 0;
+    const float* kscale = nullptr;     // NsPackSeg::kscale
+    bool no_bias = false;              // a bias-free map that is not read transposed: it shares the block of zeros all the same
 };
 static int ld4(int k) { return (k + 3) & ~3; }              // row stride of a [N][k] weight matrix (LINNA_LD)
 static Lin lin_over(const float* W, int ldw, int K, int N, int op) {   // the first K part alone: N outputs of W over K input columns
@@ -114,6 +116,11 @@ static Lin lin_block_dx(const linna_layer_t& l, int op) {
 // row-dot GEMM of the layered path reads S[k][n] as it is)
 static Lin lin_dense(const NsDense& dn, int nout, int op) {
     Lin L = lin_over(dn.S, dn.lds, nout, nout, op); L.same_buf = nout <= 256; L.dst_col = L.same_buf ? L.Kapad : 0; L.transA = dn.factored ? 1 : 0; return L;
+}
+// its transpose behind the turnaround of NS_GRAD_INPUT_DENSE: d/dd_k = sum_n (d/dU_n) L[k][n], from column 0 of the current
+// buffer (where the turnaround put d/dU) like every other backward map -- L as it lies in memory, no bias
+static Lin lin_dense_back(const NsDense& dn, int nout, int op) {
+    Lin L = lin_over(dn.S, dn.lds, nout, nout, op); L.no_bias = true; return L;
 }
 
 // ---- 1. lowering: layer list -> linear maps
@@ -185,7 +192,9 @@ static NsLowered ns_lower(const linna_layer_t* layers, int nl, int in_size, cons
         ns_push_dx(lins, layers, nl, o.dx_first);
         in_size = layers[nl - 1].N;                         // the rows of this program are d loss / d output
     } else if (!ns_push_forward(lins, &r.x0_keep, layers, nl, in_size)) return r;
-    if (lins.empty() || lins.back().relu || (int)lins.size() > NS_MAXSEG) return r;
+    // (the dense one-launch gradient alone may fill the tables: ChtoModelv2's is 22 segments; every other kind keeps its limit)
+    const int maxseg = o.dense && dxi ? NS_SEGCAP : NS_MAXSEG;
+    if (lins.empty() || lins.back().relu || (int)lins.size() > maxseg) return r;
     if (o.bf) {                                             // [x_hi ; x_lo]: the first layer twice, no padding between the halves
         Lin& f = lins[0];
         if (f.Wb || f.same_buf || f.transA || !f.Wa || f.Ka != in_size || f.x0_col) return r;
@@ -195,7 +204,7 @@ static NsLowered ns_lower(const linna_layer_t* layers, int nl, int in_size, cons
         Lin& last = lins.back();
         if (last.Wb || last.same_buf || last.dst_col) return r;               // the last op must be a plain linear layer
         last.rscale = dn->cscale; last.rshift = dn->cshift;
-        if ((int)lins.size() + 1 > NS_MAXSEG) return r;
+        if ((int)lins.size() + 1 > maxseg) return r;
         const Lin Q = lin_dense(*dn, last.N, nl);
         lins.push_back(Q);
         r.dense = 1; r.u_col = Q.dst_col; r.u_same = Q.same_buf ? 1 : 0;
@@ -205,14 +214,23 @@ static NsLowered ns_lower(const linna_layer_t* layers, int nl, int in_size, cons
     if (dxi) {
         // the prologue / turnaround constants are held for <= 64 columns; the wide-output instantiations of the fp32 kernel
         // (net_stream_wide_kernel) read the output's beyond 64 from memory -- a program kind of its own
-        if (in_size > 64 || (lins.back().N > 64) != o.wide_out) return r;
+        if (in_size > 64) return r;
+        if (o.dense) {
+            // NS_GRAD_INPUT_DENSE: the turnaround works on U = d L in LDS at any width and leaves d lnP / dU at column 0; the
+            // transposed dense map takes it back to d lnP / dd, and the chain's first map (the last layer's transpose) carries
+            // the folded output map's scale per contraction index, as the forward one carries it per column
+            if (!dn->factored) return r;
+            lins.push_back(lin_dense_back(*dn, lins.back().N, nl));
+        } else if ((lins.back().N > 64) != o.wide_out) return r;
+        const size_t first_dx = lins.size();
         ns_push_dx(lins, layers, nl, 0);
+        if (o.dense) lins[first_dx].kscale = dn->cscale;
     }
     if (train) {                                               // the turnaround works on the rows in LDS: any width
         if (nl < 2) return r;
         ns_push_dx(lins, layers, nl, 1);
     }
-    if ((int)lins.size() > NS_MAXSEG) return r;
+    if ((int)lins.size() > maxseg) return r;
     r.mlp_grad = o.bwd == NS_BWD_MLP && ns_mlp_grad_maps_ok(lins, in_size);
     r.ok = true;
     return r;
@@ -278,9 +296,9 @@ static bool ns_shape(NsShaper& sh, const Lin& L, const NsShapeCtx& c) {
     q.Wa = L.Wa; q.lda = L.lda; q.Ka = L.Ka; q.Kapad = L.Kapad; q.Wb = L.Wb; q.ldb = L.ldb; q.Kb = L.Kb; q.alpha = L.alpha;
     q.b = L.b; q.bscale = L.bscale; q.N = L.N; q.type = s.type; q.steps = s.steps; q.passes = s.passes; q.bias_off = sh.bias_off;
     q.transA = L.transA; q.transB = L.transB; q.rscale = L.rscale; q.rshift = L.rshift; q.b2 = L.b2; q.b2scale = L.b2scale;
-    q.kc = side ? kc : 1; q.side_off = 0;
+    q.kc = side ? kc : 1; q.side_off = 0; q.kscale = L.kscale;
     s.x0_col = L.x0_col; s.x0_n = L.x0_col ? ceil16(L.Kb) : 0;
-    if (L.transA && c.o.forward) {                          // transposed segments have no bias (a dX chain on its own: none has one)
+    if ((L.transA || L.no_bias) && c.o.forward) {           // transposed segments have no bias (a dX chain on its own: none has one)
         if (sh.zero_off < 0) { sh.zero_off = sh.bias_off; sh.zero_pad = 0; }
         s.bias_off = q.bias_off = sh.zero_off;
         const int grow = std::max(0, q.bias_pad - sh.zero_pad);
@@ -292,7 +310,7 @@ static bool ns_shape(NsShaper& sh, const Lin& L, const NsShapeCtx& c) {
     // tri = 2 and exactly 16 column blocks (960 < nout <= 1024): the balanced assignment instead (ns_seg_steps) -- the zero
     // rows of EVERY 64-column block are skipped, not only those of the second pass, and every wave runs the same number
     // of steps: 66 instead of 94 at nout = 1000
-    if (c.dn && c.dn->tri > 0 && s.type == NS_WIDE && c.dn->factored && L.Wa == c.dn->S && passes == 2 && ksteps > 32 && c.o.bwd != NS_BWD_TRAIN) {
+    if (c.dn && c.dn->tri > 0 && s.type == NS_WIDE && c.dn->factored && L.Wa == c.dn->S && L.transA && passes == 2 && ksteps > 32 && c.o.bwd != NS_BWD_TRAIN) {
         if (c.dn->tri == 2 && (L.N + 63) / 64 == 16 && ksteps > 60) s.zext = -1;
         else { s.kslice = 512; s.zext = ksteps - 32; }
     }
@@ -368,7 +386,7 @@ static bool ns_sizes(NsProgram& p, int maxext) {
     if (p.bias_total > 3 * 64 * NS_NW * 4) return false;    // BMAX rounds of float4 per thread
     // (the sign-bit slots' share: never for the eligible shapes.  The wide-output one-launch gradient is fitted per engine, with its
     // sign bits, by net_stream_grad_fits: here it only has to fit the smallest one)
-    if (p.lds_for(p.dxi_ok && p.nout > 64 ? 4 : NS_ROWS, true) > (size_t)NS_LDS_BYTES) return false;
+    if (p.lds_for(p.dxi_ok && (p.nout > 64 || p.dense) ? 4 : NS_ROWS, true) > (size_t)NS_LDS_BYTES) return false;
     int nrun = 0;
     for (const NsSeg& s : p.seg) nrun += s.passes;
     if (nrun > NS_MAXRUN) return false;
@@ -404,7 +422,7 @@ static NsProgram ns_build_one(const linna_layer_t* layers, int nl, int in_size, 
     p.Gstride = sh.G; p.nseg_f = nfwd; p.grad_ok = slots >= 0; p.mask_slots = std::max(slots, 0);
     for (int i = 0; i < nfwd; ++i) if (p.seg[i].type != NS_SIDE) p.G += ns_seg_steps(p.seg[i]);
     for (const Lin& L : lo.lins) { p.seg_op.push_back(L.op); p.seg_hidden.push_back(L.same_buf ? 1 : 0); }
-    p.dxi_ok = o.bwd == NS_BWD_INPUT;
+    p.dxi_ok = o.bwd == NS_BWD_INPUT; p.nops = nl;
     p.train_ok = o.bwd == NS_BWD_TRAIN;
     p.bias_total = sh.bias_off;
     p.ok = ns_sizes(p, maxext);
@@ -426,7 +444,7 @@ int net_stream_force_rows(int rows) {
 // as sign bits in LDS and the per-segment tables read through the kernel-argument segment (without that the instantiation
 // spilled 2.5 KB per lane): 151.4 -> 148.7 us at ChtoModelv2(33,33), 4096 chains (NOTES R4).  Not in bf16.
 static bool ns_side(NsKind kind, int rows) {
-    return rows == 16 && (kind == NS_SERVE || kind == NS_SERVE_DENSE || kind == NS_GRAD_INPUT || kind == NS_GRAD_INPUT_WIDE);
+    return rows == 16 && (kind == NS_SERVE || kind == NS_SERVE_DENSE || kind == NS_GRAD_INPUT || kind == NS_GRAD_INPUT_WIDE || kind == NS_GRAD_INPUT_DENSE);
 }
 
 static NsProgram ns_build_kind(NsKind kind, const linna_layer_t* layers, int nl, int in_size, const NsDense* dn, bool side) {
@@ -440,6 +458,7 @@ static NsProgram ns_build_kind(NsKind kind, const linna_layer_t* layers, int nl,
     case NS_DX_INPUT: o.forward = false; o.dx_first = 0; break;
     case NS_GRAD_INPUT: o.bwd = NS_BWD_INPUT; break;
     case NS_GRAD_INPUT_WIDE: o.bwd = NS_BWD_INPUT; o.wide_out = true; break;
+    case NS_GRAD_INPUT_DENSE: o.bwd = NS_BWD_INPUT; o.dense = true; break;
     case NS_GRAD_INPUT_BF16: o.bwd = NS_BWD_INPUT; o.bf = true; if (dn) return NsProgram(); break;
     case NS_TRAIN_STEP: case NS_TRAIN_STEP_BF16: o.dense = true; o.bwd = NS_BWD_TRAIN; o.bf = kind == NS_TRAIN_STEP_BF16; break;
     }
@@ -449,7 +468,7 @@ static NsProgram ns_build_kind(NsKind kind, const linna_layer_t* layers, int nl,
         p = ns_build_one(layers, nl, in_size, o, dn);
     }
     // the SIDE program where it fits, the plain one otherwise
-    if (side && !(p.ok && ((kind != NS_GRAD_INPUT && kind != NS_GRAD_INPUT_WIDE) || p.dxi_ok))) return ns_build_kind(kind, layers, nl, in_size, dn, false);
+    if (side && !(p.ok && ((kind != NS_GRAD_INPUT && kind != NS_GRAD_INPUT_WIDE && kind != NS_GRAD_INPUT_DENSE) || p.dxi_ok))) return ns_build_kind(kind, layers, nl, in_size, dn, false);
     return p;
 }
 NsProgramRef ns_program(NsKind kind, const linna_layer_t* layers, int nl, int in_size, const NsDense* dn, int rows) {
@@ -500,12 +519,13 @@ static std::atomic<int> g_serve_plain_sched{1};
 int net_stream_serve_plain_sched(int hand) { return hand < 0 ? g_serve_plain_sched.load() : g_serve_plain_sched.exchange(hand ? 1 : 0); }
 
 int ns_seg_cols(const NsProgram& p, const linna_layer_t* layers, int i) {
+    if (p.seg_op[i] >= p.nops) return p.nout;               // the dense pair of NS_GRAD_INPUT_DENSE (op == nl): U, d lnP / dd
     const linna_layer_t& l = layers[p.seg_op[i]];
     return p.seg_hidden[i] ? l.C : i < p.nseg_f ? l.N : l.K;
 }
 NsGates ns_gates(const NsProgram& p, const linna_layer_t* layers, int nl, int rows) {
     NsGates g;
-    for (int i = 0; i < NS_MAXSEG; ++i) g.gbit[i] = g.mbit[i] = -1;
+    for (int i = 0; i < NS_SEGCAP; ++i) g.gbit[i] = g.mbit[i] = -1;
     for (int i = 0; i < p.nseg_f; ++i) {                    // forward: keep the signs a gate will ask for
         const int op = p.seg_op[i];
         if (op >= nl || (!p.seg_hidden[i] && op == nl - 1)) continue;   // the loss segment and the network output gate nothing
@@ -516,6 +536,7 @@ NsGates ns_gates(const NsProgram& p, const linna_layer_t* layers, int nl, int ro
         // d/dh of a residual block: gated by its h; d/d(input of op): by the producing op's output, if it went through a ReLU
         const int op = p.seg_op[i];
         const bool hidden = p.seg_hidden[i] != 0;
+        if (op >= nl) continue;                              // the transposed dense map: d lnP / dd, the gradient of an output nobody gated
         if (!hidden && !(op > 0 && (layers[op - 1].op == LINNA_OP_RESBLOCK || layers[op - 1].relu))) continue;
         const int src = hidden ? op : op - 1;
         for (int j = 0; j < p.nseg_f; ++j)
@@ -540,6 +561,19 @@ static size_t ns_grad_lds(const linna_layer_t* layers, int nl, int in_size, int 
 // the 16-row one: 259.7 against 230.6 us at (26,457), 438.0 against 371.2 us at (40,1000) (wide outputs).
 bool net_stream_grad_fits(const linna_layer_t* layers, int nl, int in_size, int rows) {
     const size_t lds = ns_grad_lds(layers, nl, in_size, rows);
+    return lds && lds <= (size_t)NS_LDS_BYTES;
+}
+
+// The same two for the dense one-launch gradient (NS_GRAD_INPUT_DENSE): its program holds the dense pair and the folded
+// output map, so it is fitted with its own descriptor; every width is fitted per engine
+static size_t ns_grad_dense_lds(const linna_layer_t* layers, int nl, int in_size, const NsDense* dn, int rows) {
+    const NsProgramRef pref = ns_program(NS_GRAD_INPUT_DENSE, layers, nl, in_size, dn, rows);
+    if (!pref->ok || !pref->dxi_ok) return 0;
+    const NsGates g = ns_gates(*pref, layers, nl, rows);
+    return g.ok ? g.lds : 0;
+}
+bool net_stream_grad_dense_fits(const linna_layer_t* layers, int nl, int in_size, const NsDense* dn, int rows) {
+    const size_t lds = ns_grad_dense_lds(layers, nl, in_size, dn, rows);
     return lds && lds <= (size_t)NS_LDS_BYTES;
 }
 
@@ -568,6 +602,19 @@ NsPlan net_stream_plan(NsKind kind, const linna_layer_t* layers, int nl, int in_
         // wide outputs: on SOME engine -- a launch asks for its own (net_stream_grad_fits)
         for (int rows = 8; kind == NS_GRAD_INPUT_WIDE && rows >= 4; rows >>= 1) r.ok = r.ok || net_stream_grad_fits(layers, nl, in_size, rows);
         // one copy serves every engine: the 16-row one reads the SIDE program
+        r.packed_floats = std::max(r.packed_floats, ns_program(kind, layers, nl, in_size, dn, 16)->packed_floats);
+    }
+    if (kind == NS_GRAD_INPUT_DENSE) {
+        // the reasons of its own first (ns_lower refuses them all as "does not fit"); ok: on SOME engine, as for wide outputs
+        bool inskip = false;
+        for (int i = 0; i < nl; ++i) inskip = inskip || layers[i].op == LINNA_OP_INSKIP;
+        bool fits = false;
+        for (int rows = 16; rows >= 4; rows >>= 1) fits = fits || net_stream_grad_dense_fits(layers, nl, in_size, dn, rows);
+        if (inskip) r.why = "an input-skip network has no one-launch gradient";
+        else if (in_size > 64) r.why = "more than 64 network inputs: outside the one-launch gradient";
+        else if (!dn || !dn->S || !dn->factored) r.why = "the dense one-launch gradient needs the factored inverse covariance";
+        else if (!fits) r.why = "the program of the dense one-launch gradient fits no engine (segments, LDS or widths)";
+        r.ok = r.why == nullptr;
         r.packed_floats = std::max(r.packed_floats, ns_program(kind, layers, nl, in_size, dn, 16)->packed_floats);
     }
     if (kind == NS_SERVE_BF16) { r.why = ns_bf16_refusal(p, layers, nl, in_size); r.ok = r.why == nullptr; }
@@ -620,6 +667,20 @@ int net_stream_describe(NsKind kind, const linna_layer_t* layers, int nl, int in
                 if (lds[e] && lds[e] <= (size_t)NS_LDS_BYTES) { snprintf(line, sizeof line, " %d", 16 >> e); out += line; }
             out += fits ? ")\n" : "\n";
         }
+    }
+    if (p.ok && kind == NS_GRAD_INPUT_DENSE) {             // the dense one-launch gradient: every engine's bytes, always, then those that fit
+        const NsGates g = ns_gates(p, layers, nl, rows ? rows : NS_ROWS);
+        size_t lds[3]; int fits = 0;
+        for (int e = 0; e < 3; ++e) {
+            lds[e] = ns_grad_dense_lds(layers, nl, in_size, dn, 16 >> e);
+            fits += lds[e] && lds[e] <= (size_t)NS_LDS_BYTES;
+        }
+        snprintf(line, sizeof line, "u_same %d u_col %d\nlds 16:%zu 8:%zu 4:%zu of %d bytes with %d sign-bit columns: %s", p.u_same, p.u_col, lds[0],
+                 lds[1], lds[2], NS_LDS_BYTES, g.ncols, fits ? "one launch (rows" : "layered");
+        out += line;
+        for (int e = 0; fits && e < 3; ++e)
+            if (lds[e] && lds[e] <= (size_t)NS_LDS_BYTES) { snprintf(line, sizeof line, " %d", 16 >> e); out += line; }
+        out += fits ? ")\n" : "\n";
     }
     if (buf && n) { snprintf(buf, n, "%s", out.c_str()); }
     return p.ok ? (int)p.seg.size() : 0;

@@ -81,17 +81,17 @@ struct NsArgs {
     const int* gate;                    // optional: every workgroup leaves at once when gate[0] == 0 (speculatively queued rounds)
     // STORE instantiation (training / validation forward, nn.py:110-133): the input rows are taken as they are
     // (already X-transformed), every segment's output ALSO goes to global memory for the backward, no likelihood
-    float* gout[NS_MAXSEG]; int gld[NS_MAXSEG]; int gn[NS_MAXSEG];
+    float* gout[NS_SEGCAP]; int gld[NS_SEGCAP]; int gn[NS_SEGCAP];
     // STORE == 2 (the dX chain of a training step): a segment's output is zeroed where gmask (the stored forward
     // activation whose gradient it is) is not positive, before it is stored and handed to the next segment
-    const float* gmask[NS_MAXSEG]; int gmld[NS_MAXSEG];
+    const float* gmask[NS_SEGCAP]; int gmld[NS_SEGCAP];
     // GRAD + STORE == 2 (lnP and its gradient in one launch, any network): the backward needs the SIGN of the forward
     // activations only, and it needs it in this very workgroup -- one bit per (row, column) in LDS ([ROWS][nbw] words at
     // float offset bits_off) instead of the activations in global memory.  gbit / mbit: the first bit column (a multiple of
     // 64) of the tensor a segment writes / is gated by, -1 = none.  The merged training launch (GRAD + STORE == 3) gates the
     // same way -- its activations still go to global memory, the parameter gradients need them.
     int nbw, bits_off;
-    int gbit[NS_MAXSEG], mbit[NS_MAXSEG];
+    int gbit[NS_SEGCAP], mbit[NS_SEGCAP];
     // STORE == 3 (one launch = gather + input transform + training forward + chi^2-ratio loss and its gradient,
     // predictor_gpu.py:274-285 with util.py:1070-1116): Z is the RESIDENT training set X[n][ldz], row `t_rows[b]` is
     // transformed in the prologue (and stored to t_xb for the first layer's parameter gradient); the last network layer's
@@ -121,7 +121,7 @@ struct NsArgs {
     const float* sl_Z0; const float* sl_L; const float* sl_R; const float* sl_Zt; int sl_m, sl_nt;
     unsigned long long sl_seed; const int* sl_step; int sl_stream; const int* sl_flags;
     SliceBegin sb;                      // MOVE == 2, sb.logp != null: the half step's set-up in this launch's prologue (common.h)
-    NsSeg seg[NS_MAXSEG];
+    NsSeg seg[NS_SEGCAP];
     const float* hm_eps;                // GRAD: the leapfrog in the finish with a step size per row (the EPS instantiations: hm_ek, hm_ed then multiply it)
 };
 
@@ -135,7 +135,7 @@ struct NsArgs {
 // by inline asm: the compiler's counted waits for the ring never see them).  The step loop itself is untouched.
 //   side[w][s][t][lane][e]:  n = 16 (t % (4 / kc)) + li,  k = 16 (kc (w steps + s) + t / (4 / kc)) + 4 kq + e
 struct NsPackArgs {
-    NsPackSeg seg[NS_MAXSEG];
+    NsPackSeg seg[NS_SEGCAP];
     int run_seg[NS_MAXRUN], run_pass[NS_MAXRUN], run_first[NS_MAXRUN + 1];
     int nseg, nrun, G, bias_total;
     int small;                                     // layout of the 4x4x1 engines: lane = column, load t = k chunk
@@ -155,6 +155,7 @@ __device__ __forceinline__ float ns_pack_value(const NsPackSeg& S, int n, int k)
     float v = 0.f;
     if (k < S.Kapad) {
         if (k < S.Ka) v = !S.Wa ? (k == n ? 1.f : 0.f) : S.transA ? S.Wa[(size_t)k * S.lda + n] : S.Wa[(size_t)n * S.lda + k];
+        if (k < S.Ka && S.kscale) v *= S.kscale[k];
     } else if (k - S.Kapad < S.Kb) {
         v = S.alpha * (S.transB ? S.Wb[(size_t)(k - S.Kapad) * S.ldb + n] : S.Wb[(size_t)n * S.ldb + (k - S.Kapad)]);
     }
@@ -208,7 +209,7 @@ __global__ void ns_pack_kernel(NsPackArgs p) {
         } else if (S.type == NS_WIDE) { n = 512 * p.run_pass[r] + 64 * w + nl; k0 = 16 * s + kl + (p.run_pass[r] ? S.koff2 : 0); }
         else { n = 64 * (w % S.ncg) + nl; k0 = 16 * ((w / S.ncg) * S.steps + s) + kl; }
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (n < S.N && S.Wa && !S.transA && k0 + 3 < S.Ka && (S.lda & 3) == 0 && (reinterpret_cast<uintptr_t>(S.Wa) & 15) == 0) {
+        if (n < S.N && S.Wa && !S.transA && !S.kscale && k0 + 3 < S.Ka && (S.lda & 3) == 0 && (reinterpret_cast<uintptr_t>(S.Wa) & 15) == 0) {
             // the common case: four consecutive k of one weight row, 16 bytes aligned (rows are padded to 4 floats)
             v = *reinterpret_cast<const f32x4*>(S.Wa + (size_t)n * S.lda + k0);
             if (S.rscale) { const float r = S.rscale[n]; v = f32x4{v[0] * r, v[1] * r, v[2] * r, v[3] * r}; }
@@ -218,6 +219,7 @@ __global__ void ns_pack_kernel(NsPackArgs p) {
                 const int k = k0 + e;
                 if (k < S.Kapad) {
                     if (k < S.Ka) v[e] = !S.Wa ? (k == n ? 1.f : 0.f) : S.transA ? S.Wa[(size_t)k * S.lda + n] : S.Wa[(size_t)n * S.lda + k];
+                    if (k < S.Ka && S.kscale) v[e] *= S.kscale[k];      // (the same product the forward segment's rscale makes of this weight)
                 } else if (k - S.Kapad < S.Kb) {
                     v[e] = S.alpha * (S.transB ? S.Wb[(size_t)(k - S.Kapad) * S.ldb + n] : S.Wb[(size_t)n * S.ldb + (k - S.Kapad)]);
                 }
@@ -316,7 +318,7 @@ __device__ __forceinline__ float ns_prior_theta(float z, int flat, float a1, flo
 // instructions for every existing instantiation.)
 template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF = false>
 __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_kernel(NsArgs a) {
-    constexpr bool EPS = false, PLAIN = false, WOUT = false;
+    constexpr bool EPS = false, PLAIN = false, WOUT = false, DGR = false;
 #include "net_stream_body.inc"
 }
 // EPS: the fp32 gradient programs (GRAD, STORE 0 or 2) whose finish runs the leapfrog with a step size per row, a.hm_eps
@@ -326,7 +328,7 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_kernel(NsArgs a) {
 template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF>
 __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_eps_kernel(NsArgs a) {
     static_assert(!BF && GRAD && (STORE == 0 || STORE == 2) && MOVE == 0, "the fp32 one-launch gradients only");
-    constexpr bool EPS = true, PLAIN = false, WOUT = false;
+    constexpr bool EPS = true, PLAIN = false, WOUT = false, DGR = false;
 #include "net_stream_body.inc"
 }
 // WOUT: the fp32 one-launch gradient (GRAD + STORE == 2) of a network with MORE than 64 outputs, with and without EPS.  The
@@ -337,7 +339,19 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_eps_kernel(NsArgs a)
 template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF, bool EPSV>
 __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_wide_kernel(NsArgs a) {
     static_assert(!BF && GRAD && STORE == 2 && MOVE == 0, "the fp32 one-launch gradient of any network only");
-    constexpr bool EPS = EPSV, PLAIN = false, WOUT = true;
+    constexpr bool EPS = EPSV, PLAIN = false, WOUT = true, DGR = false;
+#include "net_stream_body.inc"
+}
+// DGR: lnP and d lnP / d z in one launch for a DENSE inverse covariance S = L L^T (NS_GRAD_INPUT_DENSE; opt-in,
+// linna_logprob_set_dense_grad), with and without EPS.  The program's forward half ends in U = d L (the output map folded
+// into the last layer, as the dense serving program has it), so the likelihood is the trivial diagonal one in U-space:
+// the turnaround takes chi2 = sum U_c^2 over the row in LDS at any width and leaves d lnP / dU_c = -U_c / T at column c
+// of the first backward segment's input, the transposed dense map; behind it runs the ordinary dX chain.  Nothing of the
+// output map, the likelihood weights or gscale is loaded.  Kernels of their own for the same reason as EPS and WOUT.
+template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF, bool EPSV>
+__global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_dense_kernel(NsArgs a) {
+    static_assert(!BF && GRAD && STORE == 2 && MOVE == 0, "the fp32 one-launch gradient of any network only");
+    constexpr bool EPS = EPSV, PLAIN = false, WOUT = false, DGR = true;
 #include "net_stream_body.inc"
 }
 // PLAIN: the serving launch of a plain MLP (ns_program_plain, net_program.hip: WIDE and SPLIT segments only, diagonal
@@ -349,7 +363,7 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_wide_kernel(NsArgs a
 template <int R>
 __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_plain_kernel(NsArgs a) {
     constexpr int MOVE = 0, STORE = 0, ROWS = 16;
-    constexpr bool GRAD = false, BF = false, EPS = false, PLAIN = true, WOUT = false;
+    constexpr bool GRAD = false, BF = false, EPS = false, PLAIN = true, WOUT = false, DGR = false;
 #include "net_stream_body.inc"
 }
 // The plain instantiation with its step placed by hand (net_stream_body.inc, HAND): the sixteen MFMAs, four refill loads, the
@@ -363,7 +377,7 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_plain_kernel(NsArgs 
 template <int R>
 __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_placed_kernel(NsArgs a) {
     constexpr int MOVE = 0, STORE = 0, ROWS = 16;
-    constexpr bool GRAD = false, BF = false, EPS = false, PLAIN = true, WOUT = false;
+    constexpr bool GRAD = false, BF = false, EPS = false, PLAIN = true, WOUT = false, DGR = false;
 #define NS_BODY_HAND
 #include "net_stream_body.inc"
 #undef NS_BODY_HAND
@@ -372,7 +386,7 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_placed_kernel(NsArgs
 template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF>
 __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_train_bf16_kernel(NsArgs a) {
     static_assert(BF && GRAD && STORE == 3 && ROWS == 4 && MOVE == 0, "the bf16 training step only");
-    constexpr bool EPS = false, PLAIN = false, WOUT = false;
+    constexpr bool EPS = false, PLAIN = false, WOUT = false, DGR = false;
 #include "net_stream_body.inc"
 }
 // BF + MOVE == 2: the ensemble slice move's evaluation on the bf16 serving engine (linna_slice_half_step,
@@ -383,7 +397,7 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_train_bf16_kernel(Ns
 template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF>
 __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_slice_bf16_kernel(NsArgs a) {
     static_assert(BF && !GRAD && STORE == 0 && MOVE == 2, "the bf16 slice evaluation only");
-    constexpr bool EPS = false, PLAIN = false, WOUT = false;
+    constexpr bool EPS = false, PLAIN = false, WOUT = false, DGR = false;
 #define NS_BODY_SLICE_BF16
 #include "net_stream_body.inc"
 #undef NS_BODY_SLICE_BF16
@@ -398,7 +412,7 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_slice_bf16_kernel(Ns
 template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF>
 __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_grad_bf16_kernel(NsArgs a) {
     static_assert(BF && GRAD && STORE == 2 && MOVE == 0, "the bf16 one-launch gradient only");
-    constexpr bool EPS = false, PLAIN = false, WOUT = false;
+    constexpr bool EPS = false, PLAIN = false, WOUT = false, DGR = false;
 #define NS_BODY_GRAD_BF16
 #include "net_stream_body.inc"
 #undef NS_BODY_GRAD_BF16
@@ -406,7 +420,7 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_grad_bf16_kernel(NsA
 template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF>
 __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_eps_bf16_kernel(NsArgs a) {      // ... with a step size per row (EPS)
     static_assert(BF && GRAD && STORE == 2 && MOVE == 0, "the bf16 one-launch gradient only");
-    constexpr bool EPS = true, PLAIN = false, WOUT = false;
+    constexpr bool EPS = true, PLAIN = false, WOUT = false, DGR = false;
 #define NS_BODY_GRAD_BF16
 #include "net_stream_body.inc"
 #undef NS_BODY_GRAD_BF16
@@ -466,7 +480,7 @@ int launch_net_stream_pack(NsKind kind, const linna_layer_t* layers, int nl, int
 typedef void (*NsKernel)(NsArgs);
 enum NsVariant { NV_SERVE, NV_STRETCH, NV_SLICE, NV_GRAD_MLP, NV_GRAD2, NV_STORE, NV_DX, NV_TRAIN_FWD, NV_TRAIN_STEP };
 // a bf16 stream; the leapfrog in the finish with a step size per row; more than 64 outputs; the plain MLP's lean serving kernel; ... hand-placed
-enum : unsigned { NF_BF16 = 1, NF_EPS = 2, NF_WIDE = 4, NF_PLAIN = 8, NF_PLACED = 16 };
+enum : unsigned { NF_BF16 = 1, NF_EPS = 2, NF_WIDE = 4, NF_PLAIN = 8, NF_PLACED = 16, NF_DENSE = 32 };   // ... a dense covariance's one-launch gradient
 struct NsEntry { NsVariant v; unsigned flags; NsKernel k[3]; const char* what; const char* stamps_lacks; bool attr_set[3]; };
 // the three engines of one kernel template: <R, MOVE, GRAD, STORE, rows, BF (, EPS)>
 #define NS_ENGINES(K, MOVE, GRAD, STORE, ...) \
@@ -488,6 +502,8 @@ static NsEntry ns_table[] = {
     {NV_GRAD2, NF_EPS, NS_ENGINES(net_stream_eps_kernel, 0, true, 2, false), "net_stream launch"},
     {NV_GRAD2, NF_WIDE, NS_ENGINES(net_stream_wide_kernel, 0, true, 2, false, false), "net_stream wide-output gradient launch"},
     {NV_GRAD2, NF_WIDE | NF_EPS, NS_ENGINES(net_stream_wide_kernel, 0, true, 2, false, true), "net_stream wide-output gradient launch"},
+    {NV_GRAD2, NF_DENSE, NS_ENGINES(net_stream_dense_kernel, 0, true, 2, false, false), "net_stream dense-covariance gradient launch"},
+    {NV_GRAD2, NF_DENSE | NF_EPS, NS_ENGINES(net_stream_dense_kernel, 0, true, 2, false, true), "net_stream dense-covariance gradient launch"},
     {NV_GRAD2, NF_BF16, NS_ENGINES(net_stream_grad_bf16_kernel, 0, true, 2, true), "net_stream bf16 gradient launch", "bf16 gradient"},
     {NV_GRAD2, NF_BF16 | NF_EPS, NS_ENGINES(net_stream_eps_bf16_kernel, 0, true, 2, true), "net_stream bf16 gradient launch", "bf16 gradient"},
     {NV_STORE, 0, NS_ENGINES(net_stream_kernel, 0, false, 1, false), "net_stream launch"},
@@ -693,7 +709,7 @@ static void ns_store_table(NsArgs& a, const NsProgram& p, const NsNet& net, cons
 // the sign-bit gates (ns_gates) into the launch; false when they do not fit the LDS or a gate has no producer (*lds_extra:
 // the launch's LDS beyond the program's own)
 static bool ns_set_gates(NsArgs& a, const NsGates& g, const NsProgram& p, int rows, size_t* lds_extra) {
-    for (int i = 0; i < NS_MAXSEG; ++i) { a.gbit[i] = g.gbit[i]; a.mbit[i] = g.mbit[i]; }
+    for (int i = 0; i < NS_SEGCAP; ++i) { a.gbit[i] = g.gbit[i]; a.mbit[i] = g.mbit[i]; }
     a.nbw = g.ncols / 32;
     a.bits_off = (int)(g.lds0 / sizeof(float));
     *lds_extra = g.lds - p.lds_for(rows, true);
@@ -812,6 +828,31 @@ int launch_net_stream_grad2(const NsNet& net, const float* packed, const NsRun& 
     // wide: the turnaround's tail over the columns past its registers (fp32 only: the bf16 program keeps the 64-output limit)
     const unsigned flags = (bf ? NF_BF16 : p.nout > 64 ? NF_WIDE : 0) | (a.hm_p && a.hm_eps ? NF_EPS : 0);
     return ns_launch_program(NV_GRAD2, flags, a, r.B, p, rows, s, 0, lds_extra);
+}
+
+// The same for a dense inverse covariance S = L L^T (NS_GRAD_INPUT_DENSE, net_stream_dense_kernel): the stream carries the
+// output map (folded into the last layer, forward and backward) and L twice -- U = d L in front of the turnaround, its
+// transpose behind it -- so the launch takes no output map, no likelihood weights and no gscale.
+int launch_net_stream_grad_dense(const NsNet& net, const float* packed, const NsRun& r, const NsInput& in, float T, const NsGrad& gr,
+                                 int rows, const NsDense& dn, hipStream_t s) {
+    const NsProgramRef pref = ns_program(NS_GRAD_INPUT_DENSE, net.layers, net.nl, net.in_size, &dn, rows);
+    const NsProgram& p = *pref;
+    if (!p.ok || !p.dxi_ok || !p.dense || !dn.factored) { set_error("net_stream: no dense forward + dX program for this network"); return LINNA_ERR_UNSUPPORTED; }
+    if (!r.lnP || !gr.G) { set_error("net_stream: the dense one-launch gradient needs lnP and G"); return LINNA_ERR_INVALID; }
+    NsArgs a = ns_args(p, packed, r.Z, r.ldz, r.B, in.nin, true);
+    ns_set_input(a, in);
+    a.T = T; a.lnP = r.lnP;
+    a.dense = 2; a.u_col = p.u_col; a.u_same = p.u_same;
+    ns_set_grad(a, gr);
+    a.gscale = nullptr;
+    const NsGates g = ns_gates(p, net.layers, net.nl, rows);
+    for (int i = 0; i < (int)p.seg.size(); ++i) if (i >= p.nseg_f || g.gbit[i] >= 0) a.gn[i] = ns_seg_cols(p, net.layers, i);
+    size_t lds_extra = 0;
+    if (!ns_set_gates(a, g, p, rows, &lds_extra)) {
+        set_error(g.ok ? "net_stream: the dense one-launch gradient does not fit the LDS of this engine" : "net_stream: a gate of the dense one-launch gradient has no producer");
+        return LINNA_ERR_UNSUPPORTED;
+    }
+    return ns_launch_program(NV_GRAD2, NF_DENSE | (a.hm_p && a.hm_eps ? NF_EPS : 0), a, r.B, p, rows, s, 0, lds_extra);
 }
 
 // the forward + loss half of a training launch (STORE == 3): the batch rows ROWS (null: 0..B-1) of X gathered and

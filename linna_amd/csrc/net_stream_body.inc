@@ -1,7 +1,7 @@
 // The body of the whole-network kernels (net_stream.hip: net_stream_kernel, net_stream_train_bf16_kernel,
-// net_stream_slice_bf16_kernel, net_stream_grad_bf16_kernel, the EPS / PLAIN / WOUT instantiations, net_stream_placed_kernel), included
-// inside each kernel's braces; its template parameters R, MOVE, GRAD, STORE, ROWS, BF, its compile-time flags EPS, PLAIN and
-// WOUT, and its argument NsArgs a are theirs.
+// net_stream_slice_bf16_kernel, net_stream_grad_bf16_kernel, the EPS / PLAIN / WOUT / DGR instantiations, net_stream_placed_kernel), included
+// inside each kernel's braces; its template parameters R, MOVE, GRAD, STORE, ROWS, BF, its compile-time flags EPS, PLAIN,
+// WOUT and DGR, and its argument NsArgs a are theirs.
     constexpr int NT = NS_NT, NW = NS_NW;
     constexpr int RG = 32;                         // threads per walker row in prologue / reduce / finish
     constexpr bool SM = ROWS < 16;                 // 4x4x1 engine: ROWS / 4 row sets, lane = column
@@ -277,6 +277,10 @@
 #pragma unroll
     for (int i = 0; i < FIN; ++i) {
         const int cc = min(pc0 + i * RG, nout - 1);
+        if constexpr (DGR) {                       // the output map and the covariance are in the stream: nothing to load
+            fgs[i] = 0.f; fcs[i] = 1.f; fct[i] = 0.f; fw[i] = 0.f;
+            continue;
+        }
         if constexpr (GRAD && !TRB) fgs[i] = a.gscale[cc]; else fgs[i] = 0.f;
         if constexpr (PLAIN) {                     // (the launcher hands over all three)
             fcs[i] = a.cscale[cc]; fct[i] = a.cshift[cc]; fw[i] = a.w[cc];
@@ -1111,6 +1115,25 @@
                                 if (c < nout) Fr[c] = g;
                             }
                         }
+                        lds_barrier();
+                    } else if constexpr (DGR) {
+                        // ---- turnaround behind the dense segment (an instantiation of its own): U = d L sits at column u_col of
+                        // buffer P behind d (u_same), or at column 0 with d in the other buffer.  chi2 = sum U_c^2 -- the factored
+                        // form linna_logprob_eval serves -- and d lnP / dU_c = -U_c / T goes to column c of buffer P, the input of
+                        // the transposed dense map: over d (which nothing reads again) or over U itself, every thread its own
+                        // columns.  The columns past nout meet zero weights there.
+                        float* const F = act + P * ABUF + pr * LD;
+                        const float* const U = a.u_same ? F + a.u_col : F;
+                        float chi = 0.f;
+                        if (prow)
+                            for (int c = pc0; c < nout; c += RG) {
+                                const float u = U[c];
+                                chi += u * u;
+                                F[c] = -u / a.T;
+                            }
+#pragma unroll
+                        for (int o = RG / 2; o >= 1; o >>= 1) chi += __shfl_xor(chi, o, 64);
+                        lnp_grad = (-0.5f * chi) / a.T + (-0.5f * zz);
                         lds_barrier();
                     } else {
                     // ---- turnaround: the output rows (bias added) sit in buffer P.  lnP as in the finish, and

@@ -491,3 +491,15 @@ def describe_grad_bf16_program(model, rows=16):
     if n < 0:
         _lib.check(n)
     return n, buf.value.decode()
+
+
+def describe_grad_dense_program(model, rows=16, tri=2):
+    """The program of the dense one-launch gradient (``Log_prob(dense_grad="fused")``) for ``model`` with a factored inverse
+    covariance of its output width, on the engine of ``rows`` rows per workgroup under ``linna_dense_tri`` mode ``tri``, as
+    text (``linna_program_describe_grad_dense``: host-side planning, no GPU needed).  0 segments: no such program."""
+    arr = program_layers(model)
+    buf = C.create_string_buffer(8192)
+    n = _lib.load().linna_program_describe_grad_dense(arr, len(model.ops), model.in_size, model.out_size, int(tri), int(rows), buf, len(buf))
+    if n < 0:
+        _lib.check(n)
+    return n, buf.value.decode()

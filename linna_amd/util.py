@@ -330,18 +330,33 @@ class Log_prob(object):
     bf16 surface ``__call__`` serves: HMC's Metropolis test samples that surface exactly, the rounding of the force costs
     acceptance rate only.  A network without such a program (an input skip, an exp output map, more than 64 inputs or
     outputs, ...) raises ``ValueError`` with the reason when the object is first used.
+
+    ``dense_grad="fused"`` (opt-in; default ``"layered"``) makes ``evaluate_with_grad`` -- and with it every leapfrog step of
+    ``BatchedHMC`` / ``HMCSampler`` -- of a DENSE inverse covariance one launch of the whole-network kernel instead of the
+    layered route's thirty or so (linna_logprob_set_dense_grad): the Cholesky factor of the inverse covariance rides behind
+    the network as one more layer, lnP is the factored surface ``__call__`` serves.  It runs on the engines whose LDS the
+    program fits (``grad_launches(B)`` tells; other batch sizes keep the layered route).  Measured against the layered route of
+    the same build (tools/grad_dense_bench.py, DESIGN.md 3.2 "Dense covariance"): ``"fused"`` pays at every batch size it runs
+    at -- ``ChtoModelv2(26,457)`` 131 / 128 / 150 us against 164 / 163 / 194 at 128 / 1024 / 2048 rows, ``ChtoModelv2(40,1000)``
+    239 / 233 / 280 against 257 / 265 / 335 -- and is the layered route itself at 4096 rows, where the program of these two
+    networks fits no engine.  It costs one more copy of the weight stream per object.
+    A diagonal or not positive definite covariance, an exp output map, an input-skip network, ``precision="bf16"`` or a
+    program that fits no engine raises ``ValueError`` with the library's reason when the object is first used.
     """
 
     def __init__(self, data_new, invcov_new, model, y_invtransform_data, transform, temperature, loglikelihoodfunc=None,
-                 nograd=False, externalloglike=None, precision="fp32", grad_precision="fp32"):
+                 nograd=False, externalloglike=None, precision="fp32", grad_precision="fp32", dense_grad="layered"):
         if precision not in _lib.PRECISION:
             raise ValueError("Log_prob: precision must be 'fp32' or 'bf16', not %r" % (precision,))
         if grad_precision not in _lib.PRECISION:
             raise ValueError("Log_prob: grad_precision must be 'fp32' or 'bf16', not %r" % (grad_precision,))
         if grad_precision == "bf16" and precision != "bf16":
             raise ValueError("Log_prob: grad_precision='bf16' needs precision='bf16' (one lnP surface per object)")
+        if dense_grad not in ("layered", "fused"):
+            raise ValueError("Log_prob: dense_grad must be 'layered' or 'fused', not %r" % (dense_grad,))
         self.precision = precision
         self._grad_precision = grad_precision
+        self._dense_grad = dense_grad
         self.data_new = data_new
         self.invcov_new = invcov_new
         self.model = model
@@ -431,6 +446,14 @@ class Log_prob(object):
                 _lib.load().linna_logprob_destroy(h)
                 if rc in (_lib.ERR_UNSUPPORTED, _lib.ERR_INVALID):
                     raise ValueError("Log_prob(grad_precision=%r): %s" % (self._grad_precision, msg))
+                _lib.check(rc)
+        if self._dense_grad == "fused":
+            rc = _lib.load().linna_logprob_set_dense_grad(h, 1)
+            if rc != 0:
+                msg = _lib.load().linna_last_error().decode()
+                _lib.load().linna_logprob_destroy(h)
+                if rc in (_lib.ERR_UNSUPPORTED, _lib.ERR_INVALID):
+                    raise ValueError("Log_prob(dense_grad='fused'): %s" % msg)
                 _lib.check(rc)
         self._plan = dict(handle=h, keep=k, desc=d, dev=dev, nin=nin, nout=nout, net_sig=net._net_sig)
         self._ws = {}
@@ -526,6 +549,11 @@ class Log_prob(object):
     def grad_precision(self):
         """``"fp32"`` or ``"bf16"``: the form ``evaluate_with_grad`` runs (fixed when the object is created)."""
         return self._grad_precision
+
+    @property
+    def dense_grad(self):
+        """``"layered"`` or ``"fused"``: how ``evaluate_with_grad`` runs a dense covariance (fixed when the object is created)."""
+        return self._dense_grad
 
     @property
     def device_only(self):
