@@ -696,6 +696,39 @@ int linna_hmc_run_dense(linna_logprob_t* lp, const linna_hmc_state_t* st, void* 
 /* linna_hmc_find_epsilon with the same trajectories. */
 int linna_hmc_find_epsilon_dense(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, const float* Cm, int ldc, float* R0,
                                  float* EPS, int* state, int* nactive, int step_offset, int max_rounds, void* stream);
+
+/* ---- the trajectory length adapted on the device (ChEES-HMC, Hoffman, Radul & Sountsov 2021; BatchedHMC.adapt_traj).
+ * All chains share one step size eps and one trajectory length T; warm-up transition t = 1 ... M runs
+ * L = clamp(ceil(h_t T / eps), 1, max_steps) leapfrog steps, h_t the base-2 van der Corput number of t, between the two
+ * launches below.  The state is one array of linna_hmc_chees_doubles(ndim) doubles in device memory:
+ *   [0] t   [1] log T   [2] log Tbar   [3] Adam a   [4] Adam v   [5] mu   [6] Hbar   [7] log eps   [8] log epsbar
+ *   [9] the last g   [10] the last hm   [11] the valid chains of the last launch,   then m0[ndim], then m1[ndim].
+ * The caller starts it with t = 1, log T = log eps = log eps0, mu = log(10 eps0) and zeros elsewhere.
+ * linna_hmc_chees_begin: m0[d] = the mean over all B chains of X[b][d], r0[b] = sum_d (X[b][d] - m0[d])^2, in float64.
+ * linna_hmc_chees_end, behind the transition (Q, P the proposal the Metropolis launch read, alpha what it wrote): a chain is
+ * valid when alpha[b] > 0 and r0[b] and every Q[b][d], P[b][d] are finite; m1 = the mean of Q over the valid chains;
+ *   c_b = h_t (sum_d (Q - m1)^2 - r0[b]) sum_d (Q - m1) v,   g = sum alpha_b c_b / sum alpha_b over the valid chains,
+ * v = P / mass, or with Cm != NULL (the factor of a dense mass, ndim <= LINNA_HMC_DENSE_MAX_NDIM; P is then the whitened
+ * momentum and mass is not read) v = C P, both in float32 as the leapfrog forms them.  Then, with the constants below,
+ *   Adam ascent on log T with the gradient g T (bias-corrected with t); skipped, as is the average of log T, without a valid chain;
+ *   hm = B / sum_b 1 / max(alpha_b, floor) over all chains, an invalid one with alpha = 0;
+ *   Hbar = (1 - 1/(t + 10)) Hbar + (delta - hm) / (t + 10);   log eps = mu - sqrt(t) / 0.05 Hbar;
+ *   log epsbar = (1 - w) log epsbar + w log eps, w = t^-0.75, and log Tbar likewise with the new log T;
+ *   log T clamped into [log eps, log(max_steps eps)];   EPS[b] = (float)eps for every chain;   t += 1.
+ * On the launch with t == M the averages are put in place instead (the freeze): EPS[b] = (float)epsbar, log T = log Tbar.
+ * All of it in float64, no floating-point atomics and a fixed summation order: the same input gives the same bits. */
+#define LINNA_HMC_CHEES_HEAD 12
+#define LINNA_HMC_CHEES_LR 0.025
+#define LINNA_HMC_CHEES_BETA1 0.9
+#define LINNA_HMC_CHEES_BETA2 0.999
+#define LINNA_HMC_CHEES_ADAM_EPS 1e-8
+#define LINNA_HMC_CHEES_ALPHA_FLOOR 1e-3
+#define LINNA_HMC_CHEES_MAX_STEPS 64            /* the default of max_steps */
+size_t linna_hmc_chees_doubles(int ndim);       /* LINNA_HMC_CHEES_HEAD + 2 ndim; 0 for ndim < 1 */
+int linna_hmc_chees_begin(linna_ctx_t* ctx, int B, int ndim, const float* X, int ldx, double* state, double* r0, void* stream);
+int linna_hmc_chees_end(linna_ctx_t* ctx, int B, int ndim, const float* mass, const float* Cm, int ldc, const float* Q, int ldq,
+                        const float* P, int ldp, const float* alpha, const double* r0, double* state, float* EPS, int M,
+                        double delta, int max_steps, void* stream);
 int linna_step_increment(linna_ctx_t* ctx, int* step_dev, void* stream);
 
 /* Ensemble slice sampling (zeus DifferentialMove behind sampler.py:728-735): per active walker a

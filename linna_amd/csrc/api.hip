@@ -1998,6 +1998,24 @@ int linna_hmc_kick_drift_dense(linna_ctx_t*, int B, int ndim, const float* Cm, i
     TRY(hmc_dense_ndim(ndim, "hmc_kick_drift_dense"));
     return launch_hmc_kick_drift_dense(B, ndim, Cm, ldc, EPS, mul_kick, mul_drift, G, ldg, W, ldw, X, ldx, Q, ldq, S(stream));
 } LINNA_CATCH_INT
+size_t linna_hmc_chees_doubles(int ndim) try {
+    if (ndim < 1) return 0;
+    return LINNA_HMC_CHEES_HEAD + 2 * (size_t)ndim;
+} LINNA_CATCH_SIZE
+int linna_hmc_chees_begin(linna_ctx_t*, int B, int ndim, const float* X, int ldx, double* state, double* r0, void* stream) try {
+    if (B < 1 || ndim < 1 || !X || ldx < ndim || !state || !r0) { set_error("hmc_chees_begin: bad arguments"); return LINNA_ERR_INVALID; }
+    return launch_hmc_chees_begin(B, ndim, X, ldx, state, r0, S(stream));
+} LINNA_CATCH_INT
+int linna_hmc_chees_end(linna_ctx_t*, int B, int ndim, const float* mass, const float* Cm, int ldc, const float* Q, int ldq,
+                        const float* P, int ldp, const float* alpha, const double* r0, double* state, float* EPS, int M, double delta,
+                        int max_steps, void* stream) try {
+    if (B < 1 || ndim < 1 || (!mass && !Cm) || (Cm && ldc < ndim) || !Q || ldq < ndim || !P || ldp < ndim || !alpha || !r0 || !state ||
+        !EPS || max_steps < 1 || !(delta > 0.0 && delta < 1.0)) {
+        set_error("hmc_chees_end: bad arguments"); return LINNA_ERR_INVALID;
+    }
+    if (Cm) TRY(hmc_dense_ndim(ndim, "hmc_chees_end"));
+    return launch_hmc_chees_end(B, ndim, mass, Cm, ldc, Q, ldq, P, ldp, alpha, r0, state, EPS, M, delta, max_steps, S(stream));
+} LINNA_CATCH_INT
 int linna_hmc_start_eps(linna_ctx_t*, int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, int step_offset,
                         const float* lnp, const float* P0, int ldp0, const float* G, int ldg, const float* EPS, float mul_kick,
                         float mul_drift, const float* X, int ldx, float* P, int ldp, float* Q, int ldq, float* H0, void* stream) try {

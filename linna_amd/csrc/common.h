@@ -327,6 +327,11 @@ int launch_hmc_comoments(int B, int ndim, const float* X, int ldx, double* mom, 
 int launch_hmc_chol_from_comoments(int ndim, double* mom, float* Cm, int ldc, int* info, int reset, hipStream_t s);
 int launch_hmc_kick_drift_dense(int B, int ndim, const float* Cm, int ldc, const float* eps, float ek, float ed, const float* G,
                                 int ldg, float* W, int ldw, const float* X, int ldx, float* Q, int ldq, hipStream_t s);
+// the trajectory length adapted across the chains (ChEES): state = {LINNA_HMC_CHEES_HEAD words, m0[ndim], m1[ndim]} (float64)
+int launch_hmc_chees_begin(int B, int ndim, const float* X, int ldx, double* state, double* r0, hipStream_t s);
+int launch_hmc_chees_end(int B, int ndim, const float* mass, const float* Cm, int ldc, const float* Q, int ldq, const float* P, int ldp,
+                         const float* alpha, const double* r0, double* state, float* eps, int M, double delta, int max_steps,
+                         hipStream_t s);
 int launch_slice_points(const float* coords, int ldc, int ndim, const int* S, int ns, const float* DIR, int ldd,
                         const float* w, float* Q, int ldq, int nrep, hipStream_t s);
 int launch_slice_expand(const float* Z0, const float* ZL, const float* ZR, float* L, float* R, int* flags, int ns,

@@ -893,6 +893,270 @@ __global__ void hmc_kick_drift_dense_kernel(int B, int ndim, const float* __rest
     if (on1) Q[(size_t)b * ldq + d1] = q1;
 }
 
+// ------------------------------------------------------------------ the trajectory length adapted on the device (ChEES-HMC)
+// Hoffman, Radul & Sountsov 2021: all chains share one step size eps and one jittered trajectory length T; log T climbs the
+// gradient of the "change in the estimator of the expected square" criterion, which is a sum over the chains.  Two launches
+// around a warm-up transition, state = {12 words, m0[ndim], m1[ndim]} in float64 (linna_hip.h):
+//   begin: m0 = the mean position of all chains, r0[b] = |x_b - m0|^2;
+//   end:   m1 = the mean proposal of the valid chains, c_b = h_t (|q'_b - m1|^2 - r0[b]) (q'_b - m1) . v'_b, g = sum alpha c / sum alpha,
+//          Adam on log T, dual averaging of log eps on the harmonic mean of alpha, eps[b] for the next transition.
+// ONE workgroup of 16 waves each (the cross-chain sums need every chain and the state one writer), a wave per chain, lane =
+// parameter, 64 parameters at a time.  The waves stride over the chains 8 rows at a time with the loads of a round
+// unconditional -- indices clamped into the matrix, values masked or selected afterwards (hmc_moments_kernel's lesson).  A
+// chain's dot products are summed over the wave in float64 (wave_sum8_f64, a butterfly in the dense instantiation), the per-wave partials meet in LDS and are added in wave
+// order: every sum's order is fixed by (B, ndim), no atomics, the same input gives the same bits.
+constexpr int CHEES_U = 8, CHEES_V = 4, CHEES_HEAD = LINNA_HMC_CHEES_HEAD;    // rows a round: CHEES_V where a row keeps two float64 sums
+enum { CH_T = 0, CH_LOGT, CH_LOGTBAR, CH_A, CH_V, CH_MU, CH_HBAR, CH_LOGEPS, CH_LOGEPSBAR, CH_G, CH_HM, CH_NVALID };
+static_assert(CH_NVALID + 1 == CHEES_HEAD, "the layout of linna_hip.h");
+static_assert(CHEES_U == 8 && 2 * CHEES_V == 8, "wave_sum8_f64 takes eight sums");
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// Eight sums over the wave at once: three halving steps (lanes 32, 16, 8 apart) in each of which a lane hands half of its values
+// to its partner and adds the partner's share of the half it keeps, then a butterfly of the one value left over lanes 4, 2
+// and 1 apart -- 10 exchanges of a double where eight butterflies take 48 (hmc_chees_begin_kernel at 4096 chains x 33: 157 ->
+// 122 us; the end kernel did not move, it waits for its loads).  The sum of value j ends in the lanes with lane >> 3 == j and
+// is read from lane 8 j; the order is fixed.
+__device__ __forceinline__ double lane_f64(double v, int src) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), src), hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
+    return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ void wave_sum8_f64(double (&v)[8], int lane) {
+#pragma unroll
+    for (int n = 4, o = 32; n >= 1; n >>= 1, o >>= 1) {
+        const bool up = lane & o;
+#pragma unroll
+        for (int i = 0; i < n; ++i) {
+            const double send = up ? v[i] : v[i + n], keep = up ? v[i + n] : v[i];
+            v[i] = keep + __shfl_xor(send, o, 64);
+        }
+    }
+    double t = v[0];
+#pragma unroll
+    for (int o = 4; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = lane_f64(t, 8 * j);
+}
+// rows b0 .. b0 + U - 1 of column dc (< ndim); a row past the end re-reads the last one
+template <int U>
+__device__ __forceinline__ void chees_load(float (&v)[U], const float* __restrict__ X, int ldx, int B, int b0, int dc) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) v[u] = X[(size_t)min(b0 + u, B - 1) * ldx + dc];
+}
+// the base-2 van der Corput number of t: 1/2, 1/4, 3/4, 1/8, ...
+__device__ __forceinline__ double chees_halton(long long t) {
+    double h = 0.0, f = 0.5;
+    for (; t > 0; t >>= 1, f *= 0.5) if (t & 1) h += f;
+    return h;
+}
+
+__global__ __launch_bounds__(MOM_WAVES * 64) void hmc_chees_begin_kernel(int B, int ndim, const float* __restrict__ X, int ldx,
+                                                                         double* state, double* __restrict__ r0) {
+    __shared__ double part[MOM_WAVES][64];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    double* m0 = state + CHEES_HEAD;
+    for (int d0 = 0; d0 < ndim; d0 += 64) {                   // the means: lane = parameter, as hmc_moments_kernel's first pass
+        const int d = d0 + lane, dc = min(d, ndim - 1);
+        float v[MOM_ROWS];
+        double s = 0.0;
+        for (int b0 = wave * MOM_ROWS; b0 < B; b0 += MOM_WAVES * MOM_ROWS) {
+            mom_load(v, X, ldx, B, b0, dc);
+#pragma unroll
+            for (int u = 0; u < MOM_ROWS; ++u) s += b0 + u < B ? (double)v[u] : 0.0;
+        }
+        const double t = mom_block_sum(part, s, wave, lane);
+        if (wave == 0 && d < ndim) m0[d] = t / (double)B;
+    }
+    __syncthreads();                                          // (m0 is read back by every wave)
+    for (int b0 = wave * CHEES_U; b0 < B; b0 += MOM_WAVES * CHEES_U) {
+        double a[CHEES_U];
+#pragma unroll
+        for (int u = 0; u < CHEES_U; ++u) a[u] = 0.0;
+        for (int d0 = 0; d0 < ndim; d0 += 64) {
+            const int dc = min(d0 + lane, ndim - 1);
+            const bool on = d0 + lane < ndim;
+            const double m = m0[dc];
+            float v[CHEES_U];
+            chees_load(v, X, ldx, B, b0, dc);
+#pragma unroll
+            for (int u = 0; u < CHEES_U; ++u) {
+                const double t = on ? (double)v[u] - m : 0.0;
+                a[u] += t * t;
+            }
+        }
+        wave_sum8_f64(a, lane);
+#pragma unroll
+        for (int u = 0; u < CHEES_U; ++u)
+            if (lane == 0 && b0 + u < B) r0[b0 + u] = a[u];
+    }
+}
+
+// what the waves of hmc_chees_end_kernel hand to its one finishing thread
+__device__ __forceinline__ void chees_wave_out(double (*red)[MOM_WAVES], int k, double s, int wave, int lane) {
+    if (lane == 0) red[k][wave] = s;
+}
+__device__ __forceinline__ double chees_red_sum(const double (*red)[MOM_WAVES], int k) {
+    double t = 0.0;
+    for (int w = 0; w < MOM_WAVES; ++w) t += red[k][w];
+    return t;
+}
+
+// A chain is valid when alpha[b] > 0 and r0[b] and every q'[b][d], p'[b][d] are finite; an invalid chain is selected out of
+// every sum (0 x NaN is NaN) and counts as alpha = 0 in the harmonic mean.  Cm != nullptr: P holds the whitened momentum w'
+// and the velocity is C w' (hmc_kick_drift_dense_kernel's drift product, ndim <= 128: a lane holds dimensions lane and
+// lane + 64; an instantiation of its own, DENSE), else p' / mass.  The velocity is the float32 one the leapfrog moved the chain with.  On the launch with
+// t == M the averaged step size and length are put in place (the freeze).
+template <bool DENSE>
+__global__ __launch_bounds__(MOM_WAVES * 64) void hmc_chees_end_kernel(int B, int ndim, const float* __restrict__ mass,
+                                                                       const float* __restrict__ Cm, int ldc,
+                                                                       const float* __restrict__ Q, int ldq,
+                                                                       const float* __restrict__ P, int ldp,
+                                                                       const float* __restrict__ alpha, const double* __restrict__ r0,
+                                                                       double* state, float* __restrict__ eps, int M, double delta,
+                                                                       int max_steps) {
+    __shared__ double part[MOM_WAVES][64];
+    __shared__ double red[4][MOM_WAVES];
+    __shared__ float eps_out;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    double* m1 = state + CHEES_HEAD + ndim;
+    double nvalid = 0.0;
+    for (int d0 = 0; d0 < ndim; d0 += 64) {                   // m1: the column sums of q' over the valid chains
+        const int d = d0 + lane, dc = min(d, ndim - 1);
+        double s = 0.0, nv = 0.0;
+        for (int b0 = wave * CHEES_U; b0 < B; b0 += MOM_WAVES * CHEES_U) {
+            float qv[CHEES_U], pv[CHEES_U], al[CHEES_U];
+            double rr[CHEES_U];
+            chees_load(qv, Q, ldq, B, b0, dc);
+            chees_load(pv, P, ldp, B, b0, dc);
+#pragma unroll
+            for (int u = 0; u < CHEES_U; ++u) { const int bc = min(b0 + u, B - 1); al[u] = alpha[bc]; rr[u] = r0[bc]; }
+            unsigned elsewhere = 0u;                                  // bit u: row u is not finite in another group of 64 (ndim > 64 only)
+            for (int e0 = 0; e0 < ndim; e0 += 64) {
+                if (e0 == d0) continue;
+                const int ec = min(e0 + lane, ndim - 1);
+                for (int u = 0; u < CHEES_U; ++u) {
+                    const size_t bc = (size_t)min(b0 + u, B - 1);
+                    if (!(isfinite(Q[bc * ldq + ec]) && isfinite(P[bc * ldp + ec]))) elsewhere |= 1u << u;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < CHEES_U; ++u) {
+                // (a clamped column is an element of the row too)
+                const int bad = !(isfinite(qv[u]) && isfinite(pv[u])) || ((elsewhere >> u) & 1u);
+                const bool ok = b0 + u < B && al[u] > 0.f && isfinite(rr[u]) && !__any(bad);
+                s += ok && d < ndim ? (double)qv[u] : 0.0;
+                nv += ok ? 1.0 : 0.0;
+            }
+        }
+        if (d0 == 0) chees_wave_out(red, 0, nv, wave, lane);
+        const double t = mom_block_sum(part, s, wave, lane);
+        if (d0 == 0) nvalid = chees_red_sum(red, 0);
+        if (wave == 0 && d < ndim) m1[d] = nvalid > 0.0 ? t / nvalid : 0.0;
+    }
+    __syncthreads();                                          // (m1 is read back by every wave)
+    double Sac = 0.0, Sa = 0.0, Sh = 0.0;                     // sum alpha c / h_t, sum alpha, sum 1 / max(alpha, floor): wave-uniform
+    if constexpr (DENSE) {
+        const int d0 = lane, d1 = lane + 64;
+        const bool on0 = d0 < ndim, on1 = d1 < ndim;
+        const float* c0 = Cm + (size_t)min(d0, ndim - 1) * ldc;
+        const float* c1 = Cm + (size_t)min(d1, ndim - 1) * ldc;
+        const double ma = on0 ? m1[d0] : 0.0, mb = on1 ? m1[d1] : 0.0;
+        for (int b = wave; b < B; b += MOM_WAVES) {
+            const float q0 = on0 ? Q[(size_t)b * ldq + d0] : 0.f, q1 = on1 ? Q[(size_t)b * ldq + d1] : 0.f;
+            const float w0 = on0 ? P[(size_t)b * ldp + d0] : 0.f, w1 = on1 ? P[(size_t)b * ldp + d1] : 0.f;
+            const float al = alpha[b];
+            const double rr = r0[b];
+            const int bad = !(isfinite(q0) && isfinite(q1) && isfinite(w0) && isfinite(w1));
+            float v0, v1;
+            wave_tri_dot<true>(c0, c1, w0, w1, d0, d1, on0, on1, ndim, v0, v1);
+            const double e0 = on0 ? (double)q0 - ma : 0.0, e1 = on1 ? (double)q1 - mb : 0.0;
+            const double a = wave_sum_f64(e0 * e0 + e1 * e1);
+            const double bq = wave_sum_f64((on0 ? e0 * (double)v0 : 0.0) + (on1 ? e1 * (double)v1 : 0.0));
+            const bool ok = al > 0.f && isfinite(rr) && !__any(bad);
+            const double aa = ok ? (double)al : 0.0;
+            if (ok) { Sac += aa * ((a - rr) * bq); Sa += aa; }
+            Sh += 1.0 / fmax(aa, LINNA_HMC_CHEES_ALPHA_FLOOR);
+        }
+    } else {
+        for (int b0 = wave * CHEES_V; b0 < B; b0 += MOM_WAVES * CHEES_V) {
+            double AB[2 * CHEES_V];                           // per row: sum (q' - m1)^2, then sum (q' - m1) v'
+            int bad[CHEES_V];
+#pragma unroll
+            for (int u = 0; u < CHEES_V; ++u) { AB[u] = 0.0; AB[CHEES_V + u] = 0.0; bad[u] = 0; }
+            for (int d0 = 0; d0 < ndim; d0 += 64) {
+                const int dc = min(d0 + lane, ndim - 1);
+                const bool on = d0 + lane < ndim;
+                const double m = m1[dc];
+                const float ms = mass[dc];
+                float qv[CHEES_V], pv[CHEES_V];
+                chees_load<CHEES_V>(qv, Q, ldq, B, b0, dc);
+                chees_load<CHEES_V>(pv, P, ldp, B, b0, dc);
+#pragma unroll
+                for (int u = 0; u < CHEES_V; ++u) {
+                    bad[u] |= !(isfinite(qv[u]) && isfinite(pv[u]));
+                    const double e = on ? (double)qv[u] - m : 0.0;
+                    AB[u] += e * e;
+                    AB[CHEES_V + u] += on ? e * (double)(pv[u] / ms) : 0.0;
+                }
+            }
+            wave_sum8_f64(AB, lane);
+#pragma unroll
+            for (int u = 0; u < CHEES_V; ++u) {
+                const int bc = min(b0 + u, B - 1);
+                const float al = alpha[bc];
+                const double rr = r0[bc];
+                const double a = AB[u], bq = AB[CHEES_V + u];
+                const bool in = b0 + u < B, ok = in && al > 0.f && isfinite(rr) && !__any(bad[u]);
+                const double aa = ok ? (double)al : 0.0;
+                if (ok) { Sac += aa * ((a - rr) * bq); Sa += aa; }
+                if (in) Sh += 1.0 / fmax(aa, LINNA_HMC_CHEES_ALPHA_FLOOR);
+            }
+        }
+    }
+    chees_wave_out(red, 1, Sac, wave, lane);
+    chees_wave_out(red, 2, Sa, wave, lane);
+    chees_wave_out(red, 3, Sh, wave, lane);
+    __syncthreads();
+    if (threadIdx.x == 0) {                                   // the state: one thread, float64
+        const double t = state[CH_T];
+        double logT = state[CH_LOGT], logTbar = state[CH_LOGTBAR], logepsbar = state[CH_LOGEPSBAR];
+        if (nvalid > 0.0) {                                   // Adam ascent on log T with the gradient g T
+            const double g = chees_halton((long long)t) * chees_red_sum(red, 1) / chees_red_sum(red, 2), G = g * exp(logT);
+            const double b1 = LINNA_HMC_CHEES_BETA1, b2 = LINNA_HMC_CHEES_BETA2;
+            const double a = b1 * state[CH_A] + (1.0 - b1) * G, v = b2 * state[CH_V] + (1.0 - b2) * G * G;
+            const double ahat = a / (1.0 - exp(t * log(b1))), vhat = v / (1.0 - exp(t * log(b2)));
+            logT += LINNA_HMC_CHEES_LR * ahat / (sqrt(vhat) + LINNA_HMC_CHEES_ADAM_EPS);
+            state[CH_A] = a;
+            state[CH_V] = v;
+            state[CH_G] = g;
+        }
+        // dual averaging of the shared step size on the harmonic mean of alpha (t0 = 10, gamma = 0.05, kappa = 0.75)
+        const double hm = (double)B / chees_red_sum(red, 3), eta = 1.0 / (t + 10.0);
+        const double Hbar = (1.0 - eta) * state[CH_HBAR] + eta * (delta - hm);
+        const double logeps = state[CH_MU] - sqrt(t) / 0.05 * Hbar, w = exp(-0.75 * log(t));
+        logepsbar = (1.0 - w) * logepsbar + w * logeps;
+        if (nvalid > 0.0) logTbar = (1.0 - w) * logTbar + w * logT;
+        logT = fmin(fmax(logT, logeps), logeps + log((double)max_steps));
+        const bool freeze = (long long)t == (long long)M;
+        if (freeze) logT = logTbar;
+        state[CH_T] = t + 1.0;
+        state[CH_LOGT] = logT;
+        state[CH_LOGTBAR] = logTbar;
+        state[CH_HBAR] = Hbar;
+        state[CH_LOGEPS] = logeps;
+        state[CH_LOGEPSBAR] = logepsbar;
+        state[CH_HM] = hm;
+        state[CH_NVALID] = nvalid;
+        eps_out = (float)exp(freeze ? logepsbar : logeps);
+    }
+    __syncthreads();
+    const float e = eps_out;
+    for (int b = threadIdx.x; b < B; b += MOM_WAVES * 64) eps[b] = e;
+}
+
 __global__ void step_increment_kernel(int* step) { step[0] += 1; }
 
 // ------------------------------------------------------------------ ensemble slice sampling (zeus, Karamanis & Beutler 2021)
@@ -1230,6 +1494,19 @@ int launch_hmc_kick_drift_dense(int B, int ndim, const float* Cm, int ldc, const
     hipLaunchKernelGGL(hmc_kick_drift_dense_kernel, dim3((B + 3) / 4), dim3(256), 0, s, B, ndim, Cm, ldc, eps, ek, ed, G, ldg, W,
                        ldw, X, ldx, Q, ldq);
     LAUNCH_CHECK("hmc_kick_drift_dense");
+}
+int launch_hmc_chees_begin(int B, int ndim, const float* X, int ldx, double* state, double* r0, hipStream_t s) {
+    hipLaunchKernelGGL(hmc_chees_begin_kernel, dim3(1), dim3(MOM_WAVES * 64), 0, s, B, ndim, X, ldx, state, r0);
+    LAUNCH_CHECK("hmc_chees_begin");
+}
+int launch_hmc_chees_end(int B, int ndim, const float* mass, const float* Cm, int ldc, const float* Q, int ldq, const float* P, int ldp,
+                         const float* alpha, const double* r0, double* state, float* eps, int M, double delta, int max_steps,
+                         hipStream_t s) {
+    if (Cm) hipLaunchKernelGGL(hmc_chees_end_kernel<true>, dim3(1), dim3(MOM_WAVES * 64), 0, s, B, ndim, mass, Cm, ldc, Q, ldq, P, ldp,
+                               alpha, r0, state, eps, M, delta, max_steps);
+    else hipLaunchKernelGGL(hmc_chees_end_kernel<false>, dim3(1), dim3(MOM_WAVES * 64), 0, s, B, ndim, mass, Cm, ldc, Q, ldq, P, ldp,
+                            alpha, r0, state, eps, M, delta, max_steps);
+    LAUNCH_CHECK("hmc_chees_end");
 }
 int launch_slice_points(const float* coords, int ldc, int ndim, const int* S, int ns, const float* DIR, int ldd,
                         const float* w, float* Q, int ldq, int nrep, hipStream_t s) {

@@ -19,6 +19,7 @@ restatements of them (``stretch_half_step`` / ``slice_half_step`` in the repo's 
 test infrastructure, never imported here) and checks the posteriors statistically.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -1391,7 +1392,11 @@ class BatchedHMC(object):
     object in dense mode: with C = chol(M^-1) the chains carry the whitened momentum w = C^T p -- the draw is w ~ N(0, I), the
     kinetic energy |w|^2 / 2, the kick w += eps C^T g and the drift q += eps C w -- so ``self.mass`` is an array of ones,
     ``self.chol`` the device pair {C, C^T} ``[2][ndim][ld]``, and every route (``step``, ``run``, ``find_reasonable_epsilon``,
-    ``run(moments=True)`` with the co-moments in ``self.comom``) enqueues the dense launches (linna_hmc_run_dense)."""
+    ``run(moments=True)`` with the co-moments in ``self.comom``) enqueues the dense launches (linna_hmc_run_dense).
+
+    ``adapt_traj`` (or ``adapt(adapt_traj=True)``) gives all chains one step size and a trajectory length ``self.traj`` learned
+    during a warm-up of its own (ChEES-HMC, linna_hmc_chees_begin / linna_hmc_chees_end); ``run()`` without ``num_steps`` then
+    runs ``steps_for(i)`` leapfrog steps at Philox step i, under whatever mass the object has."""
 
     DENSE_MAX_NDIM = 128                        # LINNA_HMC_DENSE_MAX_NDIM
 
@@ -1430,6 +1435,8 @@ class BatchedHMC(object):
         self.m = torch.ones(self.B, dtype=torch.int32, device=self.dev)
         self.mom = None                         # run(moments=True): {n, mean[ndim], M2[ndim]} of the positions, device float64
         self.num_steps = 5                     # run()'s default (HMCSampler.sample sets it)
+        # adapt_traj(): the trajectory length run() then divides into leapfrog steps, its cap, the device state of the adaptation
+        self.traj, self.max_steps, self.chees, self._traj_eps = None, _lib.CHEES_MAX_STEPS, None, None
         self.nw, self.iteration, self._dev_steps = self.B, 0, 0     # (what _run_blocks / _Ranks.gather read; Philox step = iteration)
         self._state = None
         self.lp.evaluate_with_grad(self.x, out=self.lnp, grad=self.g)
@@ -1512,27 +1519,110 @@ class BatchedHMC(object):
         step size by dual averaging towards the acceptance ``target_accept`` and freezes it at the averaged one on transition
         Madapt + 1 (the count carries over from call to call).  ``moments``: one more launch per transition merges the B
         positions behind it into ``self.mom`` = {n, mean[ndim], M2[ndim]} (device float64, linna_hmc_run_moments); the
-        chains are bit for bit the same."""
+        chains are bit for bit the same.
+
+        Without ``num_steps`` and with a trajectory length in place (``adapt_traj`` / ``set_traj``): one C call per
+        transition, the one at Philox step i with ``steps_for(i)`` leapfrog steps, into the rows of the same block --
+        bit for bit a loop of ``run(1, num_steps=steps_for(i))``.  An explicit ``num_steps`` means what it always did."""
+        by_length = num_steps is None and self.traj is not None
         num_steps = self.num_steps if num_steps is None else int(num_steps)
         chain = torch.empty((ntrans, self.B, self.ndim), dtype=torch.float32, device=self.dev) if store else None
         lps = torch.empty((ntrans, self.B), dtype=torch.float32, device=self.dev) if store else None
-        if ntrans > 0:
-            h, ws = self.lp._ensure()["handle"], _lib.ptr(self.lp._workspace(self.B, True))
-            args = (_lib.ptr(self.eps), _lib.ptr(self.epsbar), _lib.ptr(self.Hbar),
-                    _lib.ptr(self.mu), _lib.iptr(self.m), int(Madapt), float(target_accept), self.iteration - self._dev_steps,
-                    num_steps, int(ntrans), _lib.iptr(self.naccept), _lib.ptr(self.alpha), _lib.ptr(chain), _lib.ptr(lps))
-            if self.chol is not None:
-                _lib.call("linna_hmc_run_dense", h, self._hmc_state(), ws, _lib.ptr(self.chol), self.ld, *args,
-                          _lib.ptr(self._comoments(), torch.float64) if moments else None, _lib.stream())
-                self.iteration += ntrans
-                return chain, lps
-            args = (h, self._hmc_state(), ws) + args
-            if moments:
-                _lib.call("linna_hmc_run_moments", *args, _lib.ptr(self._moments(), torch.float64), _lib.stream())
-            else:
-                _lib.call("linna_hmc_run", *args, _lib.stream())
-            self.iteration += ntrans
+        if by_length:
+            for k in range(ntrans):
+                self._enqueue(1, self.steps_for(self.iteration), chain[k:k + 1] if store else None, lps[k:k + 1] if store else None,
+                              Madapt, target_accept, moments)
+        elif ntrans > 0:
+            self._enqueue(ntrans, num_steps, chain, lps, Madapt, target_accept, moments)
         return chain, lps
+
+    def _enqueue(self, ntrans, num_steps, chain, lps, Madapt, target_accept, moments):
+        """run()'s one C call: ``ntrans`` transitions of ``num_steps`` leapfrog steps, their rows to ``chain`` / ``lps``."""
+        h, ws = self.lp._ensure()["handle"], _lib.ptr(self.lp._workspace(self.B, True))
+        args = (_lib.ptr(self.eps), _lib.ptr(self.epsbar), _lib.ptr(self.Hbar),
+                _lib.ptr(self.mu), _lib.iptr(self.m), int(Madapt), float(target_accept), self.iteration - self._dev_steps,
+                int(num_steps), int(ntrans), _lib.iptr(self.naccept), _lib.ptr(self.alpha), _lib.ptr(chain), _lib.ptr(lps))
+        if self.chol is not None:
+            _lib.call("linna_hmc_run_dense", h, self._hmc_state(), ws, _lib.ptr(self.chol), self.ld, *args,
+                      _lib.ptr(self._comoments(), torch.float64) if moments else None, _lib.stream())
+        elif moments:
+            _lib.call("linna_hmc_run_moments", h, self._hmc_state(), ws, *args, _lib.ptr(self._moments(), torch.float64), _lib.stream())
+        else:
+            _lib.call("linna_hmc_run", h, self._hmc_state(), ws, *args, _lib.stream())
+        self.iteration += ntrans
+
+    @staticmethod
+    def halton(t):
+        """The base-2 van der Corput number of ``t`` >= 1: 1/2, 1/4, 3/4, 1/8, ..."""
+        h, f, t = 0.0, 0.5, int(t)
+        while t > 0:
+            if t & 1:
+                h += f
+            f *= 0.5
+            t >>= 1
+        return h
+
+    @staticmethod
+    def traj_steps(h, T, eps, max_steps):
+        """clamp(ceil(h T / eps), 1, max_steps) in float64 (anything that is not a number >= 1: one step)."""
+        r = h * T / eps
+        return int(math.ceil(min(r, float(max_steps)))) if r >= 1.0 else 1
+
+    def steps_for(self, i):
+        """The leapfrog steps of the transition at Philox step ``i`` once ``adapt_traj`` has set ``self.traj``:
+        clamp(ceil(h_{i + 1} T / eps), 1, max_steps) -- a function of ``i`` alone, so a resumed run continues the sequence."""
+        if self.traj is None:
+            raise ValueError("steps_for: no trajectory length (adapt_traj or set_traj first)")
+        return self.traj_steps(self.halton(int(i) + 1), self.traj, self._traj_eps, self.max_steps)
+
+    def set_traj(self, traj, max_steps=None):
+        """``run()`` without ``num_steps`` divides the trajectory length ``traj`` by the step size all chains share
+        (``self.eps[0]``) from now on; ``traj`` None: back to ``self.num_steps``."""
+        if traj is None:
+            self.traj = self._traj_eps = None
+            return
+        traj, max_steps = float(traj), int(self.max_steps if max_steps is None else max_steps)
+        eps = float(self.eps[0])
+        if not (np.isfinite(traj) and traj > 0 and np.isfinite(eps) and eps > 0 and max_steps >= 1):
+            raise ValueError("set_traj: trajectory length %r, step size %r, max_steps %r" % (traj, eps, max_steps))
+        self.traj, self._traj_eps, self.max_steps = traj, eps, max_steps
+
+    def adapt_traj(self, M, target_accept=0.65, max_steps=None):
+        """ChEES-HMC's warm-up (Hoffman, Radul & Sountsov 2021; include/linna_hip.h states the scheme): ``M`` transitions in
+        which all chains share one step size -- it starts at the median of ``find_reasonable_epsilon()``'s and is adapted by
+        dual averaging on the harmonic mean of the acceptance probabilities -- and one trajectory length T, which climbs
+        the gradient of the ChEES criterion by Adam.  Transition t runs clamp(ceil(h_t T / eps), 1, max_steps) leapfrog steps
+        between linna_hmc_chees_begin and linna_hmc_chees_end under the mass this object has; the host reads the 12 state
+        words once per transition to know that number.  The last transition puts the averaged step size and length in
+        place: ``self.eps[:]``, ``self.traj``; ``run()`` without ``num_steps`` then runs ``steps_for(i)`` steps.  Nothing is
+        stored; ``self.naccept`` counts the warm-up's transitions.  Returns (traj, eps)."""
+        M, max_steps = int(M), int(_lib.CHEES_MAX_STEPS if max_steps is None else max_steps)
+        if M < 1 or max_steps < 1:
+            raise ValueError("adapt_traj: M = %r warm-up transitions, max_steps = %r: both at least 1" % (M, max_steps))
+        self.traj = self._traj_eps = None
+        self.find_reasonable_epsilon()
+        eps0 = float(torch.median(self.eps))
+        if not (np.isfinite(eps0) and eps0 > 0):
+            raise ValueError("adapt_traj: the median step size of the search is %r" % (eps0,))
+        self.eps.fill_(eps0)
+        head = np.zeros(int(_lib.load().linna_hmc_chees_doubles(self.ndim)), np.float64)
+        head[0], head[1], head[5], head[7] = 1.0, math.log(eps0), math.log(10.0 * eps0), math.log(eps0)
+        self.chees = torch.as_tensor(head, device=self.dev)
+        r0 = torch.empty(self.B, dtype=torch.float64, device=self.dev)
+        dense = (None, 0) if self.chol is None else (_lib.ptr(self.chol), self.ld)
+        D = lambda t: _lib.ptr(t, torch.float64)
+        for t in range(1, M + 1):
+            st = self.chees[:_lib.CHEES_HEAD].tolist()        # (the one read of the transition: log T and log eps)
+            L = self.traj_steps(self.halton(t), math.exp(st[1]), math.exp(st[7]), max_steps)
+            _lib.call("linna_hmc_chees_begin", self.ctx, self.B, self.ndim, _lib.ptr(self.x), self.ld, D(self.chees), D(r0), _lib.stream())
+            self._enqueue(1, L, None, None, 0, target_accept, False)
+            _lib.call("linna_hmc_chees_end", self.ctx, self.B, self.ndim, _lib.ptr(self.mass), *dense, _lib.ptr(self.q), self.ld,
+                      _lib.ptr(self.p), self.ld, _lib.ptr(self.alpha), D(r0), D(self.chees), _lib.ptr(self.eps), M,
+                      float(target_accept), max_steps, _lib.stream())
+        st = self.chees[:_lib.CHEES_HEAD].tolist()
+        self.epsbar.copy_(self.eps)
+        self.set_traj(math.exp(st[1]), max_steps)
+        return self.traj, self._traj_eps
 
     def _moments(self):
         if self.mom is None:
@@ -1579,7 +1669,7 @@ class BatchedHMC(object):
         _lib.call("linna_hmc_mass_from_moments", self.ctx, self.ndim, _lib.ptr(self._moments(), torch.float64), _lib.ptr(self.mass),
                   int(bool(reset)), _lib.stream())
 
-    def adapt(self, Madapt, target_accept=0.65, adapt_mass=True):
+    def adapt(self, Madapt, target_accept=0.65, adapt_mass=True, adapt_traj=False, max_steps=None):
         """The whole warm-up: ``find_reasonable_epsilon()`` and ``Madapt`` transitions of dual averaging plus the one that puts
         the averaged step size in place.  ``adapt_mass``: Stan's windowed scheme around them -- in every window of
         ``mass_windows(Madapt)`` the positions of all chains are accumulated on the device; at its end
@@ -1590,7 +1680,16 @@ class BatchedHMC(object):
         ``adapt_mass="dense"`` (``True`` and ``"diag"`` are the scheme above): the same windows and segments for a dense mass.
         The object enters dense mode from its diagonal mass (C = diag(1 / sqrt(m))); the windows accumulate co-moments about
         the first chain's position; at a window's end ``self.chol`` <- the Cholesky factor of the pooled covariance
-        (``chol_from_comoments``).  A covariance that cannot be factored keeps the factor before it, with a warning."""
+        (``chol_from_comoments``).  A covariance that cannot be factored keeps the factor before it, with a warning.
+
+        ``adapt_traj``: behind all of the above ``adapt_traj(Madapt, target_accept, max_steps)`` adapts one shared step size
+        and the trajectory length under the mass the sequence above produced."""
+        windows = self._adapt(Madapt, target_accept, adapt_mass)
+        if adapt_traj:
+            self.adapt_traj(Madapt, target_accept, max_steps)
+        return windows
+
+    def _adapt(self, Madapt, target_accept, adapt_mass):
         Madapt = int(Madapt)
         adapt_mass = self.adapt_mass_mode(adapt_mass)
         dense = adapt_mass == "dense"
@@ -1890,7 +1989,12 @@ class HMCSampler(object):
     ``m[ndim][ndim]`` (the starting mass, or with a fixed ``samp_eps`` the mass of the run).  After such a run ``self.cov`` is
     C C^T (float64), the inverse of the mass, and ``self.mass`` = 1 / diag(cov); the file then also holds
     ``metric="dense"`` and ``chol[ndim][ndim]``, and is handed only to a run of the same metric (files without ``metric``
-    are diagonal)."""
+    are diagonal).
+
+    ``adapt_traj=True`` adapts one step size for all walkers and the trajectory length behind that warm-up
+    (``BatchedHMC.adapt_traj``, at most ``max_steps`` leapfrog steps an iteration; ``samp_steps`` is then not used).  The file
+    is then written and read with or without ``adapt_mass`` and also holds ``traj``, ``max_steps`` and ``iteration``; a resumed
+    ``adapt_traj`` run takes it only with a finite positive ``traj`` and continues the sequence of step counts."""
 
     ADAPT_FILE = "chhmc_adapt.npz"
 
@@ -1906,7 +2010,7 @@ class HMCSampler(object):
 
     def sample(self, pool, nsamp, samp_steps=0, samp_eps=0, Madapt=1000, outdir="./", progress=False, overwrite=False,
                ntimes=10, tautol=0.01, method="emcee", incremental=True, meanshift=0.1, stdshift=0.1, nk=2, ncheck=100,
-               burnin=100, profile=None, adapt_mass=False):
+               burnin=100, profile=None, adapt_mass=False, adapt_traj=False, max_steps=64):
         if method not in ("emcee", "hmc"):
             # sampler.py's "nuts" branch is unreachable in the reference and not built here
             raise NotImplementedError(method)
@@ -1918,6 +2022,14 @@ class HMCSampler(object):
         if hmc and adapt_mass and samp_eps:
             raise ValueError("adapt_mass with a fixed samp_eps = %r: the mass is adapted together with the step sizes "
                              "(samp_eps 0 or None)" % (samp_eps,))
+        if adapt_traj:
+            if not hmc:
+                raise ValueError("adapt_traj with method = %r: the trajectory length belongs to method=\"hmc\"" % (method,))
+            if samp_eps:
+                raise ValueError("adapt_traj with a fixed samp_eps = %r: the trajectory length is adapted together with the "
+                                 "step size (samp_eps 0 or None)" % (samp_eps,))
+            if int(max_steps) < 1 or int(Madapt) < 1:
+                raise ValueError("adapt_traj: max_steps = %r, Madapt = %r: both at least 1" % (max_steps, Madapt))
         import time
         t_start = time.perf_counter()
         prof = _Prof(profile)
@@ -1931,7 +2043,8 @@ class HMCSampler(object):
             return store
         x0 = self.x0
         resume = False
-        # the warm-up's result next to the chain file (single-rank runs; written and read with adapt_mass only, removed with the chain)
+        # the warm-up's result next to the chain file (single-rank runs; written and read with adapt_mass or adapt_traj only,
+        # removed with the chain)
         sidecar = os.path.join(outdir, self.ADAPT_FILE) if hmc and rk.real_world == 1 else None
         if sidecar and overwrite and os.path.exists(sidecar):
             os.remove(sidecar)
@@ -1965,7 +2078,8 @@ class HMCSampler(object):
             ens.naccept.zero_()
         if hmc:
             ens = self._hmc_chains(rk, x0, samp_steps, samp_eps, Madapt, prof, adapt_mass=adapt_mass,
-                                   sidecar=sidecar if adapt_mass else None, resume=resume)
+                                   sidecar=sidecar if adapt_mass or adapt_traj else None, resume=resume, adapt_traj=bool(adapt_traj),
+                                   max_steps=max_steps, stored=sum(len(c) for c in store.chain) if resume else 0)
             self.sampler = ens
         else:
             ens.set_state(rk.mine(x0))
@@ -2012,7 +2126,8 @@ class HMCSampler(object):
         return store
 
 
-    def _hmc_chains(self, rk, x0, samp_steps, samp_eps, Madapt, prof, adapt_mass=False, sidecar=None, resume=False):
+    def _hmc_chains(self, rk, x0, samp_steps, samp_eps, Madapt, prof, adapt_mass=False, sidecar=None, resume=False,
+                    adapt_traj=False, max_steps=64, stored=0):
         """The chains of ``method="hmc"`` (sampler.py:491-493: ``HamiltonianMove(dlnp, samp_steps, samp_eps, m)``), one per
         walker of this rank, ready for ``_run_blocks``.  ``m`` is the move's ``cov``: momenta ~ N(0, m), drift p / m
         (``_hmc_matrix``, sampler.py:311-320; tests/golden/hmc_move.npz).  ``samp_eps`` > 0: that step size for every chain,
@@ -2021,7 +2136,11 @@ class HMCSampler(object):
         puts the averaged step size in place -- none of them stored or counted; the convergence loop then runs on frozen
         step sizes.  ``samp_steps`` 0 means 5.  ``adapt_mass``: ``m`` is the starting mass of ``BatchedHMC.adapt``'s windowed
         scheme; ``sidecar`` (a file name): where its result is kept, and taken from in place of a warm-up when ``resume`` says
-        the chain file was continued and the file holds ``ndim`` masses and one step size per walker."""
+        the chain file was continued and the file holds ``ndim`` masses and one step size per walker.  ``adapt_traj``:
+        ``BatchedHMC.adapt_traj`` behind that warm-up -- one step size for all chains and a trajectory length; ``samp_steps``
+        is then not used, the file also holds ``traj``, ``max_steps`` and ``iteration`` (the Philox step of the first stored
+        transition) and is taken only with a finite positive ``traj``; such a resumed run goes on at Philox step
+        ``iteration + stored``, so that ``steps_for`` continues the sequence the first run began."""
         if samp_eps is not None and samp_eps < 0:
             raise ValueError("samp_eps = %r: a step size is positive (0 or None: found and adapted per chain)" % (samp_eps,))
         adapt_mass = BatchedHMC.adapt_mass_mode(adapt_mass)
@@ -2038,16 +2157,18 @@ class HMCSampler(object):
         if not bool(torch.isfinite(ens.lnp).all()):
             raise ValueError("initial state has non-finite log-probability")
         ens.num_steps = int(samp_steps) if samp_steps else 5
+        if adapt_traj and samp_steps:
+            print("samp_steps = %r is ignored: adapt_traj chooses the leapfrog steps of every transition" % (samp_steps,), flush=True)
         if samp_eps:
-            if adapt_mass:
-                raise ValueError("adapt_mass with a fixed samp_eps = %r" % (samp_eps,))
+            if adapt_mass or adapt_traj:
+                raise ValueError("adapt_mass / adapt_traj with a fixed samp_eps = %r" % (samp_eps,))
             ens.eps.fill_(float(samp_eps))
             self._keep_mass(ens, m)
             if ens.chol is None:
                 self.mass = m.copy()
             return ens
         metric = "dense" if adapt_mass == "dense" or ens.chol is not None else "diag"
-        kept = self._load_adaptation(sidecar, ens, metric) if resume and sidecar else None
+        kept = self._load_adaptation(sidecar, ens, metric, traj=adapt_traj) if resume and sidecar else None
         if kept is not None:
             if metric == "dense":
                 ens._set_chol(kept["chol"])
@@ -2055,10 +2176,13 @@ class HMCSampler(object):
                 ens.mass.copy_(torch.as_tensor(kept["mass"], device=ens.dev))
             ens.eps.copy_(torch.as_tensor(kept["eps"], device=ens.dev))
             ens.epsbar.copy_(ens.eps)
+            if adapt_traj:
+                ens.set_traj(kept["traj"], kept["max_steps"])
+                ens.iteration = kept["iteration"] + int(stored)
             print("hmc step sizes and mass from %s" % sidecar, flush=True)
         else:
             with prof.host("adapt"), _lib.stage("run_mcmc.hmc_adapt"):
-                ens.adapt(int(Madapt), adapt_mass=adapt_mass)
+                ens.adapt(int(Madapt), adapt_mass=adapt_mass, adapt_traj=adapt_traj, max_steps=max_steps)
                 ens.naccept.zero_()
         e = ens.eps.cpu().numpy()
         self._keep_mass(ens, m)
@@ -2066,6 +2190,10 @@ class HMCSampler(object):
         extra = {}
         if ens.chol is not None:
             extra = dict(metric="dense", chol=ens.chol[0, :, :ens.ndim].cpu().numpy())
+        if adapt_traj:
+            extra.update(traj=np.float64(ens.traj), max_steps=np.int64(ens.max_steps), iteration=np.int64(ens.iteration))
+            print("hmc trajectory length %.4g: %.4g step sizes, at most %d leapfrog steps"
+                  % (ens.traj, ens.traj / ens._traj_eps, ens.max_steps), flush=True)
         if sidecar and kept is None:
             np.savez(sidecar, mass=mm, eps=e, num_steps=np.int64(ens.num_steps), Madapt=np.int64(Madapt), **extra)
         print("hmc step sizes %s: min %.3g median %.3g max %.3g; mass min %.3g median %.3g max %.3g%s"
@@ -2083,9 +2211,10 @@ class HMCSampler(object):
             self.mass = ens.mass.cpu().numpy().astype(np.float64)
 
     @staticmethod
-    def _load_adaptation(name, ens, metric="diag"):
+    def _load_adaptation(name, ens, metric="diag", traj=False):
         """{mass, eps} (``metric`` "dense": and chol) of ``chhmc_adapt.npz`` if it is there, holds that metric (a file
-        without the word is diagonal) and fits these chains, else None."""
+        without the word is diagonal) and fits these chains, else None.  ``traj``: and {traj, max_steps, iteration}, None
+        unless the file holds a finite positive trajectory length."""
         if not os.path.exists(name):
             return None
         with np.load(name) as f:
@@ -2095,13 +2224,20 @@ class HMCSampler(object):
                 return None
             mass, eps = np.asarray(f["mass"], np.float32), np.asarray(f["eps"], np.float32)
             chol = np.asarray(f["chol"], np.float32) if metric == "dense" and "chol" in f.files else None
+            tr = None
+            if traj:
+                if not {"traj", "max_steps"} <= set(f.files):
+                    return None
+                tr = dict(traj=float(f["traj"]), max_steps=int(f["max_steps"]), iteration=int(f["iteration"]) if "iteration" in f.files else 0)
+                if not (np.isfinite(tr["traj"]) and tr["traj"] > 0 and tr["max_steps"] >= 1 and tr["iteration"] >= 0):
+                    return None
         ok = mass.shape == (ens.ndim,) and eps.shape == (ens.B,) and np.isfinite(mass).all() and (mass > 0).all() \
             and np.isfinite(eps).all() and (eps > 0).all()
         if metric == "dense":
             ok = ok and chol is not None and chol.shape == (ens.ndim, ens.ndim) and bool(np.isfinite(chol).all()) \
                 and bool((np.diag(chol) > 0).all())
-            return dict(mass=mass, eps=eps, chol=chol) if ok else None
-        return dict(mass=mass, eps=eps) if ok else None
+            return dict(mass=mass, eps=eps, chol=chol, **(tr or {})) if ok else None
+        return dict(mass=mass, eps=eps, **(tr or {})) if ok else None
 
 
 class ZeusSampler(object):
