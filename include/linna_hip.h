@@ -846,6 +846,47 @@ int linna_acorr_tau(linna_ctx_t* ctx, const float* CT, int ndim, int nwp, int nw
 int linna_chain_meanstd(linna_ctx_t* ctx, const float* CT, int ndim, int nwp, int nws, int64_t t0, int64_t tm, int64_t t1,
                         double* out, void* stream);
 
+/* ------------------------------------------------------------------ agreement BETWEEN chains: split-R-hat and multi-chain ESS
+ * (autocorr.hip; additive entries, LINNA_ABI_VERSION unchanged).  The statistics above are within-chain: they remove every
+ * walker's own mean.  Independent chains (method="hmc") also have to agree with each other.  All float64.
+ *
+ * Split-R-hat (Gelman et al., BDA3; Vehtari et al. 2021 without the rank normalisation and the folding, which need a sort
+ * over the chain).  Window [lo, hi) of CT, N = hi - lo rows, n = N / 2 (integer), ALL nw walkers (lanes 0 .. nw - 1).  Split
+ * chain 2j = rows [lo, lo + n) of walker j, split chain 2j + 1 = rows [hi - n, hi) (N odd: the middle row is dropped).  Per
+ * parameter, with xbar_c and s2_c (ddof 1) the mean and variance of split chain c:
+ *     W = mean_c s2_c,   B / n = var_c(xbar_c) (ddof 1 over the 2 nw split chains),   var+ = (n - 1) / n W + B / n,
+ *     R-hat = sqrt(var+ / W).
+ * W = 0, or a non-finite value in a row of the two halves, gives R-hat = NaN for that parameter only.  n < 2: LINNA_ERR_INVALID.
+ *
+ *   linna_chain_block_moments : M[b][2][ndim][nwp] float64, one record per complete block of LINNA_RHAT_BLOCK rows:
+ *                               M[b][0] = sum of x, M[b][1] = sum of x^2 over rows [b RB, (b + 1) RB) per lane, x relative to
+ *                               the series' row 0 as everywhere in this file.  Fills the records [b0, b1) from CT (rows up to
+ *                               b1 RB must be stored).
+ *   linna_chain_rhat          : out[ndim][4] = { R-hat, W, var+, grand mean }.  Per lane the sums of each half are formed from
+ *                               ragged head rows (CT), whole blocks (M, blocks < nblocks only), ragged tail rows (CT): a check
+ *                               reads 16 bytes per lane and 128 rows instead of 512.  M = NULL or nblocks = 0: everything
+ *                               from CT.  One workgroup per parameter; every sum has a fixed order, no floating-point atomics:
+ *                               two calls give the same bits.
+ *
+ * Multi-chain ESS (Stan's estimator) on the UNSPLIT chains of the lanes the running sums cover: nlive chains of N rows.
+ *     acov_j(k) = (1 / N) sum_t (x_t - xbar_j)(x_{t+k} - xbar_j),   A_k = mean_j acov_j(k),   W = N / (N - 1) A_0,
+ *     var+ = (N - 1) / N W + var_j(xbar_j) (ddof 1; 0 for one chain),   rho_k = 1 - (W - A_k) / var+,
+ *     P_t = rho_2t + rho_2t+1 for t = 0, 1, ... while P_t > 0 (Geyer's initial positive sequence), made monotone
+ *     (P_t = min(P_t, P_t-1)),   tau = -1 + 2 sum_{t <= T} P_t, at least 1 / log10(nlive N),   ESS = nlive N / tau.
+ * A non-finite W or var+, or var+ <= 0, gives ESS = NaN for that parameter only.
+ *
+ *   linna_acorr_ess           : the arguments of linna_acorr_tau less c; the same sums Ssum / Tsum.  out[ndim] = ESS,
+ *                               out[ndim + d] = T (the last pair used; -1: none), out[2 ndim + d] = 1 when every pair of
+ *                               the lags 0..kuse is positive and kuse < hi - lo - 1 (the caller adds lags and asks again),
+ *                               else 0.  scratch: linna_acorr_ess_scratch_bytes(ndim, nwc, kuse) bytes. */
+#define LINNA_RHAT_BLOCK 128
+int linna_chain_block_moments(linna_ctx_t* ctx, const float* CT, int ndim, int nwp, int64_t b0, int64_t b1, double* M, void* stream);
+int linna_chain_rhat(linna_ctx_t* ctx, const float* CT, int ndim, int nwp, int nw, int64_t lo, int64_t hi, const double* M,
+                     int64_t nblocks, double* out, void* stream);
+size_t linna_acorr_ess_scratch_bytes(int ndim, int nwc, int kuse);
+int linna_acorr_ess(linna_ctx_t* ctx, const float* CT, int ndim, int nwp, int nwc, int nlive, int64_t lo, int64_t hi, int kuse,
+                    const double* Ssum, const double* Tsum, double* scratch, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

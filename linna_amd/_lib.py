@@ -12,6 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LINNA_LIB_PATH") or os.path.join(_HERE, "liblinna_hip.so")   # (LINNA_LIB_PATH: a diagnostic build, tools/ns_stamps.py)
 ABI_VERSION = 12
+RHAT_BLOCK = 128        # LINNA_RHAT_BLOCK: chain rows per block-moment record of linna_chain_block_moments / linna_chain_rhat
 
 c_float_p = C.c_void_p   # device pointers travel as void*
 c_int_p = C.c_void_p
@@ -183,6 +184,10 @@ _SIGNATURES = {
     "linna_acorr_scratch_bytes": (_SZ, [_I, _I, _I]),
     "linna_acorr_tau": (_I, [_V, _V, _I, _I, _I, _I, _I64, _I64, _I, _V, _V, _D, _V, _V, _V]),
     "linna_chain_meanstd": (_I, [_V, _V, _I, _I, _I, _I64, _I64, _I64, _V, _V]),
+    "linna_chain_block_moments": (_I, [_V, _V, _I, _I, _I64, _I64, _V, _V]),
+    "linna_chain_rhat": (_I, [_V, _V, _I, _I, _I, _I64, _I64, _V, _I64, _V, _V]),
+    "linna_acorr_ess_scratch_bytes": (_SZ, [_I, _I, _I]),
+    "linna_acorr_ess": (_I, [_V, _V, _I, _I, _I, _I, _I64, _I64, _I, _V, _V, _V, _V, _V]),
     "linna_hmc_init": (_I, [_V, _I, _I, _V, _U64, _V, _V, _V, _I, _V, _I, _V, _V]),
     "linna_hmc_start": (_I, [_V, _I, _I, _V, _U64, _V, _V, _V, _I, _V, _I, _F, _F, _V, _I, _V, _I, _V, _I, _V, _V]),
     "linna_hmc_kick_drift": (_I, [_V, _I, _I, _V, _F, _F, _V, _I, _V, _I, _V, _I, _V]),

@@ -1526,6 +1526,33 @@ int linna_chain_meanstd(linna_ctx_t*, const float* CT, int ndim, int nwp, int nw
     }
     return launch_chain_meanstd(CT, ndim, nwp, nws, t0, tm, t1, out, S(stream));
 } LINNA_CATCH_INT
+int linna_chain_block_moments(linna_ctx_t*, const float* CT, int ndim, int nwp, int64_t b0, int64_t b1, double* M, void* stream) try {
+    if (!CT || !M || !ac_shape_ok(ndim, nwp) || b0 < 0 || b1 < b0 || b1 > 0x7fffff00 / LINNA_RHAT_BLOCK ||
+        (int64_t)ndim * (nwp / 64) > 0x7fffffff) {
+        set_error("chain_block_moments: bad arguments"); return LINNA_ERR_INVALID;
+    }
+    return launch_chain_block_moments(CT, ndim, nwp, b0, b1, M, S(stream));
+} LINNA_CATCH_INT
+int linna_chain_rhat(linna_ctx_t*, const float* CT, int ndim, int nwp, int nw, int64_t lo, int64_t hi, const double* M, int64_t nblocks,
+                     double* out, void* stream) try {
+    if (!CT || !out || !ac_shape_ok(ndim, nwp) || nw < 1 || nw > nwp || lo < 0 || hi < lo || (hi - lo) / 2 < 2 || nblocks < 0 ||
+        hi > 0x7fffff00) {
+        set_error("chain_rhat: bad arguments (the window [lo, hi) needs two halves of at least 2 rows)"); return LINNA_ERR_INVALID;
+    }
+    return launch_chain_rhat(CT, ndim, nwp, nw, lo, hi, M, nblocks, out, S(stream));
+} LINNA_CATCH_INT
+size_t linna_acorr_ess_scratch_bytes(int ndim, int nwc, int kuse) try {
+    if (ndim < 1 || nwc < 64 || (nwc & 63) || kuse < 0) return 0;
+    return acorr_ess_scratch_doubles(ndim * nwc, kuse, ndim) * sizeof(double);
+} LINNA_CATCH_SIZE
+int linna_acorr_ess(linna_ctx_t*, const float* CT, int ndim, int nwp, int nwc, int nlive, int64_t lo, int64_t hi, int kuse,
+                    const double* Ssum, const double* Tsum, double* scratch, double* out, void* stream) try {
+    if (!CT || !Ssum || !Tsum || !scratch || !out || !ac_shape_ok(ndim, nwp) || !ac_cover_ok(nwp, nwc, nlive) || lo < 0 || hi <= lo ||
+        kuse < 0 || (int64_t)kuse > hi - lo - 1 || kuse / 32 + 1 > 65535 || hi > 0x7fffff00) {
+        set_error("acorr_ess: bad arguments (0 <= kuse <= hi - lo - 1)"); return LINNA_ERR_INVALID;
+    }
+    return launch_acorr_ess(CT, ndim, nwp, nwc, nlive, lo, hi, kuse, Ssum, Tsum, scratch, out, S(stream));
+} LINNA_CATCH_INT
 
 }  // extern "C"
 

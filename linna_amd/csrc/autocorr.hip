@@ -22,6 +22,14 @@
 // Bound: the update is balanced between the float64 vector pipe (one v_fma_f64 per (anchor row, lag, series): MI355X has no
 // faster float64 matrix rate than vector rate) and memory (each wave re-reads a window of TT + R - 1 chain rows per TT x R
 // products from L2); everything else here is one pass over K x series values.
+//
+// All of the above is within-chain: every series loses its own mean.  Independent chains (method="hmc") also have to agree
+// with each other, so the file ends with the two between-chain statistics include/linna_hip.h defines: split-R-hat over all
+// walkers, from float64 block moments M[b][2][d][w] (sum and sum of squares of every complete block of LINNA_RHAT_BLOCK rows,
+// x relative to row 0 as above) plus the ragged rows at the ends of the two halves, so that a check does not re-read the
+// chain; and Stan's multi-chain effective sample size, from the same S, T and head / tail sums as tau with the normalisation
+// left out (acov_j(k) averaged over the chains, Geyer's initial monotone sequence).  Both reduce over the lanes with
+// wave_sum_f64 and fixed orders: no floating-point atomics, the same bits at every call.
 #include "common.h"
 #include <math.h>
 
@@ -279,7 +287,221 @@ __global__ __launch_bounds__(256) void chain_meanstd_kernel(const float* __restr
     }
 }
 
+// ------------------------------------------------------------------ split-R-hat (include/linna_hip.h states the definition)
+// block moments: M[b][0][d][lane] = sum of x, M[b][1][d][lane] = sum of x^2 over rows [b RB, (b + 1) RB), RB = LINNA_RHAT_BLOCK,
+// x relative to the series' row 0.  One thread per lane (all nwp lanes of every parameter), one block record per blockIdx.y.
+__global__ __launch_bounds__(64) void chain_block_moments_kernel(const float* __restrict__ CT, int nd, int nwp, int64_t b0,
+                                                                 double* __restrict__ M) {
+    const size_t ns = (size_t)nd * nwp;
+    const size_t s = (size_t)blockIdx.x * 64 + threadIdx.x;           // = d * nwp + lane
+    const int64_t b = b0 + blockIdx.y;
+    const float* col = CT + s;
+    const double ref = (double)col[0];
+    double s1 = 0.0, s2 = 0.0;
+#pragma unroll 8
+    for (int j = 0; j < LINNA_RHAT_BLOCK; ++j) {
+        const double v = (double)col[(size_t)(b * LINNA_RHAT_BLOCK + j) * ns] - ref;
+        s1 += v; s2 = __builtin_fma(v, v, s2);
+    }
+    M[(size_t)(2 * b) * ns + s] = s1;
+    M[(size_t)(2 * b + 1) * ns + s] = s2;
+}
+
+constexpr int RH_WAVES = 16;    // wavefronts of the R-hat workgroup: they share the rows and records of 64 lanes
+
+// One workgroup per parameter walks the lane groups (64 walkers each).  Per group its RH_WAVES wavefronts split the rows and
+// the block records of both halves [lo, lo + n) and [hi - n, hi) between them (wave q: every RH_WAVES-th item), the partial
+// sums meet in LDS and are added in wave order; wave 0 turns them into the mean and the variance of the two split chains
+// of every walker and keeps the sums over the split chains, which a wavefront reduction and lane 0 finish.  Every sum has
+// a fixed order: two calls give the same bits.  Means are taken relative to the parameter's reference CT[0][d][0].
+__global__ __launch_bounds__(64 * RH_WAVES) void chain_rhat_kernel(const float* __restrict__ CT, int nd, int nwp, int nw, int64_t lo,
+                                                                   int64_t hi, const double* __restrict__ M, int64_t nblocks,
+                                                                   double* __restrict__ out) {
+    __shared__ double part[RH_WAVES][4][64];
+    const int lane = threadIdx.x & 63, q = threadIdx.x >> 6, d = blockIdx.x;
+    const size_t ns = (size_t)nd * nwp;
+    const int64_t n = (hi - lo) / 2;
+    const double refd = (double)CT[(size_t)d * nwp];
+    double am = 0.0, am2 = 0.0, av = 0.0, bad = 0.0;                  // (wave 0) over this lane's split chains
+    for (int g = 0; g < nwp / 64; ++g) {
+        const int w = g * 64 + lane;
+        const size_t s = (size_t)d * nwp + w;
+        const float* col = CT + s;
+        const double ref = (double)col[0];
+        double sum[4];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int64_t r0 = h ? hi - n : lo, r1 = r0 + n;
+            int64_t bf = (r0 + LINNA_RHAT_BLOCK - 1) / LINNA_RHAT_BLOCK, bl = r1 / LINNA_RHAT_BLOCK;
+            if (bl > nblocks) bl = nblocks;
+            if (!M || bl <= bf) bf = bl = 0;
+            const int64_t h1 = bl > bf ? bf * LINNA_RHAT_BLOCK : r1;  // rows [r0, h1) and [t0, r1) come from the chain
+            const int64_t t0 = bl > bf ? bl * LINNA_RHAT_BLOCK : r1;
+            double s1 = 0.0, s2 = 0.0;
+#pragma unroll 4
+            for (int64_t r = r0 + q; r < h1; r += RH_WAVES) {
+                const double v = (double)col[(size_t)r * ns] - ref;
+                s1 += v; s2 = __builtin_fma(v, v, s2);
+            }
+#pragma unroll 4
+            for (int64_t b = bf + q; b < bl; b += RH_WAVES) {
+                s1 += M[(size_t)(2 * b) * ns + s];
+                s2 += M[(size_t)(2 * b + 1) * ns + s];
+            }
+#pragma unroll 4
+            for (int64_t r = t0 + q; r < r1; r += RH_WAVES) {
+                const double v = (double)col[(size_t)r * ns] - ref;
+                s1 += v; s2 = __builtin_fma(v, v, s2);
+            }
+            sum[2 * h] = s1; sum[2 * h + 1] = s2;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) part[q][i][lane] = sum[i];
+        __syncthreads();
+        if (q == 0 && w < nw) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                double s1 = 0.0, s2 = 0.0;
+                for (int j = 0; j < RH_WAVES; ++j) { s1 += part[j][2 * h][lane]; s2 += part[j][2 * h + 1][lane]; }
+                const double mrel = s1 / (double)n;
+                const double var = (s2 - s1 * mrel) / (double)(n - 1);
+                const double mean = (ref - refd) + mrel;
+                if (!isfinite(s1) || !isfinite(s2)) bad = 1.0;
+                am += mean; am2 = __builtin_fma(mean, mean, am2); av += var;
+            }
+        }
+        __syncthreads();
+    }
+    if (q == 0) {
+        am = wave_sum_f64(am); am2 = wave_sum_f64(am2); av = wave_sum_f64(av); bad = wave_sum_f64(bad);
+        if (lane == 0) {
+            const double nc = 2.0 * (double)nw;
+            const double W = av / nc;
+            const double Bn = (am2 - am * am / nc) / (nc - 1.0);
+            const double vp = (double)(n - 1) / (double)n * W + Bn;
+            const bool ok = bad == 0.0 && W > 0.0 && isfinite(W) && isfinite(vp);
+            out[4 * d + 0] = ok ? sqrt(vp / W) : NAN;
+            out[4 * d + 1] = W;
+            out[4 * d + 2] = vp;
+            out[4 * d + 3] = refd + am / nc;
+        }
+    }
+}
+
+// ------------------------------------------------------------------ multi-chain ESS from the sums (Stan's estimator)
+// The unnormalised form of acorr_rho_kernel: P[k][group] = sum over the wavefront's live lanes of acov_j(k) = acf_k / N, and
+// from the wavefronts of chunk 0 the partials of the chain means Q[0][group] = sum xbar_j, Q[1][group] = sum xbar_j^2 (xbar
+// relative to the parameter's reference CT[0][d][0]).
+__global__ __launch_bounds__(64) void acorr_cov_kernel(const float* __restrict__ CT, int nd, int nwp, int nwc, int nlive, int lo, int hi,
+                                                       int kuse, const double* __restrict__ S, const double* __restrict__ T,
+                                                       const double* __restrict__ HC, const double* __restrict__ TC,
+                                                       double* __restrict__ P, double* __restrict__ Q) {
+    const int lane = threadIdx.x, g = blockIdx.x, c = blockIdx.y;
+    const int s = g * 64 + lane;
+    const int d = (g * 64) / nwc, w = s - d * nwc;
+    const size_t ns = (size_t)nd * nwp, nser = (size_t)nd * nwc;
+    const float* col = CT + (size_t)d * nwp + w;
+    const double ref = (double)col[0];
+    const int N = hi - lo;
+    const double Tt = T[s], m = Tt / (double)N;
+    double hp = HC[(size_t)c * nser + s], tp = TC[(size_t)c * nser + s];
+    const bool live = w < nlive;
+    const int ngroups = (int)(nser >> 6);
+    if (c == 0) {
+        const double xb = live ? (ref - (double)CT[(size_t)d * nwp]) + m : 0.0;
+        const double q1 = wave_sum_f64(xb), q2 = wave_sum_f64(xb * xb);
+        if (lane == 0) { Q[g] = q1; Q[ngroups + g] = q2; }
+    }
+    const int kend = min((c + 1) * AC_CK, kuse + 1);
+    for (int k = c * AC_CK; k < kend; ++k) {
+        const double acf = S[(size_t)k * nser + s] - m * (2.0 * Tt - tp - hp) + (double)(N - k) * m * m;
+        const double sum = wave_sum_f64(live ? acf / (double)N : 0.0);
+        if (lane == 0) P[(size_t)k * ngroups + g] = sum;
+        hp += (double)col[(size_t)(lo + k) * ns] - ref;       // (k <= kuse <= N - 1: both rows exist)
+        tp += (double)col[(size_t)(hi - 1 - k) * ns] - ref;
+    }
+}
+
+// per parameter, from A_k = F[d][k] (acorr_fmean_kernel: the mean over the chains of acov_j(k)) and the partials Q:
+// W, var+, rho_k, Geyer's initial positive sequence of the pairs P_t = rho_2t + rho_2t+1 made monotone, tau, ESS.
+// out[d] = ESS, out[nd + d] = last pair index used, out[2 nd + d] = 1 when the sequence has not ended within the pairs the
+// lags 0..kuse hold and kuse < N - 1 (more lags needed), else 0.
+__global__ __launch_bounds__(256) void acorr_geyer_kernel(const double* __restrict__ F, const double* __restrict__ Q, int ngroups,
+                                                          int gpd, int nlive, int kuse, int N, int nd, double* __restrict__ out) {
+    __shared__ int first_end;
+    const int d = blockIdx.x, tid = threadIdx.x;
+    const double* A = F + (size_t)d * (kuse + 1);
+    double q1 = 0.0, q2 = 0.0;
+    for (int g = 0; g < gpd; ++g) { q1 += Q[d * gpd + g]; q2 += Q[ngroups + d * gpd + g]; }
+    const double nl = (double)nlive;
+    const double between = nlive > 1 ? (q2 - q1 * q1 / nl) / (nl - 1.0) : 0.0;
+    const double W = (double)N / (double)(N - 1) * A[0];
+    const double vp = (double)(N - 1) / (double)N * W + between;
+    const int npairs = (kuse + 1) / 2;
+    if (tid == 0) first_end = npairs;
+    __syncthreads();
+    for (int t = tid; t < npairs; t += 256) {
+        const double pt = (1.0 - (W - A[2 * t]) / vp) + (1.0 - (W - A[2 * t + 1]) / vp);
+        if (!(pt > 0.0)) { atomicMin(&first_end, t); break; }
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    const int tend = first_end;                                  // pairs 0 .. tend - 1 are positive
+    double status = 0.0;
+    if (tend == npairs && kuse < N - 1) status = 1.0;
+    double sum = 0.0, prev = INFINITY;
+    for (int t = 0; t < tend; ++t) {
+        double pt = (1.0 - (W - A[2 * t]) / vp) + (1.0 - (W - A[2 * t + 1]) / vp);
+        pt = pt < prev ? pt : prev;
+        prev = pt;
+        sum += pt;
+    }
+    double tau = -1.0 + 2.0 * sum;
+    const double total = nl * (double)N;
+    const double floor_ = 1.0 / log10(total);
+    if (tau < floor_) tau = floor_;
+    const bool ok = isfinite(W) && isfinite(vp) && vp > 0.0;
+    out[d] = ok ? total / tau : NAN;
+    out[nd + d] = (double)(tend - 1);
+    out[2 * nd + d] = ok ? status : 0.0;
+}
+
 // ------------------------------------------------------------------ launchers
+int launch_chain_block_moments(const float* CT, int ndim, int nwp, int64_t b0, int64_t b1, double* M, hipStream_t s) {
+    for (int64_t b = b0; b < b1; b += 32768) {
+        const int nb = (int)(b1 - b < 32768 ? b1 - b : 32768);
+        hipLaunchKernelGGL(chain_block_moments_kernel, dim3(ndim * (nwp / 64), nb), dim3(64), 0, s, CT, ndim, nwp, b, M);
+    }
+    return check_hip(hipGetLastError(), "chain_block_moments");
+}
+
+int launch_chain_rhat(const float* CT, int ndim, int nwp, int nw, int64_t lo, int64_t hi, const double* M, int64_t nblocks,
+                      double* out, hipStream_t s) {
+    hipLaunchKernelGGL(chain_rhat_kernel, dim3(ndim), dim3(64 * RH_WAVES), 0, s, CT, ndim, nwp, nw, lo, hi, M, nblocks, out);
+    return check_hip(hipGetLastError(), "chain_rhat");
+}
+
+size_t acorr_ess_scratch_doubles(int nser, int kuse, int nd) {
+    return acorr_scratch_doubles(nser, kuse, nd) + 2 * (size_t)(nser / 64);
+}
+
+int launch_acorr_ess(const float* CT, int ndim, int nwp, int nwc, int nlive, int64_t lo, int64_t hi, int kuse, const double* S,
+                     const double* T, double* scratch, double* out, hipStream_t s) {
+    const int nser = ndim * nwc;
+    const int nchunk = kuse / AC_CK + 1, L = kuse + 1;
+    double* HC = scratch;
+    double* TC = HC + (size_t)nchunk * nser;
+    double* P = TC + (size_t)nchunk * nser;
+    double* F = P + (size_t)nchunk * AC_CK * (nser / 64);
+    double* Q = F + (size_t)ndim * L;
+    hipLaunchKernelGGL(acorr_chunksum_kernel, dim3(nser / 64, nchunk), dim3(64), 0, s, CT, ndim, nwp, nwc, (int)lo, (int)hi, HC, TC);
+    hipLaunchKernelGGL(acorr_chunkscan_kernel, dim3(nser / 64), dim3(64), 0, s, nser, nchunk, HC, TC);
+    hipLaunchKernelGGL(acorr_cov_kernel, dim3(nser / 64, nchunk), dim3(64), 0, s, CT, ndim, nwp, nwc, nlive, (int)lo, (int)hi, kuse, S, T, HC, TC, P, Q);
+    hipLaunchKernelGGL(acorr_fmean_kernel, dim3((L + 255) / 256, ndim), dim3(256), 0, s, P, nser / 64, nwc / 64, nlive, L, ndim, F);
+    hipLaunchKernelGGL(acorr_geyer_kernel, dim3(ndim), dim3(256), 0, s, F, Q, nser / 64, nwc / 64, nlive, kuse, (int)(hi - lo), ndim, out);
+    return check_hip(hipGetLastError(), "acorr_ess");
+}
+
 int launch_chain_append_t(const float* block, int ldb, int nsteps, int nw, int ndim, int wstride, float* CT, int nwp,
                           int64_t row0, hipStream_t s) {
     const int nws = (nw + wstride - 1) / wstride;

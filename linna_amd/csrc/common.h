@@ -528,6 +528,13 @@ int launch_acorr_tau(const float* CT, int ndim, int nwp, int nwc, int nlive, int
                      const double* T, double c, double* scratch, double* out, hipStream_t s);
 int launch_chain_meanstd(const float* CT, int ndim, int nwp, int nws, int64_t t0, int64_t tm, int64_t t1, double* out,
                          hipStream_t s);
+// split-R-hat from block moments and the multi-chain ESS from the running sums
+int launch_chain_block_moments(const float* CT, int ndim, int nwp, int64_t b0, int64_t b1, double* M, hipStream_t s);
+int launch_chain_rhat(const float* CT, int ndim, int nwp, int nw, int64_t lo, int64_t hi, const double* M, int64_t nblocks,
+                      double* out, hipStream_t s);
+size_t acorr_ess_scratch_doubles(int nser, int kuse, int nd);
+int launch_acorr_ess(const float* CT, int ndim, int nwp, int nwc, int nlive, int64_t lo, int64_t hi, int kuse, const double* S,
+                     const double* T, double* scratch, double* out, hipStream_t s);
 
 int gemm_slots(int M, int N);            // number of row-dot partial slots gemm_launch will write
 int gemm_launch(const GemmArgs& a, hipStream_t stream);

@@ -28,7 +28,7 @@ import torch
 from . import _lib, h5lite
 
 __all__ = ["EnsembleSampler", "SliceEnsembleSampler", "BatchedHMC", "HMCSampler", "ZeusSampler", "checkmeanstd", "integrated_time",
-           "ChainStore", "DeviceChain", "read_chain_and_cut", "get_good_walker_list"]
+           "split_rhat", "multichain_ess", "ChainStore", "DeviceChain", "read_chain_and_cut", "get_good_walker_list"]
 
 
 # ------------------------------------------------------------------ convergence statistics (host)
@@ -72,6 +72,65 @@ def integrated_time(x, c=5.0):
     return tau
 
 
+def _chain3(x):
+    x = np.asarray(x, np.float64)
+    if x.ndim == 1:
+        x = x[:, None, None]
+    if x.ndim == 2:
+        x = x[:, :, None]
+    if x.ndim != 3:
+        raise ValueError("a chain is [nstep, nwalker, ndim]")
+    return x
+
+
+def split_rhat(x):
+    """Split-R-hat per parameter of the chains ``x[nstep, nwalker, ndim]`` (float64; the definition of include/linna_hip.h:
+    Gelman et al. BDA3 / Vehtari et al. 2021 without rank normalisation and folding).  Every walker is cut into its first and
+    last ``nstep // 2`` rows; R-hat = sqrt(((n - 1) / n W + B / n) / W) with W the mean within-variance and B / n the variance
+    of the means of the 2 nwalker split chains.  NaN where W = 0 or a row of the halves is not finite."""
+    x = _chain3(x)
+    N = len(x)
+    n = N // 2
+    if n < 2:
+        raise ValueError("split_rhat: %d rows; two halves of at least 2 rows are needed" % N)
+    h = np.concatenate([x[:n], x[N - n:]], axis=1)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        W = h.var(0, ddof=1).mean(0)
+        vp = (n - 1.0) / n * W + h.mean(0).var(0, ddof=1)
+        r = np.sqrt(vp / W)
+    r[~(W > 0) | ~np.isfinite(h).all((0, 1)) | ~np.isfinite(vp)] = np.nan
+    return r
+
+
+def multichain_ess(x, return_pairs=False):
+    """Multi-chain effective sample size per parameter of the chains ``x[nstep, nwalker, ndim]`` (float64; Stan's estimator as
+    include/linna_hip.h states it): autocovariances averaged over the chains, rho_k = 1 - (W - A_k) / var+, Geyer's initial
+    positive sequence of the pairs rho_2t + rho_2t+1 made monotone, tau at least 1 / log10(nwalker nstep), ESS = nwalker
+    nstep / tau.  NaN where a value is not finite or var+ is not positive.  ``return_pairs``: also the last pair index used."""
+    x = _chain3(x)
+    N, nw, nd = x.shape
+    ess, last = np.full(nd, np.nan), np.full(nd, -1.0)
+    for d in range(nd):
+        y = x[:, :, d]
+        if N < 2 or not np.isfinite(y).all():
+            continue
+        xb = y.mean(0)
+        f = np.fft.rfft(y - xb, n=2 * _next_pow_two(N), axis=0)
+        A = (np.fft.irfft(f * np.conjugate(f), axis=0)[:N] / N).mean(1)
+        W = N / (N - 1.0) * A[0]
+        vp = (N - 1.0) / N * W + (xb.var(ddof=1) if nw > 1 else 0.0)
+        if not (np.isfinite(W) and np.isfinite(vp) and vp > 0):
+            continue
+        rho = 1.0 - (W - A) / vp
+        npairs = N // 2
+        P = rho[0:2 * npairs:2] + rho[1:2 * npairs:2]
+        ended = ~(P > 0)
+        tend = int(np.argmax(ended)) if ended.any() else npairs
+        tau = max(-1.0 + 2.0 * np.sum(np.minimum.accumulate(P[:tend])), 1.0 / np.log10(nw * N))
+        ess[d], last[d] = nw * N / tau, tend - 1
+    return (ess, last) if return_pairs else ess
+
+
 class DeviceChain(object):
     """The chain of a run kept on the GPU for the convergence statistics, which are computed there INCREMENTALLY.
 
@@ -84,7 +143,13 @@ class DeviceChain(object):
     (csrc/autocorr.hip), no FFT.  ``K`` starts at 512 lags and grows (new lags computed from the stored chain) whenever
     the window is not found below it or comes within a third of it.  The statistics' copy of the chain is
     ``ct[row][parameter][walker]`` (walkers padded to a multiple of 64).  All work is enqueued on the current stream;
-    ``tau_begin`` / ``tau_end`` let a driver collect the result one block later without stalling the sampler."""
+    ``tau_begin`` / ``tau_end`` let a driver collect the result one block later without stalling the sampler.
+
+    Those statistics are within-chain.  For independent chains (``method="hmc"``) ``rhat_begin`` / ``rhat_end`` give
+    split-R-hat over all walkers -- from float64 block moments (sum and sum of squares per lane and block of 128 rows,
+    ``linna_chain_block_moments``, allocated and filled only once an R-hat is asked for) plus the ragged rows at the ends of
+    the two halves -- and ``ess_begin`` / ``ess_end`` Stan's multi-chain effective sample size from the same running sums
+    as tau (``linna_acorr_ess``)."""
 
     MAX_WALKERS = 1024      # the running sums (8 bytes x lags per series, read and written at every check) cover an evenly spaced
                             # subset of at most so many walkers; the drivers confirm a positive check with ALL walkers (sums
@@ -100,6 +165,7 @@ class DeviceChain(object):
         self._lo = self._hi = 0
         self._scratch = None
         self.lag_growths = 0
+        self._M, self._mb = None, 0  # block-moment records [blocks, 2, nd, nwp] float64 and how many are filled (rhat only)
 
     # -- storage
     def _setup(self, z):
@@ -204,6 +270,10 @@ class DeviceChain(object):
         """Enqueue everything a check needs on the current stream -- the sums' update, the estimate, its copy into pinned
         memory -- and return a token for ``tau_end``; nothing waits.  ``all_walkers``: the estimate over every walker of
         the ensemble (sums of their own, computed from the stored chain) instead of the routine subset."""
+        return self._sums_begin("tau", discard, c, upto, all_walkers)
+
+    def _sums_begin(self, kind, discard, c, upto, all_walkers):
+        """``tau_begin`` / ``ess_begin``: both estimates read the same running sums."""
         hi = self.n if upto is None else int(upto)
         lo = int(discard)
         if not 0 <= lo < hi <= self.n:
@@ -217,39 +287,124 @@ class DeviceChain(object):
             S, T = self._fresh(min(len(self._S) if self._S is not None else self.LAGS0, (hi - lo + 31) & ~31), full)
             self._update(S, T, lo, hi, lo, hi, 0, len(S), False)
         nlive = self.nw if full else self.nws
-        out = self._estimate(S, T, lo, hi, c, nlive)
-        pin = torch.empty(3 * self.nd, dtype=torch.float64).pin_memory()
-        pin.copy_(out, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.dev))
-        return dict(pin=pin, ev=ev, lo=lo, hi=hi, c=c, live=live, S=S, T=T, nlive=nlive)
+        tok = dict(kind=kind, lo=lo, hi=hi, c=c, live=live, S=S, T=T, nlive=nlive)
+        self._sums_enqueue(tok)
+        return tok
 
-    def tau_end(self, tok):
-        """The estimate of ``tau_begin`` as numpy [nd].  When Sokal's window lies beyond the lags kept so far they are doubled
-        (new lags from the stored chain) and the estimate repeated -- early in a run, while the estimate still grows with
-        the chain; afterwards the capacity stays ahead of the window (1.5 x)."""
+    def _sums_enqueue(self, tok):
+        if tok["kind"] == "tau":
+            out = self._estimate(tok["S"], tok["T"], tok["lo"], tok["hi"], tok["c"], tok["nlive"])
+        else:
+            out = self._estimate_ess(tok["S"], tok["T"], tok["lo"], tok["hi"], tok["nlive"])
+        if "pin" not in tok:
+            tok["pin"] = torch.empty(3 * self.nd, dtype=torch.float64).pin_memory()
+        tok["pin"].copy_(out, non_blocking=True)
+        tok["ev"] = torch.cuda.Event()
+        tok["ev"].record(torch.cuda.current_stream(self.dev))
+
+    def _sums_end(self, tok, want_of):
+        """The three rows of an estimate [3, nd] (value | window or last pair | more lags needed).  When the estimate asks for
+        more lags than are kept they are doubled (new lags from the stored chain) and the estimate repeated -- early in a
+        run, while it still grows with the chain; afterwards the capacity stays ahead of what it used (1.5 x)."""
         nd = self.nd
         while True:
             tok["ev"].synchronize()
-            r = tok["pin"].numpy()
-            tau, win, more = r[:nd].copy(), r[nd:2 * nd].copy(), r[2 * nd:]
+            r = tok["pin"].numpy().reshape(3, nd).copy()
             lo, hi, S = tok["lo"], tok["hi"], tok["S"]
-            if not np.any(more > 0):
+            if not np.any(r[2] > 0):
                 break
             S = self._grow(S, lo, hi, 2 * len(S))
             if tok["live"]:
                 self._S = S
             tok["S"] = S
-            out = self._estimate(S, tok["T"], lo, hi, tok["c"], tok["nlive"])
-            tok["pin"].copy_(out, non_blocking=True)
-            tok["ev"] = torch.cuda.Event()
-            tok["ev"].record(torch.cuda.current_stream(self.dev))
-        if tok["live"] and np.all(np.isfinite(win)):
-            want = int(1.5 * float(np.max(win))) + 64
+            self._sums_enqueue(tok)
+        if tok["live"] and np.all(np.isfinite(r[1])):
+            want = want_of(r[1])
             if want > len(self._S) and len(self._S) < ((hi - lo + 31) & ~31):
                 self._S = self._grow(self._S, lo, hi, max(want, 2 * len(self._S)))
-        self.last_window = win
-        return tau
+        return r
+
+    def tau_end(self, tok):
+        """The estimate of ``tau_begin`` as numpy [nd].  When Sokal's window lies beyond the lags kept so far they are doubled
+        (new lags from the stored chain) and the estimate repeated -- early in a run, while the estimate still grows with
+        the chain; afterwards the capacity stays ahead of the window (1.5 x)."""
+        r = self._sums_end(tok, lambda win: int(1.5 * float(np.max(win))) + 64)
+        self.last_window = r[1]
+        return r[0]
+
+    def _estimate_ess(self, S, T, lo, hi, nlive):
+        """Enqueue the multi-chain ESS from the sums; returns the device result [3 nd] (ESS | last pair | more lags needed)."""
+        kuse = min(len(S), hi - lo) - 1
+        nwc = int(S.shape[2])
+        nb = int(_lib.load().linna_acorr_ess_scratch_bytes(self.nd, nwc, kuse))
+        if self._scratch is None or self._scratch.numel() * 8 < nb:
+            self._scratch = torch.empty((nb + 7) // 8, dtype=torch.float64, device=self.dev)
+        out = torch.empty(3 * self.nd, dtype=torch.float64, device=self.dev)
+        _lib.call("linna_acorr_ess", self.ctx, _lib.ptr(self.ct), self.nd, self.nwp, nwc, int(nlive),
+                  int(lo), int(hi), int(kuse), self._dptr(S), self._dptr(T), self._dptr(self._scratch), self._dptr(out), _lib.stream())
+        return out
+
+    def ess_begin(self, discard=0, upto=None, all_walkers=False):
+        """``tau_begin`` for the multi-chain effective sample size (Stan's estimator, include/linna_hip.h) of the window
+        [discard, upto): the chains are the lanes the running sums cover -- the walker subset, or with ``all_walkers`` every
+        walker (sums of their own).  The sums, ``_advance`` and ``_grow`` are the ones of the tau estimate."""
+        return self._sums_begin("ess", discard, None, upto, all_walkers)
+
+    def ess_end(self, tok):
+        """The estimate of ``ess_begin`` as numpy [nd] (NaN: a value of the window is not finite).  More lags are added while
+        Geyer's positive sequence has not ended within the lags kept."""
+        r = self._sums_end(tok, lambda last: int(1.5 * (2.0 * float(np.max(last)) + 2.0)) + 64)
+        self.last_pair = r[1]
+        return r[0]
+
+    def ess(self, discard=0, upto=None, all_walkers=False):
+        return self.ess_end(self.ess_begin(discard, upto, all_walkers))
+
+    # -- split-R-hat from block moments
+    def _records(self):
+        """The block-moment records of every complete block of ``_lib.RHAT_BLOCK`` stored rows, filled up to the chain's length
+        on the current stream.  Nothing exists before the first R-hat is asked for."""
+        nb = self.n // _lib.RHAT_BLOCK
+        if self._M is None or nb > len(self._M):
+            big = torch.empty((max(nb, 2 * (0 if self._M is None else len(self._M)), 64), 2, self.nd, self.nwp),
+                              dtype=torch.float64, device=self.dev)
+            if self._mb:
+                big[:self._mb] = self._M[:self._mb]
+                self._M.record_stream(torch.cuda.current_stream(self.dev))      # (as the chain's buffer in append)
+            self._M = big
+        if nb > self._mb:
+            _lib.call("linna_chain_block_moments", self.ctx, _lib.ptr(self.ct), self.nd, self.nwp, self._mb, nb,
+                      self._dptr(self._M), _lib.stream())
+            self._mb = nb
+        return self._M, self._mb
+
+    def rhat_begin(self, discard=0, upto=None, records=True):
+        """Enqueue split-R-hat (include/linna_hip.h) of the rows [discard, upto) over ALL walkers on the current stream, its copy
+        into pinned memory and an event; returns a token for ``rhat_end``; nothing waits.  ``records=False``: every row is
+        read from the stored chain instead of the block moments (the from-scratch route)."""
+        hi = self.n if upto is None else int(upto)
+        lo = int(discard)
+        if not 0 <= lo < hi <= self.n:
+            raise ValueError("empty chain window")
+        M, mb = self._records() if records else (None, 0)
+        out = torch.empty((self.nd, 4), dtype=torch.float64, device=self.dev)
+        _lib.call("linna_chain_rhat", self.ctx, _lib.ptr(self.ct), self.nd, self.nwp, self.nw, lo, hi,
+                  self._dptr(M) if M is not None else None, int(mb), self._dptr(out), _lib.stream())
+        pin = torch.empty((self.nd, 4), dtype=torch.float64).pin_memory()
+        pin.copy_(out, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.dev))
+        return dict(pin=pin, ev=ev, lo=lo, hi=hi)
+
+    def rhat_end(self, tok):
+        """R-hat per parameter as numpy [nd] (NaN: no within-chain variance, or a value that is not finite);
+        ``last_rhat`` keeps all four columns (R-hat, W, var+, grand mean)."""
+        tok["ev"].synchronize()
+        self.last_rhat = tok["pin"].numpy().copy()
+        return self.last_rhat[:, 0].copy()
+
+    def rhat(self, discard=0, upto=None, records=True):
+        return self.rhat_end(self.rhat_begin(discard, upto, records))
 
     def integrated_time(self, discard=0, c=5.0, upto=None, all_walkers=False):
         """emcee's estimator (autocovariance of the mean-removed series normalised at lag 0, averaged over walkers, Sokal
@@ -1994,7 +2149,14 @@ class HMCSampler(object):
     ``adapt_traj=True`` adapts one step size for all walkers and the trajectory length behind that warm-up
     (``BatchedHMC.adapt_traj``, at most ``max_steps`` leapfrog steps an iteration; ``samp_steps`` is then not used).  The file
     is then written and read with or without ``adapt_mass`` and also holds ``traj``, ``max_steps`` and ``iteration``; a resumed
-    ``adapt_traj`` run takes it only with a finite positive ``traj`` and continues the sequence of step counts."""
+    ``adapt_traj`` run takes it only with a finite positive ``traj`` and continues the sequence of step counts.
+
+    ``criterion="rhat"`` (``method="hmc"`` only) replaces the reference's stopping rule -- tau, its change and the drift of the
+    halves, all within-chain statistics that cannot see independent chains disagree -- by the between-chain one: the run
+    stops at the first check with split-R-hat < ``rhat_tol`` (1.01, Vehtari et al. 2021) and multi-chain ESS >= ``ess_min``
+    (400) for every parameter, both computed on the device over the stored rows behind the first ``rhat_discard`` fraction
+    (``DeviceChain.rhat_begin`` / ``ess_begin``); ``self.diagnostics`` keeps the last check's values.  The default ``"tau"``
+    is the reference's rule, unchanged."""
 
     ADAPT_FILE = "chhmc_adapt.npz"
 
@@ -2006,15 +2168,26 @@ class HMCSampler(object):
         self.m = np.ones(ndim) if m is None else m
         self.mass, self.cov = None, None
         self.sampler = None
+        self.diagnostics = None                              # criterion="rhat": dict(rhat, ess, n) of the last check
         self.seed, self.group = seed, dist_group
 
     def sample(self, pool, nsamp, samp_steps=0, samp_eps=0, Madapt=1000, outdir="./", progress=False, overwrite=False,
                ntimes=10, tautol=0.01, method="emcee", incremental=True, meanshift=0.1, stdshift=0.1, nk=2, ncheck=100,
-               burnin=100, profile=None, adapt_mass=False, adapt_traj=False, max_steps=64):
+               burnin=100, profile=None, adapt_mass=False, adapt_traj=False, max_steps=64, criterion="tau", rhat_tol=1.01,
+               ess_min=400, rhat_discard=0.0):
         if method not in ("emcee", "hmc"):
             # sampler.py's "nuts" branch is unreachable in the reference and not built here
             raise NotImplementedError(method)
         hmc = method == "hmc"
+        if criterion not in ("tau", "rhat"):
+            raise ValueError("criterion = %r: \"tau\" (the reference's rule) or \"rhat\" (split-R-hat and multi-chain ESS)" % (criterion,))
+        if criterion == "rhat":
+            if not hmc:
+                raise ValueError("criterion=\"rhat\" with method = %r: R-hat compares independent chains, and the walkers of an "
+                                 "ensemble exchange positions at every move; it belongs to method=\"hmc\"" % (method,))
+            if not (float(rhat_tol) > 1.0 and float(ess_min) > 0.0 and 0.0 <= float(rhat_discard) < 1.0):
+                raise ValueError("criterion=\"rhat\": rhat_tol = %r (> 1), ess_min = %r (> 0), rhat_discard = %r (in [0, 1))"
+                                 % (rhat_tol, ess_min, rhat_discard))
         adapt_mass = BatchedHMC.adapt_mass_mode(adapt_mass)
         if hmc and not getattr(self.lnp, "device_only", True):
             raise NotImplementedError("HMC needs the gradient of the log-probability: a user loglikelihoodfunc / "
@@ -2113,8 +2286,35 @@ class HMCSampler(object):
                     np.max(np.abs(old_tau - tau) / tau), np.min(np.abs(old_tau - tau) / tau), np.max(tau), n), flush=True)
             return bool(converged)
 
+        def begin_rhat(n):
+            """Both between-chain statistics of the rows [rhat_discard n, n), enqueued behind the block's append."""
+            lo = int(float(rhat_discard) * n)
+            if n - lo < 4:                                                    # (two halves of two rows at least)
+                return dict(hi=n, lo=lo, r=None, e=None)
+            return dict(hi=n, lo=lo, r=dchain.rhat_begin(lo), e=dchain.ess_begin(lo))
+
+        def decide_rhat(tok, done_now):
+            """True = stop: every parameter's split-R-hat below ``rhat_tol`` and multi-chain ESS at least ``ess_min``.  A NaN
+            in either (a chain that never moved, a value that is not finite) is "not converged"."""
+            n, lo = tok["hi"], tok["lo"]
+            if tok["r"] is None:
+                return False
+            rhat, ess = dchain.rhat_end(tok["r"]), dchain.ess_end(tok["e"])
+            converged = self.rhat_rule(rhat, ess, rhat_tol, ess_min)
+            if converged and dchain.subset:
+                # the ESS above is the walker subset's: the decision is taken on all walkers (R-hat always is)
+                ess = dchain.ess(lo, upto=n, all_walkers=True)
+                converged = self.rhat_rule(rhat, ess, rhat_tol, ess_min)
+            self.diagnostics = dict(rhat=rhat, ess=ess, n=n)
+            print("max rhat, min ess, ninter: {0}, {1}, {2}\n".format(np.max(rhat), np.min(ess), n), flush=True)
+            return converged
+
+        self.diagnostics = None
         with _lib.stage("run_mcmc.blocks"):
-            done = _run_blocks(ens, rk, store, dchain, done, nsamp, ncheck, incremental, lambda n: dchain.tau_begin(), decide, prof)
+            if criterion == "rhat":
+                done = _run_blocks(ens, rk, store, dchain, done, nsamp, ncheck, incremental, begin_rhat, decide_rhat, prof)
+            else:
+                done = _run_blocks(ens, rk, store, dchain, done, nsamp, ncheck, incremental, lambda n: dchain.tau_begin(), decide, prof)
         if rk.rank == 0:
             with prof.host("final_flush"), _lib.stage("run_mcmc.final_flush"):
                 store.flush()
@@ -2201,6 +2401,13 @@ class HMCSampler(object):
                  mm.min(), np.median(mm), mm.max(),
                  "" if self.cov is None else "; dense, condition number of C C^T %.3g" % np.linalg.cond(self.cov)), flush=True)
         return ens
+
+    @staticmethod
+    def rhat_rule(rhat, ess, rhat_tol=1.01, ess_min=400):
+        """The stopping rule of ``criterion="rhat"``: every R-hat below ``rhat_tol`` and every ESS at least ``ess_min``.  A NaN
+        in either compares false: "not converged" (not the tau rule's NaN stop)."""
+        with np.errstate(invalid="ignore"):
+            return bool(np.all(np.asarray(rhat) < rhat_tol) and np.all(np.asarray(ess) >= ess_min))
 
     def _keep_mass(self, ens, m):
         """``self.mass`` / ``self.cov`` of the chains as they run now (dense mode: C C^T and 1 / its diagonal)."""

@@ -938,20 +938,22 @@ class NN_samplerv1(object):
                            incremental=True, progress=False, tautol=tautol, meanshift=meanshift, stdshift=stdshift, nk=nk)
 
     def _HMC_sample(self, log_prob, dlnp, ddlnp, ndim, nwalkers, init, pool, transform, samp_steps=5, samp_eps=None, Madapt=1000,
-                    max_n=1000000, adapt_mass=False, adapt_traj=False, max_steps=64):
+                    max_n=1000000, adapt_mass=False, adapt_traj=False, max_steps=64, criterion="tau", rhat_tol=1.01, ess_min=400,
+                    rhat_discard=0.0):
         """util.py:940-945 with the argument order its signature states (its caller passes ``transform`` twice, SURVEY §8
         a18).  ``samp_eps=None``: a step size per chain, found and adapted on the device (``sampler.HMCSampler.sample``) --
         the reference's 0.1 is in latent units and accepts nothing on a posterior much narrower than its prior.  The
         Hessian mass matrix of :944 is not built: unit mass, or with ``adapt_mass`` a diagonal one (``True``) or a dense one
         (``"dense"``) adapted from the chains during the warm-up (``sampler.BatchedHMC.adapt``).  ``adapt_traj``: one step
         size for all chains and the trajectory length adapted behind it (``sampler.BatchedHMC.adapt_traj``, at most
-        ``max_steps`` leapfrog steps a transition); ``samp_steps`` is then not used."""
+        ``max_steps`` leapfrog steps a transition); ``samp_steps`` is then not used.  ``criterion="rhat"`` with ``rhat_tol``,
+        ``ess_min``, ``rhat_discard``: the between-chain stopping rule of ``sampler.HMCSampler.sample``."""
         from . import sampler
         x0 = init + 0.1 * np.random.randn(nwalkers, ndim)                 # util.py:942
         samp = sampler.HMCSampler(log_prob, dlnp, ddlnp, ndim, nwalkers, x0=x0, m=None, transform=transform)
         return samp.sample(pool, max_n, samp_steps, samp_eps or 0, Madapt, outdir=self.outdir, overwrite=True, ntimes=50,
                            method="hmc", incremental=True, progress=True, adapt_mass=adapt_mass, adapt_traj=adapt_traj,
-                           max_steps=max_steps)
+                           max_steps=max_steps, criterion=criterion, rhat_tol=rhat_tol, ess_min=ess_min, rhat_discard=rhat_discard)
 
     def Zeus_sample(self, log_prob, ndim, nwalkers, init, pool, transform, ntimes=50, tautol=0.01, dlnp=None, ddlnp=None,
                     meanshift=0.1, stdshift=0.1, nk=1, max_n=1000000):
@@ -1181,24 +1183,34 @@ def read_chain_and_cut(chainname, nk, ntimes=20, walkercut=False, method="emcee"
 
 def run_mcmc(nnsampler, outdir, method, ndim, nwalkers, init, log_prob, dlnp=None, ddlnp=None, pool=None, transform=None,
              ntimes=50, tautol=0.01, meanshift=0.1, stdshift=0.1, nk=2, max_n=None, adapt_mass=False,
-             adapt_traj=False, max_steps=64):
+             adapt_traj=False, max_steps=64, criterion="tau", rhat_tol=1.01, ess_min=400, rhat_discard=0.0):
     """util.py:1474-1504.  "hmc": per-walker HMC with step sizes adapted on the device (``_HMC_sample``; the reference's own
     branch cannot run); "nuts" is not built.  ``max_n`` (not in the reference): a cap on the iterations of
     the hmc run, 1000000 as there when None.  ``adapt_mass`` (hmc only, not in the reference): also adapt a diagonal mass
     (``True``) or a dense one (``"dense"``) from the chains during the warm-up.  ``adapt_traj`` (hmc only, not in the
     reference): adapt one shared step size and the trajectory length (ChEES) in place of the fixed 5 leapfrog steps, at most
-    ``max_steps`` a transition; with another method, or ``max_steps`` < 1, a ``ValueError``."""
+    ``max_steps`` a transition; with another method, or ``max_steps`` < 1, a ``ValueError``.  ``criterion`` (hmc only, not in
+    the reference): ``"rhat"`` stops the hmc run on split-R-hat < ``rhat_tol`` and multi-chain ESS >= ``ess_min`` over the rows
+    behind the first ``rhat_discard`` fraction instead of the tau rule (``sampler.HMCSampler.sample``); with another method,
+    or another value, a ``ValueError``."""
     if adapt_traj and method != "hmc":
         raise ValueError("adapt_traj with method = %r: the trajectory length belongs to method=\"hmc\"" % (method,))
     if adapt_traj and int(max_steps) < 1:
         raise ValueError("adapt_traj: max_steps = %r: at least 1" % (max_steps,))
+    if criterion not in ("tau", "rhat"):
+        raise ValueError("criterion = %r: \"tau\" or \"rhat\"" % (criterion,))
+    if criterion == "rhat" and method != "hmc":
+        raise ValueError("criterion=\"rhat\" with method = %r: R-hat compares independent chains, and the walkers of an ensemble "
+                         "are not; it belongs to method=\"hmc\"" % (method,))
     kw = dict(ntimes=ntimes, tautol=tautol, transform=transform, dlnp=dlnp, ddlnp=ddlnp, meanshift=meanshift,
               stdshift=stdshift, nk=nk)
     if method == "hmc":
         return nnsampler._HMC_sample(log_prob, dlnp, ddlnp, ndim, nwalkers, init, pool, transform,
                                      samp_steps=0 if adapt_traj else 5, samp_eps=None, Madapt=1000, adapt_mass=adapt_mass,
                                      **({} if max_n is None else {"max_n": max_n}),
-                                     **(dict(adapt_traj=True, max_steps=max_steps) if adapt_traj else {}))
+                                     **(dict(adapt_traj=True, max_steps=max_steps) if adapt_traj else {}),
+                                     **(dict(criterion="rhat", rhat_tol=rhat_tol, ess_min=ess_min, rhat_discard=rhat_discard)
+                                        if criterion == "rhat" else {}))
     if method == "emcee":
         return nnsampler.emcee_sample(log_prob, ndim, nwalkers, init, pool, **kw)
     if method == "zeus":
