@@ -473,7 +473,9 @@ int linna_chi2_ratio_loss_fwd_bwd(linna_ctx_t* ctx, const linna_loss_desc_t* d, 
  * linna_net_forward and linna_chi2_ratio_loss_fwd_bwd instead).  X[n][ldx]: the resident, untransformed training
  * inputs; XB[B][ldxb]: the transformed batch (out; the first layer's parameter gradient reads it); ws: forward
  * workspace of linna_net_fwd_ws_bytes(net, B); PRED[B][ldp]: raw network output (out); YN[n][ldyn]: the normalised
- * targets of the resident set (linna_loss_targets). */
+ * targets of the resident set (linna_loss_targets).  XB and dPRED are written over their WHOLE row stride -- B x ldxb and
+ * B x lddp floats, zeros behind the nin / nout columns: the parameter-gradient launch reads them as padded matrices -- in
+ * this entry, linna_net_train_step and linna_net_train_step_update alike; every other output keeps the caller's pads. */
 int linna_net_prepare_loss(linna_net_t* net, const linna_loss_desc_t* d);   /* allocates its weight stream (outside a capture) */
 /* YN[i][j] = (Y[i][j]/sigma_j - ymean_j)/ystd_j, NaN where the element is masked (util.py:1072): the normalised targets
  * of a whole data set, computed once; linna_net_forward_loss subtracts its prediction from them */

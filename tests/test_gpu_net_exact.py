@@ -20,11 +20,12 @@ padding (1, 15, 16, 17, 64, 65, 256 inputs; hidden K of 16, 17, 1000), column gr
 SPLIT / WIDE choice, SIDE segments of kc 4 / 2 / 1 with one and two steps and one past, residual blocks (ChtoModelv2,
 ChtoModelsimple, custom C of 1, 16, 17, 64, the identity skip K == N that no model class reaches), dense likelihoods of 16 ...
 1024 columns, the gradient gates of 257 / 513 wide hidden layers; batches of 1, 3, 5, 9, 17, 33 and 20 rows.
-Left to its existing tolerance test: the input-skip network (ChtoModelv2_linear, its 1e-3 fold), the bf16 engines, the merged
-training step's loss, the layer-by-layer paths.
+Left to its existing tolerance test: the input-skip network (ChtoModelv2_linear, its 1e-3 fold), the layer-by-layer paths.
+The bf16 engines and the merged training step's loss: tests/test_gpu_net_exact_bf16.py, the same technique.
 
-Wall time of the module on an MI355X, measured: 123 cases in 14.6 s (the slowest, ChtoModelv2(26, 457) through the training
-forward and the dX chain, 1.0 s).
+Wall time of the module on an MI355X, measured: 153 cases in 19.4 s, the ten networks on the bf16 planner's edges among them,
+which run here in fp32 too (the slowest: ChtoModelv2(33, 33) through serving, 1.2 s, and ChtoModelv2(26, 457) through the
+training forward and the dX chain, 1.1 s).
 """
 import numpy as np
 import pytest

@@ -30,14 +30,57 @@ def networks():
     return nets
 
 
+def layer_lines(model):
+    """(the dump program's layer lines of ``model``, the layer table they were taken from)."""
+    from linna_amd import nn
+    arr = nn.program_layers(model)
+    return ["%d %d %d %d %d %r %d %d %d %d %d %d %d" % ((L.op, L.K, L.C, L.N, L.relu, L.alpha) + tuple(
+        int(getattr(L, f) or 0) for f in ("W", "b", "W1", "b1", "W2", "b2", "Ws"))) for L in arr], arr
+
+
+def case_line(case_id, kind, rows, in_size, dense, tri, nl):
+    return "case %s %d %d %d %d %d %d" % (case_id, KINDS.index(kind), rows, in_size, dense, tri, nl)
+
+
+def build_dump(directory):
+    """Compile tests/net_program_dump.hip with the planner alone (host only) into ``directory``; the executable's path."""
+    exe = os.path.join(str(directory), "dump")
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    subprocess.check_call([hipcc, "--offload-host-only", "-O1", "-std=c++17", "-I", CSRC, os.path.join(CSRC, "net_program.hip"),
+                           os.path.join(ROOT, "tests", "net_program_dump.hip"), "-o", exe])
+    return exe
+
+
+def run_dump(exe, text):
+    """(summary lines, {case id: full dump}) of the cases in ``text``."""
+    out = subprocess.run([exe], input=text, stdout=subprocess.PIPE, universal_newlines=True, check=True).stdout
+    summary, full, cur = [], {}, []
+    for line in out.splitlines():
+        if line.startswith("== "):
+            summary.append(line[3:])
+            full[line[3:].split(" | ")[0]] = "\n".join(cur)
+            cur = []
+        else:
+            cur.append(line)
+    return summary, full
+
+
+def dump_records(full_text, what):
+    """The records ``what`` ("seg", "pack", "nseg", ...) of one case's full dump, each as a {field: value} dict of strings."""
+    recs = []
+    for line in full_text.splitlines():
+        f = line.split()
+        if f and f[0] == what:
+            recs.append(dict(zip(f[0::2], f[1::2])))
+    return recs
+
+
 def case_text():
     """The dump program's input: every network x NsKind x engine (x dense form), layer lists as nn.program_layers builds them."""
-    from linna_amd import nn, _lib
+    from linna_amd import _lib
     out = []
     for name, model in networks():
-        arr = nn.program_layers(model)
-        lines = ["%d %d %d %d %d %r %d %d %d %d %d %d %d" % ((L.op, L.K, L.C, L.N, L.relu, L.alpha) + tuple(
-            int(getattr(L, f) or 0) for f in ("W", "b", "W1", "b1", "W2", "b2", "Ws"))) for L in arr]
+        lines, arr = layer_lines(model)
         trained = [ln for ln, L in zip(lines, arr) if L.op != _lib.OP_INSKIP]
         for k, kind in enumerate(KINDS):
             layers = lines if kind in SERVING else trained
@@ -51,20 +94,7 @@ def case_text():
 @pytest.fixture(scope="module")
 def dump(tmp_path_factory):
     """(summary lines, {case id: full dump}) of the planner in the tree."""
-    exe = str(tmp_path_factory.mktemp("net_program") / "dump")
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    subprocess.check_call([hipcc, "--offload-host-only", "-O1", "-std=c++17", "-I", CSRC, os.path.join(CSRC, "net_program.hip"),
-                           os.path.join(ROOT, "tests", "net_program_dump.hip"), "-o", exe])
-    text = subprocess.run([exe], input=case_text(), stdout=subprocess.PIPE, universal_newlines=True, check=True).stdout
-    summary, full, cur = [], {}, []
-    for line in text.splitlines():
-        if line.startswith("== "):
-            summary.append(line[3:])
-            full[line[3:].split(" | ")[0]] = "\n".join(cur)
-            cur = []
-        else:
-            cur.append(line)
-    return summary, full
+    return run_dump(build_dump(tmp_path_factory.mktemp("net_program")), case_text())
 
 
 def test_every_program_kind_matches_the_recorded_plan(dump):
