@@ -833,11 +833,12 @@ int linna_stretch_run(linna_logprob_t* lp, float* coords, int ldc, int ndim, flo
  *   linna_acorr_tau      : emcee's estimate from the sums for the lags 0..kuse (kuse <= min(K, hi - lo) - 1): per series
  *                          acf_k = S_k - m (2 T - tail_k - head_k) + (N - k) m^2, normalised by acf_0, averaged over the nlive
  *                          walkers; tau_M = 2 sum_{k<=M} f_k - 1 at the first M with M >= c tau_M.  out[ndim] = tau (NaN as the
- *                          host estimator gives it for a constant series), out[ndim + d] = M, out[2 ndim + d] = 1 when no such
+ *                          host estimator gives it for a constant series; M = 0 and status 0 then), out[ndim + d] = M, out[2 ndim + d] = 1 when no such
  *                          M <= kuse exists and kuse < hi - lo - 1 (the caller adds lags and asks again), else 0.
  *                          scratch: linna_acorr_scratch_bytes(ndim, nwc, kuse) bytes.
  *   linna_chain_meanstd  : out[d][h][2] = mean and population standard deviation of parameter d over rows [t0, tm) (h = 0) and
- *                          [tm, t1) (h = 1), the first nws lanes (all walkers): the moments checkmeanstd compares. */
+ *                          [tm, t1) (h = 1), the first nws lanes (all walkers): the moments checkmeanstd compares.  An empty
+ *                          half (tm = t0 or t1 = tm) gives NaN for both of its numbers (0 / 0); the other half is unaffected. */
 int linna_chain_append_t(linna_ctx_t* ctx, const float* block, int ldb, int nsteps, int nw, int ndim, int wstride, float* CT,
                          int nwp, int64_t row0, void* stream);
 int linna_acorr_update(linna_ctx_t* ctx, const float* CT, int ndim, int nwp, int nwc, int64_t a0, int64_t a1, int64_t lo,
