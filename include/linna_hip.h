@@ -853,8 +853,8 @@ int linna_chain_meanstd(linna_ctx_t* ctx, const float* CT, int ndim, int nwp, in
  * (autocorr.hip; additive entries, LINNA_ABI_VERSION unchanged).  The statistics above are within-chain: they remove every
  * walker's own mean.  Independent chains (method="hmc") also have to agree with each other.  All float64.
  *
- * Split-R-hat (Gelman et al., BDA3; Vehtari et al. 2021 without the rank normalisation and the folding, which need a sort
- * over the chain).  Window [lo, hi) of CT, N = hi - lo rows, n = N / 2 (integer), ALL nw walkers (lanes 0 .. nw - 1).  Split
+ * Split-R-hat (Gelman et al., BDA3; Vehtari et al. 2021 without the rank normalisation and the folding: those are
+ * linna_chain_rank_rhat below, a sort over the chain per check).  Window [lo, hi) of CT, N = hi - lo rows, n = N / 2 (integer), ALL nw walkers (lanes 0 .. nw - 1).  Split
  * chain 2j = rows [lo, lo + n) of walker j, split chain 2j + 1 = rows [hi - n, hi) (N odd: the middle row is dropped).  Per
  * parameter, with xbar_c and s2_c (ddof 1) the mean and variance of split chain c:
  *     W = mean_c s2_c,   B / n = var_c(xbar_c) (ddof 1 over the 2 nw split chains),   var+ = (n - 1) / n W + B / n,
@@ -889,6 +889,42 @@ int linna_chain_rhat(linna_ctx_t* ctx, const float* CT, int ndim, int nwp, int n
 size_t linna_acorr_ess_scratch_bytes(int ndim, int nwc, int kuse);
 int linna_acorr_ess(linna_ctx_t* ctx, const float* CT, int ndim, int nwp, int nwc, int nlive, int64_t lo, int64_t hi, int kuse,
                     const double* Ssum, const double* Tsum, double* scratch, double* out, void* stream);
+
+/* ------------------------------------------------------------------ rank-normalised, folded split-R-hat (chain_rank.hip;
+ * additive entries, LINNA_ABI_VERSION unchanged).  Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021.  Plain split-R-hat sees
+ * only the means of the split chains: chains that agree in location but not in scale pass it, and heavy tails make it
+ * meaningless.  Window [lo, hi) of CT, n = (hi - lo) / 2; the split chains are exactly those of linna_chain_rhat: rows
+ * [lo, lo + n) and [hi - n, hi) of every walker 0 .. nw - 1 (the middle row of an odd window is ignored, whatever it holds;
+ * padded lanes never enter).  Per parameter the pooled set is the S = 2 n nw values of those rows.
+ *   Ranks.          r = average rank (1-based, ties averaged) of each value in the pooled set; values compare as float32 with
+ *                   -0 = +0.  rank2 = 2 r is an exact integer.
+ *   Normal scores.  z = Phi^-1((r - 3/8) / (S + 1/4)), float64.
+ *   Bulk R-hat.     The split-R-hat formula above (W, B / n, var+) applied to z.  Per split chain the sums of z - z_first and
+ *                   of its square are taken over the rows in a fixed order (16 interleaved row classes added in order).
+ *   Folded.         med = the median of the pooled set, the float64 mean of the two middle sorted values (S is even).
+ *                   zeta = float32(|double(x) - med|): the difference is exact in float64 (float32 values whose
+ *                   exponents lie within 2^29 of each other; beyond that it is correctly rounded) and rounding to float32 is
+ *                   monotone, so the fold can only ADD ties to the order of |x - med|, never change it.  Tail
+ *                   R-hat is the same procedure (ranks, normal scores, split-R-hat) on zeta.
+ *   Reported.       out[ndim][4] = { max(bulk, tail), bulk R-hat, tail R-hat, med }.
+ *   NaN.            W = 0 for z or for zeta (every split chain constant included) gives NaN for that statistic and for the
+ *                   maximum, of that parameter only; a non-finite value anywhere in the two halves of a parameter gives NaN
+ *                   for all three, of that parameter only.
+ *
+ *   linna_chain_rank_rhat_scratch_bytes : bytes of scratch for npar parameters a round (rows = 2 n); 0 for bad arguments.
+ *   linna_chain_rank_rhat : per round of parameters (as many as the scratch holds, at least one; they share every launch):
+ *                   order-preserving 32-bit keys with the element index i nw + w as payload, a least-significant-digit radix
+ *                   sort (8-bit digits; per pass digit counts per workgroup, a scan, a stable scatter ranked by wavefront
+ *                   ballots: no inter-workgroup wait, no result depends on the order of an atomic), rank2 of every element
+ *                   from two binary searches of the sorted keys, the normal scores' moments per split chain, R-hat; then the
+ *                   same on zeta.  No floating-point atomics: two calls give the same bits.  Never allocates, never
+ *                   synchronises; scratch is the caller's (8-byte aligned).  rank2_out (nullable; tests):
+ *                   [2][ndim][2 n][nwp] = rank2 of the bulk, then of the folded values, padded lanes 0.
+ *                   n < 2 or nw > nwp: LINNA_ERR_INVALID; S >= 2^31: LINNA_ERR_UNSUPPORTED (32-bit element indices);
+ *                   scratch smaller than linna_chain_rank_rhat_scratch_bytes(.., 1): LINNA_ERR_INVALID. */
+size_t linna_chain_rank_rhat_scratch_bytes(int ndim, int nw, int64_t rows, int npar);
+int linna_chain_rank_rhat(linna_ctx_t* ctx, const float* CT, int ndim, int nwp, int nw, int64_t lo, int64_t hi, void* scratch,
+                          size_t scratch_bytes, uint32_t* rank2_out, double* out, void* stream);
 
 #ifdef __cplusplus
 }

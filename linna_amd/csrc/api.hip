@@ -1554,6 +1554,31 @@ int linna_acorr_ess(linna_ctx_t*, const float* CT, int ndim, int nwp, int nwc, i
     return launch_acorr_ess(CT, ndim, nwp, nwc, nlive, lo, hi, kuse, Ssum, Tsum, scratch, out, S(stream));
 } LINNA_CATCH_INT
 
+size_t linna_chain_rank_rhat_scratch_bytes(int ndim, int nw, int64_t rows, int npar) try {
+    if (ndim < 1 || nw < 1 || rows < 2 || (rows & 1) || npar < 1 || rows > 0x7fffffff / nw) return 0;
+    return chain_rank_rhat_scratch_bytes(nw, rows, npar < ndim ? npar : ndim);
+} LINNA_CATCH_SIZE
+int linna_chain_rank_rhat(linna_ctx_t*, const float* CT, int ndim, int nwp, int nw, int64_t lo, int64_t hi, void* scratch,
+                          size_t scratch_bytes, uint32_t* rank2_out, double* out, void* stream) try {
+    if (!CT || !out || !scratch || ((uintptr_t)scratch & 7) || !ac_shape_ok(ndim, nwp) || nw < 1 || nw > nwp || lo < 0 || hi < lo ||
+        (hi - lo) / 2 < 2 || hi > 0x7fffff00) {
+        set_error("chain_rank_rhat: bad arguments (the window [lo, hi) needs two halves of at least 2 rows; scratch 8-byte aligned)");
+        return LINNA_ERR_INVALID;
+    }
+    const int64_t rows = (hi - lo) / 2 * 2;
+    if (rows > 0x7fffffff / nw) {
+        set_error("chain_rank_rhat: %lld pooled values per parameter; the sort's 32-bit element indices hold fewer than 2^31",
+                  (long long)rows * nw);
+        return LINNA_ERR_UNSUPPORTED;
+    }
+    if (scratch_bytes < chain_rank_rhat_scratch_bytes(nw, rows, 1)) {
+        set_error("chain_rank_rhat: scratch of %zu bytes, one parameter needs %zu (linna_chain_rank_rhat_scratch_bytes)", scratch_bytes,
+                  chain_rank_rhat_scratch_bytes(nw, rows, 1));
+        return LINNA_ERR_INVALID;
+    }
+    return launch_chain_rank_rhat(CT, ndim, nwp, nw, lo, hi, scratch, scratch_bytes, rank2_out, out, S(stream));
+} LINNA_CATCH_INT
+
 }  // extern "C"
 
 // the gradient's destination and, with `leap`, the leapfrog's kick and drift behind it (none: an NsLeap of nulls)

@@ -532,6 +532,10 @@ int launch_chain_meanstd(const float* CT, int ndim, int nwp, int nws, int64_t t0
 int launch_chain_block_moments(const float* CT, int ndim, int nwp, int64_t b0, int64_t b1, double* M, hipStream_t s);
 int launch_chain_rhat(const float* CT, int ndim, int nwp, int nw, int64_t lo, int64_t hi, const double* M, int64_t nblocks,
                       double* out, hipStream_t s);
+// chain_rank.hip: rank-normalised, folded split-R-hat (a radix sort of the pooled values per parameter)
+size_t chain_rank_rhat_scratch_bytes(int nw, int64_t rows, int npar);
+int launch_chain_rank_rhat(const float* CT, int ndim, int nwp, int nw, int64_t lo, int64_t hi, void* scratch, size_t scratch_bytes,
+                           uint32_t* rank2_out, double* out, hipStream_t s);
 size_t acorr_ess_scratch_doubles(int nser, int kuse, int nd);
 int launch_acorr_ess(const float* CT, int ndim, int nwp, int nwc, int nlive, int64_t lo, int64_t hi, int kuse, const double* S,
                      const double* T, double* scratch, double* out, hipStream_t s);

@@ -102,6 +102,90 @@ def split_rhat(x):
     return r
 
 
+def _ndtri(p):
+    """Phi^-1 in float64 for 0 < p < 1: Wichura's algorithm AS 241 (routine PPND16, relative error about 1e-16), as the device
+    evaluates it (csrc/chain_rank.hip)."""
+    p = np.asarray(p, np.float64)
+    q = p - 0.5
+
+    def poly(r, c):
+        v = np.full_like(r, c[-1])
+        for k in c[-2::-1]:
+            v = v * r + k
+        return v
+
+    with np.errstate(invalid="ignore", divide="ignore"):
+        r = 0.180625 - q * q
+        mid = q * poly(r, (3.3871328727963666080e0, 1.3314166789178437745e+2, 1.9715909503065514427e+3, 1.3731693765509461125e+4,
+                           4.5921953931549871457e+4, 6.7265770927008700853e+4, 3.3430575583588128105e+4, 2.5090809287301226727e+3)) / \
+            poly(r, (1.0, 4.2313330701600911252e+1, 6.8718700749205790830e+2, 5.3941960214247511077e+3, 2.1213794301586595867e+4,
+                     3.9307895800092710610e+4, 2.8729085735721942674e+4, 5.2264952788528545610e+3))
+        t = np.sqrt(-np.log(np.where(q < 0, p, 1.0 - p)))
+        r = t - 1.6
+        near = poly(r, (1.42343711074968357734e0, 4.63033784615654529590e0, 5.76949722146069140550e0, 3.64784832476320460504e0,
+                        1.27045825245236838258e0, 2.41780725177450611770e-1, 2.27238449892691845833e-2, 7.74545014278341407640e-4)) / \
+            poly(r, (1.0, 2.05319162663775882187e0, 1.67638483018380384940e0, 6.89767334985100004550e-1, 1.48103976427480074590e-1,
+                     1.51986665636164571966e-2, 5.47593808499534494600e-4, 1.05075007164441684324e-9))
+        r = t - 5.0
+        far = poly(r, (6.65790464350110377720e0, 5.46378491116411436990e0, 1.78482653991729133580e0, 2.96560571828504891230e-1,
+                       2.65321895265761230930e-2, 1.24266094738807843860e-3, 2.71155556874348757815e-5, 2.01033439929228813265e-7)) / \
+            poly(r, (1.0, 5.99832206555887937690e-1, 1.36929880922735805310e-1, 1.48753612908506148525e-2, 7.86869131145613259100e-4,
+                     1.84631831751005468180e-5, 1.42151175831644588870e-7, 2.04426310338993978564e-15))
+        tail = np.where(t <= 5.0, near, far)
+        return np.where(np.abs(q) <= 0.425, mid, np.where(q < 0, -tail, tail))
+
+
+def _rank2(v):
+    """Twice the average rank (1-based, ties averaged) of every element of the 1-d array ``v``: an exact integer."""
+    order = np.argsort(v, kind="stable")
+    sv = v[order]
+    lb = np.searchsorted(sv, sv, side="left")
+    ub = np.searchsorted(sv, sv, side="right")
+    r2 = np.empty(len(v), np.int64)
+    r2[order] = lb + ub + 1
+    return r2
+
+
+def _rhat_of_scores(z, n):
+    """Split-R-hat of normal scores ``z[2 n rows, nw]`` (the first n rows: first halves, the last n: second halves); every
+    split chain's moments are taken relative to its first value, so that constant chains have exactly no variance."""
+    h = np.concatenate([z[:n], z[n:]], axis=1)
+    rel = h - h[0]
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        W = rel.var(0, ddof=1).mean()
+        vp = (n - 1.0) / n * W + (h[0] + rel.mean(0)).var(ddof=1)
+        return float(np.sqrt(vp / W)) if W > 0 and np.isfinite(W) and np.isfinite(vp) else np.nan
+
+
+def rank_rhat(x):
+    """Rank-normalised, folded split-R-hat (Vehtari et al. 2021; the definition of include/linna_hip.h) per parameter of the
+    chains ``x[nstep, nwalker, ndim]``: ``(rhat, bulk, tail)`` with rhat = max(bulk, tail), float64.  The values are compared
+    as float32 (the device's chain).  The pooled values of the 2 nwalker split chains are replaced by the normal scores
+    z = Phi^-1((r - 3/8) / (S + 1/4)) of their average ranks r: split-R-hat of z is the bulk R-hat; the same on
+    float32(|x - median|) is the folded (tail) R-hat, which sees chains that agree in location but not in scale.  NaN where a
+    value of the halves is not finite or the scores have no within-chain variance."""
+    x = np.asarray(_chain3(x), np.float32)
+    N, nw, nd = x.shape
+    n = N // 2
+    if n < 2:
+        raise ValueError("rank_rhat: %d rows; two halves of at least 2 rows are needed" % N)
+    S = 2 * n * nw
+    out = np.full((3, nd), np.nan)
+    for d in range(nd):
+        v = np.concatenate([x[:n, :, d], x[N - n:, :, d]]).reshape(-1) + np.float32(0.0)         # (-0 + 0 = +0)
+        if not np.isfinite(v).all():
+            continue
+        sv = np.sort(v).astype(np.float64)
+        med = 0.5 * (sv[S // 2 - 1] + sv[S // 2])
+        with np.errstate(over="ignore"):
+            zeta = np.abs(v.astype(np.float64) - med).astype(np.float32)
+        for k, u in ((1, v), (2, zeta)):
+            z = _ndtri((0.5 * _rank2(u) - 0.375) / (S + 0.25)).reshape(2 * n, nw)
+            out[k, d] = _rhat_of_scores(z, n)
+        out[0, d] = np.nan if np.isnan(out[1, d]) or np.isnan(out[2, d]) else max(out[1, d], out[2, d])
+    return out[0], out[1], out[2]
+
+
 def multichain_ess(x, return_pairs=False):
     """Multi-chain effective sample size per parameter of the chains ``x[nstep, nwalker, ndim]`` (float64; Stan's estimator as
     include/linna_hip.h states it): autocovariances averaged over the chains, rho_k = 1 - (W - A_k) / var+, Geyer's initial
@@ -149,12 +233,15 @@ class DeviceChain(object):
     split-R-hat over all walkers -- from float64 block moments (sum and sum of squares per lane and block of 128 rows,
     ``linna_chain_block_moments``, allocated and filled only once an R-hat is asked for) plus the ragged rows at the ends of
     the two halves -- and ``ess_begin`` / ``ess_end`` Stan's multi-chain effective sample size from the same running sums
-    as tau (``linna_acorr_ess``)."""
+    as tau (``linna_acorr_ess``).  ``rank_rhat_begin`` / ``rank_rhat_end`` give the rank-normalised, folded split-R-hat of
+    Vehtari et al. 2021 (``linna_chain_rank_rhat``: a radix sort of the pooled values per parameter), which also sees chains
+    that agree in location but not in scale."""
 
     MAX_WALKERS = 1024      # the running sums (8 bytes x lags per series, read and written at every check) cover an evenly spaced
                             # subset of at most so many walkers; the drivers confirm a positive check with ALL walkers (sums
                             # of their own, from the stored chain) before they stop.  None: every walker, always.
     LAGS0 = 512             # initial lag capacity (a multiple of 32)
+    RANK_SCRATCH = 1 << 30  # bytes the sort of rank_rhat may take for the parameters of one round (one parameter always fits)
 
     def __init__(self, max_walkers=-1):
         self.ct = None           # [capacity, nd, nwp] fp32 on the device, grown by doubling
@@ -166,6 +253,7 @@ class DeviceChain(object):
         self._scratch = None
         self.lag_growths = 0
         self._M, self._mb = None, 0  # block-moment records [blocks, 2, nd, nwp] float64 and how many are filled (rhat only)
+        self._rank_scratch = None    # the sort's buffers (rank_rhat only), bytes
 
     # -- storage
     def _setup(self, z):
@@ -405,6 +493,45 @@ class DeviceChain(object):
 
     def rhat(self, discard=0, upto=None, records=True):
         return self.rhat_end(self.rhat_begin(discard, upto, records))
+
+    # -- rank-normalised, folded split-R-hat (a sort of the pooled values per parameter: csrc/chain_rank.hip)
+    def rank_rhat_begin(self, discard=0, upto=None):
+        """Enqueue the rank-normalised, folded split-R-hat (include/linna_hip.h) of the rows [discard, upto) over ALL walkers on
+        the current stream, its copy into pinned memory and an event; returns a token for ``rank_rhat_end``; nothing waits.
+        The sort's scratch exists only once this is asked for and grows by doubling; as many parameters as ``RANK_SCRATCH``
+        bytes hold share the launches of a round (at least one)."""
+        hi = self.n if upto is None else int(upto)
+        lo = int(discard)
+        if not 0 <= lo < hi <= self.n:
+            raise ValueError("empty chain window")
+        rows = (hi - lo) // 2 * 2
+        lib = _lib.load()
+        one = int(lib.linna_chain_rank_rhat_scratch_bytes(self.nd, self.nw, rows, 1)) if rows >= 4 else 0
+        npar = max(1, min(self.nd, int(self.RANK_SCRATCH) // max(one, 1)))
+        need = int(lib.linna_chain_rank_rhat_scratch_bytes(self.nd, self.nw, rows, npar)) if one else 8
+        if self._rank_scratch is None or self._rank_scratch.numel() < need:
+            old = self._rank_scratch
+            self._rank_scratch = torch.empty(max(need, 2 * (0 if old is None else old.numel())), dtype=torch.uint8, device=self.dev)
+            if old is not None:
+                old.record_stream(torch.cuda.current_stream(self.dev))      # (a check on another stream may still sort in it)
+        out = torch.empty((self.nd, 4), dtype=torch.float64, device=self.dev)
+        _lib.call("linna_chain_rank_rhat", self.ctx, _lib.ptr(self.ct), self.nd, self.nwp, self.nw, lo, hi,
+                  _lib.ptr(self._rank_scratch, torch.uint8), int(self._rank_scratch.numel()), None, self._dptr(out), _lib.stream())
+        pin = torch.empty((self.nd, 4), dtype=torch.float64).pin_memory()
+        pin.copy_(out, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.dev))
+        return dict(pin=pin, ev=ev, lo=lo, hi=hi)
+
+    def rank_rhat_end(self, tok):
+        """max(bulk, tail) R-hat per parameter as numpy [nd] (NaN: no within-chain variance of the scores, or a value that is
+        not finite); ``last_rank_rhat`` keeps all four columns (maximum, bulk R-hat, tail R-hat, median)."""
+        tok["ev"].synchronize()
+        self.last_rank_rhat = tok["pin"].numpy().copy()
+        return self.last_rank_rhat[:, 0].copy()
+
+    def rank_rhat(self, discard=0, upto=None):
+        return self.rank_rhat_end(self.rank_rhat_begin(discard, upto))
 
     def integrated_time(self, discard=0, c=5.0, upto=None, all_walkers=False):
         """emcee's estimator (autocovariance of the mean-removed series normalised at lag 0, averaged over walkers, Sokal
@@ -2156,7 +2283,11 @@ class HMCSampler(object):
     stops at the first check with split-R-hat < ``rhat_tol`` (1.01, Vehtari et al. 2021) and multi-chain ESS >= ``ess_min``
     (400) for every parameter, both computed on the device over the stored rows behind the first ``rhat_discard`` fraction
     (``DeviceChain.rhat_begin`` / ``ess_begin``); ``self.diagnostics`` keeps the last check's values.  The default ``"tau"``
-    is the reference's rule, unchanged."""
+    is the reference's rule, unchanged.  Plain split-R-hat compares only the means of the chains: ``rhat_rank=True`` (with
+    ``criterion="rhat"`` only) confirms every check that passes with the rank-normalised, folded R-hat of Vehtari et al. 2021
+    over all walkers (``DeviceChain.rank_rhat``: bulk and tail, which also see chains that differ in scale) and stops only
+    when max(bulk, tail) < ``rhat_tol`` for every parameter as well (NaN: not converged); ``self.diagnostics`` then also holds
+    ``rhat_bulk``, ``rhat_tail`` and ``rhat_rank`` of the last confirmation.  With ``rhat_rank=False`` nothing of it runs."""
 
     ADAPT_FILE = "chhmc_adapt.npz"
 
@@ -2168,13 +2299,13 @@ class HMCSampler(object):
         self.m = np.ones(ndim) if m is None else m
         self.mass, self.cov = None, None
         self.sampler = None
-        self.diagnostics = None                              # criterion="rhat": dict(rhat, ess, n) of the last check
+        self.diagnostics = None                              # criterion="rhat": dict(rhat, ess, n) of the last check (+ rhat_rank's)
         self.seed, self.group = seed, dist_group
 
     def sample(self, pool, nsamp, samp_steps=0, samp_eps=0, Madapt=1000, outdir="./", progress=False, overwrite=False,
                ntimes=10, tautol=0.01, method="emcee", incremental=True, meanshift=0.1, stdshift=0.1, nk=2, ncheck=100,
                burnin=100, profile=None, adapt_mass=False, adapt_traj=False, max_steps=64, criterion="tau", rhat_tol=1.01,
-               ess_min=400, rhat_discard=0.0):
+               ess_min=400, rhat_discard=0.0, rhat_rank=False):
         if method not in ("emcee", "hmc"):
             # sampler.py's "nuts" branch is unreachable in the reference and not built here
             raise NotImplementedError(method)
@@ -2188,6 +2319,9 @@ class HMCSampler(object):
             if not (float(rhat_tol) > 1.0 and float(ess_min) > 0.0 and 0.0 <= float(rhat_discard) < 1.0):
                 raise ValueError("criterion=\"rhat\": rhat_tol = %r (> 1), ess_min = %r (> 0), rhat_discard = %r (in [0, 1))"
                                  % (rhat_tol, ess_min, rhat_discard))
+        elif rhat_rank:
+            raise ValueError("rhat_rank = %r with criterion = %r: the rank-normalised, folded R-hat confirms the checks of "
+                             "criterion=\"rhat\"" % (rhat_rank, criterion))
         adapt_mass = BatchedHMC.adapt_mass_mode(adapt_mass)
         if hmc and not getattr(self.lnp, "device_only", True):
             raise NotImplementedError("HMC needs the gradient of the log-probability: a user loglikelihoodfunc / "
@@ -2307,6 +2441,16 @@ class HMCSampler(object):
                 converged = self.rhat_rule(rhat, ess, rhat_tol, ess_min)
             self.diagnostics = dict(rhat=rhat, ess=ess, n=n)
             print("max rhat, min ess, ninter: {0}, {1}, {2}\n".format(np.max(rhat), np.min(ess), n), flush=True)
+            if converged and rhat_rank:
+                # a check that passes is confirmed with the rank-normalised, folded R-hat of all walkers (a sort of the window
+                # per parameter: nothing of it is enqueued, or allocated, before the cheap rule passes)
+                rr = dchain.rank_rhat(lo, upto=n)
+                with np.errstate(invalid="ignore"):
+                    converged = bool(np.all(rr < rhat_tol))
+                self.diagnostics.update(rhat_rank=rr, rhat_bulk=dchain.last_rank_rhat[:, 1].copy(),
+                                        rhat_tail=dchain.last_rank_rhat[:, 2].copy())
+                print("max bulk rhat, max tail rhat, ninter: {0}, {1}, {2}\n".format(
+                    np.max(dchain.last_rank_rhat[:, 1]), np.max(dchain.last_rank_rhat[:, 2]), n), flush=True)
             return converged
 
         self.diagnostics = None
