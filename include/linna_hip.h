@@ -368,6 +368,20 @@ int linna_serve_plain(int on);
  * value, refuses anything else.  lnP is bit-identical either way (tests, interleaved A/B).  Process-wide, one atomic read on
  * the launch path; without effect on launches that are not plain. */
 int linna_serve_plain_sched(int hand);
+/* Whether a hand-placed plain launch leaves out the MFMAs that multiply zero padding: 1 (default) it does
+ * (net_stream_trim_kernel: a wave whose fourth 16-column tile is padding skips that tile's MFMAs, and the last step of a run
+ * whose K ends one k into it issues one k slice instead of four), 0 net_stream_placed_kernel, -1 queries; returns the
+ * previous value, refuses anything else.  The products left out are zeros or feed columns nobody reads: lnP is bit-identical
+ * either way, non-finite rows included (tests, interleaved A/B).  Process-wide, one atomic read on the launch path; without
+ * effect unless linna_serve_plain and linna_serve_plain_sched are both on and the launch is plain. */
+int linna_serve_plain_trim(int on);
+/* What such a launch would leave out for this op list on the engine of `rows` rows per workgroup, as text: a header line
+ * ("plain|not plain G nseg_f"), then one line per forward segment: "WIDE|SPLIT steps passes", `slive` -- the live k slices
+ * (0-4) of the last step of each K part --, `tlive` -- the live 16-column tiles (0-4) of every (pass, wave) --, and `text`,
+ * the step text each (pass, wave) runs: full, T3 (every step without the fourth tile), S1 (the last step with one slice) or
+ * T3+S1.  Host-side planning only, like linna_program_describe.  Returns the number of forward segments, 0 when the
+ * program is not plain. */
+int linna_program_trim(const linna_layer_t* layers, int nlayers, int in_size, int rows, char* buf, size_t n);
 /* 1 when the serving program of this op list on the engine of `rows` rows per workgroup is plain (dense_nout != 0: with a
  * dense inverse covariance, never), else 0.  Host-side planning only, like linna_program_describe. */
 int linna_program_plain(const linna_layer_t* layers, int nlayers, int in_size, int rows, int dense_nout);

@@ -143,6 +143,8 @@ _SIGNATURES = {
     "linna_dense_tri": (_I, [_I]),
     "linna_serve_plain": (_I, [_I]),
     "linna_serve_plain_sched": (_I, [_I]),
+    "linna_serve_plain_trim": (_I, [_I]),
+    "linna_program_trim": (_I, [_V, _I, _I, _I, _V, C.c_size_t]),
     "linna_program_plain": (_I, [_V, _I, _I, _I, _I]),
     "linna_logprob_serve_plain": (_I, [_V, _I, _V]),
     "linna_logprob_grad_launches": (_I, [_V, _I, _V]),
@@ -387,6 +389,16 @@ def serve_plain_sched(hand=-1):
     """The step of a plain launch: 1 placed by hand (default), 0 compiler-scheduled, -1 queries.  Returns the previous value
     (tests, interleaved A/B measurements); lnP is bit-identical either way."""
     prev = load().linna_serve_plain_sched(int(hand))
+    if prev < 0:
+        check(prev)
+    return prev
+
+
+def serve_plain_trim(on=-1):
+    """Whether a hand-placed plain launch leaves out the MFMAs that multiply zero padding: 1 (default), 0 the hand-placed
+    kernel as it was, -1 queries.  Returns the previous value (tests, interleaved A/B measurements); lnP is bit-identical
+    either way."""
+    prev = load().linna_serve_plain_trim(int(on))
     if prev < 0:
         check(prev)
     return prev

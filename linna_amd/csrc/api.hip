@@ -1286,6 +1286,15 @@ int linna_serve_plain_sched(int hand) try {
     if (hand < -1 || hand > 1) { set_error("linna_serve_plain_sched: %d (-1 query, 0 or 1)", hand); return LINNA_ERR_INVALID; }
     return net_stream_serve_plain_sched(hand);
 } LINNA_CATCH_INT
+int linna_serve_plain_trim(int on) try {
+    if (on < -1 || on > 1) { set_error("linna_serve_plain_trim: %d (-1 query, 0 or 1)", on); return LINNA_ERR_INVALID; }
+    return net_stream_serve_plain_trim(on);
+} LINNA_CATCH_INT
+int linna_program_trim(const linna_layer_t* layers, int nlayers, int in_size, int rows, char* buf, size_t n) try {
+    if (!layers || nlayers < 1 || !buf || !n) { set_error("program_trim: bad arguments"); return LINNA_ERR_INVALID; }
+    TRY(check_layers(layers, nlayers, "program_trim"));
+    return net_stream_trim_describe(layers, nlayers, in_size, rows, buf, n);
+} LINNA_CATCH_INT
 int linna_program_plain(const linna_layer_t* layers, int nlayers, int in_size, int rows, int dense_nout) try {
     if (!layers || nlayers < 1) { set_error("program_plain: bad arguments"); return LINNA_ERR_INVALID; }
     TRY(check_layers(layers, nlayers, "program_plain"));

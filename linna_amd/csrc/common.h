@@ -406,6 +406,11 @@ int net_stream_serve_plain(int on);
 // The step of a plain launch: 1 (default) net_stream_placed_kernel, the step placed by hand; 0 net_stream_plain_kernel, the
 // compiler-scheduled one (same lnP bit for bit; interleaved A/B); -1 queries; returns the previous value.
 int net_stream_serve_plain_sched(int hand);
+// A hand-placed plain launch without the MFMAs that multiply zero padding: 1 (default) net_stream_trim_kernel, 0
+// net_stream_placed_kernel (same lnP bit for bit; interleaved A/B); -1 queries; returns the previous value.
+// net_stream_trim_describe: the liveness the launcher hands that kernel, as text (host-side planning only).
+int net_stream_serve_plain_trim(int on);
+int net_stream_trim_describe(const linna_layer_t* layers, int nl, int in_size, int rows, char* buf, size_t n);
 bool net_stream_program_plain(NsKind kind, const linna_layer_t* layers, int nl, int in_size, const NsDense* dn, int rows);
 bool net_stream_launch_plain_ok(bool cscale, bool cshift, bool w, bool cexp, bool lnP, bool D, bool TH, bool gate);
 // What always travels together into the launchers of the whole-network kernel: plain records, copied field by field into

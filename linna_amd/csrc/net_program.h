@@ -88,6 +88,15 @@ NsProgramRef ns_program(NsKind kind, const linna_layer_t* layers, int nl, int in
 // fp32, every forward segment WIDE or SPLIT with no short or balanced second pass, no SIDE block, no kept input rows (input
 // skip), no dense segment.  The launch adds its own conditions (net_stream_launch_plain_ok).
 bool ns_program_plain(const NsProgram& p);
+// Liveness of the matrix work of a plain program's forward segment i (what net_stream_trim_kernel leaves out; decided here,
+// on the host).  ns_trim_slive: how many of the four k slices of the LAST step of K part kp (WIDE: kp = 0) hold a real k,
+// 0 .. 4 -- rem = Ka - k of that step's first slice, min(rem, 4); 4 for a segment with a second K part.  ns_trim_tlive: how many
+// leading 16-column tiles of the 64-column block of (pass, wave) hold a real column, 0 .. 4.  ns_trim_fold: what the launcher
+// ORs into NsSeg::type beside ncg_log2 (bits 8-11): N in bits 12-23 and slive - 1 in bits 24-25 (a SPLIT segment whose K
+// parts differ, and slive 0: 3, the full text) -- the wave derives its own tlive from N, its pass and its column group.
+int ns_trim_slive(const NsProgram& p, int i, int kp);
+int ns_trim_tlive(const NsProgram& p, int i, int pass, int wave);
+int ns_trim_fold(const NsProgram& p, int i);
 // columns of what segment i of a one-launch forward + backward program (NS_GRAD_INPUT, NS_TRAIN_STEP) writes: the hidden h
 // of a residual block, a forward op's output, or (the backward half) d/d(op input)
 int ns_seg_cols(const NsProgram& p, const linna_layer_t* layers, int i);

@@ -517,6 +517,67 @@ static std::atomic<int> g_serve_plain{1};
 int net_stream_serve_plain(int on) { return on < 0 ? g_serve_plain.load() : g_serve_plain.exchange(on ? 1 : 0); }
 static std::atomic<int> g_serve_plain_sched{1};
 int net_stream_serve_plain_sched(int hand) { return hand < 0 ? g_serve_plain_sched.load() : g_serve_plain_sched.exchange(hand ? 1 : 0); }
+static std::atomic<int> g_serve_plain_trim{1};
+int net_stream_serve_plain_trim(int on) { return on < 0 ? g_serve_plain_trim.load() : g_serve_plain_trim.exchange(on ? 1 : 0); }
+
+int ns_trim_slive(const NsProgram& p, int i, int kp) {
+    const NsSeg& g = p.seg[i];
+    const NsPackSeg& q = p.pack[i];
+    if (q.Kb) return 4;
+    const int k0 = (g.type == NS_SPLIT ? kp * g.kslice : 0) + 16 * (g.steps - 1);     // first k of the part's last step
+    return std::min(std::max(q.Ka - k0, 0), 4);
+}
+int ns_trim_tlive(const NsProgram& p, int i, int pass, int wave) {
+    const NsSeg& g = p.seg[i];
+    const int c0 = 64 * (g.type == NS_WIDE ? 8 * pass + wave : wave & ((1 << g.ncg_log2) - 1));
+    return std::min(std::max((p.pack[i].N - c0 + 15) / 16, 0), 4);
+}
+static int ns_trim_slive_folded(const NsProgram& p, int i) {
+    const int nkp = p.seg[i].type == NS_SPLIT ? NS_NW >> p.seg[i].ncg_log2 : 1;
+    const int s0 = ns_trim_slive(p, i, 0);
+    for (int kp = 1; kp < nkp; ++kp)
+        if (ns_trim_slive(p, i, kp) != s0) return 4;
+#ifdef NS_TRIM_NO_S1                                        // (a diagnostic build: T3 alone, for the stamps that gate S1 by itself)
+    return 4;
+#endif
+    return s0 ? s0 : 4;
+}
+int ns_trim_fold(const NsProgram& p, int i) { return (std::min(p.pack[i].N, 4095) << 12) | ((ns_trim_slive_folded(p, i) - 1) << 24); }
+
+// Text form of a plain serving program's liveness (tests, diagnostics): per forward segment "type steps passes", the live k
+// slices of each K part's last step, the live tiles of every (pass, wave) and the step text each of them runs -- full, T3
+// (every step), S1 (the last step), T3+S1 -- as net_stream_trim_kernel derives it from ns_trim_fold.  The `text` column repeats
+// the kernel's arithmetic (begin_run, net_stream_body.inc) on the host: a host test of it pins this copy, and only the GPU
+// test (tests/test_gpu_serve_trim.py: bit-identical lnP over the same shapes) checks the kernel's own derivation.
+int net_stream_trim_describe(const linna_layer_t* layers, int nl, int in_size, int rows, char* buf, size_t n) {
+    const NsProgramRef pref = ns_program(NS_SERVE, layers, nl, in_size, nullptr, rows);
+    const NsProgram& p = *pref;
+    const bool plain = rows == 16 && ns_program_plain(p);
+    std::string out = plain ? "plain" : "not plain";
+    char line[96];
+    snprintf(line, sizeof line, " G %d nseg_f %d\n", p.G, p.nseg_f);
+    out += line;
+    for (int i = 0; plain && i < p.nseg_f; ++i) {
+        const NsSeg& g = p.seg[i];
+        const int nkp = g.type == NS_SPLIT ? NS_NW >> g.ncg_log2 : 1;
+        snprintf(line, sizeof line, "%s steps %d passes %d slive", g.type == NS_WIDE ? "WIDE" : "SPLIT", g.steps, g.passes);
+        out += line;
+        for (int kp = 0; kp < nkp; ++kp) { snprintf(line, sizeof line, " %d", ns_trim_slive(p, i, kp)); out += line; }
+        out += " tlive";
+        for (int w = 0; w < g.passes * NS_NW; ++w) { snprintf(line, sizeof line, " %d", ns_trim_tlive(p, i, w / NS_NW, w % NS_NW)); out += line; }
+        out += " text";
+        const int fold = ns_trim_fold(p, i), N = (fold >> 12) & 4095;
+        const bool s1 = ((fold >> 24) & 3) == 0;
+        for (int w = 0; w < g.passes * NS_NW; ++w) {        // the kernel's own arithmetic (begin_run)
+            const int c0 = 64 * (g.type == NS_WIDE ? w : (w % NS_NW) & ((1 << g.ncg_log2) - 1));
+            const bool t3 = N - c0 > 32 && N - c0 <= 48;
+            out += t3 && s1 ? " T3+S1" : t3 ? " T3" : s1 ? " S1" : " full";
+        }
+        out += "\n";
+    }
+    if (buf && n) snprintf(buf, n, "%s", out.c_str());
+    return plain ? p.nseg_f : 0;
+}
 
 int ns_seg_cols(const NsProgram& p, const linna_layer_t* layers, int i) {
     if (p.seg_op[i] >= p.nops) return p.nout;               // the dense pair of NS_GRAD_INPUT_DENSE (op == nl): U, d lnP / dd

@@ -382,6 +382,23 @@ __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_placed_kernel(NsArgs
 #include "net_stream_body.inc"
 #undef NS_BODY_HAND
 }
+// The hand-placed launch without the MFMAs that multiply zero padding (net_stream_body.inc, TRIM): two shorter texts of the
+// step -- T3, a wave whose fourth column tile is padding (a 33-column last layer); S1, the last step of a run whose K ends
+// one k into it (a 33-input first layer) -- chosen per run by one scalar the wave derives from what the launcher folds into
+// NsSeg::type (ns_trim_fold, net_program.hip).  The skipped products are zeros added to accumulators that are not -0, or
+// columns nobody reads: lnP is bit-identical to the kernel above, which linna_serve_plain_trim(0) keeps and whose
+// instructions this kernel's existence does not change.
+#define NS_HAVE_TRIM 1
+template <int R>
+__global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_trim_kernel(NsArgs a) {
+    constexpr int MOVE = 0, STORE = 0, ROWS = 16;
+    constexpr bool GRAD = false, BF = false, EPS = false, PLAIN = true, WOUT = false, DGR = false;
+#define NS_BODY_HAND
+#define NS_BODY_TRIM
+#include "net_stream_body.inc"
+#undef NS_BODY_TRIM
+#undef NS_BODY_HAND
+}
 #endif
 template <int R, int MOVE, bool GRAD, int STORE, int ROWS, bool BF>
 __global__ __launch_bounds__(64 * NS_NW, 1) void net_stream_train_bf16_kernel(NsArgs a) {
@@ -480,7 +497,8 @@ int launch_net_stream_pack(NsKind kind, const linna_layer_t* layers, int nl, int
 typedef void (*NsKernel)(NsArgs);
 enum NsVariant { NV_SERVE, NV_STRETCH, NV_SLICE, NV_GRAD_MLP, NV_GRAD2, NV_STORE, NV_DX, NV_TRAIN_FWD, NV_TRAIN_STEP };
 // a bf16 stream; the leapfrog in the finish with a step size per row; more than 64 outputs; the plain MLP's lean serving kernel; ... hand-placed
-enum : unsigned { NF_BF16 = 1, NF_EPS = 2, NF_WIDE = 4, NF_PLAIN = 8, NF_PLACED = 16, NF_DENSE = 32 };   // ... a dense covariance's one-launch gradient
+enum : unsigned { NF_BF16 = 1, NF_EPS = 2, NF_WIDE = 4, NF_PLAIN = 8, NF_PLACED = 16, NF_DENSE = 32,     // ... a dense covariance's one-launch gradient
+                  NF_TRIM = 64 };                                                                          // ... hand-placed, no MFMA on zero padding
 struct NsEntry { NsVariant v; unsigned flags; NsKernel k[3]; const char* what; const char* stamps_lacks; bool attr_set[3]; };
 // the three engines of one kernel template: <R, MOVE, GRAD, STORE, rows, BF (, EPS)>
 #define NS_ENGINES(K, MOVE, GRAD, STORE, ...) \
@@ -491,6 +509,9 @@ static NsEntry ns_table[] = {
     {NV_SERVE, NF_PLAIN, {net_stream_plain_kernel<NS_R>, nullptr, nullptr}, "net_stream plain launch"},
 #ifdef NS_HAVE_PLACED
     {NV_SERVE, NF_PLAIN | NF_PLACED, {net_stream_placed_kernel<NS_R>, nullptr, nullptr}, "net_stream plain launch (hand-placed step)"},
+#endif
+#ifdef NS_HAVE_TRIM
+    {NV_SERVE, NF_PLAIN | NF_PLACED | NF_TRIM, {net_stream_trim_kernel<NS_R>, nullptr, nullptr}, "net_stream plain launch (hand-placed step, trimmed)"},
 #endif
     {NV_STRETCH, 0, NS_ENGINES(net_stream_kernel, 1, false, 0, false), "net_stream launch"},
     {NV_STRETCH, NF_BF16, NS_ENGINES(net_stream_kernel, 1, false, 0, true), "net_stream launch"},
@@ -778,9 +799,17 @@ int launch_net_stream(NsKind kind, const NsNet& net, const float* packed, const 
         return ns_launch_program(NV_GRAD_MLP, a.hm_p && a.hm_eps ? NF_EPS : 0, a, r.B, p, rows, s);
     }
     // the plain MLP's serving launch: its own lean instantiation (net_stream_plain_kernel), unless linna_serve_plain(0) --
-    // with the step placed by hand (net_stream_placed_kernel) where the build has it, unless linna_serve_plain_sched(0)
+    // with the step placed by hand (net_stream_placed_kernel) where the build has it, unless linna_serve_plain_sched(0) --
+    // and without the MFMAs on zero padding (net_stream_trim_kernel: N and the live k slices of each segment's last step
+    // folded in beside ncg_log2), unless linna_serve_plain_trim(0)
     if (!net_stream_takes_plain(kind, net, out, r, mv, gr, rows, dn)) return ns_launch_program(NV_SERVE, 0, a, r.B, p, rows, s);
     for (int i = 0; i < a.nseg; ++i) a.seg[i].type |= a.seg[i].ncg_log2 << 8;      // (the eight fields it reads: net_stream_body.inc)
+#ifdef NS_HAVE_TRIM
+    if (net_stream_serve_plain_sched(-1) && net_stream_serve_plain_trim(-1)) {
+        for (int i = 0; i < a.nseg; ++i) a.seg[i].type |= ns_trim_fold(p, i);
+        return ns_launch_program(NV_SERVE, NF_PLAIN | NF_PLACED | NF_TRIM, a, r.B, p, rows, s);
+    }
+#endif
 #ifdef NS_HAVE_PLACED
     if (net_stream_serve_plain_sched(-1)) return ns_launch_program(NV_SERVE, NF_PLAIN | NF_PLACED, a, r.B, p, rows, s);
 #endif

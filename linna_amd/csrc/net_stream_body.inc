@@ -1,5 +1,6 @@
 // The body of the whole-network kernels (net_stream.hip: net_stream_kernel, net_stream_train_bf16_kernel,
-// net_stream_slice_bf16_kernel, net_stream_grad_bf16_kernel, the EPS / PLAIN / WOUT / DGR instantiations, net_stream_placed_kernel), included
+// net_stream_slice_bf16_kernel, net_stream_grad_bf16_kernel, the EPS / PLAIN / WOUT / DGR instantiations, net_stream_placed_kernel,
+// net_stream_trim_kernel), included
 // inside each kernel's braces; its template parameters R, MOVE, GRAD, STORE, ROWS, BF, its compile-time flags EPS, PLAIN,
 // WOUT and DGR, and its argument NsArgs a are theirs.
     constexpr int NT = NS_NT, NW = NS_NW;
@@ -41,6 +42,14 @@
     static_assert(PLAIN && !BF && ROWS == 16 && R == 6 && NS_NT == 4 && LATE_REFILL, "the hand-placed step: plain fp32 serving, 16 rows, six slots");
 #else
     constexpr bool HAND = false;
+#endif
+    // TRIM: the hand-placed launch without the MFMAs that multiply zero padding (net_stream_trim_kernel alone defines
+    // NS_BODY_TRIM next to NS_BODY_HAND; described at the step loop's driver below)
+#ifdef NS_BODY_TRIM
+    constexpr bool TRIM = true;
+    static_assert(HAND, "the trimmed step texts are hand-placed ones");
+#else
+    constexpr bool TRIM = false;
 #endif
     // slot u, tile t: v[128 + 16 u + 4 t ..]; A fragment i: v[224 + 4 i ..]; accumulator t: v[232 + 4 t ..]
 #define NS_HAND_RING \
@@ -327,8 +336,11 @@
         const float z = in ? zr[i] : 0.f;
         zz += z * z;
         float th = ns_prior_theta(z, zfl[i], za1[i], za2[i]);
-        float lt = log10f(th);
-        asm volatile("" : "+v"(lt));
+        float lt = th;
+        if (!TRIM || a.lg) {                        // (TRIM: a launch without a log10 index computes none -- a wave-uniform test)
+            lt = log10f(th);
+            asm volatile("" : "+v"(lt));
+        }
         theta[i] = th;
         const float t = (a.lg && zlg[i]) ? lt : th;
         float x = in ? (t - zxm[i]) / zxs[i] : 0.f;
@@ -462,6 +474,10 @@
     const int sm_arow = (4 * ((lane >> 2) & 3) + (lane & 3)) % ROWS, sm_achunk = lane >> 4;
     int si = 0, pass = 0, P = 0, kleft;
     int s_type, s_steps, s_passes, s_bias, s_dst, s_relu, s_kslice, s_zext, s_ncgl, s_mstore = 0, s_mapply = 0, s_x0col = 0, s_x0n = 0, s_kcl = 0;
+    // TRIM: the segment's output width N and whether the last step of its runs holds one live k slice (both folded into
+    // NsSeg::type by the launcher), the choice of step text for the run in flight (s_trim: bit 0 every step T3, bit 1 the last
+    // S1), and the operands of the step's text: the ring slot the next step consumes, the ring of texts, the steps to run
+    int s_N = 0, s_sl1 = 0, s_trim = 0, s_sel = 0, s_tx = 0, s_n = 0;
     unsigned* const lmask = reinterpret_cast<unsigned*>(lbias + ((a.bias_total + 3) & ~3));   // GRAD: [slot][512 lanes]
     float lnp_grad = 0.f;                          // GRAD: lnP, stored at the very end (no store next to the weight loads)
     float* s_gout = nullptr; int s_gld = 0, s_gn = 0;   // STORE: global destination of the current segment's output
@@ -497,7 +513,9 @@
     NsSeg nxp;
     auto plain_request = [&]() { nxp = ka->seg[__builtin_amdgcn_readfirstlane(min(si + 1, nseg - 1))]; };
     auto plain_take = [&](const NsSeg& X) {
-        s_type = X.type & 255; s_ncgl = X.type >> 8; kleft = s_steps = X.steps; s_passes = X.passes; s_bias = X.bias_off;
+        s_type = X.type & 255; kleft = s_steps = X.steps; s_passes = X.passes; s_bias = X.bias_off;
+        if constexpr (TRIM) { s_ncgl = (X.type >> 8) & 15; s_N = (X.type >> 12) & 4095; s_sl1 = ((X.type >> 24) & 3) == 0 ? 2 : 0; }
+        else s_ncgl = X.type >> 8;
         s_dst = X.dst_col; s_relu = X.relu; s_kslice = X.kslice; s_zext = X.zext;
     };
     auto begin_run = [&]() {                       // accumulators and A pointer of run (si, pass)
@@ -530,6 +548,12 @@
         // HAND: the run's first MFMAs sit in asm text, where the compiler's hazard recogniser pads nothing: the wait states
         // between the vector writes of the accumulators above and an MFMA that reads them are spent here
         if constexpr (HAND) asm volatile("s_nop 3" : NS_HAND_ACC);
+        // TRIM: the wave's 64-column block of this run starts at column c0 of N; with 33 .. 48 real columns in it the fourth
+        // 16-column tile is padding (tlive == 3)
+        if constexpr (TRIM) {
+            const int c0 = 64 * (s_type == NS_WIDE ? 8 * pass + wave : wave & ((1 << s_ncgl) - 1));
+            s_trim = __builtin_amdgcn_readfirstlane(s_sl1 | (s_N - c0 > 32 && s_N - c0 <= 48 ? 1 : 0));
+        }
     };
     auto lds_barrier = [&]() {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -546,9 +570,15 @@
     a_read(Aq[0]);
     }
 
-    auto step = [&](auto Uc, auto Refill) {
+    // TX: 0 the whole step -- its text, the count and the run end.  TRIM's loop takes the parts one at a time: 5 the text of
+    // a whole run from slot s_sel (s_n steps, full or T3 by s_tx) or of one S1 step (below), 4 the run end alone (the slot is
+    // a run-time value then, not U).
+    auto step = [&](auto Uc, auto Refill, auto Txc) {
         constexpr int U = decltype(Uc)::value;
         constexpr bool refill = decltype(Refill)::value;
+        constexpr int TX = decltype(Txc)::value;
+        static_assert(TX == 0 || (TRIM && refill), "parts of a step: the trimmed launch, whose steps always refill");
+        if constexpr (TX != 4) {
         // the refill of this step goes to the slot the PREVIOUS step consumed: a load whose target the MFMAs just issued
         // still read waits for them at issue (measured: the same loads one slot back, 1.2-1.4 % off every launch; R - 1
         // steps are in flight instead of R).  Not in the merged training launch: its register allocation does not survive
@@ -572,8 +602,11 @@
             // begin_run and of the run end below.
             constexpr int BU = 128 + 16 * U, BR = 128 + 16 * RU, AC = 224 + 4 * (U & 1), AN = 224 + 4 * ((U + 1) & 1);
             constexpr int TW = refill ? 0 : 4 * U;       // loads a tail step does not find in flight
-#define NS_HM(t, s) "v_mfma_f32_16x16x4_f32 v[232+4*" #t ":235+4*" #t "], v[%[ac]+" #s "], v[%[bu]+4*" #t "+" #s "], v[232+4*" #t ":235+4*" #t "]\n\t"
-#define NS_HL(t, off) "global_load_dwordx4 v[%[ru]+4*" #t ":%[ru]+4*" #t "+3], %[vo], %[sb] offset:" #off "\n\t"
+#define NS_XM(AC, BU, t, s) "v_mfma_f32_16x16x4_f32 v[232+4*" #t ":235+4*" #t "], v[" #AC "+" #s "], v[" #BU "+4*" #t "+" #s "], v[232+4*" #t ":235+4*" #t "]\n\t"
+#define NS_XLS(SB, RU, t, off) "global_load_dwordx4 v[" #RU "+4*" #t ":" #RU "+4*" #t "+3], %[vo], " #SB " offset:" #off "\n\t"
+#define NS_HM(t, s) NS_XM(%[ac], %[bu], t, s)
+#define NS_HL(t, off) NS_XLS(%[sb], %[ru], t, off)
+#define NS_XL(RU, t, off) NS_XLS(vcc, RU, t, off)
 #define NS_HAND_TEXT(HEAD, L0, L1, L2, L3) HEAD \
             "s_waitcnt lgkmcnt(0)\n\t" \
             "s_waitcnt vmcnt(%[w0])\n\t" \
@@ -592,6 +625,84 @@
             NS_HM(3, 0) \
             NS_HM(2, 1) "v_add_u32 %[ap], 64, %[ap]\n\t" \
             NS_HM(3, 1) NS_HM(2, 2) NS_HM(3, 2) NS_HM(2, 3) NS_HM(3, 3)
+            // TRIM, two shorter texts of the same step: same registers, same four refill loads, same A read and pointer add,
+            // the counted wait in front of the first MFMA that reads a tile.
+            // T3: the wave's fourth column tile is padding nobody reads -- its four MFMAs are left out (its load is not: the
+            // count of loads in flight stays what every later wait assumes).
+            // S1: the last step of a run whose K ends one k into it -- the slices s = 1, 2, 3 of every tile are the zero fill
+            // times the zero pad, added to accumulators slice 0 has already pushed through +0: left out.  With no refill
+            // issued in front of tile 2's MFMA and one in front of tile 3's, their waits are 19 - t + j = 17 and 17; the first
+            // load sits nine instructions into the text.
+            // TRIM's steps (TX == 5) are ONE block: a run of s_n steps from slot s_sel -- the six texts in a ring, full (s_tx
+            // == 0: the hidden layers) or T3 (s_tx == 1), the run's count and its test on the scalar unit behind each, which is
+            // what the compiled loop spends on --kleft == 0 -- or, s_n == 0, the single S1 step of slot s_sel, all chosen by
+            // scalar compares in front.  The compiler sees one statement with the ring, the fragments and the accumulators as
+            // its operands, as in every other step, and a loop of that statement and ONE run end.  (As eighteen statements in
+            // a switch beside compiled six-step groups the register allocation did not hold: 250 B of scratch.)  The stream
+            // address is advanced in the text too, on the scalar unit behind the step's last load: the pair is VCC (the next
+            // step's first load reads it seven instructions and more into its text).
+#define NS_XHEAD(AC, AN, BU) \
+            "s_waitcnt lgkmcnt(0)\n\t" \
+            "s_waitcnt vmcnt(19)\n\t" \
+            NS_XM(AC, BU, 0, 0) "ds_read_b128 v[" #AN ":" #AN "+3], %[ap]\n\t" \
+            "s_waitcnt vmcnt(18)\n\t" \
+            NS_XM(AC, BU, 1, 0)
+#define NS_XHALF(AC, BU, RU) \
+            NS_XM(AC, BU, 0, 1) NS_XL(RU, 0, 0) \
+            NS_XM(AC, BU, 1, 1) \
+            NS_XM(AC, BU, 0, 2) NS_XL(RU, 1, 1024) \
+            NS_XM(AC, BU, 1, 2) \
+            NS_XM(AC, BU, 0, 3) NS_XL(RU, 2, 2048) \
+            NS_XM(AC, BU, 1, 3) \
+            "s_waitcnt vmcnt(20)\n\t" \
+            NS_XM(AC, BU, 2, 0) NS_XL(RU, 3, 3072) NS_XADV
+#define NS_XADV \
+            "s_add_u32 %[wo], %[wo], 0x1000\n\t" "s_min_u32 %[wo], %[wo], %[wl]\n\t" \
+            "s_add_u32 vcc_lo, %[wbl], %[wo]\n\t" "s_addc_u32 vcc_hi, %[wbh], 0\n\t"
+#define NS_XADD "v_add_u32 %[ap], 64, %[ap]\n\t"
+#define NS_XFULL(AC, AN, BU, RU) NS_XHEAD(AC, AN, BU) NS_XHALF(AC, BU, RU) \
+            "s_waitcnt vmcnt(20)\n\t" \
+            NS_XM(AC, BU, 3, 0) \
+            NS_XM(AC, BU, 2, 1) NS_XADD \
+            NS_XM(AC, BU, 3, 1) NS_XM(AC, BU, 2, 2) NS_XM(AC, BU, 3, 2) NS_XM(AC, BU, 2, 3) NS_XM(AC, BU, 3, 3)
+#define NS_XT3(AC, AN, BU, RU) NS_XHEAD(AC, AN, BU) NS_XHALF(AC, BU, RU) \
+            NS_XM(AC, BU, 2, 1) NS_XADD \
+            NS_XM(AC, BU, 2, 2) NS_XM(AC, BU, 2, 3)
+#define NS_XS1(AC, AN, BU, RU) NS_XHEAD(AC, AN, BU) \
+            "s_waitcnt vmcnt(17)\n\t" \
+            NS_XM(AC, BU, 2, 0) NS_XL(RU, 0, 0) \
+            "s_waitcnt vmcnt(17)\n\t" \
+            NS_XM(AC, BU, 3, 0) NS_XL(RU, 1, 1024) NS_XL(RU, 2, 2048) NS_XL(RU, 3, 3072) NS_XADV \
+            NS_XADD
+            // slot U: fragment read AC, fragment requested AN, ring slot consumed BU, ring slot refilled RU (the one before)
+#define NS_XRING(L, TEXT) \
+            "s_cmp_eq_u32 %[sel], 1\n\t" "s_cbranch_scc1 " #L "1f\n\t" "s_cmp_eq_u32 %[sel], 2\n\t" "s_cbranch_scc1 " #L "2f\n\t" \
+            "s_cmp_eq_u32 %[sel], 3\n\t" "s_cbranch_scc1 " #L "3f\n\t" "s_cmp_eq_u32 %[sel], 4\n\t" "s_cbranch_scc1 " #L "4f\n\t" \
+            "s_cmp_eq_u32 %[sel], 5\n\t" "s_cbranch_scc1 " #L "5f\n\t" \
+            ".p2align 3\n" \
+            #L "0:\n\t" TEXT(224, 228, 128, 208) NS_XCNT #L "1:\n\t" TEXT(228, 224, 144, 128) NS_XCNT \
+            #L "2:\n\t" TEXT(224, 228, 160, 144) NS_XCNT #L "3:\n\t" TEXT(228, 224, 176, 160) NS_XCNT \
+            #L "4:\n\t" TEXT(224, 228, 192, 176) NS_XCNT #L "5:\n\t" TEXT(228, 224, 208, 192) NS_XCNT \
+            "s_branch " #L "0b\n"
+#define NS_XCNT "s_add_u32 %[n], %[n], -1\n\t" "s_cmp_eq_u32 %[n], 0\n\t" "s_cbranch_scc1 99f\n"
+#define NS_XONE(U, AC, AN, BU, RU) \
+            "s_cmp_lg_u32 %[sel], " #U "\n\t" "s_cbranch_scc1 1" #U "f\n\t" NS_XS1(AC, AN, BU, RU) "s_branch 99f\n" "1" #U ":\n\t"
+            if constexpr (TX == 5) {
+                static_assert(NS_STEP_B == 0x1000, "the stream advance in the text");
+                const unsigned wbl = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)wbase);
+                const unsigned wbh = __builtin_amdgcn_readfirstlane((unsigned)((uintptr_t)wbase >> 32));
+                asm volatile("s_add_u32 vcc_lo, %[wbl], %[wo]\n\t" "s_addc_u32 vcc_hi, %[wbh], 0\n\t"
+                             "s_cmp_eq_u32 %[n], 0\n\t" "s_cbranch_scc1 60f\n\t"
+                             "s_cmp_lg_u32 %[tx], 0\n\t" "s_cbranch_scc1 58f\n\t"
+                             NS_XRING(4, NS_XFULL)
+                             "58:\n\t" NS_XRING(5, NS_XT3)
+                             "60:\n\t"
+                             NS_XONE(0, 224, 228, 128, 208) NS_XONE(1, 228, 224, 144, 128) NS_XONE(2, 224, 228, 160, 144)
+                             NS_XONE(3, 228, 224, 176, 160) NS_XONE(4, 224, 228, 192, 176) NS_XONE(5, 228, 224, 208, 192) "99:\n\t"
+                             : NS_HAND_RING, NS_HAND_A, NS_HAND_ACC, [ap] "+v"(ap), [wo] "+s"(woff), [n] "+s"(s_n)
+                             : [vo] "v"(voff), [wbl] "s"(wbl), [wbh] "s"(wbh), [wl] "s"(wlast),
+                               [sel] "s"(__builtin_amdgcn_readfirstlane(s_sel)), [tx] "s"(__builtin_amdgcn_readfirstlane(s_tx)) : "memory", "scc", "vcc");
+            } else
             if constexpr (refill) {
                 const char* const sb = wbase + woff;
                 // the loop's head is 8-byte aligned: hand-written streams are sensitive to a 4-byte phase of their code
@@ -619,9 +730,22 @@
                                [w0] "n"(19 - TW), [w1] "n"(18 - TW), [w2] "n"(17 - TW), [w3] "n"(16 - TW) : "memory");
             }
 #undef NS_HAND_TEXT
+#undef NS_XONE
+#undef NS_XCNT
+#undef NS_XRING
+#undef NS_XS1
+#undef NS_XT3
+#undef NS_XFULL
+#undef NS_XADD
+#undef NS_XADV
+#undef NS_XHALF
+#undef NS_XHEAD
 #undef NS_HAND_HEAD
 #undef NS_HL
 #undef NS_HM
+#undef NS_XL
+#undef NS_XLS
+#undef NS_XM
         } else {
         if constexpr (BF) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(Aq[U & 1][0]), "+v"(Aq[U & 1][AK - 1]) :: "memory");
         else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(Aq[U & 1][0]) :: "memory");
@@ -712,7 +836,10 @@
         }
         if constexpr (refill) wadvance();
         }
-        if (--kleft == 0) {
+        }
+        bool run_end = TX == 4;
+        if constexpr (TX == 0) run_end = --kleft == 0;
+        if (run_end) {
             // HAND: the run's last MFMA left the text above a few scalar instructions ago, and the compiler's hazard
             // recogniser has not seen it: sixteen wait states (eleven are required behind this 8-pass MFMA) before the
             // epilogue's vector instructions and LDS writes read the accumulators
@@ -1291,6 +1418,13 @@
             }
             if (si < nseg) {
                 begin_run();
+                if constexpr (TX == 4) {
+                    // (the slot's parity is a run-time value here: the run's first fragment goes into BOTH fragments' registers
+                    // -- the one the step behind read is dead, and the next step's own A read overwrites it in LDS order)
+                    asm volatile("ds_read_b128 v[224:227], %2\n\tds_read_b128 v[228:231], %2"
+                                 : "={v[224:227]}"(Aq[0][0]), "={v[228:231]}"(Aq[1][0]) : "v"(ap) : "memory");
+                    ap += 64;
+                } else
                 a_read(Aq[(U + 1) & 1]);           // replaces the speculative fragment
                 if constexpr (PLAIN) { if (seg_done) plain_request(); }
             }
@@ -1300,16 +1434,37 @@
         }
     };
     using T_ = std::true_type; using F_ = std::false_type;
-#define NS_STEP(U, RF) if constexpr (U < R) step(std::integral_constant<int, U>{}, RF{});
+    using X0_ = std::integral_constant<int, 0>;
+#define NS_STEP(U, RF) if constexpr (U < R) step(std::integral_constant<int, U>{}, RF{}, X0_{});
     const int ngroups = a.G / R, rem = a.G - ngroups * R;
+    if constexpr (TRIM) {
+        // The trimmed launch: one statement for every step (TX == 5) and ONE copy of the run end.  A run is one pass through
+        // that statement -- the full text, or T3 where the wave's fourth tile is padding -- but for the last step of a run
+        // whose K ends one k into it: the S1 step, a pass of its own.  s_trim holds both choices (set in begin_run).  Every
+        // step refills (past the stream's end its last step again, never used), so every wait finds the twenty loads in
+        // flight it counts on.
+        const int G = a.G;
+        int g = 0;
+#pragma unroll 1
+        while (g < G) {
+            const int n = __builtin_amdgcn_readfirstlane((s_trim & 2) ? kleft - 1 : kleft);     // (0: the S1 step alone)
+            s_n = n;
+            s_tx = s_trim & 1;
+            step(X0_{}, T_{}, std::integral_constant<int, 5>{});
+            const int done = n ? n : 1;
+            g += done; kleft -= done; s_sel = (s_sel + done) % R;
+            if (kleft == 0) step(X0_{}, T_{}, std::integral_constant<int, 4>{});
+        }
+    } else {
 #pragma unroll 1
     for (int it = 0; it < ngroups; ++it) {
         NS_STEP(0, T_) NS_STEP(1, T_) NS_STEP(2, T_) NS_STEP(3, T_) NS_STEP(4, T_) NS_STEP(5, T_) NS_STEP(6, T_) NS_STEP(7, T_)
     }
-#define NS_TAIL(U) if constexpr (U < R - 1) { if (rem > U) step(std::integral_constant<int, U>{}, F_{}); }
+#define NS_TAIL(U) if constexpr (U < R - 1) { if (rem > U) step(std::integral_constant<int, U>{}, F_{}, X0_{}); }
     NS_TAIL(0) NS_TAIL(1) NS_TAIL(2) NS_TAIL(3) NS_TAIL(4) NS_TAIL(5) NS_TAIL(6)
-#undef NS_STEP
 #undef NS_TAIL
+    }
+#undef NS_STEP
     // The last speculative A read.  Both fragments are operands of the wait: the compiler does not know that the
     // inline-asm ds_read lands later, and a fragment nobody reads again would otherwise be dead at once -- its
     // registers could be handed to an accumulator of the final step, which the returning LDS data then overwrites.

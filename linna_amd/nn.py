@@ -481,6 +481,16 @@ def program_is_plain(model, rows=16, dense_nout=0):
     return bool(n)
 
 
+def program_trim(model, rows=16):
+    """Which matrix work on zero padding the trimmed plain launch leaves out for ``model`` on the engine of ``rows`` rows per
+    workgroup, as text (``linna_program_trim``: host-side planning, no GPU needed).  0 segments: the program is not plain."""
+    buf = C.create_string_buffer(65536)      # (a line per forward segment, <= 250 bytes each at two passes: room for every program)
+    n = _lib.load().linna_program_trim(program_layers(model), len(model.ops), model.in_size, int(rows), buf, len(buf))
+    if n < 0:
+        _lib.check(n)
+    return n, buf.value.decode()
+
+
 def describe_grad_bf16_program(model, rows=16):
     """The program of the bf16 one-launch gradient (``Log_prob(precision="bf16", grad_precision="bf16")``) for ``model`` on the
     engine of ``rows`` rows per workgroup, as text (``linna_program_describe_grad_bf16``: host-side planning, no GPU

@@ -24,9 +24,10 @@ else:
 if os.environ.get("NS_STAMPS_PLAIN"):                # 0: the generic instantiation for a plain MLP's serving launch too (linna_serve_plain)
     from linna_amd import _lib
     _lib.serve_plain(int(os.environ["NS_STAMPS_PLAIN"]))
-if os.environ.get("NS_STAMPS_SCHED"):                # 0: the plain instantiation with the compiler-scheduled step (linna_serve_plain_sched)
-    from linna_amd import _lib
-    _lib.serve_plain_sched(int(os.environ["NS_STAMPS_SCHED"]))
+if os.environ.get("NS_STAMPS_SCHED"):                # 0: the plain instantiation with the compiler-scheduled step (linna_serve_plain_sched);
+    from linna_amd import _lib                       # 1: the hand-placed kernel (linna_serve_plain_trim(0)); 2: the trimmed one (the default)
+    _lib.serve_plain_sched(min(int(os.environ["NS_STAMPS_SCHED"]), 1))
+    _lib.serve_plain_trim(int(os.environ["NS_STAMPS_SCHED"]) == 2)
 z = torch.randn(B, nin, device="cuda"); out = torch.empty(B, device="cuda")
 if os.environ.get("NS_STAMPS_STRETCH"):              # the one-launch stretch half step of an ensemble of 2 B walkers instead
     from linna_amd import sampler

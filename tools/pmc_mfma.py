@@ -9,7 +9,7 @@ rows = list(csv.DictReader(open(sys.argv[1])))
 acc = collections.defaultdict(lambda: collections.defaultdict(list))
 for r in rows:
     k = r["Kernel_Name"]
-    if "net_stream_kernel" in k:
+    if "net_stream_" in k and "_kernel" in k:           # (every instantiation: generic, plain, hand-placed, trimmed)
         acc[k][r["Counter_Name"]].append(float(r["Counter_Value"]))
         acc[k]["duration_ns"].append(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]))
 out = {}
