@@ -940,6 +940,49 @@ size_t linna_chain_rank_rhat_scratch_bytes(int ndim, int nw, int64_t rows, int n
 int linna_chain_rank_rhat(linna_ctx_t* ctx, const float* CT, int ndim, int nwp, int nw, int64_t lo, int64_t hi, void* scratch,
                           size_t scratch_bytes, uint32_t* rank2_out, double* out, void* stream);
 
+/* ------------------------------------------------------------------ rank-normalised bulk-ESS and tail-ESS (chain_rank.hip;
+ * additive entries, LINNA_ABI_VERSION unchanged).  Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021.  The multi-chain ESS
+ * above is that of the raw chain: it assumes a finite variance and says how well the MEAN is known only.  Bulk-ESS is the ESS
+ * of the normal scores of the ranks (defined for any distribution); tail-ESS is the smaller of the ESS of the indicators of
+ * the 5 % and the 95 % quantile: how well the ends of a 90 % interval are known.
+ *   Pooled set.     Window [lo, hi) of CT, n = (hi - lo) / 2, all nw walkers; the C = 2 nw split chains are exactly those of
+ *                   linna_chain_rank_rhat: rows [lo, lo + n) and [hi - n, hi) (an odd window drops its middle row).
+ *                   S = 2 n nw pooled float32 values per parameter, -0 = +0.
+ *   Bulk series.    z = float32(Phi^-1((r - 3/8) / (S + 1/4))), r the average rank: the keys, the sort, rank2 and AS 241 of the
+ *                   bulk R-hat.  z is ROUNDED TO FLOAT32, the statistics' chain type: products of two float32 are exact in
+ *                   float64 and the lagged products of autocorr.hip serve unchanged (the rounding moves bulk-ESS by about
+ *                   1e-9 relative; it is part of the definition).
+ *   Tail series.    For num = 1 and 19 (p = num / 20) the type-7 quantile of the sorted pooled values s_0 <= .. <= s_{S-1} by
+ *                   exact integer position: j = (num (S - 1)) div 20, g = ((num (S - 1)) mod 20) / 20,
+ *                   q = s_j + g (s_{min(j + 1, S - 1)} - s_j) in float64; the series is I = (double(x) <= q), 0 or 1.
+ *   ESS of a series. The multi-chain estimator above (linna_acorr_ess) applied to the C split chains of n rows: nlive = C,
+ *                   N = n, every chain relative to its own first row, Geyer's initial positive, monotone pairs, tau at least
+ *                   1 / log10(C n), ESS = C n / tau.
+ *   Reported.       out[ndim][8] = { bulk-ESS, tail-ESS = min(ESS of I_0.05, ESS of I_0.95), ESS of I_0.05, ESS of I_0.95,
+ *                   the last pair used by the bulk series, by I_0.05, by I_0.95 (as linna_acorr_ess; -1 beside a NaN),
+ *                   status }.  status = 1 when some series' pairs are all positive through lag kuse and kuse < n - 1 (the
+ *                   caller asks again with more lags), else 0.
+ *   NaN.            A non-finite value anywhere in the two halves of a parameter gives NaN for that parameter's four ESS
+ *                   values only (and status 0).  A series with var+ <= 0 (a constant parameter; an indicator that is all 1)
+ *                   gives NaN for its own ESS; tail-ESS is NaN if either quantile's ESS is.
+ *
+ *   linna_chain_rank_ess_scratch_bytes : bytes of scratch for npar parameters a round (rows = 2 n) and the lags 0 .. kuse; 0
+ *                   for bad arguments.
+ *   linna_chain_rank_ess : per round of parameters (as many as the scratch holds, at least one; they share every launch):
+ *                   ONE sort (keys, four radix passes; only the bulk order); the scores image -- float32, rows 0 .. n - 1,
+ *                   three series per parameter, the C split chains as lanes (first halves, then second halves) padded with
+ *                   zeros to a multiple of 64 -- written from the sorted order (ranks of ties by two binary searches, the
+ *                   quantiles read from the sorted keys); the image's lagged products for the lags 0 .. kuse from scratch
+ *                   and the Geyer finish per series (the kernels of linna_acorr_update and linna_acorr_ess).  No
+ *                   floating-point atomics, no workgroup waits for another: two calls give the same bits.  Never allocates,
+ *                   never synchronises; scratch is the caller's (8-byte aligned).
+ *                   n < 2, nw > nwp, kuse < 1 or kuse > n - 1, misaligned scratch, scratch smaller than
+ *                   linna_chain_rank_ess_scratch_bytes(.., kuse, 1): LINNA_ERR_INVALID, out untouched; S >= 2^31:
+ *                   LINNA_ERR_UNSUPPORTED (32-bit element indices). */
+size_t linna_chain_rank_ess_scratch_bytes(int ndim, int nw, int64_t rows, int kuse, int npar);
+int linna_chain_rank_ess(linna_ctx_t* ctx, const float* CT, int ndim, int nwp, int nw, int64_t lo, int64_t hi, int kuse,
+                         void* scratch, size_t scratch_bytes, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

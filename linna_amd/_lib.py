@@ -192,6 +192,8 @@ _SIGNATURES = {
     "linna_acorr_ess": (_I, [_V, _V, _I, _I, _I, _I, _I64, _I64, _I, _V, _V, _V, _V, _V]),
     "linna_chain_rank_rhat_scratch_bytes": (_SZ, [_I, _I, _I64, _I]),
     "linna_chain_rank_rhat": (_I, [_V, _V, _I, _I, _I, _I64, _I64, _V, _SZ, _V, _V, _V]),
+    "linna_chain_rank_ess_scratch_bytes": (_SZ, [_I, _I, _I64, _I, _I]),
+    "linna_chain_rank_ess": (_I, [_V, _V, _I, _I, _I, _I64, _I64, _I, _V, _SZ, _V, _V]),
     "linna_hmc_init": (_I, [_V, _I, _I, _V, _U64, _V, _V, _V, _I, _V, _I, _V, _V]),
     "linna_hmc_start": (_I, [_V, _I, _I, _V, _U64, _V, _V, _V, _I, _V, _I, _F, _F, _V, _I, _V, _I, _V, _I, _V, _V]),
     "linna_hmc_kick_drift": (_I, [_V, _I, _I, _V, _F, _F, _V, _I, _V, _I, _V, _I, _V]),

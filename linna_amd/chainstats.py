@@ -188,6 +188,38 @@ def multichain_ess(x, return_pairs=False):
     return (ess, last) if return_pairs else ess
 
 
+def rank_ess(x, return_all=False):
+    """Rank-normalised bulk-ESS and tail-ESS (Vehtari et al. 2021; the definition of include/linna_hip.h) per parameter of the
+    chains ``x[nstep, nwalker, ndim]``: ``(bulk, tail)``, float64.  The values are compared as float32 (the device's chain).
+    The pooled values of the 2 nwalker split chains give three series: the normal scores of their average ranks, rounded to
+    float32, and the indicators ``x <= q`` of the 5 % and the 95 % quantile (type 7, integer position arithmetic).  Each
+    series' ESS is ``multichain_ess`` of the split chains; tail = min of the two indicators'.  NaN where a value of the halves
+    is not finite, or for a series with var+ <= 0.  ``return_all``: also the two quantiles' ESS and the last pair used per
+    series ``[ndim, 3]`` (-1 beside a NaN)."""
+    x = np.asarray(_chain3(x), np.float32)
+    N, nw, nd = x.shape
+    n = N // 2
+    if n < 2:
+        raise ValueError("rank_ess: %d rows; two halves of at least 2 rows are needed" % N)
+    S = 2 * n * nw
+    ess, last = np.full((nd, 3), np.nan), np.full((nd, 3), -1.0)
+    for d in range(nd):
+        v = np.concatenate([x[:n, :, d], x[N - n:, :, d]]).reshape(-1) + np.float32(0.0)         # (-0 + 0 = +0)
+        if not np.isfinite(v).all():
+            continue
+        sv = np.sort(v).astype(np.float64)
+        series = [_ndtri((0.5 * _rank2(v) - 0.375) / (S + 0.25)).astype(np.float32).astype(np.float64)]
+        for num in (1, 19):
+            j, r = divmod(num * (S - 1), 20)
+            q = sv[j] + (r / 20.0) * (sv[min(j + 1, S - 1)] - sv[j])
+            series.append((v.astype(np.float64) <= q).astype(np.float64))
+        y = np.stack(series, axis=1).reshape(2 * n, nw, 3)
+        ess[d], last[d] = multichain_ess(np.concatenate([y[:n], y[n:]], axis=1), return_pairs=True)
+    with np.errstate(invalid="ignore"):
+        tail = np.where(np.isnan(ess[:, 1]) | np.isnan(ess[:, 2]), np.nan, np.minimum(ess[:, 1], ess[:, 2]))
+    return (ess[:, 0], tail, ess[:, 1], ess[:, 2], last) if return_all else (ess[:, 0], tail)
+
+
 class DeviceChain(object):
     """The chain of a run kept on the GPU for the convergence statistics, which are computed there INCREMENTALLY.
 
@@ -208,13 +240,14 @@ class DeviceChain(object):
     the two halves -- and ``ess_begin`` / ``ess_end`` Stan's multi-chain effective sample size from the same running sums
     as tau (``linna_acorr_ess``).  ``rank_rhat_begin`` / ``rank_rhat_end`` give the rank-normalised, folded split-R-hat of
     Vehtari et al. 2021 (``linna_chain_rank_rhat``: a radix sort of the pooled values per parameter), which also sees chains
-    that agree in location but not in scale."""
+    that agree in location but not in scale, and ``rank_ess_begin`` / ``rank_ess_end`` that paper's bulk-ESS and tail-ESS
+    (``linna_chain_rank_ess``: one sort, then the lagged products of the normal scores and of two quantile indicators)."""
 
     MAX_WALKERS = 1024      # the running sums (8 bytes x lags per series, read and written at every check) cover an evenly spaced
                             # subset of at most so many walkers; the drivers confirm a positive check with ALL walkers (sums
                             # of their own, from the stored chain) before they stop.  None: every walker, always.
     LAGS0 = 512             # initial lag capacity (a multiple of 32)
-    RANK_SCRATCH = 1 << 30  # bytes the sort of rank_rhat may take for the parameters of one round (one parameter always fits)
+    RANK_SCRATCH = 1 << 30  # bytes the sort of rank_rhat / rank_ess may take for the parameters of one round (one parameter always fits)
 
     def __init__(self, max_walkers=-1):
         self.ct = None           # [capacity, nd, nwp] fp32 on the device, grown by doubling
@@ -226,7 +259,7 @@ class DeviceChain(object):
         self._scratch = None
         self.lag_growths = 0
         self._M, self._mb = None, 0  # block-moment records [blocks, 2, nd, nwp] float64 and how many are filled (rhat only)
-        self._rank_scratch = None    # the sort's buffers (rank_rhat only), bytes
+        self._rank_scratch = None    # the sort's buffers (rank_rhat and rank_ess only), bytes
 
     # -- storage
     def _setup(self, z):
@@ -481,6 +514,46 @@ class DeviceChain(object):
 
     def rank_rhat(self, discard=0, upto=None):
         return self.rank_rhat_end(self.rank_rhat_begin(discard, upto))
+
+    # -- rank-normalised bulk-ESS and tail-ESS (one sort per parameter, then the lagged products of the scores image)
+    def rank_ess_begin(self, discard=0, upto=None):
+        """Enqueue the rank-normalised bulk-ESS and tail-ESS (include/linna_hip.h) of the rows [discard, upto) over ALL walkers on
+        the current stream, its copy into pinned memory and an event; returns a token for ``rank_ess_end``; nothing waits.
+        The scratch is the one of ``rank_rhat_begin``, grown to the larger need.  The first call asks for the lags below
+        ``LAGS0`` (all of them, for halves shorter than that)."""
+        lo, hi = self._window(discard, upto)
+        return self._rank_ess_enqueue(dict(lo=lo, hi=hi, kuse=min((hi - lo) // 2 - 1, self.LAGS0 - 1)))
+
+    def _rank_ess_enqueue(self, tok):
+        lo, hi, kuse = tok["lo"], tok["hi"], tok["kuse"]
+        rows = (hi - lo) // 2 * 2
+        lib = _lib.load()
+        one = int(lib.linna_chain_rank_ess_scratch_bytes(self.nd, self.nw, rows, kuse, 1))       # (0: a window the entry refuses)
+        npar = max(1, min(self.nd, int(self.RANK_SCRATCH) // max(one, 1)))
+        need = int(lib.linna_chain_rank_ess_scratch_bytes(self.nd, self.nw, rows, kuse, npar)) if one else 8
+        if self._rank_scratch is None or self._rank_scratch.numel() < need:
+            self._rank_scratch = self._grown(self._rank_scratch, need, 0, (), torch.uint8)
+        out = torch.empty((self.nd, 8), dtype=torch.float64, device=self.dev)
+        _lib.call("linna_chain_rank_ess", self.ctx, _lib.ptr(self.ct), self.nd, self.nwp, self.nw, lo, hi, int(kuse),
+                  _lib.ptr(self._rank_scratch, torch.uint8), int(self._rank_scratch.numel()), self._dptr(out), _lib.stream())
+        return self._hand_off(tok, out)
+
+    def rank_ess_end(self, tok):
+        """``(bulk, tail)`` ESS per parameter as numpy [nd] each (NaN: a value that is not finite, or a series without
+        variance); ``last_rank_ess`` keeps all eight columns (bulk, tail, the 5 % and the 95 % quantile's ESS, the three
+        series' last pairs, status).  While a series' positive sequence has not ended within the lags asked for, four times
+        as many are asked for, up to every lag of a half (sticky chains keep their pairs positive that far)."""
+        while True:
+            r = self._collect(tok)
+            if not np.any(r[:, 7] > 0):
+                break
+            tok["kuse"] = min((tok["hi"] - tok["lo"]) // 2 - 1, 4 * (tok["kuse"] + 1) - 1)
+            self._rank_ess_enqueue(tok)
+        self.last_rank_ess = r
+        return r[:, 0].copy(), r[:, 1].copy()
+
+    def rank_ess(self, discard=0, upto=None):
+        return self.rank_ess_end(self.rank_ess_begin(discard, upto))
 
     def integrated_time(self, discard=0, c=5.0, upto=None, all_walkers=False):
         """emcee's estimator (autocovariance of the mean-removed series normalised at lag 0, averaged over walkers, Sokal

@@ -1587,6 +1587,33 @@ int linna_chain_rank_rhat(linna_ctx_t*, const float* CT, int ndim, int nwp, int 
     }
     return launch_chain_rank_rhat(CT, ndim, nwp, nw, lo, hi, scratch, scratch_bytes, rank2_out, out, S(stream));
 } LINNA_CATCH_INT
+size_t linna_chain_rank_ess_scratch_bytes(int ndim, int nw, int64_t rows, int kuse, int npar) try {
+    if (ndim < 1 || nw < 1 || rows < 4 || (rows & 1) || npar < 1 || rows > 0x7fffffff / nw || kuse < 1 || (int64_t)kuse > rows / 2 - 1 ||
+        kuse / 32 + 1 > 65535 || nw > (1 << 24))
+        return 0;
+    return chain_rank_ess_scratch_bytes(nw, rows, kuse, npar < ndim ? npar : ndim);
+} LINNA_CATCH_SIZE
+int linna_chain_rank_ess(linna_ctx_t*, const float* CT, int ndim, int nwp, int nw, int64_t lo, int64_t hi, int kuse, void* scratch,
+                         size_t scratch_bytes, double* out, void* stream) try {
+    if (!CT || !out || !scratch || ((uintptr_t)scratch & 7) || !ac_shape_ok(ndim, nwp) || nw < 1 || nw > nwp || lo < 0 || hi < lo ||
+        (hi - lo) / 2 < 2 || hi > 0x7fffff00 || kuse < 1 || (int64_t)kuse > (hi - lo) / 2 - 1 || kuse / 32 + 1 > 65535 || nw > (1 << 24)) {
+        set_error("chain_rank_ess: bad arguments (the window [lo, hi) needs two halves of n >= 2 rows; 1 <= kuse <= n - 1; scratch "
+                  "8-byte aligned)");
+        return LINNA_ERR_INVALID;
+    }
+    const int64_t rows = (hi - lo) / 2 * 2;
+    if (rows > 0x7fffffff / nw) {
+        set_error("chain_rank_ess: %lld pooled values per parameter; the sort's 32-bit element indices hold fewer than 2^31",
+                  (long long)rows * nw);
+        return LINNA_ERR_UNSUPPORTED;
+    }
+    if (scratch_bytes < chain_rank_ess_scratch_bytes(nw, rows, kuse, 1)) {
+        set_error("chain_rank_ess: scratch of %zu bytes, one parameter needs %zu (linna_chain_rank_ess_scratch_bytes)", scratch_bytes,
+                  chain_rank_ess_scratch_bytes(nw, rows, kuse, 1));
+        return LINNA_ERR_INVALID;
+    }
+    return launch_chain_rank_ess(CT, ndim, nwp, nw, lo, hi, kuse, scratch, scratch_bytes, out, S(stream));
+} LINNA_CATCH_INT
 
 }  // extern "C"
 

@@ -23,6 +23,10 @@
 // caller's scratch holds them.  All element counts are < 2^31 (the entry refuses more); byte offsets are size_t.
 // Bound: the scatter's uncoalesced writes (one (key, index) pair per element and pass): 54-58e9 keys per second and pass
 // measured, the sort 54-57 % of a check, the binary searches 30 %.
+//
+// The file ends with that paper's rank-normalised bulk-ESS and tail-ESS: one sort of the same keys, a float32 image of the
+// normal scores and of two quantile indicators written from the sorted order, and autocorr.hip's lagged products and Geyer
+// finish on that image.
 #include "common.h"
 #include <math.h>
 
@@ -353,6 +357,150 @@ int launch_chain_rank_rhat(const float* CT, int ndim, int nwp, int nw, int64_t l
         hipLaunchKernelGGL((rank_finish_kernel<1>), dim3(np), dim3(64), 0, s, M, nw, n, flag, med, d0, out);
     }
     return check_hip(hipGetLastError(), "chain_rank_rhat");
+}
+
+// ------------------------------------------------------------------ rank-normalised bulk-ESS and tail-ESS
+// include/linna_hip.h states the definition.  One sort (the bulk order) per parameter; then the SCORES IMAGE, a chain of its
+// own in the layout of autocorr.hip: rows 0 .. n - 1, per parameter three series (float32 normal score, indicator of the 5 %
+// quantile, indicator of the 95 % quantile), the C = 2 nw split chains as lanes (first halves, then second halves) padded
+// with zeros to a multiple of 64.  The image's lagged products and their Geyer finish are autocorr.hip's, unchanged.
+//
+// sorted position j: run of equal keys [lb, ub) -> z = float32(Phi^-1((rank2 / 2 - 3/8) / (S + 1/4))) and the two indicators of
+// the value (the key's float32) to the element's row and lane of the image.  The quantiles are read from the sorted keys by
+// integer position: every thread forms both (uniform loads).
+__global__ __launch_bounds__(RK_THREADS) void rank_scores_kernel(const uint32_t* __restrict__ K, const uint32_t* __restrict__ I, uint32_t S,
+                                                                 int nw, int64_t n, int np, int cp, float* __restrict__ img) {
+    const uint32_t j = blockIdx.x * RK_THREADS + threadIdx.x;
+    const int p = blockIdx.y;
+    if (j >= S) return;
+    const uint32_t* k = K + (size_t)p * S;
+    double qv[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const uint64_t pos = (uint64_t)(t ? 19 : 1) * (uint64_t)(S - 1u);
+        const uint32_t jq = (uint32_t)(pos / 20u), j1 = jq + 1u < S ? jq + 1u : S - 1u;
+        const double g = (double)(uint32_t)(pos - (uint64_t)jq * 20u) / 20.0;
+        const double sj = (double)rk_unkey(k[jq]);
+        qv[t] = sj + g * ((double)rk_unkey(k[j1]) - sj);
+    }
+    const uint32_t key = k[j];
+    uint32_t a = 0u, b = j;                                             // lower bound in [0, j]
+    while (a < b) { const uint32_t m = a + ((b - a) >> 1); if (k[m] < key) a = m + 1u; else b = m; }
+    const uint32_t lb = a;
+    a = j + 1u; b = S;                                                  // upper bound in [j + 1, S]
+    while (a < b) { const uint32_t m = a + ((b - a) >> 1); if (k[m] <= key) a = m + 1u; else b = m; }
+    const uint32_t r2 = lb + a + 1u;
+    const uint32_t e = I[(size_t)p * S + j];
+    if (e >= S) return;
+    const uint32_t i = e / (uint32_t)nw, w = e - i * (uint32_t)nw;
+    const bool second = (int64_t)i >= n;
+    const size_t row = second ? (size_t)i - (size_t)n : (size_t)i;
+    const int lane = (second ? nw : 0) + (int)w;
+    const double x = (double)rk_unkey(key);
+    float* o = img + (row * 3 * (size_t)np + 3 * (size_t)p) * cp + lane;
+    o[0] = (float)rk_ndtri((0.5 * (double)r2 - 0.375) / ((double)S + 0.25));
+    o[cp] = x <= qv[0] ? 1.f : 0.f;
+    o[2 * (size_t)cp] = x <= qv[1] ? 1.f : 0.f;
+}
+
+// one thread per parameter: the three series' estimates G[3][3 np] (ESS | last pair | more lags needed) -> out[d][8]
+__global__ __launch_bounds__(64) void rank_ess_finish_kernel(const double* __restrict__ G, const uint32_t* __restrict__ flag, int np, int d0,
+                                                             double* __restrict__ out) {
+    const int p = blockIdx.x * 64 + threadIdx.x;
+    if (p >= np) return;
+    const bool bad = flag[p] != 0u;
+    double* o = out + 8 * (size_t)(d0 + p);
+    double status = 0.0;
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+        const double e = bad ? NAN : G[3 * p + t];
+        const bool nan = e != e;
+        o[t == 0 ? 0 : 1 + t] = e;
+        o[4 + t] = nan ? -1.0 : G[3 * np + 3 * p + t];
+        if (!nan && G[6 * np + 3 * p + t] > 0.0) status = 1.0;
+    }
+    o[1] = (o[2] != o[2] || o[3] != o[3]) ? NAN : (o[2] < o[3] ? o[2] : o[3]);
+    o[7] = status;
+}
+
+// scratch of a round of npar parameters: doubles first (lagged products, series sums, the estimator's scratch, the series'
+// estimates), then the 32-bit words (flags, the sort's buffers, digit counts, the image)
+struct RankEssLayout {
+    size_t sums, tsum, est, g, flag, keys, counts, img, per;   // byte offsets for npar parameters; per: bytes per parameter
+    uint32_t ntiles;
+    int cp, k1;
+};
+static RankEssLayout rank_ess_layout(int nw, int64_t rows, int kuse, int npar) {
+    const size_t S = (size_t)rows * nw, n = (size_t)rows / 2;
+    RankEssLayout L;
+    L.ntiles = (uint32_t)((S + RK_TILE - 1) / RK_TILE);
+    L.cp = (2 * nw + 63) & ~63;
+    L.k1 = (kuse + 32) & ~31;                                           // lags 0 .. kuse in whole blocks of 32
+    const size_t bs = (size_t)L.k1 * 3 * L.cp * sizeof(double), bt = (size_t)3 * L.cp * sizeof(double);
+    const size_t be = acorr_ess_scratch_doubles(3 * L.cp, kuse, 3) * sizeof(double), bg = 9 * sizeof(double), bflag = 8;
+    const size_t bkeys = 4 * S * sizeof(uint32_t), bcounts = (size_t)L.ntiles * RK_THREADS * sizeof(uint32_t);
+    const size_t bimg = 3 * n * L.cp * sizeof(float);
+    L.per = bs + bt + be + bg + bflag + bkeys + bcounts + bimg;
+    L.sums = 0;
+    L.tsum = L.sums + bs * npar;
+    L.est = L.tsum + bt * npar;
+    L.g = L.est + be * npar;
+    L.flag = L.g + bg * npar;
+    L.keys = L.flag + bflag * npar;
+    L.counts = L.keys + bkeys * npar;
+    L.img = L.counts + bcounts * npar;
+    return L;
+}
+size_t chain_rank_ess_scratch_bytes(int nw, int64_t rows, int kuse, int npar) {
+    return rank_ess_layout(nw, rows, kuse, npar).per * (size_t)npar;
+}
+
+int launch_chain_rank_ess(const float* CT, int ndim, int nwp, int nw, int64_t lo, int64_t hi, int kuse, void* scratch,
+                          size_t scratch_bytes, double* out, hipStream_t s) {
+    const int64_t n = (hi - lo) / 2;
+    const uint32_t S = (uint32_t)(2 * n * nw);
+    const RankEssLayout one = rank_ess_layout(nw, 2 * n, kuse, 1);
+    const size_t per = one.per;
+    const int cp = one.cp;
+    int npar = (int)(scratch_bytes / per < (size_t)ndim ? scratch_bytes / per : (size_t)ndim);
+    if (npar > 21845) npar = 21845;                                     // (the 3 npar series are a grid dimension of the estimator)
+    if (npar > 0x7fffffff / (3 * cp)) npar = 0x7fffffff / (3 * cp);     // (its series index is an int; nw <= 2^24: at least one)
+    const RankEssLayout L = rank_ess_layout(nw, 2 * n, kuse, npar);
+    char* base = (char*)scratch;
+    double* Ssum = (double*)(base + L.sums);
+    double* Tsum = (double*)(base + L.tsum);
+    double* est = (double*)(base + L.est);
+    double* G = (double*)(base + L.g);
+    uint32_t* flag = (uint32_t*)(base + L.flag);
+    uint32_t* KA = (uint32_t*)(base + L.keys);
+    uint32_t* IA = KA + (size_t)npar * S;
+    uint32_t* KB = IA + (size_t)npar * S;
+    uint32_t* IB = KB + (size_t)npar * S;
+    uint32_t* C = (uint32_t*)(base + L.counts);
+    float* img = (float*)(base + L.img);
+    const uint32_t eblocks = (S + RK_THREADS - 1) / RK_THREADS;
+    for (int d0 = 0; d0 < ndim; d0 += npar) {
+        const int np = ndim - d0 < npar ? ndim - d0 : npar;
+        // the sort's arrays keep the stride S per parameter; the image, the sums and the estimates are packed for np parameters
+        int rc = check_hip(hipMemsetAsync(flag, 0, (size_t)np * 8, s), "chain_rank_ess");
+        if (rc) return rc;
+        rc = check_hip(hipMemsetAsync(img, 0, (size_t)3 * np * n * L.cp * sizeof(float), s), "chain_rank_ess");
+        if (rc) return rc;
+        rc = check_hip(hipMemsetAsync(Ssum, 0, (size_t)L.k1 * 3 * np * L.cp * sizeof(double), s), "chain_rank_ess");
+        if (rc) return rc;
+        rc = check_hip(hipMemsetAsync(Tsum, 0, (size_t)3 * np * L.cp * sizeof(double), s), "chain_rank_ess");
+        if (rc) return rc;
+        const dim3 eg(eblocks, np);
+        hipLaunchKernelGGL((rank_keys_kernel<0>), eg, dim3(RK_THREADS), 0, s, CT, ndim, nwp, nw, d0, lo, hi, S, (const double*)nullptr, KA, IA, flag);
+        rank_sort(KA, IA, KB, IB, C, S, L.ntiles, np, s);
+        hipLaunchKernelGGL(rank_scores_kernel, eg, dim3(RK_THREADS), 0, s, KA, IA, S, nw, n, np, L.cp, img);
+        rc = launch_acorr_update(img, 3 * np, L.cp, L.cp, 0, n, 0, n, 0, L.k1, Ssum, Tsum, 0, s);
+        if (rc) return rc;
+        rc = launch_acorr_ess(img, 3 * np, L.cp, L.cp, 2 * nw, 0, n, kuse, Ssum, Tsum, est, G, s);
+        if (rc) return rc;
+        hipLaunchKernelGGL(rank_ess_finish_kernel, dim3((np + 63) / 64), dim3(64), 0, s, G, flag, np, d0, out);
+    }
+    return check_hip(hipGetLastError(), "chain_rank_ess");
 }
 
 }  // namespace linna

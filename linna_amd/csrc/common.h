@@ -541,6 +541,10 @@ int launch_chain_rhat(const float* CT, int ndim, int nwp, int nw, int64_t lo, in
 size_t chain_rank_rhat_scratch_bytes(int nw, int64_t rows, int npar);
 int launch_chain_rank_rhat(const float* CT, int ndim, int nwp, int nw, int64_t lo, int64_t hi, void* scratch, size_t scratch_bytes,
                            uint32_t* rank2_out, double* out, hipStream_t s);
+// rank-normalised bulk-ESS and tail-ESS: one sort, the scores image, autocorr.hip's lagged products and Geyer finish on it
+size_t chain_rank_ess_scratch_bytes(int nw, int64_t rows, int kuse, int npar);
+int launch_chain_rank_ess(const float* CT, int ndim, int nwp, int nw, int64_t lo, int64_t hi, int kuse, void* scratch,
+                          size_t scratch_bytes, double* out, hipStream_t s);
 size_t acorr_ess_scratch_doubles(int nser, int kuse, int nd);
 int launch_acorr_ess(const float* CT, int ndim, int nwp, int nwc, int nlive, int64_t lo, int64_t hi, int kuse, const double* S,
                      const double* T, double* scratch, double* out, hipStream_t s);

@@ -29,7 +29,7 @@ import torch
 
 from . import _lib, dist as ldist
 from .chainstats import (DeviceChain, _autocorr_1d, _chain3, _ndtri, _next_pow_two, _rank2, _rhat_of_scores, checkmeanstd,
-                         integrated_time, multichain_ess, rank_rhat, split_rhat)
+                         integrated_time, multichain_ess, rank_ess, rank_rhat, split_rhat)
 from .chainstore import ChainStore, _OnDisk, get_good_walker_list, read_chain_and_cut
 from .ensemble import EnsembleSampler, SliceEnsembleSampler, _FastOverflow
 from .hmc import BatchedHMC
@@ -253,8 +253,9 @@ class _RhatRule(object):
     rows [rhat_discard n, n), both enqueued behind the block's append.  A NaN in either (a chain that never moved, a value that
     is not finite) is "not converged".  ``drv.diagnostics`` keeps the last check's values."""
 
-    def __init__(self, dchain, drv, rhat_tol, ess_min, rhat_discard, rhat_rank):
+    def __init__(self, dchain, drv, rhat_tol, ess_min, rhat_discard, rhat_rank, ess_rank=False):
         self.dchain, self.drv, self.rhat_tol, self.ess_min, self.rhat_discard, self.rhat_rank = dchain, drv, rhat_tol, ess_min, rhat_discard, rhat_rank
+        self.ess_rank = ess_rank
 
     def begin(self, n):
         lo = int(float(self.rhat_discard) * n)
@@ -283,6 +284,14 @@ class _RhatRule(object):
             drv.diagnostics.update(rhat_rank=rr, rhat_bulk=dchain.last_rank_rhat[:, 1].copy(), rhat_tail=dchain.last_rank_rhat[:, 2].copy())
             print("max bulk rhat, max tail rhat, ninter: {0}, {1}, {2}\n".format(
                 np.max(dchain.last_rank_rhat[:, 1]), np.max(dchain.last_rank_rhat[:, 2]), n), flush=True)
+        if converged and self.ess_rank:
+            # and with the rank-normalised bulk-ESS and tail-ESS of all walkers (one sort of the window per parameter and the
+            # lagged products of its scores: nothing of it is enqueued, or allocated, before everything above passes)
+            bulk, tail = dchain.rank_ess(lo, upto=n)
+            with np.errstate(invalid="ignore"):
+                converged = bool(np.all(bulk >= self.ess_min) and np.all(tail >= self.ess_min))
+            drv.diagnostics.update(ess_bulk=bulk, ess_tail=tail)
+            print("min bulk ess, min tail ess, ninter: {0}, {1}, {2}\n".format(np.min(bulk), np.min(tail), n), flush=True)
         return converged
 
 
@@ -360,7 +369,12 @@ class HMCSampler(object):
     ``criterion="rhat"`` only) confirms every check that passes with the rank-normalised, folded R-hat of Vehtari et al. 2021
     over all walkers (``DeviceChain.rank_rhat``: bulk and tail, which also see chains that differ in scale) and stops only
     when max(bulk, tail) < ``rhat_tol`` for every parameter as well (NaN: not converged); ``self.diagnostics`` then also holds
-    ``rhat_bulk``, ``rhat_tail`` and ``rhat_rank`` of the last confirmation.  With ``rhat_rank=False`` nothing of it runs."""
+    ``rhat_bulk``, ``rhat_tail`` and ``rhat_rank`` of the last confirmation.  With ``rhat_rank=False`` nothing of it runs.
+    The rule's ESS is that of the raw chain: it assumes a finite variance and measures the mean only.  ``ess_rank=True`` (with
+    ``criterion="rhat"`` only) confirms every check that passed all of the above with that paper's rank-normalised bulk-ESS
+    and tail-ESS over all walkers (``DeviceChain.rank_ess``; tail: the smaller ESS of the 5 % and the 95 % quantile) and stops
+    only when both are at least ``ess_min`` for every parameter (NaN: not converged); ``self.diagnostics`` then also holds
+    ``ess_bulk`` and ``ess_tail``.  With ``ess_rank=False`` nothing of it runs."""
 
     ADAPT_FILE = "chhmc_adapt.npz"
 
@@ -372,15 +386,16 @@ class HMCSampler(object):
         self.m = np.ones(ndim) if m is None else m
         self.mass, self.cov = None, None
         self.sampler = None
-        self.diagnostics = None                              # criterion="rhat": dict(rhat, ess, n) of the last check (+ rhat_rank's)
+        self.diagnostics = None                              # criterion="rhat": dict(rhat, ess, n) of the last check (+ rhat_rank's, ess_rank's)
         self.seed, self.group = seed, dist_group
 
     def sample(self, pool, nsamp, samp_steps=0, samp_eps=0, Madapt=1000, outdir="./", progress=False, overwrite=False,
                ntimes=10, tautol=0.01, method="emcee", incremental=True, meanshift=0.1, stdshift=0.1, nk=2, ncheck=100,
                burnin=100, profile=None, adapt_mass=False, adapt_traj=False, max_steps=64, criterion="tau", rhat_tol=1.01,
-               ess_min=400, rhat_discard=0.0, rhat_rank=False):
+               ess_min=400, rhat_discard=0.0, rhat_rank=False, ess_rank=False):
         hmc = method == "hmc"
-        adapt_mass = self._check(self.lnp, method, samp_eps, Madapt, adapt_mass, adapt_traj, max_steps, criterion, rhat_tol, ess_min, rhat_discard, rhat_rank)
+        adapt_mass = self._check(self.lnp, method, samp_eps, Madapt, adapt_mass, adapt_traj, max_steps, criterion, rhat_tol, ess_min, rhat_discard, rhat_rank,
+                                 ess_rank)
         filename = os.path.join(outdir, "chhmc.h5" if hmc else "chemcee_256.h5")       # sampler.py:466-469
         prof, rk, store, x0, resume, done, dchain = _open_run(self, "sampler.HMCSampler.sample", filename, overwrite, profile)
         if not rk.active:
@@ -414,7 +429,7 @@ class HMCSampler(object):
                                                   adapt_traj=bool(adapt_traj), max_steps=max_steps, stored=done)
         else:
             ens.set_state(rk.mine(x0))
-        rule = _RhatRule(dchain, self, rhat_tol, ess_min, rhat_discard, rhat_rank) if criterion == "rhat" else \
+        rule = _RhatRule(dchain, self, rhat_tol, ess_min, rhat_discard, rhat_rank, ess_rank) if criterion == "rhat" else \
             _TauRule(dchain, ntimes, tautol, ncheck, nk, meanshift, stdshift)
         self.diagnostics = None
         with _lib.stage("run_mcmc.blocks"):
@@ -423,7 +438,8 @@ class HMCSampler(object):
         return _close_run(prof, rk, store, dchain, done)
 
     @staticmethod
-    def _check(lnp, method, samp_eps, Madapt, adapt_mass, adapt_traj, max_steps, criterion, rhat_tol, ess_min, rhat_discard, rhat_rank):
+    def _check(lnp, method, samp_eps, Madapt, adapt_mass, adapt_traj, max_steps, criterion, rhat_tol, ess_min, rhat_discard, rhat_rank,
+               ess_rank=False):
         """``sample``'s arguments that exclude each other, before anything is built; returns ``BatchedHMC.adapt_mass_mode(adapt_mass)``."""
         if method not in ("emcee", "hmc"):
             # sampler.py's "nuts" branch is unreachable in the reference (SURVEY section 8 a18) and not built here
@@ -441,6 +457,9 @@ class HMCSampler(object):
         elif rhat_rank:
             raise ValueError("rhat_rank = %r with criterion = %r: the rank-normalised, folded R-hat confirms the checks of "
                              "criterion=\"rhat\"" % (rhat_rank, criterion))
+        elif ess_rank:
+            raise ValueError("ess_rank = %r with criterion = %r: the rank-normalised bulk-ESS and tail-ESS confirm the checks of "
+                             "criterion=\"rhat\"" % (ess_rank, criterion))
         adapt_mass = BatchedHMC.adapt_mass_mode(adapt_mass)
         if hmc and not getattr(lnp, "device_only", True):
             raise NotImplementedError("HMC needs the gradient of the log-probability: a user loglikelihoodfunc / "
