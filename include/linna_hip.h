@@ -745,6 +745,40 @@ int linna_hmc_chees_begin(linna_ctx_t* ctx, int B, int ndim, const float* X, int
 int linna_hmc_chees_end(linna_ctx_t* ctx, int B, int ndim, const float* mass, const float* Cm, int ldc, const float* Q, int ldq,
                         const float* P, int ldp, const float* alpha, const double* r0, double* state, float* EPS, int M,
                         double delta, int max_steps, void* stream);
+
+/* ---- energy diagnostics of the HMC chains (BatchedHMC.energy_stats): divergent transitions and E-BFMI (Betancourt 2016).
+ * The Metropolis launch keeps what it has in registers; nothing is launched per transition for them.  Behind the test, per
+ * chain b (float32, as the test itself):
+ *   E  = accepted ? H1 : H0, the energy of the state the transition ends in (H1 the value the test used) -> energy[b];
+ *   dH = H1 - H0, the energy ERROR (the sign opposite to the test's H0 - H1) -> dH[b];
+ *   divergent = !(isfinite(lnp_new[b]) && dH <= max_dH): a NaN error, a proposal that is not finite or an error above max_dH;
+ *   equality is not.  A divergent transition is a rejection.  ndiv[b] += 1 then.
+ * The accumulators: estate[b] = {n, mean, M2, D2, Eprev}, LINNA_HMC_ENERGY_DOUBLES doubles per chain in device memory (zeros =
+ * empty).  For a finite E: Welford's update n += 1, d = E - mean, mean += d / n, M2 += d (E - mean); D2 += (E - Eprev)^2 where
+ * n >= 1 before it; Eprev = E.  An E that is not finite changes nothing of them.  Float64, one writer per chain, no
+ * floating-point atomics: the same input gives the same bits.
+ * linna_hmc_energy_finish: bfmi[b] = D2 / M2 -- Stan's definition, sum_{n>=1} (E_n - E_{n-1})^2 / sum_n (E_n - mean)^2, WITHOUT a
+ * factor N / (N - 1) -- NaN for n < 2 or M2 == 0; pooled[0] = the smallest bfmi over the chains (NaN ones ignored; NaN if all
+ * are), pooled[1] = sum_b ndiv[b], pooled[2] = the chains with ndiv[b] > 0 (3 doubles, device).  One workgroup, a fixed order.
+ * A divergence is judged on the END-POINT error of the trajectory: one that blows up and comes back is not seen. */
+#define LINNA_HMC_ENERGY_DOUBLES 5
+size_t linna_hmc_energy_doubles(int B);         /* LINNA_HMC_ENERGY_DOUBLES B; 0 for B < 1 */
+/* linna_hmc_accept_adapt (the same kernel) with the diagnostics behind it.  estate and ndiv: both or neither (then max_dH > 0);
+ * energy and dH: each optional.  All four NULL: linna_hmc_accept_adapt bit for bit. */
+int linna_hmc_accept_energy(linna_ctx_t* ctx, int B, int ndim, const float* mass, uint64_t seed, const int* step_dev,
+                            int step_offset, const float* H0, const float* P, int ldp, const float* Qnew, int ldq,
+                            const float* lnp_new, const float* Gnew, int ldg, const float* U, float* X, int ldx, float* lnp,
+                            float* G, int* naccept, float* alpha, float* EPS, float* EPSBAR, float* HBAR, const float* MU,
+                            int* M, int Madapt, float delta, float* chain, float* logps, double* estate, int* ndiv,
+                            float max_dH, float* energy, float* dH, void* stream);
+/* linna_hmc_run_dense (Cm == NULL: linna_hmc_run_moments, the diagonal route) with the diagnostics in every Metropolis launch;
+ * energy and dH are [ntrans][B], row i written by transition i.  The chains do not notice: bit for bit those entries'. */
+int linna_hmc_run_energy(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, const float* Cm, int ldc, float* EPS,
+                         float* EPSBAR, float* HBAR, const float* MU, int* M, int Madapt, float delta, int step_offset,
+                         int num_steps, int ntrans, int* naccept, float* alpha, float* chain, float* logps, double* mom,
+                         double* estate, int* ndiv, float max_dH, float* energy, float* dH, void* stream);
+int linna_hmc_energy_finish(linna_ctx_t* ctx, int B, const double* estate, const int* ndiv, float* bfmi, double* pooled,
+                            void* stream);
 int linna_step_increment(linna_ctx_t* ctx, int* step_dev, void* stream);
 
 /* Ensemble slice sampling (zeus DifferentialMove behind sampler.py:728-735): per active walker a

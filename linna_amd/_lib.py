@@ -85,6 +85,7 @@ COMM_ID_BYTES = 128
 LAY_K, LAY_MN = 0, 1
 # the trajectory-length adaptation (LINNA_HMC_CHEES_* of include/linna_hip.h; tests/hmc_chees_emul.py holds the same numbers)
 CHEES_HEAD, CHEES_LR, CHEES_BETA1, CHEES_BETA2, CHEES_ADAM_EPS, CHEES_ALPHA_FLOOR, CHEES_MAX_STEPS = 12, 0.025, 0.9, 0.999, 1e-8, 1e-3, 64
+ENERGY_DOUBLES = 5       # LINNA_HMC_ENERGY_DOUBLES: {n, mean, M2, D2, Eprev} per chain (energy diagnostics of the HMC chains)
 
 _V, _I, _F, _SZ, _U64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_uint64
 _I64, _D = C.c_int64, C.c_double
@@ -217,6 +218,12 @@ _SIGNATURES = {
     "linna_hmc_chees_doubles": (_SZ, [_I]),
     "linna_hmc_chees_begin": (_I, [_V, _I, _I, _V, _I, _V, _V, _V]),
     "linna_hmc_chees_end": (_I, [_V, _I, _I, _V, _V, _I, _V, _I, _V, _I, _V, _V, _V, _V, _I, _D, _I, _V]),
+    "linna_hmc_energy_doubles": (_SZ, [_I]),
+    "linna_hmc_accept_energy": (_I, [_V, _I, _I, _V, _U64, _V, _I, _V, _V, _I, _V, _I, _V, _V, _I, _V, _V, _I, _V, _V, _V, _V,
+                                     _V, _V, _V, _V, _V, _I, _F, _V, _V, _V, _V, _F, _V, _V, _V]),
+    "linna_hmc_run_energy": (_I, [_V, _V, _V, _V, _I, _V, _V, _V, _V, _V, _I, _F, _I, _I, _I, _V, _V, _V, _V, _V, _V, _V, _F, _V, _V,
+                                  _V]),
+    "linna_hmc_energy_finish": (_I, [_V, _I, _V, _V, _V, _V, _V]),
     "linna_step_increment": (_I, [_V, _V, _V]),
     "linna_slice_init": (_I, [_V, _V, _V, _I, _V, _I, _V, _I, _I, _V, _U64, _V, _I, _V, _I, _V, _V, _V, _V, _I, _V]),
     "linna_slice_points": (_I, [_V, _V, _I, _I, _V, _I, _V, _I, _V, _V, _I, _I, _V]),

@@ -1765,24 +1765,35 @@ static int hmc_trajectory(linna_logprob_t* lp, const linna_hmc_state_t* st, void
     return LINNA_OK;
 }
 
-// linna_hmc_run, linna_hmc_run_moments and linna_hmc_run_dense: mom != nullptr adds the moments launch on st->X behind every
-// Metropolis launch (under a dense mass the co-moments launch)
+// what the entries that take the energy diagnostics check of them (linna_hip.h): estate with ndiv, and then max_dH > 0
+static int hmc_energy_check(const HmcEnergy& en, const char* who) {
+    if ((en.estate != nullptr) != (en.ndiv != nullptr)) { set_error("%s: estate and ndiv come together", who); return LINNA_ERR_INVALID; }
+    if (en.estate && !(en.max_dH > 0.f)) { set_error("%s: max_dH %g is not positive", who, (double)en.max_dH); return LINNA_ERR_INVALID; }
+    return LINNA_OK;
+}
+// linna_hmc_run, linna_hmc_run_moments, linna_hmc_run_dense and linna_hmc_run_energy: mom != nullptr adds the moments launch on
+// st->X behind every Metropolis launch (under a dense mass the co-moments launch); en: the energy diagnostics in that launch,
+// its energy / dH rows [ntrans][B]
 static int hmc_run_impl(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, float* EPS, float* EPSBAR, float* HBAR, const float* MU,
                         int* M, int Madapt, float delta, int step_offset, int num_steps, int ntrans, int* naccept, float* alpha,
-                        float* chain, float* logps, double* mom, void* stream, const HmcDense& dn = HmcDense{nullptr, 0}) {
+                        float* chain, float* logps, double* mom, void* stream, const HmcDense& dn = HmcDense{nullptr, 0},
+                        const HmcEnergy& en = HmcEnergy{}) {
     if (!lp || !st || !ws || !EPS || num_steps < 1 || ntrans < 1 || Madapt < 0 || (chain != nullptr) != (logps != nullptr)) {
         set_error("hmc_run: bad arguments"); return LINNA_ERR_INVALID;
     }
     if (Madapt > 0 && (!EPSBAR || !HBAR || !MU || !M)) { set_error("hmc_run: Madapt > 0 needs the adaptation state"); return LINNA_ERR_INVALID; }
+    TRY(hmc_energy_check(en, "hmc_run_energy"));
     TRY(hmc_entry_check(lp, st, "hmc_run"));
     if (dn.C) TRY(hmc_dense_check(lp, dn, "hmc_run_dense"));
     const int B = st->B, nd = lp->d.nin, ld = st->ld;
     const HmcAdapt ad{EPS, EPSBAR, HBAR, MU, M, Madapt, delta};
     for (int i = 0; i < ntrans; ++i) {
         TRY(hmc_trajectory(lp, st, ws, nullptr, EPS, step_offset + i, num_steps, stream, dn));
+        const HmcEnergy row{en.estate, en.ndiv, en.max_dH, en.energy ? en.energy + (size_t)i * B : nullptr,
+                            en.dH ? en.dH + (size_t)i * B : nullptr};
         TRY(launch_hmc_accept(B, nd, st->mass, st->seed, st->step_dev, step_offset + i, st->H0, st->P, ld, st->Q, ld, st->lnp_new,
                               st->Gnew, ld, nullptr, st->X, ld, st->lnp, st->G, naccept, alpha, ad,
-                              chain ? chain + (size_t)i * B * nd : nullptr, logps ? logps + (size_t)i * B : nullptr, S(stream)));
+                              chain ? chain + (size_t)i * B * nd : nullptr, logps ? logps + (size_t)i * B : nullptr, row, S(stream)));
         if (mom) TRY(dn.C ? launch_hmc_comoments(B, nd, st->X, ld, mom, S(stream)) : launch_hmc_moments(B, nd, st->X, ld, mom, S(stream)));
     }
     return LINNA_OK;
@@ -1829,6 +1840,14 @@ int linna_hmc_run_dense(linna_logprob_t* lp, const linna_hmc_state_t* st, void* 
     if (!Cm) { set_error("hmc_run_dense: no factor"); return LINNA_ERR_INVALID; }
     return hmc_run_impl(lp, st, ws, EPS, EPSBAR, HBAR, MU, M, Madapt, delta, step_offset, num_steps, ntrans, naccept, alpha, chain,
                         logps, mom, stream, HmcDense{Cm, ldc});
+} LINNA_CATCH_INT
+
+int linna_hmc_run_energy(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, const float* Cm, int ldc, float* EPS, float* EPSBAR,
+                         float* HBAR, const float* MU, int* M, int Madapt, float delta, int step_offset, int num_steps, int ntrans,
+                         int* naccept, float* alpha, float* chain, float* logps, double* mom, double* estate, int* ndiv, float max_dH,
+                         float* energy, float* dH, void* stream) try {
+    return hmc_run_impl(lp, st, ws, EPS, EPSBAR, HBAR, MU, M, Madapt, delta, step_offset, num_steps, ntrans, naccept, alpha, chain,
+                        logps, mom, stream, HmcDense{Cm, Cm ? ldc : 0}, HmcEnergy{estate, ndiv, max_dH, energy, dH});
 } LINNA_CATCH_INT
 
 int linna_hmc_find_epsilon_dense(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, const float* Cm, int ldc, float* R0,
@@ -2127,14 +2146,37 @@ int linna_hmc_accept_adapt(linna_ctx_t*, int B, int ndim, const float* mass, uin
     }
     const HmcAdapt ad{EPS, EPSBAR, HBAR, MU, M, Madapt, delta};
     return launch_hmc_accept(B, ndim, mass, seed, step_dev, step_offset, H0, P, ldp, Qn, ldq, lnp_new, Gn, ldg, U, X, ldx, lnp, G,
-                             naccept, alpha, ad, chain, logps, S(stream));
+                             naccept, alpha, ad, chain, logps, HmcEnergy{}, S(stream));
+} LINNA_CATCH_INT
+size_t linna_hmc_energy_doubles(int B) try {
+    if (B < 1) return 0;
+    return (size_t)LINNA_HMC_ENERGY_DOUBLES * (size_t)B;
+} LINNA_CATCH_SIZE
+int linna_hmc_accept_energy(linna_ctx_t*, int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, int step_offset,
+                            const float* H0, const float* P, int ldp, const float* Qn, int ldq, const float* lnp_new, const float* Gn,
+                            int ldg, const float* U, float* X, int ldx, float* lnp, float* G, int* naccept, float* alpha, float* EPS,
+                            float* EPSBAR, float* HBAR, const float* MU, int* M, int Madapt, float delta, float* chain, float* logps,
+                            double* estate, int* ndiv, float max_dH, float* energy, float* dH, void* stream) try {
+    if (B < 1 || ndim < 1 || !mass || !step_dev || !H0 || !P || !Qn || !lnp_new || !Gn || !X || !lnp || !G || Madapt < 0 ||
+        (Madapt > 0 && (!EPS || !EPSBAR || !HBAR || !MU || !M))) {
+        set_error("hmc_accept_energy: bad arguments"); return LINNA_ERR_INVALID;
+    }
+    const HmcEnergy en{estate, ndiv, max_dH, energy, dH};
+    TRY(hmc_energy_check(en, "hmc_accept_energy"));
+    const HmcAdapt ad{EPS, EPSBAR, HBAR, MU, M, Madapt, delta};
+    return launch_hmc_accept(B, ndim, mass, seed, step_dev, step_offset, H0, P, ldp, Qn, ldq, lnp_new, Gn, ldg, U, X, ldx, lnp, G,
+                             naccept, alpha, ad, chain, logps, en, S(stream));
+} LINNA_CATCH_INT
+int linna_hmc_energy_finish(linna_ctx_t*, int B, const double* estate, const int* ndiv, float* bfmi, double* pooled, void* stream) try {
+    if (B < 1 || !estate || !ndiv || !bfmi || !pooled) { set_error("hmc_energy_finish: bad arguments"); return LINNA_ERR_INVALID; }
+    return launch_hmc_energy_finish(B, estate, ndiv, bfmi, pooled, S(stream));
 } LINNA_CATCH_INT
 int linna_hmc_accept(linna_ctx_t*, int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, const float* H0,
                      const float* P, int ldp, const float* Qn, int ldq, const float* lnp_new, const float* Gn, int ldg,
                      const float* U, float* X, int ldx, float* lnp, float* G, int* naccept, void* stream) try {
     // the Metropolis test alone: no acceptance rate, no chain row, no adaptation state
     return launch_hmc_accept(B, ndim, mass, seed, step_dev, 0, H0, P, ldp, Qn, ldq, lnp_new, Gn, ldg, U, X, ldx, lnp, G, naccept, nullptr,
-                             HmcAdapt{}, nullptr, nullptr, S(stream));
+                             HmcAdapt{}, nullptr, nullptr, HmcEnergy{}, S(stream));
 } LINNA_CATCH_INT
 int linna_step_increment(linna_ctx_t*, int* step_dev, void* stream) try { return launch_step_increment(step_dev, S(stream)); } LINNA_CATCH_INT
 

@@ -309,11 +309,16 @@ int launch_hmc_kick_drift(int B, int ndim, const float* mass, float ek, float ed
                           int ldp, float* Q, int ldq, hipStream_t s, const float* eps = nullptr);
 // the dual-averaging state of hmc_accept_kernel, one entry per chain (sampler.py:198-240 of the reference)
 struct HmcAdapt { float* eps; float* epsbar; float* Hbar; const float* mu; int* m; int Madapt; float delta; };
-// the one Metropolis launcher: alpha, chain, logps and ad.m are each nullable (linna_hmc_accept passes all of them null)
+// the energy diagnostics of hmc_accept_kernel (linna_hip.h, linna_hmc_accept_energy): estate[B][LINNA_HMC_ENERGY_DOUBLES] with
+// ndiv[B] (both or neither), energy[B] and dH[B] each nullable; HmcEnergy{}: the kernel does what it did before the group
+struct HmcEnergy { double* estate; int* ndiv; float max_dH; float* energy; float* dH; };
+// the one Metropolis launcher: alpha, chain, logps, ad.m and en's pointers are each nullable (linna_hmc_accept passes all of them null)
 int launch_hmc_accept(int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, int step_off, const float* H0,
                       const float* P, int ldp, const float* Qn, int ldq, const float* lnp_new, const float* Gn, int ldg,
                       const float* U, float* X, int ldx, float* lnp, float* G, int* naccept, float* alpha,
-                      const HmcAdapt& ad, float* chain, float* logps, hipStream_t s);
+                      const HmcAdapt& ad, float* chain, float* logps, const HmcEnergy& en, hipStream_t s);
+// bfmi[B] = D2 / M2 of the accumulators, pooled = {min E-BFMI, sum ndiv, chains with a divergence} (float64)
+int launch_hmc_energy_finish(int B, const double* estate, const int* ndiv, float* bfmi, double* pooled, hipStream_t s);
 int launch_hmc_find_eps_init(int B, int ndim, uint64_t seed, const int* step_dev, int step_off, float* R0, int ldr, float* eps,
                              int* state, hipStream_t s);
 int launch_hmc_find_eps(int B, int ndim, const float* mass, const float* H0, const float* P, int ldp, const float* lnp_new,

@@ -526,7 +526,15 @@ __global__ void hmc_kick_drift_kernel(int B, int ndim, const float* __restrict__
 //      Hbar = (1 - 1/(m + t0)) Hbar + (delta - alpha) / (m + t0);  eps = exp(mu - sqrt(m) / gamma Hbar);
 //      epsbar = exp((1 - m^-kappa) log epsbar + m^-kappa log eps),
 //    at m == Madapt + 1 eps = epsbar, later nothing.  This launch follows every leapfrog launch of its transition: eps[b]
-//    has no reader left.
+//    has no reader left;
+//  * en (HmcEnergy, every pointer nullable; estate and ndiv come together): the energy diagnostics of the transition, by
+//    lane 0 behind the test.  E = acc ? H1 : H0 (the energy of the state the transition ends in, H1 the value the test
+//    used) to en.energy[b]; the energy ERROR H1 - H0 (not the test's H0 - H1) to en.dH[b]; the transition is divergent
+//    unless lnp_new is finite and H1 - H0 <= en.max_dH (a NaN error is; equality is not; a divergent transition never
+//    accepts), ndiv[b] += 1 then -- a plain store, this wave owns the chain; and the chain's float64 accumulators
+//    estate[b] = {n, mean, M2, D2, Eprev} (zeros = empty): for a finite E Welford's update of n, mean, M2, for n >= 1 before it
+//    D2 += (E - Eprev)^2, then Eprev = E; a non-finite E changes nothing.  One writer, one order: the same input gives
+//    the same bits.  hmc_energy_finish_kernel turns them into E-BFMI.
 __global__ void hmc_accept_kernel(int B, int ndim, const float* __restrict__ mass, uint64_t seed,
                                   const int* __restrict__ step_dev, int step_off, const float* __restrict__ H0,
                                   const float* __restrict__ P, int ldp, const float* __restrict__ Qn, int ldq,
@@ -534,14 +542,15 @@ __global__ void hmc_accept_kernel(int B, int ndim, const float* __restrict__ mas
                                   const float* __restrict__ U,
                                   float* __restrict__ X, int ldx, float* __restrict__ lnp, float* __restrict__ G,
                                   int* __restrict__ naccept, float* __restrict__ alpha, HmcAdapt ad,
-                                  float* __restrict__ chain, float* __restrict__ logps) {
+                                  float* __restrict__ chain, float* __restrict__ logps, HmcEnergy en) {
     const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;   // a wave per chain
     if (b >= B) return;
     const float ke = wave_kinetic(P, ldp, mass, ndim, b, lane);
     const float ln = lnp_new[b];
     const float H1 = 0.5f * ke - ln;
     const U4 r = walker_bits(seed, (uint32_t)b, (uint32_t)(step_dev[0] + step_off), 2u, 0u);
-    const float dH = H0[b] - H1;
+    const float h0 = H0[b];
+    const float dH = h0 - H1;
     const float ratio = expf(dH > 0.f ? 0.f : dH);   // a NaN energy stays NaN and rejects (np.minimum; fminf would return 0)
     const float u = U ? U[b] : u01(r.x);
     const bool acc = isfinite(ln) && u < ratio;
@@ -562,6 +571,21 @@ __global__ void hmc_accept_kernel(int B, int ndim, const float* __restrict__ mas
     if (logps) logps[b] = acc ? ln : lnp[b];
     const float al = isfinite(ln) && isfinite(dH) ? ratio : 0.f;
     if (alpha) alpha[b] = al;
+    if (en.energy || en.dH || en.estate) {
+        const float E = acc ? H1 : h0, err = H1 - h0;
+        if (en.energy) en.energy[b] = E;
+        if (en.dH) en.dH[b] = err;
+        if (en.estate) {
+            if (!(isfinite(ln) && err <= en.max_dH)) en.ndiv[b] += 1;
+            if (isfinite(E)) {
+                double* s = en.estate + (size_t)LINNA_HMC_ENERGY_DOUBLES * b;
+                const double e = (double)E, n0 = s[0], n1 = n0 + 1.0, d = e - s[1], mean = s[1] + d / n1;
+                s[2] += d * (e - mean);
+                if (n0 >= 1.0) { const double t = e - s[4]; s[3] += t * t; }
+                s[0] = n1; s[1] = mean; s[4] = e;
+            }
+        }
+    }
     if (!ad.m) return;
     const int m = ad.m[b];
     ad.m[b] = m + 1;
@@ -577,6 +601,48 @@ __global__ void hmc_accept_kernel(int B, int ndim, const float* __restrict__ mas
         ad.epsbar[b] = expf((1.f - eta) * logf(ad.epsbar[b]) + eta * logf(e));
     } else if (m == ad.Madapt + 1) {
         ad.eps[b] = ad.epsbar[b];
+    }
+}
+
+// The finish of the energy diagnostics hmc_accept_kernel accumulates: bfmi[b] = D2 / M2 (Stan's E-BFMI,
+// sum_{n>=1} (E_n - E_{n-1})^2 / sum_n (E_n - mean)^2, no N / (N - 1) factor), NaN for n < 2 or M2 == 0, and
+// pooled = {the smallest E-BFMI over the chains, NaN ones ignored (NaN if all are), sum_b ndiv[b], the chains with ndiv[b] > 0}.
+// ONE workgroup, a thread per chain striding over B; the three values of a thread meet by shuffles over the wave and by
+// LDS over the waves, in wave order (a minimum has no order; the counts are integers in a double: exact).  Nothing atomic.
+constexpr int ENERGY_WAVES = 4;
+__device__ __forceinline__ double wave_min_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));      // (fmin returns the operand that is a number)
+    return v;
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__global__ __launch_bounds__(ENERGY_WAVES * 64) void hmc_energy_finish_kernel(int B, const double* __restrict__ estate,
+                                                                              const int* __restrict__ ndiv, float* __restrict__ bfmi,
+                                                                              double* __restrict__ pooled) {
+    __shared__ double red[3][ENERGY_WAVES];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    double mn = nan, total = 0.0, chains = 0.0;
+    for (int b = threadIdx.x; b < B; b += ENERGY_WAVES * 64) {
+        const double* s = estate + (size_t)LINNA_HMC_ENERGY_DOUBLES * b;
+        const double r = s[0] >= 2.0 && s[2] != 0.0 ? s[3] / s[2] : nan;
+        bfmi[b] = (float)r;
+        mn = fmin(mn, r);
+        const int k = ndiv[b];
+        total += (double)k;
+        chains += k > 0 ? 1.0 : 0.0;
+    }
+    mn = wave_min_f64(mn); total = wave_sum_f64(total); chains = wave_sum_f64(chains);
+    if (lane == 0) { red[0][wave] = mn; red[1][wave] = total; red[2][wave] = chains; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        mn = red[0][0]; total = red[1][0]; chains = red[2][0];
+        for (int w = 1; w < ENERGY_WAVES; ++w) { mn = fmin(mn, red[0][w]); total += red[1][w]; chains += red[2][w]; }
+        pooled[0] = mn; pooled[1] = total; pooled[2] = chains;
     }
 }
 
@@ -910,11 +976,6 @@ enum { CH_T = 0, CH_LOGT, CH_LOGTBAR, CH_A, CH_V, CH_MU, CH_HBAR, CH_LOGEPS, CH_
 static_assert(CH_NVALID + 1 == CHEES_HEAD, "the layout of linna_hip.h");
 static_assert(CHEES_U == 8 && 2 * CHEES_V == 8, "wave_sum8_f64 takes eight sums");
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 // Eight sums over the wave at once: three halving steps (lanes 32, 16, 8 apart) in each of which a lane hands half of its values
 // to its partner and adds the partner's share of the half it keeps, then a butterfly of the one value left over lanes 4, 2
 // and 1 apart -- 10 exchanges of a double where eight butterflies take 48 (hmc_chees_begin_kernel at 4096 chains x 33: 157 ->
@@ -1455,10 +1516,14 @@ int launch_hmc_kick_drift(int B, int ndim, const float* mass, float ek, float ed
 int launch_hmc_accept(int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, int step_off, const float* H0,
                       const float* P, int ldp, const float* Qn, int ldq, const float* lnp_new, const float* Gn, int ldg,
                       const float* U, float* X, int ldx, float* lnp, float* G, int* naccept, float* alpha,
-                      const HmcAdapt& ad, float* chain, float* logps, hipStream_t s) {
+                      const HmcAdapt& ad, float* chain, float* logps, const HmcEnergy& en, hipStream_t s) {
     hipLaunchKernelGGL(hmc_accept_kernel, dim3((B + 3) / 4), dim3(256), 0, s, B, ndim, mass, seed, step_dev, step_off, H0, P,
-                       ldp, Qn, ldq, lnp_new, Gn, ldg, U, X, ldx, lnp, G, naccept, alpha, ad, chain, logps);
+                       ldp, Qn, ldq, lnp_new, Gn, ldg, U, X, ldx, lnp, G, naccept, alpha, ad, chain, logps, en);
     LAUNCH_CHECK("hmc_accept");
+}
+int launch_hmc_energy_finish(int B, const double* estate, const int* ndiv, float* bfmi, double* pooled, hipStream_t s) {
+    hipLaunchKernelGGL(hmc_energy_finish_kernel, dim3(1), dim3(ENERGY_WAVES * 64), 0, s, B, estate, ndiv, bfmi, pooled);
+    LAUNCH_CHECK("hmc_energy_finish");
 }
 int launch_hmc_find_eps_init(int B, int ndim, uint64_t seed, const int* step_dev, int step_off, float* R0, int ldr, float* eps,
                              int* state, hipStream_t s) {

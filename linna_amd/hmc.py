@@ -35,7 +35,14 @@ class BatchedHMC(object):
 
     ``adapt_traj`` (or ``adapt(adapt_traj=True)``) gives all chains one step size and a trajectory length ``self.traj`` learned
     during a warm-up of its own (ChEES-HMC, linna_hmc_chees_begin / linna_hmc_chees_end); ``run()`` without ``num_steps`` then
-    runs ``steps_for(i)`` leapfrog steps at Philox step i, under whatever mass the object has."""
+    runs ``steps_for(i)`` leapfrog steps at Philox step i, under whatever mass the object has.
+
+    ``energy_stats()`` switches the energy diagnostics on: every transition of ``run()`` then also counts as divergent when its
+    proposal is not finite or its energy error H1 - H0 exceeds ``max_dH``, and feeds the energy of the state it ends in to
+    per-chain float64 accumulators, all inside the Metropolis launch (linna_hmc_run_energy); ``energy_summary()`` reads the
+    E-BFMI per chain (Betancourt 2016; Stan's definition) and the divergence counts.  The chains are bit for bit the same.
+    A divergence is judged on the end point of the trajectory only.  Warm-ups (``adapt``, ``adapt_traj``,
+    ``find_reasonable_epsilon``) are never counted."""
 
     DENSE_MAX_NDIM = 128                        # LINNA_HMC_DENSE_MAX_NDIM
 
@@ -76,6 +83,9 @@ class BatchedHMC(object):
         self.num_steps = 5                     # run()'s default (HMCSampler.sample sets it)
         # adapt_traj(): the trajectory length run() then divides into leapfrog steps, its cap, the device state of the adaptation
         self.traj, self.max_steps, self.chees, self._traj_eps = None, _lib.CHEES_MAX_STEPS, None, None
+        # energy_stats(): {n, mean, M2, D2, Eprev} per chain (device float64), the divergent transitions per chain, the bound on
+        # the energy error; _warm > 0 while a warm-up runs (its transitions are never counted)
+        self.estate, self.ndiv, self.max_dH, self._warm = None, None, 1000.0, 0
         self.nw, self.iteration, self._dev_steps = self.B, 0, 0     # (what _run_blocks / _Ranks.gather read; Philox step = iteration)
         self._state = None
         self.lp.evaluate_with_grad(self.x, out=self.lnp, grad=self.g)
@@ -149,7 +159,7 @@ class BatchedHMC(object):
                           "they reached" % (n, self.B, max_rounds))
         return n
 
-    def run(self, ntrans, num_steps=None, store=True, Madapt=0, target_accept=0.65, moments=False):
+    def run(self, ntrans, num_steps=None, store=True, Madapt=0, target_accept=0.65, moments=False, energy=False):
         """``ntrans`` transitions of ``num_steps`` leapfrog steps with the per-chain step sizes ``self.eps``, enqueued by ONE C
         call (linna_hmc_run: 2 + num_steps launches per transition, the chain rows written by the Metropolis launch); returns
         (chain[ntrans, B, ndim], lnp[ntrans, B]) as device tensors, (None, None) without ``store``.  Bit for bit a loop of
@@ -161,26 +171,39 @@ class BatchedHMC(object):
 
         Without ``num_steps`` and with a trajectory length in place (``adapt_traj`` / ``set_traj``): one C call per
         transition, the one at Philox step i with ``steps_for(i)`` leapfrog steps, into the rows of the same block --
-        bit for bit a loop of ``run(1, num_steps=steps_for(i))``.  An explicit ``num_steps`` means what it always did."""
+        bit for bit a loop of ``run(1, num_steps=steps_for(i))``.  An explicit ``num_steps`` means what it always did.
+
+        With ``energy_stats()`` on, every route above goes through linna_hmc_run_energy and the transitions are counted.
+        ``energy``: returns (chain, lnp, E[ntrans, B], dH[ntrans, B]) -- the energy of the state every transition ended in and
+        its energy error H1 - H0, device float32 (with the statistics off too)."""
         by_length = num_steps is None and self.traj is not None
         num_steps = self.num_steps if num_steps is None else int(num_steps)
         chain = torch.empty((ntrans, self.B, self.ndim), dtype=torch.float32, device=self.dev) if store else None
         lps = torch.empty((ntrans, self.B), dtype=torch.float32, device=self.dev) if store else None
+        E, dH = ((torch.empty((ntrans, self.B), dtype=torch.float32, device=self.dev) for _ in range(2)) if energy else (None, None))
         if by_length:
             for k in range(ntrans):
                 self._enqueue(1, self.steps_for(self.iteration), chain[k:k + 1] if store else None, lps[k:k + 1] if store else None,
-                              Madapt, target_accept, moments)
+                              Madapt, target_accept, moments, (E[k:k + 1], dH[k:k + 1]) if energy else None)
         elif ntrans > 0:
-            self._enqueue(ntrans, num_steps, chain, lps, Madapt, target_accept, moments)
-        return chain, lps
+            self._enqueue(ntrans, num_steps, chain, lps, Madapt, target_accept, moments, (E, dH) if energy else None)
+        return (chain, lps, E, dH) if energy else (chain, lps)
 
-    def _enqueue(self, ntrans, num_steps, chain, lps, Madapt, target_accept, moments):
-        """run()'s one C call: ``ntrans`` transitions of ``num_steps`` leapfrog steps, their rows to ``chain`` / ``lps``."""
+    def _enqueue(self, ntrans, num_steps, chain, lps, Madapt, target_accept, moments, rows=None):
+        """run()'s one C call: ``ntrans`` transitions of ``num_steps`` leapfrog steps, their rows to ``chain`` / ``lps`` (and
+        ``rows`` = (E, dH)); through linna_hmc_run_energy when ``rows`` are asked for or the energy statistics count."""
         h, ws = self.lp._ensure()["handle"], _lib.ptr(self.lp._workspace(self.B, True))
         args = (_lib.ptr(self.eps), _lib.ptr(self.epsbar), _lib.ptr(self.Hbar),
                 _lib.ptr(self.mu), _lib.iptr(self.m), int(Madapt), float(target_accept), self.iteration - self._dev_steps,
                 int(num_steps), int(ntrans), _lib.iptr(self.naccept), _lib.ptr(self.alpha), _lib.ptr(chain), _lib.ptr(lps))
-        if self.chol is not None:
+        count = self.estate is not None and not self._warm
+        if count or rows is not None:
+            mom = None if not moments else _lib.ptr(self._moments() if self.chol is None else self._comoments(), torch.float64)
+            E, dH = rows if rows is not None else (None, None)
+            _lib.call("linna_hmc_run_energy", h, self._hmc_state(), ws, _lib.ptr(self.chol), self.ld if self.chol is not None else 0,
+                      *args, mom, _lib.ptr(self.estate, torch.float64) if count else None, _lib.iptr(self.ndiv) if count else None,
+                      float(self.max_dH), _lib.ptr(E), _lib.ptr(dH), _lib.stream())
+        elif self.chol is not None:
             _lib.call("linna_hmc_run_dense", h, self._hmc_state(), ws, _lib.ptr(self.chol), self.ld, *args,
                       _lib.ptr(self._comoments(), torch.float64) if moments else None, _lib.stream())
         elif moments:
@@ -188,6 +211,47 @@ class BatchedHMC(object):
         else:
             _lib.call("linna_hmc_run", h, self._hmc_state(), ws, *args, _lib.stream())
         self.iteration += ntrans
+
+    def energy_stats(self, on=True, max_dH=1000.0):
+        """Switch the energy diagnostics on (the accumulators allocated, or zeroed if they exist) or off.  ``max_dH``: the
+        energy error H1 - H0 above which a transition is divergent (Stan's 1000); not positive: a ``ValueError``."""
+        if not on:
+            self.estate = self.ndiv = None
+            return
+        if not float(max_dH) > 0.0:
+            raise ValueError("energy_stats: max_dH = %r is not positive" % (max_dH,))
+        self.max_dH = float(max_dH)
+        if self.estate is None:
+            self.estate = torch.zeros((self.B, _lib.ENERGY_DOUBLES), dtype=torch.float64, device=self.dev)
+            self.ndiv = torch.zeros(self.B, dtype=torch.int32, device=self.dev)
+        else:
+            self.energy_reset()
+
+    def energy_reset(self):
+        """Empty the accumulators and the divergence counts (nothing without ``energy_stats()``)."""
+        if self.estate is not None:
+            self.estate.zero_()
+            self.ndiv.zero_()
+
+    def energy_finish(self, estate=None, ndiv=None):
+        """linna_hmc_energy_finish on the accumulators (or on copies of them): (bfmi[B] float32, pooled[3] float64), device."""
+        estate, ndiv = self.estate if estate is None else estate, self.ndiv if ndiv is None else ndiv
+        bfmi = torch.empty(self.B, dtype=torch.float32, device=self.dev)
+        pooled = torch.empty(3, dtype=torch.float64, device=self.dev)
+        _lib.call("linna_hmc_energy_finish", self.ctx, self.B, _lib.ptr(estate, torch.float64), _lib.iptr(ndiv), _lib.ptr(bfmi),
+                  _lib.ptr(pooled, torch.float64), _lib.stream())
+        return bfmi, pooled
+
+    def energy_summary(self):
+        """dict(bfmi[B], ndivergent[B], n[B], bfmi_min, ndivergent_total, chains_divergent, max_dH) of the transitions counted
+        so far: E-BFMI per chain as D2 / M2 (Stan's definition; NaN for fewer than two energies or a constant one), its
+        minimum over the chains (NaN ones ignored), the divergent transitions per chain, their sum and the chains that had one."""
+        if self.estate is None:
+            raise ValueError("energy_summary: the energy diagnostics are off (energy_stats() first)")
+        bfmi, pooled = self.energy_finish()
+        pooled = pooled.tolist()
+        return dict(bfmi=bfmi.cpu().numpy(), ndivergent=self.ndiv.cpu().numpy(), n=self.estate[:, 0].cpu().numpy().astype(np.int64),
+                    bfmi_min=pooled[0], ndivergent_total=int(pooled[1]), chains_divergent=int(pooled[2]), max_dH=self.max_dH)
 
     @staticmethod
     def halton(t):
@@ -237,6 +301,13 @@ class BatchedHMC(object):
         M, max_steps = int(M), int(_lib.CHEES_MAX_STEPS if max_steps is None else max_steps)
         if M < 1 or max_steps < 1:
             raise ValueError("adapt_traj: M = %r warm-up transitions, max_steps = %r: both at least 1" % (M, max_steps))
+        self._warm += 1
+        try:
+            return self._adapt_traj(M, target_accept, max_steps)
+        finally:
+            self._warm -= 1
+
+    def _adapt_traj(self, M, target_accept, max_steps):
         self.traj = self._traj_eps = None
         self.find_reasonable_epsilon()
         eps0 = float(torch.median(self.eps))
@@ -322,9 +393,13 @@ class BatchedHMC(object):
 
         ``adapt_traj``: behind all of the above ``adapt_traj(Madapt, target_accept, max_steps)`` adapts one shared step size
         and the trajectory length under the mass the sequence above produced."""
-        windows = self._adapt(Madapt, target_accept, adapt_mass)
-        if adapt_traj:
-            self.adapt_traj(Madapt, target_accept, max_steps)
+        self._warm += 1
+        try:
+            windows = self._adapt(Madapt, target_accept, adapt_mass)
+            if adapt_traj:
+                self.adapt_traj(Madapt, target_accept, max_steps)
+        finally:
+            self._warm -= 1
         return windows
 
     def _adapt(self, Madapt, target_accept, adapt_mass):

@@ -150,7 +150,99 @@ class _Prof(object):
         self.out.update(extra)
 
 
-def _run_blocks(ens, rk, store, dchain, done, nsamp, ncheck, incremental, rule, prof):
+class _EnergyLog(object):
+    """``energy_stats=True``: what the driver keeps of the chains' energy diagnostics (``BatchedHMC.energy_stats``; single-rank
+    runs).  Every block's dH rows and a copy of the accumulators as the block left them -- taken on the sampling stream, so
+    that the block sampled during a check does not show in them and a block that is dropped can be taken back -- go to the
+    host on the statistics stream behind the block's chain rows; at the check ``drv.diagnostics`` gains ``bfmi``,
+    ``ndivergent`` and ``divergent_fraction``, one line is printed, and ``bfmi_min`` / ``max_divergent`` gate a check that
+    passed (NaN: not converged).  ``divergent_at`` collects (stored row, walker) of the divergent stored transitions: the
+    start point of such a trajectory is the chain row before it.  ``chhmc_energy.npz`` holds all of it and continues a
+    resumed run."""
+
+    FILE = "chhmc_energy.npz"
+
+    def __init__(self, drv, ens, path, bfmi_min, max_divergent, resume):
+        self.drv, self.ens, self.path, self.bfmi_min, self.max_divergent = drv, ens, path, bfmi_min, max_divergent
+        self.at, self.new, self.kept, self.pending, self.last = [np.zeros((0, 2), np.int64)], None, None, None, None
+        if resume and os.path.exists(path):
+            with np.load(path) as f:
+                if {"estate", "ndivergent", "divergent_at"} <= set(f.files) and f["estate"].shape == (ens.B, _lib.ENERGY_DOUBLES) \
+                        and f["ndivergent"].shape == (ens.B,):
+                    ens.estate.copy_(torch.as_tensor(np.asarray(f["estate"], np.float64)))
+                    ens.ndiv.copy_(torch.as_tensor(np.asarray(f["ndivergent"], np.int32)))
+                    self.at = [np.asarray(f["divergent_at"], np.int64).reshape(-1, 2)]
+        self.kept = (ens.estate.clone(), ens.ndiv.clone())
+
+    def run(self, ncheck):
+        """``ens.run(ncheck)`` with the block's dH rows and the accumulators behind it put aside."""
+        c, l, _, dh = self.ens.run(ncheck, energy=True)
+        self.new = (dh, self.ens.estate.clone(), self.ens.ndiv.clone())
+        return c, l
+
+    def drop(self):
+        """The block sampled last is not stored: the accumulators go back to where the last stored block left them."""
+        self.ens.estate.copy_(self.kept[0])
+        self.ens.ndiv.copy_(self.kept[1])
+
+    def keep(self, first_row):
+        """The block sampled last is stored as rows ``first_row`` ...: its finish and its way to the host, enqueued on the
+        current (statistics) stream."""
+        dh, est, nd = self.new
+        self.kept = (est, nd)
+        bfmi, pooled = self.ens.energy_finish(est, nd)
+        host = []
+        for t in (dh, est, nd, bfmi, pooled):
+            h = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+            h.copy_(t, non_blocking=True)
+            host.append(h)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.pending = (first_row, host, ev, (dh, bfmi, pooled))        # (the device tensors live until the copies are done)
+
+    @staticmethod
+    def divergent(dH, max_dH):
+        """The kernel's flag from the energy errors alone: an error that is NaN or above ``max_dH``, and an error of -inf, which
+        only a proposal with lnP = +inf gives a chain that started finite."""
+        dH = np.asarray(dH)
+        with np.errstate(invalid="ignore"):
+            return ~(dH <= np.float32(max_dH)) | np.isneginf(dH)
+
+    def check(self, converged, n):
+        """Behind a convergence check over ``n`` stored rows: the diagnostics of those rows, and the gates."""
+        if self.pending is None:
+            return converged
+        first_row, host, ev, _ = self.pending
+        self.pending = None
+        ev.synchronize()
+        dh, est, nd, bfmi, pooled = (h.numpy().copy() for h in host)
+        t, w = np.nonzero(self.divergent(dh, self.ens.max_dH))
+        self.at.append(np.stack([t + first_row, w], axis=1).astype(np.int64))
+        stored = est[:, 0].sum()
+        frac = float(pooled[1] / stored) if stored > 0 else float("nan")
+        self.last = dict(estate=est, ndivergent=nd.astype(np.int64), bfmi=bfmi)
+        if self.drv.diagnostics is None or self.drv.diagnostics.get("n") != n:      # (criterion="tau" keeps none of its own)
+            self.drv.diagnostics = dict(n=n)
+        self.drv.diagnostics.update(bfmi=bfmi, ndivergent=self.last["ndivergent"], divergent_fraction=frac)
+        print("min bfmi, divergent transitions, chains with one, ninter: {0}, {1}, {2}, {3}\n".format(
+            pooled[0], int(pooled[1]), int(pooled[2]), n), flush=True)
+        with np.errstate(invalid="ignore"):
+            if self.bfmi_min is not None:
+                converged = bool(converged and np.all(bfmi >= self.bfmi_min))
+            if self.max_divergent is not None:
+                converged = bool(converged and frac <= self.max_divergent)
+        return converged
+
+    def save(self):
+        """``chhmc_energy.npz``: bfmi[B], ndivergent[B], divergent_at[k][2], n[B], max_dH and the raw accumulators."""
+        if self.last is None:
+            return
+        est = self.last["estate"]
+        np.savez(self.path, bfmi=self.last["bfmi"], ndivergent=self.last["ndivergent"], divergent_at=np.concatenate(self.at, axis=0),
+                 n=est[:, 0].astype(np.int64), max_dH=np.float64(self.ens.max_dH), estate=est)
+
+
+def _run_blocks(ens, rk, store, dchain, done, nsamp, ncheck, incremental, rule, prof, elog=None):
     """The sampling loop of both drivers (sampler.py:530-552, :728-735): blocks of ``ncheck`` iterations, each followed by
     the chain-file append and a convergence check.  Software-pipelined: the statistics of block i run on a stream of
     their own WHILE the sampler already advances block i + 1, and the host reads their verdict (33 numbers in pinned
@@ -163,14 +255,18 @@ def _run_blocks(ens, rk, store, dchain, done, nsamp, ncheck, incremental, rule, 
     with _lib.quiet_gc():                 # (no full pass of the cyclic collector while the launch queue is a few ms deep)
         while done < nsamp:
             with prof.both("sampling"):
-                c, l = ens.run(ncheck)
+                c, l = ens.run(ncheck) if elog is None else elog.run(ncheck)
             c, l, acc = rk.gather(ens, c, l)
             stop = False
             if rk.rank == 0 and pending is not None:
                 with prof.host("wait_check"), torch.cuda.stream(stats):
                     stop = rule.decide(pending, done)
+                    if elog is not None:
+                        stop = elog.check(stop, done)
                 pending = None
             if rk.bcast(stop):
+                if elog is not None:
+                    elog.drop()
                 break
             done += ncheck
             if rk.rank == 0:
@@ -187,9 +283,13 @@ def _run_blocks(ens, rk, store, dchain, done, nsamp, ncheck, incremental, rule, 
                     c.record_stream(stats)
                     dchain.append(c)
                     pending = rule.begin(done)
+                    if elog is not None:
+                        elog.keep(done - ncheck)
     if rk.rank == 0 and pending is not None:                              # the last block's check: printed, not acted upon
         with prof.host("wait_check"), torch.cuda.stream(stats):
-            rule.decide(pending, done)
+            stop = rule.decide(pending, done)
+            if elog is not None:
+                elog.check(stop, done)
     if stats is not None:
         stats.synchronize()
     return done
@@ -374,7 +474,21 @@ class HMCSampler(object):
     ``criterion="rhat"`` only) confirms every check that passed all of the above with that paper's rank-normalised bulk-ESS
     and tail-ESS over all walkers (``DeviceChain.rank_ess``; tail: the smaller ESS of the 5 % and the 95 % quantile) and stops
     only when both are at least ``ess_min`` for every parameter (NaN: not converged); ``self.diagnostics`` then also holds
-    ``ess_bulk`` and ``ess_tail``.  With ``ess_rank=False`` nothing of it runs."""
+    ``ess_bulk`` and ``ess_tail``.  With ``ess_rank=False`` nothing of it runs.
+
+    ``energy_stats=True`` (``method="hmc"``, single-rank runs; otherwise a ``ValueError``) reports whether the Hamiltonian
+    dynamics are healthy, which neither R-hat nor ESS can: the stored transitions whose proposal was not finite or whose
+    energy error H1 - H0 exceeded ``max_dH`` (divergent; judged on the trajectory's end point only) and every chain's E-BFMI
+    (Betancourt 2016, Stan's definition), both accumulated inside the Metropolis launch (``BatchedHMC.energy_stats``); the
+    warm-up is not counted.  At every check ``self.diagnostics`` gains ``bfmi[nwalkers]``, ``ndivergent[nwalkers]`` and
+    ``divergent_fraction`` (a ``"tau"`` run gets a dict of its own) and a line is printed; at the end ``chhmc_energy.npz``
+    next to ``chhmc.h5`` holds ``bfmi``, ``ndivergent``, ``divergent_at[k][2]`` = (stored row, walker) of every divergent
+    stored transition -- the trajectory started at the row before it --, ``n``, ``max_dH`` and the raw accumulators
+    ``estate``; a resumed run whose file fits ``nwalkers`` continues them, ``overwrite=True`` removes the file.  ``bfmi_min``
+    and ``max_divergent`` (a fraction of the stored transitions; with ``criterion="rhat"`` and ``energy_stats`` only) gate the
+    stopping rule: a check that passed everything else converges only with every chain's E-BFMI >= ``bfmi_min`` and the
+    divergent fraction <= ``max_divergent`` (NaN: not converged).  Both default to None, report only: no threshold has been
+    measured on this emulator (Stan warns below an E-BFMI of 0.3).  ``chhmc.h5`` and the chains are the same either way."""
 
     ADAPT_FILE = "chhmc_adapt.npz"
 
@@ -392,14 +506,18 @@ class HMCSampler(object):
     def sample(self, pool, nsamp, samp_steps=0, samp_eps=0, Madapt=1000, outdir="./", progress=False, overwrite=False,
                ntimes=10, tautol=0.01, method="emcee", incremental=True, meanshift=0.1, stdshift=0.1, nk=2, ncheck=100,
                burnin=100, profile=None, adapt_mass=False, adapt_traj=False, max_steps=64, criterion="tau", rhat_tol=1.01,
-               ess_min=400, rhat_discard=0.0, rhat_rank=False, ess_rank=False):
+               ess_min=400, rhat_discard=0.0, rhat_rank=False, ess_rank=False, energy_stats=False, max_dH=1000.0, bfmi_min=None,
+               max_divergent=None):
         hmc = method == "hmc"
         adapt_mass = self._check(self.lnp, method, samp_eps, Madapt, adapt_mass, adapt_traj, max_steps, criterion, rhat_tol, ess_min, rhat_discard, rhat_rank,
-                                 ess_rank)
+                                 ess_rank, energy_stats, max_dH, bfmi_min, max_divergent, world=ldist.world_size(self.group))
         filename = os.path.join(outdir, "chhmc.h5" if hmc else "chemcee_256.h5")       # sampler.py:466-469
         prof, rk, store, x0, resume, done, dchain = _open_run(self, "sampler.HMCSampler.sample", filename, overwrite, profile)
         if not rk.active:
             return store
+        efile = os.path.join(outdir, _EnergyLog.FILE)
+        if hmc and rk.rank == 0 and overwrite and os.path.exists(efile):
+            os.remove(efile)
         # the warm-up's result next to the chain file (single-rank runs; written and read with adapt_mass or adapt_traj only,
         # removed with the chain)
         sidecar = os.path.join(outdir, self.ADAPT_FILE) if hmc and rk.real_world == 1 else None
@@ -426,25 +544,43 @@ class HMCSampler(object):
         if hmc:
             ens = self.sampler = self._hmc_chains(rk, x0, samp_steps, samp_eps, Madapt, prof, adapt_mass=adapt_mass,
                                                   sidecar=sidecar if adapt_mass or adapt_traj else None, resume=resume,
-                                                  adapt_traj=bool(adapt_traj), max_steps=max_steps, stored=done)
+                                                  adapt_traj=bool(adapt_traj), max_steps=max_steps, stored=done,
+                                                  max_dH=max_dH if energy_stats else None)
         else:
             ens.set_state(rk.mine(x0))
         rule = _RhatRule(dchain, self, rhat_tol, ess_min, rhat_discard, rhat_rank, ess_rank) if criterion == "rhat" else \
             _TauRule(dchain, ntimes, tautol, ncheck, nk, meanshift, stdshift)
+        elog = _EnergyLog(self, ens, efile, bfmi_min, max_divergent, resume) if energy_stats else None
         self.diagnostics = None
         with _lib.stage("run_mcmc.blocks"):
-            done = _run_blocks(ens, rk, store, dchain, done, nsamp, ncheck, incremental, rule, prof)
+            done = _run_blocks(ens, rk, store, dchain, done, nsamp, ncheck, incremental, rule, prof, elog)
+        if elog is not None:
+            elog.save()
         self.sampler = None
         return _close_run(prof, rk, store, dchain, done)
 
     @staticmethod
     def _check(lnp, method, samp_eps, Madapt, adapt_mass, adapt_traj, max_steps, criterion, rhat_tol, ess_min, rhat_discard, rhat_rank,
-               ess_rank=False):
-        """``sample``'s arguments that exclude each other, before anything is built; returns ``BatchedHMC.adapt_mass_mode(adapt_mass)``."""
+               ess_rank=False, energy_stats=False, max_dH=1000.0, bfmi_min=None, max_divergent=None, world=1):
+        """``sample``'s arguments that exclude each other, before anything is built; returns ``BatchedHMC.adapt_mass_mode(adapt_mass)``.
+        ``world``: the ranks of the run."""
         if method not in ("emcee", "hmc"):
             # sampler.py's "nuts" branch is unreachable in the reference (SURVEY section 8 a18) and not built here
             raise NotImplementedError(method)
         hmc = method == "hmc"
+        if energy_stats:
+            if not hmc:
+                raise ValueError("energy_stats with method = %r: divergences and E-BFMI are diagnostics of Hamiltonian "
+                                 "trajectories; they belong to method=\"hmc\"" % (method,))
+            if not float(max_dH) > 0.0:
+                raise ValueError("energy_stats: max_dH = %r is not positive" % (max_dH,))
+            if world > 1:
+                raise ValueError("energy_stats=True in a multi-rank run (%d ranks): the energy diagnostics are single-rank only, the "
+                                 "accumulators of the ranks are not gathered" % (world,))
+        for name, v in (("bfmi_min", bfmi_min), ("max_divergent", max_divergent)):
+            if v is not None and not (energy_stats and criterion == "rhat"):
+                raise ValueError("%s = %r without %s: it gates the checks of criterion=\"rhat\" on the diagnostics of "
+                                 "energy_stats=True" % (name, v, "energy_stats=True" if not energy_stats else "criterion=\"rhat\""))
         if criterion not in ("tau", "rhat"):
             raise ValueError("criterion = %r: \"tau\" (the reference's rule) or \"rhat\" (split-R-hat and multi-chain ESS)" % (criterion,))
         if criterion == "rhat":
@@ -478,7 +614,7 @@ class HMCSampler(object):
         return adapt_mass
 
     def _hmc_chains(self, rk, x0, samp_steps, samp_eps, Madapt, prof, adapt_mass=False, sidecar=None, resume=False,
-                    adapt_traj=False, max_steps=64, stored=0):
+                    adapt_traj=False, max_steps=64, stored=0, max_dH=None):
         """The chains of ``method="hmc"`` (sampler.py:491-493: ``HamiltonianMove(dlnp, samp_steps, samp_eps, m)``), one per
         walker of this rank, ready for ``_run_blocks``.  ``m`` is the move's ``cov``: momenta ~ N(0, m), drift p / m
         (``_hmc_matrix``, sampler.py:311-320; tests/golden/hmc_move.npz).  ``samp_eps`` > 0: that step size for every chain,
@@ -491,7 +627,8 @@ class HMCSampler(object):
         ``BatchedHMC.adapt_traj`` behind that warm-up -- one step size for all chains and a trajectory length; ``samp_steps``
         is then not used, the file also holds ``traj``, ``max_steps`` and ``iteration`` (the Philox step of the first stored
         transition) and is taken only with a finite positive ``traj``; such a resumed run goes on at Philox step
-        ``iteration + stored``, so that ``steps_for`` continues the sequence the first run began."""
+        ``iteration + stored``, so that ``steps_for`` continues the sequence the first run began.  ``max_dH``: the chains
+        count their energy diagnostics (``BatchedHMC.energy_stats``), emptied behind the warm-up."""
         if samp_eps is not None and samp_eps < 0:
             raise ValueError("samp_eps = %r: a step size is positive (0 or None: found and adapted per chain)" % (samp_eps,))
         adapt_mass = BatchedHMC.adapt_mass_mode(adapt_mass)
@@ -508,6 +645,8 @@ class HMCSampler(object):
         if not bool(torch.isfinite(ens.lnp).all()):
             raise ValueError("initial state has non-finite log-probability")
         ens.num_steps = int(samp_steps) if samp_steps else 5
+        if max_dH is not None:
+            ens.energy_stats(True, max_dH)
         if adapt_traj and samp_steps:
             print("samp_steps = %r is ignored: adapt_traj chooses the leapfrog steps of every transition" % (samp_steps,), flush=True)
         if samp_eps:
@@ -535,6 +674,7 @@ class HMCSampler(object):
             with prof.host("adapt"), _lib.stage("run_mcmc.hmc_adapt"):
                 ens.adapt(int(Madapt), adapt_mass=adapt_mass, adapt_traj=adapt_traj, max_steps=max_steps)
                 ens.naccept.zero_()
+                ens.energy_reset()
         e = ens.eps.cpu().numpy()
         self._keep_mass(ens, m)
         mm = self.mass.astype(np.float32)

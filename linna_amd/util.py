@@ -939,7 +939,8 @@ class NN_samplerv1(object):
 
     def _HMC_sample(self, log_prob, dlnp, ddlnp, ndim, nwalkers, init, pool, transform, samp_steps=5, samp_eps=None, Madapt=1000,
                     max_n=1000000, adapt_mass=False, adapt_traj=False, max_steps=64, criterion="tau", rhat_tol=1.01, ess_min=400,
-                    rhat_discard=0.0, rhat_rank=False, ess_rank=False):
+                    rhat_discard=0.0, rhat_rank=False, ess_rank=False, energy_stats=False, max_dH=1000.0, bfmi_min=None,
+                    max_divergent=None):
         """util.py:940-945 with the argument order its signature states (its caller passes ``transform`` twice, SURVEY §8
         a18).  ``samp_eps=None``: a step size per chain, found and adapted on the device (``sampler.HMCSampler.sample``) --
         the reference's 0.1 is in latent units and accepts nothing on a posterior much narrower than its prior.  The
@@ -949,14 +950,18 @@ class NN_samplerv1(object):
         ``max_steps`` leapfrog steps a transition); ``samp_steps`` is then not used.  ``criterion="rhat"`` with ``rhat_tol``,
         ``ess_min``, ``rhat_discard``: the between-chain stopping rule of ``sampler.HMCSampler.sample``; ``rhat_rank``: its
         confirmation with the rank-normalised, folded R-hat; ``ess_rank``: its confirmation with the rank-normalised bulk-ESS
-        and tail-ESS."""
+        and tail-ESS.  ``energy_stats`` with ``max_dH``, ``bfmi_min``, ``max_divergent``: the energy diagnostics of
+        ``sampler.HMCSampler.sample`` (divergent transitions and E-BFMI, ``chhmc_energy.npz``) and their gates on that rule."""
         from . import sampler
         x0 = init + 0.1 * np.random.randn(nwalkers, ndim)                 # util.py:942
         samp = sampler.HMCSampler(log_prob, dlnp, ddlnp, ndim, nwalkers, x0=x0, m=None, transform=transform)
         return samp.sample(pool, max_n, samp_steps, samp_eps or 0, Madapt, outdir=self.outdir, overwrite=True, ntimes=50,
                            method="hmc", incremental=True, progress=True, adapt_mass=adapt_mass, adapt_traj=adapt_traj,
                            max_steps=max_steps, criterion=criterion, rhat_tol=rhat_tol, ess_min=ess_min, rhat_discard=rhat_discard,
-                           **(dict(rhat_rank=True) if rhat_rank else {}), **(dict(ess_rank=True) if ess_rank else {}))
+                           **(dict(rhat_rank=True) if rhat_rank else {}), **(dict(ess_rank=True) if ess_rank else {}),
+                           **(dict(energy_stats=True, max_dH=max_dH) if energy_stats else {}),
+                           **({} if bfmi_min is None else dict(bfmi_min=bfmi_min)),
+                           **({} if max_divergent is None else dict(max_divergent=max_divergent)))
 
     def Zeus_sample(self, log_prob, ndim, nwalkers, init, pool, transform, ntimes=50, tautol=0.01, dlnp=None, ddlnp=None,
                     meanshift=0.1, stdshift=0.1, nk=1, max_n=1000000):
@@ -1187,7 +1192,7 @@ def read_chain_and_cut(chainname, nk, ntimes=20, walkercut=False, method="emcee"
 def run_mcmc(nnsampler, outdir, method, ndim, nwalkers, init, log_prob, dlnp=None, ddlnp=None, pool=None, transform=None,
              ntimes=50, tautol=0.01, meanshift=0.1, stdshift=0.1, nk=2, max_n=None, adapt_mass=False,
              adapt_traj=False, max_steps=64, criterion="tau", rhat_tol=1.01, ess_min=400, rhat_discard=0.0,
-             rhat_rank=False, ess_rank=False):
+             rhat_rank=False, ess_rank=False, energy_stats=False, max_dH=1000.0, bfmi_min=None, max_divergent=None):
     """util.py:1474-1504.  "hmc": per-walker HMC with step sizes adapted on the device (``_HMC_sample``; the reference's own
     branch cannot run); "nuts" is not built.  ``max_n`` (not in the reference): a cap on the iterations of
     the hmc run, 1000000 as there when None.  ``adapt_mass`` (hmc only, not in the reference): also adapt a diagonal mass
@@ -1200,7 +1205,18 @@ def run_mcmc(nnsampler, outdir, method, ndim, nwalkers, init, log_prob, dlnp=Non
     passes is confirmed with the rank-normalised, folded split-R-hat of Vehtari et al. 2021 (bulk and tail R-hat over all
     walkers, both below ``rhat_tol``), which also sees chains that agree in location but not in scale.  ``ess_rank`` (with
     ``criterion="rhat"`` only, else a ``ValueError``): a check that passes all of that is confirmed with that paper's
-    rank-normalised bulk-ESS and tail-ESS over all walkers, both at least ``ess_min``."""
+    rank-normalised bulk-ESS and tail-ESS over all walkers, both at least ``ess_min``.  ``energy_stats`` (hmc only, single-rank
+    runs, not in the reference; else a ``ValueError``): count the divergent transitions (proposal not finite, or energy error
+    above ``max_dH``) and every chain's E-BFMI, reported at every check and kept in ``chhmc_energy.npz``; ``bfmi_min`` and
+    ``max_divergent`` (with ``energy_stats`` and ``criterion="rhat"`` only, else a ``ValueError``; None: report only) gate that
+    rule on them."""
+    if energy_stats and method != "hmc":
+        raise ValueError("energy_stats with method = %r: divergences and E-BFMI belong to method=\"hmc\"" % (method,))
+    if energy_stats and not float(max_dH) > 0.0:
+        raise ValueError("energy_stats: max_dH = %r is not positive" % (max_dH,))
+    for name, v in (("bfmi_min", bfmi_min), ("max_divergent", max_divergent)):
+        if v is not None and not (energy_stats and criterion == "rhat"):
+            raise ValueError("%s = %r: it needs energy_stats=True and criterion=\"rhat\"" % (name, v))
     if adapt_traj and method != "hmc":
         raise ValueError("adapt_traj with method = %r: the trajectory length belongs to method=\"hmc\"" % (method,))
     if adapt_traj and int(max_steps) < 1:
@@ -1224,7 +1240,9 @@ def run_mcmc(nnsampler, outdir, method, ndim, nwalkers, init, log_prob, dlnp=Non
                                      **(dict(criterion="rhat", rhat_tol=rhat_tol, ess_min=ess_min, rhat_discard=rhat_discard)
                                         if criterion == "rhat" else {}),
                                      **(dict(rhat_rank=True) if rhat_rank else {}),
-                                     **(dict(ess_rank=True) if ess_rank else {}))
+                                     **(dict(ess_rank=True) if ess_rank else {}),
+                                     **(dict(energy_stats=True, max_dH=max_dH, bfmi_min=bfmi_min, max_divergent=max_divergent)
+                                        if energy_stats else {}))
     if method == "emcee":
         return nnsampler.emcee_sample(log_prob, ndim, nwalkers, init, pool, **kw)
     if method == "zeus":
