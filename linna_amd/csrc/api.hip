@@ -1,6 +1,7 @@
 // C-ABI entry points of liblinna_hip.so (declared in include/linna_hip.h) and the host-side
 // orchestration above the kernels: network forward/backward as chains of fused GEMMs, the
-// serving pipeline (Log_prob), the training loss.  No device allocation, no sync.
+// serving pipeline (Log_prob), the training loss, the ensemble moves.  No device allocation, no sync.  A subsystem with a
+// file of its own keeps its entries there: hmc.hip, autocorr.hip, chain_rank.hip, comm.hip.
 #include "common.h"
 
 #include <stdarg.h>
@@ -39,15 +40,7 @@ int check_hip(hipError_t e, const char* what) {
 }
 
 static inline int ld4(int w) { return (w + 3) & ~3; }
-static inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
-#define TRY(expr) do { int rc__ = (expr); if (rc__ != LINNA_OK) return rc__; } while (0)
-
-// a descriptor struct filled against another layout of include/linna_hip.h is refused, not read at wrong offsets
-#define CHECK_STRUCT(ptr, T, who) do { if ((ptr)->struct_size != sizeof(T)) { \
-        set_error("%s: " #T "::struct_size is %u, this library's sizeof is %zu -- set it to sizeof(" #T ") of the header you built against; " \
-                  "a mismatch means that header is not this library's (LINNA_ABI_VERSION %d)", who, (unsigned)(ptr)->struct_size, sizeof(T), LINNA_ABI_VERSION); \
-        return LINNA_ERR_INVALID; } } while (0)
 // every element of a caller's layer array (the first entry's size is the array's stride: it is checked before walking on)
 static int check_layers(const linna_layer_t* layers, int n, const char* who) {
     for (int i = 0; i < n; ++i) CHECK_STRUCT(layers + i, linna_layer_t, who);
@@ -1497,124 +1490,6 @@ int linna_stretch_run(linna_logprob_t* lp, float* coords, int ldc, int ndim, flo
     return LINNA_OK;
 } LINNA_CATCH_INT
 
-// ---- convergence statistics of a chain (autocorr.hip)
-static bool ac_shape_ok(int ndim, int nwp) { return ndim >= 1 && nwp >= 64 && (nwp & 63) == 0; }
-int linna_chain_append_t(linna_ctx_t*, const float* block, int ldb, int nsteps, int nw, int ndim, int wstride, float* CT, int nwp,
-                         int64_t row0, void* stream) try {
-    if (!block || !CT || nsteps < 1 || nw < 1 || wstride < 1 || ldb < ndim || row0 < 0 || !ac_shape_ok(ndim, nwp) ||
-        nw > nwp || nsteps > 65535 || (size_t)64 * (ndim + 1) * sizeof(float) > 64 * 1024) {
-        set_error("chain_append_t: bad arguments"); return LINNA_ERR_INVALID;
-    }
-    return launch_chain_append_t(block, ldb, nsteps, nw, ndim, wstride, CT, nwp, row0, S(stream));
-} LINNA_CATCH_INT
-static bool ac_cover_ok(int nwp, int nwc, int nlive) { return nwc >= 64 && (nwc & 63) == 0 && nwc <= nwp && nlive >= 1 && nlive <= nwc; }
-int linna_acorr_update(linna_ctx_t*, const float* CT, int ndim, int nwp, int nwc, int64_t a0, int64_t a1, int64_t lo, int64_t hi, int k0,
-                       int k1, double* Ssum, double* Tsum, int remove, void* stream) try {
-    if (!CT || !Ssum || !ac_shape_ok(ndim, nwp) || !ac_cover_ok(nwp, nwc, 1) || k0 < 0 || k1 < k0 || (k0 & 31) || (k1 & 31) || lo < 0 ||
-        hi < lo || a0 < lo || a1 > hi || a1 < a0 || (k1 - k0) / 32 > 4 * 65535 || hi > 0x7fffff00) {
-        set_error("acorr_update: bad arguments (lag ranges are multiples of 32, anchors inside [lo, hi))"); return LINNA_ERR_INVALID;
-    }
-    return launch_acorr_update(CT, ndim, nwp, nwc, a0, a1, lo, hi, k0, k1, Ssum, Tsum, remove, S(stream));
-} LINNA_CATCH_INT
-size_t linna_acorr_scratch_bytes(int ndim, int nwc, int kuse) try {
-    if (ndim < 1 || nwc < 64 || (nwc & 63) || kuse < 0) return 0;
-    return acorr_scratch_doubles(ndim * nwc, kuse, ndim) * sizeof(double);
-} LINNA_CATCH_SIZE
-int linna_acorr_tau(linna_ctx_t*, const float* CT, int ndim, int nwp, int nwc, int nlive, int64_t lo, int64_t hi, int kuse,
-                    const double* Ssum, const double* Tsum, double c, double* scratch, double* out, void* stream) try {
-    if (!CT || !Ssum || !Tsum || !scratch || !out || !ac_shape_ok(ndim, nwp) || !ac_cover_ok(nwp, nwc, nlive) || lo < 0 || hi <= lo ||
-        kuse < 0 || (int64_t)kuse > hi - lo - 1 || kuse / 32 + 1 > 65535 || !(c > 0.0) || hi > 0x7fffff00) {
-        set_error("acorr_tau: bad arguments (0 <= kuse <= hi - lo - 1)"); return LINNA_ERR_INVALID;
-    }
-    return launch_acorr_tau(CT, ndim, nwp, nwc, nlive, lo, hi, kuse, Ssum, Tsum, c, scratch, out, S(stream));
-} LINNA_CATCH_INT
-int linna_chain_meanstd(linna_ctx_t*, const float* CT, int ndim, int nwp, int nws, int64_t t0, int64_t tm, int64_t t1, double* out,
-                        void* stream) try {
-    if (!CT || !out || !ac_shape_ok(ndim, nwp) || nws < 1 || nws > nwp || t0 < 0 || tm < t0 || t1 < tm || ndim > 65535) {
-        set_error("chain_meanstd: bad arguments"); return LINNA_ERR_INVALID;
-    }
-    return launch_chain_meanstd(CT, ndim, nwp, nws, t0, tm, t1, out, S(stream));
-} LINNA_CATCH_INT
-int linna_chain_block_moments(linna_ctx_t*, const float* CT, int ndim, int nwp, int64_t b0, int64_t b1, double* M, void* stream) try {
-    if (!CT || !M || !ac_shape_ok(ndim, nwp) || b0 < 0 || b1 < b0 || b1 > 0x7fffff00 / LINNA_RHAT_BLOCK ||
-        (int64_t)ndim * (nwp / 64) > 0x7fffffff) {
-        set_error("chain_block_moments: bad arguments"); return LINNA_ERR_INVALID;
-    }
-    return launch_chain_block_moments(CT, ndim, nwp, b0, b1, M, S(stream));
-} LINNA_CATCH_INT
-int linna_chain_rhat(linna_ctx_t*, const float* CT, int ndim, int nwp, int nw, int64_t lo, int64_t hi, const double* M, int64_t nblocks,
-                     double* out, void* stream) try {
-    if (!CT || !out || !ac_shape_ok(ndim, nwp) || nw < 1 || nw > nwp || lo < 0 || hi < lo || (hi - lo) / 2 < 2 || nblocks < 0 ||
-        hi > 0x7fffff00) {
-        set_error("chain_rhat: bad arguments (the window [lo, hi) needs two halves of at least 2 rows)"); return LINNA_ERR_INVALID;
-    }
-    return launch_chain_rhat(CT, ndim, nwp, nw, lo, hi, M, nblocks, out, S(stream));
-} LINNA_CATCH_INT
-size_t linna_acorr_ess_scratch_bytes(int ndim, int nwc, int kuse) try {
-    if (ndim < 1 || nwc < 64 || (nwc & 63) || kuse < 0) return 0;
-    return acorr_ess_scratch_doubles(ndim * nwc, kuse, ndim) * sizeof(double);
-} LINNA_CATCH_SIZE
-int linna_acorr_ess(linna_ctx_t*, const float* CT, int ndim, int nwp, int nwc, int nlive, int64_t lo, int64_t hi, int kuse,
-                    const double* Ssum, const double* Tsum, double* scratch, double* out, void* stream) try {
-    if (!CT || !Ssum || !Tsum || !scratch || !out || !ac_shape_ok(ndim, nwp) || !ac_cover_ok(nwp, nwc, nlive) || lo < 0 || hi <= lo ||
-        kuse < 0 || (int64_t)kuse > hi - lo - 1 || kuse / 32 + 1 > 65535 || hi > 0x7fffff00) {
-        set_error("acorr_ess: bad arguments (0 <= kuse <= hi - lo - 1)"); return LINNA_ERR_INVALID;
-    }
-    return launch_acorr_ess(CT, ndim, nwp, nwc, nlive, lo, hi, kuse, Ssum, Tsum, scratch, out, S(stream));
-} LINNA_CATCH_INT
-
-size_t linna_chain_rank_rhat_scratch_bytes(int ndim, int nw, int64_t rows, int npar) try {
-    if (ndim < 1 || nw < 1 || rows < 2 || (rows & 1) || npar < 1 || rows > 0x7fffffff / nw) return 0;
-    return chain_rank_rhat_scratch_bytes(nw, rows, npar < ndim ? npar : ndim);
-} LINNA_CATCH_SIZE
-int linna_chain_rank_rhat(linna_ctx_t*, const float* CT, int ndim, int nwp, int nw, int64_t lo, int64_t hi, void* scratch,
-                          size_t scratch_bytes, uint32_t* rank2_out, double* out, void* stream) try {
-    if (!CT || !out || !scratch || ((uintptr_t)scratch & 7) || !ac_shape_ok(ndim, nwp) || nw < 1 || nw > nwp || lo < 0 || hi < lo ||
-        (hi - lo) / 2 < 2 || hi > 0x7fffff00) {
-        set_error("chain_rank_rhat: bad arguments (the window [lo, hi) needs two halves of at least 2 rows; scratch 8-byte aligned)");
-        return LINNA_ERR_INVALID;
-    }
-    const int64_t rows = (hi - lo) / 2 * 2;
-    if (rows > 0x7fffffff / nw) {
-        set_error("chain_rank_rhat: %lld pooled values per parameter; the sort's 32-bit element indices hold fewer than 2^31",
-                  (long long)rows * nw);
-        return LINNA_ERR_UNSUPPORTED;
-    }
-    if (scratch_bytes < chain_rank_rhat_scratch_bytes(nw, rows, 1)) {
-        set_error("chain_rank_rhat: scratch of %zu bytes, one parameter needs %zu (linna_chain_rank_rhat_scratch_bytes)", scratch_bytes,
-                  chain_rank_rhat_scratch_bytes(nw, rows, 1));
-        return LINNA_ERR_INVALID;
-    }
-    return launch_chain_rank_rhat(CT, ndim, nwp, nw, lo, hi, scratch, scratch_bytes, rank2_out, out, S(stream));
-} LINNA_CATCH_INT
-size_t linna_chain_rank_ess_scratch_bytes(int ndim, int nw, int64_t rows, int kuse, int npar) try {
-    if (ndim < 1 || nw < 1 || rows < 4 || (rows & 1) || npar < 1 || rows > 0x7fffffff / nw || kuse < 1 || (int64_t)kuse > rows / 2 - 1 ||
-        kuse / 32 + 1 > 65535 || nw > (1 << 24))
-        return 0;
-    return chain_rank_ess_scratch_bytes(nw, rows, kuse, npar < ndim ? npar : ndim);
-} LINNA_CATCH_SIZE
-int linna_chain_rank_ess(linna_ctx_t*, const float* CT, int ndim, int nwp, int nw, int64_t lo, int64_t hi, int kuse, void* scratch,
-                         size_t scratch_bytes, double* out, void* stream) try {
-    if (!CT || !out || !scratch || ((uintptr_t)scratch & 7) || !ac_shape_ok(ndim, nwp) || nw < 1 || nw > nwp || lo < 0 || hi < lo ||
-        (hi - lo) / 2 < 2 || hi > 0x7fffff00 || kuse < 1 || (int64_t)kuse > (hi - lo) / 2 - 1 || kuse / 32 + 1 > 65535 || nw > (1 << 24)) {
-        set_error("chain_rank_ess: bad arguments (the window [lo, hi) needs two halves of n >= 2 rows; 1 <= kuse <= n - 1; scratch "
-                  "8-byte aligned)");
-        return LINNA_ERR_INVALID;
-    }
-    const int64_t rows = (hi - lo) / 2 * 2;
-    if (rows > 0x7fffffff / nw) {
-        set_error("chain_rank_ess: %lld pooled values per parameter; the sort's 32-bit element indices hold fewer than 2^31",
-                  (long long)rows * nw);
-        return LINNA_ERR_UNSUPPORTED;
-    }
-    if (scratch_bytes < chain_rank_ess_scratch_bytes(nw, rows, kuse, 1)) {
-        set_error("chain_rank_ess: scratch of %zu bytes, one parameter needs %zu (linna_chain_rank_ess_scratch_bytes)", scratch_bytes,
-                  chain_rank_ess_scratch_bytes(nw, rows, kuse, 1));
-        return LINNA_ERR_INVALID;
-    }
-    return launch_chain_rank_ess(CT, ndim, nwp, nw, lo, hi, kuse, scratch, scratch_bytes, out, S(stream));
-} LINNA_CATCH_INT
-
 }  // extern "C"
 
 // the gradient's destination and, with `leap`, the leapfrog's kick and drift behind it (none: an NsLeap of nulls)
@@ -1635,10 +1510,12 @@ static int lp_grad_refused(const LpRouted& rt) {
     set_error("logprob_grad: %s", rt.why);
     return rt.err;
 }
-static int logprob_grad_ready(const linna_logprob_t* lp) { return lp_grad_refused(lp_grad_route(lp, 1)); }
+// ---- what hmc.hip's whole-transition driver sees of this file (common.h)
+int linna::logprob_nin(const linna_logprob_t* lp) { return lp->d.nin; }
+int linna::logprob_grad_ready(const linna_logprob_t* lp) { return lp_grad_refused(lp_grad_route(lp, 1)); }
 // lnP and its gradient at Z; `leap`: the leapfrog's kick and drift -- in the finish of the one-launch forms, as a launch of
 // its own behind the others
-static int logprob_grad_impl(linna_logprob_t* lp, const float* Z, int ldz, int B, void* ws, float* lnP, float* G, int ldg,
+int linna::logprob_grad_impl(linna_logprob_t* lp, const float* Z, int ldz, int B, void* ws, float* lnP, float* G, int ldg,
                              const NsLeap* leap, void* stream) {
     if (!lp || !Z || !ws || !lnP || !G || B < 1) { set_error("logprob_grad: bad arguments"); return LINNA_ERR_INVALID; }
     const LpRouted rt = lp_grad_route(lp, B);
@@ -1714,146 +1591,6 @@ int linna_logprob_grad_leapfrog_eps(linna_logprob_t* lp, float* Q, int ldq, int 
     if (!P || !mass || !Q || !EPS) { set_error("logprob_grad_leapfrog_eps: bad arguments"); return LINNA_ERR_INVALID; }
     const NsLeap leap{P, ldp, Q, mass, mul_kick, mul_drift, EPS};
     return logprob_grad_impl(lp, Q, ldq, B, ws, lnP, G, ldg, &leap, stream);
-} LINNA_CATCH_INT
-
-// ---- whole HMC transitions per call (linna_hip.h)
-static bool hmc_state_ok(const linna_hmc_state_t* st) {
-    return st && st->B >= 1 && st->ld >= 1 && st->X && st->lnp && st->G && st->P && st->Q && st->lnp_new && st->Gnew && st->H0 &&
-           st->mass && st->step_dev;
-}
-// what the entries that run whole transitions check of their state before they enqueue anything
-static int hmc_entry_check(const linna_logprob_t* lp, const linna_hmc_state_t* st, const char* who) {
-    CHECK_STRUCT(st, linna_hmc_state_t, who);
-    if (!hmc_state_ok(st)) { set_error("%s: incomplete state", who); return LINNA_ERR_INVALID; }
-    if (st->ld < lp->d.nin) { set_error("%s: ld %d < %d parameters", who, st->ld, lp->d.nin); return LINNA_ERR_INVALID; }
-    return logprob_grad_ready(lp);
-}
-// a dense mass's factor {C, C^T} (linna_hip.h); C == nullptr: the diagonal route
-struct HmcDense { const float* C; int ldc; };
-static int hmc_dense_check(const linna_logprob_t* lp, const HmcDense& dn, const char* who) {
-    if (lp->d.nin > LINNA_HMC_DENSE_MAX_NDIM) {
-        set_error("%s: a dense mass holds at most %d parameters, not %d", who, LINNA_HMC_DENSE_MAX_NDIM, lp->d.nin); return LINNA_ERR_UNSUPPORTED;
-    }
-    if (dn.ldc < lp->d.nin) { set_error("%s: ldc %d < %d parameters", who, dn.ldc, lp->d.nin); return LINNA_ERR_INVALID; }
-    return LINNA_OK;
-}
-// one trajectory from st->X with the momenta hmc_start draws (P0 == nullptr) or is given: start, num_steps gradient launches.
-// dn.C: st->P is the whitened momentum (st->mass an array of ones), the gradient launch runs without a leapfrog in its finish
-// and the dense kick and drift follow it as a launch of their own
-static int hmc_trajectory(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, const float* P0, const float* EPS, int step_off,
-                          int num_steps, void* stream, const HmcDense& dn = HmcDense{nullptr, 0}) {
-    const int B = st->B, nd = lp->d.nin, ld = st->ld;
-    if (dn.C) {
-        TRY(launch_hmc_start(B, nd, st->mass, st->seed, st->step_dev, st->lnp, P0, ld, nullptr, 0, 0.f, 0.f, nullptr, 0, st->P, ld,
-                             nullptr, 0, st->H0, S(stream), nullptr, step_off));
-        TRY(launch_hmc_kick_drift_dense(B, nd, dn.C, dn.ldc, EPS, 0.5f, 1.f, st->G, ld, st->P, ld, st->X, ld, st->Q, ld, S(stream)));
-        for (int i = 0; i < num_steps; ++i) {
-            const bool last = i == num_steps - 1;
-            TRY(logprob_grad_impl(lp, st->Q, ld, B, ws, st->lnp_new, st->Gnew, ld, nullptr, stream));
-            TRY(launch_hmc_kick_drift_dense(B, nd, dn.C, dn.ldc, EPS, last ? 0.5f : 1.f, last ? 0.f : 1.f, st->Gnew, ld, st->P, ld,
-                                            nullptr, 0, st->Q, ld, S(stream)));
-        }
-        return LINNA_OK;
-    }
-    TRY(launch_hmc_start(B, nd, st->mass, st->seed, st->step_dev, st->lnp, P0, ld, st->G, ld, 0.5f, 1.f, st->X, ld, st->P, ld, st->Q, ld,
-                         st->H0, S(stream), EPS, step_off));
-    for (int i = 0; i < num_steps; ++i) {
-        const bool last = i == num_steps - 1;                                      // a half kick behind the last step, no drift
-        const NsLeap leap{st->P, ld, st->Q, st->mass, last ? 0.5f : 1.f, last ? 0.f : 1.f, EPS};
-        TRY(logprob_grad_impl(lp, st->Q, ld, B, ws, st->lnp_new, st->Gnew, ld, &leap, stream));
-    }
-    return LINNA_OK;
-}
-
-// what the entries that take the energy diagnostics check of them (linna_hip.h): estate with ndiv, and then max_dH > 0
-static int hmc_energy_check(const HmcEnergy& en, const char* who) {
-    if ((en.estate != nullptr) != (en.ndiv != nullptr)) { set_error("%s: estate and ndiv come together", who); return LINNA_ERR_INVALID; }
-    if (en.estate && !(en.max_dH > 0.f)) { set_error("%s: max_dH %g is not positive", who, (double)en.max_dH); return LINNA_ERR_INVALID; }
-    return LINNA_OK;
-}
-// linna_hmc_run, linna_hmc_run_moments, linna_hmc_run_dense and linna_hmc_run_energy: mom != nullptr adds the moments launch on
-// st->X behind every Metropolis launch (under a dense mass the co-moments launch); en: the energy diagnostics in that launch,
-// its energy / dH rows [ntrans][B]
-static int hmc_run_impl(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, float* EPS, float* EPSBAR, float* HBAR, const float* MU,
-                        int* M, int Madapt, float delta, int step_offset, int num_steps, int ntrans, int* naccept, float* alpha,
-                        float* chain, float* logps, double* mom, void* stream, const HmcDense& dn = HmcDense{nullptr, 0},
-                        const HmcEnergy& en = HmcEnergy{}) {
-    if (!lp || !st || !ws || !EPS || num_steps < 1 || ntrans < 1 || Madapt < 0 || (chain != nullptr) != (logps != nullptr)) {
-        set_error("hmc_run: bad arguments"); return LINNA_ERR_INVALID;
-    }
-    if (Madapt > 0 && (!EPSBAR || !HBAR || !MU || !M)) { set_error("hmc_run: Madapt > 0 needs the adaptation state"); return LINNA_ERR_INVALID; }
-    TRY(hmc_energy_check(en, "hmc_run_energy"));
-    TRY(hmc_entry_check(lp, st, "hmc_run"));
-    if (dn.C) TRY(hmc_dense_check(lp, dn, "hmc_run_dense"));
-    const int B = st->B, nd = lp->d.nin, ld = st->ld;
-    const HmcAdapt ad{EPS, EPSBAR, HBAR, MU, M, Madapt, delta};
-    for (int i = 0; i < ntrans; ++i) {
-        TRY(hmc_trajectory(lp, st, ws, nullptr, EPS, step_offset + i, num_steps, stream, dn));
-        const HmcEnergy row{en.estate, en.ndiv, en.max_dH, en.energy ? en.energy + (size_t)i * B : nullptr,
-                            en.dH ? en.dH + (size_t)i * B : nullptr};
-        TRY(launch_hmc_accept(B, nd, st->mass, st->seed, st->step_dev, step_offset + i, st->H0, st->P, ld, st->Q, ld, st->lnp_new,
-                              st->Gnew, ld, nullptr, st->X, ld, st->lnp, st->G, naccept, alpha, ad,
-                              chain ? chain + (size_t)i * B * nd : nullptr, logps ? logps + (size_t)i * B : nullptr, row, S(stream)));
-        if (mom) TRY(dn.C ? launch_hmc_comoments(B, nd, st->X, ld, mom, S(stream)) : launch_hmc_moments(B, nd, st->X, ld, mom, S(stream)));
-    }
-    return LINNA_OK;
-}
-
-int linna_hmc_run(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, float* EPS, float* EPSBAR, float* HBAR, const float* MU,
-                  int* M, int Madapt, float delta, int step_offset, int num_steps, int ntrans, int* naccept, float* alpha,
-                  float* chain, float* logps, void* stream) try {
-    return hmc_run_impl(lp, st, ws, EPS, EPSBAR, HBAR, MU, M, Madapt, delta, step_offset, num_steps, ntrans, naccept, alpha, chain,
-                        logps, nullptr, stream);
-} LINNA_CATCH_INT
-
-int linna_hmc_run_moments(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, float* EPS, float* EPSBAR, float* HBAR,
-                          const float* MU, int* M, int Madapt, float delta, int step_offset, int num_steps, int ntrans,
-                          int* naccept, float* alpha, float* chain, float* logps, double* mom, void* stream) try {
-    return hmc_run_impl(lp, st, ws, EPS, EPSBAR, HBAR, MU, M, Madapt, delta, step_offset, num_steps, ntrans, naccept, alpha, chain,
-                        logps, mom, stream);
-} LINNA_CATCH_INT
-
-static int hmc_find_epsilon_impl(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, float* R0, float* EPS, int* state, int* nactive,
-                                 int step_offset, int max_rounds, void* stream, const HmcDense& dn) {
-    if (!lp || !st || !ws || !R0 || !EPS || !state || !nactive || max_rounds < 1) { set_error("hmc_find_epsilon: bad arguments"); return LINNA_ERR_INVALID; }
-    TRY(hmc_entry_check(lp, st, "hmc_find_epsilon"));
-    if (dn.C) TRY(hmc_dense_check(lp, dn, "hmc_find_epsilon_dense"));
-    const int B = st->B, nd = lp->d.nin, ld = st->ld;
-    TRY(check_hip(hipMemsetAsync(nactive, 0, sizeof(int), S(stream)), "hipMemsetAsync"));
-    TRY(launch_hmc_find_eps_init(B, nd, st->seed, st->step_dev, step_offset, R0, ld, EPS, state, S(stream)));
-    for (int r = 0; r < max_rounds; ++r) {
-        TRY(hmc_trajectory(lp, st, ws, R0, EPS, step_offset, 1, stream, dn));
-        TRY(launch_hmc_find_eps(B, nd, st->mass, st->H0, st->P, ld, st->lnp_new, st->Gnew, ld, EPS, state,
-                                r + 1 == max_rounds ? nactive : nullptr, S(stream)));
-    }
-    return LINNA_OK;
-}
-
-int linna_hmc_find_epsilon(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, float* R0, float* EPS, int* state, int* nactive,
-                           int step_offset, int max_rounds, void* stream) try {
-    return hmc_find_epsilon_impl(lp, st, ws, R0, EPS, state, nactive, step_offset, max_rounds, stream, HmcDense{nullptr, 0});
-} LINNA_CATCH_INT
-
-int linna_hmc_run_dense(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, const float* Cm, int ldc, float* EPS, float* EPSBAR,
-                        float* HBAR, const float* MU, int* M, int Madapt, float delta, int step_offset, int num_steps, int ntrans,
-                        int* naccept, float* alpha, float* chain, float* logps, double* mom, void* stream) try {
-    if (!Cm) { set_error("hmc_run_dense: no factor"); return LINNA_ERR_INVALID; }
-    return hmc_run_impl(lp, st, ws, EPS, EPSBAR, HBAR, MU, M, Madapt, delta, step_offset, num_steps, ntrans, naccept, alpha, chain,
-                        logps, mom, stream, HmcDense{Cm, ldc});
-} LINNA_CATCH_INT
-
-int linna_hmc_run_energy(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, const float* Cm, int ldc, float* EPS, float* EPSBAR,
-                         float* HBAR, const float* MU, int* M, int Madapt, float delta, int step_offset, int num_steps, int ntrans,
-                         int* naccept, float* alpha, float* chain, float* logps, double* mom, double* estate, int* ndiv, float max_dH,
-                         float* energy, float* dH, void* stream) try {
-    return hmc_run_impl(lp, st, ws, EPS, EPSBAR, HBAR, MU, M, Madapt, delta, step_offset, num_steps, ntrans, naccept, alpha, chain,
-                        logps, mom, stream, HmcDense{Cm, Cm ? ldc : 0}, HmcEnergy{estate, ndiv, max_dH, energy, dH});
-} LINNA_CATCH_INT
-
-int linna_hmc_find_epsilon_dense(linna_logprob_t* lp, const linna_hmc_state_t* st, void* ws, const float* Cm, int ldc, float* R0,
-                                 float* EPS, int* state, int* nactive, int step_offset, int max_rounds, void* stream) try {
-    if (!Cm) { set_error("hmc_find_epsilon_dense: no factor"); return LINNA_ERR_INVALID; }
-    return hmc_find_epsilon_impl(lp, st, ws, R0, EPS, state, nactive, step_offset, max_rounds, stream, HmcDense{Cm, ldc});
 } LINNA_CATCH_INT
 
 // ------------------------------------------------------------------ training
@@ -2054,129 +1791,6 @@ int linna_stretch_accept(linna_ctx_t*, float* coords, int ldc, int ndim, float* 
                          const float* Q, int ldq, const float* logp_new, const float* factors, uint64_t seed,
                          const int* step_dev, int stream_id, int* naccept, void* stream) try {
     return launch_stretch_accept(coords, ldc, ndim, logp, S_idx, ns, Q, ldq, logp_new, factors, seed, step_dev, stream_id, naccept, S(stream));
-} LINNA_CATCH_INT
-int linna_hmc_init(linna_ctx_t*, int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, const float* lnp,
-                   const float* P0, int ldp0, float* P, int ldp, float* H0, void* stream) try {
-    return launch_hmc_start(B, ndim, mass, seed, step_dev, lnp, P0, ldp0, nullptr, 0, 0.f, 0.f, nullptr, 0, P, ldp, nullptr, 0, H0, S(stream));
-} LINNA_CATCH_INT
-int linna_hmc_start(linna_ctx_t*, int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, const float* lnp,
-                    const float* P0, int ldp0, const float* G, int ldg, float eps_kick, float eps_drift, const float* X, int ldx,
-                    float* P, int ldp, float* Q, int ldq, float* H0, void* stream) try {
-    if (B < 1 || ndim < 1 || !mass || !step_dev || !lnp || !G || !X || !P || !Q || !H0) { set_error("hmc_start: bad arguments"); return LINNA_ERR_INVALID; }
-    return launch_hmc_start(B, ndim, mass, seed, step_dev, lnp, P0, ldp0, G, ldg, eps_kick, eps_drift, X, ldx, P, ldp, Q, ldq, H0, S(stream));
-} LINNA_CATCH_INT
-int linna_hmc_kick_drift(linna_ctx_t*, int B, int ndim, const float* mass, float ek, float ed, const float* G, int ldg,
-                         float* P, int ldp, float* Q, int ldq, void* stream) try {
-    return launch_hmc_kick_drift(B, ndim, mass, ek, ed, G, ldg, P, ldp, Q, ldq, S(stream));
-} LINNA_CATCH_INT
-int linna_hmc_moments(linna_ctx_t*, int B, int ndim, const float* X, int ldx, double* mom, void* stream) try {
-    if (B < 1 || ndim < 1 || !X || ldx < ndim || !mom) { set_error("hmc_moments: bad arguments"); return LINNA_ERR_INVALID; }
-    return launch_hmc_moments(B, ndim, X, ldx, mom, S(stream));
-} LINNA_CATCH_INT
-int linna_hmc_mass_from_moments(linna_ctx_t*, int ndim, double* mom, float* mass, int reset, void* stream) try {
-    if (ndim < 1 || !mom || !mass) { set_error("hmc_mass_from_moments: bad arguments"); return LINNA_ERR_INVALID; }
-    return launch_hmc_mass_from_moments(ndim, mom, mass, reset, S(stream));
-} LINNA_CATCH_INT
-static int hmc_dense_ndim(int ndim, const char* who) {
-    if (ndim > LINNA_HMC_DENSE_MAX_NDIM) {
-        set_error("%s: a dense mass holds at most %d parameters, not %d", who, LINNA_HMC_DENSE_MAX_NDIM, ndim); return LINNA_ERR_UNSUPPORTED;
-    }
-    return LINNA_OK;
-}
-size_t linna_hmc_comoments_doubles(int ndim) try {
-    if (ndim < 1 || ndim > LINNA_HMC_DENSE_MAX_NDIM) return 0;
-    return 1 + (size_t)ndim + LINNA_HMC_COMOMENT_SLOTS * ((size_t)ndim + (size_t)ndim * ndim);
-} LINNA_CATCH_SIZE
-int linna_hmc_comoments(linna_ctx_t*, int B, int ndim, const float* X, int ldx, double* mom, void* stream) try {
-    if (B < 1 || ndim < 1 || !X || ldx < ndim || !mom) { set_error("hmc_comoments: bad arguments"); return LINNA_ERR_INVALID; }
-    TRY(hmc_dense_ndim(ndim, "hmc_comoments"));
-    return launch_hmc_comoments(B, ndim, X, ldx, mom, S(stream));
-} LINNA_CATCH_INT
-int linna_hmc_chol_from_comoments(linna_ctx_t*, int ndim, double* mom, float* Cm, int ldc, int* info, int reset, void* stream) try {
-    if (ndim < 1 || !mom || !Cm || ldc < ndim || !info) { set_error("hmc_chol_from_comoments: bad arguments"); return LINNA_ERR_INVALID; }
-    TRY(hmc_dense_ndim(ndim, "hmc_chol_from_comoments"));
-    return launch_hmc_chol_from_comoments(ndim, mom, Cm, ldc, info, reset, S(stream));
-} LINNA_CATCH_INT
-int linna_hmc_kick_drift_dense(linna_ctx_t*, int B, int ndim, const float* Cm, int ldc, const float* EPS, float mul_kick, float mul_drift,
-                               const float* G, int ldg, float* W, int ldw, const float* X, int ldx, float* Q, int ldq, void* stream) try {
-    if (B < 1 || ndim < 1 || !Cm || ldc < ndim || !G || ldg < ndim || !W || ldw < ndim || !Q || ldq < ndim || (X && ldx < ndim)) {
-        set_error("hmc_kick_drift_dense: bad arguments"); return LINNA_ERR_INVALID;
-    }
-    TRY(hmc_dense_ndim(ndim, "hmc_kick_drift_dense"));
-    return launch_hmc_kick_drift_dense(B, ndim, Cm, ldc, EPS, mul_kick, mul_drift, G, ldg, W, ldw, X, ldx, Q, ldq, S(stream));
-} LINNA_CATCH_INT
-size_t linna_hmc_chees_doubles(int ndim) try {
-    if (ndim < 1) return 0;
-    return LINNA_HMC_CHEES_HEAD + 2 * (size_t)ndim;
-} LINNA_CATCH_SIZE
-int linna_hmc_chees_begin(linna_ctx_t*, int B, int ndim, const float* X, int ldx, double* state, double* r0, void* stream) try {
-    if (B < 1 || ndim < 1 || !X || ldx < ndim || !state || !r0) { set_error("hmc_chees_begin: bad arguments"); return LINNA_ERR_INVALID; }
-    return launch_hmc_chees_begin(B, ndim, X, ldx, state, r0, S(stream));
-} LINNA_CATCH_INT
-int linna_hmc_chees_end(linna_ctx_t*, int B, int ndim, const float* mass, const float* Cm, int ldc, const float* Q, int ldq,
-                        const float* P, int ldp, const float* alpha, const double* r0, double* state, float* EPS, int M, double delta,
-                        int max_steps, void* stream) try {
-    if (B < 1 || ndim < 1 || (!mass && !Cm) || (Cm && ldc < ndim) || !Q || ldq < ndim || !P || ldp < ndim || !alpha || !r0 || !state ||
-        !EPS || max_steps < 1 || !(delta > 0.0 && delta < 1.0)) {
-        set_error("hmc_chees_end: bad arguments"); return LINNA_ERR_INVALID;
-    }
-    if (Cm) TRY(hmc_dense_ndim(ndim, "hmc_chees_end"));
-    return launch_hmc_chees_end(B, ndim, mass, Cm, ldc, Q, ldq, P, ldp, alpha, r0, state, EPS, M, delta, max_steps, S(stream));
-} LINNA_CATCH_INT
-int linna_hmc_start_eps(linna_ctx_t*, int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, int step_offset,
-                        const float* lnp, const float* P0, int ldp0, const float* G, int ldg, const float* EPS, float mul_kick,
-                        float mul_drift, const float* X, int ldx, float* P, int ldp, float* Q, int ldq, float* H0, void* stream) try {
-    if (B < 1 || ndim < 1 || !mass || !step_dev || !lnp || !G || !EPS || !X || !P || !Q || !H0) { set_error("hmc_start_eps: bad arguments"); return LINNA_ERR_INVALID; }
-    return launch_hmc_start(B, ndim, mass, seed, step_dev, lnp, P0, ldp0, G, ldg, mul_kick, mul_drift, X, ldx, P, ldp, Q, ldq, H0, S(stream),
-                            EPS, step_offset);
-} LINNA_CATCH_INT
-int linna_hmc_kick_drift_eps(linna_ctx_t*, int B, int ndim, const float* mass, const float* EPS, float mul_kick, float mul_drift,
-                             const float* G, int ldg, float* P, int ldp, float* Q, int ldq, void* stream) try {
-    if (B < 1 || ndim < 1 || !mass || !EPS || !G || !P || !Q) { set_error("hmc_kick_drift_eps: bad arguments"); return LINNA_ERR_INVALID; }
-    return launch_hmc_kick_drift(B, ndim, mass, mul_kick, mul_drift, G, ldg, P, ldp, Q, ldq, S(stream), EPS);
-} LINNA_CATCH_INT
-int linna_hmc_accept_adapt(linna_ctx_t*, int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, int step_offset,
-                           const float* H0, const float* P, int ldp, const float* Qn, int ldq, const float* lnp_new, const float* Gn,
-                           int ldg, const float* U, float* X, int ldx, float* lnp, float* G, int* naccept, float* alpha, float* EPS,
-                           float* EPSBAR, float* HBAR, const float* MU, int* M, int Madapt, float delta, float* chain, float* logps,
-                           void* stream) try {
-    if (B < 1 || ndim < 1 || !mass || !step_dev || !H0 || !P || !Qn || !lnp_new || !Gn || !X || !lnp || !G || Madapt < 0 ||
-        (Madapt > 0 && (!EPS || !EPSBAR || !HBAR || !MU || !M))) {
-        set_error("hmc_accept_adapt: bad arguments"); return LINNA_ERR_INVALID;
-    }
-    const HmcAdapt ad{EPS, EPSBAR, HBAR, MU, M, Madapt, delta};
-    return launch_hmc_accept(B, ndim, mass, seed, step_dev, step_offset, H0, P, ldp, Qn, ldq, lnp_new, Gn, ldg, U, X, ldx, lnp, G,
-                             naccept, alpha, ad, chain, logps, HmcEnergy{}, S(stream));
-} LINNA_CATCH_INT
-size_t linna_hmc_energy_doubles(int B) try {
-    if (B < 1) return 0;
-    return (size_t)LINNA_HMC_ENERGY_DOUBLES * (size_t)B;
-} LINNA_CATCH_SIZE
-int linna_hmc_accept_energy(linna_ctx_t*, int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, int step_offset,
-                            const float* H0, const float* P, int ldp, const float* Qn, int ldq, const float* lnp_new, const float* Gn,
-                            int ldg, const float* U, float* X, int ldx, float* lnp, float* G, int* naccept, float* alpha, float* EPS,
-                            float* EPSBAR, float* HBAR, const float* MU, int* M, int Madapt, float delta, float* chain, float* logps,
-                            double* estate, int* ndiv, float max_dH, float* energy, float* dH, void* stream) try {
-    if (B < 1 || ndim < 1 || !mass || !step_dev || !H0 || !P || !Qn || !lnp_new || !Gn || !X || !lnp || !G || Madapt < 0 ||
-        (Madapt > 0 && (!EPS || !EPSBAR || !HBAR || !MU || !M))) {
-        set_error("hmc_accept_energy: bad arguments"); return LINNA_ERR_INVALID;
-    }
-    const HmcEnergy en{estate, ndiv, max_dH, energy, dH};
-    TRY(hmc_energy_check(en, "hmc_accept_energy"));
-    const HmcAdapt ad{EPS, EPSBAR, HBAR, MU, M, Madapt, delta};
-    return launch_hmc_accept(B, ndim, mass, seed, step_dev, step_offset, H0, P, ldp, Qn, ldq, lnp_new, Gn, ldg, U, X, ldx, lnp, G,
-                             naccept, alpha, ad, chain, logps, en, S(stream));
-} LINNA_CATCH_INT
-int linna_hmc_energy_finish(linna_ctx_t*, int B, const double* estate, const int* ndiv, float* bfmi, double* pooled, void* stream) try {
-    if (B < 1 || !estate || !ndiv || !bfmi || !pooled) { set_error("hmc_energy_finish: bad arguments"); return LINNA_ERR_INVALID; }
-    return launch_hmc_energy_finish(B, estate, ndiv, bfmi, pooled, S(stream));
-} LINNA_CATCH_INT
-int linna_hmc_accept(linna_ctx_t*, int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, const float* H0,
-                     const float* P, int ldp, const float* Qn, int ldq, const float* lnp_new, const float* Gn, int ldg,
-                     const float* U, float* X, int ldx, float* lnp, float* G, int* naccept, void* stream) try {
-    // the Metropolis test alone: no acceptance rate, no chain row, no adaptation state
-    return launch_hmc_accept(B, ndim, mass, seed, step_dev, 0, H0, P, ldp, Qn, ldq, lnp_new, Gn, ldg, U, X, ldx, lnp, G, naccept, nullptr,
-                             HmcAdapt{}, nullptr, nullptr, HmcEnergy{}, S(stream));
 } LINNA_CATCH_INT
 int linna_step_increment(linna_ctx_t*, int* step_dev, void* stream) try { return launch_step_increment(step_dev, S(stream)); } LINNA_CATCH_INT
 

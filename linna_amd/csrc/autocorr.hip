@@ -40,12 +40,6 @@ constexpr int AC_TT = 16;       // anchor rows per tile
 constexpr int AC_WAVES = 4;     // wavefronts (lag blocks) per workgroup
 constexpr int AC_CK = 32;       // lags per chunk of the finalising kernels
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // ------------------------------------------------------------------ transposing append
 // block[nsteps][nw][ldb] (the sampler's chain block, walker-major) -> CT[row0 + i][d][lane(w)].  Every wstride-th walker --
 // the subset the routine checks average over -- takes the first nws lanes of a parameter, the others follow in order:
@@ -466,27 +460,35 @@ __global__ __launch_bounds__(256) void acorr_geyer_kernel(const double* __restri
     out[2 * nd + d] = ok ? status : 0.0;
 }
 
-// ------------------------------------------------------------------ launchers
-int launch_chain_block_moments(const float* CT, int ndim, int nwp, int64_t b0, int64_t b1, double* M, hipStream_t s) {
-    for (int64_t b = b0; b < b1; b += 32768) {
-        const int nb = (int)(b1 - b < 32768 ? b1 - b : 32768);
-        hipLaunchKernelGGL(chain_block_moments_kernel, dim3(ndim * (nwp / 64), nb), dim3(64), 0, s, CT, ndim, nwp, b, M);
-    }
-    return check_hip(hipGetLastError(), "chain_block_moments");
+// ------------------------------------------------------------------ launch code
+// Only the two estimators, each a sequence of five kernels, have a function: every other kernel is launched by its entry.
+static size_t acorr_scratch_doubles(int nser, int kuse, int nd) {
+    const size_t nchunk = (size_t)kuse / AC_CK + 1;
+    return 2 * nchunk * nser + nchunk * AC_CK * (size_t)(nser / 64) + (size_t)nd * (kuse + 1);
 }
 
-int launch_chain_rhat(const float* CT, int ndim, int nwp, int nw, int64_t lo, int64_t hi, const double* M, int64_t nblocks,
-                      double* out, hipStream_t s) {
-    hipLaunchKernelGGL(chain_rhat_kernel, dim3(ndim), dim3(64 * RH_WAVES), 0, s, CT, ndim, nwp, nw, lo, hi, M, nblocks, out);
-    return check_hip(hipGetLastError(), "chain_rhat");
+static int launch_acorr_tau(const float* CT, int ndim, int nwp, int nwc, int nlive, int64_t lo, int64_t hi, int kuse, const double* S,
+                            const double* T, double c, double* scratch, double* out, hipStream_t s) {
+    const int nser = ndim * nwc;
+    const int nchunk = kuse / AC_CK + 1, L = kuse + 1;
+    double* HC = scratch;
+    double* TC = HC + (size_t)nchunk * nser;
+    double* P = TC + (size_t)nchunk * nser;
+    double* F = P + (size_t)nchunk * AC_CK * (nser / 64);
+    hipLaunchKernelGGL(acorr_chunksum_kernel, dim3(nser / 64, nchunk), dim3(64), 0, s, CT, ndim, nwp, nwc, (int)lo, (int)hi, HC, TC);
+    hipLaunchKernelGGL(acorr_chunkscan_kernel, dim3(nser / 64), dim3(64), 0, s, nser, nchunk, HC, TC);
+    hipLaunchKernelGGL(acorr_rho_kernel, dim3(nser / 64, nchunk), dim3(64), 0, s, CT, ndim, nwp, nwc, nlive, (int)lo, (int)hi, kuse, S, T, HC, TC, P);
+    hipLaunchKernelGGL(acorr_fmean_kernel, dim3((L + 255) / 256, ndim), dim3(256), 0, s, P, nser / 64, nwc / 64, nlive, L, ndim, F);
+    hipLaunchKernelGGL(acorr_window_kernel, dim3(ndim), dim3(256), 0, s, F, kuse, (int)(hi - lo), c, ndim, out);
+    LAUNCH_CHECK("acorr_tau");
 }
 
-size_t acorr_ess_scratch_doubles(int nser, int kuse, int nd) {
+static size_t acorr_ess_scratch_doubles(int nser, int kuse, int nd) {
     return acorr_scratch_doubles(nser, kuse, nd) + 2 * (size_t)(nser / 64);
 }
 
-int launch_acorr_ess(const float* CT, int ndim, int nwp, int nwc, int nlive, int64_t lo, int64_t hi, int kuse, const double* S,
-                     const double* T, double* scratch, double* out, hipStream_t s) {
+static int launch_acorr_ess(const float* CT, int ndim, int nwp, int nwc, int nlive, int64_t lo, int64_t hi, int kuse, const double* S,
+                            const double* T, double* scratch, double* out, hipStream_t s) {
     const int nser = ndim * nwc;
     const int nchunk = kuse / AC_CK + 1, L = kuse + 1;
     double* HC = scratch;
@@ -499,52 +501,90 @@ int launch_acorr_ess(const float* CT, int ndim, int nwp, int nwc, int nlive, int
     hipLaunchKernelGGL(acorr_cov_kernel, dim3(nser / 64, nchunk), dim3(64), 0, s, CT, ndim, nwp, nwc, nlive, (int)lo, (int)hi, kuse, S, T, HC, TC, P, Q);
     hipLaunchKernelGGL(acorr_fmean_kernel, dim3((L + 255) / 256, ndim), dim3(256), 0, s, P, nser / 64, nwc / 64, nlive, L, ndim, F);
     hipLaunchKernelGGL(acorr_geyer_kernel, dim3(ndim), dim3(256), 0, s, F, Q, nser / 64, nwc / 64, nlive, kuse, (int)(hi - lo), ndim, out);
-    return check_hip(hipGetLastError(), "acorr_ess");
-}
-
-int launch_chain_append_t(const float* block, int ldb, int nsteps, int nw, int ndim, int wstride, float* CT, int nwp,
-                          int64_t row0, hipStream_t s) {
-    const int nws = (nw + wstride - 1) / wstride;
-    hipLaunchKernelGGL(chain_append_t_kernel, dim3(nwp / 64, nsteps), dim3(256), (size_t)64 * (ndim + 1) * sizeof(float), s,
-                       block, ldb, nw, ndim, wstride, nws, CT, nwp, row0);
-    return check_hip(hipGetLastError(), "chain_append_t");
-}
-
-int launch_acorr_update(const float* CT, int nd, int nwp, int nwc, int64_t a0, int64_t a1, int64_t lo, int64_t hi, int k0, int k1,
-                        double* S, double* T, int remove, hipStream_t s) {
-    if (a1 <= a0 || k1 <= k0) return LINNA_OK;
-    const int nblk = (k1 - k0) / AC_R;
-    const dim3 grid(nd * nwc / 64, (nblk + AC_WAVES - 1) / AC_WAVES), block(64 * AC_WAVES);
-    if (remove) hipLaunchKernelGGL((acorr_update_kernel<1>), grid, block, 0, s, CT, nd, nwp, nwc, (int)a0, (int)a1, (int)lo, (int)hi, k0, k1, S, T, -1.0);
-    else hipLaunchKernelGGL((acorr_update_kernel<-1>), grid, block, 0, s, CT, nd, nwp, nwc, (int)a0, (int)a1, (int)lo, (int)hi, k0, k1, S, T, 1.0);
-    return check_hip(hipGetLastError(), "acorr_update");
-}
-
-size_t acorr_scratch_doubles(int nser, int kuse, int nd) {
-    const size_t nchunk = (size_t)kuse / AC_CK + 1;
-    return 2 * nchunk * nser + nchunk * AC_CK * (size_t)(nser / 64) + (size_t)nd * (kuse + 1);
-}
-
-int launch_acorr_tau(const float* CT, int ndim, int nwp, int nwc, int nlive, int64_t lo, int64_t hi, int kuse, const double* S,
-                     const double* T, double c, double* scratch, double* out, hipStream_t s) {
-    const int nser = ndim * nwc;
-    const int nchunk = kuse / AC_CK + 1, L = kuse + 1;
-    double* HC = scratch;
-    double* TC = HC + (size_t)nchunk * nser;
-    double* P = TC + (size_t)nchunk * nser;
-    double* F = P + (size_t)nchunk * AC_CK * (nser / 64);
-    hipLaunchKernelGGL(acorr_chunksum_kernel, dim3(nser / 64, nchunk), dim3(64), 0, s, CT, ndim, nwp, nwc, (int)lo, (int)hi, HC, TC);
-    hipLaunchKernelGGL(acorr_chunkscan_kernel, dim3(nser / 64), dim3(64), 0, s, nser, nchunk, HC, TC);
-    hipLaunchKernelGGL(acorr_rho_kernel, dim3(nser / 64, nchunk), dim3(64), 0, s, CT, ndim, nwp, nwc, nlive, (int)lo, (int)hi, kuse, S, T, HC, TC, P);
-    hipLaunchKernelGGL(acorr_fmean_kernel, dim3((L + 255) / 256, ndim), dim3(256), 0, s, P, nser / 64, nwc / 64, nlive, L, ndim, F);
-    hipLaunchKernelGGL(acorr_window_kernel, dim3(ndim), dim3(256), 0, s, F, kuse, (int)(hi - lo), c, ndim, out);
-    return check_hip(hipGetLastError(), "acorr_tau");
-}
-
-int launch_chain_meanstd(const float* CT, int ndim, int nwp, int nws, int64_t t0, int64_t tm, int64_t t1, double* out,
-                         hipStream_t s) {
-    hipLaunchKernelGGL(chain_meanstd_kernel, dim3(ndim, 2), dim3(256), 0, s, CT, ndim, nwp, nws, t0, tm, t1, out);
-    return check_hip(hipGetLastError(), "chain_meanstd");
+    LAUNCH_CHECK("acorr_ess");
 }
 
 }  // namespace linna
+
+using namespace linna;
+
+// ------------------------------------------------------------------ the entries (include/linna_hip.h)
+// chain_rank.hip runs the lagged products and the Geyer finish on its scores image through linna_acorr_update,
+// linna_acorr_ess_scratch_bytes and linna_acorr_ess, like any other caller.
+int linna_chain_append_t(linna_ctx_t*, const float* block, int ldb, int nsteps, int nw, int ndim, int wstride, float* CT, int nwp,
+                         int64_t row0, void* stream) try {
+    if (!block || !CT || nsteps < 1 || nw < 1 || wstride < 1 || ldb < ndim || row0 < 0 || !ac_shape_ok(ndim, nwp) ||
+        nw > nwp || nsteps > 65535 || (size_t)64 * (ndim + 1) * sizeof(float) > 64 * 1024) {
+        set_error("chain_append_t: bad arguments"); return LINNA_ERR_INVALID;
+    }
+    const int nws = (nw + wstride - 1) / wstride;
+    hipLaunchKernelGGL(chain_append_t_kernel, dim3(nwp / 64, nsteps), dim3(256), (size_t)64 * (ndim + 1) * sizeof(float), S(stream),
+                       block, ldb, nw, ndim, wstride, nws, CT, nwp, row0);
+    LAUNCH_CHECK("chain_append_t");
+} LINNA_CATCH_INT
+static bool ac_cover_ok(int nwp, int nwc, int nlive) { return nwc >= 64 && (nwc & 63) == 0 && nwc <= nwp && nlive >= 1 && nlive <= nwc; }
+int linna_acorr_update(linna_ctx_t*, const float* CT, int ndim, int nwp, int nwc, int64_t a0, int64_t a1, int64_t lo, int64_t hi, int k0,
+                       int k1, double* Ssum, double* Tsum, int remove, void* stream) try {
+    if (!CT || !Ssum || !ac_shape_ok(ndim, nwp) || !ac_cover_ok(nwp, nwc, 1) || k0 < 0 || k1 < k0 || (k0 & 31) || (k1 & 31) || lo < 0 ||
+        hi < lo || a0 < lo || a1 > hi || a1 < a0 || (k1 - k0) / 32 > 4 * 65535 || hi > 0x7fffff00) {
+        set_error("acorr_update: bad arguments (lag ranges are multiples of 32, anchors inside [lo, hi))"); return LINNA_ERR_INVALID;
+    }
+    if (a1 <= a0 || k1 <= k0) return LINNA_OK;
+    const int nblk = (k1 - k0) / AC_R;
+    const dim3 grid(ndim * nwc / 64, (nblk + AC_WAVES - 1) / AC_WAVES), block(64 * AC_WAVES);
+    if (remove) hipLaunchKernelGGL((acorr_update_kernel<1>), grid, block, 0, S(stream), CT, ndim, nwp, nwc, (int)a0, (int)a1, (int)lo, (int)hi, k0, k1, Ssum, Tsum, -1.0);
+    else hipLaunchKernelGGL((acorr_update_kernel<-1>), grid, block, 0, S(stream), CT, ndim, nwp, nwc, (int)a0, (int)a1, (int)lo, (int)hi, k0, k1, Ssum, Tsum, 1.0);
+    LAUNCH_CHECK("acorr_update");
+} LINNA_CATCH_INT
+size_t linna_acorr_scratch_bytes(int ndim, int nwc, int kuse) try {
+    if (ndim < 1 || nwc < 64 || (nwc & 63) || kuse < 0) return 0;
+    return acorr_scratch_doubles(ndim * nwc, kuse, ndim) * sizeof(double);
+} LINNA_CATCH_SIZE
+int linna_acorr_tau(linna_ctx_t*, const float* CT, int ndim, int nwp, int nwc, int nlive, int64_t lo, int64_t hi, int kuse,
+                    const double* Ssum, const double* Tsum, double c, double* scratch, double* out, void* stream) try {
+    if (!CT || !Ssum || !Tsum || !scratch || !out || !ac_shape_ok(ndim, nwp) || !ac_cover_ok(nwp, nwc, nlive) || lo < 0 || hi <= lo ||
+        kuse < 0 || (int64_t)kuse > hi - lo - 1 || kuse / 32 + 1 > 65535 || !(c > 0.0) || hi > 0x7fffff00) {
+        set_error("acorr_tau: bad arguments (0 <= kuse <= hi - lo - 1)"); return LINNA_ERR_INVALID;
+    }
+    return launch_acorr_tau(CT, ndim, nwp, nwc, nlive, lo, hi, kuse, Ssum, Tsum, c, scratch, out, S(stream));
+} LINNA_CATCH_INT
+int linna_chain_meanstd(linna_ctx_t*, const float* CT, int ndim, int nwp, int nws, int64_t t0, int64_t tm, int64_t t1, double* out,
+                        void* stream) try {
+    if (!CT || !out || !ac_shape_ok(ndim, nwp) || nws < 1 || nws > nwp || t0 < 0 || tm < t0 || t1 < tm || ndim > 65535) {
+        set_error("chain_meanstd: bad arguments"); return LINNA_ERR_INVALID;
+    }
+    hipLaunchKernelGGL(chain_meanstd_kernel, dim3(ndim, 2), dim3(256), 0, S(stream), CT, ndim, nwp, nws, t0, tm, t1, out);
+    LAUNCH_CHECK("chain_meanstd");
+} LINNA_CATCH_INT
+int linna_chain_block_moments(linna_ctx_t*, const float* CT, int ndim, int nwp, int64_t b0, int64_t b1, double* M, void* stream) try {
+    if (!CT || !M || !ac_shape_ok(ndim, nwp) || b0 < 0 || b1 < b0 || b1 > 0x7fffff00 / LINNA_RHAT_BLOCK ||
+        (int64_t)ndim * (nwp / 64) > 0x7fffffff) {
+        set_error("chain_block_moments: bad arguments"); return LINNA_ERR_INVALID;
+    }
+    for (int64_t b = b0; b < b1; b += 32768) {
+        const int nb = (int)(b1 - b < 32768 ? b1 - b : 32768);
+        hipLaunchKernelGGL(chain_block_moments_kernel, dim3(ndim * (nwp / 64), nb), dim3(64), 0, S(stream), CT, ndim, nwp, b, M);
+    }
+    LAUNCH_CHECK("chain_block_moments");
+} LINNA_CATCH_INT
+int linna_chain_rhat(linna_ctx_t*, const float* CT, int ndim, int nwp, int nw, int64_t lo, int64_t hi, const double* M, int64_t nblocks,
+                     double* out, void* stream) try {
+    if (!CT || !out || !ac_shape_ok(ndim, nwp) || nw < 1 || nw > nwp || lo < 0 || hi < lo || (hi - lo) / 2 < 2 || nblocks < 0 ||
+        hi > 0x7fffff00) {
+        set_error("chain_rhat: bad arguments (the window [lo, hi) needs two halves of at least 2 rows)"); return LINNA_ERR_INVALID;
+    }
+    hipLaunchKernelGGL(chain_rhat_kernel, dim3(ndim), dim3(64 * RH_WAVES), 0, S(stream), CT, ndim, nwp, nw, lo, hi, M, nblocks, out);
+    LAUNCH_CHECK("chain_rhat");
+} LINNA_CATCH_INT
+size_t linna_acorr_ess_scratch_bytes(int ndim, int nwc, int kuse) try {
+    if (ndim < 1 || nwc < 64 || (nwc & 63) || kuse < 0) return 0;
+    return acorr_ess_scratch_doubles(ndim * nwc, kuse, ndim) * sizeof(double);
+} LINNA_CATCH_SIZE
+int linna_acorr_ess(linna_ctx_t*, const float* CT, int ndim, int nwp, int nwc, int nlive, int64_t lo, int64_t hi, int kuse,
+                    const double* Ssum, const double* Tsum, double* scratch, double* out, void* stream) try {
+    if (!CT || !Ssum || !Tsum || !scratch || !out || !ac_shape_ok(ndim, nwp) || !ac_cover_ok(nwp, nwc, nlive) || lo < 0 || hi <= lo ||
+        kuse < 0 || (int64_t)kuse > hi - lo - 1 || kuse / 32 + 1 > 65535 || hi > 0x7fffff00) {
+        set_error("acorr_ess: bad arguments (0 <= kuse <= hi - lo - 1)"); return LINNA_ERR_INVALID;
+    }
+    return launch_acorr_ess(CT, ndim, nwp, nwc, nlive, lo, hi, kuse, Ssum, Tsum, scratch, out, S(stream));
+} LINNA_CATCH_INT

@@ -38,12 +38,6 @@ constexpr int RK_CHUNKS = 16;                    // chunks of RK_THREADS element
 constexpr int RK_TILE = RK_THREADS * RK_CHUNKS;  // elements per workgroup and pass
 constexpr int RK_MW = 16;                        // wavefronts of the moments workgroup
 
-__device__ __forceinline__ double rk_wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __device__ __forceinline__ uint32_t rk_key(uint32_t bits) {
     if ((bits << 1) == 0u) bits = 0u;                                   // -0 = +0
     return (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);
@@ -264,7 +258,7 @@ __global__ __launch_bounds__(64) void rank_finish_kernel(const double* __restric
         const double mean = m[2 * (size_t)c], var = m[2 * (size_t)c + 1];
         am += mean; am2 = __builtin_fma(mean, mean, am2); av += var;
     }
-    am = rk_wave_sum_f64(am); am2 = rk_wave_sum_f64(am2); av = rk_wave_sum_f64(av);
+    am = wave_sum_f64(am); am2 = wave_sum_f64(am2); av = wave_sum_f64(av);
     if (lane != 0) return;
     const double nc = 2.0 * (double)nw;
     const double W = av / nc;
@@ -300,7 +294,7 @@ static RankLayout rank_layout(int nw, int64_t rows, int npar) {
     L.counts = L.keys + bkeys * npar;
     return L;
 }
-size_t chain_rank_rhat_scratch_bytes(int nw, int64_t rows, int npar) { return rank_layout(nw, rows, npar).per * (size_t)npar; }
+static size_t chain_rank_rhat_scratch_bytes(int nw, int64_t rows, int npar) { return rank_layout(nw, rows, npar).per * (size_t)npar; }
 
 static void rank_sort(uint32_t* KA, uint32_t* IA, uint32_t* KB, uint32_t* IB, uint32_t* C, uint32_t S, uint32_t ntiles, int npar,
                       hipStream_t s) {
@@ -314,8 +308,8 @@ static void rank_sort(uint32_t* KA, uint32_t* IA, uint32_t* KB, uint32_t* IB, ui
     }                                                                   // (4 passes: the sorted pairs are back in KA, IA)
 }
 
-int launch_chain_rank_rhat(const float* CT, int ndim, int nwp, int nw, int64_t lo, int64_t hi, void* scratch, size_t scratch_bytes,
-                           uint32_t* rank2_out, double* out, hipStream_t s) {
+static int launch_chain_rank_rhat(const float* CT, int ndim, int nwp, int nw, int64_t lo, int64_t hi, void* scratch, size_t scratch_bytes,
+                                  uint32_t* rank2_out, double* out, hipStream_t s) {
     const int64_t n = (hi - lo) / 2;
     const uint32_t S = (uint32_t)(2 * n * nw);
     const size_t per = rank_layout(nw, 2 * n, 1).per;
@@ -437,7 +431,7 @@ static RankEssLayout rank_ess_layout(int nw, int64_t rows, int kuse, int npar) {
     L.cp = (2 * nw + 63) & ~63;
     L.k1 = (kuse + 32) & ~31;                                           // lags 0 .. kuse in whole blocks of 32
     const size_t bs = (size_t)L.k1 * 3 * L.cp * sizeof(double), bt = (size_t)3 * L.cp * sizeof(double);
-    const size_t be = acorr_ess_scratch_doubles(3 * L.cp, kuse, 3) * sizeof(double), bg = 9 * sizeof(double), bflag = 8;
+    const size_t be = linna_acorr_ess_scratch_bytes(3, L.cp, kuse), bg = 9 * sizeof(double), bflag = 8;
     const size_t bkeys = 4 * S * sizeof(uint32_t), bcounts = (size_t)L.ntiles * RK_THREADS * sizeof(uint32_t);
     const size_t bimg = 3 * n * L.cp * sizeof(float);
     L.per = bs + bt + be + bg + bflag + bkeys + bcounts + bimg;
@@ -451,12 +445,12 @@ static RankEssLayout rank_ess_layout(int nw, int64_t rows, int kuse, int npar) {
     L.img = L.counts + bcounts * npar;
     return L;
 }
-size_t chain_rank_ess_scratch_bytes(int nw, int64_t rows, int kuse, int npar) {
+static size_t chain_rank_ess_scratch_bytes(int nw, int64_t rows, int kuse, int npar) {
     return rank_ess_layout(nw, rows, kuse, npar).per * (size_t)npar;
 }
 
-int launch_chain_rank_ess(const float* CT, int ndim, int nwp, int nw, int64_t lo, int64_t hi, int kuse, void* scratch,
-                          size_t scratch_bytes, double* out, hipStream_t s) {
+static int launch_chain_rank_ess(const float* CT, int ndim, int nwp, int nw, int64_t lo, int64_t hi, int kuse, void* scratch,
+                                 size_t scratch_bytes, double* out, hipStream_t s) {
     const int64_t n = (hi - lo) / 2;
     const uint32_t S = (uint32_t)(2 * n * nw);
     const RankEssLayout one = rank_ess_layout(nw, 2 * n, kuse, 1);
@@ -494,9 +488,10 @@ int launch_chain_rank_ess(const float* CT, int ndim, int nwp, int nw, int64_t lo
         hipLaunchKernelGGL((rank_keys_kernel<0>), eg, dim3(RK_THREADS), 0, s, CT, ndim, nwp, nw, d0, lo, hi, S, (const double*)nullptr, KA, IA, flag);
         rank_sort(KA, IA, KB, IB, C, S, L.ntiles, np, s);
         hipLaunchKernelGGL(rank_scores_kernel, eg, dim3(RK_THREADS), 0, s, KA, IA, S, nw, n, np, L.cp, img);
-        rc = launch_acorr_update(img, 3 * np, L.cp, L.cp, 0, n, 0, n, 0, L.k1, Ssum, Tsum, 0, s);
+        // the image is a chain like any other: its lagged products and their Geyer finish through autocorr.hip's own entries
+        rc = linna_acorr_update(nullptr, img, 3 * np, L.cp, L.cp, 0, n, 0, n, 0, L.k1, Ssum, Tsum, 0, s);
         if (rc) return rc;
-        rc = launch_acorr_ess(img, 3 * np, L.cp, L.cp, 2 * nw, 0, n, kuse, Ssum, Tsum, est, G, s);
+        rc = linna_acorr_ess(nullptr, img, 3 * np, L.cp, L.cp, 2 * nw, 0, n, kuse, Ssum, Tsum, est, G, s);
         if (rc) return rc;
         hipLaunchKernelGGL(rank_ess_finish_kernel, dim3((np + 63) / 64), dim3(64), 0, s, G, flag, np, d0, out);
     }
@@ -504,3 +499,58 @@ int launch_chain_rank_ess(const float* CT, int ndim, int nwp, int nw, int64_t lo
 }
 
 }  // namespace linna
+
+using namespace linna;
+
+// ------------------------------------------------------------------ the entries (include/linna_hip.h)
+size_t linna_chain_rank_rhat_scratch_bytes(int ndim, int nw, int64_t rows, int npar) try {
+    if (ndim < 1 || nw < 1 || rows < 2 || (rows & 1) || npar < 1 || rows > 0x7fffffff / nw) return 0;
+    return chain_rank_rhat_scratch_bytes(nw, rows, npar < ndim ? npar : ndim);
+} LINNA_CATCH_SIZE
+int linna_chain_rank_rhat(linna_ctx_t*, const float* CT, int ndim, int nwp, int nw, int64_t lo, int64_t hi, void* scratch,
+                          size_t scratch_bytes, uint32_t* rank2_out, double* out, void* stream) try {
+    if (!CT || !out || !scratch || ((uintptr_t)scratch & 7) || !ac_shape_ok(ndim, nwp) || nw < 1 || nw > nwp || lo < 0 || hi < lo ||
+        (hi - lo) / 2 < 2 || hi > 0x7fffff00) {
+        set_error("chain_rank_rhat: bad arguments (the window [lo, hi) needs two halves of at least 2 rows; scratch 8-byte aligned)");
+        return LINNA_ERR_INVALID;
+    }
+    const int64_t rows = (hi - lo) / 2 * 2;
+    if (rows > 0x7fffffff / nw) {
+        set_error("chain_rank_rhat: %lld pooled values per parameter; the sort's 32-bit element indices hold fewer than 2^31",
+                  (long long)rows * nw);
+        return LINNA_ERR_UNSUPPORTED;
+    }
+    if (scratch_bytes < chain_rank_rhat_scratch_bytes(nw, rows, 1)) {
+        set_error("chain_rank_rhat: scratch of %zu bytes, one parameter needs %zu (linna_chain_rank_rhat_scratch_bytes)", scratch_bytes,
+                  chain_rank_rhat_scratch_bytes(nw, rows, 1));
+        return LINNA_ERR_INVALID;
+    }
+    return launch_chain_rank_rhat(CT, ndim, nwp, nw, lo, hi, scratch, scratch_bytes, rank2_out, out, S(stream));
+} LINNA_CATCH_INT
+size_t linna_chain_rank_ess_scratch_bytes(int ndim, int nw, int64_t rows, int kuse, int npar) try {
+    if (ndim < 1 || nw < 1 || rows < 4 || (rows & 1) || npar < 1 || rows > 0x7fffffff / nw || kuse < 1 || (int64_t)kuse > rows / 2 - 1 ||
+        kuse / 32 + 1 > 65535 || nw > (1 << 24))
+        return 0;
+    return chain_rank_ess_scratch_bytes(nw, rows, kuse, npar < ndim ? npar : ndim);
+} LINNA_CATCH_SIZE
+int linna_chain_rank_ess(linna_ctx_t*, const float* CT, int ndim, int nwp, int nw, int64_t lo, int64_t hi, int kuse, void* scratch,
+                         size_t scratch_bytes, double* out, void* stream) try {
+    if (!CT || !out || !scratch || ((uintptr_t)scratch & 7) || !ac_shape_ok(ndim, nwp) || nw < 1 || nw > nwp || lo < 0 || hi < lo ||
+        (hi - lo) / 2 < 2 || hi > 0x7fffff00 || kuse < 1 || (int64_t)kuse > (hi - lo) / 2 - 1 || kuse / 32 + 1 > 65535 || nw > (1 << 24)) {
+        set_error("chain_rank_ess: bad arguments (the window [lo, hi) needs two halves of n >= 2 rows; 1 <= kuse <= n - 1; scratch "
+                  "8-byte aligned)");
+        return LINNA_ERR_INVALID;
+    }
+    const int64_t rows = (hi - lo) / 2 * 2;
+    if (rows > 0x7fffffff / nw) {
+        set_error("chain_rank_ess: %lld pooled values per parameter; the sort's 32-bit element indices hold fewer than 2^31",
+                  (long long)rows * nw);
+        return LINNA_ERR_UNSUPPORTED;
+    }
+    if (scratch_bytes < chain_rank_ess_scratch_bytes(nw, rows, kuse, 1)) {
+        set_error("chain_rank_ess: scratch of %zu bytes, one parameter needs %zu (linna_chain_rank_ess_scratch_bytes)", scratch_bytes,
+                  chain_rank_ess_scratch_bytes(nw, rows, kuse, 1));
+        return LINNA_ERR_INVALID;
+    }
+    return launch_chain_rank_ess(CT, ndim, nwp, nw, lo, hi, kuse, scratch, scratch_bytes, out, S(stream));
+} LINNA_CATCH_INT

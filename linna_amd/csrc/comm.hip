@@ -80,17 +80,15 @@ using namespace linna;
 void** linna_ctx_comm_slot(linna_ctx_t* ctx);
 int linna_ctx_device(const linna_ctx_t* ctx);
 
-#define TRYC(expr) do { int rc__ = (expr); if (rc__ != LINNA_OK) return rc__; } while (0)
-
 static CommState* state_of(linna_ctx_t* ctx) {
     return ctx ? static_cast<CommState*>(*linna_ctx_comm_slot(ctx)) : nullptr;
 }
 
 int linna_comm_unique_id(void* id) try {
     if (!id) { set_error("comm_unique_id: null id"); return LINNA_ERR_INVALID; }
-    TRYC(rccl());
+    TRY(rccl());
     UniqueId u;
-    TRYC(check_rccl(g_rccl.GetUniqueId(&u), "ncclGetUniqueId"));
+    TRY(check_rccl(g_rccl.GetUniqueId(&u), "ncclGetUniqueId"));
     memcpy(id, u.internal, LINNA_COMM_ID_BYTES);
     return LINNA_OK;
 } LINNA_CATCH_INT
@@ -101,12 +99,12 @@ int linna_comm_init(linna_ctx_t* ctx, int rank, int nranks, const void* id) try 
         return LINNA_ERR_INVALID;
     }
     if (state_of(ctx)) { set_error("comm_init: this context already holds a communicator"); return LINNA_ERR_INVALID; }
-    TRYC(rccl());
-    TRYC(check_hip(hipSetDevice(linna_ctx_device(ctx)), "hipSetDevice"));
+    TRY(rccl());
+    TRY(check_hip(hipSetDevice(linna_ctx_device(ctx)), "hipSetDevice"));
     UniqueId u;
     memcpy(u.internal, id, LINNA_COMM_ID_BYTES);
     Comm c = nullptr;
-    TRYC(check_rccl(g_rccl.CommInitRank(&c, nranks, u, rank), "ncclCommInitRank"));
+    TRY(check_rccl(g_rccl.CommInitRank(&c, nranks, u, rank), "ncclCommInitRank"));
     CommState* st = new (std::nothrow) CommState();
     if (!st) { (void)g_rccl.CommDestroy(c); return LINNA_ERR_INVALID; }
     st->comm = c; st->rank = rank; st->nranks = nranks;

@@ -37,6 +37,13 @@ __device__ __forceinline__ U4 walker_bits(uint64_t seed, uint32_t w, uint32_t st
     return philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
 }
 
+// the float64 sum over a wave's 64 lanes, in every lane (a butterfly: one fixed order)
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
 // ---- ensemble slice sampling: the rules of one half step, each written ONCE below with a WAVE per walker -- the set-up
 // (slice_setup_wave), stepping out (slice_expand_wave), trial placement (slice_draw_wave), judging a round's trials
 // (slice_judge_wave) and the commit (slice_commit_wave).  Every slice logic kernel of pointwise.hip is a thin wrapper of them:
@@ -254,6 +261,19 @@ int caught_exception(const char* what) noexcept;      // sets the text, returns 
 #define LINNA_CATCH_SIZE \
     catch (const std::exception& e_) { (void)::linna::caught_exception(e_.what()); return 0; } \
     catch (...) { (void)::linna::caught_exception(nullptr); return 0; }
+// What the files that hold extern "C" entries share (api.hip, comm.hip and a subsystem's own file -- hmc.hip, autocorr.hip,
+// chain_rank.hip: its kernels, its launch code and its entries)
+inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
+inline dim3 grid1d(size_t n, int block) { return dim3((unsigned)((n + block - 1) / block)); }
+#define TRY(expr) do { int rc__ = (expr); if (rc__ != LINNA_OK) return rc__; } while (0)
+#define LAUNCH_CHECK(name) return check_hip(hipGetLastError(), name)
+// a descriptor struct filled against another layout of include/linna_hip.h is refused, not read at wrong offsets
+#define CHECK_STRUCT(ptr, T, who) do { if ((ptr)->struct_size != sizeof(T)) { \
+        set_error("%s: " #T "::struct_size is %u, this library's sizeof is %zu -- set it to sizeof(" #T ") of the header you built against; " \
+                  "a mismatch means that header is not this library's (LINNA_ABI_VERSION %d)", who, (unsigned)(ptr)->struct_size, sizeof(T), LINNA_ABI_VERSION); \
+        return LINNA_ERR_INVALID; } } while (0)
+// the (parameters, padded walkers) shape every chain-statistics entry demands of the transposed chain CT
+inline bool ac_shape_ok(int ndim, int nwp) { return ndim >= 1 && nwp >= 64 && (nwp & 63) == 0; }
 
 // Operand storage seen by the GEMM: LAY_K = contraction index contiguous
 // (A as [M][K], B as [N][K]); LAY_MN = k-major (A as [K][M], B as [K][N]).
@@ -300,43 +320,10 @@ int launch_stretch_propose(const float* coords, int ldc, int ndim, const int* S,
 int launch_stretch_accept(float* coords, int ldc, int ndim, float* logp, const int* S, int ns, const float* Q, int ldq,
                           const float* lp_new, const float* factors, uint64_t seed, const int* step_dev, int stream_id,
                           int* naccept, hipStream_t s);
-// eps (nullable, here and below): a step size per chain in device memory, ek / ed then multiply it; step_off: added to step_dev[0].
-// G == nullptr (X, Q then unused): only the momenta and H0, what linna_hmc_init asks for
-int launch_hmc_start(int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, const float* lnp, const float* P0,
-                     int ldp0, const float* G, int ldg, float ek, float ed, const float* X, int ldx, float* P, int ldp, float* Q,
-                     int ldq, float* H0, hipStream_t s, const float* eps = nullptr, int step_off = 0);
+// hmc.hip: the leapfrog's kick and drift as a launch of its own, P += ek G; Q += ed P / mass -- what the layered gradient route
+// of api.hip enqueues behind its last launch.  eps (nullable): a step size per chain in device memory, ek / ed then multiply it
 int launch_hmc_kick_drift(int B, int ndim, const float* mass, float ek, float ed, const float* G, int ldg, float* P,
                           int ldp, float* Q, int ldq, hipStream_t s, const float* eps = nullptr);
-// the dual-averaging state of hmc_accept_kernel, one entry per chain (sampler.py:198-240 of the reference)
-struct HmcAdapt { float* eps; float* epsbar; float* Hbar; const float* mu; int* m; int Madapt; float delta; };
-// the energy diagnostics of hmc_accept_kernel (linna_hip.h, linna_hmc_accept_energy): estate[B][LINNA_HMC_ENERGY_DOUBLES] with
-// ndiv[B] (both or neither), energy[B] and dH[B] each nullable; HmcEnergy{}: the kernel does what it did before the group
-struct HmcEnergy { double* estate; int* ndiv; float max_dH; float* energy; float* dH; };
-// the one Metropolis launcher: alpha, chain, logps, ad.m and en's pointers are each nullable (linna_hmc_accept passes all of them null)
-int launch_hmc_accept(int B, int ndim, const float* mass, uint64_t seed, const int* step_dev, int step_off, const float* H0,
-                      const float* P, int ldp, const float* Qn, int ldq, const float* lnp_new, const float* Gn, int ldg,
-                      const float* U, float* X, int ldx, float* lnp, float* G, int* naccept, float* alpha,
-                      const HmcAdapt& ad, float* chain, float* logps, const HmcEnergy& en, hipStream_t s);
-// bfmi[B] = D2 / M2 of the accumulators, pooled = {min E-BFMI, sum ndiv, chains with a divergence} (float64)
-int launch_hmc_energy_finish(int B, const double* estate, const int* ndiv, float* bfmi, double* pooled, hipStream_t s);
-int launch_hmc_find_eps_init(int B, int ndim, uint64_t seed, const int* step_dev, int step_off, float* R0, int ldr, float* eps,
-                             int* state, hipStream_t s);
-int launch_hmc_find_eps(int B, int ndim, const float* mass, const float* H0, const float* P, int ldp, const float* lnp_new,
-                        const float* Gn, int ldg, float* eps, int* state, int* nactive, hipStream_t s);
-// running moments of the chain positions, mom = {n, mean[ndim], M2[ndim]} (float64), and the diagonal mass they give
-int launch_hmc_moments(int B, int ndim, const float* X, int ldx, double* mom, hipStream_t s);
-int launch_hmc_mass_from_moments(int ndim, double* mom, float* mass, int reset, hipStream_t s);
-// a dense mass (ndim <= LINNA_HMC_DENSE_MAX_NDIM): shifted co-moments of the positions, the Cholesky factor {C, C^T} of their
-// shrunk covariance, and the leapfrog's kick and drift in the whitened momentum (eps nullable: a step size per chain)
-int launch_hmc_comoments(int B, int ndim, const float* X, int ldx, double* mom, hipStream_t s);
-int launch_hmc_chol_from_comoments(int ndim, double* mom, float* Cm, int ldc, int* info, int reset, hipStream_t s);
-int launch_hmc_kick_drift_dense(int B, int ndim, const float* Cm, int ldc, const float* eps, float ek, float ed, const float* G,
-                                int ldg, float* W, int ldw, const float* X, int ldx, float* Q, int ldq, hipStream_t s);
-// the trajectory length adapted across the chains (ChEES): state = {LINNA_HMC_CHEES_HEAD words, m0[ndim], m1[ndim]} (float64)
-int launch_hmc_chees_begin(int B, int ndim, const float* X, int ldx, double* state, double* r0, hipStream_t s);
-int launch_hmc_chees_end(int B, int ndim, const float* mass, const float* Cm, int ldc, const float* Q, int ldq, const float* P, int ldp,
-                         const float* alpha, const double* r0, double* state, float* eps, int M, double delta, int max_steps,
-                         hipStream_t s);
 int launch_slice_points(const float* coords, int ldc, int ndim, const int* S, int ns, const float* DIR, int ldd,
                         const float* w, float* Q, int ldq, int nrep, hipStream_t s);
 int launch_slice_expand(const float* Z0, const float* ZL, const float* ZR, float* L, float* R, int* flags, int ns,
@@ -472,6 +459,13 @@ int launch_net_stream_train_bwd(const NsNet& net, const float* packed, const NsB
 // launch's own input rows (P == nullptr: none rides); eps (nullable): a step size per row, ek and ed are then its multipliers
 struct NsLeap { float* P; int ldp; float* Q; const float* mass; float ek, ed; const float* eps; };
 struct NsGrad { const float* gscale; float* G; int ldg; NsLeap leap; };
+// ALL that hmc.hip's whole-transition driver sees of a log-probability object (api.hip; struct linna_logprob stays private to
+// it): its input width; LINNA_OK where a gradient route exists, else the refusal with its text; and lnP[B] with G = d lnP / d z
+// at Z enqueued on `stream`, with `leap` (nullable) the leapfrog's kick and drift behind it -- linna_logprob_grad's checks
+int logprob_nin(const linna_logprob_t* lp);
+int logprob_grad_ready(const linna_logprob_t* lp);
+int logprob_grad_impl(linna_logprob_t* lp, const float* Z, int ldz, int B, void* ws, float* lnP, float* G, int ldg,
+                      const NsLeap* leap, void* stream);
 // AdamW that also writes the two weight streams of a training step (net_stream.hip: adamw_streams_kernel; gemm.hip: the
 // update epilogue of the grouped parameter-gradient launch).  An AsPlace says where the elements of a weight matrix sit
 // in one fragment-order stream (segment type 0 = WIDE, 1 = SPLIT; see net_stream.hip).
@@ -527,32 +521,6 @@ bool net_stream_takes_plain(NsKind kind, const NsNet& net, const NsOutput& out, 
                             const NsDense* dn);   // what launch_net_stream decides
 int launch_net_stream(NsKind kind, const NsNet& net, const float* packed, const NsRun& r, const NsInput& in, const NsOutput& out,
                       const NsMove* mv, const NsGrad* gr, int rows, const NsDense* dn, hipStream_t s);
-
-// autocorr.hip: convergence statistics of a walker chain (running lagged products, emcee's estimator, checkmeanstd's moments)
-int launch_chain_append_t(const float* block, int ldb, int nsteps, int nw, int ndim, int wstride, float* CT, int nwp,
-                          int64_t row0, hipStream_t s);
-int launch_acorr_update(const float* CT, int nd, int nwp, int nwc, int64_t a0, int64_t a1, int64_t lo, int64_t hi, int k0, int k1,
-                        double* S, double* T, int remove, hipStream_t s);
-size_t acorr_scratch_doubles(int nser, int kuse, int nd);
-int launch_acorr_tau(const float* CT, int ndim, int nwp, int nwc, int nlive, int64_t lo, int64_t hi, int kuse, const double* S,
-                     const double* T, double c, double* scratch, double* out, hipStream_t s);
-int launch_chain_meanstd(const float* CT, int ndim, int nwp, int nws, int64_t t0, int64_t tm, int64_t t1, double* out,
-                         hipStream_t s);
-// split-R-hat from block moments and the multi-chain ESS from the running sums
-int launch_chain_block_moments(const float* CT, int ndim, int nwp, int64_t b0, int64_t b1, double* M, hipStream_t s);
-int launch_chain_rhat(const float* CT, int ndim, int nwp, int nw, int64_t lo, int64_t hi, const double* M, int64_t nblocks,
-                      double* out, hipStream_t s);
-// chain_rank.hip: rank-normalised, folded split-R-hat (a radix sort of the pooled values per parameter)
-size_t chain_rank_rhat_scratch_bytes(int nw, int64_t rows, int npar);
-int launch_chain_rank_rhat(const float* CT, int ndim, int nwp, int nw, int64_t lo, int64_t hi, void* scratch, size_t scratch_bytes,
-                           uint32_t* rank2_out, double* out, hipStream_t s);
-// rank-normalised bulk-ESS and tail-ESS: one sort, the scores image, autocorr.hip's lagged products and Geyer finish on it
-size_t chain_rank_ess_scratch_bytes(int nw, int64_t rows, int kuse, int npar);
-int launch_chain_rank_ess(const float* CT, int ndim, int nwp, int nw, int64_t lo, int64_t hi, int kuse, void* scratch,
-                          size_t scratch_bytes, double* out, hipStream_t s);
-size_t acorr_ess_scratch_doubles(int nser, int kuse, int nd);
-int launch_acorr_ess(const float* CT, int ndim, int nwp, int nwc, int nlive, int64_t lo, int64_t hi, int kuse, const double* S,
-                     const double* T, double* scratch, double* out, hipStream_t s);
 
 int gemm_slots(int M, int N);            // number of row-dot partial slots gemm_launch will write
 int gemm_launch(const GemmArgs& a, hipStream_t stream);

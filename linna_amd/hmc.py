@@ -21,7 +21,7 @@ class BatchedHMC(object):
     force costs acceptance rate only.  A ``precision="bf16"`` object without the second opt-in raises here.
 
     ``step`` / ``sample`` take one scalar step size and enqueue a transition launch by launch.  ``run`` enqueues a block of
-    transitions in one C call with a step size per chain (``self.eps``, device), which ``find_reasonable_epsilon`` chooses
+    transitions in one C call (always linna_hmc_run_energy: whatever is off is a null pointer) with a step size per chain (``self.eps``, device), which ``find_reasonable_epsilon`` chooses
     and ``run(..., Madapt=n)`` adapts by dual averaging (``self.epsbar``, ``Hbar``, ``mu``, ``m``): what ``HMCSampler.sample(
     method="hmc")`` drives.  Both routes share one Philox sequence (``iteration``).  ``adapt`` is the whole warm-up, with
     the diagonal mass adapted from the positions of all chains on request (``mass_windows``, ``run(moments=True)``,
@@ -31,7 +31,7 @@ class BatchedHMC(object):
     object in dense mode: with C = chol(M^-1) the chains carry the whitened momentum w = C^T p -- the draw is w ~ N(0, I), the
     kinetic energy |w|^2 / 2, the kick w += eps C^T g and the drift q += eps C w -- so ``self.mass`` is an array of ones,
     ``self.chol`` the device pair {C, C^T} ``[2][ndim][ld]``, and every route (``step``, ``run``, ``find_reasonable_epsilon``,
-    ``run(moments=True)`` with the co-moments in ``self.comom``) enqueues the dense launches (linna_hmc_run_dense).
+    ``run(moments=True)`` with the co-moments in ``self.comom``) enqueues the dense launches (those of linna_hmc_run_dense).
 
     ``adapt_traj`` (or ``adapt(adapt_traj=True)``) gives all chains one step size and a trajectory length ``self.traj`` learned
     during a warm-up of its own (ChEES-HMC, linna_hmc_chees_begin / linna_hmc_chees_end); ``run()`` without ``num_steps`` then
@@ -161,19 +161,19 @@ class BatchedHMC(object):
 
     def run(self, ntrans, num_steps=None, store=True, Madapt=0, target_accept=0.65, moments=False, energy=False):
         """``ntrans`` transitions of ``num_steps`` leapfrog steps with the per-chain step sizes ``self.eps``, enqueued by ONE C
-        call (linna_hmc_run: 2 + num_steps launches per transition, the chain rows written by the Metropolis launch); returns
+        call (``_enqueue``: 2 + num_steps launches per transition, the chain rows written by the Metropolis launch); returns
         (chain[ntrans, B, ndim], lnp[ntrans, B]) as device tensors, (None, None) without ``store``.  Bit for bit a loop of
         ``step()`` at that step size.  ``Madapt`` > 0: every chain whose transition count ``self.m`` is <= Madapt adapts its
         step size by dual averaging towards the acceptance ``target_accept`` and freezes it at the averaged one on transition
         Madapt + 1 (the count carries over from call to call).  ``moments``: one more launch per transition merges the B
-        positions behind it into ``self.mom`` = {n, mean[ndim], M2[ndim]} (device float64, linna_hmc_run_moments); the
-        chains are bit for bit the same.
+        positions behind it into ``self.mom`` = {n, mean[ndim], M2[ndim]} (device float64; what linna_hmc_run_moments adds
+        to linna_hmc_run); the chains are bit for bit the same.
 
         Without ``num_steps`` and with a trajectory length in place (``adapt_traj`` / ``set_traj``): one C call per
         transition, the one at Philox step i with ``steps_for(i)`` leapfrog steps, into the rows of the same block --
         bit for bit a loop of ``run(1, num_steps=steps_for(i))``.  An explicit ``num_steps`` means what it always did.
 
-        With ``energy_stats()`` on, every route above goes through linna_hmc_run_energy and the transitions are counted.
+        With ``energy_stats()`` on, the transitions of every route above are counted.
         ``energy``: returns (chain, lnp, E[ntrans, B], dH[ntrans, B]) -- the energy of the state every transition ended in and
         its energy error H1 - H0, device float32 (with the statistics off too)."""
         by_length = num_steps is None and self.traj is not None
@@ -191,25 +191,18 @@ class BatchedHMC(object):
 
     def _enqueue(self, ntrans, num_steps, chain, lps, Madapt, target_accept, moments, rows=None):
         """run()'s one C call: ``ntrans`` transitions of ``num_steps`` leapfrog steps, their rows to ``chain`` / ``lps`` (and
-        ``rows`` = (E, dH)); through linna_hmc_run_energy when ``rows`` are asked for or the energy statistics count."""
+        ``rows`` = (E, dH)).  Always linna_hmc_run_energy: what is off -- a dense factor, the moments, the energy statistics,
+        the rows -- is a null pointer, and the call is then bit for bit linna_hmc_run / _run_moments / _run_dense."""
         h, ws = self.lp._ensure()["handle"], _lib.ptr(self.lp._workspace(self.B, True))
-        args = (_lib.ptr(self.eps), _lib.ptr(self.epsbar), _lib.ptr(self.Hbar),
-                _lib.ptr(self.mu), _lib.iptr(self.m), int(Madapt), float(target_accept), self.iteration - self._dev_steps,
-                int(num_steps), int(ntrans), _lib.iptr(self.naccept), _lib.ptr(self.alpha), _lib.ptr(chain), _lib.ptr(lps))
         count = self.estate is not None and not self._warm
-        if count or rows is not None:
-            mom = None if not moments else _lib.ptr(self._moments() if self.chol is None else self._comoments(), torch.float64)
-            E, dH = rows if rows is not None else (None, None)
-            _lib.call("linna_hmc_run_energy", h, self._hmc_state(), ws, _lib.ptr(self.chol), self.ld if self.chol is not None else 0,
-                      *args, mom, _lib.ptr(self.estate, torch.float64) if count else None, _lib.iptr(self.ndiv) if count else None,
-                      float(self.max_dH), _lib.ptr(E), _lib.ptr(dH), _lib.stream())
-        elif self.chol is not None:
-            _lib.call("linna_hmc_run_dense", h, self._hmc_state(), ws, _lib.ptr(self.chol), self.ld, *args,
-                      _lib.ptr(self._comoments(), torch.float64) if moments else None, _lib.stream())
-        elif moments:
-            _lib.call("linna_hmc_run_moments", h, self._hmc_state(), ws, *args, _lib.ptr(self._moments(), torch.float64), _lib.stream())
-        else:
-            _lib.call("linna_hmc_run", h, self._hmc_state(), ws, *args, _lib.stream())
+        mom = None if not moments else _lib.ptr(self._moments() if self.chol is None else self._comoments(), torch.float64)
+        E, dH = rows if rows is not None else (None, None)
+        _lib.call("linna_hmc_run_energy", h, self._hmc_state(), ws, _lib.ptr(self.chol), self.ld if self.chol is not None else 0,
+                  _lib.ptr(self.eps), _lib.ptr(self.epsbar), _lib.ptr(self.Hbar), _lib.ptr(self.mu), _lib.iptr(self.m), int(Madapt),
+                  float(target_accept), self.iteration - self._dev_steps, int(num_steps), int(ntrans), _lib.iptr(self.naccept),
+                  _lib.ptr(self.alpha), _lib.ptr(chain), _lib.ptr(lps), mom,
+                  _lib.ptr(self.estate, torch.float64) if count else None, _lib.iptr(self.ndiv) if count else None,
+                  float(self.max_dH), _lib.ptr(E), _lib.ptr(dH), _lib.stream())
         self.iteration += ntrans
 
     def energy_stats(self, on=True, max_dH=1000.0):

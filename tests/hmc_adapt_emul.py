@@ -1,4 +1,4 @@
-"""numpy restatement of the per-chain step size HMC of csrc/pointwise.hip, shared by tests/test_hmc_adapt_host.py and
+"""numpy restatement of the per-chain step size HMC of csrc/hmc.hip, shared by tests/test_hmc_adapt_host.py and
 tests/test_gpu_hmc_adapt.py (not a test module).
 
 * ``transition``: one transition of every chain with a step size per chain -- ``oracle.sampling.hmc_batched_step`` with

@@ -1,5 +1,5 @@
 """numpy restatement of the trajectory-length adaptation of ``method="hmc"`` (ChEES-HMC, Hoffman, Radul & Sountsov 2021:
-hmc_chees_begin_kernel and hmc_chees_end_kernel of csrc/pointwise.hip, ``BatchedHMC.adapt_traj``), in float64 on the kernels'
+hmc_chees_begin_kernel and hmc_chees_end_kernel of csrc/hmc.hip, ``BatchedHMC.adapt_traj``), in float64 on the kernels'
 own Philox draws, on top of tests/hmc_adapt_emul.py and tests/hmc_dense_emul.py; shared by tests/test_hmc_chees_host.py and
 tests/test_gpu_hmc_chees.py (not a test module).
 

@@ -1,5 +1,5 @@
 """numpy restatement of the dense mass of ``method="hmc"`` (hmc_comoments_kernel, hmc_chol_from_comoments_kernel and
-hmc_kick_drift_dense_kernel of csrc/pointwise.hip, ``BatchedHMC.adapt(adapt_mass="dense")``), on top of
+hmc_kick_drift_dense_kernel of csrc/hmc.hip, ``BatchedHMC.adapt(adapt_mass="dense")``), on top of
 tests/hmc_adapt_emul.py and tests/hmc_mass_emul.py; shared by tests/test_hmc_dense_host.py and tests/test_gpu_hmc_dense.py
 (not a test module).
 

@@ -1,4 +1,4 @@
-"""numpy restatement of the energy diagnostics of csrc/pointwise.hip (hmc_accept_kernel's HmcEnergy group and
+"""numpy restatement of the energy diagnostics of csrc/hmc.hip (hmc_accept_kernel's HmcEnergy group and
 hmc_energy_finish_kernel), shared by tests/test_hmc_energy_host.py and tests/test_gpu_hmc_energy.py (not a test module).
 
 * ``accept``: one Metropolis launch in float32 -- H1, the test on given uniforms, and behind it E = acc ? H1 : H0, the energy

@@ -1,5 +1,5 @@
 """numpy restatement of the diagonal mass adaptation of ``method="hmc"`` (``BatchedHMC.adapt``, hmc_moments_kernel and
-hmc_mass_from_moments_kernel of csrc/pointwise.hip), on top of tests/hmc_adapt_emul.py; shared by
+hmc_mass_from_moments_kernel of csrc/hmc.hip), on top of tests/hmc_adapt_emul.py; shared by
 tests/test_hmc_mass_host.py and tests/test_gpu_hmc_mass.py (not a test module).
 
 * ``mass_windows``: Stan's schedule of "slow" windows, ``BatchedHMC.mass_windows``.

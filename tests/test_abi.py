@@ -6,6 +6,8 @@ import re
 
 import pytest
 
+import csrc_text
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "linna_hip.h")
 
@@ -236,9 +238,8 @@ def test_no_cpp_exception_crosses_the_c_boundary():
 
 def test_every_entry_definition_is_a_function_try_block():
     """Source-level: each function the header declares (bar the two that cannot throw: version, error text) is defined
-    as `... ) try {` and closed by LINNA_CATCH_INT / LINNA_CATCH_SIZE in api.hip / comm.hip."""
-    csrc = os.path.join(ROOT, "linna_amd", "csrc")
-    src = open(os.path.join(csrc, "api.hip")).read() + open(os.path.join(csrc, "comm.hip")).read()
+    as `... ) try {` and closed by LINNA_CATCH_INT / LINNA_CATCH_SIZE in the file of csrc/ that holds it."""
+    src = csrc_text.hip_sources()
     guarded = set()
     for m in re.finditer(r"^(?:int|size_t) (linna_\w+)\(([^{;]*)\) try \{", src, flags=re.M):
         guarded.add(m.group(1))

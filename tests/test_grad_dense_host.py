@@ -9,6 +9,7 @@ import re
 import pytest
 
 import codeobj
+import csrc_text
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "linna_hip.h")
@@ -145,7 +146,7 @@ def test_entries_header_and_binding():
     from linna_amd import _lib, util
     lib = _lib.load()
     src = open(HEADER).read()
-    api = open(os.path.join(ROOT, "linna_amd", "csrc", "api.hip")).read()
+    api = csrc_text.hip_sources()
     assert re.search(r"int linna_logprob_set_dense_grad\(linna_logprob_t\* lp, int on\);", src)
     assert re.search(r"int linna_logprob_dense_grad\(const linna_logprob_t\* lp, int\* out\);", src)
     assert re.search(r"int linna_program_describe_grad_dense\(const linna_layer_t\* layers, int nlayers, int in_size, int nout, int tri, int rows,", src)

@@ -8,6 +8,7 @@ import re
 import pytest
 
 import codeobj
+import csrc_text
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "linna_hip.h")
@@ -103,7 +104,7 @@ def test_entry_header_and_binding():
     assert re.search(r"int linna_logprob_grad_launches\(linna_logprob_t\* lp, int B, int\* out\);", src)
     assert hasattr(lib, "linna_logprob_grad_launches") and "linna_logprob_grad_launches" in _lib.EXPORTED
     assert re.search(r"#define LINNA_ABI_VERSION 12\b", src) and lib.linna_abi_version() == 12
-    api = open(os.path.join(ROOT, "linna_amd", "csrc", "api.hip")).read()
+    api = csrc_text.hip_sources()
     assert re.search(r"int linna_logprob_grad_launches\(linna_logprob_t\* lp, int B, int\* out\) try \{", api)
     # bad arguments are refused on the host, with a text, and leave *out alone
     out = ctypes.c_int(7)

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import chain_exact as ce
+import csrc_text
 import rank_ess_emul as emul
 import rhat_emul
 
@@ -137,7 +138,7 @@ def test_quantile_positions_are_integers(S1):
 def test_the_entries_are_declared_guarded_and_bound():
     from linna_amd import _lib, sampler
     header = open(os.path.join(ROOT, "include", "linna_hip.h")).read()
-    api = open(os.path.join(ROOT, "linna_amd", "csrc", "api.hip")).read()
+    api = csrc_text.hip_sources()
     for name, nargs in (("linna_chain_rank_ess_scratch_bytes", 5), ("linna_chain_rank_ess", 12)):
         assert re.search(r"\b%s\s*\(" % name, header)
         assert re.search(r"^(?:int|size_t) %s\(([^{;]*)\) try \{" % name, api, flags=re.M), name

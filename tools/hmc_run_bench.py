@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""HMC transitions per second: ``BatchedHMC.run`` (linna_hmc_run: one C call per block of transitions, the step sizes in a device
-array) against a loop of ``BatchedHMC.step`` (3 + num_steps ctypes calls per transition, the step size a scalar), at 128 and
+"""HMC transitions per second: ``BatchedHMC.run`` (linna_hmc_run_energy with everything optional null, which is linna_hmc_run:
+one C call per block of transitions, the step sizes in a device array) against a loop of ``BatchedHMC.step`` (3 + num_steps ctypes calls per transition, the step size a scalar), at 128 and
 4096 chains, on ChtoModelv2(33,33) and the 4x512 MLP (bench.py's problem), fp32 and bf16 gradient engine, 5 leapfrog steps.
 Host clock around work that ends in a device synchronise (the host's share is what differs), the two routes alternating
 in one process, `--repeats` timed windows each; median and spread.  Prints ONE JSON line.
@@ -12,10 +12,10 @@ in one process, `--repeats` timed windows each; median and spread.  Prints ONE J
         each in a fresh process (LINNA_LIB_PATH), `--rounds` of both; prints the medians and ratios.  With `--scalar-only`
         the children time the step() loop alone (a library older than linna_hmc_run); `--this THIRD_LIB.so` puts a third
         build in this tree's place (two copies of one build against each other: the spread of the comparison itself)
-  python tools/hmc_run_bench.py --moments              ``run(moments=True)`` (linna_hmc_run_moments: one launch more per transition,
+  python tools/hmc_run_bench.py --moments              ``run(moments=True)`` (linna_hmc_run_moments' launches: one more per transition,
         the positions of all chains merged into running float64 moments -- what the mass adaptation's windows enqueue) against
         ``run()``, alternating in one process, ChtoModelv2(33,33) only; prints both rates and their ratio
-  python tools/hmc_run_bench.py --dense                ``run()`` under a dense mass with C = I (linna_hmc_run_dense: the kick and the
+  python tools/hmc_run_bench.py --dense                ``run()`` under a dense mass with C = I (linna_hmc_run_dense's launches: the kick and the
         drift as a launch of their own behind every gradient launch, 2 + num_steps launches more per transition) against
         ``run()`` at unit mass -- the same chains --, with and without the (co-)moments launch, alternating in one process,
         ChtoModelv2(33,33) only; and the duration of one linna_hmc_chol_from_comoments launch at 33 and 128 parameters
